@@ -15,8 +15,13 @@ sharded over the ranks (one process per GPU, one engine replica each, no data-pa
   python bench.py --gpus 8 --mode strong           global batch fixed at 32 -> 4 images per GPU
   python bench.py --config retinaface_r50 --gpus 8 C4: RetinaFace-R50 1280x1280, global batch 8, image-sharded (1 per GPU at N=8)
   python bench.py --config resnet50 | rcnn_r50c4   C2 / C5 lines (conv backbone only / full plugin chain)
+  python bench.py --full                           + every side measurement (below)
+  python bench.py --dump-outputs DIR               + what the last timed step returned, as DIR/<name>.npy
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus `roofline`, `cpu_baseline` (+ `parity`, C3 at N=1).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ONE leg of exactly --steps steps and prints the driver contract fields
+(`value`, `ms_per_step`, ...).  --full adds what the line carried before: `value` as the median of --repeats legs (default 7), the
+single-context / D2H-inclusive / host-fed legs, the fp32 `tolerance_engine`, `roofline` (serialized per-kernel profile passes),
+`cpu_baseline` and `parity` (C3 at N=1).
 """
 import argparse
 import ctypes
@@ -39,6 +44,7 @@ MFMA_PEAK_TFLOPS = 2500.0        # MI355X dense fp16/bf16 MFMA peak (MI355X_MICR
 MFMA_F32_PEAK_TFLOPS = 157.3     # v_mfma_f32_16x16x4_f32 / 32x32x2_f32: fp32 operands, exact fp32 (MI355X_MICROARCH.md) - the fp32 engine's convolutions
 HBM_PEAK_GBPS = 8000.0           # MI355X HBM3E peak (MI355X_MICROARCH.md; ~6.3 TB/s is what a streaming copy reaches)
 N_INPUT_SETS = 8                 # rotating input batches: a step never re-reads the batch the previous step left in the caches
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 
 # model -> (BASELINE config, per-GPU batch at weak scaling, H, W, input scale, global batch of the "strong" partition)
 CONFIGS = {
@@ -269,6 +275,46 @@ def cpu_baseline_and_parity_other(config, path, H, W, sample, gpu_out, seconds_b
     return base, par
 
 
+def _decode_records(buf, rec):
+    """a decode buffer [B, 1 + cap * rec]: per image a count, then records of `rec` floats.  The records past the count are whatever an
+    earlier step left in that buffer, so they are zeroed: two runs on the same inputs then return the same array."""
+    import numpy as np
+    buf = np.array(buf, dtype=np.float32).reshape(buf.shape[0], -1)
+    cap = (buf.shape[1] - 1) // rec
+    for b in range(buf.shape[0]):
+        n = int(min(max(buf[b, 0], 0), cap))
+        buf[b, 1 + n * rec:] = 0.0
+    return buf
+
+
+def _nms_arrays(keep_cnt, keep_idx, keep_det):
+    """the GPU NMS results as the caller reads them: per image the kept count, then that many slot indices / [x1 y1 x2 y2 conf class] rows;
+    the entries past the count are stale and are set to -1 / 0"""
+    import numpy as np
+    cnt = np.asarray(keep_cnt).astype(np.int64).clip(0, keep_idx.shape[1])
+    idx = np.asarray(keep_idx).astype(np.float64)
+    det = np.array(keep_det, dtype=np.float32)
+    for b, n in enumerate(cnt):
+        idx[b, n:] = -1.0
+        det[b, n:] = 0.0
+    return {"nms_keep_count": cnt.astype(np.float64), "nms_keep_index": idx, "nms_keep_det": det}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: name -> numpy array (what the timed path returned in its last step) written as out_dir/<name>.npy, float32 (float64 for
+    integer-valued arrays).  At most DUMP_LIMIT_BYTES in all: an array larger than its share of that is replaced by a fixed, seeded sample of
+    its elements (flattened, in index order), so that two runs still write the same thing."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _spawn_self(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks through torch.distributed.run and relay the JSON line."""
     s = socket.socket()
@@ -381,6 +427,10 @@ def run_in_process(args):
     dt = sorted(legs)[len(legs) // 2]
     if not dry:
         tc.set_device(reps.devices[0])
+    if args.dump_outputs:   # device 0's slot of the last timed step
+        last = slots[0][(args.steps - 1) % n_ctx]
+        dump_outputs(args.dump_outputs, dict(output=_decode_records(last.out.cpu().numpy(), 90),
+                                             **_nms_arrays(last.keep_cnt.cpu().numpy(), last.keep_idx.cpu().numpy(), last.keep_det.cpu().numpy())))
     kept = float(slots[0][0].keep_cnt.float().mean().item())
     res = {
         "metric": f"images/sec @ batch={batch} {W}x{H} fp16 (yolov8n conv backbone + YoloLayer decode + NMS)", "value": n_dev * batch * args.steps / dt, "unit": "images/sec",
@@ -415,19 +465,30 @@ def main():
     ap.add_argument("--copy-priority", type=int, default=1, help="host-fed leg: 1 = the upload stream is a high-priority stream (default), 0 = a plain one")
     ap.add_argument("--upload-buffers", type=int, default=0,
                     help="host-fed leg: device frame buffers the uploads rotate through (0 = 2 x contexts + 2)")
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="the W-warm-up + K-step timed leg is run this many times back to back; `value` is the MEDIAN leg (all legs are printed)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the W-warm-up + K-step timed leg is run this many times back to back; `value` is the MEDIAN leg (all legs are printed); "
+                         "default 1, with --full 7")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: 7 legs by default, single-context / D2H / host-fed legs, the fp32 tolerance engine, "
+                         "the per-kernel roofline profile, cpu_baseline and parity")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (engine outputs, and the NMS results where the config runs NMS) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--replicas", default="processes", choices=["processes", "in-process"],
                     help="processes (default, the driver's contract): one rank per GPU; in-process: this one process drives --gpus devices through DeviceReplicas")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline / parity")
     ap.add_argument("--no-pin", action="store_true", help="leave the process's CPU affinity alone (default: the cores of the GPU's NUMA node)")
-    ap.add_argument("--no-tolerance-engine", action="store_true", help="skip the fp32-engine leg (yolov8n fp16 runs print it as `tolerance_engine`)")
+    ap.add_argument("--no-tolerance-engine", action="store_true", help="--full without the fp32-engine leg (yolov8n fp16 runs print it as `tolerance_engine`)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of this script's control flow (ranks over gloo, rank 0 builds and broadcasts the plan, legs / barriers / "
                          "max-over-ranks, JSON assembly) with stand-ins for every GPU object (tensorrtx_amd/dryrun.py); the line is marked dry_run and "
                          "its numbers mean nothing")
     ap.add_argument("--dump-ops", default="", help="write the per-op hipEvent timing table (JSON) to this path")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
+    if args.dump_ops and not args.full:
+        ap.error("--dump-ops writes the per-op table of the --full profile passes: add --full")
 
     if args.replicas == "in-process":
         return run_in_process(args)
@@ -637,7 +698,7 @@ def main():
     # the single-context engine is built (and its tactics timed) BEFORE any timed leg, so that no timed leg is the first GPU work
     # after seconds of host-only set-up
     eng1 = one = None
-    if n_ctx > 1:
+    if n_ctx > 1 and args.full:
         eng1 = make_engine(build_shared(-1))
         one = make_slots(eng1, 1)
     # settle (set-up, untimed, before the W warm-up steps the contract asks for): every slot, stream and input batch has been used
@@ -654,12 +715,53 @@ def main():
     dt, value_legs, value_trace = legs(slots, args.repeats)
     affinity_all = replicas.gather_notes(affinity_note, dist)   # every rank's pinning report (a mis-pinned straggler would otherwise be invisible)
     detections = None
+    last = slots[(args.steps - 1) % n_ctx]   # the slot of the last timed step: nothing has run on it since
     if cfg["nms"]:
         tc.synchronize()
-        last = slots[(args.steps - 1) % n_ctx]
         detections = {"decode_candidates_per_image": float(last.out[:, 0].float().mean().item()),
                       "kept_after_nms_per_image": float(last.keep_cnt.float().mean().item()),
                       "note": "last timed step; seeded random weights: counts are not those of a trained model"}
+    if args.dump_outputs and rank == 0:
+        tc.synchronize()
+        out = {}
+        for i, t in last.outs.items():
+            a = t.cpu().numpy().reshape([batch] + list(last.e.dims[i]))
+            rec = {"output": 90, "prob": 15}.get(last.e.names[i]) if args.config in ("yolov8n", "retinaface_r50") else None
+            out[last.e.names[i]] = _decode_records(a, rec) if rec else a   # yolov8n / RetinaFace: decode buffers (count + records)
+        if cfg["nms"]:
+            out.update(_nms_arrays(last.keep_cnt.cpu().numpy(), last.keep_idx.cpu().numpy(), last.keep_det.cpu().numpy()))
+        dump_outputs(args.dump_outputs, out)
+    res = {
+        "metric": f"images/sec @ batch={cfg['batch']} {W}x{H} {args.precision} ({args.config}" + (" conv backbone + YoloLayer decode + NMS)" if cfg["nms"] else ", IExecutionContext::enqueue)"),
+        "value": (global_batch if mode == "strong" else world * batch) * args.steps / dt, "unit": "images/sec", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": mode,
+        "legs_ms": value_legs,
+        "timing": (f"{len(value_legs)} leg(s) back to back, each = {args.warmup} untimed warm-up steps + exactly {args.steps} timed steps between barrier + "
+                   f"synchronize on both sides (max over ranks); `value` / `ms_per_step` are the MEDIAN leg, `legs_ms` lists all of them "
+                   f"(ms per step); {settle_steps} untimed settle steps ran before the first leg" + ("" if args.full else "; side legs, roofline, cpu_baseline and parity: --full")),
+        "vs_baseline": None, "dtype": "f16" if args.precision == "fp16" else "i8 (+f16 fallback layers)", "data": "synthetic",
+        "config": {"workload": f"{args.config} {args.precision} {W}x{H}, {cfg['tag']}: per-GPU batch {batch}, " +
+                               ("enqueue + GPU NMS" if cfg["nms"] else "enqueue (all plugins inside the engine)") +
+                               (f", {n_ctx} execution contexts in flight (one stream each, setMaxAuxStreams(0)); every step is a full batch-{batch} pass"
+                                if n_ctx > 1 else ", one execution context (3 auxiliary streams), steps strictly in sequence") +
+                               f", {len(inputs)} rotating input batches resident in HBM",
+                   "contexts": n_ctx,
+                   "global_batch": global_batch, "parallelism": f"replica-per-GPU x{world} (image-sharded, no data-path collective; RCCL only brackets the timed region)",
+                   "weights": "seeded synthetic .wts (no trained weights offline)", "cpu_affinity_rank0": affinity_note, "cpu_affinity_per_rank": affinity_all},
+        "per_rank_ms_per_step": value_trace.get("per_rank_ms_per_step_median_leg"),
+    }
+    if not args.full:   # the headline figure alone
+        if detections is not None:
+            res["detections"] = detections
+        if dry:
+            res["dry_run"] = True
+            res["data"] = "NONE: --dry-run rehearses the control flow on CPU; every number in this line is meaningless"
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        eng.close()
+        if dist:
+            dist.destroy_process_group()
+        return
     n_side = max(3, min(args.repeats, 5))
     dt_d2h, d2h_legs, _ = legs(slots, n_side, with_d2h=True) if cfg["nms"] else (None, None, None)
     # the reference's own loop shape for comparison: ONE context, batches strictly one after the other (3 auxiliary streams inside it)
@@ -926,26 +1028,7 @@ def main():
     roofline["frac_serialized_kernels"] = roofline["frac"]
     roofline["frac_whole_step_hbm"] = roofline["whole_step_hbm_view"]["frac"]
     roofline["frac_single_context_hbm"] = (alg_bytes / (single_prof[0] * 1e-3) / 1e9 / HBM_PEAK_GBPS) if single_prof else None
-    res = {
-        "metric": f"images/sec @ batch={cfg['batch']} {W}x{H} {args.precision} ({args.config}" + (" conv backbone + YoloLayer decode + NMS)" if cfg["nms"] else ", IExecutionContext::enqueue)"),
-        "value": (global_batch if mode == "strong" else world * batch) * args.steps / dt, "unit": "images/sec", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": mode,
-        "legs_ms": value_legs,
-        "timing": (f"{len(value_legs)} legs back to back, each = {args.warmup} untimed warm-up steps + exactly {args.steps} timed steps between barrier + "
-                   f"synchronize on both sides (max over ranks); `value` / `ms_per_step` are the MEDIAN leg, `legs_ms` lists all of them "
-                   f"(ms per step); {settle_steps} untimed settle steps ran before the first leg"),
-        "vs_baseline": None, "dtype": "f16" if args.precision == "fp16" else "i8 (+f16 fallback layers)", "data": "synthetic",
-        "config": {"workload": f"{args.config} {args.precision} {W}x{H}, {cfg['tag']}: per-GPU batch {batch}, " +
-                               ("enqueue + GPU NMS" if cfg["nms"] else "enqueue (all plugins inside the engine)") +
-                               (f", {n_ctx} execution contexts in flight (one stream each, setMaxAuxStreams(0)); every step is a full batch-{batch} pass"
-                                if n_ctx > 1 else ", one execution context (3 auxiliary streams), steps strictly in sequence") +
-                               f", {len(inputs)} rotating input batches resident in HBM",
-                   "contexts": n_ctx,
-                   "global_batch": global_batch, "parallelism": f"replica-per-GPU x{world} (image-sharded, no data-path collective; RCCL only brackets the timed region)",
-                   "weights": "seeded synthetic .wts (no trained weights offline)", "cpu_affinity_rank0": affinity_note, "cpu_affinity_per_rank": affinity_all},
-        "per_rank_ms_per_step": value_trace.get("per_rank_ms_per_step_median_leg"),
-        "roofline": roofline,
-    }
+    res["roofline"] = roofline
     if dt_single is not None:
         res["single_context"] = {"value": (global_batch if mode == "strong" else world * batch) * args.steps / dt_single, "unit": "images/sec",
                                  "ms_per_step": dt_single / args.steps * 1e3, "legs_ms": single_legs,

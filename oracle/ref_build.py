@@ -24,7 +24,6 @@ when the directory exists); on the GPU box the prebuilt files are used.  Run dir
 import os
 import re
 import subprocess
-import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -203,6 +202,7 @@ def build_all(verbose=False):
 
 
 if __name__ == "__main__":
-    ok = build_all(verbose=True)
+    build_all(verbose=True)
+    # without the reference (and no prebuilt oracle/_ref) there is nothing to build: a clean checkout still builds, and the tests that run
+    # the reference's own code skip with that reason while the committed goldens keep pinning the oracle
     print("oracle/_ref:", sorted(f for f in os.listdir(OUT) if f.endswith(".so")) if os.path.isdir(OUT) else "absent")
-    sys.exit(0 if ok or os.path.isdir(OUT) else 1)

@@ -3,6 +3,7 @@
 
   host part (CPU, runs anywhere oracle/_ref/libref_host.so exists):
       python tests/golden/make_ref_golden.py host
+      python tests/golden/make_ref_golden.py sweeps      (-> ref_host_sweeps.npz)
   plugin part (needs the MI355X: the reference's CUDA plugins compiled by hipcc run on the GPU):
       gpurun -- python tests/golden/make_ref_golden.py plugins gpurun_out/ref_golden
       cp gpurun_out/ref_golden/ref_plugins.npz tests/golden/
@@ -37,6 +38,20 @@ def host(out_dir):
     print("wrote", len(res), "arrays")
 
 
+def sweeps(out_dir):
+    """the reference's yolov8 NMS on the random sweep of ref_host_cases.yolov8_sweep_cases() and its OBB NMS on the seeded OBB decode
+    buffers of tests/test_gpu_yolo8_branches.py -> ref_host_sweeps.npz"""
+    import ref_host_cases as hc
+    import test_gpu_yolo8_branches as br
+    from oracle import ref
+    res = {f"yolov8_sweep/{t}": ref.yolov8_nms(row[0])[:, :6] for t, row in enumerate(hc.yolov8_sweep_cases())}
+    dec = br.obb_nms_case()
+    for b in range(dec.shape[0]):
+        res[f"yolov8_obb/{b}"] = ref.yolov8_nms_obb(dec[b])
+    np.savez_compressed(os.path.join(out_dir, "ref_host_sweeps.npz"), **res)
+    print("wrote", len(res), "arrays")
+
+
 def plugins(out_dir, only_missing=False):
     """only_missing ("plugins_missing"): keep every array of the committed file and add the cases it does not hold yet"""
     import torch
@@ -60,4 +75,4 @@ def plugins(out_dir, only_missing=False):
 if __name__ == "__main__":
     what = sys.argv[1]
     out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden")
-    {"host": host, "plugins": plugins, "plugins_missing": lambda o: plugins(o, only_missing=True)}[what](out)
+    {"host": host, "sweeps": sweeps, "plugins": plugins, "plugins_missing": lambda o: plugins(o, only_missing=True)}[what](out)

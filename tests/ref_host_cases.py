@@ -78,3 +78,19 @@ def yolov5_cases():
     cases["chain_degenerate"] = rows([[50, 50, 100, 100, 0.9, 3], [90, 50, 100, 100, 0.8, 3], [145, 50, 100, 100, 0.7, 3],
                                       [90, 50, 100, 100, 0.85, 4], [300, 300, 0, 0, 0.95, 3], [300, 300, 0, 0, 0.6, 3]])
     return cases
+
+
+def yolov8_sweep_cases():
+    """40 random one-image decode buffers (clustered boxes, 1-5 classes) for the reference-vs-oracle NMS sweep (tests/test_ref_pinning.py);
+    the reference's results on them are committed as tests/golden/ref_host_sweeps.npz (make_ref_golden.py sweeps)"""
+    rng = np.random.default_rng(7)
+    out = []
+    for trial in range(40):
+        n = int(rng.integers(1, 400))
+        cx, cy = rng.uniform(50, 590, size=(2, 12))
+        k = rng.integers(0, 12, size=n)
+        x = cx[k] + rng.normal(0, 12, n); y = cy[k] + rng.normal(0, 12, n)
+        w, h = rng.uniform(20, 120, size=(2, n))
+        dets = np.stack([x - w / 2, y - h / 2, x + w / 2, y + h / 2, rng.uniform(0.3, 1.0, n), rng.integers(0, 1 + trial % 5, n)], 1)
+        out.append(_yolo_rows(dets.astype(np.float32)))
+    return out

@@ -21,15 +21,17 @@ def _free_port():
     return p
 
 
-def _run(n, extra=()):
+def _run(n, extra=(), full=True):
+    """full: the line with every side measurement (--full, three legs); otherwise the plain run the driver times"""
     env = dict(os.environ, PYTHONPATH=ROOT)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
+    flags = ["--steps", "6", "--warmup", "2"] + (["--repeats", "3", "--full"] if full else []) + list(extra)
     if n == 1:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--gpus", "1", "--steps", "6", "--warmup", "2", "--repeats", "3", *extra]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--gpus", "1", *flags]
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port",
-               str(_free_port()), os.path.join(ROOT, "bench.py"), "--dry-run", "--gpus", str(n), "--steps", "6", "--warmup", "2", "--repeats", "3", *extra]
+               str(_free_port()), os.path.join(ROOT, "bench.py"), "--dry-run", "--gpus", str(n), *flags]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -113,3 +115,61 @@ def test_bench_in_process_replicas_control_flow():
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["dry_run"] is True and d["n_gpus"] == 3 and d["config"]["global_batch"] == 96 and len(d["legs_ms"]) == 3
     assert abs(d["value"] - 96 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_run_times_one_leg_of_exactly_the_steps_and_nothing_else(n):
+    """Without --full the line is the headline figure alone: one leg of exactly --steps timed steps (ms_per_step is that leg's), none of the
+    side legs, the roofline profile, the fp32 engine or the CPU oracle."""
+    d = _run(n, full=False)
+    assert d["dry_run"] is True and d["n_gpus"] == n and d["steps"] == 6 and d["warmup"] == 2
+    assert d["higher_is_better"] is True and d["unit"] == "images/sec" and d["dtype"] == "f16" and d["metric"].startswith("images/sec @ batch=32 640x640 fp16")
+    assert len(d["legs_ms"]) == 1 and d["legs_ms"][0] == round(d["ms_per_step"], 4)
+    assert abs(d["value"] - 32 * n / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "single_context", "d2h_inclusive", "host_fed", "tolerance_engine", "cpu_baseline", "parity"):
+        assert k not in d, k
+
+
+def _dumped(path):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path)) if f.endswith(".npy")}
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_dump_outputs_writes_the_last_steps_results(tmp_path, full):
+    """--dump-outputs DIR: the decode buffer and the NMS results of the last timed step as DIR/<name>.npy, float32 / float64, at most 64 MB,
+    the same from run to run (stale records past each image's count are zeroed)."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    _run(1, ("--dump-outputs", str(a)), full=full)
+    _run(1, ("--dump-outputs", str(b)), full=full)
+    da, db = _dumped(a), _dumped(b)
+    assert sorted(da) == ["nms_keep_count", "nms_keep_det", "nms_keep_index", "output"]
+    assert da["output"].shape == (32, 1 + 1000 * 90) and da["nms_keep_det"].shape == (32, 1000, 6) and da["nms_keep_count"].shape == (32,)
+    assert all(x.dtype in (np.float32, np.float64) for x in da.values())
+    assert sum(x.nbytes for x in da.values()) <= 64 << 20
+    assert all(np.array_equal(da[k], db[k]) for k in da)
+
+
+def test_dump_helpers_canonicalise_and_bound_the_outputs(tmp_path):
+    """the dump's own rules, on made-up arrays: records past a decode count and NMS entries past the kept count are cleared; an output larger
+    than the 64 MB budget is replaced by the same seeded sample every time"""
+    code = r'''
+import sys, os, numpy as np
+import bench
+buf = np.arange(2 * (1 + 3 * 2), dtype=np.float32).reshape(2, 7); buf[0, 0] = 1; buf[1, 0] = 9
+d = bench._decode_records(buf, 2)
+assert d[0, 1:3].tolist() == [1, 2] and not d[0, 3:].any() and d[1, 1:].tolist() == buf[1, 1:].tolist()
+n = bench._nms_arrays(np.array([1, 0], np.int32), np.array([[5, 6], [7, 8]], np.int32), np.ones((2, 2, 6), np.float32))
+assert n["nms_keep_index"].tolist() == [[5, -1], [-1, -1]] and n["nms_keep_det"][0, 0].all() and not n["nms_keep_det"][0, 1:].any()
+assert n["nms_keep_count"].dtype == np.float64 and not n["nms_keep_det"][1].any()
+big = np.arange(10 << 20, dtype=np.float64)   # 80 MB
+for out in sys.argv[1:]:
+    bench.dump_outputs(out, {"big": big, "small": np.arange(4, dtype=np.int32)})
+x, y = (np.load(os.path.join(o, "big.npy")) for o in sys.argv[1:])
+assert x.nbytes <= 32 << 20 and np.array_equal(x, y) and np.all(np.diff(x) > 0)
+assert np.load(os.path.join(sys.argv[1], "small.npy")).dtype == np.float64
+'''
+    r = subprocess.run([sys.executable, "-c", code, str(tmp_path / "a"), str(tmp_path / "b")], cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

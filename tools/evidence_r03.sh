@@ -14,29 +14,29 @@ cd $R
 PART=${1:-all}
 if [ $PART = bench ] || [ $PART = all ]; then
   for i in 1 2 3; do
-    timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $E/bench_c3_driverflags_$i.log 2> $E/bench_c3_driverflags_$i.err
+    timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $E/bench_c3_driverflags_$i.log 2> $E/bench_c3_driverflags_$i.err
   done
-  timeout 300 python bench.py --steps 20 --warmup 5 --contexts 1 --no-cpu-baseline --dump-ops $E/ops_c3_1ctx.json > $E/bench_c3_1ctx.log 2>/dev/null
-  TRTX_TUNE=0 TRTX_TACTIC_CACHE= timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $E/bench_c3_untuned.log 2>/dev/null
-  TRTX_FOLD_UPSAMPLE=0 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $E/bench_c3_nofold.log 2>/dev/null
-  timeout 500 python bench.py --steps 20 --warmup 5 --precision int8 > $E/bench_c3_int8.log 2>/dev/null
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --contexts 1 --no-cpu-baseline --dump-ops $E/ops_c3_1ctx.json > $E/bench_c3_1ctx.log 2>/dev/null
+  TRTX_TUNE=0 TRTX_TACTIC_CACHE= timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $E/bench_c3_untuned.log 2>/dev/null
+  TRTX_FOLD_UPSAMPLE=0 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $E/bench_c3_nofold.log 2>/dev/null
+  timeout 500 python bench.py --full --steps 20 --warmup 5 --precision int8 > $E/bench_c3_int8.log 2>/dev/null
   for cfg in resnet50 retinaface_r50 rcnn_r50c4; do
-    timeout 400 python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline > $E/bench_$cfg.log 2>/dev/null
+    timeout 400 python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline > $E/bench_$cfg.log 2>/dev/null
   done
   python tools/show_bench.py $E/bench_*.log
   timeout 300 python tools/layer_table.py $E/layer_table.json > $E/layer_table.txt 2>&1; tail -5 $E/layer_table.txt
 fi
 if [ $PART = prof ] || [ $PART = all ]; then
-  timeout 300 python bench.py --steps 5 --warmup 2 --repeats 3 --no-cpu-baseline > /dev/null 2>&1            # fills the tactic cache (3 contexts + 1 context engines)
+  timeout 300 python bench.py --full --steps 5 --warmup 2 --repeats 3 --no-cpu-baseline > /dev/null 2>&1            # fills the tactic cache (3 contexts + 1 context engines)
   prof() {  # name, bench args
-    (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $E/prof_$1 -o p -- python $R/bench.py $2 --steps 20 --warmup 5 --no-cpu-baseline > $E/prof_$1.log 2>&1)
-    { echo "# rocprofv3 --kernel-trace --stats -- python bench.py $2 --steps 20 --warmup 5 --no-cpu-baseline   (round 3, final build; TRTX_TACTIC_CACHE set: no tactic-timing launches inside)"; python tools/rocprof_summary.py $E/prof_$1; } > $E/kernel_stats_$1.txt 2>&1
+    (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $E/prof_$1 -o p -- python $R/bench.py --full $2 --steps 20 --warmup 5 --no-cpu-baseline > $E/prof_$1.log 2>&1)
+    { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full $2 --steps 20 --warmup 5 --no-cpu-baseline   (round 3, final build; TRTX_TACTIC_CACHE set: no tactic-timing launches inside)"; python tools/rocprof_summary.py $E/prof_$1; } > $E/kernel_stats_$1.txt 2>&1
     head -9 $E/kernel_stats_$1.txt | cut -c1-170
     rm -rf $E/prof_$1
   }
   prof c3 ""
   TRTX_LANES=1 prof c3_1ctx_lanes1 "--contexts 1"     # no kernels overlap: per-kernel durations comparable with bench.py's serialized profile passes
-  for cfg in resnet50 retinaface_r50 rcnn_r50c4; do timeout 300 python bench.py --config $cfg --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > /dev/null 2>&1; done
+  for cfg in resnet50 retinaface_r50 rcnn_r50c4; do timeout 300 python bench.py --full --config $cfg --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > /dev/null 2>&1; done
   prof c2 "--config resnet50"
   prof c4 "--config retinaface_r50"
   prof c5 "--config rcnn_r50c4"
@@ -45,12 +45,12 @@ if [ $PART = pmc ] || [ $PART = prof ] || [ $PART = all ]; then
   # HBM traffic of the conv launches from the L2 fabric counters, one pass per configuration (its own run: --pmc with --kernel-trace only)
   for cfg in yolov8n resnet50 retinaface_r50 rcnn_r50c4; do
     OUT=$E/pmc_$cfg
-    timeout 300 python bench.py --config $cfg --contexts 1 --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline > /dev/null 2>&1      # tactic cache
-    (cd /tmp && timeout 400 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -d $OUT -o c -- python $R/bench.py --config $cfg --contexts 1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > $OUT.log 2>&1)
+    timeout 300 python bench.py --full --config $cfg --contexts 1 --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline > /dev/null 2>&1      # tactic cache
+    (cd /tmp && timeout 400 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -d $OUT -o c -- python $R/bench.py --full --config $cfg --contexts 1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > $OUT.log 2>&1)
   done
   python - <<PY
 import csv, glob, collections, json
-lines = ["# rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace -- python bench.py --config X --contexts 1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline (round 3, final build)",
+lines = ["# rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace -- python bench.py --full --config X --contexts 1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline (round 3, final build)",
          "# bytes = (2 x RDREQ + WRREQ) x 64 B  (reads doubled: gfx950 counts 128-B read requests at 64 B, MI355X_MICROARCH.md HBM section); per launch, mean over the launches of the run"]
 out = {}
 for cfg in ("yolov8n", "resnet50", "retinaface_r50", "rcnn_r50c4"):

@@ -14,32 +14,32 @@ cd $R
 PART=${1:-all}
 if [ $PART = bench ] || [ $PART = all ]; then
   for i in 1 2; do
-    timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $E/bench_c3_driverflags_$i.log 2> $E/bench_c3_driverflags_$i.err
+    timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $E/bench_c3_driverflags_$i.log 2> $E/bench_c3_driverflags_$i.err
   done
-  timeout 300 python bench.py --steps 20 --warmup 5 --contexts 1 --no-cpu-baseline --no-tolerance-engine --dump-ops $E/ops_c3_1ctx.json > $E/bench_c3_1ctx.log 2>/dev/null
-  timeout 500 python bench.py --steps 20 --warmup 5 --precision int8 > $E/bench_c3_int8.log 2>/dev/null
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --contexts 1 --no-cpu-baseline --no-tolerance-engine --dump-ops $E/ops_c3_1ctx.json > $E/bench_c3_1ctx.log 2>/dev/null
+  timeout 500 python bench.py --full --steps 20 --warmup 5 --precision int8 > $E/bench_c3_int8.log 2>/dev/null
   for cfg in resnet50 retinaface_r50 rcnn_r50c4; do
-    timeout 600 python bench.py --config $cfg --steps 20 --warmup 5 > $E/bench_$cfg.log 2>/dev/null
+    timeout 600 python bench.py --full --config $cfg --steps 20 --warmup 5 > $E/bench_$cfg.log 2>/dev/null
   done
   python tools/show_bench.py $E/bench_*.log
   timeout 300 python tools/layer_table.py $E/layer_table.json > $E/layer_table.txt 2>&1; tail -5 $E/layer_table.txt
   timeout 300 python tools/f32_engine_probe.py > $E/f32_engine_probe.txt 2>&1; grep -v "^   op\|   tactic" $E/f32_engine_probe.txt | tail -6
 fi
 if [ $PART = prof ] || [ $PART = all ]; then
-  timeout 300 python bench.py --steps 5 --warmup 2 --repeats 3 --no-cpu-baseline > /dev/null 2>&1            # fills the tactic cache (3 contexts + 1 context + fp32 engines)
+  timeout 300 python bench.py --full --steps 5 --warmup 2 --repeats 3 --no-cpu-baseline > /dev/null 2>&1            # fills the tactic cache (3 contexts + 1 context + fp32 engines)
   prof() {  # name, command
     (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $E/prof_$1 -o p -- $2 > $E/prof_$1.log 2>&1)
     { echo "# rocprofv3 --kernel-trace --stats -- $2   (round 5, final build; TRTX_TACTIC_CACHE set: no tactic-timing launches inside)"; python tools/rocprof_summary.py $E/prof_$1; } > $E/kernel_stats_$1.txt 2>&1
     head -12 $E/kernel_stats_$1.txt | cut -c1-170
     rm -rf $E/prof_$1
   }
-  prof c3 "python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine"
-  TRTX_LANES=1 prof c3_1ctx_lanes1 "python $R/bench.py --contexts 1 --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine"
+  prof c3 "python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine"
+  TRTX_LANES=1 prof c3_1ctx_lanes1 "python $R/bench.py --full --contexts 1 --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine"
   TRTX_LANES=1 prof c3_fp32_1ctx_lanes1 "python $R/tools/f32_engine_probe.py --contexts 1 --steps 40 --no-oracle"
-  timeout 300 python bench.py --config rcnn_r50c4 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > /dev/null 2>&1
-  TRTX_LANES=1 prof c5_1ctx_lanes1 "python $R/bench.py --config rcnn_r50c4 --contexts 1 --steps 20 --warmup 5 --no-cpu-baseline"
+  timeout 300 python bench.py --full --config rcnn_r50c4 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > /dev/null 2>&1
+  TRTX_LANES=1 prof c5_1ctx_lanes1 "python $R/bench.py --full --config rcnn_r50c4 --contexts 1 --steps 20 --warmup 5 --no-cpu-baseline"
   OUT=$E/pmc_yolov8n
-  (cd /tmp && timeout 400 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -d $OUT -o c -- python $R/bench.py --config yolov8n --contexts 1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline --no-tolerance-engine > $OUT.log 2>&1)
+  (cd /tmp && timeout 400 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -d $OUT -o c -- python $R/bench.py --full --config yolov8n --contexts 1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline --no-tolerance-engine > $OUT.log 2>&1)
   python - <<PY | tee $E/pmc_conv_traffic.txt
 import csv, glob, collections
 fs = glob.glob("$E/pmc_yolov8n/**/c_counter_collection.csv", recursive=True)

@@ -39,7 +39,7 @@ for round in 1 2; do
       patch_groups) export TRTX_HIP_LIB=$L/libtrtx_hip.so TRTX_CONV_PATCH=2; unset TRTX_GROUP_CONVS;;   # ... and the grouped launches whose members all qualify (the head's second 3x3s)
       patch_ungrouped) export TRTX_HIP_LIB=$L/libtrtx_hip.so TRTX_CONV_PATCH=1 TRTX_GROUP_CONVS=0;;
     esac
-    TRTX_TACTIC_CACHE=/tmp/tc_$v.txt timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${v}_$round.json 2> /dev/null
+    TRTX_TACTIC_CACHE=/tmp/tc_$v.txt timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${v}_$round.json 2> /dev/null
   done
 done
 unset TRTX_HIP_LIB TRTX_CONV_PATCH TRTX_GROUP_CONVS

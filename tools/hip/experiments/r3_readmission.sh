@@ -40,7 +40,7 @@ for round in 1 2; do
       r3) export TRTX_HIP_LIB=$L/libtrtx_hip.so TRTX_TACTICS_R3=1; unset TRTX_GROUP_CONVS;;
       r3_ungrouped) export TRTX_HIP_LIB=$L/libtrtx_hip.so TRTX_TACTICS_R3=1 TRTX_GROUP_CONVS=0;;
     esac
-    TRTX_TACTIC_CACHE=/tmp/tc_$v.txt timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${v}_$round.json 2> /dev/null
+    TRTX_TACTIC_CACHE=/tmp/tc_$v.txt timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${v}_$round.json 2> /dev/null
   done
 done
 unset TRTX_HIP_LIB TRTX_TACTICS_R3 TRTX_GROUP_CONVS

@@ -28,7 +28,7 @@ for round in 1 2; do
       patch_groups) export TRTX_HIP_LIB=$LP/libtrtx_hip.so TRTX_CONV_PATCH=2;;
       r3) export TRTX_HIP_LIB=$LR/libtrtx_hip.so TRTX_TACTICS_R3=1;;
     esac
-    TRTX_TACTIC_CACHE=/tmp/tc_$v.txt timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${v}_$round.json 2> $O/bench_${v}_$round.err
+    TRTX_TACTIC_CACHE=/tmp/tc_$v.txt timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${v}_$round.json 2> $O/bench_${v}_$round.err
   done
 done
 unset TRTX_HIP_LIB TRTX_CONV_PATCH TRTX_TACTICS_R3

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 export TMPDIR=/tmp
 O=$R/gpurun_out/${1:-r06_ef32}; mkdir -p $O; cd $R
 for res in 7 0 7 0; do
-  TRTX_CONV_RES=$res timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_res$res.json 2> $O/bench_res$res.err
+  TRTX_CONV_RES=$res timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_res$res.json 2> $O/bench_res$res.err
   python - $O/bench_res$res.json $res <<'P' | tee -a $O/engine_f32.txt
 import json, sys
 for line in open(sys.argv[1]):

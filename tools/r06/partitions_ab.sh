@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 export TMPDIR=/tmp TRTX_TACTIC_CACHE=/tmp/trtx_tactics.txt
 O=$R/gpurun_out/${1:-r06_part}; mkdir -p $O; cd $R
 run() {  # label, bench args
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine $2 > $O/bench_$1.json 2> $O/bench_$1.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine $2 > $O/bench_$1.json 2> $O/bench_$1.err
   python - $O/bench_$1.json "$1" <<'P' | tee -a $O/summary.txt
 import json, sys
 ok = False

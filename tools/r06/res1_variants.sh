@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 export TMPDIR=/tmp
 O=$R/gpurun_out/${1:-r06_res1_var}; mkdir -p $O; cd $R
 run() {  # name, TRTX_CONV_RES, TRTX_CONV_DBG
-  TRTX_CONV_RES=$2 TRTX_CONV_DBG=$3 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine > $O/bench_$1.json 2> $O/bench_$1.err
+  TRTX_CONV_RES=$2 TRTX_CONV_DBG=$3 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine > $O/bench_$1.json 2> $O/bench_$1.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench_$1.json").read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_conv_f32.py -m gpu -q -x 2>&1 | tail
 timeout 600 python tools/conv_f32_shape_ab.py 32 80 80 64 64 3 1  32 40 40 64 64 3 1  32 80 80 32 32 3 1  32 160 160 16 16 3 1  32 80 80 64 80 3 1  32 80 80 80 80 3 1  32 80 80 128 64 1 1  32 80 80 64 64 1 1  32 40 40 256 128 1 1  32 160 160 32 32 1 1  32 80 80 96 64 1 1  32 40 40 192 128 1 1  32 20 20 384 256 1 1  32 80 80 80 80 1 1 2>&1 | grep -E "GFLOP|res3|res1|ptch|bm 128 dma  bk 16|bm  64 dma  bk 16|bm 128 regs|bm 128 role" | tee $O/res_f32_shape_ab.txt
 if [ "${2:-}" = engine ]; then
 for res in 7 0 7 0; do
-  TRTX_CONV_RES=$res timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_res$res.json 2> $O/bench_res$res.err
+  TRTX_CONV_RES=$res timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_res$res.json 2> $O/bench_res$res.err
   python - $O/bench_res$res.json $res <<'P' | tee -a $O/engine_f32.txt
 import json, sys
 for line in open(sys.argv[1]):

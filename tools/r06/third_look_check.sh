@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 export TMPDIR=/tmp TRTX_TUNE_VERBOSE=1
 O=$R/gpurun_out/${1:-r06_tl}; mkdir -p $O; cd $R
 run() {  # label, args
-  timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $2 > $O/bench_$1.json 2> $O/bench_$1.err
+  timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $2 > $O/bench_$1.json 2> $O/bench_$1.err
   grep "three contexts in flight" $O/bench_$1.err | sed "s/^/   $1: /" | tee -a $O/summary.txt
   python - $O/bench_$1.json "$1" <<'P' | tee -a $O/summary.txt
 import json, sys

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 export TMPDIR=/tmp
 O=$R/gpurun_out/${1:-r06_tm}; mkdir -p $O; cd $R
 run() {
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine > $O/bench_$1.json 2>/dev/null
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-tolerance-engine > $O/bench_$1.json 2>/dev/null
   python - $O/bench_$1.json "$1" <<'P' | tee -a $O/summary.txt
 import json, sys
 for line in open(sys.argv[1]):
