@@ -9,6 +9,7 @@ from .capi import check, lib
 from .engine import Dims
 
 P_STRIDE, P_PADDING, P_DILATION, P_GROUPS, P_KERNEL, P_NB_OUT = 1, 2, 3, 4, 15, 16
+TRTX_P_AXIS, TRTX_P_RESHAPE, TRTX_P_FIRST_TRANSPOSE, TRTX_P_SECOND_TRANSPOSE = 7, 8, 9, 10
 ACT = {"relu": 0, "sigmoid": 1, "tanh": 2, "leaky": 3}
 FLAG_FP16, FLAG_INT8 = 0, 1
 
@@ -58,8 +59,8 @@ class Network:
         arr = (ctypes.c_int32 * 2)(v, v) if np.isscalar(v) else (ctypes.c_int32 * 2)(*v)
         check(self.L.trtx_layer_set_ints(self.n, layer, param, arr, 2), "trtx_layer_set_ints")
 
-    def conv(self, x, w, bias=None, stride=1, padding=0, deconv=False):
-        """w: KCRS (conv) or CKRS (deconv) fp32 numpy; returns the layer index"""
+    def conv(self, x, w, bias=None, stride=1, padding=0, deconv=False, groups=1):
+        """w: KCRS (conv, C = input channels / groups) or CKRS (deconv) fp32 numpy; returns the layer index"""
         w = np.ascontiguousarray(w, dtype=np.float32)
         nb_out = w.shape[1] if deconv else w.shape[0]
         wa, wp, wn = _f(w)
@@ -69,6 +70,8 @@ class Network:
         l = self._layer(fn(self.n, x, nb_out, w.shape[2], w.shape[3], wp, ctypes.c_int64(wn), bp, ctypes.c_int64(bn)), "add_conv")
         self._set2(l, P_STRIDE, stride)
         self._set2(l, P_PADDING, padding)
+        if groups != 1:
+            check(self.L.trtx_layer_set_ints(self.n, l, P_GROUPS, (ctypes.c_int32 * 1)(groups), 1), "trtx_layer_set_ints(groups)")
         return l
 
     def activation(self, x, kind):
@@ -120,6 +123,41 @@ class Network:
         c, h, w = chw
         st, sz, sp = _dims((start, 0, 0)), _dims((size, h, w)), _dims((1, 1, 1))
         return self._layer(self.L.trtx_add_slice(self.n, x, ctypes.byref(st), ctypes.byref(sz), ctypes.byref(sp)), "add_slice")
+
+    def slice(self, x, start, size, step=None):
+        """ISliceLayer, any rank"""
+        st, sz, sp = _dims(start), _dims(size), _dims(step if step is not None else (1,) * len(start))
+        return self._layer(self.L.trtx_add_slice(self.n, x, ctypes.byref(st), ctypes.byref(sz), ctypes.byref(sp)), "add_slice")
+
+    def shuffle(self, x, reshape=None, perm1=None, perm2=None):
+        """IShuffleLayer: first transpose, reshape (0 copies, -1 infers), second transpose"""
+        l = self._layer(self.L.trtx_add_shuffle(self.n, x), "add_shuffle")
+        for param, perm in ((TRTX_P_FIRST_TRANSPOSE, perm1), (TRTX_P_SECOND_TRANSPOSE, perm2)):
+            if perm is not None:
+                check(self.L.trtx_layer_set_ints(self.n, l, param, (ctypes.c_int32 * len(perm))(*perm), len(perm)), "trtx_layer_set_ints(transpose)")
+        if reshape is not None:
+            d = _dims(reshape)
+            check(self.L.trtx_layer_set_dims(self.n, l, TRTX_P_RESHAPE, ctypes.byref(d)), "trtx_layer_set_dims(reshape)")
+        return l
+
+    def softmax(self, x, axes=None):
+        """ISoftMaxLayer; axes: bit mask (setAxes), None keeps the default axis"""
+        l = self._layer(self.L.trtx_add_softmax(self.n, x), "add_softmax")
+        if axes is not None:
+            check(self.L.trtx_layer_set_ints(self.n, l, TRTX_P_AXIS, (ctypes.c_int32 * 1)(axes), 1), "trtx_layer_set_ints(axes)")
+        return l
+
+    def matmul(self, a, b, transpose_a=False, transpose_b=False):
+        """IMatrixMultiplyLayer, MatrixOperation kNONE / kTRANSPOSE"""
+        return self._layer(self.L.trtx_add_matrix_multiply(self.n, a, int(transpose_a), b, int(transpose_b)), "add_matrix_multiply")
+
+    def scale_uniform(self, x, scale, shift=0.0):
+        """IScaleLayer, ScaleMode::kUNIFORM (the Attention's score scale, yolo11/src/block.cpp:313-324)"""
+        sa, sp, sn = _f(np.array([shift]))
+        ca, cp, cn = _f(np.array([scale]))
+        pa, pp, pn = _f(np.array([1.0]))
+        self._keep += [sa, ca, pa]
+        return self._layer(self.L.trtx_add_scale(self.n, x, 0, sp, ctypes.c_int64(sn), cp, ctypes.c_int64(cn), pp, ctypes.c_int64(pn)), "add_scale")
 
     def concat(self, tensors):
         arr = (ctypes.c_int32 * len(tensors))(*tensors)

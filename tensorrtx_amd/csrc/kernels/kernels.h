@@ -148,6 +148,14 @@ struct StemFrame {
 int32_t conv_stem_frames_f32(const ConvArgs& a, const StemFrame* frames, hipStream_t s);
 // generic direct convolution (any groups / dilation / channel count), T = activation dtype, fp32 weights
 int32_t conv_direct(const ConvArgs& a, int dtype, hipStream_t s);
+// depthwise convolution (conv_dw.hip): groups == Cin == Cout, k 3 / 5 / 7 with pad k/2, stride 1 / 2, no dilation; weights fp32 [kh*kw][C]
+bool conv_dw_supported(const ConvArgs& a);
+// fused PSA attention (attention.hip): NHWC fp16 qkv [B][N][ld_qkv] (head h: q at h*(2kd+hd), k next, v next) -> O [B][N][ld_out] and the
+// gathered V image [B][N][ld_v], channel h*hd + d; kd == 32, hd == 64
+bool psa_attention_supported(int kd, int hd);
+int32_t psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
+                          float scale, hipStream_t s);
+int32_t conv_dw(const ConvArgs& a, int dtype, hipStream_t s);
 // generic transposed convolution, fp32 weights laid out [Cin][kh][kw][Cout/groups]
 int32_t deconv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 
@@ -201,9 +209,10 @@ int32_t lin_scatter(const float* in, float* out, const StridedView& v, hipStream
 int32_t lin_elementwise(const float* a, const float* b, float* out, int op, const StridedView& v, hipStream_t s);
 int32_t lin_activation(const float* in, float* out, int act, float alpha, long n, hipStream_t s);
 int32_t lin_softmax(const float* in, float* out, long outer, long axis, long inner, hipStream_t s);
-// C[b][m][n] = sum_k A(b,m,k) * B(b,k,n); ta/tb: operand stored transposed; batch stride 0 = broadcast
+// C[b][m][n] = sum_k A(b,m,k) * B(b,k,n); ta/tb: operand stored transposed; batch stride 0 = broadcast.
+// The batch index splits into (b / binner, b % binner), strided by (bsA, bsA2) / (bsB, bsB2): two broadcast patterns
 int32_t lin_matmul(const float* A, const float* B, float* C, int batch, int M, int N, int K, int ta, int tb,
-                   long bsA, long bsB, hipStream_t s);
+                   long bsA, long bsB, hipStream_t s, int binner = 1, long bsA2 = 0, long bsB2 = 0);
 int32_t lin_reduce(const float* in, float* out, int op /*0 sum,1 avg,2 max*/, long outer, long axis, long inner,
                    hipStream_t s);
 int32_t lin_scale(const float* in, float* out, const float* scale, const float* shift, const float* power, int mode,

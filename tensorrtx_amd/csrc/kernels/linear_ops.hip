@@ -112,15 +112,17 @@ __global__ void softmax_kernel(const float* __restrict__ in, float* __restrict__
 }
 
 __global__ void matmul_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C,
-                              int batch, int M, int N, int K, int ta, int tb, long bsA, long bsB) {
+                              int batch, int M, int N, int K, int ta, int tb, long bsA, long bsB, int binner, long bsA2, long bsB2) {
     const long total = (long)batch * M * N;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int n = (int)(i % N);
         const long t = i / N;
         const int m = (int)(t % M);
         const long b = t / M;
-        const float* a = A + b * bsA;
-        const float* bb = B + b * bsB;
+        // batch index = (outer, inner) with inner < binner: per-operand strides, 0 where that operand broadcasts
+        const long bo = b / binner, bi = b - bo * binner;
+        const float* a = A + bo * bsA + bi * bsA2;
+        const float* bb = B + bo * bsB + bi * bsB2;
         float acc = 0.f;
         for (int k = 0; k < K; ++k) {
             const float x = ta ? a[(long)k * M + m] : a[(long)m * K + k];
@@ -203,9 +205,10 @@ int32_t lin_softmax(const float* in, float* out, long outer, long axis, long inn
 }
 
 int32_t lin_matmul(const float* A, const float* B, float* C, int batch, int M, int N, int K, int ta, int tb, long bsA,
-                   long bsB, hipStream_t s) {
+                   long bsB, hipStream_t s, int binner, long bsA2, long bsB2) {
+    if (binner < 1) return TRTX_ERR_INVALID;
     hipLaunchKernelGGL(matmul_kernel, dim3(grid_for((long)batch * M * N)), dim3(kThreads), 0, s, A, B, C, batch, M, N,
-                       K, ta, tb, bsA, bsB);
+                       K, ta, tb, bsA, bsB, binner, bsA2, bsB2);
     return check_launch("lin_matmul");
 }
 

@@ -163,7 +163,8 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 a.wgt = W + op.w_off;
                 a.bias = reinterpret_cast<const float*>(W + op.b_off);
                 a.cscale = a.in_i8 ? reinterpret_cast<const float*>(W + op.s_off) : nullptr;
-                a.N = op.stem ? batch : nb(t0);
+                // (the stem reads the LINEAR network input: in an explicit-batch plan its leading dimension is the image count)
+                a.N = op.stem ? (plan.explicit_batch ? (int)t0.dims.d[0] : batch) : nb(t0);
                 a.M = a.N * a.Ho * a.Wo;
                 if (op.kind == OP_DECONV)
                     st = deconv_direct(a, op.dtype, stream);
@@ -175,7 +176,9 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
                     st = a.f32 ? conv_igemm_f32(a, stream) : conv_igemm_f16(a, stream);
                     conv_set_launch_probe(nullptr);
-                } else
+                } else if (op.dw)
+                    st = conv_dw(a, op.dtype, stream);
+                else
                     st = conv_direct(a, op.dtype, stream);
                 break;
             }
@@ -310,6 +313,15 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 break;
             case OP_MATMUL: {
                 const PTensor& t1 = plan.tensors[op.in[1]];
+                if (op.view.rank > 0) {   // leading dims > 1 (lowering: op.view = the merged (outer, inner) batch dims and both operands' strides)
+                    const StridedView& v = op.view;
+                    const long outer = v.rank == 2 ? v.shape[0] : 1, inner = v.shape[v.rank - 1];
+                    st = lin_matmul(static_cast<const float*>(R.ptr(op.in[0])), static_cast<const float*>(R.ptr(op.in[1])),
+                                    static_cast<float*>(R.ptr(op.out[0])), (int)(outer * inner), op.i[0], op.i[1], op.i[2], op.i[3], op.i[4],
+                                    v.rank == 2 ? v.stride_in[0] : 0, v.rank == 2 ? v.stride_in2[0] : 0, stream, (int)inner,
+                                    v.stride_in[v.rank - 1], v.stride_in2[v.rank - 1]);
+                    break;
+                }
                 st = lin_matmul(static_cast<const float*>(R.ptr(op.in[0])), static_cast<const float*>(R.ptr(op.in[1])),
                                 static_cast<float*>(R.ptr(op.out[0])), to.batched ? batch : 1, op.i[0], op.i[1], op.i[2],
                                 op.i[3], op.i[4], t0.batched ? t0.dims.volume() : 0, t1.batched ? t1.dims.volume() : 0,
@@ -326,7 +338,9 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 for (int t : op.in) ins.push_back(R.ptr(t));
                 for (int t : op.out) outs.push_back(R.ptr(t));
                 void* ws = op.ws_bytes ? static_cast<char*>(c->d_arena) + op.ws_off : nullptr;
-                const int rc = op.plugin->v.enqueue(op.plugin->v.self, batch, ins.data(), outs.data(), ws, stream);
+                // explicit batch: the plugin's batchSize is the leading dimension of its tensors (lowering: op.i[0])
+                const int pb = plan.explicit_batch && op.i[0] > 0 ? op.i[0] : batch;
+                const int rc = op.plugin->v.enqueue(op.plugin->v.self, pb, ins.data(), outs.data(), ws, stream);
                 if (rc != 0) {
                     fprintf(stderr, "[trtx_hip] plugin %s enqueue returned %d\n", op.name.c_str(), rc);
                     st = TRTX_ERR_HIP;
@@ -342,8 +356,14 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     lds[k] = plan.tensors[op.in[k]].ld;
                 }
                 st = (t0.dtype == DT_F32 ? trtx_yolo_head_decode_nhwc_f32 : trtx_yolo_head_decode_nhwc)(
-                        heads, lds, nl, batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
+                        heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+                break;
+            }
+            case OP_ATTENTION: {
+                const PTensor &to2 = plan.tensors[op.out[1]];
+                st = psa_attention_f16(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, R.ptr(op.out[1]), to2.ld, nb(t0), op.i[0], op.i[1], op.i[2],
+                                       op.i[3], op.f[0], stream);
                 break;
             }
             case OP_ROI_ALIGN: {

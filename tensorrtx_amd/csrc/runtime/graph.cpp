@@ -283,11 +283,29 @@ bool Network::infer(int li) {
             return true;
         }
         case L_PLUGIN: {
+            // explicit batch (TensorRT's rule for IPluginV2-family plugins): the leading dimension is the batch, every input must
+            // carry the same one, getOutputDimensions sees the dims without it and the outputs get it prepended
             std::vector<Dims> ins;
-            for (size_t i = 0; i < l.inputs.size(); ++i) ins.push_back(in((int)i));
+            int64_t lead = -1;
+            for (size_t i = 0; i < l.inputs.size(); ++i) {
+                Dims d = in((int)i);
+                if (explicit_batch) {
+                    if (d.nb < 1 || (lead >= 0 && d.d[0] != lead)) return fail(this, l.name + ": plugin inputs disagree on the batch dimension");
+                    lead = d.d[0];
+                    for (int k = 1; k < d.nb; ++k) d.d[k - 1] = d.d[k];
+                    --d.nb;
+                }
+                ins.push_back(d);
+            }
             for (size_t s = 0; s < l.outputs.size(); ++s) {
                 Dims o;
                 if (!l.plugin->output_dims((int)s, ins, &o)) return fail(this, l.name + ": plugin getOutputDimensions failed");
+                if (explicit_batch && lead >= 0) {
+                    if (o.nb >= 8) return fail(this, l.name + ": plugin output rank");
+                    for (int k = o.nb; k > 0; --k) o.d[k] = o.d[k - 1];
+                    o.d[0] = lead;
+                    ++o.nb;
+                }
                 set_out((int)s, o);
             }
             return true;

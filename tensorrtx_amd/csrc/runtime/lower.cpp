@@ -17,8 +17,8 @@ const char* op_kind_name(int k) {
     static const char* n[] = {"conv",     "deconv",    "pool",      "resize",     "ew_nhwc", "act_nhwc", "scale_nhwc",
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
-                              "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group"};
-    return (k >= 0 && k <= OP_CONV_GROUP) ? n[k] : "?";
+                              "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention"};
+    return (k >= 0 && k <= OP_ATTENTION) ? n[k] : "?";
 }
 
 namespace {
@@ -65,6 +65,13 @@ struct YoloHeadFuse {
     YoloLayerParams params;
 };
 
+struct AttentionFuse {
+    int qkv = -1;                    // network tensor: the qkv convolution's output (B, heads*(2kd+hd), H, W)
+    int out_o = -1, out_v = -1;      // network tensors: O reshaped to (B, heads*hd, H, W), and v reshaped the same way
+    int heads = 0, N = 0, kd = 0, hd = 0;
+    float scale = 0.f;
+};
+
 struct Lowerer {
     const Network& net;
     Plan& plan;
@@ -78,6 +85,8 @@ struct Lowerer {
     std::vector<FusedConv> groups;
     std::vector<YoloHeadFuse> yolo_heads;
     std::vector<int> yolo_at;
+    std::vector<AttentionFuse> attns;
+    std::vector<int> attn_at;
     std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src
     std::string err;
 
@@ -93,6 +102,7 @@ struct Lowerer {
         stride_folded.assign(n.layers.size(), 0);
         group_at.assign(n.layers.size(), -1);
         yolo_at.assign(n.layers.size(), -1);
+        attn_at.assign(n.layers.size(), -1);
     }
 
     bool fail(const std::string& m) {
@@ -361,8 +371,12 @@ struct Lowerer {
         return true;
     }
     bool match_yolo_level(int plugin_layer, int t_in, int classes, int* head, int* conv_layer, std::vector<int>* used) {
+        // explicit batch (YOLO11, yolo11/src/model.cpp:336-390): the same graph with a leading batch dimension B on every tensor;
+        // e = 1 shifts every per-sample axis, and each tensor's dim 0 must be that B (full, unsliced)
+        const int e = net.explicit_batch ? 1 : 0;
+        const int64_t B = e ? net.tensors[t_in].dims.d[0] : 1;
         const int lc = producer(t_in);
-        if (lc < 0 || net.layers[lc].kind != L_CONCAT || net.layers[lc].inputs.size() != 2 || net.layers[lc].axis != 0) return false;
+        if (lc < 0 || net.layers[lc].kind != L_CONCAT || net.layers[lc].inputs.size() != 2 || net.layers[lc].axis != e) return false;
         if (!only_used_by(t_in, {plugin_layer})) return false;
         const int ta = net.layers[lc].inputs[0], tb = net.layers[lc].inputs[1];
         // box branch
@@ -370,8 +384,8 @@ struct Lowerer {
         if (lsh2 < 0 || net.layers[lsh2].kind != L_SHUFFLE || !only_used_by(ta, {lc})) return false;
         const LayerDef& sh2 = net.layers[lsh2];
         const Dims& d2 = net.tensors[ta].dims;
-        if (d2.nb != 2 || d2.d[0] != 4 || !ident(sh2.perm1, 3) || !ident(sh2.perm2, 2)) return false;
-        const int64_t g = d2.d[1];
+        if (d2.nb != 2 + e || (e && d2.d[0] != B) || d2.d[e] != 4 || !ident(sh2.perm1, 3 + e) || !ident(sh2.perm2, 2 + e)) return false;
+        const int64_t g = d2.d[1 + e];
         const int tconv = sh2.inputs[0];
         const int lconv = producer(tconv);
         if (lconv < 0 || net.layers[lconv].kind != L_CONV || !only_used_by(tconv, {lsh2})) return false;
@@ -382,41 +396,45 @@ struct Lowerer {
         const int tsm = cv.inputs[0];
         const int lsm = producer(tsm);
         if (lsm < 0 || net.layers[lsm].kind != L_SOFTMAX || !only_used_by(tsm, {lconv})) return false;
-        if (!(net.layers[lsm].axis < 0 || net.layers[lsm].axis == 1)) return false;
+        if (!(net.layers[lsm].axis < 0 || net.layers[lsm].axis == (1 << e))) return false;
         const int tsh1 = net.layers[lsm].inputs[0];
         const int lsh1 = producer(tsh1);
         if (lsh1 < 0 || net.layers[lsh1].kind != L_SHUFFLE || !only_used_by(tsh1, {lsm})) return false;
         const LayerDef& sh1 = net.layers[lsh1];
         const Dims& d1 = net.tensors[tsh1].dims;
-        if (d1.nb != 3 || d1.d[0] != 16 || d1.d[1] != 4 || d1.d[2] != g) return false;
-        if (!ident(sh1.perm1, 2) || sh1.reshape.nb != 3 || sh1.perm2[0] != 1 || sh1.perm2[1] != 0 || sh1.perm2[2] != 2) return false;
+        if (d1.nb != 3 + e || (e && d1.d[0] != B) || d1.d[e] != 16 || d1.d[1 + e] != 4 || d1.d[2 + e] != g) return false;
+        if (!ident(sh1.perm1, 2 + e) || sh1.reshape.nb != 3 + e || (e && sh1.perm2[0] != 0) || sh1.perm2[e] != 1 + e || sh1.perm2[1 + e] != e ||
+            sh1.perm2[2 + e] != 2 + e)
+            return false;
         const int tsa = sh1.inputs[0];
         const int lsa = producer(tsa);
         if (lsa < 0 || net.layers[lsa].kind != L_SLICE || !only_used_by(tsa, {lsh1})) return false;
         const LayerDef& sa = net.layers[lsa];
-        if (sa.start.nb != 2 || sa.start.d[0] != 0 || sa.start.d[1] != 0 || sa.size.d[0] != 64 || sa.size.d[1] != g ||
-            sa.step.d[0] != 1 || sa.step.d[1] != 1)
+        auto lead_ok = [&](const LayerDef& sl) { return !e || (sl.start.d[0] == 0 && sl.size.d[0] == B && sl.step.d[0] == 1); };
+        if (sa.start.nb != 2 + e || !lead_ok(sa) || sa.start.d[e] != 0 || sa.start.d[1 + e] != 0 || sa.size.d[e] != 64 || sa.size.d[1 + e] != g ||
+            sa.step.d[e] != 1 || sa.step.d[1 + e] != 1)
             return false;
         // class branch
         const int lsb = producer(tb);
         if (lsb < 0 || net.layers[lsb].kind != L_SLICE || !only_used_by(tb, {lc})) return false;
         const LayerDef& sb = net.layers[lsb];
-        if (sb.start.nb != 2 || sb.start.d[0] != 64 || sb.start.d[1] != 0 || sb.size.d[0] != classes || sb.size.d[1] != g ||
-            sb.step.d[0] != 1 || sb.step.d[1] != 1 || sb.inputs[0] != sa.inputs[0])
+        if (sb.start.nb != 2 + e || !lead_ok(sb) || sb.start.d[e] != 64 || sb.start.d[1 + e] != 0 || sb.size.d[e] != classes ||
+            sb.size.d[1 + e] != g || sb.step.d[e] != 1 || sb.step.d[1 + e] != 1 || sb.inputs[0] != sa.inputs[0])
             return false;
         const int tflat = sa.inputs[0];
         const int lflat = producer(tflat);
         if (lflat < 0 || net.layers[lflat].kind != L_SHUFFLE || !only_used_by(tflat, {lsa, lsb})) return false;
         const LayerDef& fl = net.layers[lflat];
         const Dims& dx = net.tensors[fl.inputs[0]].dims;
-        if (!ident(fl.perm1, 3) || !ident(fl.perm2, 2) || !spatial(dx) || dx.d[0] != 64 + classes || dx.d[1] * dx.d[2] != g) return false;
+        if (!ident(fl.perm1, 3 + e) || !ident(fl.perm2, 2 + e) || !spatial(dx) || (e && dx.d[0] != B) || dx.d[e] != 64 + classes ||
+            dx.d[1 + e] * dx.d[2 + e] != g)
+            return false;
         *head = fl.inputs[0];
         *conv_layer = lconv;
         for (int l : {lc, lsh2, lconv, lsm, lsh1, lsa, lsb, lflat}) used->push_back(l);
         return true;
     }
-    void analyse_yolo_head() {
-        if (net.explicit_batch) return;   // (fp16 and, since round 5, fp32 engines: the kernel reads either element type)
+    void analyse_yolo_head() {   // (fp16 and, since round 5, fp32 engines: the kernel reads either element type; implicit and explicit batch)
         for (size_t li = 0; li < net.layers.size(); ++li) {
             const LayerDef& l = net.layers[li];
             if (l.kind != L_PLUGIN || l.outputs.size() != 1) continue;
@@ -430,7 +448,9 @@ struct Lowerer {
                 ok = match_yolo_level((int)li, l.inputs[k], f.params.classes, &head, &conv, &used);
                 if (!ok) break;
                 const Dims& dh = net.tensors[head].dims;
-                ok = dh.d[1] == f.params.net_h / f.params.strides[k] && dh.d[2] == f.params.net_w / f.params.strides[k];
+                const int e = net.explicit_batch ? 1 : 0;
+                ok = dh.d[1 + e] == f.params.net_h / f.params.strides[k] && dh.d[2 + e] == f.params.net_w / f.params.strides[k];
+                if (e && dh.d[0] != net.tensors[l.inputs[0]].dims.d[0]) ok = false;
                 if (f.dfl_conv_layer >= 0 && net.layers[conv].w0 != net.layers[f.dfl_conv_layer].w0) ok = false;
                 f.dfl_conv_layer = conv;
                 f.head_tensor.push_back(head);
@@ -444,6 +464,111 @@ struct Lowerer {
             yolo_heads.push_back(f);
         }
     }
+    // ---- YOLO11 PSA attention (yolo11/src/block.cpp:287-339): qkv -> view (B, heads, 2kd+hd, N) -> q / k / v slices -> q^T k -> uniform
+    // scale -> softmax over the keys -> v @ attn^T -> view (B, heads*hd, H, W), and v viewed the same way for `pe`.  Every shape, permutation,
+    // slice and the scale are checked and every intermediate must have no other reader; anything else keeps the generic linear path.
+    // fp16 engines only (fp32 engines, the tolerance build, keep the generic path).
+    void analyse_attention() {
+        if (!net.explicit_batch || dt != DT_F16) return;
+        auto shuffle_only_perm1 = [&](const LayerDef& l, std::initializer_list<int> p) {
+            if (l.kind != L_SHUFFLE || l.reshape.nb != 0) return false;
+            int k = 0;
+            for (int v : p)
+                if (l.perm1[k++] != v) return false;
+            return ident(l.perm2, 4);
+        };
+        for (size_t li = 0; li < net.layers.size(); ++li) {
+            const LayerDef& m1 = net.layers[li];
+            if (m1.kind != L_MATMUL || m1.mm_op[0] != TRTX_MATMUL_NONE || m1.mm_op[1] != TRTX_MATMUL_NONE || absorbed[li]) continue;
+            const int lqt = producer(m1.inputs[0]), lk = producer(m1.inputs[1]);
+            if (lqt < 0 || lk < 0 || !shuffle_only_perm1(net.layers[lqt], {0, 1, 3, 2}) || net.layers[lk].kind != L_SLICE) continue;
+            const int lq = producer(net.layers[lqt].inputs[0]);
+            if (lq < 0 || net.layers[lq].kind != L_SLICE) continue;
+            const int tx = net.layers[lq].inputs[0];
+            if (net.layers[lk].inputs[0] != tx) continue;
+            const int lview = producer(tx);
+            if (lview < 0 || net.layers[lview].kind != L_SHUFFLE || !ident(net.layers[lview].perm1, 4) || !ident(net.layers[lview].perm2, 4)) continue;
+            const int tqkv = net.layers[lview].inputs[0];
+            const Dims &dx = net.tensors[tx].dims, &dq = net.tensors[tqkv].dims;
+            if (dx.nb != 4 || dq.nb != 4 || dx.d[0] != dq.d[0] || dx.d[3] != dq.d[2] * dq.d[3] || dx.d[1] * dx.d[2] != dq.d[1]) continue;
+            const int64_t B = dx.d[0], heads = dx.d[1], rows = dx.d[2], N = dx.d[3];
+            auto slice_rows = [&](const LayerDef& sl, int64_t r0, int64_t nr) {
+                return sl.start.nb == 4 && sl.start.d[0] == 0 && sl.start.d[1] == 0 && sl.start.d[2] == r0 && sl.start.d[3] == 0 && sl.size.d[0] == B &&
+                       sl.size.d[1] == heads && sl.size.d[2] == nr && sl.size.d[3] == N && sl.step.d[0] == 1 && sl.step.d[1] == 1 && sl.step.d[2] == 1 &&
+                       sl.step.d[3] == 1;
+            };
+            const int64_t kd = net.layers[lq].size.d[2];
+            const int64_t hd = rows - 2 * kd;
+            if (!slice_rows(net.layers[lq], 0, kd) || !slice_rows(net.layers[lk], kd, kd) || hd < 1) continue;
+            // the v slice: the third reader of the view
+            int lv = -1;
+            for (int c : consumers[tx])
+                if (c != lq && c != lk) lv = c;
+            if (lv < 0 || net.layers[lv].kind != L_SLICE || !slice_rows(net.layers[lv], 2 * kd, hd) || !only_used_by(tx, {lq, lk, lv})) continue;
+            // scale -> softmax -> transpose -> second matmul
+            int lsc, lsm, lat, m2, lre, lvre = -1;
+            if (!sole_consumer(m1.outputs[0], &lsc) || net.layers[lsc].kind != L_SCALE || net.layers[lsc].op != TRTX_SCALE_UNIFORM) continue;
+            const LayerDef& sc = net.layers[lsc];
+            if (sc.w1.size() != 1 || (!sc.w0.empty() && (sc.w0.size() != 1 || sc.w0[0] != 0.f)) || (!sc.w2.empty() && (sc.w2.size() != 1 || sc.w2[0] != 1.f)))
+                continue;
+            if (!sole_consumer(sc.outputs[0], &lsm) || net.layers[lsm].kind != L_SOFTMAX || net.layers[lsm].axis != (1 << 3)) continue;
+            if (!sole_consumer(net.layers[lsm].outputs[0], &lat) || !shuffle_only_perm1(net.layers[lat], {0, 1, 3, 2})) continue;
+            if (!sole_consumer(net.layers[lat].outputs[0], &m2)) continue;
+            const LayerDef& mm2 = net.layers[m2];
+            if (mm2.kind != L_MATMUL || mm2.mm_op[0] != TRTX_MATMUL_NONE || mm2.mm_op[1] != TRTX_MATMUL_NONE || mm2.inputs[1] != net.layers[lat].outputs[0] ||
+                mm2.inputs[0] != net.layers[lv].outputs[0])
+                continue;
+            if (!sole_consumer(mm2.outputs[0], &lre)) continue;
+            const int tv = net.layers[lv].outputs[0];
+            for (int c : consumers[tv])
+                if (c != m2) lvre = c;
+            if (lvre < 0 || !only_used_by(tv, {m2, lvre})) continue;
+            auto view_bchw = [&](int l) {   // reshape (B, heads*hd, H, W) of a (B, heads, hd, N) tensor, no transposes
+                const LayerDef& r = net.layers[l];
+                const Dims& o = net.tensors[r.outputs[0]].dims;
+                return r.kind == L_SHUFFLE && ident(r.perm1, 4) && ident(r.perm2, 4) && r.reshape.nb == 4 && o.nb == 4 && o.d[0] == B &&
+                       o.d[1] == heads * hd && o.d[2] == dq.d[2] && o.d[3] == dq.d[3];
+            };
+            if (!view_bchw(lre) || !view_bchw(lvre) || !psa_attention_supported((int)kd, (int)hd) || !only_used_by(m1.inputs[0], {(int)li}) ||
+                !only_used_by(m1.inputs[1], {(int)li}) || !only_used_by(net.layers[lqt].inputs[0], {lqt}))
+                continue;
+            const int used[] = {lview, lq, lk, lv, lqt, (int)li, lsc, lsm, lat, m2, lre, lvre};
+            bool free = true;
+            for (int u : used) free = free && !absorbed[u] && !net.tensors[net.layers[u].outputs[0]].is_output;
+            if (!free) continue;
+            AttentionFuse f;
+            f.qkv = tqkv;
+            f.out_o = net.layers[lre].outputs[0];
+            f.out_v = net.layers[lvre].outputs[0];
+            f.heads = (int)heads;
+            f.N = (int)N;
+            f.kd = (int)kd;
+            f.hd = (int)hd;
+            f.scale = sc.w1[0];
+            int at = 0;
+            for (int u : used) {
+                absorbed[u] = true;
+                at = std::max(at, u);
+            }
+            attn_at[at] = (int)attns.size();
+            attns.push_back(f);
+        }
+    }
+    bool emit_attention(const AttentionFuse& f) {
+        const int in = need_nhwc(f.qkv);
+        const int o = new_tensor(f.out_o, net.tensors[f.out_o].dims, LAY_NHWC, true);
+        const int v = new_tensor(f.out_v, net.tensors[f.out_v].dims, LAY_NHWC, true);
+        POp& op = add_op(OP_ATTENTION, "attention:" + net.tensors[f.qkv].name, {in}, {o, v});
+        op.i[0] = f.heads; op.i[1] = f.N; op.i[2] = f.kd; op.i[3] = f.hd;
+        op.f[0] = f.scale;
+        const double B = plan.tensors[in].nfix;
+        op.flops = 2.0 * B * f.heads * (double)f.N * f.N * (f.kd + f.hd);
+        op.bytes = 2.0 * B * f.N * ((double)plan.tensors[in].C + 2.0 * f.heads * f.hd);
+        pt_of[f.out_o] = o;
+        pt_of[f.out_v] = v;
+        return true;
+    }
+
     bool emit_yolo_head(const YoloHeadFuse& f) {
         const LayerDef& l = net.layers[f.plugin_layer];
         std::vector<int> ins;
@@ -457,7 +582,9 @@ struct Lowerer {
         op.i[3] = f.params.max_out;
         op.i[4] = (int)f.params.strides.size();
         for (size_t k = 0; k < f.params.strides.size(); ++k) op.i[5 + k] = f.params.strides[k];
-        op.ws_bytes = trtx_yolo_head_decode_workspace(plan.max_batch, f.params.net_h, f.params.net_w, f.params.strides.data(),
+        // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
+        if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
+        op.ws_bytes = trtx_yolo_head_decode_workspace(net.explicit_batch ? op.i[11] : plan.max_batch, f.params.net_h, f.params.net_w, f.params.strides.data(),
                                                       (int)f.params.strides.size());
         for (int t : ins) op.bytes += (double)dtype_size(dt) * plan.tensors[t].dims.volume();
         op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
@@ -722,10 +849,12 @@ struct Lowerer {
             }
             case L_MATMUL: {
                 const Dims &da = net.tensors[l.inputs[0]].dims, &db = net.tensors[l.inputs[1]].dims;
-                for (int k = 0; k < da.nb - 2; ++k)
-                    if (da.d[k] != 1 || db.d[k] != 1) return fail(l.name + ": matmul with leading dims > 1 is not implemented");
+                bool lead = false;
+                for (int k = 0; k < da.nb - 2; ++k) lead = lead || da.d[k] != 1 || db.d[k] != 1;
                 if (l.mm_op[0] == TRTX_MATMUL_VECTOR || l.mm_op[1] == TRTX_MATMUL_VECTOR) return fail(l.name + ": kVECTOR matmul");
                 const int a = need_lin(l.inputs[0]), b = need_lin(l.inputs[1]);
+                if (lead && (plan.tensors[a].batched || plan.tensors[b].batched))
+                    return fail(l.name + ": matmul with leading dims > 1 on a tensor that also carries the implicit batch is not implemented");
                 const Dims& dout = out_dims();
                 const int out = new_tensor(l.outputs[0], dout, LAY_LINEAR, plan.tensors[a].batched || plan.tensors[b].batched);
                 POp& op = add_op(OP_MATMUL, l.name, {a, b}, {out});
@@ -734,6 +863,35 @@ struct Lowerer {
                 op.i[0] = (int)dout.d[n - 2]; op.i[1] = (int)dout.d[n - 1];
                 op.i[2] = (int)(ta ? da.d[n - 2] : da.d[n - 1]); op.i[3] = ta; op.i[4] = tb;
                 op.flops = 2.0 * op.i[0] * op.i[1] * op.i[2];
+                if (lead) {
+                    // batched matmul over the leading dims, a dim of 1 broadcasting against a larger one: per leading dim the element
+                    // stride of A and B (0 where broadcast); adjacent dims that walk both operands contiguously merge, and the
+                    // kernel takes at most two (outer, inner) - op.view holds them (rank, shape, stride_in = A, stride_in2 = B)
+                    long sa = (long)da.d[n - 2] * da.d[n - 1], sb = (long)db.d[n - 2] * db.d[n - 1];
+                    std::vector<long> shp, ssa, ssb;
+                    for (int k = n - 3; k >= 0; --k) {
+                        const long ea = da.d[k] == 1 ? 0 : sa, eb = db.d[k] == 1 ? 0 : sb;
+                        sa *= da.d[k];
+                        sb *= db.d[k];
+                        if (dout.d[k] == 1) continue;
+                        if (!shp.empty() && ssa.back() * shp.back() == ea && ssb.back() * shp.back() == eb) {
+                            shp.back() *= dout.d[k];   // (merge: ea / eb continue the inner dim's walk; broadcast dims stay 0 * x == 0)
+                            continue;
+                        }
+                        shp.push_back(dout.d[k]);
+                        ssa.push_back(ea);
+                        ssb.push_back(eb);
+                    }
+                    if (shp.size() > 2) return fail(l.name + ": matmul with more than two independent broadcast patterns in its leading dims");
+                    op.view.rank = (int)shp.size();
+                    for (size_t k = 0; k < shp.size(); ++k) {   // view dim 0 = outer
+                        const size_t j = shp.size() - 1 - k;
+                        op.view.shape[k] = shp[j];
+                        op.view.stride_in[k] = ssa[j];
+                        op.view.stride_in2[k] = ssb[j];
+                    }
+                    op.flops *= (double)dout.volume() / ((double)op.i[0] * op.i[1]);
+                }
                 pt_of[l.outputs[0]] = out;
                 return true;
             }
@@ -861,6 +1019,7 @@ struct Lowerer {
                 }
                 POp& op = add_op(OP_PLUGIN, l.name, ins, outs);
                 op.plugin = l.plugin;
+                if (net.explicit_batch && !l.inputs.empty()) op.i[0] = (int)net.tensors[l.inputs[0]].dims.d[0];   // the plugin's batchSize
                 return true;
             }
             case L_IDENTITY: {
@@ -1050,10 +1209,15 @@ struct Lowerer {
             pt_of[t] = p;
         }
         analyse_yolo_head();  // before conv fusion: it claims the DFL 1x1 convolutions
+        analyse_attention();
         analyse_fusion();
         for (size_t li = 0; li < net.layers.size(); ++li) {
             if (yolo_at[li] >= 0) {
                 if (!emit_yolo_head(yolo_heads[yolo_at[li]])) return false;
+                continue;
+            }
+            if (attn_at[li] >= 0) {
+                if (!emit_attention(attns[attn_at[li]])) return false;
                 continue;
             }
             if (group_at[li] >= 0) {
@@ -1563,6 +1727,9 @@ struct Lowerer {
                 }
             }
         }
+        // depthwise (YOLO11 DWConv and the PSA attention's pe): kernels/conv_dw.hip, fp16 and fp32, any channel stride
+        op.dw = op.kind == OP_CONV && !op.igemm && !op.stem && !op.from_deconv && op.extra_in.empty() && ti.dtype == dt && to.dtype == dt &&
+                (op.in.size() < 2 || plan.tensors[op.in[1]].dtype == dt) && conv_dw_supported(a);
         return op.igemm;
     }
 
@@ -1655,14 +1822,23 @@ struct Lowerer {
         for (size_t k = 0; k < plan.ops.size(); ++k) {
             POp& op = plan.ops[k];
             if (op.kind != OP_PLUGIN) continue;
+            // explicit batch: configurePlugin / getWorkspaceSize see the dims without the leading batch dimension, and that as maxBatch
+            const bool eb = plan.explicit_batch && op.i[0] > 0;
+            auto strip = [&](Dims d) {
+                if (eb && d.nb > 0) {
+                    for (int q = 1; q < d.nb; ++q) d.d[q - 1] = d.d[q];
+                    --d.nb;
+                }
+                return to_c(d);
+            };
+            const int mb = eb ? op.i[0] : plan.max_batch;
             std::vector<trtx_dims> din, dout;
-            for (int t : op.in) din.push_back(to_c(plan.tensors[t].dims));
-            for (int t : op.out) dout.push_back(to_c(plan.tensors[t].dims));
+            for (int t : op.in) din.push_back(strip(plan.tensors[t].dims));
+            for (int t : op.out) dout.push_back(strip(plan.tensors[t].dims));
             if (op.plugin->v.configure &&
-                op.plugin->v.configure(op.plugin->v.self, din.data(), (int)din.size(), dout.data(), (int)dout.size(),
-                                       plan.max_batch) != 0)
+                op.plugin->v.configure(op.plugin->v.self, din.data(), (int)din.size(), dout.data(), (int)dout.size(), mb) != 0)
                 return fail(op.name + ": plugin configurePlugin rejected the tensor shapes");
-            op.ws_bytes = op.plugin->v.workspace_size ? op.plugin->v.workspace_size(op.plugin->v.self, plan.max_batch) : 0;
+            op.ws_bytes = op.plugin->v.workspace_size ? op.plugin->v.workspace_size(op.plugin->v.self, mb) : 0;
             for (int t : op.in) op.bytes += 4.0 * plan.tensors[t].dims.volume();
             for (int t : op.out) op.bytes += 4.0 * plan.tensors[t].dims.volume();
         }
@@ -1958,6 +2134,12 @@ bool pack_weights(const Network& net, Plan* plan) {
                 op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
                 pack_conv_weights_f16(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
                                       reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+            } else if (op.dw) {
+                // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load
+                op.w_off = reserve((size_t)a.kh * a.kw * cout * 4);
+                float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
+                for (int co = 0; co < cout; ++co)
+                    for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = l.w0[(size_t)co * a.kh * a.kw + t] * sc[co];
             } else {
                 op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
                 pack_conv_weights_f32(l.w0.data(), cout, cin_logical / a.groups, a.kh, a.kw, sc.data(),
@@ -2031,8 +2213,10 @@ std::string Plan::describe_json() const {
               << ",\"bn_folded\":" << (op.scale_layer >= 0 ? "true" : "false") << ",\"ld_in\":" << a.ld_in
               << ",\"ld_out\":" << a.ld_out << ",\"i8\":[" << a.in_i8 << "," << a.out_i8 << "," << a.res_i8 << "],\"nmul\":" << (op.stem ? 1 : tensors[op.in[0]].nmul) << ",\"nfix\":"
               << (op.stem ? 0 : tensors[op.in[0]].nfix);
+            if (op.dw) o << ",\"dw\":true";
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
+        if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
         if (op.kind == OP_CONV_GROUP) {
             o << ",\"members\":[";
             for (size_t j = 0; j < op.group.size(); ++j) {

@@ -46,6 +46,7 @@ enum OpKind : int {
     OP_ROI_ALIGN,     // detectron2 ROIAlign on the NHWC feature map, NHWC [P][res][res][C] out (fused form of the "RoiAlign" plugin)
     OP_RESERVED_47,   // (rounds 3-4: OP_CONV_CHAIN, the fused convolution chains - tools/hip/experiments/)
     OP_CONV_GROUP,    // 2..4 INDEPENDENT implicit-GEMM convolutions of one kernel instantiation in one launch (POp::group; round 4)
+    OP_ATTENTION,     // YOLO11 PSA attention on the NHWC fp16 qkv tensor: O and the V image (kernels/attention.hip); i = heads, N, kd, hd, f[0] = scale
 };
 const char* op_kind_name(int k);
 
@@ -94,6 +95,7 @@ struct POp {
     bool igemm = false;
     bool stem = false;         // conv_stem kernel: reads the LINEAR fp32 input directly
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
+    bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
     // OP_CONV_GROUP: the member convolutions, each a complete OP_CONV record (its own in / out tensors, ConvArgs, weights); the group's
     // in / out are the unions, so dependencies, lanes and buffer lifetimes see one op
     std::vector<POp> group;

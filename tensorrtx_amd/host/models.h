@@ -40,6 +40,28 @@ struct Yolov8Config {
 nvinfer1::IHostMemory* buildEngineYolov8Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
                                             const std::string& wts, const Yolov8Config& cfg);
 
+// yolo11/include/config.h constants as run-time configuration.  Explicit batch like the reference (model.cpp:143-149): the batch is
+// part of the input dims, so a plan serves exactly `batch` images per enqueue.
+struct Yolo11Config {
+    int input_h = 640, input_w = 640;   // kInputH / kInputW
+    int num_class = 80;                 // kNumClass
+    int batch = 1;                      // kBatchSize (Dims4{kBatchSize, 3, kInputH, kInputW})
+    int max_out_bbox = 1000;            // kMaxNumOutputBbox
+    bool fp16 = true;                   // USE_FP16
+    float gd = 0.50f, gw = 0.25f;       // 'n' scale (yolo11_det.cpp:120-150; yolo11_scale)
+    int max_channels = 1024;
+    bool c3k = false;                   // C3k blocks inside C3K2 (m / l / x; model.cpp:160-163)
+    bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
+    int task = 0;                       // 0 det; seg / pose / obb / cls are not built yet
+    int num_points = 17;                // kNumberOfPoints
+    float kpt_conf = 0.5f;              // kConfThreshKeypoints (truncated into the plugin field like the reference)
+};
+// the n / s / m / l / x scale: gd, gw, max_channels and the c3k flag; false for an unknown letter
+bool yolo11_scale(char type, Yolo11Config* cfg);
+// yolo11/src/model.cpp:138-400 with yolo11/src/block.cpp
+nvinfer1::IHostMemory* buildEngineYolo11Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
+                                            const std::string& wts, const Yolo11Config& cfg);
+
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {
     int input_h = 800, input_w = 1067;      // INPUT_H / INPUT_W: 480x640 resized by calculateSize() (rcnn.cpp:349-366)

@@ -1,0 +1,321 @@
+// YOLO11 detection network through the network-definition API, explicit batch like the reference.
+// Mirrors the reference blocks and builder:
+//   convBnSiLU / bottleneck / SPPF / DFL / addYoLoLayer / C3k / C3K2 / convBn / Attention / PSABlock / C2PSA / DWConv
+//                                                              yolo11/src/block.cpp:73-437
+//   get_width / get_depth / calculateStrides / buildEngineYolo11Det   yolo11/src/model.cpp:9-31, 138-400
+// Graph, weight keys ("model.<n>...") and layer order are those of the reference.
+#include <cmath>
+#include <vector>
+
+#include "common.h"
+#include "models.h"
+
+using namespace nvinfer1;
+
+namespace trtx_host {
+namespace {
+
+int get_width(int x, float gw, int max_channels, int divisor = 8) {  // model.cpp:9-13 (YOLO11 caps before scaling, unlike v8)
+    const int ch = std::min(x, max_channels);
+    return int(ceil((ch * gw) / divisor)) * divisor;
+}
+
+int get_depth(int x, float gd) {  // model.cpp:15-22
+    if (x == 1) return 1;
+    int r = (int)round(x * gd);
+    if (x * gd - int(x * gd) == 0.5 && (int(x * gd) % 2) == 0) --r;
+    return std::max<int>(r, 1);
+}
+
+struct Ctx {
+    INetworkDefinition* net;
+    WeightMap& wm;
+    std::vector<float*> owned;   // the Attention's 1-element scale weights (block.cpp:313-322), alive until the plan is built
+    ~Ctx() {
+        for (float* p : owned) delete[] p;
+    }
+    Weights scalar(float v) {
+        float* p = new float[1]{v};
+        owned.push_back(p);
+        return Weights{DataType::kFLOAT, p, 1};
+    }
+};
+
+// Conv (no bias, 'same' padding k/2, groups g) + BN (eps 1e-3)   (block.cpp:73-92 without the SiLU; convBn :271-285)
+ITensor* convBn(Ctx& c, ITensor& in, int ch, int k, int s, const std::string& lname, int g = 1) {
+    auto* conv = c.net->addConvolutionNd(in, ch, DimsHW{k, k}, need(c.wm, lname + ".conv.weight"), noWeights());
+    assert(conv);
+    conv->setStrideNd(DimsHW{s, s});
+    conv->setPaddingNd(DimsHW{k / 2, k / 2});
+    if (g != 1) conv->setNbGroups(g);
+    return addBatchNorm2d(c.net, c.wm, *conv->getOutput(0), lname + ".bn", 1e-3f)->getOutput(0);
+}
+
+// SiLU spelled Sigmoid * x (block.cpp:88-91)
+ITensor* silu(Ctx& c, ITensor* x) {
+    ITensor* sig = c.net->addActivation(*x, ActivationType::kSIGMOID)->getOutput(0);
+    return c.net->addElementWise(*x, *sig, ElementWiseOperation::kPROD)->getOutput(0);
+}
+
+ITensor* convBnSiLU(Ctx& c, ITensor& in, int ch, int k, int s, const std::string& lname) { return silu(c, convBn(c, in, ch, k, s, lname)); }
+
+// DWConv: depthwise conv (groups = ch) + BN + SiLU (block.cpp:417-437)
+ITensor* DWConv(Ctx& c, ITensor& in, int ch, int k, int s, const std::string& lname) { return silu(c, convBn(c, in, ch, k, s, lname, ch)); }
+
+ITensor* bottleneck(Ctx& c, ITensor& in, int c1, int c2, bool shortcut, float e, const std::string& lname) {  // block.cpp:94-109 (k 3x3, 3x3)
+    const int c_ = (int)((float)c2 * e);
+    ITensor* a = convBnSiLU(c, in, c_, 3, 1, lname + ".cv1");
+    ITensor* b = convBnSiLU(c, *a, c2, 3, 1, lname + ".cv2");
+    if (shortcut && c1 == c2) return c.net->addElementWise(in, *b, ElementWiseOperation::kSUM)->getOutput(0);
+    return b;
+}
+
+ITensor* cat2(Ctx& c, ITensor* a, ITensor* b) {
+    ITensor* v[] = {a, b};
+    return c.net->addConcatenation(v, 2)->getOutput(0);
+}
+
+ITensor* C3k(Ctx& c, ITensor& in, int c2, int n, bool shortcut, float e, const std::string& lname) {  // block.cpp:207-224
+    const int c_ = (int)((float)c2 * e);
+    ITensor* y = convBnSiLU(c, in, c_, 1, 1, lname + ".cv1");
+    ITensor* b = convBnSiLU(c, in, c_, 1, 1, lname + ".cv2");
+    for (int i = 0; i < n; ++i) y = bottleneck(c, *y, c_, c_, shortcut, 1.0f, lname + ".m." + std::to_string(i));
+    return convBnSiLU(c, *cat2(c, y, b), c2, 1, 1, lname + ".cv3");
+}
+
+// C3K2 (block.cpp:226-262): cv1 to 2c_, split in halves along channels, n C3k / bottleneck blocks on the second half, every
+// result appended to the running concat, cv2
+ITensor* C3K2(Ctx& c, ITensor& in, int c2, int n, bool c3k, bool shortcut, float e, const std::string& lname) {
+    const int c_ = (int)((float)c2 * e);
+    ITensor* cv1 = convBnSiLU(c, in, 2 * c_, 1, 1, lname + ".cv1");
+    const Dims d = cv1->getDimensions();
+    const Dims4 half{d.d[0], d.d[1] / 2, d.d[2], d.d[3]}, unit{1, 1, 1, 1};
+    ITensor* s1 = c.net->addSlice(*cv1, Dims4{0, 0, 0, 0}, half, unit)->getOutput(0);
+    ITensor* s2 = c.net->addSlice(*cv1, Dims4{0, d.d[1] / 2, 0, 0}, half, unit)->getOutput(0);
+    ITensor* cat = cat2(c, s1, s2);
+    ITensor* y = s2;
+    for (int i = 0; i < n; ++i) {
+        const std::string m = lname + ".m." + std::to_string(i);
+        y = c3k ? C3k(c, *y, c_, 2, shortcut, 0.5f, m) : bottleneck(c, *y, c_, c_, shortcut, 0.5f, m);
+        cat = cat2(c, cat, y);
+    }
+    return convBnSiLU(c, *cat, c2, 1, 1, lname + ".cv2");
+}
+
+ITensor* SPPF(Ctx& c, ITensor& in, int c1, int c2, int k, const std::string& lname) {  // block.cpp:111-138
+    ITensor* x = convBnSiLU(c, in, c1 / 2, 1, 1, lname + ".cv1");
+    std::vector<ITensor*> parts{x};
+    for (int i = 0; i < 3; ++i) {
+        auto* pool = c.net->addPoolingNd(*parts.back(), PoolingType::kMAX, DimsHW{k, k});
+        pool->setStrideNd(DimsHW{1, 1});
+        pool->setPaddingNd(DimsHW{k / 2, k / 2});
+        parts.push_back(pool->getOutput(0));
+    }
+    return convBnSiLU(c, *c.net->addConcatenation(parts.data(), 4)->getOutput(0), c2, 1, 1, lname + ".cv2");
+}
+
+// Attention (block.cpp:287-339): qkv 1x1 conv+BN, view (B, heads, 2*kd + hd, N), split q / k / v, softmax(scale * q^T k) over the
+// keys, v @ attn^T viewed back as (B, dim, H, W), plus the depthwise positional conv pe(v), then proj 1x1 conv+BN
+ITensor* Attention(Ctx& c, ITensor& in, int dim, int num_heads, float attn_ratio, const std::string& lname) {
+    const int head_dim = dim / num_heads;
+    const int key_dim = (int)(head_dim * attn_ratio);
+    const float scale = (float)pow(key_dim, -0.5);
+    const int nh_kd = key_dim * num_heads;
+    const int h = dim + nh_kd * 2;
+    const Dims d = in.getDimensions();
+    const int B = (int)d.d[0], H = (int)d.d[2], W = (int)d.d[3], N = H * W;
+    ITensor* qkv = convBn(c, in, h, 1, 1, lname + ".qkv");
+    auto* sh = c.net->addShuffle(*qkv);
+    sh->setReshapeDimensions(Dims4{B, num_heads, -1, N});
+    ITensor* x = sh->getOutput(0);
+    const Dims d1 = x->getDimensions();
+    const Dims4 unit{1, 1, 1, 1};
+    ITensor* q = c.net->addSlice(*x, Dims4{0, 0, 0, 0}, Dims4{d1.d[0], d1.d[1], key_dim, d1.d[3]}, unit)->getOutput(0);
+    ITensor* k = c.net->addSlice(*x, Dims4{0, 0, key_dim, 0}, Dims4{d1.d[0], d1.d[1], key_dim, d1.d[3]}, unit)->getOutput(0);
+    ITensor* v = c.net->addSlice(*x, Dims4{0, 0, key_dim * 2, 0}, Dims4{d1.d[0], d1.d[1], head_dim, d1.d[3]}, unit)->getOutput(0);
+    auto* qT = c.net->addShuffle(*q);
+    qT->setFirstTranspose(Permutation{0, 1, 3, 2});
+    ITensor* attn = c.net->addMatrixMultiply(*qT->getOutput(0), MatrixOperation::kNONE, *k, MatrixOperation::kNONE)->getOutput(0);
+    attn = c.net->addScale(*attn, ScaleMode::kUNIFORM, c.scalar(0.f), c.scalar(scale), c.scalar(1.f))->getOutput(0);
+    auto* sm = c.net->addSoftMax(*attn);
+    sm->setAxes(1 << 3);
+    auto* attnT = c.net->addShuffle(*sm->getOutput(0));
+    attnT->setFirstTranspose(Permutation{0, 1, 3, 2});
+    ITensor* o = c.net->addMatrixMultiply(*v, MatrixOperation::kNONE, *attnT->getOutput(0), MatrixOperation::kNONE)->getOutput(0);
+    auto* re = c.net->addShuffle(*o);
+    re->setReshapeDimensions(Dims4{B, -1, H, W});
+    auto* vre = c.net->addShuffle(*v);
+    vre->setReshapeDimensions(Dims4{B, -1, H, W});
+    ITensor* pe = convBn(c, *vre->getOutput(0), dim, 3, 1, lname + ".pe", dim);
+    ITensor* sum = c.net->addElementWise(*re->getOutput(0), *pe, ElementWiseOperation::kSUM)->getOutput(0);
+    return convBn(c, *sum, dim, 1, 1, lname + ".proj");
+}
+
+ITensor* PSABlock(Ctx& c, ITensor& in, int dim, float attn_ratio, int num_heads, bool shortcut, const std::string& lname) {  // block.cpp:341-364
+    ITensor* a = Attention(c, in, dim, num_heads, attn_ratio, lname + ".attn");
+    ITensor* x = shortcut ? c.net->addElementWise(in, *a, ElementWiseOperation::kSUM)->getOutput(0) : a;
+    ITensor* f0 = convBnSiLU(c, *x, dim * 2, 1, 1, lname + ".ffn.0");
+    ITensor* f1 = convBn(c, *f0, dim, 1, 1, lname + ".ffn.1");
+    return shortcut ? c.net->addElementWise(*x, *f1, ElementWiseOperation::kSUM)->getOutput(0) : f1;
+}
+
+ITensor* C2PSA(Ctx& c, ITensor& in, int c1, int c2, int n, float e, const std::string& lname) {  // block.cpp:366-415
+    const int ch = (int)(c1 * e);
+    ITensor* cv1 = convBnSiLU(c, in, 2 * ch, 1, 1, lname + ".cv1");
+    const Dims d = cv1->getDimensions();
+    const Dims4 half{d.d[0], d.d[1] / 2, d.d[2], d.d[3]}, unit{1, 1, 1, 1};
+    ITensor* s1 = c.net->addSlice(*cv1, Dims4{0, 0, 0, 0}, half, unit)->getOutput(0);
+    ITensor* y = c.net->addSlice(*cv1, Dims4{0, d.d[1] / 2, 0, 0}, half, unit)->getOutput(0);
+    for (int i = 0; i < n; ++i) y = PSABlock(c, *y, ch, 0.5f, ch / 64, true, lname + ".m." + std::to_string(i));
+    return convBnSiLU(c, *cat2(c, s1, y), c2, 1, 1, lname + ".cv2");
+}
+
+ITensor* upsample2x(Ctx& c, ITensor& in) {  // model.cpp:205-209
+    const float scale[] = {1.0f, 1.0f, 2.0f, 2.0f};
+    auto* r = c.net->addResize(in);
+    assert(r);
+    r->setResizeMode(ResizeMode::kNEAREST);
+    r->setScales(scale, 4);
+    return r->getOutput(0);
+}
+
+// (B, 64, g) -> (B, 4, 16, g) -> transpose (B, 16, 4, g) -> softmax over the 16 bins -> 1x1 conv with weights arange(16) -> (B, 4, g)
+// (block.cpp:140-160)
+ITensor* DFL(Ctx& c, ITensor& in, int B, int grid, const std::string& wkey) {
+    auto* sh1 = c.net->addShuffle(in);
+    sh1->setReshapeDimensions(Dims4{B, 4, 16, grid});
+    sh1->setSecondTranspose(Permutation{0, 2, 1, 3});
+    auto* sm = c.net->addSoftMax(*sh1->getOutput(0));
+    sm->setAxes(1 << 1);
+    auto* conv = c.net->addConvolutionNd(*sm->getOutput(0), 1, DimsHW{1, 1}, need(c.wm, wkey), noWeights());
+    conv->setStrideNd(DimsHW{1, 1});
+    conv->setPaddingNd(DimsHW{0, 0});
+    auto* sh2 = c.net->addShuffle(*conv->getOutput(0));
+    sh2->setReshapeDimensions(Dims3{B, 4, grid});
+    return sh2->getOutput(0);
+}
+
+// block.cpp:162-205: the 9 netinfo fields, then the strides
+IPluginV2Layer* addYoLoLayer(Ctx& c, const std::vector<ITensor*>& dets, const std::vector<int>& strides, const Yolo11Config& cfg) {
+    auto* creator = getPluginRegistry()->getPluginCreator("YoloLayer_TRT", "1");
+    assert(creator && "YoloLayer_TRT creator not registered");
+    std::vector<int> info = {cfg.num_class, cfg.num_points, (int)cfg.kpt_conf, cfg.input_w, cfg.input_h, cfg.max_out_bbox,
+                             cfg.task == 1, cfg.task == 2, cfg.task == 3};
+    info.insert(info.end(), strides.begin(), strides.end());
+    PluginField field("combinedInfo", info.data(), PluginFieldType::kINT32, (int32_t)info.size());
+    PluginFieldCollection fc{1, &field};
+    IPluginV2* plugin = creator->createPlugin("yololayer", &fc);
+    assert(plugin);
+    std::vector<ITensor*> ins(dets);
+    auto* layer = c.net->addPluginV2(ins.data(), (int32_t)ins.size(), *plugin);
+    plugin->destroy();  // the network holds its own clone
+    return layer;
+}
+
+}  // namespace
+
+bool yolo11_scale(char type, Yolo11Config* cfg) {  // yolo11_det.cpp:120-150
+    switch (type) {
+        case 'n': cfg->gd = 0.50f; cfg->gw = 0.25f; cfg->max_channels = 1024; break;
+        case 's': cfg->gd = 0.50f; cfg->gw = 0.50f; cfg->max_channels = 1024; break;
+        case 'm': cfg->gd = 0.50f; cfg->gw = 1.00f; cfg->max_channels = 512; break;
+        case 'l': cfg->gd = 1.00f; cfg->gw = 1.00f; cfg->max_channels = 512; break;
+        case 'x': cfg->gd = 1.00f; cfg->gw = 1.50f; cfg->max_channels = 512; break;
+        default: return false;
+    }
+    cfg->c3k = type == 'm' || type == 'l' || type == 'x';   // model.cpp:160-163
+    return true;
+}
+
+IHostMemory* buildEngineYolo11Det(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolo11Config& cfg) {
+    if (cfg.task != 0) return nullptr;   // seg / pose / obb / cls: not yet
+    WeightMap wm = loadWeights(wts);
+    INetworkDefinition* net = builder->createNetworkV2(1U << static_cast<uint32_t>(NetworkDefinitionCreationFlag::kEXPLICIT_BATCH));
+    IHostMemory* plan = nullptr;
+    {
+        Ctx c{net, wm, {}};
+        const float gd = cfg.gd, gw = cfg.gw;
+        const int mc = cfg.max_channels, B = cfg.batch, nc = cfg.num_class;
+        const bool c3k = cfg.c3k;
+        auto W = [&](int x) { return get_width(x, gw, mc); };
+
+        ITensor* data = net->addInput("images", DataType::kFLOAT, Dims4{B, 3, cfg.input_h, cfg.input_w});
+        assert(data);
+        // ---- backbone (model.cpp:156-199)
+        ITensor* conv0 = convBnSiLU(c, *data, W(64), 3, 2, "model.0");
+        ITensor* conv1 = convBnSiLU(c, *conv0, W(128), 3, 2, "model.1");
+        ITensor* conv2 = C3K2(c, *conv1, W(256), get_depth(2, gd), c3k, true, 0.25f, "model.2");
+        ITensor* conv3 = convBnSiLU(c, *conv2, W(256), 3, 2, "model.3");
+        ITensor* conv4 = C3K2(c, *conv3, W(512), get_depth(2, gd), c3k, true, 0.25f, "model.4");
+        ITensor* conv5 = convBnSiLU(c, *conv4, W(512), 3, 2, "model.5");
+        ITensor* conv6 = C3K2(c, *conv5, W(512), get_depth(2, gd), true, true, 0.5f, "model.6");
+        ITensor* conv7 = convBnSiLU(c, *conv6, W(1024), 3, 2, "model.7");
+        ITensor* conv8 = C3K2(c, *conv7, W(1024), get_depth(2, gd), true, true, 0.5f, "model.8");
+        ITensor* conv9 = SPPF(c, *conv8, W(1024), W(1024), 5, "model.9");
+        ITensor* conv10 = C2PSA(c, *conv9, W(1024), W(1024), get_depth(2, gd), 0.5f, "model.10");
+        // ---- neck (model.cpp:203-254)
+        ITensor* conv13 = C3K2(c, *cat2(c, upsample2x(c, *conv10), conv6), W(512), get_depth(2, gd), c3k, true, 0.5f, "model.13");
+        ITensor* conv16 = C3K2(c, *cat2(c, upsample2x(c, *conv13), conv4), W(256), get_depth(2, gd), c3k, true, 0.5f, "model.16");
+        ITensor* conv17 = convBnSiLU(c, *conv16, W(256), 3, 2, "model.17");
+        ITensor* conv19 = C3K2(c, *cat2(c, conv17, conv13), W(512), get_depth(2, gd), c3k, true, 0.5f, "model.19");
+        ITensor* conv20 = convBnSiLU(c, *conv19, W(512), 3, 2, "model.20");
+        ITensor* conv22 = C3K2(c, *cat2(c, conv20, conv10), W(1024), get_depth(2, gd), true, true, 0.5f, "model.22");
+
+        // ---- detect head (model.cpp:259-334): per level a 64-channel box branch and a DWConv class branch
+        const int c2 = std::max(std::max(16, W(256) / 4), 16 * 4);
+        const int c3 = std::max(W(256), std::min(nc, 100));
+        ITensor* feats[3] = {conv16, conv19, conv22};
+        const int feat_w[3] = {W(256), W(512), W(1024)};
+        std::vector<ITensor*> cats;
+        for (int lv = 0; lv < 3; ++lv) {
+            const std::string s = "model.23.cv2." + std::to_string(lv), t = "model.23.cv3." + std::to_string(lv);
+            ITensor* b = convBnSiLU(c, *feats[lv], c2, 3, 1, s + ".0");
+            b = convBnSiLU(c, *b, c2, 3, 1, s + ".1");
+            auto* box = net->addConvolutionNd(*b, 64, DimsHW{1, 1}, need(wm, s + ".2.weight"), need(wm, s + ".2.bias"));
+            box->setStrideNd(DimsHW{1, 1});
+            box->setPaddingNd(DimsHW{0, 0});
+            ITensor* k = DWConv(c, *feats[lv], feat_w[lv], 3, 1, t + ".0.0");
+            k = convBnSiLU(c, *k, c3, 1, 1, t + ".0.1");
+            k = DWConv(c, *k, c3, 3, 1, t + ".1.0");
+            k = convBnSiLU(c, *k, c3, 1, 1, t + ".1.1");
+            auto* cls = net->addConvolutionNd(*k, nc, DimsHW{1, 1}, need(wm, t + ".2.weight"), need(wm, t + ".2.bias"));
+            cls->setStrideNd(DimsHW{1, 1});
+            cls->setPaddingNd(DimsHW{0, 0});
+            cats.push_back(cat2(c, box->getOutput(0), cls->getOutput(0)));
+        }
+        // ---- detect tail (model.cpp:336-390): strides from the backbone maps, flatten, split, DFL, re-join along axis 1
+        std::vector<int> strides;
+        for (ITensor* t : {conv3, conv5, conv7}) strides.push_back(cfg.input_h / (int)t->getDimensions().d[2]);
+        std::vector<ITensor*> dets;
+        for (int lv = 0; lv < 3; ++lv) {
+            const int grid = (cfg.input_h / strides[lv]) * (cfg.input_w / strides[lv]);
+            auto* flat = net->addShuffle(*cats[lv]);
+            flat->setReshapeDimensions(Dims3{B, 64 + nc, grid});
+            ITensor* boxPart = net->addSlice(*flat->getOutput(0), Dims3{0, 0, 0}, Dims3{B, 64, grid}, Dims3{1, 1, 1})->getOutput(0);
+            ITensor* clsPart = net->addSlice(*flat->getOutput(0), Dims3{0, 64, 0}, Dims3{B, nc, grid}, Dims3{1, 1, 1})->getOutput(0);
+            ITensor* dfl = DFL(c, *boxPart, B, grid, "model.23.dfl.conv.weight");
+            ITensor* v[] = {dfl, clsPart};
+            auto* cat = net->addConcatenation(v, 2);
+            cat->setAxis(1);
+            dets.push_back(cat->getOutput(0));
+        }
+        if (cfg.mark_heads)
+            for (size_t i = 0; i < dets.size(); ++i) {
+                dets[i]->setName(("head" + std::to_string(i)).c_str());
+                net->markOutput(*dets[i]);
+            }
+        IPluginV2Layer* yolo = addYoLoLayer(c, dets, strides, cfg);
+        assert(yolo);
+        yolo->getOutput(0)->setName("output");
+        net->markOutput(*yolo->getOutput(0));
+
+        config->setMaxWorkspaceSize(16 * (1 << 20));
+        if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
+        plan = builder->buildSerializedNetwork(*net, *config);
+    }
+    delete net;
+    freeWeights(wm);
+    return plan;
+}
+
+}  // namespace trtx_host

@@ -174,6 +174,119 @@ def yolov8n_state(seed=0, num_class=80):
     return OrderedDict((k, v.numpy()) for k, v in sd.items())
 
 
+YOLO11_SCALES = {  # yolo11_det.cpp:120-150: gd, gw, max_channels; m / l / x use C3k blocks (model.cpp:160-163)
+    "n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)}
+
+
+def yolo11_state(scale="n", seed=0, num_class=80):
+    """Seeded synthetic weights of YOLO11{n,s,m,l,x}-det under the reference's `.wts` key names (ultralytics state_dict keys, as
+    read by yolo11/src/block.cpp / model.cpp:138-400): OrderedDict name -> fp32 array.  He-scaled convolutions with near-identity
+    BatchNorm statistics (the yolov8n_state recipe); the class head has gain 800 and bias -8 so that a few hundred cells per image
+    pass the 0.1 confidence gate."""
+    import math
+    from collections import OrderedDict
+
+    import torch
+    gd, gw, mc = YOLO11_SCALES[scale]
+    c3k = scale in "mlx"
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+
+    def W(x):
+        return int(math.ceil(min(x, mc) * gw / 8)) * 8
+
+    def D(x):
+        if x == 1:
+            return 1
+        r = round(x * gd)   # Python's round: half to even, as get_depth
+        return max(int(r), 1)
+
+    def conv(name, cout, cin, k, gain=2.0):
+        sd[name + ".weight"] = (randn(cout, cin, k, k) * math.sqrt(gain / (cin * k * k))).float()
+
+    def cb(name, cout, cin, k, groups=1, gain=2.0):  # Conv + BatchNorm (+ SiLU)
+        conv(name + ".conv", cout, cin // groups, k, gain)
+        sd[name + ".bn.weight"] = (0.9 + 0.2 * rand(cout)).float()
+        sd[name + ".bn.bias"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_mean"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_var"] = (0.8 + 0.4 * rand(cout)).float()
+        sd[name + ".bn.num_batches_tracked"] = torch.zeros(1)
+
+    def bottleneck(name, c1, c2, e):
+        c_ = int(c2 * e)
+        cb(name + ".cv1", c_, c1, 3)
+        cb(name + ".cv2", c2, c_, 3)
+
+    def c3k_block(name, c1, c2, n, e=0.5):
+        c_ = int(c2 * e)
+        cb(name + ".cv1", c_, c1, 1)
+        cb(name + ".cv2", c_, c1, 1)
+        for i in range(n):
+            bottleneck(f"{name}.m.{i}", c_, c_, 1.0)
+        cb(name + ".cv3", c2, 2 * c_, 1)
+
+    def c3k2(name, c1, c2, n, use_c3k, e):
+        c_ = int(c2 * e)
+        cb(name + ".cv1", 2 * c_, c1, 1)
+        for i in range(n):
+            if use_c3k:
+                c3k_block(f"{name}.m.{i}", c_, c_, 2)
+            else:
+                bottleneck(f"{name}.m.{i}", c_, c_, 0.5)
+        cb(name + ".cv2", c2, (2 + n) * c_, 1)
+
+    def c2psa(name, c1, c2, n):
+        c = int(c1 * 0.5)
+        cb(name + ".cv1", 2 * c, c1, 1)
+        heads = c // 64
+        kd = (c // heads) // 2
+        for i in range(n):
+            m = f"{name}.m.{i}"
+            cb(m + ".attn.qkv", c + 2 * kd * heads, c, 1)
+            cb(m + ".attn.proj", c, c, 1, gain=1.0)
+            cb(m + ".attn.pe", c, c, 3, groups=c, gain=1.0)
+            cb(m + ".ffn.0", 2 * c, c, 1)
+            cb(m + ".ffn.1", c, 2 * c, 1, gain=1.0)
+        cb(name + ".cv2", c2, 2 * c, 1)
+
+    cb("model.0", W(64), 3, 3)
+    cb("model.1", W(128), W(64), 3)
+    c3k2("model.2", W(128), W(256), D(2), c3k, 0.25)
+    cb("model.3", W(256), W(256), 3)
+    c3k2("model.4", W(256), W(512), D(2), c3k, 0.25)
+    cb("model.5", W(512), W(512), 3)
+    c3k2("model.6", W(512), W(512), D(2), True, 0.5)
+    cb("model.7", W(1024), W(512), 3)
+    c3k2("model.8", W(1024), W(1024), D(2), True, 0.5)
+    cb("model.9.cv1", W(1024) // 2, W(1024), 1)
+    cb("model.9.cv2", W(1024), 2 * W(1024), 1)
+    c2psa("model.10", W(1024), W(1024), D(2))
+    c3k2("model.13", W(1024) + W(512), W(512), D(2), c3k, 0.5)
+    c3k2("model.16", W(512) + W(512), W(256), D(2), c3k, 0.5)
+    cb("model.17", W(256), W(256), 3)
+    c3k2("model.19", W(256) + W(512), W(512), D(2), c3k, 0.5)
+    cb("model.20", W(512), W(512), 3)
+    c3k2("model.22", W(512) + W(1024), W(1024), D(2), True, 0.5)
+    c2 = max(16, W(256) // 4, 64)
+    c3 = max(W(256), min(num_class, 100))
+    for lv, cin in enumerate((W(256), W(512), W(1024))):
+        cb(f"model.23.cv2.{lv}.0", c2, cin, 3)
+        cb(f"model.23.cv2.{lv}.1", c2, c2, 3)
+        conv(f"model.23.cv2.{lv}.2", 64, c2, 1, gain=4.0)
+        sd[f"model.23.cv2.{lv}.2.bias"] = (1.0 + 0.1 * randn(64)).float()
+        cb(f"model.23.cv3.{lv}.0.0", cin, cin, 3, groups=cin, gain=1.0)
+        cb(f"model.23.cv3.{lv}.0.1", c3, cin, 1)
+        cb(f"model.23.cv3.{lv}.1.0", c3, c3, 3, groups=c3, gain=1.0)
+        cb(f"model.23.cv3.{lv}.1.1", c3, c3, 1)
+        conv(f"model.23.cv3.{lv}.2", num_class, c3, 1, gain=800.0)
+        sd[f"model.23.cv3.{lv}.2.bias"] = (-8.0 + 0.1 * randn(num_class)).float()
+        if lv == 0:
+            sd["model.23.dfl.conv.weight"] = torch.arange(16.0).reshape(1, 16, 1, 1)
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
+
+
 class _Draw:
     """Seeded tensor provider of the synthetic-weight generators below: the draw order and distributions are those of the test-suite's
     generator (oracle/models_torch.py run in init mode), so both write the same file - tests/test_runtime_cpu.py asserts it per model.
