@@ -82,6 +82,24 @@ int32_t trtx_yolo_head_decode_nhwc(const void* const* heads, const int* ld, int 
 int32_t trtx_yolo_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes,
                                    int net_h, int net_w, const int* strides, const float* dfl_weights, int max_out,
                                    float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Fused DFL + YOLO11 seg / pose / obb decode on the NHWC fp16 head and branch tensors of an explicit-batch engine: what the engine
+ * uses instead of the flatten / slice / DFL chain, the cv4 branch's reshape and the [dfl, classes, branch] concat of
+ * yolo11/src/model.cpp:595-756 (seg), 960-1060 (pose), 1265-1358 (obb) followed by YoloLayerPlugin::enqueue (yololayer.cu:178-279).
+ * heads[l]: [batch][cells_l][ld[l]] as for trtx_yolo_head_decode_nhwc, any classes >= 1 (ld[l] >= 64 + classes);
+ * branches[l]: [batch][cells_l][branch_ld[l]], channels [0, extra) = the cv4 convolution's output (32 mask coefficients,
+ * 3 * n_kpt keypoint values or 1 angle logit).  Exactly one of is_seg / is_pose / is_obb.  Output format, candidate order and
+ * branch arithmetic are those of trtx_yolo_decode_ex; workspace: trtx_yolo_head_decode_workspace.
+ */
+int32_t trtx_yolo_task_head_decode_nhwc(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld,
+                                        int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                                        const float* dfl_weights, int max_out, int is_seg, int is_pose, int is_obb, int n_kpt,
+                                        float kpt_conf, float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* The same on the NHWC fp32 head and branch tensors of an fp32 engine (yolo11/src/model.cpp:785-796 without kFP16): ld in floats. */
+int32_t trtx_yolo_task_head_decode_nhwc_f32(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld,
+                                            int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                                            const float* dfl_weights, int max_out, int is_seg, int is_pose, int is_obb, int n_kpt,
+                                            float kpt_conf, float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 
 /*
  * Class-aware greedy NMS over the decode buffer.  Replaces host batch_nms()/nms()

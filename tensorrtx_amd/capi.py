@@ -131,6 +131,48 @@ def yolo_decode_ex(inputs, classes, net_h, net_w, strides, max_out=1000, nk=17, 
     return out
 
 
+def _head_table(tensors):
+    n = len(tensors)
+    return (ctypes.c_void_p * n)(*[x.data_ptr() for x in tensors]), (ctypes.c_int * n)(*[x.shape[-1] for x in tensors])
+
+
+def yolo_head_decode_nhwc(heads, classes, net_h, net_w, strides, dfl_w, max_out=1000):
+    """The fused det head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32): trtx_yolo_head_decode_nhwc{,_f32}."""
+    import torch
+    L = lib()
+    B, n = heads[0].shape[0], len(heads)
+    hp, hl = _head_table(heads)
+    st = (ctypes.c_int * n)(*strides)
+    L.trtx_yolo_head_decode_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolo_head_decode_workspace(B, net_h, net_w, st, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=heads[0].device)
+    out = torch.zeros(B, 1 + max_out * DET_FLOATS, dtype=torch.float32, device=heads[0].device)
+    fn = L.trtx_yolo_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolo_head_decode_nhwc
+    check(fn(hp, hl, n, B, classes, net_h, net_w, st, _p(dfl_w), max_out, _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()),
+          "trtx_yolo_head_decode_nhwc")
+    return out
+
+
+def yolo_task_head_decode_nhwc(heads, branches, classes, net_h, net_w, strides, dfl_w, max_out=1000, nk=17, kpt_conf=0.0, seg=False,
+                               pose=False, obb=False):
+    """The fused YOLO11 task head (trtx_yolo_task_head_decode_nhwc{,_f32}): NHWC head tensors [B, gh, gw, ld] and branch tensors
+    [B, gh, gw, branch_ld], fp16 or fp32; output rows as yolo_decode_ex."""
+    import torch
+    L = lib()
+    B, n = heads[0].shape[0], len(heads)
+    hp, hl = _head_table(heads)
+    bp, bl = _head_table(branches)
+    st = (ctypes.c_int * n)(*strides)
+    L.trtx_yolo_head_decode_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolo_head_decode_workspace(B, net_h, net_w, st, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=heads[0].device)
+    out = torch.zeros(B, 1 + max_out * DET_FLOATS, dtype=torch.float32, device=heads[0].device)
+    fn = L.trtx_yolo_task_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolo_task_head_decode_nhwc
+    check(fn(hp, hl, bp, bl, n, B, classes, net_h, net_w, st, _p(dfl_w), max_out, int(seg), int(pose), int(obb), nk, ctypes.c_float(kpt_conf),
+             _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolo_task_head_decode_nhwc")
+    return out
+
+
 def yolo_nms_obb(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
     """nms_obb replacement (yolov8/src/postprocess.cpp:303-393).  keep_det: [B, max_out, 7] = cx, cy, w, h, conf, cls, angle."""
     import torch

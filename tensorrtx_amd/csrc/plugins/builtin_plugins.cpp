@@ -486,6 +486,11 @@ bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out) {
     out->max_out = y->max_out;
     out->strides = y->strides;
     out->det_only = !(y->seg || y->pose || y->obb);
+    out->seg = y->seg;
+    out->pose = y->pose;
+    out->obb = y->obb;
+    out->nk = y->n_kpt;
+    out->kpt_conf = y->kpt_conf;
     return true;
 }
 

@@ -525,3 +525,357 @@ extern "C" int32_t trtx_yolo_head_decode_nhwc_f32(const void* const* heads, cons
                                                   size_t workspace_bytes, hipStream_t stream) {
     return head_decode(heads, ld, 4, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
 }
+
+
+// ---------------------------------------------------------------------------------------------------------
+// Fused task head (YOLO11 seg / pose / obb, explicit batch): the det head's score pass with a masked class tail, and an emit pass
+// that also reads the cell's task branch from its own NHWC tensor - the output of the cv4 1x1 convolution (yolo11/src/model.cpp:474-507).
+// It replaces, per level, the (64 + classes)-channel head converted to fp32 LINEAR, the slices, the DFL chain, the branch's own
+// conversion, the concat scatters and then the plugin's two passes (yololayer.cu:178-279).  The det kernels above stay as they are:
+// their code objects are pinned by the det plans, and the plugin's by tests/test_ref_pinning.py.
+namespace {
+
+struct BranchTable {
+    const void* in[kMaxLevels];  // device pointers, [batch][cells_l][ld[l]]: channels [0, extra) of the cell's branch
+    int ld[kMaxLevels];
+    int vec;                      // every ld and base allows 16-byte loads
+};
+
+// Pass 1 of the task head: yolo_head_score_kernel's DFL and class scan, with `classes` any count >= 1.  The last (classes % 8) logits
+// are read one by one, so the NHWC padding channels behind them never reach the argmax (nor a load past the tensor's last pixel).
+// With classes % 8 == 0 the arithmetic is the det kernel's, operation for operation, so boxes, confidences and classes are the same bits.
+template <typename T>
+__global__ __launch_bounds__(256) void yolo_task_score_kernel(HeadTable t, int classes, int total_cells,
+                                                              const float* __restrict__ dfl_w,
+                                                              float* __restrict__ score, int* __restrict__ cls_out,
+                                                              float4* __restrict__ boxes,
+                                                              int* __restrict__ chunk_cnt, int n_chunks) {
+    __shared__ int s_list[256];
+    __shared__ int s_n, s_keep;
+    const int b = blockIdx.y;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int full = classes & ~7;   // classes read eight at a time; [full, classes) one at a time
+    if (threadIdx.x == 0) {
+        s_n = 0;
+        s_keep = 0;
+    }
+    __syncthreads();
+    auto cell_ptr = [&](int gg) {
+        int l = 0;
+#pragma unroll
+        for (int i = 1; i < kMaxLevels; ++i)
+            if (i < t.n_levels && gg >= t.cell_off[i]) l = i;
+        const int cells = t.cell_off[l + 1] - t.cell_off[l];
+        return static_cast<const T*>(t.in[l]) + ((size_t)b * cells + (gg - t.cell_off[l])) * t.ld[l];
+    };
+    // phase 1, every cell: some raw logit > -2.3 (sigmoid >= 0.1 needs >= -2.1972); read by the wave, one piece of eight per lane
+    s_list[threadIdx.x] = 0;
+    __syncthreads();
+    {
+        const int wave0 = threadIdx.x & ~63, lane = threadIdx.x & 63;
+        const int pieces = (classes + 7) >> 3;
+        const int g0 = blockIdx.x * 256 + wave0;
+        int cells_here = total_cells - g0;
+        cells_here = cells_here > 64 ? 64 : cells_here;
+        const int n = cells_here * pieces;
+        for (int j = lane; j < n; j += 64) {
+            const int c = j / pieces, q = j - c * pieces;
+            const T* p = cell_ptr(g0 + c) + 64 + q * 8;
+            float m;
+            if (q * 8 < full) {
+                float v[8];
+                load8(p, v);
+                m = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+            } else {
+                m = -INFINITY;
+                for (int i = 0; i < classes - full; ++i) m = fmaxf(m, (float)p[i]);
+            }
+            if (m > -2.3f) s_list[wave0 + c] = 1;
+        }
+    }
+    __syncthreads();
+    bool maybe = false;
+    if (g < total_cells) {
+        maybe = s_list[threadIdx.x] != 0;
+        if (!maybe) {
+            const size_t o = (size_t)b * total_cells + g;
+            score[o] = -1.0f;
+            cls_out[o] = 0;
+        }
+    }
+    __syncthreads();
+    {
+        const unsigned long long m = __ballot(maybe);
+        int base = 0;
+        if ((threadIdx.x & 63) == 0 && m) base = atomicAdd(&s_n, __popcll(m));
+        base = __shfl(base, 0);
+        if (maybe) s_list[base + __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull))] = threadIdx.x;
+    }
+    __syncthreads();
+    // phase 2, possible survivors only: DFL softmax . w per side, sigmoid of every class, strict '>' argmax (as the det kernel)
+    int kept = 0;
+    for (int k = threadIdx.x; k < s_n; k += 256) {
+        const int gg = blockIdx.x * 256 + s_list[k];
+        const T* cell = cell_ptr(gg);
+        float w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = dfl_w[i];
+        float side[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            float lo[8], hi[8], x[16];
+            load8(cell + s * 16, lo);
+            load8(cell + s * 16 + 8, hi);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                x[i] = lo[i];
+                x[8 + i] = hi[i];
+            }
+            float mx = x[0];
+#pragma unroll
+            for (int i = 1; i < 16; ++i) mx = fmaxf(mx, x[i]);
+            float sum = 0.f, acc = 0.f;
+            if constexpr (sizeof(T) == 4) {
+                float ex[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    ex[i] = expf(x[i] - mx);
+                    sum += ex[i];
+                }
+                const float inv = 1.0f / sum;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc = fmaf(ex[i] * inv, w[i], acc);
+                side[s] = acc;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float ex = expf(x[i] - mx);
+                    sum += ex;
+                    acc = fmaf(ex, w[i], acc);
+                }
+                side[s] = acc / sum;
+            }
+        }
+        float best = 0.0f;
+        int bcls = 0;
+        const T* cl = cell + 64;
+        for (int c0 = 0; c0 < full; c0 += 8) {
+            float v[8];
+            load8(cl + c0, v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float pr = logist(v[i]);
+                if (pr > best) {
+                    best = pr;
+                    bcls = c0 + i;
+                }
+            }
+        }
+        for (int c = full; c < classes; ++c) {
+            const float pr = logist((float)cl[c]);
+            if (pr > best) {
+                best = pr;
+                bcls = c;
+            }
+        }
+        const bool keep = !((double)best < 0.1);
+        const size_t o = (size_t)b * total_cells + gg;
+        score[o] = keep ? best : -1.0f;
+        cls_out[o] = bcls;
+        boxes[o] = make_float4(side[0], side[1], side[2], side[3]);
+        kept += keep ? 1 : 0;
+    }
+    if (kept) atomicAdd(&s_keep, kept);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_keep) atomicAdd(&chunk_cnt[b * n_chunks + (blockIdx.x * 256) / kChunk], s_keep);
+}
+
+// The seg / pose / obb fields of one Detection record (yololayer.cu:222-279) from the cell's branch channels `br` (contiguous; `vec`:
+// 16-byte aligned).  The arithmetic is the plugin's (yolo_emit_kernel above): keypoints as (v * 2.0 + col) * stride in double rounded
+// once, a sigmoid confidence and the -1 triple below kpt_conf or outside the box; obb rotates the centre by (sigmoid(a) - 0.25) * pi.
+template <typename T>
+__device__ __forceinline__ void task_branch(float* det, const T* br, bool vec, const YoloBranches& b, float4 d, int row, int col, int istride) {
+    if (b.seg) {
+        if (vec) {
+#pragma unroll
+            for (int k = 0; k < 32; k += 8) {
+                float v[8];
+                load8(br + k, v);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) det[6 + k + i] = v[i];
+            }
+        } else {
+            for (int k = 0; k < 32; ++k) det[6 + k] = (float)br[k];
+        }
+    }
+    if (b.pose) {
+        for (int k = 0; k < b.nk; ++k) {
+            const float kconf = 1.0f / (1.0f + expf(-(float)br[k * 3 + 2]));
+            const float kx = (float)(((float)br[k * 3] * 2.0 + col) * istride);
+            const float ky = (float)(((float)br[k * 3 + 1] * 2.0 + row) * istride);
+            const bool inside = kx >= det[0] && kx <= det[2] && ky >= det[1] && ky <= det[3];
+            float* o = det + 38 + k * 3;
+            if (kconf < b.kpt_conf || !inside) {
+                o[0] = -1;
+                o[1] = -1;
+                o[2] = -1;
+            } else {
+                o[0] = kx;
+                o[1] = ky;
+                o[2] = kconf;
+            }
+        }
+    }
+    if (b.obb) {
+        const double pi = 3.14159265358979323846;
+        const float ain = (float)br[0];
+        const double angle = ((1.0f / (1.0f + expf(-ain))) - 0.25f) * pi;
+        const double cos1 = cos(angle), sin1 = sin(angle);
+        const float xf = (d.z - d.x) / 2, yf = (d.w - d.y) / 2;
+        const double x = xf * cos1 - yf * sin1;
+        const double y = xf * sin1 + yf * cos1;
+        det[0] = (float)((col + 0.5f + x) * istride);
+        det[1] = (float)((row + 0.5f + y) * istride);
+        det[2] = (d.x + d.z) * istride;
+        det[3] = (d.y + d.w) * istride;
+        det[trtx::kYoloDetFloats - 1] = (float)angle;
+    }
+}
+
+// Pass 2 of the task head: yolo_emit_kernel's ordered compaction and box / conf / class record, then the branch of the cell.
+template <typename T>
+__global__ __launch_bounds__(kChunk) void yolo_task_emit_kernel(LevelTable t, BranchTable bt, int total_cells,
+                                                                const float* __restrict__ score,
+                                                                const int* __restrict__ cls_in,
+                                                                const int* __restrict__ chunk_cnt, int n_chunks,
+                                                                int max_out, int out_elem, float* __restrict__ output,
+                                                                const float4* __restrict__ boxes, YoloBranches br) {
+    const int b = blockIdx.y;
+    const int chunk = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    constexpr int kWaves = kChunk / 64;
+    __shared__ int s_wave[kWaves];
+    __shared__ int s_base;
+    if (wave == 0) {
+        int acc = 0;
+        for (int j = lane; j < chunk; j += 64) acc += chunk_cnt[b * n_chunks + j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+        if (lane == 0) s_base = acc;
+    }
+    const int g = chunk * kChunk + threadIdx.x;
+    float sc = -1.0f;
+    if (g < total_cells) sc = score[(size_t)b * total_cells + g];
+    const bool keep = sc >= 0.0f;
+    const unsigned long long m = __ballot(keep);
+    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int before = s_base;
+#pragma unroll
+    for (int wv = 0; wv < kWaves; ++wv)
+        if (wv < wave) before += s_wave[wv];
+    const int slot = before + in_wave;
+    float* out = output + (size_t)b * out_elem;
+    if (keep && slot < max_out) {
+        const int l = find_level(t, g);
+        const int cells = t.cell_off[l + 1] - t.cell_off[l];
+        const int e = g - t.cell_off[l];
+        const int gw = t.grid_w[l];
+        const float stride = (float)t.stride[l];
+        const float4 d = boxes[(size_t)b * total_cells + g];
+        const int row = e / gw, col = e - row * gw;
+        float* det = out + 1 + (size_t)slot * trtx::kYoloDetFloats;
+        det[0] = (col + 0.5f - d.x) * stride;
+        det[1] = (row + 0.5f - d.y) * stride;
+        det[2] = (col + 0.5f + d.z) * stride;
+        det[3] = (row + 0.5f + d.w) * stride;
+        det[4] = sc;
+        det[5] = (float)cls_in[(size_t)b * total_cells + g];
+        const T* bp = static_cast<const T*>(bt.in[l]) + ((size_t)b * cells + e) * bt.ld[l];
+        task_branch(det, bp, bt.vec != 0, br, d, row, col, t.stride[l]);
+    }
+    if (chunk == n_chunks - 1 && threadIdx.x == kChunk - 1) {
+        int total = before + in_wave + (keep ? 1 : 0);
+        out[0] = (float)(total < max_out ? total : max_out);
+    }
+}
+
+}  // namespace
+
+static int32_t task_head_decode(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld, int elem_bytes,
+                                int n_levels, int batch, int classes, int net_h, int net_w, const int* strides, const float* dfl_weights,
+                                int max_out, int is_seg, int is_pose, int is_obb, int n_kpt, float kpt_conf, float* output, void* workspace,
+                                size_t workspace_bytes, hipStream_t stream) {
+    if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !heads || !ld || !branches || !branch_ld ||
+        !dfl_weights || !output || !workspace || (is_seg != 0) + (is_pose != 0) + (is_obb != 0) != 1 || (is_pose && (n_kpt < 1 || n_kpt > 17)))
+        return TRTX_ERR_INVALID;
+    if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
+    const int extra = is_seg ? 32 : (is_pose ? 3 * n_kpt : 1);
+    const int vec_elems = 16 / elem_bytes;
+    HeadTable h{};
+    LevelTable t{};
+    BranchTable bt{};
+    h.n_levels = t.n_levels = n_levels;
+    bt.vec = 1;
+    int off = 0;
+    for (int i = 0; i < n_levels; ++i) {
+        const int gh = net_h / strides[i], gw = net_w / strides[i];
+        // the head's 16-byte loads read channels up to 64 + (classes & ~7): a stride of at least 64 + classes, a multiple of 16 bytes
+        if (ld[i] % vec_elems || ld[i] < 64 + classes || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
+        if (!branches[i] || branch_ld[i] < extra) return TRTX_ERR_INVALID;
+        if (branch_ld[i] % vec_elems || (reinterpret_cast<uintptr_t>(branches[i]) & 15)) bt.vec = 0;
+        h.in[i] = heads[i];
+        h.ld[i] = ld[i];
+        bt.in[i] = branches[i];
+        bt.ld[i] = branch_ld[i];
+        h.cell_off[i] = t.cell_off[i] = off;
+        t.grid_w[i] = gw;
+        t.stride[i] = strides[i];
+        off += gh * gw;
+    }
+    for (int i = n_levels; i <= kMaxLevels; ++i) h.cell_off[i] = t.cell_off[i] = off;
+    const int total_cells = off;
+    const int n_chunks = (total_cells + kChunk - 1) / kChunk;
+    char* ws = static_cast<char*>(workspace);
+    float* score = reinterpret_cast<float*>(ws);
+    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float), 256);
+    int* cls = reinterpret_cast<int*>(ws);
+    ws += trtx::align_up((size_t)batch * total_cells * sizeof(int), 256);
+    float4* boxes = reinterpret_cast<float4*>(ws);
+    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float4), 256);
+    int* chunk_cnt = reinterpret_cast<int*>(ws);
+    if (hipMemsetAsync(chunk_cnt, 0, (size_t)batch * n_chunks * sizeof(int), stream) != hipSuccess) return TRTX_ERR_HIP;
+    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
+    const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, is_pose ? n_kpt : 0, kpt_conf};
+    const dim3 sgrid((total_cells + 255) / 256, batch), egrid(n_chunks, batch);
+    if (elem_bytes == 2) {
+        hipLaunchKernelGGL(yolo_task_score_kernel<_Float16>, sgrid, dim3(256), 0, stream, h, classes, total_cells, dfl_weights, score, cls, boxes,
+                           chunk_cnt, n_chunks);
+        hipLaunchKernelGGL(yolo_task_emit_kernel<_Float16>, egrid, dim3(kChunk), 0, stream, t, bt, total_cells, score, cls, chunk_cnt, n_chunks,
+                           max_out, out_elem, output, (const float4*)boxes, br);
+    } else {
+        hipLaunchKernelGGL(yolo_task_score_kernel<float>, sgrid, dim3(256), 0, stream, h, classes, total_cells, dfl_weights, score, cls, boxes,
+                           chunk_cnt, n_chunks);
+        hipLaunchKernelGGL(yolo_task_emit_kernel<float>, egrid, dim3(kChunk), 0, stream, t, bt, total_cells, score, cls, chunk_cnt, n_chunks,
+                           max_out, out_elem, output, (const float4*)boxes, br);
+    }
+    return trtx::check_launch("trtx_yolo_task_head_decode_nhwc");
+}
+
+extern "C" int32_t trtx_yolo_task_head_decode_nhwc(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld,
+                                                   int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                                                   const float* dfl_weights, int max_out, int is_seg, int is_pose, int is_obb, int n_kpt,
+                                                   float kpt_conf, float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return task_head_decode(heads, ld, branches, branch_ld, 2, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, is_seg,
+                            is_pose, is_obb, n_kpt, kpt_conf, output, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_yolo_task_head_decode_nhwc_f32(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld,
+                                                       int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                                                       const float* dfl_weights, int max_out, int is_seg, int is_pose, int is_obb, int n_kpt,
+                                                       float kpt_conf, float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return task_head_decode(heads, ld, branches, branch_ld, 4, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, is_seg,
+                            is_pose, is_obb, n_kpt, kpt_conf, output, workspace, workspace_bytes, stream);
+}

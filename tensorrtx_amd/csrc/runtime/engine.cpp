@@ -151,7 +151,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
         int32_t st = TRTX_OK;
-        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_ROI_ALIGN);
+        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
@@ -357,6 +357,23 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 }
                 st = (t0.dtype == DT_F32 ? trtx_yolo_head_decode_nhwc_f32 : trtx_yolo_head_decode_nhwc)(
                         heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
+                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+                break;
+            }
+            case OP_YOLO_TASK_HEAD: {
+                const int nl = op.i[4];
+                const void* heads[4];
+                const void* branches[4];
+                int lds[4], blds[4];
+                for (int k = 0; k < nl; ++k) {
+                    heads[k] = R.ptr(op.in[k]);
+                    lds[k] = plan.tensors[op.in[k]].ld;
+                    branches[k] = R.ptr(op.extra_in[k]);
+                    blds[k] = plan.tensors[op.extra_in[k]].ld;
+                }
+                st = (t0.dtype == DT_F32 ? trtx_yolo_task_head_decode_nhwc_f32 : trtx_yolo_task_head_decode_nhwc)(
+                        heads, lds, branches, blds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5],
+                        reinterpret_cast<const float*>(W + op.w_off), op.i[3], op.i[9] == 1, op.i[9] == 2, op.i[9] == 3, op.i[10], op.f[0],
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
                 break;
             }

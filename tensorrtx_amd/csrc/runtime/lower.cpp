@@ -17,8 +17,9 @@ const char* op_kind_name(int k) {
     static const char* n[] = {"conv",     "deconv",    "pool",      "resize",     "ew_nhwc", "act_nhwc", "scale_nhwc",
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
-                              "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention"};
-    return (k >= 0 && k <= OP_ATTENTION) ? n[k] : "?";
+                              "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
+                              "yolo_task_head"};
+    return (k >= 0 && k <= OP_YOLO_TASK_HEAD) ? n[k] : "?";
 }
 
 namespace {
@@ -61,6 +62,7 @@ struct FusedConv {
 struct YoloHeadFuse {
     int plugin_layer = -1;
     std::vector<int> head_tensor;  // network tensor per level: CHW (64 + classes, gh, gw)
+    std::vector<int> branch_tensor;  // task head: network tensor per level, the cv4 convolution's output (B, extra, gh, gw)
     int dfl_conv_layer = -1;
     YoloLayerParams params;
 };
@@ -378,7 +380,11 @@ struct Lowerer {
         const int lc = producer(t_in);
         if (lc < 0 || net.layers[lc].kind != L_CONCAT || net.layers[lc].inputs.size() != 2 || net.layers[lc].axis != e) return false;
         if (!only_used_by(t_in, {plugin_layer})) return false;
-        const int ta = net.layers[lc].inputs[0], tb = net.layers[lc].inputs[1];
+        return match_dfl_classes(lc, net.layers[lc].inputs[0], net.layers[lc].inputs[1], B, classes, head, conv_layer, used);
+    }
+    // the two first inputs of the head concat `lc`: ta = DFL(slice [0, 64) of the flattened head), tb = slice [64, 64 + classes) of it
+    bool match_dfl_classes(int lc, int ta, int tb, int64_t B, int classes, int* head, int* conv_layer, std::vector<int>* used) {
+        const int e = net.explicit_batch ? 1 : 0;
         // box branch
         const int lsh2 = producer(ta);
         if (lsh2 < 0 || net.layers[lsh2].kind != L_SHUFFLE || !only_used_by(ta, {lc})) return false;
@@ -433,6 +439,60 @@ struct Lowerer {
         *conv_layer = lconv;
         for (int l : {lc, lsh2, lconv, lsm, lsh1, lsa, lsb, lflat}) used->push_back(l);
         return true;
+    }
+    // ---- YOLO11 seg / pose / obb tail (yolo11/src/model.cpp:595-756, 960-1060, 1265-1358), explicit batch only: each plugin input is the
+    // axis-1 concat of [DFL chain, class slice, the cv4 branch reshaped (B, extra, H, W) -> (B, extra, g)].  The branch convolution keeps
+    // its NHWC output, which the fused op reads next to the head (extra_in).
+    void analyse_yolo_task_head() {
+        if (!net.explicit_batch) return;
+        for (size_t li = 0; li < net.layers.size(); ++li) {
+            const LayerDef& l = net.layers[li];
+            if (l.kind != L_PLUGIN || l.outputs.size() != 1 || absorbed[li]) continue;
+            YoloHeadFuse f;
+            if (!builtin_yolo_params(l.plugin->v, &f.params)) continue;
+            const YoloLayerParams& pr = f.params;
+            if (pr.seg + pr.pose + pr.obb != 1 || pr.strides.size() != l.inputs.size() || l.inputs.size() > 4) continue;
+            if (pr.pose && (pr.nk < 1 || pr.nk > 17)) continue;
+            const int64_t extra = pr.seg ? 32 : (pr.pose ? 3 * pr.nk : 1);
+            std::vector<int> used;
+            bool ok = true;
+            for (size_t k = 0; ok && k < l.inputs.size(); ++k) {
+                const int t_in = l.inputs[k];
+                const int64_t B = net.tensors[t_in].dims.d[0];
+                const int lc = producer(t_in);
+                ok = lc >= 0 && net.layers[lc].kind == L_CONCAT && net.layers[lc].inputs.size() == 3 && net.layers[lc].axis == 1 &&
+                     only_used_by(t_in, {(int)li}) && B == net.tensors[l.inputs[0]].dims.d[0];
+                int head = -1, conv = -1;
+                ok = ok && match_dfl_classes(lc, net.layers[lc].inputs[0], net.layers[lc].inputs[1], B, pr.classes, &head, &conv, &used);
+                if (!ok) break;
+                const Dims& dh = net.tensors[head].dims;
+                ok = dh.d[2] == pr.net_h / pr.strides[k] && dh.d[3] == pr.net_w / pr.strides[k];
+                if (f.dfl_conv_layer >= 0 && net.layers[conv].w0 != net.layers[f.dfl_conv_layer].w0) ok = false;
+                // the branch: a reshape-only shuffle of a convolution's (B, extra, H, W) output to (B, extra, H * W)
+                const int tc = net.layers[lc].inputs[2];
+                const int lsh = producer(tc);
+                ok = ok && lsh >= 0 && net.layers[lsh].kind == L_SHUFFLE && only_used_by(tc, {lc});
+                if (!ok) break;
+                const LayerDef& sh = net.layers[lsh];
+                const int tb = sh.inputs[0];
+                const Dims &dx = net.tensors[tb].dims, &dc = net.tensors[tc].dims;
+                const int lb = producer(tb);
+                ok = ident(sh.perm1, 4) && ident(sh.perm2, 3) && dx.nb == 4 && dc.nb == 3 && dx.d[0] == B && dc.d[0] == B && dx.d[1] == extra &&
+                     dc.d[1] == extra && dx.d[2] == dh.d[2] && dx.d[3] == dh.d[3] && dc.d[2] == dx.d[2] * dx.d[3] && lb >= 0 &&
+                     net.layers[lb].kind == L_CONV && only_used_by(tb, {lsh});
+                for (int u : {lc, lsh}) used.push_back(u);
+                f.dfl_conv_layer = conv;
+                f.head_tensor.push_back(head);
+                f.branch_tensor.push_back(tb);
+            }
+            for (int u : used) ok = ok && !absorbed[u];
+            if (!ok) continue;
+            for (int u : used) absorbed[u] = true;
+            f.plugin_layer = (int)li;
+            absorbed[li] = true;
+            yolo_at[li] = (int)yolo_heads.size();
+            yolo_heads.push_back(f);
+        }
     }
     void analyse_yolo_head() {   // (fp16 and, since round 5, fp32 engines: the kernel reads either element type; implicit and explicit batch)
         for (size_t li = 0; li < net.layers.size(); ++li) {
@@ -571,10 +631,13 @@ struct Lowerer {
 
     bool emit_yolo_head(const YoloHeadFuse& f) {
         const LayerDef& l = net.layers[f.plugin_layer];
-        std::vector<int> ins;
+        std::vector<int> ins, branches;
         for (int t : f.head_tensor) ins.push_back(need_nhwc(t));
+        for (int t : f.branch_tensor) branches.push_back(need_nhwc(t));
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
-        POp& op = add_op(OP_YOLO_HEAD, l.name + " [fused DFL+decode]", ins, {out});
+        const bool task = !f.branch_tensor.empty();
+        POp& op = add_op(task ? OP_YOLO_TASK_HEAD : OP_YOLO_HEAD, l.name + (task ? " [fused DFL+task decode]" : " [fused DFL+decode]"), ins, {out});
+        op.extra_in = branches;
         op.src_layer = f.dfl_conv_layer;
         op.i[0] = f.params.classes;
         op.i[1] = f.params.net_h;
@@ -582,6 +645,12 @@ struct Lowerer {
         op.i[3] = f.params.max_out;
         op.i[4] = (int)f.params.strides.size();
         for (size_t k = 0; k < f.params.strides.size(); ++k) op.i[5 + k] = f.params.strides[k];
+        if (task) {
+            op.i[9] = f.params.seg ? 1 : (f.params.pose ? 2 : 3);
+            op.i[10] = f.params.pose ? f.params.nk : 0;
+            op.f[0] = f.params.kpt_conf;
+            for (int t : branches) op.bytes += (double)dtype_size(dt) * plan.tensors[t].dims.volume();
+        }
         // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
         if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
         op.ws_bytes = trtx_yolo_head_decode_workspace(net.explicit_batch ? op.i[11] : plan.max_batch, f.params.net_h, f.params.net_w, f.params.strides.data(),
@@ -1208,7 +1277,8 @@ struct Lowerer {
             plan.binding_is_input.push_back(true);
             pt_of[t] = p;
         }
-        analyse_yolo_head();  // before conv fusion: it claims the DFL 1x1 convolutions
+        analyse_yolo_task_head();  // before conv fusion: these claim the DFL 1x1 convolutions
+        analyse_yolo_head();
         analyse_attention();
         analyse_fusion();
         for (size_t li = 0; li < net.layers.size(); ++li) {
@@ -1976,7 +2046,8 @@ struct Lowerer {
         // plugin workspaces are short-lived arena blocks
         std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
         for (int k = 0; k < nops; ++k) {
-            if ((plan.ops[k].kind != OP_PLUGIN && plan.ops[k].kind != OP_YOLO_HEAD) || plan.ops[k].ws_bytes == 0) continue;
+            const int kind = plan.ops[k].kind;
+            if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD) || plan.ops[k].ws_bytes == 0) continue;
             Storage s;
             s.kind = ST_ARENA;
             s.bytes = plan.ops[k].ws_bytes;
@@ -2148,7 +2219,7 @@ bool pack_weights(const Network& net, Plan* plan) {
             op.b_off = reserve(bias.size() * 4);
             memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
             op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (size_t)cout * a.K * 4);
-        } else if (op.kind == OP_YOLO_HEAD) {
+        } else if (op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);
             memcpy(blob.data() + op.w_off, l.w0.data(), 16 * 4);
@@ -2217,6 +2288,12 @@ std::string Plan::describe_json() const {
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
+        if (op.kind == OP_YOLO_TASK_HEAD) {
+            o << ",\"task\":\"" << (op.i[9] == 1 ? "seg" : (op.i[9] == 2 ? "pose" : "obb")) << "\",\"classes\":" << op.i[0] << ",\"nk\":" << op.i[10]
+              << ",\"branch_ld\":[";
+            for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
+            o << "]";
+        }
         if (op.kind == OP_CONV_GROUP) {
             o << ",\"members\":[";
             for (size_t j = 0; j < op.group.size(); ++j) {

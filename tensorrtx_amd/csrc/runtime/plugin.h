@@ -84,6 +84,9 @@ struct YoloLayerParams {
     int classes, net_w, net_h, max_out;
     std::vector<int> strides;
     bool det_only;
+    bool seg = false, pose = false, obb = false;   // the plugin's task branches (yololayer.cu:222-279)
+    int nk = 0;                                   // keypoints per record (pose)
+    float kpt_conf = 0.f;                         // keypoint confidence threshold (pose)
 };
 bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out);
 // true for the built-in "Mish_TRT" (plugins/builtin_plugins.cpp; yolov4/mish.{h,cu}): a pointwise activation, which the lowering pass

@@ -92,11 +92,13 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         cfg.fp16 = geti(o, "fp16", 1) != 0;
         cfg.input_h = geti(o, "h", 640);
         cfg.input_w = geti(o, "w", 640);
-        cfg.num_class = geti(o, "classes", 80);
+        cfg.task = geti(o, "task", 0);  // 0 det, 1 seg, 2 pose, 3 obb, 4 cls
+        if (cfg.task < 0 || cfg.task > 4 || cfg.batch < 1) return TRTX_ERR_INVALID;
+        static const int kClasses[] = {80, 80, 1, 15, 1000};   // kNumClass, kPoseNumClass, kObbNumClass, kClsNumClass (yolo11/include/config.h)
+        cfg.num_class = geti(o, "classes", kClasses[cfg.task]);
         cfg.max_out_bbox = geti(o, "max_out", 1000);
         cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
-        cfg.task = geti(o, "task", 0);
-        if (cfg.task != 0 || cfg.batch < 1) return TRTX_ERR_INVALID;
+        cfg.num_points = geti(o, "points", cfg.num_points);
         plan.reset(trtx_host::buildEngineYolo11Det(builder.get(), config.get(), wts_path, cfg));
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;

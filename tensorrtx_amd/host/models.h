@@ -52,13 +52,16 @@ struct Yolo11Config {
     int max_channels = 1024;
     bool c3k = false;                   // C3k blocks inside C3K2 (m / l / x; model.cpp:160-163)
     bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
-    int task = 0;                       // 0 det; seg / pose / obb / cls are not built yet
+    // 0 det, 1 seg (buildEngineYolo11Seg, model.cpp:509-799: + 32 mask coefficients per cell and the "proto" output), 2 pose
+    // (..Pose, :801-1090: + 3 * num_points keypoint values), 3 obb (..Obb, :1092-1389: + 1 angle logit), 4 cls (..Cls, :33-136: logits)
+    int task = 0;
     int num_points = 17;                // kNumberOfPoints
     float kpt_conf = 0.5f;              // kConfThreshKeypoints (truncated into the plugin field like the reference)
 };
 // the n / s / m / l / x scale: gd, gw, max_channels and the c3k flag; false for an unknown letter
 bool yolo11_scale(char type, Yolo11Config* cfg);
-// yolo11/src/model.cpp:138-400 with yolo11/src/block.cpp
+// yolo11/src/model.cpp:138-400 (det), 509-799 (seg), 801-1090 (pose), 1092-1389 (obb) with yolo11/src/block.cpp: one graph, the task adds the
+// cv4 branch (and Proto for seg); task 4 builds the classifier (model.cpp:33-136) instead
 nvinfer1::IHostMemory* buildEngineYolo11Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
                                             const std::string& wts, const Yolo11Config& cfg);
 

@@ -3,6 +3,8 @@
 //   convBnSiLU / bottleneck / SPPF / DFL / addYoLoLayer / C3k / C3K2 / convBn / Attention / PSABlock / C2PSA / DWConv
 //                                                              yolo11/src/block.cpp:73-437
 //   get_width / get_depth / calculateStrides / buildEngineYolo11Det   yolo11/src/model.cpp:9-31, 138-400
+//   Proto / cv4_conv_combined / buildEngineYolo11{Seg,Pose,Obb}       yolo11/src/model.cpp:412-1389
+//   buildEngineYolo11Cls                                             yolo11/src/model.cpp:33-136
 // Graph, weight keys ("model.<n>...") and layer order are those of the reference.
 #include <cmath>
 #include <vector>
@@ -195,7 +197,7 @@ ITensor* DFL(Ctx& c, ITensor& in, int B, int grid, const std::string& wkey) {
     return sh2->getOutput(0);
 }
 
-// block.cpp:162-205: the 9 netinfo fields, then the strides
+// block.cpp:162-205: the 9 netinfo fields (the keypoint threshold truncated to int like the reference), then the strides
 IPluginV2Layer* addYoLoLayer(Ctx& c, const std::vector<ITensor*>& dets, const std::vector<int>& strides, const Yolo11Config& cfg) {
     auto* creator = getPluginRegistry()->getPluginCreator("YoloLayer_TRT", "1");
     assert(creator && "YoloLayer_TRT creator not registered");
@@ -210,6 +212,80 @@ IPluginV2Layer* addYoLoLayer(Ctx& c, const std::vector<ITensor*>& dets, const st
     auto* layer = c.net->addPluginV2(ins.data(), (int32_t)ins.size(), *plugin);
     plugin->destroy();  // the network holds its own clone
     return layer;
+}
+
+// cv4_conv_combined (model.cpp:474-507): two 3x3 convBnSiLU to c4, a biased 1x1 conv to the task's extra channels (32 mask
+// coefficients, 3 * nk keypoint values or kObbNe = 1 angle logit), reshaped to (B, extra, grid)
+ITensor* cv4Branch(Ctx& c, ITensor& in, const std::string& lname, int B, int grid, int w256, const Yolo11Config& cfg) {
+    const int extra = cfg.task == 1 ? 32 : (cfg.task == 2 ? cfg.num_points * 3 : 1);
+    const int c4 = std::max(w256 / 4, extra);
+    ITensor* a = convBnSiLU(c, in, c4, 3, 1, lname + ".0");
+    ITensor* b = convBnSiLU(c, *a, c4, 3, 1, lname + ".1");
+    auto* cv = c.net->addConvolutionNd(*b, extra, DimsHW{1, 1}, need(c.wm, lname + ".2.weight"), need(c.wm, lname + ".2.bias"));
+    assert(cv);
+    cv->setStrideNd(DimsHW{1, 1});
+    auto* sh = c.net->addShuffle(*cv->getOutput(0));
+    sh->setReshapeDimensions(Dims3{B, extra, grid});
+    return sh->getOutput(0);
+}
+
+// Proto (model.cpp:412-472): 3x3 convBnSiLU -> 2x2 stride-2 deconvolution with bias -> 3x3 convBnSiLU -> 1x1 convBnSiLU to 32
+ITensor* proto(Ctx& c, ITensor& in, int mid) {
+    ITensor* a = convBnSiLU(c, in, mid, 3, 1, "model.23.proto.cv1");
+    auto* up = c.net->addDeconvolutionNd(*a, mid, DimsHW{2, 2}, need(c.wm, "model.23.proto.upsample.weight"),
+                                         need(c.wm, "model.23.proto.upsample.bias"));
+    assert(up);
+    up->setStrideNd(DimsHW{2, 2});
+    up->setPaddingNd(DimsHW{0, 0});
+    ITensor* b = convBnSiLU(c, *up->getOutput(0), mid, 3, 1, "model.23.proto.cv2");
+    return convBnSiLU(c, *b, 32, 1, 1, "model.23.proto.cv3");
+}
+
+// buildEngineYolo11Cls (model.cpp:33-136): the backbone to model.8, C2PSA as model.9 (no SPPF), then model.10: 1x1 convBnSiLU to
+// 1280, average pool over the whole map, (B, 1280) x linear.weight^T + linear.bias
+IHostMemory* buildCls(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolo11Config& cfg) {
+    WeightMap wm = loadWeights(wts);
+    INetworkDefinition* net = builder->createNetworkV2(1U << static_cast<uint32_t>(NetworkDefinitionCreationFlag::kEXPLICIT_BATCH));
+    IHostMemory* plan = nullptr;
+    {
+        Ctx c{net, wm, {}};
+        const float gd = cfg.gd, gw = cfg.gw;
+        const int mc = cfg.max_channels, B = cfg.batch, nc = cfg.num_class;
+        const bool c3k = cfg.c3k;
+        auto W = [&](int x) { return get_width(x, gw, mc); };
+        ITensor* data = net->addInput("images", DataType::kFLOAT, Dims4{B, 3, cfg.input_h, cfg.input_w});
+        assert(data);
+        ITensor* x = convBnSiLU(c, *data, W(64), 3, 2, "model.0");
+        x = convBnSiLU(c, *x, W(128), 3, 2, "model.1");
+        x = C3K2(c, *x, W(256), get_depth(2, gd), c3k, true, 0.25f, "model.2");
+        x = convBnSiLU(c, *x, W(256), 3, 2, "model.3");
+        x = C3K2(c, *x, W(512), get_depth(2, gd), c3k, true, 0.25f, "model.4");
+        x = convBnSiLU(c, *x, W(512), 3, 2, "model.5");
+        x = C3K2(c, *x, W(512), get_depth(2, gd), true, true, 0.5f, "model.6");
+        x = convBnSiLU(c, *x, W(1024), 3, 2, "model.7");
+        x = C3K2(c, *x, W(1024), get_depth(2, gd), true, true, 0.5f, "model.8");
+        x = C2PSA(c, *x, W(1024), W(1024), get_depth(2, gd), 0.5f, "model.9");
+        ITensor* head = convBnSiLU(c, *x, 1280, 1, 1, "model.10.conv");
+        const Dims d = head->getDimensions();
+        auto* pool = net->addPoolingNd(*head, PoolingType::kAVERAGE, DimsHW{(int)d.d[2], (int)d.d[3]});
+        assert(pool);
+        auto* flat = net->addShuffle(*pool->getOutput(0));
+        flat->setReshapeDimensions(Dims2{B, 1280});
+        ITensor* w = net->addConstant(Dims2{nc, 1280}, need(wm, "model.10.linear.weight"))->getOutput(0);
+        // The reference declares the bias as Dims2{kBatchSize, kClsNumClass} over kClsNumClass values (model.cpp:104-105), which
+        // holds only for kBatchSize = 1.  Here it is (1, classes) and the element-wise sum broadcasts it over the batch.
+        ITensor* bias = net->addConstant(Dims2{1, nc}, need(wm, "model.10.linear.bias"))->getOutput(0);
+        ITensor* mm = net->addMatrixMultiply(*flat->getOutput(0), MatrixOperation::kNONE, *w, MatrixOperation::kTRANSPOSE)->getOutput(0);
+        ITensor* y = net->addElementWise(*mm, *bias, ElementWiseOperation::kSUM)->getOutput(0);
+        y->setName("output");
+        net->markOutput(*y);
+        config->setMaxWorkspaceSize(16 * (1 << 20));
+        if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
+        plan = builder->buildSerializedNetwork(*net, *config);
+    }
+    delete net;
+    freeWeights(wm);
+    return plan;
 }
 
 }  // namespace
@@ -228,7 +304,8 @@ bool yolo11_scale(char type, Yolo11Config* cfg) {  // yolo11_det.cpp:120-150
 }
 
 IHostMemory* buildEngineYolo11Det(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolo11Config& cfg) {
-    if (cfg.task != 0) return nullptr;   // seg / pose / obb / cls: not yet
+    if (cfg.task == 4) return buildCls(builder, config, wts, cfg);
+    if (cfg.task < 0 || cfg.task > 4) return nullptr;
     WeightMap wm = loadWeights(wts);
     INetworkDefinition* net = builder->createNetworkV2(1U << static_cast<uint32_t>(NetworkDefinitionCreationFlag::kEXPLICIT_BATCH));
     IHostMemory* plan = nullptr;
@@ -287,6 +364,7 @@ IHostMemory* buildEngineYolo11Det(IBuilder* builder, IBuilderConfig* config, con
         std::vector<int> strides;
         for (ITensor* t : {conv3, conv5, conv7}) strides.push_back(cfg.input_h / (int)t->getDimensions().d[2]);
         std::vector<ITensor*> dets;
+        std::vector<std::pair<ITensor*, ITensor*>> tails;
         for (int lv = 0; lv < 3; ++lv) {
             const int grid = (cfg.input_h / strides[lv]) * (cfg.input_w / strides[lv]);
             auto* flat = net->addShuffle(*cats[lv]);
@@ -294,8 +372,25 @@ IHostMemory* buildEngineYolo11Det(IBuilder* builder, IBuilderConfig* config, con
             ITensor* boxPart = net->addSlice(*flat->getOutput(0), Dims3{0, 0, 0}, Dims3{B, 64, grid}, Dims3{1, 1, 1})->getOutput(0);
             ITensor* clsPart = net->addSlice(*flat->getOutput(0), Dims3{0, 64, 0}, Dims3{B, nc, grid}, Dims3{1, 1, 1})->getOutput(0);
             ITensor* dfl = DFL(c, *boxPart, B, grid, "model.23.dfl.conv.weight");
-            ITensor* v[] = {dfl, clsPart};
-            auto* cat = net->addConcatenation(v, 2);
+            if (cfg.task == 0) {
+                ITensor* v[] = {dfl, clsPart};
+                auto* cat = net->addConcatenation(v, 2);
+                cat->setAxis(1);
+                dets.push_back(cat->getOutput(0));
+            } else if (cfg.task == 2) {   // pose joins each level right after its DFL: [dfl(4), classes, keypoints] (model.cpp:1000-1060)
+                ITensor* v[] = {dfl, clsPart, cv4Branch(c, *feats[lv], "model.23.cv4." + std::to_string(lv), B, grid, W(256), cfg)};
+                auto* cat = net->addConcatenation(v, 3);
+                cat->setAxis(1);
+                dets.push_back(cat->getOutput(0));
+            } else {                      // seg / obb finish all three DFL tails first (model.cpp:695-730, 1290-1330)
+                tails.push_back({dfl, clsPart});
+            }
+        }
+        for (size_t lv = 0; lv < tails.size(); ++lv) {   // seg / obb: [dfl(4), classes, mask coefficients | angle] (model.cpp:732-756, 1332-1358)
+            const int grid = (cfg.input_h / strides[lv]) * (cfg.input_w / strides[lv]);
+            ITensor* v[] = {tails[lv].first, tails[lv].second,
+                            cv4Branch(c, *feats[lv], "model.23.cv4." + std::to_string(lv), B, grid, W(256), cfg)};
+            auto* cat = net->addConcatenation(v, 3);
             cat->setAxis(1);
             dets.push_back(cat->getOutput(0));
         }
@@ -308,6 +403,11 @@ IHostMemory* buildEngineYolo11Det(IBuilder* builder, IBuilderConfig* config, con
         assert(yolo);
         yolo->getOutput(0)->setName("output");
         net->markOutput(*yolo->getOutput(0));
+        if (cfg.task == 1) {   // model.cpp:765-767
+            ITensor* pr = proto(c, *conv16, W(256));
+            pr->setName("proto");
+            net->markOutput(*pr);
+        }
 
         config->setMaxWorkspaceSize(16 * (1 << 20));
         if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);

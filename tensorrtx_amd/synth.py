@@ -178,11 +178,19 @@ YOLO11_SCALES = {  # yolo11_det.cpp:120-150: gd, gw, max_channels; m / l / x use
     "n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)}
 
 
-def yolo11_state(scale="n", seed=0, num_class=80):
-    """Seeded synthetic weights of YOLO11{n,s,m,l,x}-det under the reference's `.wts` key names (ultralytics state_dict keys, as
-    read by yolo11/src/block.cpp / model.cpp:138-400): OrderedDict name -> fp32 array.  He-scaled convolutions with near-identity
-    BatchNorm statistics (the yolov8n_state recipe); the class head has gain 800 and bias -8 so that a few hundred cells per image
-    pass the 0.1 confidence gate."""
+YOLO11_TASK_CLS_BIAS = {0: -8.0, 1: -8.0, 2: -2.0, 3: -5.0}   # class-head bias per task: one (pose) or 15 (obb) classes need a higher one
+
+
+def yolo11_state(scale="n", seed=0, num_class=80, task=0):
+    """Seeded synthetic weights of YOLO11{n,s,m,l,x} under the reference's `.wts` key names (ultralytics state_dict keys, as
+    read by yolo11/src/block.cpp / model.cpp): OrderedDict name -> fp32 array.  He-scaled convolutions with near-identity
+    BatchNorm statistics (the yolov8n_state recipe); the class head has gain 800 and bias -8 (det / seg; see YOLO11_TASK_CLS_BIAS)
+    so that a few hundred cells per image pass the 0.1 confidence gate.
+
+    task: 0 det, 1 seg, 2 pose, 3 obb, 4 cls.  The task tensors (model.23.cv4.*, model.23.proto.*) are drawn after every det
+    tensor, so a seg / pose / obb model shares its backbone and neck with the det model of the same seed, and its detect head as
+    well when num_class is the same (the class biases are drawn num_class at a time, so every later draw moves with it).  cls
+    (model.cpp:33-136) has its own keys after model.8: C2PSA as model.9, then model.10.conv and model.10.linear."""
     import math
     from collections import OrderedDict
 
@@ -260,6 +268,12 @@ def yolo11_state(scale="n", seed=0, num_class=80):
     c3k2("model.6", W(512), W(512), D(2), True, 0.5)
     cb("model.7", W(1024), W(512), 3)
     c3k2("model.8", W(1024), W(1024), D(2), True, 0.5)
+    if task == 4:
+        c2psa("model.9", W(1024), W(1024), D(2))
+        cb("model.10.conv", 1280, W(1024), 1)
+        sd["model.10.linear.weight"] = (randn(num_class, 1280) * math.sqrt(1.0 / 1280)).float()
+        sd["model.10.linear.bias"] = (0.1 * randn(num_class)).float()
+        return OrderedDict((k, v.numpy()) for k, v in sd.items())
     cb("model.9.cv1", W(1024) // 2, W(1024), 1)
     cb("model.9.cv2", W(1024), 2 * W(1024), 1)
     c2psa("model.10", W(1024), W(1024), D(2))
@@ -281,9 +295,24 @@ def yolo11_state(scale="n", seed=0, num_class=80):
         cb(f"model.23.cv3.{lv}.1.0", c3, c3, 3, groups=c3, gain=1.0)
         cb(f"model.23.cv3.{lv}.1.1", c3, c3, 1)
         conv(f"model.23.cv3.{lv}.2", num_class, c3, 1, gain=800.0)
-        sd[f"model.23.cv3.{lv}.2.bias"] = (-8.0 + 0.1 * randn(num_class)).float()
+        sd[f"model.23.cv3.{lv}.2.bias"] = (YOLO11_TASK_CLS_BIAS[task] + 0.1 * randn(num_class)).float()
         if lv == 0:
             sd["model.23.dfl.conv.weight"] = torch.arange(16.0).reshape(1, 16, 1, 1)
+    if task in (1, 2, 3):   # cv4_conv_combined (model.cpp:474-507): 32 mask coefficients, 17 * 3 keypoint values or one angle logit
+        extra = {1: 32, 2: 17 * 3, 3: 1}[task]
+        c4 = max(W(256) // 4, extra)
+        for lv, cin in enumerate((W(256), W(512), W(1024))):
+            cb(f"model.23.cv4.{lv}.0", c4, cin, 3)
+            cb(f"model.23.cv4.{lv}.1", c4, c4, 3)
+            conv(f"model.23.cv4.{lv}.2", extra, c4, 1, gain=0.5 if task == 2 else 2.0)   # keypoints stay near their cell
+            sd[f"model.23.cv4.{lv}.2.bias"] = (0.1 * randn(extra)).float()
+    if task == 1:           # Proto (model.cpp:412-472)
+        mid = W(256)
+        cb("model.23.proto.cv1", mid, W(256), 3)
+        sd["model.23.proto.upsample.weight"] = (randn(mid, mid, 2, 2) * math.sqrt(2.0 / (mid * 4))).float()
+        sd["model.23.proto.upsample.bias"] = (0.1 * randn(mid)).float()
+        cb("model.23.proto.cv2", mid, mid, 3)
+        cb("model.23.proto.cv3", 32, mid, 1)
     return OrderedDict((k, v.numpy()) for k, v in sd.items())
 
 
