@@ -155,6 +155,12 @@ bool conv_dw_supported(const ConvArgs& a);
 bool psa_attention_supported(int kd, int hd);
 int32_t psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
                           float scale, hipStream_t s);
+// area attention on the matrix pipe (attention_mfma.hip; YOLOv12's AAttn): the same tensors as psa_attention_f16, the N pixels of an image
+// split into `area` contiguous ranges of N / area pixels that attend within themselves (area = 1: the whole image); kd == hd == 32.
+// A base pointer or channel stride that rules out 16-byte accesses takes element-wise loads / stores, not an error.
+bool area_attention_supported(int kd, int hd);
+int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd,
+                           int hd, float scale, hipStream_t s);
 int32_t conv_dw(const ConvArgs& a, int dtype, hipStream_t s);
 // generic transposed convolution, fp32 weights laid out [Cin][kh][kw][Cout/groups]
 int32_t deconv_direct(const ConvArgs& a, int dtype, hipStream_t s);

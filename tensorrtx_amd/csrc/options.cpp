@@ -35,6 +35,7 @@ Options read_options() {
     o.res = env_int("TRTX_CONV_RES", 7);
     o.roles = !env_is("TRTX_CONV_ROLES", 0);
     o.f32_mfma = !env_set("TRTX_F32_DIRECT");
+    o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.roialign_fused = !env_set("TRTX_ROIALIGN_PLUGIN");
     o.roialign_fold_stride = !env_is("TRTX_ROIALIGN_FOLD_STRIDE", 0);
     o.profile_kernel_events = !env_set("TRTX_PROFILE_NO_KERNEL_EVENTS");

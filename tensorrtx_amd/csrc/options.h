@@ -30,6 +30,7 @@ struct Options {
     int res = 7;                 // TRTX_CONV_RES=<mask>: resident-operand kernels (conv_res.hip) among the candidates / in the grouped launches: 1 = the 3x3 kernel, 2 = the 1x1 kernel, 4 = the 3x3 kernel in grouped launches too; 0 = none
     bool roles = true;           // TRTX_CONV_ROLES=0: no fetching / multiplying wave-role variants among the candidates (fp32 plans)
     bool f32_mfma = true;        // TRTX_F32_DIRECT=1: fp32 engines on the scalar direct kernel of rounds 1-4 (no fp32 MFMA, no fp32 stem kernel)
+    bool area_attention = true;  // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
     bool roialign_fused = true;  // TRTX_ROIALIGN_PLUGIN=1: RoIAlign stays a plugin op (fp32 NCHW edge)
     bool roialign_fold_stride = true;   // TRTX_ROIALIGN_FOLD_STRIDE=0: RoIAlign emits all 14 x 14 bins
     bool profile_kernel_events = true;  // TRTX_PROFILE_NO_KERNEL_EVENTS=1: trtx_context_profile without per-launch start / stop events

@@ -379,8 +379,12 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
             }
             case OP_ATTENTION: {
                 const PTensor &to2 = plan.tensors[op.out[1]];
-                st = psa_attention_f16(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, R.ptr(op.out[1]), to2.ld, nb(t0), op.i[0], op.i[1], op.i[2],
-                                       op.i[3], op.f[0], stream);
+                if (op.i[4] > 0)
+                    st = area_attention_f16(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, R.ptr(op.out[1]), to2.ld, nb(t0), op.i[0], op.i[1], op.i[4],
+                                            op.i[2], op.i[3], op.f[0], stream);
+                else
+                    st = psa_attention_f16(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, R.ptr(op.out[1]), to2.ld, nb(t0), op.i[0], op.i[1], op.i[2],
+                                           op.i[3], op.f[0], stream);
                 break;
             }
             case OP_ROI_ALIGN: {

@@ -72,6 +72,7 @@ struct AttentionFuse {
     int out_o = -1, out_v = -1;      // network tensors: O reshaped to (B, heads*hd, H, W), and v reshaped the same way
     int heads = 0, N = 0, kd = 0, hd = 0;
     float scale = 0.f;
+    int area = 0;                    // 0: YOLO11 PSA (psa_attention_kernel); >= 1: YOLOv12 area attention (area_attention_mfma_kernel), N / area keys per query
 };
 
 struct Lowerer {
@@ -614,15 +615,132 @@ struct Lowerer {
             attns.push_back(f);
         }
     }
+    // ---- YOLOv12 area attention (yolov12/src/block.cpp:522-625): qkv (B, heads*96, H, W) -> [reshape (B, -1, N), transpose {0,2,1}] ->
+    // [reshape (B area, N / area, heads, 96), transpose {0,2,3,1}] -> q / k / v slices of 32 rows -> q^T k -> uniform scale -> softmax over the
+    // keys -> v @ attn^T -> transpose {0,3,1,2} -> reshape (B, H, W, C) -> transpose {0,3,1,2}, and v through the same three shuffles for
+    // `pe`.  In NHWC that is: area a = the pixel range [a N/area, (a+1) N/area) of an image, head h = channels h*96 + {q | k | v}.  Every
+    // shape, permutation, slice and the scale are checked and no intermediate may have another reader or be an output; anything else keeps
+    // the generic linear path.  fp16 explicit-batch engines only, and not with TRTX_AREA_ATTENTION=0.
+    void analyse_area_attention() {
+        if (!net.explicit_batch || dt != DT_F16 || !opt.area_attention) return;
+        auto perm_is = [](const int32_t* p, std::initializer_list<int> want) {
+            int k = 0;
+            for (int v : want)
+                if (p[k++] != v) return false;
+            return true;
+        };
+        auto transpose_only = [&](int l, std::initializer_list<int> p) {   // a shuffle that is one first transpose of a 4-d tensor
+            const LayerDef& sh = net.layers[l];
+            return sh.kind == L_SHUFFLE && sh.reshape.nb == 0 && perm_is(sh.perm1, p) && ident(sh.perm2, 4);
+        };
+        for (size_t li = 0; li < net.layers.size(); ++li) {
+            const LayerDef& m1 = net.layers[li];
+            if (m1.kind != L_MATMUL || m1.mm_op[0] != TRTX_MATMUL_NONE || m1.mm_op[1] != TRTX_MATMUL_NONE || absorbed[li]) continue;
+            const int lqt = producer(m1.inputs[0]), lk = producer(m1.inputs[1]);
+            if (lqt < 0 || lk < 0 || !transpose_only(lqt, {0, 1, 3, 2}) || net.layers[lk].kind != L_SLICE) continue;
+            const int lq = producer(net.layers[lqt].inputs[0]);
+            if (lq < 0 || net.layers[lq].kind != L_SLICE) continue;
+            const int tx = net.layers[lq].inputs[0];
+            if (net.layers[lk].inputs[0] != tx) continue;
+            // the two shuffles between the qkv image and the (B area, heads, 96, N / area) tensor
+            const int l2 = producer(tx);
+            if (l2 < 0 || net.layers[l2].kind != L_SHUFFLE || net.layers[l2].reshape.nb != 4 || !ident(net.layers[l2].perm1, 3) ||
+                !perm_is(net.layers[l2].perm2, {0, 2, 3, 1}))
+                continue;
+            const int tl = net.layers[l2].inputs[0];
+            const int l1 = producer(tl);
+            if (l1 < 0 || net.layers[l1].kind != L_SHUFFLE || net.layers[l1].reshape.nb != 3 || !ident(net.layers[l1].perm1, 4) ||
+                !perm_is(net.layers[l1].perm2, {0, 2, 1}))
+                continue;
+            const int tqkv = net.layers[l1].inputs[0];
+            const Dims &dx = net.tensors[tx].dims, &dl = net.tensors[tl].dims, &dq = net.tensors[tqkv].dims;
+            if (dx.nb != 4 || dl.nb != 3 || dq.nb != 4) continue;
+            const int64_t B = dq.d[0], C3 = dq.d[1], N = dq.d[2] * dq.d[3];
+            const int64_t Ba = dx.d[0], heads = dx.d[1], rows = dx.d[2], Na = dx.d[3];
+            if (dl.d[0] != B || dl.d[1] != N || dl.d[2] != C3 || B < 1 || Na < 1 || Ba % B != 0 || heads * rows != C3) continue;
+            const int64_t area = Ba / B;
+            if (area < 1 || Na * area != N) continue;   // the area count must divide the pixels
+            auto slice_rows = [&](const LayerDef& sl, int64_t r0, int64_t nr) {
+                return sl.start.nb == 4 && sl.start.d[0] == 0 && sl.start.d[1] == 0 && sl.start.d[2] == r0 && sl.start.d[3] == 0 && sl.size.d[0] == Ba &&
+                       sl.size.d[1] == heads && sl.size.d[2] == nr && sl.size.d[3] == Na && sl.step.d[0] == 1 && sl.step.d[1] == 1 && sl.step.d[2] == 1 &&
+                       sl.step.d[3] == 1;
+            };
+            const int64_t kd = net.layers[lq].size.d[2];
+            const int64_t hd = rows - 2 * kd;
+            if (!slice_rows(net.layers[lq], 0, kd) || !slice_rows(net.layers[lk], kd, kd) || hd < 1) continue;
+            int lv = -1;
+            for (int c : consumers[tx])
+                if (c != lq && c != lk) lv = c;
+            if (lv < 0 || net.layers[lv].kind != L_SLICE || !slice_rows(net.layers[lv], 2 * kd, hd) || !only_used_by(tx, {lq, lk, lv})) continue;
+            if (!only_used_by(tl, {l2}) || !area_attention_supported((int)kd, (int)hd)) continue;
+            // scale -> softmax -> transpose -> second matmul
+            int lsc, lsm, lat, m2;
+            if (!sole_consumer(m1.outputs[0], &lsc) || net.layers[lsc].kind != L_SCALE || net.layers[lsc].op != TRTX_SCALE_UNIFORM) continue;
+            const LayerDef& sc = net.layers[lsc];
+            if (sc.w1.size() != 1 || (!sc.w0.empty() && (sc.w0.size() != 1 || sc.w0[0] != 0.f)) || (!sc.w2.empty() && (sc.w2.size() != 1 || sc.w2[0] != 1.f)))
+                continue;
+            if (!sole_consumer(sc.outputs[0], &lsm) || net.layers[lsm].kind != L_SOFTMAX || net.layers[lsm].axis != (1 << 3)) continue;
+            if (!sole_consumer(net.layers[lsm].outputs[0], &lat) || !transpose_only(lat, {0, 1, 3, 2})) continue;
+            if (!sole_consumer(net.layers[lat].outputs[0], &m2)) continue;
+            const LayerDef& mm2 = net.layers[m2];
+            if (mm2.kind != L_MATMUL || mm2.mm_op[0] != TRTX_MATMUL_NONE || mm2.mm_op[1] != TRTX_MATMUL_NONE || mm2.inputs[1] != net.layers[lat].outputs[0] ||
+                mm2.inputs[0] != net.layers[lv].outputs[0])
+                continue;
+            // the way back to an image, for O and for v: transpose {0,3,1,2} -> reshape (B, H, W, heads*hd) -> transpose {0,3,1,2}
+            auto image_of = [&](int t_from, int skip, int* used3, int* t_img) {
+                int a = -1;
+                for (int c : consumers[t_from])
+                    if (c != skip) a = c;
+                if (a < 0 || net.tensors[t_from].is_output || consumers[t_from].size() != (skip >= 0 ? 2u : 1u) || !transpose_only(a, {0, 3, 1, 2})) return false;
+                int r, b2;
+                if (!sole_consumer(net.layers[a].outputs[0], &r)) return false;
+                const LayerDef& re = net.layers[r];
+                const Dims& dr = net.tensors[re.outputs[0]].dims;
+                if (re.kind != L_SHUFFLE || re.reshape.nb != 4 || !ident(re.perm1, 4) || !ident(re.perm2, 4) || dr.nb != 4 || dr.d[0] != B ||
+                    dr.d[1] != dq.d[2] || dr.d[2] != dq.d[3] || dr.d[3] != heads * hd)
+                    return false;
+                if (!sole_consumer(re.outputs[0], &b2) || !transpose_only(b2, {0, 3, 1, 2})) return false;
+                used3[0] = a; used3[1] = r; used3[2] = b2;
+                *t_img = net.layers[b2].outputs[0];
+                return true;
+            };
+            int uo[3], uv[3], t_o = -1, t_v = -1;
+            const int tv = net.layers[lv].outputs[0];
+            if (!image_of(mm2.outputs[0], -1, uo, &t_o) || !image_of(tv, m2, uv, &t_v)) continue;
+            if (!only_used_by(m1.inputs[0], {(int)li}) || !only_used_by(m1.inputs[1], {(int)li}) || !only_used_by(net.layers[lqt].inputs[0], {lqt})) continue;
+            const int used[] = {l1, l2, lq, lk, lv, lqt, (int)li, lsc, lsm, lat, m2, uo[0], uo[1], uo[2], uv[0], uv[1], uv[2]};
+            bool free = true;
+            for (int u : used) free = free && !absorbed[u] && (u == uo[2] || u == uv[2] || !net.tensors[net.layers[u].outputs[0]].is_output);
+            if (!free || net.tensors[t_o].is_output || net.tensors[t_v].is_output) continue;
+            AttentionFuse f;
+            f.qkv = tqkv;
+            f.out_o = t_o;
+            f.out_v = t_v;
+            f.heads = (int)heads;
+            f.N = (int)N;
+            f.kd = (int)kd;
+            f.hd = (int)hd;
+            f.scale = sc.w1[0];
+            f.area = (int)area;
+            int at = 0;
+            for (int u : used) {
+                absorbed[u] = true;
+                at = std::max(at, u);
+            }
+            attn_at[at] = (int)attns.size();
+            attns.push_back(f);
+        }
+    }
     bool emit_attention(const AttentionFuse& f) {
         const int in = need_nhwc(f.qkv);
         const int o = new_tensor(f.out_o, net.tensors[f.out_o].dims, LAY_NHWC, true);
         const int v = new_tensor(f.out_v, net.tensors[f.out_v].dims, LAY_NHWC, true);
         POp& op = add_op(OP_ATTENTION, "attention:" + net.tensors[f.qkv].name, {in}, {o, v});
         op.i[0] = f.heads; op.i[1] = f.N; op.i[2] = f.kd; op.i[3] = f.hd;
+        op.i[4] = f.area;
         op.f[0] = f.scale;
         const double B = plan.tensors[in].nfix;
-        op.flops = 2.0 * B * f.heads * (double)f.N * f.N * (f.kd + f.hd);
+        op.flops = 2.0 * B * f.heads * (double)f.N * (f.N / std::max(f.area, 1)) * (f.kd + f.hd);   // area * (N / area)^2 score and value products
         op.bytes = 2.0 * B * f.N * ((double)plan.tensors[in].C + 2.0 * f.heads * f.hd);
         pt_of[f.out_o] = o;
         pt_of[f.out_v] = v;
@@ -1280,6 +1398,7 @@ struct Lowerer {
         analyse_yolo_task_head();  // before conv fusion: these claim the DFL 1x1 convolutions
         analyse_yolo_head();
         analyse_attention();
+        analyse_area_attention();
         analyse_fusion();
         for (size_t li = 0; li < net.layers.size(); ++li) {
             if (yolo_at[li] >= 0) {
@@ -2288,6 +2407,7 @@ std::string Plan::describe_json() const {
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
+        if (op.kind == OP_ATTENTION && op.i[4] > 0) o << ",\"area\":" << op.i[4] << ",\"kernel\":\"mfma\"";
         if (op.kind == OP_YOLO_TASK_HEAD) {
             o << ",\"task\":\"" << (op.i[9] == 1 ? "seg" : (op.i[9] == 2 ? "pose" : "obb")) << "\",\"classes\":" << op.i[0] << ",\"nk\":" << op.i[10]
               << ",\"branch_ld\":[";

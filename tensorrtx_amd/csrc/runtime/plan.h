@@ -46,7 +46,8 @@ enum OpKind : int {
     OP_ROI_ALIGN,     // detectron2 ROIAlign on the NHWC feature map, NHWC [P][res][res][C] out (fused form of the "RoiAlign" plugin)
     OP_RESERVED_47,   // (rounds 3-4: OP_CONV_CHAIN, the fused convolution chains - tools/hip/experiments/)
     OP_CONV_GROUP,    // 2..4 INDEPENDENT implicit-GEMM convolutions of one kernel instantiation in one launch (POp::group; round 4)
-    OP_ATTENTION,     // YOLO11 PSA attention on the NHWC fp16 qkv tensor: O and the V image (kernels/attention.hip); i = heads, N, kd, hd, f[0] = scale
+    OP_ATTENTION,     // YOLO11 PSA attention on the NHWC fp16 qkv tensor: O and the V image (kernels/attention.hip); i = heads, N, kd, hd, f[0] = scale;
+                      // i[4] = 0.  With i[4] = area >= 1: YOLOv12 area attention on the same tensors (kernels/attention_mfma.hip), N / area keys per query
     OP_YOLO_TASK_HEAD,  // fused DFL + YoloLayer seg / pose / obb decode (explicit batch): `in` = NHWC heads, `extra_in` = NHWC task branches;
                         // i as OP_YOLO_HEAD with at most 4 strides in i[5..8], i[9] = 1 seg / 2 pose / 3 obb, i[10] = keypoints, f[0] = kpt_conf
 };

@@ -53,7 +53,7 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
             const trtx_host::HostOptions ho = trtx_host::read_host_options(o);   // calibration directory / cache: option string, else environment (host/options.h)
             const std::string m0(model);
             calibrator.reset(new trtx_host::Int8EntropyCalibrator2(geti(o, "calib_batch", 1), geti(o, "w", 640), geti(o, "h", 640), ho.calib_dir.c_str(),
-                                                                   ho.calib_table.c_str(), (m0 == "yolov8n" || m0.compare(0, 6, "yolo11") == 0) ? "images" : "data"));
+                                                                   ho.calib_table.c_str(), (m0 == "yolov8n" || m0.compare(0, 6, "yolo11") == 0 || m0.compare(0, 6, "yolo12") == 0) ? "images" : "data"));
         }
         config->setInt8Calibrator(calibrator.get());
     }
@@ -100,6 +100,19 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
         cfg.num_points = geti(o, "points", cfg.num_points);
         plan.reset(trtx_host::buildEngineYolo11Det(builder.get(), config.get(), wts_path, cfg));
+    } else if (m.size() == 7 && m.compare(0, 6, "yolo12") == 0) {   // yolo12n / s / m / l / x (detection only)
+        trtx_host::Yolo12Config cfg;
+        if (!trtx_host::yolo12_scale(m[6], &cfg)) return TRTX_ERR_INVALID;
+        cfg.batch = geti(o, "batch", 1);
+        cfg.fp16 = geti(o, "fp16", 1) != 0;
+        cfg.input_h = geti(o, "h", 640);
+        cfg.input_w = geti(o, "w", 640);
+        if (geti(o, "task", 0) != 0 || cfg.batch < 1) return TRTX_ERR_INVALID;
+        cfg.num_class = geti(o, "classes", 80);
+        cfg.max_out_bbox = geti(o, "max_out", 1000);
+        cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
+        plan.reset(trtx_host::buildEngineYolo12Det(builder.get(), config.get(), wts_path, cfg));
+        if (!plan) return TRTX_ERR_INVALID;   // the stride-16 grid is not divisible by the attention's area count
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);

@@ -65,6 +65,25 @@ bool yolo11_scale(char type, Yolo11Config* cfg);
 nvinfer1::IHostMemory* buildEngineYolo11Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
                                             const std::string& wts, const Yolo11Config& cfg);
 
+// yolov12/include/config.h constants as run-time configuration; explicit batch like YOLO11.  Detection only (the reference has no other
+// YOLOv12 program).
+struct Yolo12Config {
+    int input_h = 640, input_w = 640;   // kInputH / kInputW
+    int num_class = 80;                 // kNumClass
+    int batch = 1;                      // kBatchSize
+    int max_out_bbox = 1000;            // kMaxNumOutputBbox
+    bool fp16 = true;                   // USE_FP16
+    float gd = 0.50f, gw = 0.25f;       // 'n' scale (yolo12_det.cpp:120-150; yolo12_scale)
+    int max_channels = 1024;
+    bool c3k = false;                   // C3k blocks inside C3K2 (m / l / x; model.cpp:60-63)
+    bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
+};
+bool yolo12_scale(char type, Yolo12Config* cfg);
+// yolov12/src/model.cpp:33-302 with yolov12/src/block.cpp (A2C2f / ABlock / AAttn: area attention in the backbone).  Returns null when
+// the stride-16 grid's H * W is not divisible by the attention's area count (4).
+nvinfer1::IHostMemory* buildEngineYolo12Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
+                                            const std::string& wts, const Yolo12Config& cfg);
+
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {
     int input_h = 800, input_w = 1067;      // INPUT_H / INPUT_W: 480x640 resized by calculateSize() (rcnn.cpp:349-366)

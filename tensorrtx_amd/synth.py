@@ -316,6 +316,123 @@ def yolo11_state(scale="n", seed=0, num_class=80, task=0):
     return OrderedDict((k, v.numpy()) for k, v in sd.items())
 
 
+YOLO12_QKV_GAIN = 100.0   # He gain of the q and k rows of the AAttn qkv convolutions: large enough that the softmax over an area's keys is far from uniform
+
+
+def yolo12_state(scale="n", seed=0, num_class=80):
+    """Seeded synthetic weights of YOLOv12{n,s,m,l,x} detection under the reference's `.wts` key names (yolov12/src/block.cpp /
+    model.cpp): OrderedDict name -> fp32 array.  The yolo11_state recipe (He-scaled convolutions, near-identity BatchNorm statistics, a
+    class head with gain 800 and bias -8; with these backbones most cells pass the 0.1 confidence gate, 6.6k of 8.4k per image for n at
+    640 x 640 and all of them for s, so tests that compare detections give the plugin `max_out` above the cell count), and the q and k rows of the qkv
+    convolutions of the eight area-attention blocks with gain YOLO12_QKV_GAIN: tests/test_yolo12_cpu.py asserts that the attention these weights
+    produce is not uniform, so an engine that averaged V instead of attending would not pass.
+
+    Channel counts follow the reference's A2C2f (block.cpp:459-495), not ultralytics': c = c2 / 4, and cv1, the blocks and the C3k
+    branch all work on 2c channels."""
+    import math
+    from collections import OrderedDict
+
+    import torch
+    gd, gw, mc = YOLO11_SCALES[scale]   # yolo12_det.cpp:120-150 has the same table
+    c3k = scale in "mlx"
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+
+    def W(x):
+        return int(math.ceil(min(x, mc) * gw / 8)) * 8
+
+    def D(x):
+        return 1 if x == 1 else max(int(round(x * gd)), 1)
+
+    def conv(name, cout, cin, k, gain=2.0):
+        sd[name + ".weight"] = (randn(cout, cin, k, k) * math.sqrt(gain / (cin * k * k))).float()
+
+    def cb(name, cout, cin, k, groups=1, gain=2.0, bias=False):  # Conv + BatchNorm (+ SiLU)
+        conv(name + ".conv", cout, cin // groups, k, gain)
+        if bias:
+            sd[name + ".conv.bias"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.weight"] = (0.9 + 0.2 * rand(cout)).float()
+        sd[name + ".bn.bias"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_mean"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_var"] = (0.8 + 0.4 * rand(cout)).float()
+        sd[name + ".bn.num_batches_tracked"] = torch.zeros(1)
+
+    def bottleneck(name, c1, c2, e):
+        c_ = int(c2 * e)
+        cb(name + ".cv1", c_, c1, 3)
+        cb(name + ".cv2", c2, c_, 3)
+
+    def c3k_block(name, c1, c2, n, e=0.5):
+        c_ = int(c2 * e)
+        cb(name + ".cv1", c_, c1, 1)
+        cb(name + ".cv2", c_, c1, 1)
+        for i in range(n):
+            bottleneck(f"{name}.m.{i}", c_, c_, 1.0)
+        cb(name + ".cv3", c2, 2 * c_, 1)
+
+    def c3k2(name, c1, c2, n, use_c3k, e):
+        c_ = int(c2 * e)
+        cb(name + ".cv1", 2 * c_, c1, 1)
+        for i in range(n):
+            if use_c3k:
+                c3k_block(f"{name}.m.{i}", c_, c_, 2)
+            else:
+                bottleneck(f"{name}.m.{i}", c_, c_, 0.5)
+        cb(name + ".cv2", c2, (2 + n) * c_, 1)
+
+    def a2c2f(name, c1, c2, a2):
+        c = 2 * int(c2 * 0.25)   # the channel count everything inside works on
+        cb(name + ".cv1", c, c1, 1)
+        if a2:
+            for m in (f"{name}.m.0.0", f"{name}.m.0.1", f"{name}.m.1.0", f"{name}.m.1.1"):
+                cb(m + ".attn.qkv", 3 * c, c, 1)
+                qk = sd[m + ".attn.qkv.conv.weight"].view(c // 32, 3, 32, c)   # per head: 32 q rows, 32 k rows, 32 v rows
+                # the first block of a stage reads cv1's SiLU output, whose common positive mean makes all keys look alike: four times the gain
+                qk[:, :2] *= math.sqrt(YOLO12_QKV_GAIN * (4.0 if m.endswith(".m.0.0") else 1.0) / 2.0)
+                cb(m + ".attn.pe", c, c, 7, groups=c, gain=1.0, bias=True)
+                cb(m + ".attn.proj", c, c, 1, gain=0.1)    # the two residual branches of the eight blocks in a row stay small against
+                cb(m + ".mlp.0", 2 * c, c, 1)              # the stream they add to, so it keeps its magnitude to the last block
+                cb(m + ".mlp.1", c, 2 * c, 1, gain=0.1)
+            cb(name + ".cv2", c2, 3 * c, 1)
+        else:
+            c3k_block(name + ".m.0", c, c, 2)
+            cb(name + ".cv2", c2, 2 * c, 1)
+
+    cb("model.0", W(64), 3, 3)
+    cb("model.1", W(128), W(64), 3)
+    c3k2("model.2", W(128), W(256), D(2), c3k, 0.25)
+    cb("model.3", W(256), W(256), 3)
+    c3k2("model.4", W(256), W(512), D(2), c3k, 0.25)
+    cb("model.5", W(512), W(512), 3)
+    a2c2f("model.6", W(512), W(512), True)
+    cb("model.7", W(1024), W(512), 3)
+    a2c2f("model.8", W(1024), W(1024), True)
+    a2c2f("model.11", W(1024) + W(512), W(512), False)
+    a2c2f("model.14", W(512) + W(512), W(256), False)
+    cb("model.15", W(256), W(256), 3)
+    a2c2f("model.17", W(256) + W(512), W(512), False)
+    cb("model.18", W(512), W(512), 3)
+    c3k2("model.20", W(512) + W(1024), W(1024), D(2), True, 0.5)
+    c2 = max(16, W(256) // 4, 64)
+    c3 = max(W(256), min(num_class, 100))
+    for lv, cin in enumerate((W(256), W(512), W(1024))):
+        cb(f"model.21.cv2.{lv}.0", c2, cin, 3)
+        cb(f"model.21.cv2.{lv}.1", c2, c2, 3)
+        conv(f"model.21.cv2.{lv}.2", 64, c2, 1, gain=4.0)
+        sd[f"model.21.cv2.{lv}.2.bias"] = (1.0 + 0.1 * randn(64)).float()
+        cb(f"model.21.cv3.{lv}.0.0", cin, cin, 3, groups=cin, gain=1.0)
+        cb(f"model.21.cv3.{lv}.0.1", c3, cin, 1)
+        cb(f"model.21.cv3.{lv}.1.0", c3, c3, 3, groups=c3, gain=1.0)
+        cb(f"model.21.cv3.{lv}.1.1", c3, c3, 1)
+        conv(f"model.21.cv3.{lv}.2", num_class, c3, 1, gain=800.0)
+        sd[f"model.21.cv3.{lv}.2.bias"] = (-8.0 + 0.1 * randn(num_class)).float()
+        if lv == 0:
+            sd["model.21.dfl.conv.weight"] = torch.arange(16.0).reshape(1, 16, 1, 1)
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
+
+
 class _Draw:
     """Seeded tensor provider of the synthetic-weight generators below: the draw order and distributions are those of the test-suite's
     generator (oracle/models_torch.py run in init mode), so both write the same file - tests/test_runtime_cpu.py asserts it per model.
