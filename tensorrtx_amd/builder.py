@@ -9,8 +9,11 @@ from .capi import check, lib
 from .engine import Dims
 
 P_STRIDE, P_PADDING, P_DILATION, P_GROUPS, P_KERNEL, P_NB_OUT = 1, 2, 3, 4, 15, 16
+TRTX_P_ALPHA, TRTX_P_RESIZE_SCALES, TRTX_P_RESIZE_OUT_DIMS, TRTX_P_AVG_EXCLUSIVE = 5, 12, 13, 14
 TRTX_P_AXIS, TRTX_P_RESHAPE, TRTX_P_FIRST_TRANSPOSE, TRTX_P_SECOND_TRANSPOSE = 7, 8, 9, 10
 ACT = {"relu": 0, "sigmoid": 1, "tanh": 2, "leaky": 3}
+EW = {"sum": 0, "prod": 1, "max": 2, "min": 3, "sub": 4, "div": 5, "pow": 6}
+REDUCE = {"sum": 0, "max": 2, "avg": 4}
 FLAG_FP16, FLAG_INT8 = 0, 1
 
 
@@ -59,10 +62,11 @@ class Network:
         arr = (ctypes.c_int32 * 2)(v, v) if np.isscalar(v) else (ctypes.c_int32 * 2)(*v)
         check(self.L.trtx_layer_set_ints(self.n, layer, param, arr, 2), "trtx_layer_set_ints")
 
-    def conv(self, x, w, bias=None, stride=1, padding=0, deconv=False, groups=1):
-        """w: KCRS (conv, C = input channels / groups) or CKRS (deconv) fp32 numpy; returns the layer index"""
+    def conv(self, x, w, bias=None, stride=1, padding=0, deconv=False, groups=1, dilation=1):
+        """w: KCRS (conv, C = input channels / groups) or CKRS (deconv, K = output channels / groups) fp32 numpy; stride, padding and
+        dilation: one int or (h, w); returns the layer index"""
         w = np.ascontiguousarray(w, dtype=np.float32)
-        nb_out = w.shape[1] if deconv else w.shape[0]
+        nb_out = w.shape[1] * groups if deconv else w.shape[0]
         wa, wp, wn = _f(w)
         ba, bp, bn = _f(bias)
         self._keep += [wa, ba]
@@ -70,12 +74,18 @@ class Network:
         l = self._layer(fn(self.n, x, nb_out, w.shape[2], w.shape[3], wp, ctypes.c_int64(wn), bp, ctypes.c_int64(bn)), "add_conv")
         self._set2(l, P_STRIDE, stride)
         self._set2(l, P_PADDING, padding)
+        if not np.isscalar(dilation) or dilation != 1:
+            self._set2(l, P_DILATION, dilation)
         if groups != 1:
             check(self.L.trtx_layer_set_ints(self.n, l, P_GROUPS, (ctypes.c_int32 * 1)(groups), 1), "trtx_layer_set_ints(groups)")
         return l
 
-    def activation(self, x, kind):
-        return self._layer(self.L.trtx_add_activation(self.n, x, ACT[kind]), "add_activation")
+    def activation(self, x, kind, alpha=None):
+        """IActivationLayer; alpha: setAlpha (the slope of kLEAKY_RELU; the layer's default is 0.01)"""
+        l = self._layer(self.L.trtx_add_activation(self.n, x, ACT[kind]), "add_activation")
+        if alpha is not None:
+            check(self.L.trtx_layer_set_floats(self.n, l, TRTX_P_ALPHA, (ctypes.c_float * 1)(float(alpha)), 1), "trtx_layer_set_floats(alpha)")
+        return l
 
     def scale(self, x, shift, scale, power=None):
         """IScaleLayer, ScaleMode::kCHANNEL (a folded BatchNorm, e.g. addBatchNorm2d of yolov4/yolov4.cpp:181-197)"""
@@ -102,21 +112,54 @@ class Network:
         destroy(vt[0])
         return l
 
-    def pooling(self, x, k, stride, padding=0, avg=False):
-        l = self._layer(self.L.trtx_add_pooling(self.n, x, 1 if avg else 0, k, k), "add_pooling")
+    def pooling(self, x, k, stride, padding=0, avg=False, avg_exclusive=None):
+        """IPoolingLayer; k, stride, padding: one int or (h, w); avg_exclusive: setAverageCountExcludesPadding"""
+        kh, kw = (k, k) if np.isscalar(k) else k
+        l = self._layer(self.L.trtx_add_pooling(self.n, x, 1 if avg else 0, kh, kw), "add_pooling")
         self._set2(l, P_STRIDE, stride)
         self._set2(l, P_PADDING, padding)
+        if avg_exclusive is not None:
+            check(self.L.trtx_layer_set_ints(self.n, l, TRTX_P_AVG_EXCLUSIVE, (ctypes.c_int32 * 1)(int(avg_exclusive)), 1),
+                  "trtx_layer_set_ints(avg_exclusive)")
         return l
 
     def elementwise(self, a, b, op=0):
-        return self._layer(self.L.trtx_add_elementwise(self.n, a, b, op), "add_elementwise")
+        """IElementWiseLayer; op: an ElementWiseOperation code or its name in EW"""
+        return self._layer(self.L.trtx_add_elementwise(self.n, a, b, EW.get(op, op)), "add_elementwise")
 
-    def resize_nearest(self, x, scale=2):
-        """IResizeLayer, nearest, integer scale on H and W (setScales({1, s, s}))"""
+    def resize_nearest(self, x, scale=2, out_dims=None):
+        """IResizeLayer, nearest: integer scale on H and W (setScales({1, s, s})), or out_dims = the full output dims (setOutputDimensions)"""
         l = self._layer(self.L.trtx_add_resize(self.n, x), "add_resize")
+        if out_dims is not None:
+            d = _dims(out_dims)
+            check(self.L.trtx_layer_set_dims(self.n, l, TRTX_P_RESIZE_OUT_DIMS, ctypes.byref(d)), "trtx_layer_set_dims(resize out dims)")
+            return l
         sc = (ctypes.c_float * 3)(1.0, float(scale), float(scale))
-        check(self.L.trtx_layer_set_floats(self.n, l, 12, sc, 3), "trtx_layer_set_floats(resize scales)")   # TRTX_P_RESIZE_SCALES
+        check(self.L.trtx_layer_set_floats(self.n, l, TRTX_P_RESIZE_SCALES, sc, 3), "trtx_layer_set_floats(resize scales)")
         return l
+
+    def reduce(self, x, op, axes, keep_dims=False):
+        """IReduceLayer; op: "sum" / "avg" / "max"; axes: bit mask over the tensor's dims"""
+        self.L.trtx_add_reduce.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32]
+        return self._layer(self.L.trtx_add_reduce(self.n, x, REDUCE.get(op, op), int(axes), int(bool(keep_dims))), "add_reduce")
+
+    def fully_connected(self, x, w, bias=None):
+        """IFullyConnectedLayer on a (C, H, W) tensor; w: (nb_out, C * H * W)"""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        wa, wp, wn = _f(w)
+        ba, bp, bn = _f(bias)
+        self._keep += [wa, ba]
+        return self._layer(self.L.trtx_add_fully_connected(self.n, x, w.shape[0], wp, ctypes.c_int64(wn), bp, ctypes.c_int64(bn)), "add_fully_connected")
+
+    def constant(self, values):
+        """IConstantLayer: a tensor of values.shape (no batch dimension in an implicit-batch network)"""
+        va, vp, vn = _f(values)
+        self._keep.append(va)
+        d = _dims(va.shape)
+        return self._layer(self.L.trtx_add_constant(self.n, ctypes.byref(d), vp, ctypes.c_int64(vn)), "add_constant")
+
+    def identity(self, x):
+        return self._layer(self.L.trtx_add_identity(self.n, x), "add_identity")
 
     def slice_channels(self, x, start, size, chw):
         """ISliceLayer over the channel axis of a (C, H, W) tensor: channels [start, start + size) (block.cpp:134-149, the C2f split)"""
@@ -151,17 +194,21 @@ class Network:
         """IMatrixMultiplyLayer, MatrixOperation kNONE / kTRANSPOSE"""
         return self._layer(self.L.trtx_add_matrix_multiply(self.n, a, int(transpose_a), b, int(transpose_b)), "add_matrix_multiply")
 
-    def scale_uniform(self, x, scale, shift=0.0):
+    def scale_uniform(self, x, scale, shift=0.0, power=1.0):
         """IScaleLayer, ScaleMode::kUNIFORM (the Attention's score scale, yolo11/src/block.cpp:313-324)"""
         sa, sp, sn = _f(np.array([shift]))
         ca, cp, cn = _f(np.array([scale]))
-        pa, pp, pn = _f(np.array([1.0]))
+        pa, pp, pn = _f(np.array([power]))
         self._keep += [sa, ca, pa]
         return self._layer(self.L.trtx_add_scale(self.n, x, 0, sp, ctypes.c_int64(sn), cp, ctypes.c_int64(cn), pp, ctypes.c_int64(pn)), "add_scale")
 
-    def concat(self, tensors):
+    def concat(self, tensors, axis=None):
+        """IConcatenationLayer; axis: setAxis (None keeps the default, the channel axis)"""
         arr = (ctypes.c_int32 * len(tensors))(*tensors)
-        return self._layer(self.L.trtx_add_concatenation(self.n, arr, len(tensors)), "add_concatenation")
+        l = self._layer(self.L.trtx_add_concatenation(self.n, arr, len(tensors)), "add_concatenation")
+        if axis is not None:
+            check(self.L.trtx_layer_set_ints(self.n, l, TRTX_P_AXIS, (ctypes.c_int32 * 1)(axis), 1), "trtx_layer_set_ints(axis)")
+        return l
 
     def mark_output(self, tensor, name):
         check(self.L.trtx_tensor_set_name(self.n, tensor, name.encode()), "set_name")
