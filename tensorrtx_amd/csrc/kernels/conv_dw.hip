@@ -9,7 +9,7 @@
 // consecutive channel vectors of a pixel first, so a wave's loads are contiguous runs of the pixel's channels.  fp32 accumulation,
 // summed in the direct kernel's order (bias first, then taps row by row); the direct kernel's epilogue: act1, + residual, act2.
 //
-// Weights: fp32 [kh*kw][C] (tap-major, the folded BN scale applied; runtime/lower.cpp pack_weights), bias fp32 [C].
+// Weights: fp32 [kh*kw][C] (tap-major, the folded BN scale applied; runtime/pack.cpp pack_weights), bias fp32 [C].
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <math.h>

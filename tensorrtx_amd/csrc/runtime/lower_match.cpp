@@ -1,0 +1,458 @@
+// The lowering's graph matchers.  See lower_match.h.
+#include "lower_match.h"
+
+#include <algorithm>
+
+namespace trtx {
+
+int act_code(int trt_type) {
+    switch (trt_type) {
+        case TRTX_ACTIVATION_RELU: return ACT_RELU;
+        case TRTX_ACTIVATION_SIGMOID: return ACT_SIGMOID;
+        case TRTX_ACTIVATION_TANH: return ACT_TANH;
+        case TRTX_ACTIVATION_LEAKY_RELU: return ACT_LEAKY;
+        default: return -1;
+    }
+}
+
+NetView::NetView(const Network& n) : net(n), dt(n.fp16 ? DT_F16 : DT_F32), consumers(n.tensors.size()) {
+    for (size_t li = 0; li < n.layers.size(); ++li)
+        for (int t : n.layers[li].inputs) consumers[t].push_back((int)li);
+}
+
+bool NetView::only_used_by(int tensor, std::initializer_list<int> layers) const {
+    if (net.tensors[tensor].is_output) return false;
+    std::vector<int> want(layers), have(consumers[tensor]);
+    std::sort(want.begin(), want.end());
+    std::sort(have.begin(), have.end());
+    return want == have;
+}
+
+namespace {
+
+// ---- Conv (+ Scale) (+ activation) (+ residual (+ activation)) -> one fused convolution ---------------------
+void match_conv_fusion(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (l.kind != L_CONV && l.kind != L_FULLY_CONNECTED) continue;
+        if (f.absorbed[li]) continue;  // already claimed (fused YOLO head)
+        if (!g.spatial(net.tensors[l.inputs[0]].dims)) continue;
+        FusedConv c;
+        c.conv_layer = (int)li;
+        int t = l.outputs[0], last = (int)li, nx;
+        auto take = [&](int layer, int out) {   // `layer` joins the fused op, whose result is now tensor `out`
+            f.absorbed[layer] = true;
+            t = out;
+            last = std::max(last, layer);
+        };
+        // Conv -> Scale (BatchNorm folded by the host code, block.cpp:45-77)
+        if (g.sole_consumer(t, &nx) && !f.absorbed[nx] && net.layers[nx].kind == L_SCALE && net.layers[nx].op != TRTX_SCALE_ELEMENTWISE) {
+            const LayerDef& s = net.layers[nx];
+            bool pow1 = true;
+            for (float p : s.w2) pow1 = pow1 && p == 1.0f;
+            if (pow1) {
+                c.scale_layer = nx;
+                take(nx, s.outputs[0]);
+            }
+        }
+        // SiLU spelled as Sigmoid + Prod (block.cpp:91-94), or a plain activation
+        if (!net.tensors[t].is_output && g.consumers[t].size() == 2) {
+            int a = g.consumers[t][0], b = g.consumers[t][1];
+            if (net.layers[a].kind != L_ACTIVATION) std::swap(a, b);
+            const LayerDef &la = net.layers[a], &lb = net.layers[b];
+            if (la.kind == L_ACTIVATION && la.op == TRTX_ACTIVATION_SIGMOID && lb.kind == L_ELEMENTWISE &&
+                lb.op == TRTX_ELEMENTWISE_PROD && a != b && !f.absorbed[a] && !f.absorbed[b]) {
+                const int so = la.outputs[0];
+                const bool uses = (lb.inputs[0] == t && lb.inputs[1] == so) || (lb.inputs[1] == t && lb.inputs[0] == so);
+                int only;
+                if (uses && g.sole_consumer(so, &only) && only == b) {
+                    c.act1 = ACT_SILU;
+                    take(a, lb.outputs[0]);
+                    take(b, lb.outputs[0]);
+                }
+            }
+        } else if (g.sole_consumer(t, &nx) && !f.absorbed[nx] && net.layers[nx].kind == L_ACTIVATION && act_code(net.layers[nx].op) >= 0) {
+            c.act1 = act_code(net.layers[nx].op);
+            c.alpha1 = net.layers[nx].alpha;
+            take(nx, net.layers[nx].outputs[0]);
+        } else if (g.sole_consumer(t, &nx) && !f.absorbed[nx] && g.is_builtin_mish(nx)) {
+            // Conv -> Scale(BN) -> Mish_TRT (convBnMish, yolov4/yolov4.cpp:199-213): the plugin is a pointwise activation
+            c.act1 = ACT_MISH;
+            take(nx, net.layers[nx].outputs[0]);
+        }
+        // + residual (block.cpp:104-108 ; resnet50.cpp:146), then an optional trailing activation
+        if (g.sole_consumer(t, &nx) && !f.absorbed[nx] && net.layers[nx].kind == L_ELEMENTWISE && net.layers[nx].op == TRTX_ELEMENTWISE_SUM) {
+            const LayerDef& e = net.layers[nx];
+            const int other = e.inputs[0] == t ? e.inputs[1] : e.inputs[0];
+            if (other != t && net.tensors[other].dims == net.tensors[t].dims) {
+                c.residual = other;
+                take(nx, e.outputs[0]);
+                int n2;
+                if (g.sole_consumer(t, &n2) && !f.absorbed[n2] && net.layers[n2].kind == L_ACTIVATION && act_code(net.layers[n2].op) >= 0) {
+                    c.act2 = act_code(net.layers[n2].op);
+                    c.alpha2 = net.layers[n2].alpha;
+                    take(n2, net.layers[n2].outputs[0]);
+                }
+            }
+        }
+        c.out_tensor = t;
+        c.emit_at = last;
+        f.absorbed[li] = true;
+        f.group_at[last] = (int)f.groups.size();
+        f.groups.push_back(c);
+    }
+}
+
+// Activation applied to a concatenation of un-activated convolution outputs (RetinaFace SSH, retina_r50.cpp:87-98):
+// relu(cat(a, b, c)) == cat(relu a, relu b, relu c), so the activation moves into the producers' epilogues (it edits the records of
+// match_conv_fusion) and the concat output is used as is.
+void match_concat_activation(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (l.kind != L_CONCAT || f.absorbed[li]) continue;
+        int nx;
+        if (!g.sole_consumer(l.outputs[0], &nx) || f.absorbed[nx] || net.layers[nx].kind != L_ACTIVATION) continue;
+        const int code = act_code(net.layers[nx].op);
+        if (code < 0) continue;
+        std::vector<int> gs;
+        bool ok = true;
+        for (int t : l.inputs) {
+            int gi = -1;
+            for (size_t k = 0; k < f.groups.size(); ++k)
+                if (f.groups[k].out_tensor == t) gi = (int)k;
+            int only;
+            ok = ok && gi >= 0 && f.groups[gi].act1 == ACT_NONE && f.groups[gi].residual < 0 && f.groups[gi].act2 == ACT_NONE &&
+                 g.sole_consumer(t, &only) && only == (int)li;
+            gs.push_back(gi);
+        }
+        if (!ok) continue;
+        for (int gi : gs) {
+            f.groups[gi].act1 = code;
+            f.groups[gi].alpha1 = net.layers[nx].alpha;
+        }
+        f.absorbed[nx] = true;
+        f.aliases.push_back({net.layers[nx].outputs[0], l.outputs[0]});
+    }
+}
+
+// ---- YOLOv8 detect tail: flatten -> slice -> DFL(shuffle, softmax, 1x1 conv, shuffle) -> concat -> YoloLayer_TRT
+// (yolov8/src/model.cpp:263-303, block.cpp:239-257) collapses into one fused kernel when the plugin is the
+// built-in one and every intermediate tensor has no other use.  Explicit batch (YOLO11, yolo11/src/model.cpp:336-390): the same graph
+// with a leading batch dimension B on every tensor; e = 1 shifts every per-sample axis, and each tensor's dim 0 must be that B (full,
+// unsliced).  One level of it, from the two first inputs of the head concat `lc`: ta = DFL(slice [0, 64) of the flattened head),
+// tb = slice [64, 64 + classes) of it.
+bool match_dfl_classes(const NetView& g, int lc, int ta, int tb, int64_t B, int classes, int* head, int* conv_layer, std::vector<int>* used) {
+    const Network& net = g.net;
+    const int e = net.explicit_batch ? 1 : 0;
+    // box branch
+    const int lsh2 = g.producer(ta);
+    if (lsh2 < 0 || net.layers[lsh2].kind != L_SHUFFLE || !g.only_used_by(ta, {lc})) return false;
+    const LayerDef& sh2 = net.layers[lsh2];
+    const Dims& d2 = net.tensors[ta].dims;
+    if (d2.nb != 2 + e || (e && d2.d[0] != B) || d2.d[e] != 4 || !ident(sh2.perm1, 3 + e) || !ident(sh2.perm2, 2 + e)) return false;
+    const int64_t ng = d2.d[1 + e];
+    const int tconv = sh2.inputs[0];
+    const int lconv = g.producer(tconv);
+    if (lconv < 0 || net.layers[lconv].kind != L_CONV || !g.only_used_by(tconv, {lsh2})) return false;
+    const LayerDef& cv = net.layers[lconv];
+    if (cv.nb_out != 1 || cv.kernel[0] != 1 || cv.kernel[1] != 1 || cv.groups != 1 || cv.stride[0] != 1 || cv.stride[1] != 1 ||
+        cv.padding[0] != 0 || cv.padding[1] != 0 || cv.w0.size() != 16 || !cv.w1.empty())
+        return false;
+    const int tsm = cv.inputs[0];
+    const int lsm = g.producer(tsm);
+    if (lsm < 0 || net.layers[lsm].kind != L_SOFTMAX || !g.only_used_by(tsm, {lconv})) return false;
+    if (!(net.layers[lsm].axis < 0 || net.layers[lsm].axis == (1 << e))) return false;
+    const int tsh1 = net.layers[lsm].inputs[0];
+    const int lsh1 = g.producer(tsh1);
+    if (lsh1 < 0 || net.layers[lsh1].kind != L_SHUFFLE || !g.only_used_by(tsh1, {lsm})) return false;
+    const LayerDef& sh1 = net.layers[lsh1];
+    const Dims& d1 = net.tensors[tsh1].dims;
+    if (d1.nb != 3 + e || (e && d1.d[0] != B) || d1.d[e] != 16 || d1.d[1 + e] != 4 || d1.d[2 + e] != ng) return false;
+    if (!ident(sh1.perm1, 2 + e) || sh1.reshape.nb != 3 + e || (e && sh1.perm2[0] != 0) || sh1.perm2[e] != 1 + e || sh1.perm2[1 + e] != e ||
+        sh1.perm2[2 + e] != 2 + e)
+        return false;
+    const int tsa = sh1.inputs[0];
+    const int lsa = g.producer(tsa);
+    if (lsa < 0 || net.layers[lsa].kind != L_SLICE || !g.only_used_by(tsa, {lsh1})) return false;
+    const LayerDef& sa = net.layers[lsa];
+    auto lead_ok = [&](const LayerDef& sl) { return !e || (sl.start.d[0] == 0 && sl.size.d[0] == B && sl.step.d[0] == 1); };
+    if (sa.start.nb != 2 + e || !lead_ok(sa) || sa.start.d[e] != 0 || sa.start.d[1 + e] != 0 || sa.size.d[e] != 64 || sa.size.d[1 + e] != ng ||
+        sa.step.d[e] != 1 || sa.step.d[1 + e] != 1)
+        return false;
+    // class branch
+    const int lsb = g.producer(tb);
+    if (lsb < 0 || net.layers[lsb].kind != L_SLICE || !g.only_used_by(tb, {lc})) return false;
+    const LayerDef& sb = net.layers[lsb];
+    if (sb.start.nb != 2 + e || !lead_ok(sb) || sb.start.d[e] != 64 || sb.start.d[1 + e] != 0 || sb.size.d[e] != classes ||
+        sb.size.d[1 + e] != ng || sb.step.d[e] != 1 || sb.step.d[1 + e] != 1 || sb.inputs[0] != sa.inputs[0])
+        return false;
+    const int tflat = sa.inputs[0];
+    const int lflat = g.producer(tflat);
+    if (lflat < 0 || net.layers[lflat].kind != L_SHUFFLE || !g.only_used_by(tflat, {lsa, lsb})) return false;
+    const LayerDef& fl = net.layers[lflat];
+    const Dims& dx = net.tensors[fl.inputs[0]].dims;
+    if (!ident(fl.perm1, 3 + e) || !ident(fl.perm2, 2 + e) || !g.spatial(dx) || (e && dx.d[0] != B) || dx.d[e] != 64 + classes ||
+        dx.d[1 + e] * dx.d[2 + e] != ng)
+        return false;
+    *head = fl.inputs[0];
+    *conv_layer = lconv;
+    for (int l : {lc, lsh2, lconv, lsm, lsh1, lsa, lsb, lflat}) used->push_back(l);
+    return true;
+}
+
+// One loop for both fused heads (fp16 and fp32 engines: the kernel reads either element type):
+//  - OP_YOLO_HEAD (task = false; implicit and explicit batch): each plugin input is the concat of [DFL chain, class slice] above.
+//  - OP_YOLO_TASK_HEAD (task = true), the YOLO11 seg / pose / obb tail (yolo11/src/model.cpp:595-756, 960-1060, 1265-1358), explicit batch
+//    only: each plugin input is the axis-1 concat of [DFL chain, class slice, the cv4 branch reshaped (B, extra, H, W) -> (B, extra, g)].
+//    The branch convolution keeps its NHWC output, which the fused op reads next to the head (extra_in).
+// The parameter gates are disjoint (det_only = none of seg / pose / obb), so a plugin layer is claimed by at most one of the two.
+void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
+    const Network& net = g.net;
+    const int e = net.explicit_batch ? 1 : 0;
+    if (task && !e) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li]) continue;
+        YoloHeadFuse h;
+        if (!builtin_yolo_params(l.plugin->v, &h.params)) continue;
+        const YoloLayerParams& pr = h.params;
+        if (pr.strides.size() != l.inputs.size()) continue;
+        if (task ? (pr.seg + pr.pose + pr.obb != 1 || l.inputs.size() > 4 || (pr.pose && (pr.nk < 1 || pr.nk > 17)))
+                 : (!pr.det_only || pr.classes % 8 || l.inputs.size() > 6))
+            continue;
+        const int64_t extra = pr.seg ? 32 : (pr.pose ? 3 * pr.nk : 1);
+        std::vector<int> used;
+        bool ok = true;
+        for (size_t k = 0; ok && k < l.inputs.size(); ++k) {
+            const int t_in = l.inputs[k];
+            const int64_t B = e ? net.tensors[t_in].dims.d[0] : 1;
+            const int lc = g.producer(t_in);
+            ok = lc >= 0 && net.layers[lc].kind == L_CONCAT && net.layers[lc].inputs.size() == (task ? 3u : 2u) && net.layers[lc].axis == e &&
+                 g.only_used_by(t_in, {(int)li}) && (!e || B == net.tensors[l.inputs[0]].dims.d[0]);
+            int head = -1, conv = -1;
+            ok = ok && match_dfl_classes(g, lc, net.layers[lc].inputs[0], net.layers[lc].inputs[1], B, pr.classes, &head, &conv, &used);
+            if (!ok) break;
+            const Dims& dh = net.tensors[head].dims;
+            ok = dh.d[1 + e] == pr.net_h / pr.strides[k] && dh.d[2 + e] == pr.net_w / pr.strides[k];
+            if (h.dfl_conv_layer >= 0 && net.layers[conv].w0 != net.layers[h.dfl_conv_layer].w0) ok = false;   // one DFL kernel for all levels
+            h.dfl_conv_layer = conv;
+            h.head_tensor.push_back(head);
+            if (!task) continue;
+            // the branch: a reshape-only shuffle of a convolution's (B, extra, H, W) output to (B, extra, H * W)
+            const int tc = net.layers[lc].inputs[2];
+            const int lsh = g.producer(tc);
+            ok = ok && lsh >= 0 && net.layers[lsh].kind == L_SHUFFLE && g.only_used_by(tc, {lc});
+            if (!ok) break;
+            const LayerDef& sh = net.layers[lsh];
+            const int tb = sh.inputs[0];
+            const Dims &dx = net.tensors[tb].dims, &dc = net.tensors[tc].dims;
+            const int lb = g.producer(tb);
+            ok = ident(sh.perm1, 4) && ident(sh.perm2, 3) && dx.nb == 4 && dc.nb == 3 && dx.d[0] == B && dc.d[0] == B && dx.d[1] == extra &&
+                 dc.d[1] == extra && dx.d[2] == dh.d[2] && dx.d[3] == dh.d[3] && dc.d[2] == dx.d[2] * dx.d[3] && lb >= 0 &&
+                 net.layers[lb].kind == L_CONV && g.only_used_by(tb, {lsh});
+            for (int u : {lc, lsh}) used.push_back(u);
+            h.branch_tensor.push_back(tb);
+        }
+        for (int u : used) ok = ok && !f.absorbed[u];
+        if (!ok) continue;
+        for (int u : used) f.absorbed[u] = true;
+        h.plugin_layer = (int)li;
+        f.absorbed[li] = true;
+        f.yolo_at[li] = (int)f.yolo_heads.size();
+        f.yolo_heads.push_back(h);
+    }
+}
+
+// ---- attention: what the YOLO11 PSA block and the YOLOv12 area attention share, from the first matmul to the second one:
+// x (B', heads, 2kd+hd, N') -> q / k / v slices of rows -> q^T k -> uniform scale -> softmax over the keys -> v @ attn^T.
+// Every shape, permutation, slice and the scale are checked and q, k and the scores must have no other reader.  How the qkv image
+// becomes x, and how O and v (which has exactly one more reader) become images again, is each caller's part.
+struct AttentionCore {
+    int lq, lk, lv, lqt, m1, lsc, lsm, lat, m2;   // the layers, all claimed by the fused op
+    int tx;                                       // network tensor x
+    int64_t kd, hd;
+    float scale;
+};
+bool transpose_only(const LayerDef& l, std::initializer_list<int> p) {   // a shuffle that is one first transpose of a 4-d tensor
+    return l.kind == L_SHUFFLE && l.reshape.nb == 0 && perm_is(l.perm1, p) && ident(l.perm2, 4);
+}
+bool plain_matmul(const LayerDef& l) { return l.kind == L_MATMUL && l.mm_op[0] == TRTX_MATMUL_NONE && l.mm_op[1] == TRTX_MATMUL_NONE; }
+
+bool match_attention_core(const NetView& g, int li, AttentionCore* c) {
+    const Network& net = g.net;
+    const LayerDef& m1 = net.layers[li];
+    if (!plain_matmul(m1)) return false;
+    c->m1 = li;
+    const int lqt = c->lqt = g.producer(m1.inputs[0]), lk = c->lk = g.producer(m1.inputs[1]);
+    if (lqt < 0 || lk < 0 || !transpose_only(net.layers[lqt], {0, 1, 3, 2}) || net.layers[lk].kind != L_SLICE) return false;
+    const int lq = c->lq = g.producer(net.layers[lqt].inputs[0]);
+    if (lq < 0 || net.layers[lq].kind != L_SLICE) return false;
+    const int tx = c->tx = net.layers[lq].inputs[0];
+    const Dims& dx = net.tensors[tx].dims;
+    if (net.layers[lk].inputs[0] != tx || dx.nb != 4) return false;
+    auto slice_rows = [&](const LayerDef& sl, int64_t r0, int64_t nr) {   // rows [r0, r0 + nr) of every head, everything else whole
+        return sl.start.nb == 4 && sl.start.d[0] == 0 && sl.start.d[1] == 0 && sl.start.d[2] == r0 && sl.start.d[3] == 0 && sl.size.d[0] == dx.d[0] &&
+               sl.size.d[1] == dx.d[1] && sl.size.d[2] == nr && sl.size.d[3] == dx.d[3] && sl.step.d[0] == 1 && sl.step.d[1] == 1 && sl.step.d[2] == 1 &&
+               sl.step.d[3] == 1;
+    };
+    const int64_t kd = c->kd = net.layers[lq].size.d[2];
+    const int64_t hd = c->hd = dx.d[2] - 2 * kd;
+    if (!slice_rows(net.layers[lq], 0, kd) || !slice_rows(net.layers[lk], kd, kd) || hd < 1) return false;
+    // the v slice: the third reader of x
+    int lv = -1;
+    for (int r : g.consumers[tx])
+        if (r != lq && r != lk) lv = r;
+    c->lv = lv;
+    if (lv < 0 || net.layers[lv].kind != L_SLICE || !slice_rows(net.layers[lv], 2 * kd, hd) || !g.only_used_by(tx, {lq, lk, lv})) return false;
+    // scale -> softmax -> transpose -> second matmul
+    if (!g.sole_consumer(m1.outputs[0], &c->lsc) || net.layers[c->lsc].kind != L_SCALE || net.layers[c->lsc].op != TRTX_SCALE_UNIFORM) return false;
+    const LayerDef& sc = net.layers[c->lsc];
+    if (sc.w1.size() != 1 || (!sc.w0.empty() && (sc.w0.size() != 1 || sc.w0[0] != 0.f)) || (!sc.w2.empty() && (sc.w2.size() != 1 || sc.w2[0] != 1.f)))
+        return false;
+    c->scale = sc.w1[0];
+    if (!g.sole_consumer(sc.outputs[0], &c->lsm) || net.layers[c->lsm].kind != L_SOFTMAX || net.layers[c->lsm].axis != (1 << 3)) return false;
+    if (!g.sole_consumer(net.layers[c->lsm].outputs[0], &c->lat) || !transpose_only(net.layers[c->lat], {0, 1, 3, 2})) return false;
+    const int t_at = net.layers[c->lat].outputs[0];
+    if (!g.sole_consumer(t_at, &c->m2)) return false;
+    const LayerDef& mm2 = net.layers[c->m2];
+    if (!plain_matmul(mm2) || mm2.inputs[1] != t_at || mm2.inputs[0] != net.layers[lv].outputs[0]) return false;
+    return g.only_used_by(m1.inputs[0], {li}) && g.only_used_by(m1.inputs[1], {li}) && g.only_used_by(net.layers[lqt].inputs[0], {lqt});
+}
+// Claims the core's layers and the caller's `own` ones for one OP_ATTENTION, emitted at the last of them - unless one of them is
+// already claimed or produces a network output.
+void claim_attention(const NetView& g, const AttentionCore& c, std::vector<int> own, AttentionFuse a, Fusions& f) {
+    for (int u : {c.lq, c.lk, c.lv, c.lqt, c.m1, c.lsc, c.lsm, c.lat, c.m2}) own.push_back(u);
+    for (int u : own)
+        if (f.absorbed[u] || g.net.tensors[g.net.layers[u].outputs[0]].is_output) return;
+    a.heads = (int)g.net.tensors[c.tx].dims.d[1];
+    a.kd = (int)c.kd;
+    a.hd = (int)c.hd;
+    a.scale = c.scale;
+    int at = 0;
+    for (int u : own) {
+        f.absorbed[u] = true;
+        at = std::max(at, u);
+    }
+    f.attn_at[at] = (int)f.attns.size();
+    f.attns.push_back(a);
+}
+
+// ---- YOLO11 PSA attention (yolo11/src/block.cpp:287-339): qkv -> view (B, heads, 2kd+hd, N) -> the core above -> view
+// (B, heads*hd, H, W), and v viewed the same way for `pe`.  Anything else keeps the generic linear path.
+// fp16 engines only (fp32 engines, the tolerance build, keep the generic path).
+void match_psa_attention(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (!net.explicit_batch || g.dt != DT_F16) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        AttentionCore c;
+        if (f.absorbed[li] || !match_attention_core(g, (int)li, &c)) continue;
+        // the way in: one reshape-only view of the qkv image
+        const int lview = g.producer(c.tx);
+        if (lview < 0 || net.layers[lview].kind != L_SHUFFLE || !ident(net.layers[lview].perm1, 4) || !ident(net.layers[lview].perm2, 4)) continue;
+        const int tqkv = net.layers[lview].inputs[0];
+        const Dims &dx = net.tensors[c.tx].dims, &dq = net.tensors[tqkv].dims;
+        if (dq.nb != 4 || dx.d[0] != dq.d[0] || dx.d[3] != dq.d[2] * dq.d[3] || dx.d[1] * dx.d[2] != dq.d[1]) continue;
+        // the way out: O's only reader and v's other reader
+        int lre, lvre = -1;
+        if (!g.sole_consumer(net.layers[c.m2].outputs[0], &lre)) continue;
+        const int tv = net.layers[c.lv].outputs[0];
+        for (int r : g.consumers[tv])
+            if (r != c.m2) lvre = r;
+        if (lvre < 0 || !g.only_used_by(tv, {c.m2, lvre})) continue;
+        auto view_bchw = [&](int l) {   // reshape (B, heads*hd, H, W) of a (B, heads, hd, N) tensor, no transposes
+            const LayerDef& r = net.layers[l];
+            const Dims& o = net.tensors[r.outputs[0]].dims;
+            return r.kind == L_SHUFFLE && ident(r.perm1, 4) && ident(r.perm2, 4) && r.reshape.nb == 4 && o.nb == 4 && o.d[0] == dx.d[0] &&
+                   o.d[1] == dx.d[1] * c.hd && o.d[2] == dq.d[2] && o.d[3] == dq.d[3];
+        };
+        if (!view_bchw(lre) || !view_bchw(lvre) || !psa_attention_supported((int)c.kd, (int)c.hd)) continue;
+        AttentionFuse a;
+        a.qkv = tqkv;
+        a.out_o = net.layers[lre].outputs[0];
+        a.out_v = net.layers[lvre].outputs[0];
+        a.N = (int)dx.d[3];
+        claim_attention(g, c, {lview, lre, lvre}, a, f);
+    }
+}
+
+// ---- YOLOv12 area attention (yolov12/src/block.cpp:522-625): qkv (B, heads*96, H, W) -> [reshape (B, -1, N), transpose {0,2,1}] ->
+// [reshape (B area, N / area, heads, 96), transpose {0,2,3,1}] -> the core above on q / k / v slices of 32 rows -> transpose {0,3,1,2}
+// -> reshape (B, H, W, C) -> transpose {0,3,1,2}, and v through the same three shuffles for `pe`.  In NHWC that is: area a = the
+// pixel range [a N/area, (a+1) N/area) of an image, head h = channels h*96 + {q | k | v}.  Anything else keeps the generic linear
+// path.  fp16 explicit-batch engines only, and not with TRTX_AREA_ATTENTION=0.
+void match_area_attention(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (!net.explicit_batch || g.dt != DT_F16 || !g.opt.area_attention) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        AttentionCore c;
+        if (f.absorbed[li] || !match_attention_core(g, (int)li, &c)) continue;
+        // the way in: the two shuffles between the qkv image and the (B area, heads, 96, N / area) tensor
+        const int l2 = g.producer(c.tx);
+        if (l2 < 0 || net.layers[l2].kind != L_SHUFFLE || net.layers[l2].reshape.nb != 4 || !ident(net.layers[l2].perm1, 3) ||
+            !perm_is(net.layers[l2].perm2, {0, 2, 3, 1}))
+            continue;
+        const int tl = net.layers[l2].inputs[0];
+        const int l1 = g.producer(tl);
+        if (l1 < 0 || net.layers[l1].kind != L_SHUFFLE || net.layers[l1].reshape.nb != 3 || !ident(net.layers[l1].perm1, 4) ||
+            !perm_is(net.layers[l1].perm2, {0, 2, 1}))
+            continue;
+        const int tqkv = net.layers[l1].inputs[0];
+        const Dims &dx = net.tensors[c.tx].dims, &dl = net.tensors[tl].dims, &dq = net.tensors[tqkv].dims;
+        if (dl.nb != 3 || dq.nb != 4) continue;
+        const int64_t B = dq.d[0], C3 = dq.d[1], N = dq.d[2] * dq.d[3];
+        const int64_t Ba = dx.d[0], heads = dx.d[1], rows = dx.d[2], Na = dx.d[3];
+        if (dl.d[0] != B || dl.d[1] != N || dl.d[2] != C3 || B < 1 || Na < 1 || Ba % B != 0 || heads * rows != C3) continue;
+        const int64_t area = Ba / B;
+        if (area < 1 || Na * area != N) continue;   // the area count must divide the pixels
+        if (!g.only_used_by(tl, {l2}) || !area_attention_supported((int)c.kd, (int)c.hd)) continue;
+        // the way back to an image, for O and for v: transpose {0,3,1,2} -> reshape (B, H, W, heads*hd) -> transpose {0,3,1,2}
+        auto image_of = [&](int t_from, int skip, int* used3, int* t_img) {
+            int a = -1;
+            for (int r : g.consumers[t_from])
+                if (r != skip) a = r;
+            if (a < 0 || net.tensors[t_from].is_output || g.consumers[t_from].size() != (skip >= 0 ? 2u : 1u) || !transpose_only(net.layers[a], {0, 3, 1, 2}))
+                return false;
+            int r, b2;
+            if (!g.sole_consumer(net.layers[a].outputs[0], &r)) return false;
+            const LayerDef& re = net.layers[r];
+            const Dims& dr = net.tensors[re.outputs[0]].dims;
+            if (re.kind != L_SHUFFLE || re.reshape.nb != 4 || !ident(re.perm1, 4) || !ident(re.perm2, 4) || dr.nb != 4 || dr.d[0] != B ||
+                dr.d[1] != dq.d[2] || dr.d[2] != dq.d[3] || dr.d[3] != heads * c.hd)
+                return false;
+            if (!g.sole_consumer(re.outputs[0], &b2) || !transpose_only(net.layers[b2], {0, 3, 1, 2})) return false;
+            used3[0] = a; used3[1] = r; used3[2] = b2;
+            *t_img = net.layers[b2].outputs[0];
+            return true;
+        };
+        int uo[3], uv[3];
+        AttentionFuse a;
+        if (!image_of(net.layers[c.m2].outputs[0], -1, uo, &a.out_o) || !image_of(net.layers[c.lv].outputs[0], c.m2, uv, &a.out_v)) continue;
+        a.qkv = tqkv;
+        a.N = (int)N;
+        a.area = (int)area;
+        claim_attention(g, c, {l1, l2, uo[0], uo[1], uo[2], uv[0], uv[1], uv[2]}, a, f);
+    }
+}
+
+}  // namespace
+
+// The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
+// (before conv fusion: they claim the DFL 1x1 convolutions), PSA attention, area attention, convolution fusion, and last the
+// concat-activation rewrite, which edits the convolution records.
+Fusions match_fusions(const NetView& g) {
+    Fusions f;
+    const size_t nl = g.net.layers.size();
+    f.absorbed.assign(nl, false);
+    f.group_at = f.yolo_at = f.attn_at = std::vector<int>(nl, -1);
+    match_yolo_heads(g, true, f);
+    match_yolo_heads(g, false, f);
+    match_psa_attention(g, f);
+    match_area_attention(g, f);
+    match_conv_fusion(g, f);
+    match_concat_activation(g, f);
+    return f;
+}
+
+}  // namespace trtx

@@ -1,0 +1,92 @@
+// Graph pattern matching for the lowering (internal to runtime/): which layers of a Network collapse into one fused plan op.
+// A matcher reads the network through a NetView and claims layers in Fusions::absorbed; it never sees the Plan.  lower.cpp emits
+// one op per fusion record at the layer index the *_at tables name.
+#pragma once
+#include <initializer_list>
+#include <utility>
+#include <vector>
+
+#include "../kernels/kernels.h"
+#include "../options.h"
+#include "graph.h"
+#include "plugin.h"
+
+namespace trtx {
+
+struct FusedConv {
+    int conv_layer = -1;
+    int scale_layer = -1;
+    int act1 = ACT_NONE, act2 = ACT_NONE;   // before / after the residual add
+    float alpha1 = 0.f, alpha2 = 0.f;
+    int residual = -1;  // network tensor id
+    int out_tensor = -1;  // network tensor the fused op produces
+    int emit_at = -1;     // layer index at which the fused op is scheduled
+};
+
+struct YoloHeadFuse {
+    int plugin_layer = -1;
+    std::vector<int> head_tensor;  // network tensor per level: CHW (64 + classes, gh, gw)
+    std::vector<int> branch_tensor;  // task head: network tensor per level, the cv4 convolution's output (B, extra, gh, gw)
+    int dfl_conv_layer = -1;
+    YoloLayerParams params;
+};
+
+struct AttentionFuse {
+    int qkv = -1;                    // network tensor: the qkv convolution's output (B, heads*(2kd+hd), H, W)
+    int out_o = -1, out_v = -1;      // network tensors: O reshaped to (B, heads*hd, H, W), and v reshaped the same way
+    int heads = 0, N = 0, kd = 0, hd = 0;
+    float scale = 0.f;
+    int area = 0;                    // 0: YOLO11 PSA (psa_attention_kernel); >= 1: YOLOv12 area attention (area_attention_mfma_kernel), N / area keys per query
+};
+
+// What the matchers found.  *_at[layer] = index of the record whose op is emitted at that layer, or -1.
+struct Fusions {
+    std::vector<FusedConv> groups;
+    std::vector<YoloHeadFuse> yolo_heads;
+    std::vector<AttentionFuse> attns;
+    std::vector<int> group_at, yolo_at, attn_at;
+    std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own
+    std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src
+};
+
+inline bool ident(const int32_t* p, int n) {
+    for (int k = 0; k < n; ++k)
+        if (p[k] != k) return false;
+    return true;
+}
+inline bool perm_is(const int32_t* p, std::initializer_list<int> want) {
+    int k = 0;
+    for (int v : want)
+        if (p[k++] != v) return false;
+    return true;
+}
+int act_code(int trt_type);   // ACT_* of a TRTX_ACTIVATION_* type the kernels' epilogues know, or -1
+
+// The network as the matchers (and the emission) read it: the definition, who reads each tensor, and the switches of THIS lowering.
+struct NetView {
+    const Network& net;
+    const int dt;                             // dtype of NHWC tensors (the engine's)
+    const Options opt = read_options();       // the environment's A/B switches as of THIS lowering (tests flip them inside one process)
+    std::vector<std::vector<int>> consumers;  // per tensor: the layers that read it
+    explicit NetView(const Network& n);
+
+    int producer(int tensor) const { return net.tensors[tensor].producer; }
+    bool sole_consumer(int tensor, int* layer) const {
+        if (consumers[tensor].size() != 1 || net.tensors[tensor].is_output) return false;
+        *layer = consumers[tensor][0];
+        return true;
+    }
+    bool only_used_by(int tensor, std::initializer_list<int> layers) const;
+    // image tensors: (C,H,W) per sample, or (P,C,H,W) per sample where the leading P folds into the image count
+    // (TensorRT applies conv/pool/FC to the last three dims; rcnn.cpp:154-160 runs res5 on a (1000,C,14,14) tensor)
+    bool spatial(const Dims& d) const { return net.explicit_batch ? d.nb == 4 : (d.nb == 3 || d.nb == 4); }
+    bool is_builtin_mish(int li) const {
+        const LayerDef& l = net.layers[li];
+        return l.kind == L_PLUGIN && l.plugin && l.inputs.size() == 1 && l.outputs.size() == 1 && builtin_is_mish(l.plugin->v);
+    }
+};
+
+// Runs every matcher, in the order that is part of the behaviour (see the definition).
+Fusions match_fusions(const NetView& g);
+
+}  // namespace trtx

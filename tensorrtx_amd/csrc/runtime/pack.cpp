@@ -3,7 +3,10 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "../kernels/kernels.h"
+#include "plan.h"
 
 namespace trtx {
 
@@ -89,6 +92,143 @@ void pack_deconv_weights_f32(const float* w, int cin, int cout, int groups, int 
                             w[(((size_t)ci * cout_g + col) * kh + r) * kw + q];
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+bool pack_weights(const Network& net, Plan* plan) {
+    std::vector<uint8_t>& blob = plan->weight_blob;
+    blob.clear();
+    auto reserve = [&](size_t bytes) {
+        const size_t off = align256(blob.size());
+        blob.resize(off + bytes, 0);
+        return off;
+    };
+    // constants
+    for (auto& t : plan->tensors) {
+        if (t.storage < 0 || plan->storages[t.storage].kind != ST_WEIGHTS || t.parent >= 0) continue;
+        const TensorDef& nt = net.tensors[t.net_tensor];
+        const LayerDef& l = net.layers[nt.producer];
+        const size_t off = reserve(l.w0.size() * 4);
+        memcpy(blob.data() + off, l.w0.data(), l.w0.size() * 4);
+        plan->storages[t.storage].offset = off;
+    }
+    std::vector<POp*> every;   // the members of a conv group are packed like the convolutions they are
+    for (auto& op : plan->ops) {
+        for (auto& m : op.group) every.push_back(&m);
+        every.push_back(&op);
+    }
+    for (POp* pop : every) {
+        POp& op = *pop;
+        if (op.kind == OP_CONV || op.kind == OP_DECONV) {
+            const LayerDef& l = net.layers[op.src_layer];
+            const ConvArgs& a = op.conv;
+            const int cout = a.Cout;
+            // folded per-channel scale / shift
+            std::vector<float> sc(cout, 1.f), bias(std::max(a.Cout_pad, cout), 0.f);
+            for (int c = 0; c < cout && c < (int)l.w1.size(); ++c) bias[c] = l.w1[c];
+            if (op.scale_layer >= 0) {
+                const LayerDef& s = net.layers[op.scale_layer];
+                for (int c = 0; c < cout; ++c) {
+                    const float scale = s.w1.empty() ? 1.f : (s.w1.size() == 1 ? s.w1[0] : s.w1[c]);
+                    const float shift = s.w0.empty() ? 0.f : (s.w0.size() == 1 ? s.w0[0] : s.w0[c]);
+                    sc[c] = scale;
+                    bias[c] = bias[c] * scale + shift;
+                }
+            }
+            const TensorDef& tin = net.tensors[l.inputs[0]];
+            const int cin_logical = (int)tin.dims.d[tin.dims.nb - 3];
+            if (op.kind == OP_DECONV) {
+                op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
+                pack_deconv_weights_f32(l.w0.data(), cin_logical, cout, a.groups, a.kh, a.kw,
+                                        reinterpret_cast<float*>(blob.data() + op.w_off));
+            } else if (op.stem) {
+                // [tap = (c*kh + r)*kw + q][cout], BN scale folded
+                op.w_off = reserve((size_t)a.kh * a.kw * cin_logical * cout * 4);
+                float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
+                for (int co = 0; co < cout; ++co)
+                    for (int t = 0; t < cin_logical * a.kh * a.kw; ++t)
+                        dst[(size_t)t * cout + co] = l.w0[(size_t)co * cin_logical * a.kh * a.kw + t] * sc[co];
+            } else if (op.from_deconv) {
+                // CKRS [Cin][Cout][kh][kw] -> KCRS of the stand-in 1x1 conv: output channel (r*kw + q)*Cout + co.  The re-layout
+                // (and the per-sub-position bias) does not depend on which conv kernel runs the stand-in: the kernel choice may refuse
+                // the MFMA path (kh*kw*Cin < 32, > 2 GB images) and the direct kernel must then see the same KCRS weights.
+                const int taps = l.kernel[0] * l.kernel[1], dc = l.nb_out;
+                std::vector<float> w2((size_t)cout * cin_logical);
+                for (int ci = 0; ci < cin_logical; ++ci)
+                    for (int co = 0; co < dc; ++co)
+                        for (int t = 0; t < taps; ++t) w2[(size_t)(t * dc + co) * cin_logical + ci] = l.w0[((size_t)ci * dc + co) * taps + t];
+                for (int c = 0; c < cout; ++c) bias[c] = l.w1.empty() ? 0.f : l.w1[c % dc];
+                if (op.igemm) {
+                    op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
+                    pack_conv_weights_f16(w2.data(), cout, cin_logical, 1, 1, a.CinK, a.bk, sc.data(),
+                                          reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+                } else {
+                    op.w_off = reserve((size_t)cout * cin_logical * 4);
+                    pack_conv_weights_f32(w2.data(), cout, cin_logical, 1, 1, sc.data(), reinterpret_cast<float*>(blob.data() + op.w_off));
+                }
+            } else if (op.igemm && a.in_i8) {
+                // int8 weights, per-output-channel scales; cscale[c] = input tensor scale * weight scale (dequantises the int32 sums)
+                const size_t kpad_bytes = (size_t)a.Kpad * 2;
+                op.w_off = reserve((size_t)a.Cout_pad * kpad_bytes);
+                std::vector<float> wscale(a.Cout_pad, 1.f);
+                conv_pack_weights_i8(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK * 2, sc.data(), a.Cout_pad, (int)kpad_bytes,
+                                     reinterpret_cast<int8_t*>(blob.data() + op.w_off), wscale.data());
+                const float s_in = plan->tensors[op.in[0]].scale;
+                for (float& v : wscale) v *= s_in;
+                op.s_off = reserve(wscale.size() * 4);
+                memcpy(blob.data() + op.s_off, wscale.data(), wscale.size() * 4);
+            } else if (op.igemm && a.f32) {
+                op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 4);
+                conv_pack_weights_igemm_f32(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
+                                            reinterpret_cast<float*>(blob.data() + op.w_off));
+            } else if (op.igemm) {
+                op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
+                pack_conv_weights_f16(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
+                                      reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+            } else if (op.dw) {
+                // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load
+                op.w_off = reserve((size_t)a.kh * a.kw * cout * 4);
+                float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
+                for (int co = 0; co < cout; ++co)
+                    for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = l.w0[(size_t)co * a.kh * a.kw + t] * sc[co];
+            } else {
+                op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
+                pack_conv_weights_f32(l.w0.data(), cout, cin_logical / a.groups, a.kh, a.kw, sc.data(),
+                                      reinterpret_cast<float*>(blob.data() + op.w_off));
+            }
+            op.b_off = reserve(bias.size() * 4);
+            memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
+            op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (size_t)cout * a.K * 4);
+        } else if (op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD) {
+            const LayerDef& l = net.layers[op.src_layer];
+            op.w_off = reserve(16 * 4);
+            memcpy(blob.data() + op.w_off, l.w0.data(), 16 * 4);
+        } else if (op.kind == OP_SCALE_NHWC || op.kind == OP_SCALE_LIN) {
+            const LayerDef& l = net.layers[op.src_layer];
+            const int C = op.kind == OP_SCALE_NHWC ? plan->tensors[op.in[0]].C : (op.i[0] == 1 ? op.i[2] : 1);
+            auto expand = [&](const std::vector<float>& w, float dflt) {
+                std::vector<float> v(C, dflt);
+                for (int c = 0; c < C; ++c)
+                    if (!w.empty()) v[c] = w.size() == 1 ? w[0] : w[c];
+                return v;
+            };
+            const auto shift = expand(l.w0, 0.f), scale = expand(l.w1, 1.f), power = expand(l.w2, 1.f);
+            op.s_off = reserve(C * 4);
+            memcpy(blob.data() + op.s_off, scale.data(), C * 4);
+            op.b_off = reserve(C * 4);
+            memcpy(blob.data() + op.b_off, shift.data(), C * 4);
+            op.w_off = reserve(C * 4);
+            memcpy(blob.data() + op.w_off, power.data(), C * 4);
+        }
+    }
+    for (auto& op : plan->ops)   // a grouped launch moves what its members move (their packed weights were priced just above)
+        if (op.kind == OP_CONV_GROUP) {
+            op.bytes = 0;
+            for (const POp& m : op.group) op.bytes += m.bytes;
+        }
+    plan->weight_bytes = align256(blob.size());
+    blob.resize(plan->weight_bytes, 0);
+    return true;
 }
 
 }  // namespace trtx

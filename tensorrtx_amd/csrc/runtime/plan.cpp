@@ -1,0 +1,102 @@
+// What a plan says about itself: op kind names and the JSON description.  See plan.h.
+#include "plan.h"
+
+#include <sstream>
+
+namespace trtx {
+
+const char* op_kind_name(int k) {
+    static const char* n[] = {"conv",     "deconv",    "pool",      "resize",     "ew_nhwc", "act_nhwc", "scale_nhwc",
+                              "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
+                              "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
+                              "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
+                              "yolo_task_head"};
+    return (k >= 0 && k <= OP_YOLO_TASK_HEAD) ? n[k] : "?";
+}
+
+std::string Plan::describe_json() const {
+    std::ostringstream o;
+    double flops = 0, bytes = 0;
+    int n_conv = 0, n_igemm = 0;
+    for (const auto& op : ops) {
+        flops += op.flops;
+        bytes += op.bytes;
+        if (op.kind == OP_CONV) {
+            ++n_conv;
+            n_igemm += op.igemm ? 1 : 0;
+        }
+        n_conv += (int)op.group.size();
+        n_igemm += (int)op.group.size();
+    }
+    o << "{\"fp16\":" << (fp16 ? "true" : "false") << ",\"max_batch\":" << max_batch << ",\"arena_bytes\":" << arena_bytes
+      << ",\"weight_bytes\":" << weight_bytes << ",\"n_lanes\":" << num_lanes << ",\"n_ops\":" << ops.size() << ",\"n_conv\":" << n_conv
+      << ",\"n_igemm\":" << n_igemm << ",\"flops_per_sample\":" << flops << ",\"bytes_per_sample\":" << bytes
+      << ",\"ops\":[";
+    for (size_t k = 0; k < ops.size(); ++k) {
+        const POp& op = ops[k];
+        o << (k ? "," : "") << "{\"kind\":\"" << op_kind_name(op.kind) << "\",\"name\":\"";
+        for (char c : op.name) o << ((c == '"' || c == '\\' || (unsigned char)c < 0x20) ? ' ' : c);
+        o << "\",\"flops\":" << op.flops << ",\"bytes\":" << op.bytes;
+        auto conv_fields = [&](const POp& op) {
+            const ConvArgs& a = op.conv;
+            o << ",\"igemm\":" << (op.igemm ? "true" : "false") << ",\"stem\":" << (op.stem ? "true" : "false") << ",\"cin\":" << (a.in_i8 ? 2 * a.Cin : a.Cin) << ",\"cout\":" << a.Cout
+              << ",\"k\":[" << a.kh << "," << a.kw << "],\"stride\":[" << a.stride_h << "," << a.stride_w << "],\"hw_in\":["
+              << a.H << "," << a.W << "],\"hw_out\":[" << a.Ho << "," << a.Wo << "],\"act1\":" << a.act1
+              << ",\"act2\":" << a.act2 << ",\"alpha1\":" << a.alpha1 << ",\"alpha2\":" << a.alpha2 << ",\"up_c\":" << a.up_C << ",\"residual\":" << (op.in.size() > 1 ? "true" : "false")
+              << ",\"bn_folded\":" << (op.scale_layer >= 0 ? "true" : "false") << ",\"ld_in\":" << a.ld_in
+              << ",\"ld_out\":" << a.ld_out << ",\"i8\":[" << a.in_i8 << "," << a.out_i8 << "," << a.res_i8 << "],\"nmul\":" << (op.stem ? 1 : tensors[op.in[0]].nmul) << ",\"nfix\":"
+              << (op.stem ? 0 : tensors[op.in[0]].nfix);
+            if (op.dw) o << ",\"dw\":true";
+        };
+        if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
+        if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
+        if (op.kind == OP_ATTENTION && op.i[4] > 0) o << ",\"area\":" << op.i[4] << ",\"kernel\":\"mfma\"";
+        if (op.kind == OP_YOLO_TASK_HEAD) {
+            o << ",\"task\":\"" << (op.i[9] == 1 ? "seg" : (op.i[9] == 2 ? "pose" : "obb")) << "\",\"classes\":" << op.i[0] << ",\"nk\":" << op.i[10]
+              << ",\"branch_ld\":[";
+            for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
+            o << "]";
+        }
+        if (op.kind == OP_CONV_GROUP) {
+            o << ",\"members\":[";
+            for (size_t j = 0; j < op.group.size(); ++j) {
+                const POp& m = op.group[j];
+                o << (j ? "," : "") << "{\"name\":\"";
+                for (char c : m.name) o << ((c == '"' || c == '\\' || (unsigned char)c < 0x20) ? ' ' : c);
+                o << "\",\"flops\":" << m.flops << ",\"bytes\":" << m.bytes;
+                conv_fields(m);
+                o << ",\"in\":[";
+                for (size_t q = 0; q < m.in.size(); ++q) o << (q ? "," : "") << m.in[q];
+                o << "],\"out\":[" << m.out[0] << "]}";
+            }
+            o << "]";
+        }
+        o << ",\"lane\":" << op.lane << ",\"waits\":[";
+        for (size_t j = 0; j < op.wait_ops.size(); ++j) o << (j ? "," : "") << op.wait_ops[j];
+        o << "],\"in\":[";
+        for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << op.in[j];
+        o << "],\"out\":[";
+        for (size_t j = 0; j < op.out.size(); ++j) o << (j ? "," : "") << op.out[j];
+        o << "]}";
+    }
+    o << "],\"tensors\":[";
+    for (size_t k = 0; k < tensors.size(); ++k) {
+        const PTensor& t = tensors[k];
+        o << (k ? "," : "") << "{\"id\":" << t.id << ",\"net\":" << t.net_tensor << ",\"layout\":\""
+          << (t.layout == LAY_NHWC ? "nhwc" : "linear") << "\",\"dims\":[";
+        for (int d = 0; d < t.dims.nb; ++d) o << (d ? "," : "") << t.dims.d[d];
+        o << "],\"storage\":" << t.storage << ",\"coff\":" << t.rcoff << ",\"ld\":" << t.ld << ",\"dtype\":" << t.dtype << ",\"scale\":" << t.scale
+          << ",\"view\":"
+          << (t.parent >= 0 ? "true" : "false") << "}";
+    }
+    o << "],\"storages\":[";
+    for (size_t k = 0; k < storages.size(); ++k) {
+        const Storage& s = storages[k];
+        o << (k ? "," : "") << "{\"kind\":" << s.kind << ",\"bytes\":" << s.bytes << ",\"offset\":" << s.offset
+          << ",\"first\":" << s.first_use << ",\"last\":" << s.last_use << "}";
+    }
+    o << "]}";
+    return o.str();
+}
+
+}  // namespace trtx

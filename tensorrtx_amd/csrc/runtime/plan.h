@@ -85,6 +85,7 @@ struct Storage {
     int binding = -1;      // ST_BINDING
     int first_use = 1 << 30, last_use = -1;
 };
+inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }   // every block of the arena and of the weight blob starts on 256 bytes
 
 struct POp {
     int kind = 0;

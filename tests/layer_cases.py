@@ -709,7 +709,7 @@ for bias in (True, False):
     _fc(16, 4, 4, 33, bias)
 
 
-# ---- 10. direct convolution: fp32 weights in both engines (lower.cpp packs them with pack_conv_weights_f32), kh * kw * Cin / groups terms
+# ---- 10. direct convolution: fp32 weights in both engines (pack.cpp packs them with pack_conv_weights_f32), kh * kw * Cin / groups terms
 #          + bias + shortcut, one fp16 store of the fused result (1 site) -----------------------------------------------------------------------
 def _conv(name, Cin, Cout, H, W, k, stride=1, padding=0, dilation=1, groups=1, fusedep=False, B=2, max_batch=None, wrap="plain"):
     kh, kw_ = (k, k) if np.isscalar(k) else k

@@ -383,7 +383,7 @@ def test_engine_is_bound_to_its_device_and_device_replicas_run(gpu):
 
 
 def test_yolov8n_fp16_folded_upsample_is_bit_identical_to_the_resize_launches(gpu):
-    """Upsample -> Concat -> Conv1x1 folded into the convolution's A-gather (lower.cpp fold_upsample, ConvArgs::up_in) against the same plan
+    """Upsample -> Concat -> Conv1x1 folded into the convolution's A-gather (plan_passes.cpp fold_upsample, ConvArgs::up_in) against the same plan
     lowered with the two nearest-resize launches (TRTX_FOLD_UPSAMPLE=0).  With every layer on a plain implicit-GEMM tile (those sum K in
     one order; the weight-stationary and wave-split-K kernels, which the unfolded 1x1s may otherwise take, are switched off for the
     process) the same operands are multiplied in the same order: every output float is the same.  Own process: the switches are read once."""
@@ -470,7 +470,7 @@ def test_conv_bn_mish_engine_matches_the_reference_expression(gpu, fp16, fused):
 
 @pytest.mark.parametrize("tuned", [False, True], ids=["static", "tuned"])
 def test_grouped_sibling_convolutions_return_the_bits_of_one_launch_each(gpu, tuned):
-    """lower.cpp group_convs / conv_igemm_group_f16_kernel: the detect head's 18 convolutions in 6 launches of 3 sibling layers each - every
+    """plan_passes.cpp group_convs / conv_igemm_group_f16_kernel: the detect head's 18 convolutions in 6 launches of 3 sibling layers each - every
     member computed exactly as its own launch computes it.  Both engines on the static kernel choice, same input: every head tensor and the
     decode buffer equal bit for bit; and the grouped plan really has the 6 groups.  No TRTX_CONV_NOWSK since round 5: a group member
     is marked "never wave-split-K", so its own launch - TRTX_GROUP_CONVS=0 here, or the executor's per-member fallback at another batch - walks K in

@@ -8,7 +8,7 @@ Error model, per element, nothing fitted:
     for the fp32 depthwise kernel, n * 2^-24 the worst case of the kernel's own sequential fp32 sum of n terms, amp the derived amplification
     of an argument's rounding (softmax, pow), magnitude the same expression on absolute values;
   * fp16 storage: + tests.parity.fp16_walk(sites, magnitude), the sites counted per family in tests/layer_cases.py.
-The direct convolution kernels read fp32 weights in both engines (`const float* w` in conv_direct_kernel / deconv_direct_kernel; lower.cpp
+The direct convolution kernels read fp32 weights in both engines (`const float* w` in conv_direct_kernel / deconv_direct_kernel; pack.cpp
 packs them with pack_conv_weights_f32 / pack_deconv_weights_f32), so their weights are no rounding site.
 
 Every element of every output binding is compared.  The bindings are allocated for the plan's max_batch and pre-filled with NaN: the

@@ -127,7 +127,7 @@ def test_yolov8n_lowering_at_benchmark_size(monkeypatch):
     # layer by layer (the default): Appendix C.1's 63 convolutions = 1 stem (fp32 NCHW in) + 62 MFMA implicit-GEMM; the DFL
     # 1x1 convs are absorbed by the fused head kernel
     # round 4: the detect head's 18 convolutions - six chains of depth three over three levels (model.cpp:188-251) - go out as 6 grouped
-    # launches of 3 sibling layers each (lower.cpp group_convs): 65 -> 53 ops, 62 -> 50 MFMA conv launches
+    # launches of 3 sibling layers each (plan_passes.cpp group_convs): 65 -> 53 ops, 62 -> 50 MFMA conv launches
     grouped = engine.describe_plan(plan, lowered=True)
     groups = [o for o in grouped["ops"] if o["kind"] == "conv_group"]
     assert len(grouped["ops"]) == 53 and len(groups) == 6 and all(len(g["members"]) == 3 for g in groups)
@@ -493,7 +493,7 @@ def test_int8_tensor_on_a_convolution_without_the_mfma_path_falls_back_to_fp16()
     """kINT8 promises that layers which cannot run in int8 stay in fp16.  The assignment screens by shape only; whether a convolution
     really takes the implicit-GEMM path is decided later from strides / offsets / K.  Here a 1x1 convolution over 16 channels (K = 16:
     the direct kernel) produces a 32-channel tensor with a calibrated scale that a 3x3 convolution consumes - the producer cannot write
-    int8, so the tensor must stay fp16 (it used to be marked int8 and the whole build then failed in finalize)."""
+    int8, so the tensor must stay fp16 (it used to be marked int8 and the whole build then failed in finalize_plan)."""
     import struct
     from tensorrtx_amd import calibrator, capi
     L = capi.lib()
@@ -592,7 +592,7 @@ def _upsample_concat_net(extra_reader=False, cin_up=64, cin_skip=32, k=1, fp16=T
 
 
 def test_upsample_is_folded_only_where_it_is_safe(monkeypatch):
-    """lower.cpp fold_upsample: the resize disappears into the 1x1 convolution that reads the concat buffer - but not when something else
+    """plan_passes.cpp fold_upsample: the resize disappears into the 1x1 convolution that reads the concat buffer - but not when something else
     reads the upsampled tensor, not into a 3x3, not when the slice is not a whole number of 64-channel k-steps, and not with
     TRTX_FOLD_UPSAMPLE=0.  Since round 5 fp32 engines fold too (their convolutions run on the same skeleton, kernels/conv_igemm_f32.hip)."""
     def kinds(plan):

@@ -63,7 +63,7 @@ class Emu:
         if bn:
             w = p.conv_w(name + ".conv.weight", cout, x.shape[1], k)
             g, b, m, v = p.bn(name + ".bn", cout)
-            scale = g / torch.sqrt(v + 1e-3)           # block.cpp:79-96 (float sqrt), folded as runtime/lower.cpp does
+            scale = g / torch.sqrt(v + 1e-3)           # block.cpp:79-96 (float sqrt), folded as runtime/pack.cpp pack_weights does
             w = w * scale[:, None, None, None]
             bias = b - m * scale
         else:

@@ -59,7 +59,7 @@ def det_stats(dec, dec_ref, conf_floor=0.25):
 
 
 def int8_site(name):
-    """activation sites the int8 engine holds in int8 (runtime/lower.cpp assign_int8): conv outputs read by MFMA convolutions.  Not: the
+    """activation sites the int8 engine holds in int8 (runtime/plan_passes.cpp assign_int8): conv outputs read by MFMA convolutions.  Not: the
     stem's output (conv_stem has no requantising epilogue), SPPF's cv1 (the pool chain reads it), the detect convs' outputs (the fused
     head reads fp16), the fp16 value before a shortcut add."""
     if not name.startswith("a:") or name.endswith("(pre-add)"):
