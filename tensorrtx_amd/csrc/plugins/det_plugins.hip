@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../common.h"
+#include "decode_common.h"
 
 namespace {
 
@@ -692,7 +693,7 @@ __global__ __launch_bounds__(kRfChunk) void retina_count_kernel(RfLevels t, int 
     const int g = blockIdx.x * kRfChunk + threadIdx.x;
     int c = 0;
     if (g < total_cells) {
-        const int l = g >= t.cell_off[2] ? 2 : (g >= t.cell_off[1] ? 1 : 0);
+        const int l = trtx::find_level(t.cell_off, 3, g);
         const int total = t.w[l] * t.h[l];
         const int idx = g - t.cell_off[l];
         const float* cls_reg = t.in[l] + (size_t)b * 32 * total + 2 * 4 * total;
@@ -703,11 +704,8 @@ __global__ __launch_bounds__(kRfChunk) void retina_count_kernel(RfLevels t, int 
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    int w = c;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o);
-    if ((threadIdx.x & 63) == 0 && w) atomicAdd(&s_cnt, w);
-    __syncthreads();
+    const int w = trtx::wave_sum(c);
+    trtx::workgroup_count(&s_cnt, (threadIdx.x & 63) == 0 ? w : 0);
     if (threadIdx.x == 0) chunk_cnt[b * n_chunks + blockIdx.x] = s_cnt;
 }
 
@@ -921,16 +919,6 @@ __global__ void rpn_decode_kernel(const int* __restrict__ order, int n_order, in
     ob[2] = r2;
     ob[3] = r3;
     os[d] = (r2 - r0 <= 0.0f || r3 - r1 <= 0.0f) ? -FLT_MAX : in_scores[i];
-}
-
-// keys for the re-sort after NMS: (~ord(updated score) << 32) | sorted position
-__global__ void rekey_kernel(const float* __restrict__ scores, int n, int n_pad, uint64_t* __restrict__ keys) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_pad) return;
-    const int b = blockIdx.y;
-    uint64_t k = ~0ull;
-    if (r < n) k = ((uint64_t)(uint32_t)~ord_f32(scores[(size_t)b * n + r]) << 32) | (uint32_t)r;
-    keys[(size_t)b * n_pad + r] = k;
 }
 
 // out[d] = record of original index order1[pos2[d]] (RpnNms.cu:116, BatchedNms.cu:150-158)
@@ -1185,7 +1173,7 @@ static int32_t sorted_nms(int mode, int batch, const float* scores, const float*
         if (a.n_cap <= 1024) hipLaunchKernelGGL(greedy_nms_small_kernel, dim3(batch), dim3(1024), 0, stream, a);
         else hipLaunchKernelGGL(greedy_nms_kernel, dim3(batch), dim3(1024), 0, stream, a);
     }
-    hipLaunchKernelGGL(rekey_kernel, grid1(n_pad, batch), dim3(256), 0, stream, sorted, n, n_pad, keys);
+    hipLaunchKernelGGL(make_keys_kernel, grid1(n_pad, batch), dim3(256), 0, stream, sorted, n, n_pad, keys);
     st = sort_keys(keys, batch, n_pad, stream);
     if (st != TRTX_OK) return st;
     hipLaunchKernelGGL(gather_after_nms_kernel, grid1(n_out, batch), dim3(256), 0, stream, keys, n_pad, order, n, sorted, boxes,

@@ -17,8 +17,11 @@
 #include <stdint.h>
 
 #include "../common.h"
+#include "decode_common.h"
 
 namespace {
+
+using trtx::logist;
 
 constexpr int kMaxLevels = 8;
 constexpr int kAnchors = 3;   // kNumAnchor, yolov5/src/config.h:35
@@ -33,16 +36,6 @@ struct Level5Table {
     int n_levels;
 };
 
-__device__ __forceinline__ float logist(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ int find_level(const Level5Table& t, int g) {
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxLevels; ++i)
-        if (i < t.n_levels && g >= t.cell_off[i]) l = i;
-    return l;
-}
-
 // Pass 1: conf / class of every (cell, anchor); -1 marks a dropped candidate.  score / cls: [batch][cells][3].
 __global__ __launch_bounds__(kChunk) void yolo5_score_kernel(Level5Table t, int classes, int info_len, int total_cells,
                                                              float* __restrict__ score,
@@ -51,7 +44,7 @@ __global__ __launch_bounds__(kChunk) void yolo5_score_kernel(Level5Table t, int 
     const int g = blockIdx.x * kChunk + threadIdx.x;
     int nkeep = 0;
     if (g < total_cells) {
-        const int l = find_level(t, g);
+        const int l = trtx::find_level(t.cell_off, t.n_levels, g);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         const int e = g - t.cell_off[l];
         const float* cur = t.in[l] + (size_t)b * info_len * cells * kAnchors + e;
@@ -83,11 +76,8 @@ __global__ __launch_bounds__(kChunk) void yolo5_score_kernel(Level5Table t, int 
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    int w = nkeep;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o);
-    if ((threadIdx.x & 63) == 0 && w) atomicAdd(&s_cnt, w);
-    __syncthreads();
+    const int w = trtx::wave_sum(nkeep);
+    trtx::workgroup_count(&s_cnt, (threadIdx.x & 63) == 0 ? w : 0);
     if (threadIdx.x == 0) chunk_cnt[b * n_chunks + blockIdx.x] = s_cnt;
 }
 
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(kChunk) void yolo5_emit_kernel(Level5Table t, int c
         if (wv < wave) slot += s_wave[wv];
     float* out = output + (size_t)b * out_elem;
     if (mine) {
-        const int l = find_level(t, g);
+        const int l = trtx::find_level(t.cell_off, t.n_levels, g);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         const int e = g - t.cell_off[l];
         const int gw = t.grid_w[l], gh = t.grid_h[l];

@@ -15,8 +15,12 @@
 #include <stdint.h>
 
 #include "../common.h"
+#include "decode_common.h"
 
 namespace {
+
+using trtx::find_level;
+using trtx::logist;
 
 constexpr int kMaxLevels = 8;
 constexpr int kChunk = 512;  // cells per workgroup in both passes
@@ -35,19 +39,6 @@ struct LevelTable {
     int n_levels;
 };
 
-__device__ __forceinline__ float logist(float x) {
-    return 1.0f / (1.0f + expf(-x));
-}
-
-__device__ __forceinline__ int find_level(const LevelTable& t, int g) {
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxLevels; ++i)
-        if (i < t.n_levels && g >= t.cell_off[i])
-            l = i;
-    return l;
-}
-
 // Pass 1: per cell best class/prob.  VEC cells per thread (VEC = 4 -> 16-byte loads).
 template <int VEC>
 __global__ __launch_bounds__(kChunk / VEC) void yolo_score_kernel(LevelTable t, int classes, int info_len, int total_cells,
@@ -59,7 +50,7 @@ __global__ __launch_bounds__(kChunk / VEC) void yolo_score_kernel(LevelTable t, 
     const int g0 = chunk * kChunk + threadIdx.x * VEC;
     int nflag = 0;
     if (g0 < total_cells) {
-        const int l = find_level(t, g0);
+        const int l = find_level(t.cell_off, t.n_levels, g0);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         const int e0 = g0 - t.cell_off[l];
         const float* cur = t.in[l] + (size_t)b * cells * info_len + e0;
@@ -101,15 +92,11 @@ __global__ __launch_bounds__(kChunk / VEC) void yolo_score_kernel(LevelTable t, 
             }
         }
     }
-    // workgroup reduction of nflag
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    int w = nflag;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o);
-    if ((threadIdx.x & 63) == 0 && w) atomicAdd(&s_cnt, w);
-    __syncthreads();
+    const int w = trtx::wave_sum(nflag);
+    trtx::workgroup_count(&s_cnt, (threadIdx.x & 63) == 0 ? w : 0);
     if (threadIdx.x == 0) chunk_cnt[b * n_chunks + chunk] = s_cnt;
 }
 
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(kChunk) void yolo_emit_kernel(LevelTable t, int cla
     const int slot = before + in_wave;
     float* out = output + (size_t)b * out_elem;
     if (keep && slot < max_out) {
-        const int l = find_level(t, g);
+        const int l = find_level(t.cell_off, t.n_levels, g);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         const int e = g - t.cell_off[l];
         const int gw = t.grid_w[l];
@@ -221,22 +208,7 @@ __global__ __launch_bounds__(kChunk) void yolo_emit_kernel(LevelTable t, int cla
     }
 }
 
-
-// ---------------------------------------------------------------------------------------------------------
-// Fused detect-head tail: reads the NHWC fp16 output of the head convolutions directly
-// (channels [0,64) = 4 sides x 16 DFL bins, [64, 64+classes) = class logits) and performs, per cell,
-//   DFL: softmax over the 16 bins of each side, expectation with the 1x1 "dfl.conv" weights
-//        (yolov8/src/block.cpp:239-257 — shuffle/softmax/conv/shuffle collapsed into registers, fp32), and
-//   the CalDetection class scan (sigmoid, strict-'>' argmax, 0.1 threshold; yololayer.cu:195-204).
-// It replaces ~10 layout/shuffle/slice/softmax/concat launches per level of the un-fused graph.
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-
-struct HeadTable {
-    const void* in[kMaxLevels];
-    int ld[kMaxLevels];
-    int cell_off[kMaxLevels + 1];
-    int n_levels;
-};
 
 // eight consecutive channels of a cell as floats: one 16-byte load of an fp16 engine's tensor, two of an fp32 engine's
 template <typename T>
@@ -252,14 +224,41 @@ __device__ __forceinline__ void load8(const T* p, float (&x)[8]) {
     }
 }
 
-// T = element type of the NHWC head tensors: _Float16 (kFP16 engines) or float (fp32 engines, round 5: the build that meets BASELINE's tolerance
-// had run the un-fused graph, ~30 layout / shuffle / softmax launches)
-template <typename T>
-__global__ __launch_bounds__(256) void yolo_head_score_kernel(HeadTable t, int classes, int total_cells,
-                                                              const float* __restrict__ dfl_w,
-                                                              float* __restrict__ score, int* __restrict__ cls_out,
-                                                              float4* __restrict__ boxes,
-                                                              int* __restrict__ chunk_cnt, int n_chunks) {
+
+// ---------------------------------------------------------------------------------------------------------
+// Fused detect-head tail: reads the NHWC fp16 output of the head convolutions directly
+// (channels [0,64) = 4 sides x 16 DFL bins, [64, 64+classes) = class logits) and performs, per cell,
+//   DFL: softmax over the 16 bins of each side, expectation with the 1x1 "dfl.conv" weights
+//        (yolov8/src/block.cpp:239-257 — shuffle/softmax/conv/shuffle collapsed into registers, fp32), and
+//   the CalDetection class scan (sigmoid, strict-'>' argmax, 0.1 threshold; yololayer.cu:195-204).
+// It replaces ~10 layout/shuffle/slice/softmax/concat launches per level of the un-fused graph.
+
+struct HeadTable {
+    const void* in[kMaxLevels];
+    int ld[kMaxLevels];
+    int cell_off[kMaxLevels + 1];
+    int n_levels;
+};
+
+struct BranchTable {
+    const void* in[kMaxLevels];  // device pointers, [batch][cells_l][ld[l]]: channels [0, extra) of the cell's branch
+    int ld[kMaxLevels];
+    int vec;                      // every ld and base allows 16-byte loads
+};
+
+// Pass 1 of the fused heads.  T = element type of the NHWC head tensors: _Float16 (kFP16 engines) or float (fp32 engines, round 5:
+// the build that meets BASELINE's tolerance had run the un-fused graph, ~30 layout / shuffle / softmax launches).
+// TAIL = false (det head): classes % 8 == 0, every logit is read in 16-byte pieces.  TAIL = true (task head): any classes >= 1; the
+// last (classes % 8) logits are read one by one, so the NHWC padding channels behind them never reach the argmax (nor a load past
+// the tensor's last pixel).  With classes % 8 == 0 both are the same arithmetic, operation for operation.
+// The det and the task kernel used to be two copies, the det one pinned by being left untouched.  Now both are this body, and what pins
+// it is: the tail is `if constexpr`, so the det instantiations hold none of it (their ISA equals the pre-merge kernels' up to the operand
+// order of commutative packed adds and multiplies); the det plans' hashes (tests/golden/yolo11_det_plan_sha256.json); and the bit-for-bit tests against
+// the oracle and the reference's own plugin (tests/test_gpu_yolo11_tasks.py, test_gpu_yolo_plugins.py, test_ref_pinning.py).
+template <typename T, bool TAIL>
+__device__ __forceinline__ void head_score(const HeadTable& t, int classes, int total_cells, const float* __restrict__ dfl_w,
+                                           float* __restrict__ score, int* __restrict__ cls_out, float4* __restrict__ boxes,
+                                           int* __restrict__ chunk_cnt, int n_chunks) {
     __shared__ int s_list[256];
     __shared__ int s_n, s_keep;
     const int b = blockIdx.y;
@@ -269,11 +268,9 @@ __global__ __launch_bounds__(256) void yolo_head_score_kernel(HeadTable t, int c
         s_keep = 0;
     }
     __syncthreads();
+    const int full = TAIL ? classes & ~7 : classes;  // classes read eight at a time; [full, classes) one at a time
     auto cell_ptr = [&](int gg) {
-        int l = 0;
-#pragma unroll
-        for (int i = 1; i < kMaxLevels; ++i)
-            if (i < t.n_levels && gg >= t.cell_off[i]) l = i;
+        const int l = find_level(t.cell_off, t.n_levels, gg);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         return static_cast<const T*>(t.in[l]) + ((size_t)b * cells + (gg - t.cell_off[l])) * t.ld[l];
     };
@@ -288,16 +285,24 @@ __global__ __launch_bounds__(256) void yolo_head_score_kernel(HeadTable t, int c
     __syncthreads();
     {
         const int wave0 = threadIdx.x & ~63, lane = threadIdx.x & 63;
-        const int pieces = classes >> 3;                 // classes % 8 == 0 on this path
+        const int pieces = TAIL ? (classes + 7) >> 3 : classes >> 3;
         const int g0 = blockIdx.x * 256 + wave0;
         int cells_here = total_cells - g0;
         cells_here = cells_here > 64 ? 64 : cells_here;
         const int n = cells_here * pieces;
         for (int j = lane; j < n; j += 64) {
             const int c = j / pieces, q = j - c * pieces;
-            float v[8];
-            load8(cell_ptr(g0 + c) + 64 + q * 8, v);
-            float m = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+            const T* p = cell_ptr(g0 + c) + 64 + q * 8;
+            bool tail_piece = false;
+            if constexpr (TAIL) tail_piece = q * 8 >= full;
+            float m = -INFINITY;
+            if (!tail_piece) {
+                float v[8];
+                load8(p, v);
+                m = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+            } else if constexpr (TAIL) {
+                for (int i = 0; i < classes - full; ++i) m = fmaxf(m, (float)p[i]);
+            }
             if (m > -2.3f) s_list[wave0 + c] = 1;
         }
     }
@@ -371,294 +376,6 @@ __global__ __launch_bounds__(256) void yolo_head_score_kernel(HeadTable t, int c
         float best = 0.0f;
         int bcls = 0;
         const T* cl = cell + 64;
-        for (int c0 = 0; c0 < classes; c0 += 8) {  // classes % 8 == 0 on this path
-            float v[8];
-            load8(cl + c0, v);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float pr = logist(v[i]);
-                if (pr > best) {
-                    best = pr;
-                    bcls = c0 + i;
-                }
-            }
-        }
-        const bool keep = !((double)best < 0.1);
-        const size_t o = (size_t)b * total_cells + gg;
-        score[o] = keep ? best : -1.0f;
-        cls_out[o] = bcls;
-        boxes[o] = make_float4(side[0], side[1], side[2], side[3]);
-        kept += keep ? 1 : 0;
-    }
-    // per-kChunk candidate counts (two 256-thread workgroups feed one chunk counter)
-    if (kept) atomicAdd(&s_keep, kept);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_keep) atomicAdd(&chunk_cnt[b * n_chunks + (blockIdx.x * 256) / kChunk], s_keep);
-}
-
-}  // namespace
-
-extern "C" size_t trtx_yolo_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels) {
-    size_t cells = 0;
-    for (int i = 0; i < n_levels; ++i) cells += (size_t)(net_h / strides[i]) * (net_w / strides[i]);
-    const size_t n_chunks = (cells + kChunk - 1) / kChunk;
-    return trtx::align_up((size_t)batch * cells * sizeof(float), 256) +
-           trtx::align_up((size_t)batch * cells * sizeof(int), 256) +
-           trtx::align_up((size_t)batch * n_chunks * sizeof(int), 256);
-}
-
-extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
-                                       const int* strides, int max_out, int n_kpt, float kpt_conf, int is_seg, int is_pose, int is_obb,
-                                       float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !inputs || !output ||
-        !workspace || n_kpt < 0 || n_kpt > 17)
-        return TRTX_ERR_INVALID;
-    if (workspace_bytes < trtx_yolo_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
-    const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, n_kpt, kpt_conf};
-    const int info_len = 4 + classes + (br.seg ? 32 : 0) + (br.pose ? n_kpt * 3 : 0) + (br.obb ? 1 : 0);
-    LevelTable t{};
-    t.n_levels = n_levels;
-    bool vec4 = true;
-    int off = 0;
-    for (int i = 0; i < n_levels; ++i) {
-        const int gh = net_h / strides[i], gw = net_w / strides[i];
-        t.in[i] = inputs[i];
-        t.cell_off[i] = off;
-        t.grid_w[i] = gw;
-        t.stride[i] = strides[i];
-        off += gh * gw;
-        if ((gh * gw) % 4 != 0 || (reinterpret_cast<uintptr_t>(inputs[i]) & 15) != 0) vec4 = false;
-    }
-    for (int i = n_levels; i <= kMaxLevels; ++i) t.cell_off[i] = off;
-    const int total_cells = off;
-    const int n_chunks = (total_cells + kChunk - 1) / kChunk;
-    char* ws = static_cast<char*>(workspace);
-    float* score = reinterpret_cast<float*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float), 256);
-    int* cls = reinterpret_cast<int*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(int), 256);
-    int* chunk_cnt = reinterpret_cast<int*>(ws);
-    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
-    dim3 grid(n_chunks, batch);
-    if (vec4)
-        hipLaunchKernelGGL(yolo_score_kernel<4>, grid, dim3(kChunk / 4), 0, stream, t, classes, info_len, total_cells, score,
-                           cls, chunk_cnt, n_chunks);
-    else
-        hipLaunchKernelGGL(yolo_score_kernel<1>, grid, dim3(kChunk), 0, stream, t, classes, info_len, total_cells, score, cls,
-                           chunk_cnt, n_chunks);
-    hipLaunchKernelGGL(yolo_emit_kernel, grid, dim3(kChunk), 0, stream, t, classes, total_cells, score, cls,
-                       chunk_cnt, n_chunks, max_out, out_elem, output, (const float4*)nullptr, br);
-    return trtx::check_launch("trtx_yolo_decode");
-}
-
-extern "C" int32_t trtx_yolo_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h,
-                                    int net_w, const int* strides, int max_out, float* output, void* workspace,
-                                    size_t workspace_bytes, hipStream_t stream) {
-    return trtx_yolo_decode_ex(inputs, n_levels, batch, classes, net_h, net_w, strides, max_out, 0, 0.f, 0, 0, 0, output, workspace,
-                               workspace_bytes, stream);
-}
-
-
-extern "C" size_t trtx_yolo_head_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels) {
-    size_t cells = 0;
-    for (int i = 0; i < n_levels; ++i) cells += (size_t)(net_h / strides[i]) * (net_w / strides[i]);
-    const size_t n_chunks = (cells + kChunk - 1) / kChunk;
-    return trtx::align_up((size_t)batch * cells * sizeof(float), 256) +
-           trtx::align_up((size_t)batch * cells * sizeof(int), 256) +
-           trtx::align_up((size_t)batch * cells * sizeof(float4), 256) +
-           trtx::align_up((size_t)batch * n_chunks * sizeof(int), 256);
-}
-
-static int32_t head_decode(const void* const* heads, const int* ld, int elem_bytes, int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
-                           const float* dfl_weights, int max_out, float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 8 || classes % 8 || max_out < 1 || !heads ||
-        !ld || !dfl_weights || !output || !workspace)
-        return TRTX_ERR_INVALID;
-    if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
-    HeadTable h{};
-    LevelTable t{};
-    h.n_levels = t.n_levels = n_levels;
-    int off = 0;
-    for (int i = 0; i < n_levels; ++i) {
-        const int gh = net_h / strides[i], gw = net_w / strides[i];
-        if (ld[i] % (16 / elem_bytes) || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
-        h.in[i] = heads[i];
-        h.ld[i] = ld[i];
-        h.cell_off[i] = t.cell_off[i] = off;
-        t.grid_w[i] = gw;
-        t.stride[i] = strides[i];
-        off += gh * gw;
-    }
-    for (int i = n_levels; i <= kMaxLevels; ++i) h.cell_off[i] = t.cell_off[i] = off;
-    const int total_cells = off;
-    const int n_chunks = (total_cells + kChunk - 1) / kChunk;
-    char* ws = static_cast<char*>(workspace);
-    float* score = reinterpret_cast<float*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float), 256);
-    int* cls = reinterpret_cast<int*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(int), 256);
-    float4* boxes = reinterpret_cast<float4*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float4), 256);
-    int* chunk_cnt = reinterpret_cast<int*>(ws);
-    if (hipMemsetAsync(chunk_cnt, 0, (size_t)batch * n_chunks * sizeof(int), stream) != hipSuccess) return TRTX_ERR_HIP;
-    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
-    if (elem_bytes == 2)
-        hipLaunchKernelGGL(yolo_head_score_kernel<_Float16>, dim3((total_cells + 255) / 256, batch), dim3(256), 0, stream, h, classes, total_cells, dfl_weights,
-                           score, cls, boxes, chunk_cnt, n_chunks);
-    else
-        hipLaunchKernelGGL(yolo_head_score_kernel<float>, dim3((total_cells + 255) / 256, batch), dim3(256), 0, stream, h, classes, total_cells, dfl_weights,
-                           score, cls, boxes, chunk_cnt, n_chunks);
-    hipLaunchKernelGGL(yolo_emit_kernel, dim3(n_chunks, batch), dim3(kChunk), 0, stream, t, classes, total_cells, score,
-                       cls, chunk_cnt, n_chunks, max_out, out_elem, output, (const float4*)boxes, YoloBranches{0, 0, 0, 0, 0.f});
-    return trtx::check_launch("trtx_yolo_head_decode_nhwc");
-}
-
-extern "C" int32_t trtx_yolo_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch,
-                                              int classes, int net_h, int net_w, const int* strides,
-                                              const float* dfl_weights, int max_out, float* output, void* workspace,
-                                              size_t workspace_bytes, hipStream_t stream) {
-    return head_decode(heads, ld, 2, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
-}
-
-extern "C" int32_t trtx_yolo_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
-                                                  const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
-                                                  size_t workspace_bytes, hipStream_t stream) {
-    return head_decode(heads, ld, 4, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------
-// Fused task head (YOLO11 seg / pose / obb, explicit batch): the det head's score pass with a masked class tail, and an emit pass
-// that also reads the cell's task branch from its own NHWC tensor - the output of the cv4 1x1 convolution (yolo11/src/model.cpp:474-507).
-// It replaces, per level, the (64 + classes)-channel head converted to fp32 LINEAR, the slices, the DFL chain, the branch's own
-// conversion, the concat scatters and then the plugin's two passes (yololayer.cu:178-279).  The det kernels above stay as they are:
-// their code objects are pinned by the det plans, and the plugin's by tests/test_ref_pinning.py.
-namespace {
-
-struct BranchTable {
-    const void* in[kMaxLevels];  // device pointers, [batch][cells_l][ld[l]]: channels [0, extra) of the cell's branch
-    int ld[kMaxLevels];
-    int vec;                      // every ld and base allows 16-byte loads
-};
-
-// Pass 1 of the task head: yolo_head_score_kernel's DFL and class scan, with `classes` any count >= 1.  The last (classes % 8) logits
-// are read one by one, so the NHWC padding channels behind them never reach the argmax (nor a load past the tensor's last pixel).
-// With classes % 8 == 0 the arithmetic is the det kernel's, operation for operation, so boxes, confidences and classes are the same bits.
-template <typename T>
-__global__ __launch_bounds__(256) void yolo_task_score_kernel(HeadTable t, int classes, int total_cells,
-                                                              const float* __restrict__ dfl_w,
-                                                              float* __restrict__ score, int* __restrict__ cls_out,
-                                                              float4* __restrict__ boxes,
-                                                              int* __restrict__ chunk_cnt, int n_chunks) {
-    __shared__ int s_list[256];
-    __shared__ int s_n, s_keep;
-    const int b = blockIdx.y;
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    const int full = classes & ~7;   // classes read eight at a time; [full, classes) one at a time
-    if (threadIdx.x == 0) {
-        s_n = 0;
-        s_keep = 0;
-    }
-    __syncthreads();
-    auto cell_ptr = [&](int gg) {
-        int l = 0;
-#pragma unroll
-        for (int i = 1; i < kMaxLevels; ++i)
-            if (i < t.n_levels && gg >= t.cell_off[i]) l = i;
-        const int cells = t.cell_off[l + 1] - t.cell_off[l];
-        return static_cast<const T*>(t.in[l]) + ((size_t)b * cells + (gg - t.cell_off[l])) * t.ld[l];
-    };
-    // phase 1, every cell: some raw logit > -2.3 (sigmoid >= 0.1 needs >= -2.1972); read by the wave, one piece of eight per lane
-    s_list[threadIdx.x] = 0;
-    __syncthreads();
-    {
-        const int wave0 = threadIdx.x & ~63, lane = threadIdx.x & 63;
-        const int pieces = (classes + 7) >> 3;
-        const int g0 = blockIdx.x * 256 + wave0;
-        int cells_here = total_cells - g0;
-        cells_here = cells_here > 64 ? 64 : cells_here;
-        const int n = cells_here * pieces;
-        for (int j = lane; j < n; j += 64) {
-            const int c = j / pieces, q = j - c * pieces;
-            const T* p = cell_ptr(g0 + c) + 64 + q * 8;
-            float m;
-            if (q * 8 < full) {
-                float v[8];
-                load8(p, v);
-                m = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
-            } else {
-                m = -INFINITY;
-                for (int i = 0; i < classes - full; ++i) m = fmaxf(m, (float)p[i]);
-            }
-            if (m > -2.3f) s_list[wave0 + c] = 1;
-        }
-    }
-    __syncthreads();
-    bool maybe = false;
-    if (g < total_cells) {
-        maybe = s_list[threadIdx.x] != 0;
-        if (!maybe) {
-            const size_t o = (size_t)b * total_cells + g;
-            score[o] = -1.0f;
-            cls_out[o] = 0;
-        }
-    }
-    __syncthreads();
-    {
-        const unsigned long long m = __ballot(maybe);
-        int base = 0;
-        if ((threadIdx.x & 63) == 0 && m) base = atomicAdd(&s_n, __popcll(m));
-        base = __shfl(base, 0);
-        if (maybe) s_list[base + __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull))] = threadIdx.x;
-    }
-    __syncthreads();
-    // phase 2, possible survivors only: DFL softmax . w per side, sigmoid of every class, strict '>' argmax (as the det kernel)
-    int kept = 0;
-    for (int k = threadIdx.x; k < s_n; k += 256) {
-        const int gg = blockIdx.x * 256 + s_list[k];
-        const T* cell = cell_ptr(gg);
-        float w[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = dfl_w[i];
-        float side[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            float lo[8], hi[8], x[16];
-            load8(cell + s * 16, lo);
-            load8(cell + s * 16 + 8, hi);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                x[i] = lo[i];
-                x[8 + i] = hi[i];
-            }
-            float mx = x[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mx = fmaxf(mx, x[i]);
-            float sum = 0.f, acc = 0.f;
-            if constexpr (sizeof(T) == 4) {
-                float ex[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    ex[i] = expf(x[i] - mx);
-                    sum += ex[i];
-                }
-                const float inv = 1.0f / sum;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc = fmaf(ex[i] * inv, w[i], acc);
-                side[s] = acc;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float ex = expf(x[i] - mx);
-                    sum += ex;
-                    acc = fmaf(ex, w[i], acc);
-                }
-                side[s] = acc / sum;
-            }
-        }
-        float best = 0.0f;
-        int bcls = 0;
-        const T* cl = cell + 64;
         for (int c0 = 0; c0 < full; c0 += 8) {
             float v[8];
             load8(cl + c0, v);
@@ -671,11 +388,13 @@ __global__ __launch_bounds__(256) void yolo_task_score_kernel(HeadTable t, int c
                 }
             }
         }
-        for (int c = full; c < classes; ++c) {
-            const float pr = logist((float)cl[c]);
-            if (pr > best) {
-                best = pr;
-                bcls = c;
+        if constexpr (TAIL) {
+            for (int c = full; c < classes; ++c) {
+                const float pr = logist((float)cl[c]);
+                if (pr > best) {
+                    best = pr;
+                    bcls = c;
+                }
             }
         }
         const bool keep = !((double)best < 0.1);
@@ -685,9 +404,27 @@ __global__ __launch_bounds__(256) void yolo_task_score_kernel(HeadTable t, int c
         boxes[o] = make_float4(side[0], side[1], side[2], side[3]);
         kept += keep ? 1 : 0;
     }
-    if (kept) atomicAdd(&s_keep, kept);
-    __syncthreads();
+    // per-kChunk candidate counts (two 256-thread workgroups feed one chunk counter)
+    trtx::workgroup_count(&s_keep, kept);
     if (threadIdx.x == 0 && s_keep) atomicAdd(&chunk_cnt[b * n_chunks + (blockIdx.x * 256) / kChunk], s_keep);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void yolo_head_score_kernel(HeadTable t, int classes, int total_cells,
+                                                              const float* __restrict__ dfl_w,
+                                                              float* __restrict__ score, int* __restrict__ cls_out,
+                                                              float4* __restrict__ boxes,
+                                                              int* __restrict__ chunk_cnt, int n_chunks) {
+    head_score<T, false>(t, classes, total_cells, dfl_w, score, cls_out, boxes, chunk_cnt, n_chunks);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void yolo_task_score_kernel(HeadTable t, int classes, int total_cells,
+                                                              const float* __restrict__ dfl_w,
+                                                              float* __restrict__ score, int* __restrict__ cls_out,
+                                                              float4* __restrict__ boxes,
+                                                              int* __restrict__ chunk_cnt, int n_chunks) {
+    head_score<T, true>(t, classes, total_cells, dfl_w, score, cls_out, boxes, chunk_cnt, n_chunks);
 }
 
 // The seg / pose / obb fields of one Detection record (yololayer.cu:222-279) from the cell's branch channels `br` (contiguous; `vec`:
@@ -779,7 +516,7 @@ __global__ __launch_bounds__(kChunk) void yolo_task_emit_kernel(LevelTable t, Br
     const int slot = before + in_wave;
     float* out = output + (size_t)b * out_elem;
     if (keep && slot < max_out) {
-        const int l = find_level(t, g);
+        const int l = find_level(t.cell_off, t.n_levels, g);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         const int e = g - t.cell_off[l];
         const int gw = t.grid_w[l];
@@ -804,6 +541,178 @@ __global__ __launch_bounds__(kChunk) void yolo_task_emit_kernel(LevelTable t, Br
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------
+// Host side.  The three entry paths (plugin, det head, task head) share the level geometry and the workspace layout.
+
+// geometry of the levels, for however many of them fit the table; `in` is left to the caller (the plugin's planar inputs)
+static LevelTable make_levels(int n_levels, int net_h, int net_w, const int* strides) {
+    LevelTable t{};
+    t.n_levels = n_levels;
+    int off = 0;
+    for (int i = 0; i < n_levels && i < kMaxLevels; ++i) {
+        t.cell_off[i] = off;
+        t.grid_w[i] = net_w / strides[i];
+        t.stride[i] = strides[i];
+        off += (net_h / strides[i]) * t.grid_w[i];
+    }
+    for (int i = n_levels < 0 ? 0 : n_levels; i <= kMaxLevels; ++i) t.cell_off[i] = off;
+    return t;
+}
+
+static size_t count_cells(int net_h, int net_w, const int* strides, int n_levels) {
+    size_t cells = 0;
+    for (int i = 0; i < n_levels; ++i) cells += (size_t)(net_h / strides[i]) * (net_w / strides[i]);
+    return cells;
+}
+
+// the NHWC head tensors over the same levels
+static HeadTable make_head(const LevelTable& t, const void* const* heads, const int* ld) {
+    HeadTable h{};
+    h.n_levels = t.n_levels;
+    for (int i = 0; i < t.n_levels; ++i) {
+        h.in[i] = heads[i];
+        h.ld[i] = ld[i];
+    }
+    for (int i = 0; i <= kMaxLevels; ++i) h.cell_off[i] = t.cell_off[i];
+    return h;
+}
+
+// score | cls | boxes (fused heads only) | chunk_cnt, each aligned to 256 bytes.  The *_workspace functions carve a null base, so the
+// size they report is the end of the same layout.
+struct Workspace {
+    float* score;
+    int* cls;
+    float4* boxes;
+    int* chunk_cnt;
+    int n_chunks;
+    size_t bytes;
+};
+
+static Workspace carve(void* base, int batch, size_t cells, bool with_boxes) {
+    Workspace w{};
+    w.n_chunks = (int)((cells + kChunk - 1) / kChunk);
+    const auto take = [&](size_t bytes) {
+        void* p = base ? static_cast<char*>(base) + w.bytes : nullptr;
+        w.bytes += trtx::align_up(bytes, 256);
+        return p;
+    };
+    w.score = static_cast<float*>(take((size_t)batch * cells * sizeof(float)));
+    w.cls = static_cast<int*>(take((size_t)batch * cells * sizeof(int)));
+    if (with_boxes) w.boxes = static_cast<float4*>(take((size_t)batch * cells * sizeof(float4)));
+    w.chunk_cnt = static_cast<int*>(take((size_t)batch * w.n_chunks * sizeof(int)));
+    return w;
+}
+
+extern "C" size_t trtx_yolo_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels) {
+    return carve(nullptr, batch, count_cells(net_h, net_w, strides, n_levels), false).bytes;
+}
+
+extern "C" size_t trtx_yolo_head_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels) {
+    return carve(nullptr, batch, count_cells(net_h, net_w, strides, n_levels), true).bytes;
+}
+
+extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
+                                       const int* strides, int max_out, int n_kpt, float kpt_conf, int is_seg, int is_pose, int is_obb,
+                                       float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !inputs || !output ||
+        !workspace || n_kpt < 0 || n_kpt > 17)
+        return TRTX_ERR_INVALID;
+    if (workspace_bytes < trtx_yolo_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
+    const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, n_kpt, kpt_conf};
+    const int info_len = 4 + classes + (br.seg ? 32 : 0) + (br.pose ? n_kpt * 3 : 0) + (br.obb ? 1 : 0);
+    LevelTable t = make_levels(n_levels, net_h, net_w, strides);
+    bool vec4 = true;
+    for (int i = 0; i < n_levels; ++i) {
+        t.in[i] = inputs[i];
+        if ((t.cell_off[i + 1] - t.cell_off[i]) % 4 != 0 || (reinterpret_cast<uintptr_t>(inputs[i]) & 15) != 0) vec4 = false;
+    }
+    const int total_cells = t.cell_off[n_levels];
+    const Workspace w = carve(workspace, batch, total_cells, false);
+    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
+    dim3 grid(w.n_chunks, batch);
+    if (vec4)
+        hipLaunchKernelGGL(yolo_score_kernel<4>, grid, dim3(kChunk / 4), 0, stream, t, classes, info_len, total_cells, w.score,
+                           w.cls, w.chunk_cnt, w.n_chunks);
+    else
+        hipLaunchKernelGGL(yolo_score_kernel<1>, grid, dim3(kChunk), 0, stream, t, classes, info_len, total_cells, w.score, w.cls,
+                           w.chunk_cnt, w.n_chunks);
+    hipLaunchKernelGGL(yolo_emit_kernel, grid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls,
+                       w.chunk_cnt, w.n_chunks, max_out, out_elem, output, (const float4*)nullptr, br);
+    return trtx::check_launch("trtx_yolo_decode");
+}
+
+extern "C" int32_t trtx_yolo_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h,
+                                    int net_w, const int* strides, int max_out, float* output, void* workspace,
+                                    size_t workspace_bytes, hipStream_t stream) {
+    return trtx_yolo_decode_ex(inputs, n_levels, batch, classes, net_h, net_w, strides, max_out, 0, 0.f, 0, 0, 0, output, workspace,
+                               workspace_bytes, stream);
+}
+
+// The fused heads after their argument checks: `bt` = nullptr is the det head (yolo_head_score_kernel, then the plugin's emit pass on
+// the DFL boxes), otherwise the task head with the masked class tail and the branch tensors of `bt`.
+static int32_t launch_head(const LevelTable& t, const HeadTable& h, const BranchTable* bt, int elem_bytes, int batch, int classes,
+                           const float* dfl_weights, int max_out, const YoloBranches& br, float* output, void* workspace, hipStream_t stream,
+                           const char* what) {
+    const int total_cells = t.cell_off[t.n_levels];
+    const Workspace w = carve(workspace, batch, total_cells, true);
+    if (hipMemsetAsync(w.chunk_cnt, 0, (size_t)batch * w.n_chunks * sizeof(int), stream) != hipSuccess) return TRTX_ERR_HIP;
+    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
+    const dim3 sgrid((total_cells + 255) / 256, batch), egrid(w.n_chunks, batch);
+    const auto score = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, sgrid, dim3(256), 0, stream, h, classes, total_cells, dfl_weights, w.score, w.cls, w.boxes, w.chunk_cnt,
+                           w.n_chunks);
+    };
+    const auto task_emit = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, egrid, dim3(kChunk), 0, stream, t, *bt, total_cells, w.score, w.cls, w.chunk_cnt, w.n_chunks, max_out,
+                           out_elem, output, (const float4*)w.boxes, br);
+    };
+    if (!bt) {
+        if (elem_bytes == 2)
+            score(yolo_head_score_kernel<_Float16>);
+        else
+            score(yolo_head_score_kernel<float>);
+        hipLaunchKernelGGL(yolo_emit_kernel, egrid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls, w.chunk_cnt,
+                           w.n_chunks, max_out, out_elem, output, (const float4*)w.boxes, br);
+    } else if (elem_bytes == 2) {
+        score(yolo_task_score_kernel<_Float16>);
+        task_emit(yolo_task_emit_kernel<_Float16>);
+    } else {
+        score(yolo_task_score_kernel<float>);
+        task_emit(yolo_task_emit_kernel<float>);
+    }
+    return trtx::check_launch(what);
+}
+
+static int32_t head_decode(const void* const* heads, const int* ld, int elem_bytes, int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                           const float* dfl_weights, int max_out, float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 8 || classes % 8 || max_out < 1 || !heads ||
+        !ld || !dfl_weights || !output || !workspace)
+        return TRTX_ERR_INVALID;
+    if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
+    for (int i = 0; i < n_levels; ++i)
+        if (ld[i] % (16 / elem_bytes) || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
+    const LevelTable t = make_levels(n_levels, net_h, net_w, strides);
+    return launch_head(t, make_head(t, heads, ld), nullptr, elem_bytes, batch, classes, dfl_weights, max_out, YoloBranches{0, 0, 0, 0, 0.f},
+                       output, workspace, stream, "trtx_yolo_head_decode_nhwc");
+}
+
+extern "C" int32_t trtx_yolo_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch,
+                                              int classes, int net_h, int net_w, const int* strides,
+                                              const float* dfl_weights, int max_out, float* output, void* workspace,
+                                              size_t workspace_bytes, hipStream_t stream) {
+    return head_decode(heads, ld, 2, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_yolo_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                  const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                                  size_t workspace_bytes, hipStream_t stream) {
+    return head_decode(heads, ld, 4, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
+}
+
+// Fused task head (YOLO11 seg / pose / obb, explicit batch): reads, besides the det head's tensors, the cell's task branch from its own
+// NHWC tensor - the output of the cv4 1x1 convolution (yolo11/src/model.cpp:474-507).  It replaces, per level, the (64 + classes)-channel
+// head converted to fp32 LINEAR, the slices, the DFL chain, the branch's own conversion, the concat scatters and then the plugin's two
+// passes (yololayer.cu:178-279).
 static int32_t task_head_decode(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld, int elem_bytes,
                                 int n_levels, int batch, int classes, int net_h, int net_w, const int* strides, const float* dfl_weights,
                                 int max_out, int is_seg, int is_pose, int is_obb, int n_kpt, float kpt_conf, float* output, void* workspace,
@@ -814,54 +723,20 @@ static int32_t task_head_decode(const void* const* heads, const int* ld, const v
     if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
     const int extra = is_seg ? 32 : (is_pose ? 3 * n_kpt : 1);
     const int vec_elems = 16 / elem_bytes;
-    HeadTable h{};
-    LevelTable t{};
     BranchTable bt{};
-    h.n_levels = t.n_levels = n_levels;
     bt.vec = 1;
-    int off = 0;
     for (int i = 0; i < n_levels; ++i) {
-        const int gh = net_h / strides[i], gw = net_w / strides[i];
         // the head's 16-byte loads read channels up to 64 + (classes & ~7): a stride of at least 64 + classes, a multiple of 16 bytes
         if (ld[i] % vec_elems || ld[i] < 64 + classes || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
         if (!branches[i] || branch_ld[i] < extra) return TRTX_ERR_INVALID;
         if (branch_ld[i] % vec_elems || (reinterpret_cast<uintptr_t>(branches[i]) & 15)) bt.vec = 0;
-        h.in[i] = heads[i];
-        h.ld[i] = ld[i];
         bt.in[i] = branches[i];
         bt.ld[i] = branch_ld[i];
-        h.cell_off[i] = t.cell_off[i] = off;
-        t.grid_w[i] = gw;
-        t.stride[i] = strides[i];
-        off += gh * gw;
     }
-    for (int i = n_levels; i <= kMaxLevels; ++i) h.cell_off[i] = t.cell_off[i] = off;
-    const int total_cells = off;
-    const int n_chunks = (total_cells + kChunk - 1) / kChunk;
-    char* ws = static_cast<char*>(workspace);
-    float* score = reinterpret_cast<float*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float), 256);
-    int* cls = reinterpret_cast<int*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(int), 256);
-    float4* boxes = reinterpret_cast<float4*>(ws);
-    ws += trtx::align_up((size_t)batch * total_cells * sizeof(float4), 256);
-    int* chunk_cnt = reinterpret_cast<int*>(ws);
-    if (hipMemsetAsync(chunk_cnt, 0, (size_t)batch * n_chunks * sizeof(int), stream) != hipSuccess) return TRTX_ERR_HIP;
-    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
+    const LevelTable t = make_levels(n_levels, net_h, net_w, strides);
     const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, is_pose ? n_kpt : 0, kpt_conf};
-    const dim3 sgrid((total_cells + 255) / 256, batch), egrid(n_chunks, batch);
-    if (elem_bytes == 2) {
-        hipLaunchKernelGGL(yolo_task_score_kernel<_Float16>, sgrid, dim3(256), 0, stream, h, classes, total_cells, dfl_weights, score, cls, boxes,
-                           chunk_cnt, n_chunks);
-        hipLaunchKernelGGL(yolo_task_emit_kernel<_Float16>, egrid, dim3(kChunk), 0, stream, t, bt, total_cells, score, cls, chunk_cnt, n_chunks,
-                           max_out, out_elem, output, (const float4*)boxes, br);
-    } else {
-        hipLaunchKernelGGL(yolo_task_score_kernel<float>, sgrid, dim3(256), 0, stream, h, classes, total_cells, dfl_weights, score, cls, boxes,
-                           chunk_cnt, n_chunks);
-        hipLaunchKernelGGL(yolo_task_emit_kernel<float>, egrid, dim3(kChunk), 0, stream, t, bt, total_cells, score, cls, chunk_cnt, n_chunks,
-                           max_out, out_elem, output, (const float4*)boxes, br);
-    }
-    return trtx::check_launch("trtx_yolo_task_head_decode_nhwc");
+    return launch_head(t, make_head(t, heads, ld), &bt, elem_bytes, batch, classes, dfl_weights, max_out, br, output, workspace, stream,
+                       "trtx_yolo_task_head_decode_nhwc");
 }
 
 extern "C" int32_t trtx_yolo_task_head_decode_nhwc(const void* const* heads, const int* ld, const void* const* branches, const int* branch_ld,
