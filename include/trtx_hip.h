@@ -131,6 +131,22 @@ size_t trtx_yolov5_decode_workspace(int batch, const int* grid_w, const int* gri
 int32_t trtx_yolov5_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
                            const int* grid_w, const int* grid_h, const float* anchors, int max_out, int is_segmentation,
                            float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Fused anchor head: trtx_yolov5_decode (detection, no mask coefficients) on the detect convolutions' own NHWC output, what the engine
+ * uses instead of one layout pass per level followed by YoloLayerPlugin::enqueue (yolov5/src/model.cpp:331-343, yololayer.cu:161-227).
+ *   heads[l]   device fp16 [batch][grid_h[l] * grid_w[l]][ld[l]]; channel k * (5 + classes) + j of a pixel = value j of anchor k
+ *              (x, y, w, h, objectness, class logits); ld[l] >= 3 * (5 + classes), channels beyond that are padding and never read
+ *              into a result.  Rows whose base and ld are multiples of 16 bytes are read with 16-byte loads, others element-wise.
+ *   `heads`, `ld`, `grid_w`, `grid_h` and `anchors` are HOST arrays.  Output, candidate order and arithmetic: trtx_yolov5_decode.
+ */
+size_t trtx_yolov5_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels);
+int32_t trtx_yolov5_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                     const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                     void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* The same on the NHWC fp32 head tensors of an fp32 engine: ld in floats. */
+int32_t trtx_yolov5_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                         const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                         void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /* Oriented boxes (yolov8 obb): host nms_obb() on the GPU (yolov8/src/postprocess.cpp:303-393, ProbIoU, "conf <= thresh" dropped,
  * erased when probiou >= nms_thresh); keep_det is [batch][max_out][7] = cx, cy, w, h, conf, class, angle.  And the reference's
  * GPU mode for oriented boxes, cuda_decode_obb + cuda_nms_obb (yolov8/src/postprocess.cu:7-40, 113-166): out [batch][1 + max_out*8]. */

@@ -95,16 +95,30 @@ class Network:
         self._keep += [sa, ca, pa]
         return self._layer(self.L.trtx_add_scale(self.n, x, 1, sp, ctypes.c_int64(sn), cp, ctypes.c_int64(cn), pp, ctypes.c_int64(pn)), "add_scale")
 
-    def plugin(self, inputs, name, version="1"):
-        """getPluginRegistry()->getPluginCreator(name, version)->createPlugin(name, empty field collection), then addPluginV2 -
-        what convBnMish does for "Mish_TRT" (yolov4/yolov4.cpp:207-212).  The v-tables are opaque blobs here (sized generously)."""
+    def plugin(self, inputs, name, version="1", fields=None):
+        """getPluginRegistry()->getPluginCreator(name, version)->createPlugin(name, field collection), then addPluginV2 - with the empty
+        collection what convBnMish does for "Mish_TRT" (yolov4/yolov4.cpp:207-212).  fields: [(name, int32 / float32 / uint8 array)] or
+        [(name, array, length)] where the creator counts elements of a struct type (the "kernels" field of the anchor-based
+        "YoloLayer_TRT", yolov5/src/model.cpp:270-273).  The v-tables are opaque blobs here (sized generously)."""
         creator = (ctypes.c_void_p * 8)()
         self.L.trtx_registry_get.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p]
         self.L.trtx_add_plugin_v2.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
         check(self.L.trtx_registry_get(name.encode(), version.encode(), ctypes.cast(creator, ctypes.c_void_p)), f"no plugin creator {name}/{version}")
         create = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p)(creator[3])
         vt = (ctypes.c_void_p * 16)()
-        if create(creator[0], name.encode(), None, 0, ctypes.cast(vt, ctypes.c_void_p)) != 0:
+        farr, nf, keep = None, 0, []
+        if fields:
+            class Field(ctypes.Structure):   # trtx_plugin_field
+                _fields_ = [("name", ctypes.c_char_p), ("data", ctypes.c_void_p), ("type", ctypes.c_int32), ("length", ctypes.c_int32)]
+            nf = len(fields)
+            farr = (Field * nf)()
+            for i, f in enumerate(fields):
+                a = np.ascontiguousarray(f[1])
+                keep.append(a)
+                code = 5 if a.dtype == np.int32 else (1 if a.dtype == np.float32 else 6)   # nvinfer1::PluginFieldType
+                farr[i] = Field(f[0].encode(), a.ctypes.data_as(ctypes.c_void_p), code, f[2] if len(f) > 2 else a.size)
+            farr = ctypes.cast(farr, ctypes.c_void_p)
+        if create(creator[0], name.encode(), farr, nf, ctypes.cast(vt, ctypes.c_void_p)) != 0:
             raise RuntimeError(f"createPlugin({name}) failed")
         arr = (ctypes.c_int32 * len(inputs))(*inputs)
         l = self._layer(self.L.trtx_add_plugin_v2(self.n, ctypes.cast(arr, ctypes.c_void_p), len(inputs), ctypes.cast(vt, ctypes.c_void_p)), "add_plugin_v2")

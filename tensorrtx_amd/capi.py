@@ -223,6 +223,27 @@ def yolov5_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, i
     return out
 
 
+def yolov5_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_out=1000):
+    """The fused anchor head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32; ld >= 3 * (5 + classes), the rest is padding):
+    trtx_yolov5_head_decode_nhwc{,_f32}.  grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1 + max_out * 38]"""
+    import numpy as np
+    import torch
+    L = lib()
+    B, n, dev = heads[0].shape[0], len(heads), heads[0].device
+    hp, hl = _head_table(heads)
+    gw = (ctypes.c_int * n)(*[g[0] for g in grids])
+    gh = (ctypes.c_int * n)(*[g[1] for g in grids])
+    an = np.ascontiguousarray(anchors, dtype=np.float32).reshape(n, 6)
+    L.trtx_yolov5_head_decode_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolov5_head_decode_workspace(B, gw, gh, n)
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    out = torch.zeros((B, 1 + max_out * DET5_FLOATS), dtype=torch.float32, device=dev)
+    fn = L.trtx_yolov5_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolov5_head_decode_nhwc
+    check(fn(hp, hl, n, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out), _p(ws), ctypes.c_size_t(ws_bytes),
+             _stream()), "trtx_yolov5_head_decode_nhwc")
+    return out
+
+
 def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
     """yolov5 batch_nms replacement (yolov5/src/postprocess.cpp:30-80). Returns keep_idx, keep_cnt, keep_det [B, max_out, 6]."""
     import torch

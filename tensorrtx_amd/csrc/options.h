@@ -31,6 +31,7 @@ struct Options {
     bool roles = true;           // TRTX_CONV_ROLES=0: no fetching / multiplying wave-role variants among the candidates (fp32 plans)
     bool f32_mfma = true;        // TRTX_F32_DIRECT=1: fp32 engines on the scalar direct kernel of rounds 1-4 (no fp32 MFMA, no fp32 stem kernel)
     bool area_attention = true;  // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
+    bool yolo5_head = true;      // TRTX_YOLO5_HEAD=0: the anchor-based (YOLOv5) detect tail keeps the plugin route (layout passes to fp32 planes + YoloLayer_TRT)
     bool roialign_fused = true;  // TRTX_ROIALIGN_PLUGIN=1: RoIAlign stays a plugin op (fp32 NCHW edge)
     bool roialign_fold_stride = true;   // TRTX_ROIALIGN_FOLD_STRIDE=0: RoIAlign emits all 14 x 14 bins
     bool profile_kernel_events = true;  // TRTX_PROFILE_NO_KERNEL_EVENTS=1: trtx_context_profile without per-launch start / stop events

@@ -494,6 +494,21 @@ bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out) {
     return true;
 }
 
+bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
+    if (v.enqueue != yolo5_enqueue || !v.self) return false;
+    const auto* y = static_cast<const Yolo5Layer*>(v.self);
+    out->classes = y->class_count;
+    out->net_w = y->net_w;
+    out->net_h = y->net_h;
+    out->max_out = y->max_out;
+    out->seg = y->seg;
+    out->grid_w.clear();
+    out->grid_h.clear();
+    out->anchors.clear();
+    y->geometry(&out->grid_w, &out->grid_h, &out->anchors);
+    return true;
+}
+
 // built-in plugins only enqueue kernels and stream-ordered memsets on the caller's stream: safe inside a stream capture
 bool builtin_plugin_capturable(const trtx_plugin_vtbl& v) {
     return v.enqueue == yolo_enqueue || v.enqueue == yolo5_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;

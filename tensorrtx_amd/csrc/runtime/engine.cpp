@@ -151,7 +151,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
         int32_t st = TRTX_OK;
-        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_ROI_ALIGN);
+        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
@@ -374,6 +374,22 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 st = (t0.dtype == DT_F32 ? trtx_yolo_task_head_decode_nhwc_f32 : trtx_yolo_task_head_decode_nhwc)(
                         heads, lds, branches, blds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5],
                         reinterpret_cast<const float*>(W + op.w_off), op.i[3], op.i[9] == 1, op.i[9] == 2, op.i[9] == 3, op.i[10], op.f[0],
+                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+                break;
+            }
+            case OP_YOLO5_HEAD: {
+                const int nl = op.i[4];
+                const void* heads[8];
+                int lds[8], gw[8], gh[8];
+                if (nl < 1 || nl > 8 || (int)op.iv.size() != 2 * nl || (int)op.fv.size() != 6 * nl) { st = TRTX_ERR_STATE; break; }
+                for (int k = 0; k < nl; ++k) {
+                    heads[k] = R.ptr(op.in[k]);
+                    lds[k] = plan.tensors[op.in[k]].ld;
+                    gw[k] = op.iv[2 * k];
+                    gh[k] = op.iv[2 * k + 1];
+                }
+                st = (t0.dtype == DT_F32 ? trtx_yolov5_head_decode_nhwc_f32 : trtx_yolov5_head_decode_nhwc)(
+                        heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], gw, gh, op.fv.data(), op.i[3],
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
                 break;
             }

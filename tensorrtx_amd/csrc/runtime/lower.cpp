@@ -209,6 +209,37 @@ struct Lowerer {
         return true;
     }
 
+    // The anchor head at its plugin's layer: the detect convolutions' NHWC tensors in, the plugin's LINEAR output out.
+    bool emit_yolo5_head(const Yolo5HeadFuse& f) {
+        const LayerDef& l = net.layers[f.plugin_layer];
+        const Yolo5LayerParams& pr = f.params;
+        std::vector<int> ins;
+        for (int t : f.head_tensor) {
+            if (plan.tensors[pt_of[t]].layout != LAY_NHWC) return fail(l.name + ": fused anchor head on a tensor that is not NHWC");
+            ins.push_back(pt_of[t]);
+        }
+        const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
+        POp& op = add_op(OP_YOLO5_HEAD, l.name + " [fused anchor decode]", ins, {out});
+        op.i[0] = pr.classes;
+        op.i[1] = pr.net_h;
+        op.i[2] = pr.net_w;
+        op.i[3] = pr.max_out;
+        op.i[4] = (int)ins.size();
+        for (size_t k = 0; k < ins.size(); ++k) {
+            op.iv.push_back(pr.grid_w[k]);
+            op.iv.push_back(pr.grid_h[k]);
+        }
+        op.fv = pr.anchors;
+        // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
+        if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
+        op.ws_bytes = trtx_yolov5_head_decode_workspace(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
+        // what it must read: the three objectness values of every pixel (nothing else of a pixel without a candidate), and what it writes
+        for (int t : ins) op.bytes += (double)dtype_size(dt) * plan.tensors[t].H * plan.tensors[t].W * 3;
+        op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
+        pt_of[l.outputs[0]] = out;
+        return true;
+    }
+
     // ---- per-kind emission ----------------------------------------------------------------------------
     bool emit_conv(const FusedConv& c) {
         const LayerDef& l = net.layers[c.conv_layer];
@@ -250,6 +281,12 @@ struct Lowerer {
         a.Ho = to.H;
         a.Wo = to.W;
         a.Cout = to.C;
+        // a detect convolution under the fused anchor head (its only reader, which knows the real channel count): the output channels round
+        // up to the tensor's 16-byte pixel stride, with zero filter rows and biases, so that 255 channels keep the 16-byte stores
+        if (fu.pad_cout[c.conv_layer] && to.Calloc > to.C && c.residual < 0) {
+            op.cout_real = to.C;
+            a.Cout = to.Calloc;
+        }
         if (l.kind == L_FULLY_CONNECTED) {
             a.kh = ti.H;
             a.kw = ti.W;
@@ -273,7 +310,7 @@ struct Lowerer {
         a.alpha1 = c.alpha1;
         a.act2 = c.act2;
         a.alpha2 = c.alpha2;
-        op.flops = 2.0 * to.nmul * a.Ho * a.Wo * a.Cout * (double)a.kh * a.kw * (a.Cin / a.groups);
+        op.flops = 2.0 * to.nmul * a.Ho * a.Wo * to.C * (double)a.kh * a.kw * (a.Cin / a.groups);
         pt_of[c.out_tensor] = out;
         return true;
     }
@@ -797,6 +834,10 @@ struct Lowerer {
         for (size_t li = 0; li < net.layers.size(); ++li) {
             if (fu.yolo_at[li] >= 0) {
                 if (!emit_yolo_head(fu.yolo_heads[fu.yolo_at[li]])) return false;
+                continue;
+            }
+            if (fu.yolo5_at[li] >= 0) {
+                if (!emit_yolo5_head(fu.yolo5_heads[fu.yolo5_at[li]])) return false;
                 continue;
             }
             if (fu.attn_at[li] >= 0) {

@@ -265,6 +265,47 @@ void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
     }
 }
 
+// ---- YOLOv5 detect tail (yolov5/src/model.cpp:331-343): three or four biased 1x1 detect convolutions straight into the anchor-based
+// YoloLayer_TRT.  When the plugin is the built-in one (detection, no mask coefficients) and every input is the output of a groups-1,
+// 1x1, stride-1 convolution with 3 * (5 + classes) outputs that nobody else reads and that is no network output, the plugin becomes one
+// OP_YOLO5_HEAD on the convolutions' NHWC tensors (fp16 and fp32 engines).  The convolutions stay ordinary convolutions; pad_cout marks
+// them so that a channel count that is no 16-byte multiple (255) does not cost them their vector stores.  Anything else keeps the
+// plugin: marked heads, a second reader, another kernel or channel count, a grid that is not the tensor's, TRTX_YOLO5_HEAD=0.
+void match_yolo5_heads(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    const int e = net.explicit_batch ? 1 : 0;
+    if (!g.opt.yolo5_head) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li] || !l.plugin) continue;
+        Yolo5HeadFuse h;
+        if (!builtin_yolo5_params(l.plugin->v, &h.params)) continue;
+        const Yolo5LayerParams& pr = h.params;
+        if (pr.seg || pr.classes < 1 || l.inputs.empty() || l.inputs.size() > 8 || l.inputs.size() != pr.grid_w.size()) continue;
+        bool ok = true;
+        for (size_t k = 0; ok && k < l.inputs.size(); ++k) {
+            const int t = l.inputs[k];
+            const int lc = g.producer(t);
+            const Dims& d = net.tensors[t].dims;
+            ok = lc >= 0 && net.layers[lc].kind == L_CONV && !f.absorbed[lc] && g.only_used_by(t, {(int)li}) && d.nb == 3 + e;
+            if (!ok) break;
+            const LayerDef& cv = net.layers[lc];
+            ok = cv.groups == 1 && cv.kernel[0] == 1 && cv.kernel[1] == 1 && cv.stride[0] == 1 && cv.stride[1] == 1 && cv.padding[0] == 0 &&
+                 cv.padding[1] == 0 && cv.nb_out == 3 * (5 + pr.classes) && d.d[e] == cv.nb_out && d.d[1 + e] == pr.grid_h[k] &&
+                 d.d[2 + e] == pr.grid_w[k] && (!e || d.d[0] == net.tensors[l.inputs[0]].dims.d[0]);
+            for (size_t j = 0; j < k; ++j) ok = ok && l.inputs[j] != t;
+            h.head_tensor.push_back(t);
+            h.conv_layer.push_back(lc);
+        }
+        if (!ok) continue;
+        h.plugin_layer = (int)li;
+        f.absorbed[li] = true;
+        for (int lc : h.conv_layer) f.pad_cout[lc] = true;
+        f.yolo5_at[li] = (int)f.yolo5_heads.size();
+        f.yolo5_heads.push_back(h);
+    }
+}
+
 // ---- attention: what the YOLO11 PSA block and the YOLOv12 area attention share, from the first matmul to the second one:
 // x (B', heads, 2kd+hd, N') -> q / k / v slices of rows -> q^T k -> uniform scale -> softmax over the keys -> v @ attn^T.
 // Every shape, permutation, slice and the scale are checked and q, k and the scores must have no other reader.  How the qkv image
@@ -439,15 +480,17 @@ void match_area_attention(const NetView& g, Fusions& f) {
 }  // namespace
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
-// (before conv fusion: they claim the DFL 1x1 convolutions), PSA attention, area attention, convolution fusion, and last the
-// concat-activation rewrite, which edits the convolution records.
+// (before conv fusion: they claim the DFL 1x1 convolutions), the anchor head (it claims its plugin layer only), PSA attention, area
+// attention, convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
-    f.group_at = f.yolo_at = f.attn_at = std::vector<int>(nl, -1);
+    f.pad_cout.assign(nl, false);
+    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
+    match_yolo5_heads(g, f);
     match_psa_attention(g, f);
     match_area_attention(g, f);
     match_conv_fusion(g, f);

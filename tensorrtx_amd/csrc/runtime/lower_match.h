@@ -31,6 +31,13 @@ struct YoloHeadFuse {
     YoloLayerParams params;
 };
 
+struct Yolo5HeadFuse {
+    int plugin_layer = -1;
+    std::vector<int> head_tensor;   // network tensor per level: a detect convolution's output (3 * (5 + classes), gh, gw)
+    std::vector<int> conv_layer;    // ... and the layer that produces it
+    Yolo5LayerParams params;
+};
+
 struct AttentionFuse {
     int qkv = -1;                    // network tensor: the qkv convolution's output (B, heads*(2kd+hd), H, W)
     int out_o = -1, out_v = -1;      // network tensors: O reshaped to (B, heads*hd, H, W), and v reshaped the same way
@@ -44,7 +51,9 @@ struct Fusions {
     std::vector<FusedConv> groups;
     std::vector<YoloHeadFuse> yolo_heads;
     std::vector<AttentionFuse> attns;
-    std::vector<int> group_at, yolo_at, attn_at;
+    std::vector<Yolo5HeadFuse> yolo5_heads;
+    std::vector<int> group_at, yolo_at, attn_at, yolo5_at;
+    std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor head: its output channels round up to 16 bytes
     std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own
     std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src
 };

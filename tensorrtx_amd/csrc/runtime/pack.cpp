@@ -123,12 +123,13 @@ bool pack_weights(const Network& net, Plan* plan) {
             const LayerDef& l = net.layers[op.src_layer];
             const ConvArgs& a = op.conv;
             const int cout = a.Cout;
+            const int cout_real = op.cout_real > 0 ? op.cout_real : cout;   // (output channels rounded up: zero filter rows and biases beyond the layer's own)
             // folded per-channel scale / shift
             std::vector<float> sc(cout, 1.f), bias(std::max(a.Cout_pad, cout), 0.f);
-            for (int c = 0; c < cout && c < (int)l.w1.size(); ++c) bias[c] = l.w1[c];
+            for (int c = 0; c < cout_real && c < (int)l.w1.size(); ++c) bias[c] = l.w1[c];
             if (op.scale_layer >= 0) {
                 const LayerDef& s = net.layers[op.scale_layer];
-                for (int c = 0; c < cout; ++c) {
+                for (int c = 0; c < cout_real; ++c) {
                     const float scale = s.w1.empty() ? 1.f : (s.w1.size() == 1 ? s.w1[0] : s.w1[c]);
                     const float shift = s.w0.empty() ? 0.f : (s.w0.size() == 1 ? s.w0[0] : s.w0[c]);
                     sc[c] = scale;
@@ -137,6 +138,13 @@ bool pack_weights(const Network& net, Plan* plan) {
             }
             const TensorDef& tin = net.tensors[l.inputs[0]];
             const int cin_logical = (int)tin.dims.d[tin.dims.nb - 3];
+            std::vector<float> w0_padded;
+            const float* w0 = l.w0.data();
+            if (cout_real < cout) {
+                w0_padded = l.w0;
+                w0_padded.resize((size_t)cout * a.kh * a.kw * (cin_logical / a.groups), 0.f);
+                w0 = w0_padded.data();
+            }
             if (op.kind == OP_DECONV) {
                 op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
                 pack_deconv_weights_f32(l.w0.data(), cin_logical, cout, a.groups, a.kh, a.kw,
@@ -171,7 +179,7 @@ bool pack_weights(const Network& net, Plan* plan) {
                 const size_t kpad_bytes = (size_t)a.Kpad * 2;
                 op.w_off = reserve((size_t)a.Cout_pad * kpad_bytes);
                 std::vector<float> wscale(a.Cout_pad, 1.f);
-                conv_pack_weights_i8(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK * 2, sc.data(), a.Cout_pad, (int)kpad_bytes,
+                conv_pack_weights_i8(w0, cout, cin_logical, a.kh, a.kw, a.CinK * 2, sc.data(), a.Cout_pad, (int)kpad_bytes,
                                      reinterpret_cast<int8_t*>(blob.data() + op.w_off), wscale.data());
                 const float s_in = plan->tensors[op.in[0]].scale;
                 for (float& v : wscale) v *= s_in;
@@ -179,11 +187,11 @@ bool pack_weights(const Network& net, Plan* plan) {
                 memcpy(blob.data() + op.s_off, wscale.data(), wscale.size() * 4);
             } else if (op.igemm && a.f32) {
                 op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 4);
-                conv_pack_weights_igemm_f32(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
+                conv_pack_weights_igemm_f32(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
                                             reinterpret_cast<float*>(blob.data() + op.w_off));
             } else if (op.igemm) {
                 op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
-                pack_conv_weights_f16(l.w0.data(), cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
+                pack_conv_weights_f16(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
                                       reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
             } else if (op.dw) {
                 // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load
@@ -193,7 +201,7 @@ bool pack_weights(const Network& net, Plan* plan) {
                     for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = l.w0[(size_t)co * a.kh * a.kw + t] * sc[co];
             } else {
                 op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
-                pack_conv_weights_f32(l.w0.data(), cout, cin_logical / a.groups, a.kh, a.kw, sc.data(),
+                pack_conv_weights_f32(w0, cout, cin_logical / a.groups, a.kh, a.kw, sc.data(),
                                       reinterpret_cast<float*>(blob.data() + op.w_off));
             }
             op.b_off = reserve(bias.size() * 4);

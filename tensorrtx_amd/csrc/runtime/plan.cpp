@@ -10,8 +10,8 @@ const char* op_kind_name(int k) {
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
-                              "yolo_task_head"};
-    return (k >= 0 && k <= OP_YOLO_TASK_HEAD) ? n[k] : "?";
+                              "yolo_task_head", "yolo5_head"};
+    return (k >= 0 && k <= OP_YOLO5_HEAD) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -47,6 +47,7 @@ std::string Plan::describe_json() const {
               << ",\"ld_out\":" << a.ld_out << ",\"i8\":[" << a.in_i8 << "," << a.out_i8 << "," << a.res_i8 << "],\"nmul\":" << (op.stem ? 1 : tensors[op.in[0]].nmul) << ",\"nfix\":"
               << (op.stem ? 0 : tensors[op.in[0]].nfix);
             if (op.dw) o << ",\"dw\":true";
+            if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
@@ -55,6 +56,13 @@ std::string Plan::describe_json() const {
             o << ",\"task\":\"" << (op.i[9] == 1 ? "seg" : (op.i[9] == 2 ? "pose" : "obb")) << "\",\"classes\":" << op.i[0] << ",\"nk\":" << op.i[10]
               << ",\"branch_ld\":[";
             for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
+            o << "]";
+        }
+        if (op.kind == OP_YOLO5_HEAD) {
+            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"anchor_levels\":" << op.fv.size() / 6 << ",\"grids\":[";
+            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]";
+            o << "],\"ld\":[";
+            for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
             o << "]";
         }
         if (op.kind == OP_CONV_GROUP) {

@@ -50,6 +50,8 @@ enum OpKind : int {
                       // i[4] = 0.  With i[4] = area >= 1: YOLOv12 area attention on the same tensors (kernels/attention_mfma.hip), N / area keys per query
     OP_YOLO_TASK_HEAD,  // fused DFL + YoloLayer seg / pose / obb decode (explicit batch): `in` = NHWC heads, `extra_in` = NHWC task branches;
                         // i as OP_YOLO_HEAD with at most 4 strides in i[5..8], i[9] = 1 seg / 2 pose / 3 obb, i[10] = keypoints, f[0] = kpt_conf
+    OP_YOLO5_HEAD,      // fused anchor-based YoloLayer decode (YOLOv5) on the detect convolutions' NHWC output (plugins/yolo5_head.hip): i[0] = classes,
+                        // i[1] / i[2] = net h / w, i[3] = max_out, i[4] = levels, i[11] as OP_YOLO_HEAD; iv = (grid_w, grid_h) per level, fv = 6 anchors per level
 };
 const char* op_kind_name(int k);
 
@@ -100,6 +102,8 @@ struct POp {
     bool stem = false;         // conv_stem kernel: reads the LINEAR fp32 input directly
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
     bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
+    int cout_real = 0;         // > 0: conv.Cout is this channel count rounded up to a 16-byte multiple; the filter rows and biases beyond it are zero
+                               // and the output tensor's padding channels take the zeros (a detect convolution under OP_YOLO5_HEAD)
     // OP_CONV_GROUP: the member convolutions, each a complete OP_CONV record (its own in / out tensors, ConvArgs, weights); the group's
     // in / out are the unions, so dependencies, lanes and buffer lifetimes see one op
     std::vector<POp> group;
@@ -109,6 +113,8 @@ struct POp {
     // generic parameters
     int i[12] = {0};
     float f[4] = {0};
+    std::vector<int> iv;       // per-level tables of ops that have them (OP_YOLO5_HEAD)
+    std::vector<float> fv;
     StridedView view{};
     long off0 = 0;             // element offset applied to the strided side of a gather/scatter
     bool view_batched_in = false, view_batched_in2 = false, view_batched_out = true;

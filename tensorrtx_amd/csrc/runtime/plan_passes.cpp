@@ -62,8 +62,12 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
             const PTensor& tr = plan.tensors[op.in[1]];
             vec_out = vec_out && tr.rcoff % 8 == 0 && tr.ld % 8 == 0;
         }
-        // tiny reductions (K < 32, e.g. the DFL 1x1) stay on the direct kernel
-        ok = ok && a.kh * a.kw * cin_eff >= 32;
+        // tiny reductions (K < 32, e.g. the DFL 1x1) stay on the direct kernel - except the square 1x1 over 16 channels (YOLOv5n's first C3
+        // bottleneck, 16 -> 16 on the stride-4 map, the one such layer the builders here produce): a memory-bound layer that the
+        // two-taps-per-step form (CinK = 16; its second tap lies outside the 1x1 filter and loads zeros) streams with 16-byte accesses.
+        // Wider outputs over 16 channels (the qkv convolutions of the attention test graphs) keep the direct kernel: nothing measured
+        // says otherwise.  Not in kINT8 engines either, where such a layer stays the fp16 island it has been.
+        ok = ok && (a.kh * a.kw * cin_eff >= 32 || (!e.int8 && a.kh == 1 && a.kw == 1 && a.Cin == 16 && a.Cout == 16));
         if (ok) {
             ConvArgs t = a;
             t.scalar_out = vec_out ? 0 : 1;
@@ -708,7 +712,7 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
     for (int k = 0; k < nops; ++k) {
         const int kind = plan.ops[k].kind;
-        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD) || plan.ops[k].ws_bytes == 0) continue;
+        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD && kind != OP_YOLO5_HEAD) || plan.ops[k].ws_bytes == 0) continue;
         Storage s;
         s.kind = ST_ARENA;
         s.bytes = plan.ops[k].ws_bytes;

@@ -89,6 +89,15 @@ struct YoloLayerParams {
     float kpt_conf = 0.f;                         // keypoint confidence threshold (pose)
 };
 bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out);
+// parameters of a *built-in* anchor-based YoloLayer_TRT instance (the yolov5 field set "netinfo" + "kernels"; false for anything else):
+// lets the lowering pass replace the layout passes + plugin tail by the fused anchor head
+struct Yolo5LayerParams {
+    int classes, net_w, net_h, max_out;
+    bool seg;
+    std::vector<int> grid_w, grid_h;   // per level (YoloKernel::width / height)
+    std::vector<float> anchors;        // per level 6 floats
+};
+bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
 // true for the built-in "Mish_TRT" (plugins/builtin_plugins.cpp; yolov4/mish.{h,cu}): a pointwise activation, which the lowering pass
 // folds into the producing convolution's epilogue (ACT_MISH) or runs as an activation op in the tensor's own layout
 bool builtin_is_mish(const trtx_plugin_vtbl& v);

@@ -113,6 +113,21 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
         plan.reset(trtx_host::buildEngineYolo12Det(builder.get(), config.get(), wts_path, cfg));
         if (!plan) return TRTX_ERR_INVALID;   // the stride-16 grid is not divisible by the attention's area count
+    } else if ((m.size() == 7 || (m.size() == 8 && m[7] == '6')) && m.compare(0, 6, "yolov5") == 0) {   // yolov5n / s / m / l / x and the P6 models yolov5n6 ...
+        trtx_host::Yolov5Config cfg;
+        if (!trtx_host::yolov5_scale(m[6], &cfg)) return TRTX_ERR_INVALID;
+        cfg.p6 = m.size() == 8;
+        cfg.max_batch = geti(o, "batch", 1);
+        cfg.fp16 = geti(o, "fp16", 1) != 0;
+        cfg.input_h = geti(o, "h", 640);
+        cfg.input_w = geti(o, "w", 640);
+        cfg.num_class = geti(o, "classes", 80);
+        cfg.max_out_bbox = geti(o, "max_out", 1000);
+        cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
+        const int top = cfg.p6 ? 64 : 32;   // the largest stride: the down- and upsampled pyramid levels meet only on sizes it divides
+        if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < top || cfg.input_w < top || cfg.input_h % top || cfg.input_w % top)
+            return TRTX_ERR_INVALID;
+        plan.reset(trtx_host::buildEngineYolov5Det(builder.get(), config.get(), wts_path, cfg));
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);

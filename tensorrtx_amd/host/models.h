@@ -84,6 +84,25 @@ bool yolo12_scale(char type, Yolo12Config* cfg);
 nvinfer1::IHostMemory* buildEngineYolo12Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
                                             const std::string& wts, const Yolo12Config& cfg);
 
+// yolov5/src/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
+// setMaxBatchSize): a plan serves any batch up to max_batch.  Detection only (build_det_engine / build_det_p6_engine).
+struct Yolov5Config {
+    int input_h = 640, input_w = 640;   // kInputH / kInputW
+    int num_class = 80;                 // kNumClass
+    int max_batch = 1;                  // kBatchSize
+    int max_out_bbox = 1000;            // kMaxNumOutputBbox
+    bool fp16 = true;                   // USE_FP16
+    float gd = 0.33f, gw = 0.25f;       // 'n' scale (yolov5_det.cpp:22-41; yolov5_scale)
+    bool p6 = false;                    // the P6 models (n6 ... x6): four detect levels, strides 8 .. 64
+    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes), gh, gw) as "head0..N-1"
+};
+// the n / s / m / l / x scale: gd and gw; false for an unknown letter
+bool yolov5_scale(char type, Yolov5Config* cfg);
+// yolov5/src/model.cpp:286-373 (P5) and 375-476 (P6).  Input "data", output "prob" (1 + max_out * 38 floats).  Returns null when the
+// weight map's anchor_grid / strides do not describe one level per detect convolution.
+nvinfer1::IHostMemory* buildEngineYolov5Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                            const Yolov5Config& cfg);
+
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {
     int input_h = 800, input_w = 1067;      // INPUT_H / INPUT_W: 480x640 resized by calculateSize() (rcnn.cpp:349-366)

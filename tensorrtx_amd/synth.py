@@ -599,4 +599,118 @@ def yolov5_head_tensors(batch, classes=80, net_h=640, net_w=640, strides=(8, 16,
     return [x.reshape(batch, 3 * info, -1) for x in outs]
 
 
+YOLOV5_P6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542],
+                     [436, 615, 739, 380, 925, 792]]  # yolov5s6 P3 .. P6 (ultralytics yaml)
+YOLOV5_SCALES = {"n": (0.33, 0.25), "s": (0.33, 0.50), "m": (0.67, 0.75), "l": (1.0, 1.0), "x": (1.33, 1.25)}   # yolov5_det.cpp:22-41: gd, gw
+YOLOV5_OBJ_SCALE, YOLOV5_OBJ_BIAS = 24.0, -5.0   # objectness rows of the detect convolutions: He rows times the scale, around the bias
+YOLOV5_CLS_BIAS, YOLOV5_CLS_MARGIN = -2.0, 2.5   # class rows: every class around the bias, one favoured class per (level, anchor) above it by the margin
+
+
+def yolov5_state(scale="n", seed=0, num_class=80, p6=False):
+    """Seeded synthetic weights of YOLOv5{n,s,m,l,x} (v6 graph; p6: the n6 ... x6 models) under the reference's `.wts` key names
+    (ultralytics state_dict keys as gen_wts.py writes them, read by yolov5/src/model.cpp:99-476): OrderedDict name -> fp32 array,
+    including <detect>.anchor_grid (P5: YOLOV5_ANCHORS) and <detect>.strides.  He-scaled convolutions with near-identity BatchNorm
+    statistics (the yolov8n_state recipe).  The detect convolutions are He rows (gain 2) with biases 0.1 N(0, 1), except:
+      * the three objectness rows are scaled by YOLOV5_OBJ_SCALE around a bias of YOLOV5_OBJ_BIAS.  The features these random backbones
+        produce vary little over an image (a He row gives logits with a spread of 0.1 - 0.5), so it takes that scale for a useful share
+        of the anchors to pass the plugin's 0.1 gate (logit > -2.197): 2 - 55 % of them, by model and size (the counts measured with
+        the fp32 twin are in tests/test_gpu_yolov5.py);
+      * the class rows sit around YOLOV5_CLS_BIAS and, per (level, anchor), one favoured class (7 level + 29 anchor + 3 mod the class
+        count) lies YOLOV5_CLS_MARGIN above.  The gate of this plugin is on objectness alone, so unlike YOLOv8's the class argmax of EVERY
+        passing anchor is compared between engines; eighty near-equal logits would flip it under fp16 rounding in 1 - 2 % of them (the
+        top-two gap of 80 equal-variance logits is below twice the rounding error that often, at any gain), above the 0.5 % the fp16
+        allowance has for all causes together.
+    """
+    import math
+    from collections import OrderedDict
+
+    import torch
+    gd, gw = YOLOV5_SCALES[scale]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+
+    def W(x):
+        return int(math.ceil(x * gw / 8)) * 8
+
+    def D(x):
+        return 1 if x == 1 else max(int(round(x * gd)), 1)   # Python's round: half to even, as get_depth
+
+    def cb(name, cout, cin, k):  # Conv + BatchNorm (+ SiLU)
+        sd[name + ".conv.weight"] = (randn(cout, cin, k, k) * math.sqrt(2.0 / (cin * k * k))).float()
+        sd[name + ".bn.weight"] = (0.9 + 0.2 * rand(cout)).float()
+        sd[name + ".bn.bias"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_mean"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_var"] = (0.8 + 0.4 * rand(cout)).float()
+        sd[name + ".bn.num_batches_tracked"] = torch.zeros(1)
+
+    def c3(name, c1, c2, n):
+        c_ = int(c2 * 0.5)
+        cb(name + ".cv1", c_, c1, 1)
+        cb(name + ".cv2", c_, c1, 1)
+        cb(name + ".cv3", c2, 2 * c_, 1)
+        for i in range(n):
+            cb(f"{name}.m.{i}.cv1", c_, c_, 1)
+            cb(f"{name}.m.{i}.cv2", c_, c_, 3)
+
+    def sppf(name, c1, c2):
+        cb(name + ".cv1", c1 // 2, c1, 1)
+        cb(name + ".cv2", c2, 2 * c1, 1)
+
+    cb("model.0", W(64), 3, 6)
+    cb("model.1", W(128), W(64), 3)
+    c3("model.2", W(128), W(128), D(3))
+    cb("model.3", W(256), W(128), 3)
+    c3("model.4", W(256), W(256), D(6))
+    cb("model.5", W(512), W(256), 3)
+    c3("model.6", W(512), W(512), D(9))
+    if not p6:
+        cb("model.7", W(1024), W(512), 3)
+        c3("model.8", W(1024), W(1024), D(3))
+        sppf("model.9", W(1024), W(1024))
+        cb("model.10", W(512), W(1024), 1)
+        c3("model.13", W(1024), W(512), D(3))
+        cb("model.14", W(256), W(512), 1)
+        c3("model.17", W(512), W(256), D(3))
+        cb("model.18", W(256), W(256), 3)
+        c3("model.20", W(512), W(512), D(3))
+        cb("model.21", W(512), W(512), 3)
+        c3("model.23", W(1024), W(1024), D(3))
+        det, feats, anchors, strides = "model.24", (W(256), W(512), W(1024)), YOLOV5_ANCHORS, (8, 16, 32)
+    else:
+        cb("model.7", W(768), W(512), 3)
+        c3("model.8", W(768), W(768), D(3))
+        cb("model.9", W(1024), W(768), 3)
+        c3("model.10", W(1024), W(1024), D(3))
+        sppf("model.11", W(1024), W(1024))
+        cb("model.12", W(768), W(1024), 1)
+        c3("model.15", W(1536), W(768), D(3))
+        cb("model.16", W(512), W(768), 1)
+        c3("model.19", W(1024), W(512), D(3))
+        cb("model.20", W(256), W(512), 1)
+        c3("model.23", W(512), W(256), D(3))
+        cb("model.24", W(256), W(256), 3)
+        c3("model.26", W(512), W(512), D(3))
+        cb("model.27", W(512), W(512), 3)
+        c3("model.29", W(1024), W(768), D(3))
+        cb("model.30", W(768), W(768), 3)
+        c3("model.32", W(1536), W(1024), D(3))
+        det, feats, anchors, strides = "model.33", (W(256), W(512), W(768), W(1024)), YOLOV5_P6_ANCHORS, (8, 16, 32, 64)
+    info = 5 + num_class
+    for lv, cin in enumerate(feats):
+        w = randn(3 * info, cin, 1, 1) * math.sqrt(2.0 / cin)
+        b = 0.1 * randn(3 * info)
+        for k in range(3):
+            w[k * info + 4] *= YOLOV5_OBJ_SCALE
+            b[k * info + 4] += YOLOV5_OBJ_BIAS
+            b[k * info + 5:(k + 1) * info] += YOLOV5_CLS_BIAS
+            b[k * info + 5 + (7 * lv + 29 * k + 3) % num_class] += YOLOV5_CLS_MARGIN
+        sd[f"{det}.m.{lv}.weight"] = w.float()
+        sd[f"{det}.m.{lv}.bias"] = b.float()
+    sd[det + ".anchor_grid"] = torch.tensor(anchors, dtype=torch.float32).reshape(len(feats), 1, 3, 1, 1, 2)
+    sd[det + ".strides"] = torch.tensor(strides, dtype=torch.float32)
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
+
+
 STATE["yolov8n"] = yolov8n_state
