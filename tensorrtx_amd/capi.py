@@ -273,6 +273,14 @@ def yolo_postprocess_gpu(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "silu": 3, "leaky": 4, "tanh": 5}
 
 
+def _hw(v):
+    """an int, or an (h, w) pair -> (h, w)"""
+    if isinstance(v, (tuple, list)):
+        h, w = v
+        return int(h), int(w)
+    return int(v), int(v)
+
+
 def pack_conv_weights_f16(w_kcrs, cin_pad=None, ch_scale=None):
     """Host: KCRS fp32 numpy -> (packed uint16 [Cout_pad, Kpad], cout_pad, kpad, bn)."""
     import numpy as np
@@ -295,17 +303,18 @@ def pack_conv_weights_f16(w_kcrs, cin_pad=None, ch_scale=None):
 
 def conv2d_nhwc_f16(x, wpacked, bias, cout, kh, kw, stride, pad, act1="none", residual=None, act2="none",
                     out=None, out_ld=None):
-    """Single fused conv launch on NHWC fp16 tensors (x: [N,H,W,Cin] CUDA half)."""
+    """Single fused conv launch on NHWC fp16 tensors (x: [N,H,W,Cin] CUDA half); stride / pad: an int or an (h, w) pair."""
     import torch
     L = lib()
     N, H, W, Cin = x.shape
-    Ho = (H + 2 * pad - kh) // stride + 1
-    Wo = (W + 2 * pad - kw) // stride + 1
+    (sh, sw), (ph, pw) = _hw(stride), _hw(pad)
+    Ho = (H + 2 * ph - kh) // sh + 1
+    Wo = (W + 2 * pw - kw) // sw + 1
     if out is None:
         out = torch.empty((N, Ho, Wo, cout), dtype=torch.float16, device=x.device)
     ld_out = out_ld or out.shape[-1]
     check(L.trtx_op_conv2d_nhwc_f16(_p(x), N, H, W, Cin, x.stride(2), _p(wpacked), _p(bias), _p(out), cout, ld_out,
-                                    kh, kw, stride, stride, pad, pad, ACT[act1], _p(residual),
+                                    kh, kw, sh, sw, ph, pw, ACT[act1], _p(residual),
                                     residual.stride(2) if residual is not None else 0, ACT[act2], _stream()),
           "trtx_op_conv2d_nhwc_f16")
     return out
@@ -330,29 +339,32 @@ def pack_conv_weights_f32(w_kcrs, cin_pad=None, ch_scale=None):
 
 
 def conv2d_nhwc_f32(x, wpacked, bias, cout, kh, kw, stride, pad, act1="none", residual=None, act2="none", out=None, out_ld=None, tile=None):
-    """Single fused conv launch on NHWC fp32 tensors (x: [N,H,W,Cin] CUDA float32, Cin % 4 == 0); tile = (bn, bm, operand path, channels per k-step) or None.
+    """Single fused conv launch on NHWC fp32 tensors (x: [N,H,W,Cin] CUDA float32, Cin % 4 == 0); stride / pad: an int or an (h, w) pair; tile = (bn, bm, operand path, channels per k-step) or None.
     bias: cout_pad floats (cout rounded up to 16; pack_conv_weights_f32 returns cout_pad) - the kernel reads it in 16-byte pieces up to the padded width."""
     import torch
     L = lib()
     N, H, W, Cin = x.shape
     if bias is not None and bias.numel() < (cout + 15) // 16 * 16:
         raise ValueError(f"bias holds {bias.numel()} floats, the fp32 tile reads cout_pad = {(cout + 15) // 16 * 16}")
-    Ho = (H + 2 * pad - kh) // stride + 1
-    Wo = (W + 2 * pad - kw) // stride + 1
+    (sh, sw), (ph, pw) = _hw(stride), _hw(pad)
+    Ho = (H + 2 * ph - kh) // sh + 1
+    Wo = (W + 2 * pw - kw) // sw + 1
     if out is None:
         out = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=x.device)
     ld_out = out_ld or out.shape[-1]
     t2 = (ctypes.c_int32 * 4)(*tile) if tile is not None else None
-    check(L.trtx_op_conv2d_nhwc_f32(_p(x), N, H, W, Cin, x.stride(2), _p(wpacked), _p(bias), _p(out), cout, ld_out, kh, kw, stride, stride, pad, pad,
+    check(L.trtx_op_conv2d_nhwc_f32(_p(x), N, H, W, Cin, x.stride(2), _p(wpacked), _p(bias), _p(out), cout, ld_out, kh, kw, sh, sw, ph, pw,
                                     ACT[act1], _p(residual), residual.stride(2) if residual is not None else 0, ACT[act2], t2, _stream()),
           "trtx_op_conv2d_nhwc_f32")
     return out
 
 
 def conv2d_tactics_f32(N, H, W, Cin, Cout, k, stride, pad, residual=False, ld_in=None, ld_out=None, ld_res=None, max_out=32):
-    """The launch configurations (bn, bm, operand path, channels per k-step) of one fp32 conv layer (host only); [0] is the launcher's own choice."""
+    """The launch configurations (bn, bm, operand path, channels per k-step) of one fp32 conv layer (host only); [0] is the launcher's own choice.
+    k: an int or (kh, kw); stride / pad: an int or an (h, w) pair."""
     arr = (ctypes.c_int32 * (4 * max_out))()
-    n = lib().trtx_op_conv2d_tactics_f32(N, H, W, Cin, ld_in or Cin, Cout, ld_out or Cout, k, k, stride, stride, pad, pad, 1 if residual else 0,
+    (kh, kw), (sh, sw), (ph, pw) = _hw(k), _hw(stride), _hw(pad)
+    n = lib().trtx_op_conv2d_tactics_f32(N, H, W, Cin, ld_in or Cin, Cout, ld_out or Cout, kh, kw, sh, sw, ph, pw, 1 if residual else 0,
                                          (ld_res or Cout) if residual else 0, arr, max_out)
     return [(arr[4 * i], arr[4 * i + 1], arr[4 * i + 2], arr[4 * i + 3]) for i in range(n)]
 
@@ -369,9 +381,11 @@ def poison_lds(sync=True):
 
 
 def conv2d_tactics(N, H, W, Cin, Cout, k, stride, pad, residual=False, ld_in=None, ld_out=None, ld_res=None, max_out=32):
-    """The exchangeable launch configurations of one conv layer (host only): list of (bn, bk, bm, wsk, ws, r3); [0] is the default."""
+    """The exchangeable launch configurations of one conv layer (host only): list of (bn, bk, bm, wsk, ws, r3); [0] is the default.
+    k: an int or (kh, kw); stride / pad: an int or an (h, w) pair."""
     arr = (ctypes.c_int32 * (6 * max_out))()
-    n = lib().trtx_op_conv2d_tactics(N, H, W, Cin, ld_in or Cin, Cout, ld_out or Cout, k, k, stride, stride, pad, pad, 1 if residual else 0,
+    (kh, kw), (sh, sw), (ph, pw) = _hw(k), _hw(stride), _hw(pad)
+    n = lib().trtx_op_conv2d_tactics(N, H, W, Cin, ld_in or Cin, Cout, ld_out or Cout, kh, kw, sh, sw, ph, pw, 1 if residual else 0,
                                      (ld_res or Cout) if residual else 0, arr, max_out)
     return [tuple(arr[6 * i + j] for j in range(6)) for i in range(n)]
 
@@ -404,15 +418,18 @@ def pack_conv_weights_i8(w_kcrs, ch_scale=None):
 
 
 def conv2d_nhwc_i8(x_i8, wpacked, cscale, bias, cout, kh, kw, stride, pad, act1="none", out_scale=None, residual=None, res_scale=1.0,
-                   act2="none"):
-    """int8 MFMA conv: x_i8 CUDA int8 [N,H,W,Cin]; returns int8 (out_scale given: quantised with 1/out_scale) or fp16 NHWC."""
+                   act2="none", out=None, out_ld=None):
+    """int8 MFMA conv: x_i8 CUDA int8 [N,H,W,Cin]; returns int8 (out_scale given: quantised with 1/out_scale) or fp16 NHWC.
+    stride / pad: an int or an (h, w) pair; out / out_ld: a channel slice of a wider buffer (offset and width multiples of 8)."""
     import torch
     N, H, W, Cin = x_i8.shape
-    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
-    out = torch.empty((N, Ho, Wo, cout), dtype=torch.int8 if out_scale else torch.float16, device=x_i8.device)
+    (sh, sw), (ph, pw) = _hw(stride), _hw(pad)
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    if out is None:
+        out = torch.empty((N, Ho, Wo, cout), dtype=torch.int8 if out_scale else torch.float16, device=x_i8.device)
     res_i8 = residual is not None and residual.dtype == torch.int8
     check(lib().trtx_op_conv2d_nhwc_i8(_p(x_i8), N, H, W, Cin, x_i8.stride(2), _p(wpacked), _p(cscale), _p(bias), _p(out), 1 if out_scale else 0,
-                                       ctypes.c_float(1.0 / out_scale if out_scale else 0.0), cout, cout, kh, kw, stride, stride, pad, pad, ACT[act1],
+                                       ctypes.c_float(1.0 / out_scale if out_scale else 0.0), cout, out_ld or out.shape[-1], kh, kw, sh, sw, ph, pw, ACT[act1],
                                        _p(residual), 1 if res_i8 else 0, ctypes.c_float(res_scale), residual.stride(2) if residual is not None else 0,
                                        ACT[act2], _stream()), "trtx_op_conv2d_nhwc_i8")
     return out

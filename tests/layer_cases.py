@@ -4,6 +4,8 @@
   * `inputs`: name -> (dims, generator); dims are per sample (implicit batch) or whole (explicit batch), the data is seeded by the name;
   * `build(net, t)`: the network, through tensorrtx_amd.builder.Network, on the input tensor ids `t`; returns {output name: tensor id};
   * `ref(x)`: the same computation written directly in torch fp64 on the inputs `x` (already rounded to the engine's storage type);
+    with `by_precision` set it is `ref(x, fp16)` - the MFMA convolutions and the stem of an fp16 plan multiply fp16 WEIGHTS, a rounding
+    of a constant the reference has to apply itself rather than count as a site;
     returns {output name: Out or [Out, ...]} with, per Out, the reference, its magnitude (None = bit-exact data movement), the number
     of terms of the longest fp32 sum, an extra relative term where the function amplifies the rounding of its argument, and the fp16
     rounding sites between the rounded input and the output (counted next to each family below);
@@ -56,6 +58,9 @@ class Case:
     explicit: bool = False
     cond: object = None     # conditioning of the reference alone: callable(x) that asserts
     direct: bool = False    # every conv / deconv of the plan must be the direct kernel (igemm, dw and stem false)
+    igemm: bool = False     # the convolution under test (the plan's last; helpers come first) is on the MFMA implicit-GEMM kernel, in both plans
+    stem: bool = False      # ... is the stem kernel (it reads the fp32 network input itself), in both plans
+    by_precision: bool = False   # ref takes (x, fp16)
     fused: dict = None      # conv fields the lowered plan must show (act1, act2, residual)
 
     def __post_init__(self):
@@ -137,8 +142,10 @@ def build_plan(case, fp16):
         net.close()
 
 
-def outs_of(case, x):
-    return {k: (v if isinstance(v, list) else [v]) for k, v in case.ref(x).items()}
+def outs_of(case, x, fp16=0):
+    """the reference of the inputs `x` = ref_inputs(case, inputs, fp16)"""
+    r = case.ref(x, bool(fp16)) if case.by_precision else case.ref(x)
+    return {k: (v if isinstance(v, list) else [v]) for k, v in r.items()}
 
 
 def fp32_bound(o):
@@ -767,6 +774,81 @@ _conv("conv_g2_13x17_slice", 6, 10, 13, 17, 3, padding=1, groups=2, wrap="slice"
 _conv("conv_g2_13x17_concat", 6, 10, 13, 17, 3, padding=1, groups=2, wrap="concat")
 _conv("conv_g2_13x17_fused_b1_of3", 6, 10, 13, 17, 3, padding=1, groups=2, fusedep=True, B=1, max_batch=3)
 _conv("conv_g2_128x128_big", 6, 12, 128, 128, 3, padding=1, groups=2, B=3)
+
+
+# ---- 10b. the MFMA convolutions at engine level: implicit GEMM (kernels/igemm_tile.h; `igemm: true` in the fp16 AND the fp32 plan) and the stem
+#           kernels (conv_stem.hip / conv_stem_f32.hip; `stem: true`) on rectangular, strided and padded geometry.  An fp16 plan packs fp16 weights
+#           (the stem converts them when it loads them): the reference multiplies w.half() there.  kh * kw * Cin products + bias + shortcut; one fp16
+#           store, two with a shortcut (the MFMA epilogue rounds to fp16 in front of the add, and the sum again).  The operation-level table is
+#           tests/conv_cases.py; here the same kernels meet what only a plan produces: zero-padded channels of a freshly converted tensor, channel
+#           slices, a concat neighbour, an enqueue below max_batch, the fused epilogue chain ----------------------------------------------------------
+def _mfma(name, Cin, Cout, H, W, k, stride=1, padding=0, fusedep=False, B=2, max_batch=None, wrap="plain", stem=False):
+    kh, kw_ = (k, k) if np.isscalar(k) else k
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    w = (rng.standard_normal((Cout, Cin, kh, kw_)) / math.sqrt(kh * kw_ * Cin)).astype(np.float32)
+    b = rng.standard_normal(Cout).astype(np.float32) if fusedep or stem else None
+    conv = lambda x, ww, bb: F.conv2d(x, ww, bb, stride, padding)  # noqa: E731
+    Ho, Wo = conv(torch.zeros(1, Cin, H, W, dtype=torch.float64), torch.zeros(Cout, Cin, kh, kw_, dtype=torch.float64), None).shape[2:]
+
+    def build(net, t):
+        x = t["x"]
+        if wrap == "slice":     # channels [8, 8 + Cin) of a wider NHWC tensor: an aligned view in both plans
+            x = net.out(net.slice_channels(nhwc(net, x), 8, Cin, (Cin + 8, H, W)))
+        elif wrap not in ("fresh", "stem"):
+            x = nhwc(net, x)    # ("fresh": the conv reads the converted network input itself, Cin padded with zeros to the vector width)
+        z = select_conv(net, nhwc(net, t["z"]), 8, NEIGHBOUR) if wrap == "concat" else None   # (the helper convolution first)
+        y = net.out(net.conv(x, w, b, stride, padding))
+        if fusedep:
+            y = net.out(net.activation(y, "leaky", 0.1))
+            y = net.out(net.elementwise(y, nhwc(net, t["r"]), "sum"))
+            y = net.out(net.activation(y, "relu"))
+        elif stem:
+            y = net.out(net.activation(y, "relu"))
+        if wrap == "concat":
+            y = net.out(net.concat([z, y]))
+        return {"y": y}
+
+    def ref(x, fp16):
+        wd = torch.from_numpy(w)
+        wd = (wd.half() if fp16 else wd).double()
+        bd = None if b is None else torch.from_numpy(b).double()
+        v = x["x"][:, 8:] if wrap == "slice" else x["x"]
+        r, mag = conv(v, wd, bd), conv(v.abs(), wd.abs(), None if bd is None else bd.abs())
+        if fusedep:
+            r, mag = torch.relu(F.leaky_relu(r, 0.1) + x["r"]), mag + x["r"].abs()
+        elif stem:
+            r = torch.relu(r)
+        o = Out(r, mag, n=kh * kw_ * Cin + 2, sites=2 if fusedep else 1)
+        if wrap == "concat":
+            o.ch = slice(12, None)
+            return {"y": [Out(x["z"][:, NEIGHBOUR], ch=slice(0, 12)), o]}
+        return {"y": o}
+    inputs = {"x": ((Cin + 8 if wrap == "slice" else Cin, H, W), "n")}
+    if fusedep:
+        inputs["r"] = ((Cout, Ho, Wo), "n")
+    if wrap == "concat":
+        inputs["z"] = ((8, Ho, Wo), "n")
+    add(name=name, family="conv_mfma", inputs=inputs, build=build, ref=ref, kinds={"conv"}, absent={"ew_nhwc", "act_nhwc"}, batch=B, max_batch=max_batch,
+        igemm=not stem, stem=stem, by_precision=True,
+        fused=None if wrap == "concat" else dict(act1=4 if fusedep else (1 if stem else 0), act2=1 if fusedep else 0, residual=fusedep))
+
+
+_mfma("mfma_k1x3_c16_o16_13x17", 16, 16, 13, 17, (1, 3), padding=(0, 1))                               # two taps per k-step, three taps
+_mfma("mfma_k7x1_s1x2_c32_o24_13x17", 32, 24, 13, 17, (7, 1), stride=(1, 2), padding=(3, 0))
+_mfma("mfma_k3x5_s2x1_p0x2_c16_o40_13x17", 16, 40, 13, 17, (3, 5), stride=(2, 1), padding=(0, 2))      # 15 taps of 16 channels: the last k-step holds one
+_mfma("mfma_k5x6_c32_o16_13x17", 32, 16, 13, 17, (5, 6), padding=2)                                    # 30 taps, the limit
+_mfma("mfma_k3x3_p2_c24_o16_13x17", 24, 16, 13, 17, 3, padding=2)                                      # padding beyond k / 2, a ragged channel chunk
+_mfma("mfma_k1x1_s2_p1_c64_o32_13x17", 64, 32, 13, 17, 1, stride=2, padding=1)                         # a border without a valid tap; not a plain GEMM
+_mfma("mfma_k2x2_s2_c16_o21_13x17", 16, 21, 13, 17, 2, stride=2)                                       # Cout 21: element-wise stores
+_mfma("mfma_k3x1_c20_o16_13x17_fresh", 20, 16, 13, 17, (3, 1), padding=(1, 0), wrap="fresh")           # Cin 20 -> 24 zero-padded channels: with Cin % 8 != 0 the plan grants `igemm` only to a tensor it knows zero-padded, so the flag asserts that path
+_mfma("mfma_k1x7_p0x3_c16_o16_13x17_slice", 16, 16, 13, 17, (1, 7), padding=(0, 3), wrap="slice")      # reads a channel slice (ld_in 24)
+_mfma("mfma_k3x5_p1x2_c16_o16_13x17_concat", 16, 16, 13, 17, (3, 5), padding=(1, 2), wrap="concat")    # writes behind the 12-channel neighbour
+_mfma("mfma_k5x3_s2x1_c32_o16_13x17_b1_of3", 32, 16, 13, 17, (5, 3), stride=(2, 1), padding=(2, 1), B=1, max_batch=3)
+_mfma("mfma_k3x5_s1x2_c32_o32_13x17_fused", 32, 32, 13, 17, (3, 5), stride=(1, 2), padding=(1, 2), fusedep=True)   # bias, leaky, shortcut, relu
+_mfma("mfma_k1x3_c16_o16_1x9", 16, 16, 1, 9, (1, 3), padding=(0, 1), B=3)                              # a single row
+_mfma("stem_k3x5_s2x1_p0x2_c3_o16_13x17", 3, 16, 13, 17, (3, 5), stride=(2, 1), padding=(0, 2), wrap="stem", stem=True)
+_mfma("stem_k7x3_p0_c3_o32_13x17", 3, 32, 13, 17, (7, 3), wrap="stem", stem=True)
+_mfma("mfma_k3x5_p1x2_c16_o16_128x128_big", 16, 16, 128, 128, (3, 5), padding=(1, 2), B=3)             # 384 row tiles
 
 
 # ---- 11. direct transposed convolution: fp32 weights (pack_deconv_weights_f32), at most kh * kw * Cin / groups terms + bias, one fp16 store --------

@@ -93,6 +93,10 @@ def test_plan_lowers_to_the_intended_kernels(case, fp16, plans):
     convs = [o for o in desc["ops"] if o["kind"] in ("conv", "deconv")]
     if case.direct:
         assert convs and not any(o["igemm"] or o["stem"] or o.get("dw") for o in convs)
+    if case.igemm:
+        assert convs and convs[-1]["igemm"] and not convs[-1]["stem"], convs[-1]
+    if case.stem:
+        assert convs and convs[-1]["stem"], convs[-1]
     if case.fused:
         (o,) = convs
         assert {k: o[k] for k in case.fused} == case.fused   # bias, activation, shortcut and second activation live in the one conv op
@@ -131,13 +135,13 @@ def test_interpreter_matches_the_fp64_reference(case, plans):
         x = lc.ref_inputs(case, inputs, fp16)
         if case.cond:
             case.cond(x)
-        for name, outs in lc.outs_of(case, x).items():
+        for name, outs in lc.outs_of(case, x, fp16).items():
             for o in outs:
                 assert torch.isfinite(o.ref).all() and o.ref.abs().max() <= lc.F16_MAX, name   # every result fits fp16
                 if o.mag is not None:
                     assert (o.mag >= o.ref.abs() * (1 - 1e-12)).all(), name   # the magnitude bounds the value it belongs to
     got = gi.run(engine.describe_plan(plan), plan, inputs, batch=case.batch)
-    for name, outs in lc.outs_of(case, lc.ref_inputs(case, inputs, 0)).items():
+    for name, outs in lc.outs_of(case, lc.ref_inputs(case, inputs, 0), 0).items():
         g = got[name].double()
         for o in outs:
             part = g if o.ch is None else g[:, o.ch]
