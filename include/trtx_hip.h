@@ -158,6 +158,26 @@ int32_t trtx_yolo_postprocess_gpu_obb(const float* decode_out, int batch, int ma
  * class-wise greedy suppression in conf-descending order.  Same outputs / workspace as trtx_yolo_nms; records are 38 floats. */
 int32_t trtx_yolov5_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
                         int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Mask assembly of the seg programs: the coefficient x prototype loop of the host process_mask with its get_downscale_rect
+ * (yolov5/src/postprocess.cpp:94-120; yolov8/yolov8_seg.cpp:17-53 and yolo11/yolo11_seg.cpp:17-53, one body), on the engine's
+ * device buffers.  cv::resize, scale_mask and drawing stay with the caller.
+ *   decode_out  device fp32 [batch][1 + max_out * det_floats], the engine's decode binding; det_floats 38 (yolov5) or 90 (yolov8 /
+ *               yolo11): bbox is floats 0-3 and the 32 coefficients floats 6-37 of a record in both
+ *   keep_idx    device [batch][max_out], keep_cnt device [batch]: the outputs of trtx_yolov5_nms / trtx_yolo_nms
+ *   proto       device fp32 [batch][32][mask_h][mask_w], the engine's proto binding; net_w / mask_w must be an integer equal to
+ *               net_h / mask_h and to the reference's 4, anything else is TRTX_ERR_INVALID
+ *   box_format  0: centre boxes, Rect(round(left), round(top), round(right - left), round(bottom - top)) (yolov5);
+ *               1: corner boxes clamped to [0, net], the same with int() truncation (yolov8 / yolo11); fp32 as written there
+ *   masks       device fp32 [batch][max_keep][mask_h][mask_w]: slot d of image b is kept detection d in NMS emission order for
+ *               d < min(keep_cnt[b], max_keep), 1 / (1 + expf(-sum_j coef[j] * proto[j][y][x])) (j ascending, fp32) inside the rect
+ *               and 0.0f elsewhere; later slots are not written.
+ * Unlike the reference (cv::Mat::at, unchecked) the rect is intersected with the plane, and a rect with a non-finite edge is empty.
+ * One launch, no workspace, no synchronisation.
+ */
+int32_t trtx_seg_masks(const float* decode_out, int det_floats, int box_format, const int32_t* keep_idx, const int32_t* keep_cnt, int batch,
+                       int max_out, int max_keep, const float* proto, int mask_h, int mask_w, int net_h, int net_w, float* masks,
+                       trtx_stream_t stream);
 
 /*
  * Letterbox pre-processing (the reference's cuda_preprocess / cuda_batch_preprocess, yolov8/src/preprocess.cu:7-127):

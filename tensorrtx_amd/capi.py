@@ -260,6 +260,28 @@ def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
     return keep_idx, keep_cnt, keep_det
 
 
+def seg_masks(decode_out, keep_idx, keep_cnt, proto, net_h, net_w, max_keep, box_format=0, out=None):
+    """process_mask's coefficient loop on the GPU (yolov5/src/postprocess.cpp:94-120, yolov8/yolov8_seg.cpp:17-53).
+    decode_out [B, 1 + max_out * 38 | 90] (the record length follows from keep_idx's max_out), keep_idx [B, max_out] and keep_cnt [B]
+    as yolov5_nms / yolo_nms return them, proto [B, 32, mask_h, mask_w].  box_format 0: yolov5's centre boxes, 1: yolov8 / yolo11's
+    corner boxes.  Returns masks [B, max_keep, mask_h, mask_w] (`out`, or a new zero-filled tensor): slot d of an image is its kept
+    detection d for d < min(keep_cnt, max_keep); later slots are not written."""
+    import torch
+    B, max_out = keep_idx.shape
+    assert decode_out.shape[0] == B and (decode_out.shape[1] - 1) % max_out == 0
+    det_floats = (decode_out.shape[1] - 1) // max_out
+    assert proto.dim() == 4 and proto.shape[0] == B and proto.shape[1] == 32
+    mask_h, mask_w = int(proto.shape[2]), int(proto.shape[3])
+    for t, dt in ((decode_out, torch.float32), (keep_idx, torch.int32), (keep_cnt, torch.int32), (proto, torch.float32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    if out is None:
+        out = torch.zeros((B, max(max_keep, 0), mask_h, mask_w), dtype=torch.float32, device=proto.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= B * max(max_keep, 0) * mask_h * mask_w
+    check(lib().trtx_seg_masks(_p(decode_out), det_floats, box_format, _p(keep_idx), _p(keep_cnt), B, max_out, max_keep, _p(proto), mask_h,
+                               mask_w, net_h, net_w, _p(out), _stream()), "trtx_seg_masks")
+    return out
+
+
 def yolo_postprocess_gpu(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
     """The reference's GPU post-processing mode "g" (yolov8/src/postprocess.cu:42-111): [B, 1 + max_out*7]."""
     import torch

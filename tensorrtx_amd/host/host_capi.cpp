@@ -121,13 +121,20 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         cfg.fp16 = geti(o, "fp16", 1) != 0;
         cfg.input_h = geti(o, "h", 640);
         cfg.input_w = geti(o, "w", 640);
-        cfg.num_class = geti(o, "classes", 80);
+        cfg.task = geti(o, "task", 0);  // 0 det, 1 seg, 4 cls (yolo11's numbers); P5 only, and no INT8, like the det builder
+        if (!trtx_host::yolov5_task_valid(cfg.task, cfg.p6)) return TRTX_ERR_INVALID;
+        if (cfg.task != 0 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;
+        if (cfg.task == 4) {   // kClsInputH / kClsInputW / kClsNumClass (yolov5/src/config.h)
+            cfg.input_h = geti(o, "h", 224);
+            cfg.input_w = geti(o, "w", 224);
+        }
+        cfg.num_class = geti(o, "classes", cfg.task == 4 ? 1000 : 80);
         cfg.max_out_bbox = geti(o, "max_out", 1000);
         cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
         const int top = cfg.p6 ? 64 : 32;   // the largest stride: the down- and upsampled pyramid levels meet only on sizes it divides
         if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < top || cfg.input_w < top || cfg.input_h % top || cfg.input_w % top)
             return TRTX_ERR_INVALID;
-        plan.reset(trtx_host::buildEngineYolov5Det(builder.get(), config.get(), wts_path, cfg));
+        plan.reset(trtx_host::buildEngineYolov5(builder.get(), config.get(), wts_path, cfg));
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);

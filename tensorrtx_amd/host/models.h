@@ -85,7 +85,7 @@ nvinfer1::IHostMemory* buildEngineYolo12Det(nvinfer1::IBuilder* builder, nvinfer
                                             const std::string& wts, const Yolo12Config& cfg);
 
 // yolov5/src/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
-// setMaxBatchSize): a plan serves any batch up to max_batch.  Detection only (build_det_engine / build_det_p6_engine).
+// setMaxBatchSize): a plan serves any batch up to max_batch.  Detection, segmentation and classification: `task`.
 struct Yolov5Config {
     int input_h = 640, input_w = 640;   // kInputH / kInputW
     int num_class = 80;                 // kNumClass
@@ -94,14 +94,27 @@ struct Yolov5Config {
     bool fp16 = true;                   // USE_FP16
     float gd = 0.33f, gw = 0.25f;       // 'n' scale (yolov5_det.cpp:22-41; yolov5_scale)
     bool p6 = false;                    // the P6 models (n6 ... x6): four detect levels, strides 8 .. 64
-    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes), gh, gw) as "head0..N-1"
+    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes (+ 32)), gh, gw) as "head0..N-1"
+    // 0 det (build_det_engine / build_det_p6_engine), 1 seg (build_seg_engine, model.cpp:539-628: + 32 mask coefficients per anchor, the
+    // plugin's is_segmentation flag and the "proto" output), 4 cls (build_cls_engine, :479-537: logits; num_class is kClsNumClass, input_h /
+    // input_w kClsInputH / kClsInputW).  The numbers are Yolo11Config's.  P5 only: the reference has no P6 seg / cls builder.
+    int task = 0;
 };
 // the n / s / m / l / x scale: gd and gw; false for an unknown letter
 bool yolov5_scale(char type, Yolov5Config* cfg);
-// yolov5/src/model.cpp:286-373 (P5) and 375-476 (P6).  Input "data", output "prob" (1 + max_out * 38 floats).  Returns null when the
-// weight map's anchor_grid / strides do not describe one level per detect convolution.
-nvinfer1::IHostMemory* buildEngineYolov5Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
-                                            const Yolov5Config& cfg);
+// what the builder accepts: task 0 on any model, 1 and 4 on the P5 models (the one statement of that rule: trtx_host_build answers
+// TRTX_ERR_INVALID where it is false)
+inline bool yolov5_task_valid(int task, bool p6) { return task == 0 || ((task == 1 || task == 4) && !p6); }
+// yolov5/src/model.cpp:286-373 (P5), 375-476 (P6), 539-628 (seg) and 479-537 (cls).  Input "data", output "prob" (det / seg:
+// 1 + max_out * 38 floats; cls: num_class logits), seg also "proto" (32, H / 4, W / 4).  Returns null where yolov5_task_valid is false
+// and when the weight map's anchor_grid / strides do not describe one level per detect convolution.
+nvinfer1::IHostMemory* buildEngineYolov5(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                         const Yolov5Config& cfg);
+// the name the builder had while it built detection only
+inline nvinfer1::IHostMemory* buildEngineYolov5Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                                   const Yolov5Config& cfg) {
+    return buildEngineYolov5(builder, config, wts, cfg);
+}
 
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {

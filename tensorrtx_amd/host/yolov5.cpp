@@ -1,9 +1,10 @@
-// YOLOv5 detection (the v6 / v7 graphs: 6x6 stem, C3, SPPF; P5 and P6) through the network-definition API, implicit batch like the
-// reference.  Mirrors the reference blocks and builders:
-//   convBlock / bottleneck / C3 / SPPF / getAnchors / addYoLoLayer     yolov5/src/model.cpp:99-217, 234-284
-//   get_width / get_depth / build_det_engine / build_det_p6_engine    yolov5/src/model.cpp:53-64, 286-476
-// Graph, weight keys ("model.<n>...") and layer order are those of the reference.  Not built: build_cls_engine, build_seg_engine and
-// Proto, the v1 - v5 era blocks (focus, bottleneckCSP, SPP), INT8.
+// YOLOv5 detection, segmentation and classification (the v6 / v7 graphs: 6x6 stem, C3, SPPF; P5, and P6 for detection) through the
+// network-definition API, implicit batch like the reference.  Mirrors the reference blocks and builders:
+//   convBlock / bottleneck / C3 / SPPF / Proto / getAnchors / addYoLoLayer   yolov5/src/model.cpp:99-232, 234-284
+//   get_width / get_depth / build_det_engine / build_det_p6_engine          yolov5/src/model.cpp:53-64, 286-476
+//   build_cls_engine / build_seg_engine                                     yolov5/src/model.cpp:479-537, 539-628
+// Graph, weight keys ("model.<n>...") and layer order are those of the reference.  Not built: P6 seg / cls (the reference has none),
+// the v1 - v5 era blocks (focus, bottleneckCSP, SPP), INT8.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -77,8 +78,9 @@ ITensor* upcat(Ctx& c, ITensor& in, ITensor* lateral) {
     return cat2(c, r->getOutput(0), lateral);
 }
 
-ITensor* detect(Ctx& c, ITensor& in, int nc, const std::string& lname) {   // the biased 1x1 detect convolutions (model.cpp:331)
-    auto* det = c.net->addConvolutionNd(in, kNumAnchor * (nc + 5), DimsHW{1, 1}, need(c.wm, lname + ".weight"), need(c.wm, lname + ".bias"));
+// the biased 1x1 detect convolutions (model.cpp:331; seg, model.cpp:582: 32 mask coefficients more per anchor)
+ITensor* detect(Ctx& c, ITensor& in, int info, const std::string& lname) {
+    auto* det = c.net->addConvolutionNd(in, kNumAnchor * info, DimsHW{1, 1}, need(c.wm, lname + ".weight"), need(c.wm, lname + ".bias"));
     assert(det);
     return det->getOutput(0);
 }
@@ -94,7 +96,7 @@ IPluginV2Layer* addYoLoLayer(Ctx& c, const std::string& lname, const std::vector
     const Weights& st = need(c.wm, lname + ".strides");
     const size_t levels = (size_t)ag.count / (kNumAnchor * 2);
     if (levels != dets.size() || (size_t)st.count < levels) return nullptr;
-    int netinfo[5] = {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox, 0};
+    int netinfo[5] = {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox, cfg.task == 1};   // [4]: is_segmentation
     std::vector<YoloKernel> kernels(levels);
     for (size_t i = 0; i < levels; ++i) {
         const int scale = (int)static_cast<const float*>(st.values)[i];
@@ -114,6 +116,57 @@ IPluginV2Layer* addYoLoLayer(Ctx& c, const std::string& lname, const std::vector
     return layer;
 }
 
+// Proto (model.cpp:219-232): 3x3 convBlock, nearest resize by the scales {1, 2, 2}, 3x3 convBlock, 1x1 convBlock to c2 channels
+ITensor* Proto(Ctx& c, ITensor& in, int c_, int c2, const std::string& lname) {
+    ITensor* cv1 = convBlock(c, in, c_, 3, 1, lname + ".cv1");
+    auto* up = c.net->addResize(*cv1);
+    assert(up);
+    up->setResizeMode(ResizeMode::kNEAREST);
+    const float scales[] = {1, 2, 2};
+    up->setScales(scales, 3);
+    ITensor* cv2 = convBlock(c, *up->getOutput(0), c_, 3, 1, lname + ".cv2");
+    return convBlock(c, *cv2, c2, 1, 1, lname + ".cv3");
+}
+
+// build_cls_engine (model.cpp:479-537): the backbone to model.8, convBlock to 1280 channels, average pool over the whole map, fully
+// connected layer.  The reference pools DimsHW{k, k} with k = kClsInputH / 32, the square case of (h / 32, w / 32).
+IHostMemory* buildCls(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov5Config& cfg) {
+    WeightMap wm = loadWeights(wts);
+    INetworkDefinition* net = builder->createNetworkV2(0U);
+    IHostMemory* plan = nullptr;
+    {
+        Ctx c{net, wm, {}};
+        auto W = [&](int x) { return get_width(x, cfg.gw); };
+        auto D = [&](int x) { return get_depth(x, cfg.gd); };
+        ITensor* data = net->addInput("data", DataType::kFLOAT, Dims3{3, cfg.input_h, cfg.input_w});
+        assert(data);
+        ITensor* x = convBlock(c, *data, W(64), 6, 2, "model.0");
+        x = convBlock(c, *x, W(128), 3, 2, "model.1");
+        x = C3(c, *x, W(128), D(3), true, "model.2");
+        x = convBlock(c, *x, W(256), 3, 2, "model.3");
+        x = C3(c, *x, W(256), D(6), true, "model.4");
+        x = convBlock(c, *x, W(512), 3, 2, "model.5");
+        x = C3(c, *x, W(512), D(9), true, "model.6");
+        x = convBlock(c, *x, W(1024), 3, 2, "model.7");
+        x = C3(c, *x, W(1024), D(3), true, "model.8");
+        ITensor* conv_class = convBlock(c, *x, 1280, 1, 1, "model.9.conv");
+        auto* pool = net->addPoolingNd(*conv_class, PoolingType::kAVERAGE, DimsHW{cfg.input_h / 32, cfg.input_w / 32});
+        assert(pool);
+        auto* fc = net->addFullyConnected(*pool->getOutput(0), cfg.num_class, need(wm, "model.9.linear.weight"), need(wm, "model.9.linear.bias"));
+        assert(fc);
+        fc->getOutput(0)->setName("prob");
+        net->markOutput(*fc->getOutput(0));
+
+        builder->setMaxBatchSize(cfg.max_batch);
+        config->setMaxWorkspaceSize(16 * (1 << 20));
+        if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
+        plan = builder->buildSerializedNetwork(*net, *config);
+    }
+    delete net;
+    freeWeights(wm);
+    return plan;
+}
+
 }  // namespace
 
 bool yolov5_scale(char type, Yolov5Config* cfg) {  // yolov5_det.cpp:22-41
@@ -128,14 +181,16 @@ bool yolov5_scale(char type, Yolov5Config* cfg) {  // yolov5_det.cpp:22-41
     return true;
 }
 
-IHostMemory* buildEngineYolov5Det(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov5Config& cfg) {
+IHostMemory* buildEngineYolov5(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov5Config& cfg) {
+    if (!yolov5_task_valid(cfg.task, cfg.p6)) return nullptr;
+    if (cfg.task == 4) return buildCls(builder, config, wts, cfg);
     WeightMap wm = loadWeights(wts);
     INetworkDefinition* net = builder->createNetworkV2(0U);
     IHostMemory* plan = nullptr;
     {
         Ctx c{net, wm, {}};
         const float gd = cfg.gd;
-        const int nc = cfg.num_class;
+        const int nc = cfg.num_class + 5 + (cfg.task == 1 ? 32 : 0);   // values per anchor of a detect convolution
         auto W = [&](int x) { return get_width(x, cfg.gw); };
         auto D = [&](int x) { return get_depth(x, gd); };
 
@@ -143,6 +198,7 @@ IHostMemory* buildEngineYolov5Det(IBuilder* builder, IBuilderConfig* config, con
         assert(data);
         std::vector<ITensor*> dets;
         std::string detect_name;
+        ITensor* proto_in = nullptr;   // seg: Proto reads model.17's output
         // ---- backbone, the part P5 and P6 share (model.cpp:295-302, 385-391): the 6x6 stride-2 stem with padding 2, then C3 stages
         ITensor* x = convBlock(c, *data, W(64), 6, 2, "model.0");
         x = convBlock(c, *x, W(128), 3, 2, "model.1");
@@ -161,6 +217,7 @@ IHostMemory* buildEngineYolov5Det(IBuilder* builder, IBuilderConfig* config, con
             ITensor* c14 = convBlock(c, *c13, W(256), 1, 1, "model.14");
             ITensor* c17 = C3(c, *upcat(c, *c14, c4), W(256), D(3), false, "model.17");
             dets.push_back(detect(c, *c17, nc, "model.24.m.0"));
+            proto_in = c17;
             ITensor* c18 = convBlock(c, *c17, W(256), 3, 2, "model.18");
             ITensor* c20 = C3(c, *cat2(c, c18, c14), W(512), D(3), false, "model.20");
             dets.push_back(detect(c, *c20, nc, "model.24.m.1"));
@@ -200,6 +257,11 @@ IHostMemory* buildEngineYolov5Det(IBuilder* builder, IBuilderConfig* config, con
         if (yolo) {
             yolo->getOutput(0)->setName("prob");
             net->markOutput(*yolo->getOutput(0));
+            if (cfg.task == 1) {   // model.cpp:598-600: after the plugin, so the bindings are data, prob, proto
+                ITensor* proto = Proto(c, *proto_in, W(256), 32, detect_name + ".proto");
+                proto->setName("proto");
+                net->markOutput(*proto);
+            }
 
             builder->setMaxBatchSize(cfg.max_batch);
             config->setMaxWorkspaceSize(16 * (1 << 20));

@@ -606,7 +606,11 @@ YOLOV5_OBJ_SCALE, YOLOV5_OBJ_BIAS = 24.0, -5.0   # objectness rows of the detect
 YOLOV5_CLS_BIAS, YOLOV5_CLS_MARGIN = -2.0, 2.5   # class rows: every class around the bias, one favoured class per (level, anchor) above it by the margin
 
 
-def yolov5_state(scale="n", seed=0, num_class=80, p6=False):
+YOLOV5_COEF_SCALE = 4.0     # seg: the 32 mask-coefficient rows per anchor are He rows (gain 2) times this
+YOLOV5_PROTO_SCALE = 8.0    # seg: the rows of Proto's last convolution (model.24.proto.cv3) are He rows (gain 2) times this
+
+
+def yolov5_state(scale="n", seed=0, num_class=80, p6=False, task=0):
     """Seeded synthetic weights of YOLOv5{n,s,m,l,x} (v6 graph; p6: the n6 ... x6 models) under the reference's `.wts` key names
     (ultralytics state_dict keys as gen_wts.py writes them, read by yolov5/src/model.cpp:99-476): OrderedDict name -> fp32 array,
     including <detect>.anchor_grid (P5: YOLOV5_ANCHORS) and <detect>.strides.  He-scaled convolutions with near-identity BatchNorm
@@ -620,6 +624,20 @@ def yolov5_state(scale="n", seed=0, num_class=80, p6=False):
         passing anchor is compared between engines; eighty near-equal logits would flip it under fp16 rounding in 1 - 2 % of them (the
         top-two gap of 80 equal-variance logits is below twice the rounding error that often, at any gain), above the 0.5 % the fp16
         allowance has for all causes together.
+
+    task: 0 det, 1 seg, 4 cls (P5 only).  With task = 0 the dict is what it was before the keyword existed, tensor for tensor and in
+    draw order.  The task tensors are drawn after every tensor the det model shares with them:
+      * seg (yolov5/src/model.cpp:539-628): the detect rows are drawn with 5 + classes + 32 values per anchor, objectness and class rows
+        by the recipe above.  The 32 coefficient rows per anchor are He rows times YOLOV5_COEF_SCALE, and Proto (model.24.proto.cv1 /
+        cv2 / cv3, drawn last) ends in a convolution of He rows times YOLOV5_PROTO_SCALE.  Plain He rows give mask logits
+        e = sum_j coef_j * proto_j that are flat (std 0.13 on yolov5n, 0.014 on yolov5s: sigmoid within 0.41 - 0.59), for the reason the
+        objectness rows are scaled; much larger scales saturate them (4 x 16: 43 % of yolov5n's logits beyond +-8).  Measured with the
+        fp64 twin (weight seed 0 unless stated) on synth.images(2, S, S, seed=12), over the candidates that pass the 0.1 gate and every pixel of the plane:
+        yolov5n, 160^2 (507 candidates): e mean 0.02, std 3.8, max |e| 10.9, 0.2 % beyond +-8; yolov5s, 128^2, at weight seed 1 (689
+        candidates; seed 0 passes a single anchor at that size, over which the spread is 0.43): mean -1.7, std 0.94, max |e| 7.7
+        (sigmoid 0.0005 - 0.94); seeds 2 - 8 of yolov5s: std 0.46 - 2.9, max |e| 2.4 - 13.2, at most 0.7 % beyond +-8
+      * cls (model.cpp:479-537): the backbone to model.8 as det, then model.9.conv (to 1280 channels) and model.9.linear
+        (N(0, 1 / 1280) rows, biases 0.1 N(0, 1)); num_class is the classifier's class count (kClsNumClass is 1000).
     """
     import math
     from collections import OrderedDict
@@ -665,6 +683,14 @@ def yolov5_state(scale="n", seed=0, num_class=80, p6=False):
     c3("model.4", W(256), W(256), D(6))
     cb("model.5", W(512), W(256), 3)
     c3("model.6", W(512), W(512), D(9))
+    assert task in (0, 1, 4) and not (task and p6), "yolov5 tasks: 0 det, 1 seg, 4 cls; P6 is det only"
+    if task == 4:
+        cb("model.7", W(1024), W(512), 3)
+        c3("model.8", W(1024), W(1024), D(3))
+        cb("model.9.conv", 1280, W(1024), 1)   # Classify.conv is a Conv module: model.9.conv.conv.weight, model.9.conv.bn.*
+        sd["model.9.linear.weight"] = (randn(num_class, 1280) * math.sqrt(1.0 / 1280)).float()
+        sd["model.9.linear.bias"] = (0.1 * randn(num_class)).float()
+        return OrderedDict((k, v.numpy()) for k, v in sd.items())
     if not p6:
         cb("model.7", W(1024), W(512), 3)
         c3("model.8", W(1024), W(1024), D(3))
@@ -697,19 +723,26 @@ def yolov5_state(scale="n", seed=0, num_class=80, p6=False):
         cb("model.30", W(768), W(768), 3)
         c3("model.32", W(1536), W(1024), D(3))
         det, feats, anchors, strides = "model.33", (W(256), W(512), W(768), W(1024)), YOLOV5_P6_ANCHORS, (8, 16, 32, 64)
-    info = 5 + num_class
+    info = 5 + num_class + (32 if task == 1 else 0)
     for lv, cin in enumerate(feats):
         w = randn(3 * info, cin, 1, 1) * math.sqrt(2.0 / cin)
         b = 0.1 * randn(3 * info)
         for k in range(3):
             w[k * info + 4] *= YOLOV5_OBJ_SCALE
             b[k * info + 4] += YOLOV5_OBJ_BIAS
-            b[k * info + 5:(k + 1) * info] += YOLOV5_CLS_BIAS
+            b[k * info + 5:k * info + 5 + num_class] += YOLOV5_CLS_BIAS
             b[k * info + 5 + (7 * lv + 29 * k + 3) % num_class] += YOLOV5_CLS_MARGIN
+            if task == 1:
+                w[k * info + 5 + num_class:(k + 1) * info] *= YOLOV5_COEF_SCALE
         sd[f"{det}.m.{lv}.weight"] = w.float()
         sd[f"{det}.m.{lv}.bias"] = b.float()
     sd[det + ".anchor_grid"] = torch.tensor(anchors, dtype=torch.float32).reshape(len(feats), 1, 3, 1, 1, 2)
     sd[det + ".strides"] = torch.tensor(strides, dtype=torch.float32)
+    if task == 1:   # Proto (model.cpp:219-232): 3x3, nearest x2, 3x3, 1x1 to 32
+        cb(det + ".proto.cv1", W(256), W(256), 3)
+        cb(det + ".proto.cv2", W(256), W(256), 3)
+        cb(det + ".proto.cv3", 32, W(256), 1)
+        sd[det + ".proto.cv3.conv.weight"] *= YOLOV5_PROTO_SCALE
     return OrderedDict((k, v.numpy()) for k, v in sd.items())
 
 
