@@ -333,6 +333,16 @@ int32_t trtx_conv_pack_weights_i8(const float* w_kcrs, int cout, int cin, int kh
 int32_t trtx_op_conv2d_nhwc_i8(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* cscale, const float* bias, void* out,
                                int out_is_i8, float out_inv_scale, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw, int act1,
                                const void* residual, int res_is_i8, float res_scale, int ld_res, int act2, trtx_stream_t stream);
+/* Grouped convolution on the matrix pipe (tests / tools): 2 <= groups <= 8, Cin / groups and Cout / groups multiples of 16 up to 64, Cout <= 128,
+ * k = 1 with pad 0 or k = 3 with pad 1, stride 1; NHWC fp16 in / out / residual with channel strides that are multiples of 8 and 16-byte aligned
+ * pointers (TRTX_ERR_UNSUPPORTED / TRTX_ERR_INVALID otherwise).  The packed filter is fp16 [Cout][kpad], k = tap * Cin_g + c, kpad = K rounded up to
+ * 32 (packed == NULL: only *kpad_out); bias: Cout floats.  This is the layer the reference hands to cuDNN through
+ * addConvolutionNd + setNbGroups (yolov9/src/block.cpp:355-366, DetectBbox_Conv). */
+int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale, uint16_t* packed,
+                                           int32_t* kpad_out);
+int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out,
+                                        int Cout, int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2,
+                                        trtx_stream_t stream);
 int32_t trtx_op_poison_lds(void* device_word, trtx_stream_t stream); /* test support: NaN patterns into every CU's LDS */
 int32_t trtx_op_nchw_f32_to_nhwc_f16(const float* in, void* out, int N, int C, int H, int W, int Cpad, int ld_out,
                                      trtx_stream_t stream);

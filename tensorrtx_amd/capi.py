@@ -342,6 +342,37 @@ def conv2d_nhwc_f16(x, wpacked, bias, cout, kh, kw, stride, pad, act1="none", re
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- grouped conv on the matrix pipe (tests / tools)
+def pack_conv_weights_grouped_f16(w_kcrs, ch_scale=None):
+    """Host: KCRS fp32 numpy [Cout, Cin / groups, k, k] -> packed uint16 [Cout, Kpad] for conv2d_grouped_nhwc_f16."""
+    import numpy as np
+    L = lib()
+    w = np.ascontiguousarray(w_kcrs, dtype=np.float32)
+    cout, cin_g, kh, kw = w.shape
+    kp = ctypes.c_int32()
+    check(L.trtx_conv_pack_weights_grouped_f16(w.ctypes.data_as(ctypes.c_void_p), cout, cin_g, kh, kw, None, None, ctypes.byref(kp)),
+          "trtx_conv_pack_weights_grouped_f16 (dims)")
+    packed = np.zeros((cout, kp.value), dtype=np.uint16)
+    sc = None if ch_scale is None else np.ascontiguousarray(ch_scale, dtype=np.float32)
+    check(L.trtx_conv_pack_weights_grouped_f16(w.ctypes.data_as(ctypes.c_void_p), cout, cin_g, kh, kw,
+                                               sc.ctypes.data_as(ctypes.c_void_p) if sc is not None else None,
+                                               packed.ctypes.data_as(ctypes.c_void_p), ctypes.byref(kp)), "trtx_conv_pack_weights_grouped_f16")
+    return packed
+
+
+def conv2d_grouped_nhwc_f16(x, wpacked, bias, cout, groups, k, pad, act1="none", residual=None, act2="none", out=None, out_ld=None):
+    """Single grouped-convolution launch (kernels/conv_grouped.hip) on NHWC fp16 tensors; x: [N,H,W,Cin] CUDA half or a channel slice of
+    a wider tensor (its pixel stride is taken from x.stride(2)); out / out_ld: a channel slice of a wider buffer."""
+    import torch
+    N, H, W, Cin = x.shape
+    if out is None:
+        out = torch.empty((N, H + 2 * pad - k + 1, W + 2 * pad - k + 1, cout), dtype=torch.float16, device=x.device)
+    check(lib().trtx_op_conv2d_grouped_nhwc_f16(_p(x), N, H, W, Cin, x.stride(2), _p(wpacked), _p(bias), _p(out), cout, out_ld or out.shape[-1], groups, k,
+                                                pad, ACT[act1], _p(residual), residual.stride(2) if residual is not None else 0, ACT[act2], _stream()),
+          "trtx_op_conv2d_grouped_nhwc_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- fp32 engines: conv on the fp32 MFMA (tests / tools)
 def pack_conv_weights_f32(w_kcrs, cin_pad=None, ch_scale=None):
     """Host: KCRS fp32 numpy -> (packed float32 [Cout_pad, Kpad], cout_pad, kpad, cink) for conv2d_nhwc_f32."""

@@ -162,6 +162,12 @@ bool area_attention_supported(int kd, int hd);
 int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd,
                            int hd, float scale, hipStream_t s);
 int32_t conv_dw(const ConvArgs& a, int dtype, hipStream_t s);
+// grouped convolution on the matrix pipe (conv_grouped.hip): fp16, 2 <= groups <= 8, Cin / groups and Cout / groups multiples of 16 up to 64,
+// Cout <= 128, 1x1 pad 0 or 3x3 pad 1, stride 1, no dilation, channel strides multiples of 8.  Weights fp16 [group][Cout_g][Kpad],
+// k = tap * Cin_g + c, Kpad = conv_grouped_kpad() = K rounded up to 32 (ConvArgs::Kpad must say so); bias fp32 [Cout]
+bool conv_grouped_supported(const ConvArgs& a);
+int conv_grouped_kpad(const ConvArgs& a);
+int32_t conv_grouped(const ConvArgs& a, hipStream_t s);
 // generic transposed convolution, fp32 weights laid out [Cin][kh][kw][Cout/groups]
 int32_t deconv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 

@@ -126,6 +126,38 @@ extern "C" int32_t trtx_op_conv2d_nhwc_f16(const void* in, int N, int H, int W, 
     return st;
 }
 
+// --- grouped convolution on the matrix pipe (kernels/conv_grouped.hip), test / tool entry points
+extern "C" int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale, uint16_t* packed,
+                                                      int32_t* kpad_out) {
+    if (!w_kcrs || cout < 1 || cin_g < 1 || kh < 1 || kw < 1) return TRTX_ERR_INVALID;
+    const int kpad = (kh * kw * cin_g + 31) / 32 * 32;
+    if (kpad_out) *kpad_out = kpad;
+    if (packed) pack_conv_weights_grouped_f16(w_kcrs, cout, cin_g, kh, kw, kpad, ch_scale, packed);
+    return TRTX_OK;
+}
+
+extern "C" int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out,
+                                                   int Cout, int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2,
+                                                   trtx_stream_t stream) {
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || groups < 1 || k < 1 || pad < 0 || H + 2 * pad < k || W + 2 * pad < k) return TRTX_ERR_INVALID;
+    ConvArgs a{};
+    a.in = in; a.wgt = wpacked; a.bias = bias; a.out = out; a.residual = residual;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
+    a.Ho = H + 2 * pad - k + 1;
+    a.Wo = W + 2 * pad - k + 1;
+    a.Cout = Cout; a.Cout_pad = Cout; a.ld_out = ld_out; a.ld_res = ld_res;
+    a.kh = k; a.kw = k; a.stride_h = 1; a.stride_w = 1; a.pad_h = pad; a.pad_w = pad; a.dil_h = 1; a.dil_w = 1;
+    a.groups = groups;
+    a.K = k * k * (Cin / groups);
+    a.Kpad = conv_grouped_kpad(a);
+    a.M = N * a.Ho * a.Wo;
+    a.act1 = act1; a.act2 = act2; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    const int reps = options().op_reps;   // timing tools only
+    int32_t st = TRTX_OK;
+    for (int r = 0; r < reps && st == TRTX_OK; ++r) st = conv_grouped(a, static_cast<hipStream_t>(stream));
+    return st;
+}
+
 // --- fp32 engines: the implicit-GEMM convolution on the fp32 MFMA (kernels/conv_igemm_f32.hip), test / tool entry points
 static ConvArgs op_conv_args_f32(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw,
                                  int act1, int has_res, int ld_res, int act2) {

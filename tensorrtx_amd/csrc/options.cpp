@@ -35,6 +35,7 @@ Options read_options() {
     o.res = env_int("TRTX_CONV_RES", 7);
     o.roles = !env_is("TRTX_CONV_ROLES", 0);
     o.f32_mfma = !env_set("TRTX_F32_DIRECT");
+    o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);
     o.roialign_fused = !env_set("TRTX_ROIALIGN_PLUGIN");

@@ -30,6 +30,7 @@ struct Options {
     int res = 7;                 // TRTX_CONV_RES=<mask>: resident-operand kernels (conv_res.hip) among the candidates / in the grouped launches: 1 = the 3x3 kernel, 2 = the 1x1 kernel, 4 = the 3x3 kernel in grouped launches too; 0 = none
     bool roles = true;           // TRTX_CONV_ROLES=0: no fetching / multiplying wave-role variants among the candidates (fp32 plans)
     bool f32_mfma = true;        // TRTX_F32_DIRECT=1: fp32 engines on the scalar direct kernel of rounds 1-4 (no fp32 MFMA, no fp32 stem kernel)
+    bool conv_grouped = true;    // TRTX_CONV_GROUPED=0: grouped (not depthwise) convolutions stay on the scalar direct kernel (no kernels/conv_grouped.hip)
     bool area_attention = true;  // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
     bool yolo5_head = true;      // TRTX_YOLO5_HEAD=0: the anchor-based (YOLOv5) detect tail keeps the plugin route (layout passes to fp32 planes + YoloLayer_TRT)
     bool roialign_fused = true;  // TRTX_ROIALIGN_PLUGIN=1: RoIAlign stays a plugin op (fp32 NCHW edge)

@@ -178,6 +178,8 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     conv_set_launch_probe(nullptr);
                 } else if (op.dw)
                     st = conv_dw(a, op.dtype, stream);
+                else if (op.grouped)
+                    st = conv_grouped(a, stream);
                 else
                     st = conv_direct(a, op.dtype, stream);
                 break;

@@ -80,6 +80,17 @@ void pack_conv_weights_f32(const float* w, int cout, int cin_g, int kh, int kw, 
     }
 }
 
+void pack_conv_weights_grouped_f16(const float* w, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed) {
+    memset(packed, 0, sizeof(uint16_t) * (size_t)cout * kpad);
+    for (int co = 0; co < cout; ++co) {   // (KCRS rows are already group-major: channel co belongs to group co / Cout_g)
+        const float sc = ch_scale ? ch_scale[co] : 1.0f;
+        for (int c = 0; c < cin_g; ++c)
+            for (int r = 0; r < kh; ++r)
+                for (int q = 0; q < kw; ++q)
+                    packed[(size_t)co * kpad + (size_t)(r * kw + q) * cin_g + c] = f32_to_f16_bits(w[(((size_t)co * cin_g + c) * kh + r) * kw + q] * sc);
+    }
+}
+
 void pack_deconv_weights_f32(const float* w, int cin, int cout, int groups, int kh, int kw, float* packed) {
     const int cin_g = cin / groups, cout_g = cout / groups;
     for (int co = 0; co < cout; ++co) {
@@ -193,6 +204,9 @@ bool pack_weights(const Network& net, Plan* plan) {
                 op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
                 pack_conv_weights_f16(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
                                       reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+            } else if (op.grouped) {
+                op.w_off = reserve((size_t)cout * a.Kpad * 2);
+                pack_conv_weights_grouped_f16(w0, cout, cin_logical / a.groups, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
             } else if (op.dw) {
                 // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load
                 op.w_off = reserve((size_t)a.kh * a.kw * cout * 4);
@@ -206,7 +220,7 @@ bool pack_weights(const Network& net, Plan* plan) {
             }
             op.b_off = reserve(bias.size() * 4);
             memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
-            op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (size_t)cout * a.K * 4);
+            op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (op.grouped ? (size_t)cout * a.Kpad * 2 : (size_t)cout * a.K * 4));
         } else if (op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);

@@ -15,6 +15,10 @@ void pack_conv_weights_f16(const float* w_kcrs, int cout, int cin, int kh, int k
 void pack_conv_weights_f32(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale,
                            float* packed);
 
+// fp16 [group][Cout_g][kpad] = rows [Cout][kpad] for the grouped MFMA kernel (kernels/conv_grouped.hip): k = (r*kw + q)*cin_g + c, kpad = K rounded
+// up to 32, zero padded; the per-output-channel scale is multiplied in before rounding to fp16, as in pack_conv_weights_f16
+void pack_conv_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed);
+
 // TensorRT deconvolution weights are CKRS ([Cin][Cout/groups][kh][kw]); gather form for
 // deconv_direct is [Cout][kh][kw][Cin/groups].
 void pack_deconv_weights_f32(const float* w_ckrs, int cin, int cout, int groups, int kh, int kw, float* packed);

@@ -47,6 +47,7 @@ std::string Plan::describe_json() const {
               << ",\"ld_out\":" << a.ld_out << ",\"i8\":[" << a.in_i8 << "," << a.out_i8 << "," << a.res_i8 << "],\"nmul\":" << (op.stem ? 1 : tensors[op.in[0]].nmul) << ",\"nfix\":"
               << (op.stem ? 0 : tensors[op.in[0]].nfix);
             if (op.dw) o << ",\"dw\":true";
+            if (op.grouped) o << ",\"grouped\":true";
             if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);

@@ -102,6 +102,7 @@ struct POp {
     bool stem = false;         // conv_stem kernel: reads the LINEAR fp32 input directly
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
     bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
+    bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one
     int cout_real = 0;         // > 0: conv.Cout is this channel count rounded up to a 16-byte multiple; the filter rows and biases beyond it are zero
                                // and the output tensor's padding channels take the zeros (a detect convolution under OP_YOLO5_HEAD)
     // OP_CONV_GROUP: the member convolutions, each a complete OP_CONV record (its own in / out tensors, ConvArgs, weights); the group's

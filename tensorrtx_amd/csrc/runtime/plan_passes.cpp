@@ -153,6 +153,21 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
     // depthwise (YOLO11 DWConv and the PSA attention's pe): kernels/conv_dw.hip, fp16 and fp32, any channel stride
     op.dw = op.kind == OP_CONV && !op.igemm && !op.stem && !op.from_deconv && op.extra_in.empty() && ti.dtype == e.dt && to.dtype == e.dt &&
             (op.in.size() < 2 || plan.tensors[op.in[1]].dtype == e.dt) && conv_dw_supported(a);
+    // grouped, not depthwise (YOLOv9's DetectBbox_Conv: 64 -> 64 with g = 4): kernels/conv_grouped.hip, fp16 engines only, 16-byte aligned channel
+    // views; a.Kpad becomes the packed row length.  TRTX_CONV_GROUPED=0 leaves such layers on the direct kernel (A/B).  Not in kINT8 engines.
+    op.grouped = false;
+    if (op.kind == OP_CONV && !op.igemm && !op.dw && !op.stem && !op.from_deconv && op.extra_in.empty() && e.opt.conv_grouped && !e.int8 &&
+        !CalibrationLowering::active() && e.dt == DT_F16 && ti.dtype == DT_F16 && to.dtype == DT_F16 && ti.rcoff % 8 == 0 && to.rcoff % 8 == 0) {
+        bool ok = true;
+        if (op.in.size() > 1) {
+            const PTensor& tr = plan.tensors[op.in[1]];
+            ok = tr.dtype == DT_F16 && tr.rcoff % 8 == 0 && tr.ld % 8 == 0 && tr.ld >= a.Cout;
+        }
+        if (ok && conv_grouped_supported(a)) {
+            op.grouped = true;
+            a.Kpad = conv_grouped_kpad(a);
+        }
+    }
     return op.igemm;
 }
 
