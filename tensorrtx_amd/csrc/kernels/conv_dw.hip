@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 
 namespace trtx {
@@ -35,18 +36,6 @@ template <typename T, int V>
 struct alignas(sizeof(T) * V) Pack {
     T v[V];
 };
-
-__device__ __forceinline__ float dw_act(float v, int act, float alpha) {   // the direct kernel's act_f (nhwc_ops.hip)
-    switch (act) {
-        case ACT_RELU: return v > 0.f ? v : 0.f;
-        case ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
-        case ACT_SILU: return v / (1.0f + expf(-v));
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
-}
 
 template <typename T, int V>
 __device__ __forceinline__ void load_vec(const T* p, float (&x)[V]) {
@@ -118,9 +107,9 @@ __global__ __launch_bounds__(kThreads) void conv_dw_kernel(const ConvArgs p) {
             Pack<T, V> v;
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                float y = dw_act(acc[o][e], p.act1, p.alpha1);
+                float y = act_exact(acc[o][e], p.act1, p.alpha1);
                 if (res) y += r[e];
-                y = dw_act(y, p.act2, p.alpha2);
+                y = act_exact(y, p.act2, p.alpha2);
                 v.v[e] = (T)y;
             }
             *reinterpret_cast<Pack<T, V>*>(out + m * p.ld_out + c0) = v;

@@ -23,15 +23,13 @@
 #include <stdlib.h>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 #include "launch.h"
 
 namespace trtx {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr unsigned kOOB = 0x80000000u;
@@ -40,23 +38,6 @@ constexpr int ROW_B = BK * 2;            // 128 bytes per LDS row
 constexpr int HALF_B = 128 * ROW_B;      // one half-tile: 128 rows = 16 KB
 constexpr int BUF_B = 4 * HALF_B;        // A-lo, A-hi, B-lo, B-hi
 constexpr int LDS_B = 2 * BUF_B;         // 128 KB
-
-// the activations of conv_igemm.hip's epilogue, expression for expression (bit-identical outputs are the contract)
-__device__ __attribute__((noinline)) float g256_act_slow(float v, int act, float alpha) {
-    switch (act) {
-        case ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
-}
-__device__ __forceinline__ float g256_act(float v, int act, float alpha) {
-    if (act == ACT_NONE) return v;
-    if (act == ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-    return g256_act_slow(v, act, alpha);
-}
 
 // CONV3: the same GEMM over a 3x3 stride-1 pad-1 convolution's implicit A matrix (Cin a whole number of 64-channel K-tiles; K runs
 // (tap, channel slice) like the packed weights): a lane's four A rows carry the byte offset of their pixel's top-left tap and a 9-bit mask of the
@@ -286,7 +267,7 @@ __global__ __launch_bounds__(512) void conv_gemm256_f16_kernel(const ConvArgs p,
                     }
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) h[e] = round_to_half(g256_act_slow(v[e] + bias[j][e], p.act1, p.alpha1));
+                    for (int e = 0; e < 4; ++e) h[e] = round_to_half(act_fast_rare(v[e] + bias[j][e], p.act1, p.alpha1));
                 }
                 *reinterpret_cast<half4*>(mine + (i * 16 + (lane & 15)) * EPS + (j * 16 + 4 * (lane >> 4)) * 2) = h;
             }
@@ -312,7 +293,7 @@ __global__ __launch_bounds__(512) void conv_gemm256_f16_kernel(const ConvArgs p,
                     }
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = round_to_half(g256_act((float)v[e] + (float)rv[e], p.act2, p.alpha2));
+                    for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_fast((float)v[e] + (float)rv[e], p.act2, p.alpha2));
                 }
             }
             *reinterpret_cast<half8*>(out + (size_t)m * p.ld_out + n) = v;

@@ -27,15 +27,12 @@
 #include <algorithm>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 #include "launch.h"
 
 namespace trtx {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRows = 4;          // 16-pixel fragments per tile (3x3: tile rows)
 constexpr int kTilePx = kRows * 16;
@@ -52,21 +49,6 @@ constexpr int gr_ks(int taps, int cing) { return (taps * cing * 16 + 31) / 32; }
 // registers a wave keeps live: stationary weights, A offsets, accumulators of the four fragments, A operands in flight, bookkeeping
 constexpr int gr_regs(int taps, int cing, int upw) { return upw * gr_ks(taps, cing) * 4 + gr_ks(taps, cing) + 16 + 16 + 36; }
 constexpr int gr_min_waves(int regs) { return regs <= 128 ? 4 : (regs <= 200 ? 2 : 1); }
-
-__device__ __forceinline__ float gr_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __attribute__((noinline)) float gr_act_rare(float v, int act, float alpha) {
-    if (act == ACT_LEAKY) return v > 0.f ? v : v * alpha;
-    if (act == ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (act == ACT_TANH) return tanhf(v);
-    if (act == ACT_MISH) return mish_ref(v);
-    return v;
-}
-__device__ __forceinline__ float gr_act(float v, int act, float alpha) {
-    if (act == ACT_NONE) return v;
-    if (act == ACT_SILU) return gr_silu(v);
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-    return gr_act_rare(v, act, alpha);
-}
 
 // TAPS: 1 (1x1) or 9 (3x3); CING: Cin per group / 16; UPW: units per wave (1 or 2)
 template <int TAPS, int CING, int UPW>
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(256, gr_min_waves(gr_regs(TAPS, CING, UPW))) void c
             for (int f = 0; f < kRows; ++f) {
                 float v[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = gr_act(acc[f][e] + b4[e], p.act1, p.alpha1);
+                for (int e = 0; e < 4; ++e) v[e] = act_fast(acc[f][e] + b4[e], p.act1, p.alpha1);
                 if (second) {
                     float r4[4] = {0.f, 0.f, 0.f, 0.f};
                     if (res) {
@@ -192,7 +174,7 @@ __global__ __launch_bounds__(256, gr_min_waves(gr_regs(TAPS, CING, UPW))) void c
                         }
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = gr_act(v[e] + r4[e], p.act2, p.alpha2);
+                    for (int e = 0; e < 4; ++e) v[e] = act_fast(v[e] + r4[e], p.act2, p.alpha2);
                 }
                 half4 o;
 #pragma unroll

@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void conv_igemm_wsk_f16_kernel(const ConvArgs 
             for (int e = 0; e < 8; ++e) v[e] = round_to_half(x[e]);
         } else {
 #pragma nounroll
-            for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_slow(x[e], p.act1, p.alpha1));
+            for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_fast_rare(x[e], p.act1, p.alpha1));
         }
         const bool vec = !p.scalar_out;
         if (second) {
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256) void conv_igemm_wsk_f16_kernel(const ConvArgs 
                 }
             } else {
 #pragma nounroll
-                for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_apply((float)v[e] + (float)rv[e], p.act2, p.alpha2));
+                for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_fast((float)v[e] + (float)rv[e], p.act2, p.alpha2));
             }
         }
         if (vec) {
@@ -370,43 +370,34 @@ void launch_wsk(const ConvArgs& a, unsigned in_bytes, unsigned w_bytes, hipStrea
                        chunk);
 }
 
+bool plain_gemm(const ConvArgs& a) {   // the ONE instantiation's condition
+    return a.kh == 1 && a.kw == 1 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 0 && a.pad_w == 0 && a.Cin == a.CinK && a.Kpad == a.K;
+}
+
 template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2>
 void launch(const ConvArgs& a, unsigned in_bytes, unsigned w_bytes, hipStream_t s) {
     const int BN = 16 * NFRAG, BMT = 64 * MI;
     const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = a.Cout_pad / BN;
     const int total = tiles_m * tiles_n;
-    constexpr bool plain = false;   // (XCD-aware tile order always)
-    const int chunk = (total + 7) / 8;
-    const int dbg = options().conv_dbg;   // ablation builds only (the product kernels ignore it)
+    const int chunk = (total + 7) / 8;   // (XCD-aware tile order always)
+    const dim3 grid(chunk * 8), block(256);
     const bool rs_on = a.t_rs != 0;
     if constexpr (TPS == 1 && !I8) {
         if (a.up_C > 0) {   // folded upsample (conv_igemm_supported has checked the geometry)
-            if (rs_on)
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, 1, 0, false, 4, true, true>), dim3(plain ? total : chunk * 8), dim3(256), 0, s, a,
-                            in_bytes, w_bytes, tiles_n, total, chunk, dbg);
-            else
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, 1, 0, false, 4, false, true>), dim3(plain ? total : chunk * 8), dim3(256), 0, s, a,
-                            in_bytes, w_bytes, tiles_n, total, chunk, dbg);
+            if (rs_on) TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, true, true>), grid, block, 0, s, a, in_bytes, w_bytes, tiles_n, total, chunk);
+            else TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, false, true>), grid, block, 0, s, a, in_bytes, w_bytes, tiles_n, total, chunk);
             return;
         }
     }
     if constexpr (TPS == 1) {   // (int8 too since round 5: the addressing and the operand path do not depend on what the 16 bytes hold)
-        if (a.kh == 1 && a.kw == 1 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 0 && a.pad_w == 0 && a.Cin == a.CinK && a.Kpad == a.K) {
-            if (rs_on)
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, 1, 0, false, 4, true, false, true>), dim3(plain ? total : chunk * 8), dim3(256), 0, s, a,
-                            in_bytes, w_bytes, tiles_n, total, chunk, dbg);
-            else
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, 1, 0, false, 4, false, false, true>), dim3(plain ? total : chunk * 8), dim3(256), 0, s, a,
-                            in_bytes, w_bytes, tiles_n, total, chunk, dbg);
+        if (plain_gemm(a)) {
+            if (rs_on) TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, true, false, true>), grid, block, 0, s, a, in_bytes, w_bytes, tiles_n, total, chunk);
+            else TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, false, false, true>), grid, block, 0, s, a, in_bytes, w_bytes, tiles_n, total, chunk);
             return;
         }
     }
-    if (rs_on)
-        TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, 1, 0, false, 4, true>), dim3(plain ? total : chunk * 8), dim3(256), 0, s, a, in_bytes,
-                    w_bytes, tiles_n, total, chunk, dbg);
-    else
-    TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI>), dim3(plain ? total : chunk * 8), dim3(256), 0, s, a, in_bytes,
-                       w_bytes, tiles_n, total, chunk, dbg);
+    if (rs_on) TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI, true>), grid, block, 0, s, a, in_bytes, w_bytes, tiles_n, total, chunk);
+    else TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, BKT, TPS, I8, MI>), grid, block, 0, s, a, in_bytes, w_bytes, tiles_n, total, chunk);
 }
 
 template <int BKT, int TPS, bool I8 = false, int MI = 2>
@@ -444,13 +435,11 @@ bool wsk_default(const ConvArgs& a) {
     const int tiles128 = ((a.M + 127) / 128) * (a.Cout_pad / a.bn);
     return !no_wsk && wsk_possible(a) && tiles128 <= 256 && a.Kpad / 32 >= 16;
 }
-bool r3_possible(const ConvArgs&) { return false; }   // (the row-reuse kernel of rounds 2-4 left the library in round 5: tools/hip/experiments/README.md)
 // the resident-patch kernel: fp16 3x3 stride 1 pad 1 over at most 128 (or exactly 256) input channels, 16-byte output stores, 64 / 80 / 128-wide column tiles
 bool patch_possible(const ConvArgs& a) {
     return !a.up_C && !a.in_i8 && !a.out_i8 && !a.res_i8 && a.kh == 3 && a.kw == 3 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 1 && a.pad_w == 1 &&
            a.dil_h == 1 && a.dil_w == 1 && a.groups == 1 && a.bk == 32 && a.CinK % 32 == 0 && (a.CinK <= 128 || a.CinK == 256) && a.Cin % 8 == 0 && a.Kpad == 9 * a.CinK &&
-           !a.scalar_out && a.Ho == a.H && a.Wo == a.W && (a.bn == 64 || a.bn == 80 || a.bn == 128) && a.Cout_pad % a.bn == 0 && (a.bm == 0 || a.bm == 128) &&
-           a.t_r3 == 0;
+           !a.scalar_out && a.Ho == a.H && a.Wo == a.W && (a.bn == 64 || a.bn == 80 || a.bn == 128) && a.Cout_pad % a.bn == 0 && (a.bm == 0 || a.bm == 128);
 }
 // 64-row tiles are instantiated for the fp16 one-tap-per-step kernels (both k-step widths)
 bool bm64_possible(const ConvArgs& a) { return !a.in_i8 && a.CinK != 16; }
@@ -490,10 +479,10 @@ int conv_igemm_pick_cink(int cin, int bk) {
 }
 
 bool conv_igemm_supported(const ConvArgs& a) {
-    if (a.bn == 256) return conv_gemm256_possible(a) && a.t_r3 == 0 && a.Kpad == (a.kh * a.kw * a.CinK + 63) / 64 * 64;   // the 256 x 256 x 64 tactic
+    if (a.bn == 256) return conv_gemm256_possible(a) && a.Kpad == (a.kh * a.kw * a.CinK + 63) / 64 * 64;   // the 256 x 256 x 64 tactic
     if (a.in_i8 && (a.bk != 32 || a.CinK % 32 || a.scalar_out)) return false;  // int8: 64-channel k-steps, vector epilogue
     if (a.up_C != 0 && (a.up_C < 0 || a.in_i8 || a.kh != 1 || a.kw != 1 || a.stride_h != 1 || a.stride_w != 1 || a.pad_h || a.pad_w || a.up_C % 64 || a.up_C >= a.Cin ||
-                        a.H != 2 * a.up_H || a.W != 2 * a.up_W || a.up_ld % 8 || a.CinK == 16 || a.t_r3 != 0))
+                        a.H != 2 * a.up_H || a.W != 2 * a.up_W || a.up_ld % 8 || a.CinK == 16))
         return false;  // folded upsample: 1x1 stride 1, a whole number of k-steps from the half-resolution tensor
     if ((a.out_i8 || a.res_i8) && a.scalar_out) return false;
     const bool out_vec = a.ld_out % 8 == 0 && a.Cout % 8 == 0 && (!a.residual || a.ld_res % 8 == 0);
@@ -503,7 +492,7 @@ bool conv_igemm_supported(const ConvArgs& a) {
     return a.Cin % 8 == 0 && a.ld_in % 8 == 0 && a.groups == 1 && a.dil_h == 1 && a.dil_w == 1 && a.kh * a.kw <= kMaxTaps && cink_ok && a.CinK >= a.Cin &&
            a.Kpad == (a.kh * a.kw * a.CinK + bk - 1) / bk * bk && (out_vec || a.scalar_out) && img_bytes < 2.0e9 && w_b < 2.0e9 &&
            valid_bn(a.bn) && a.Cout_pad % a.bn == 0 && (a.bm == 0 || a.bm == 128 || (a.bm == 64 && bm64_possible(a)) || (a.bm == 256 && bm256_possible(a))) &&
-           (a.t_r3 == 0 || r3_possible(a))  && a.t_ws != 6;   // (wave roles, t_ws == 6, are an fp32 tactic: measured on the fp16 tiles, -3..-17 % on small maps alone, +-0 on the bench line: profiles/r05_fp16_roles_*)
+           a.t_ws != WS_F32_ROLES;   // (wave roles are an fp32 tactic: measured on the fp16 tiles, -3..-17 % on small maps alone, +-0 on the bench line: profiles/r05_fp16_roles_*)
 }
 
 // ---- tactics: the launch configurations of one layer that produce the SAME packed-weight layout, so that they can be exchanged
@@ -512,13 +501,13 @@ bool conv_igemm_supported(const ConvArgs& a) {
 // results may differ in the last place).
 int conv_tactics(const ConvArgs& a0, ConvTactic* out, int max_out, bool work_efficient_only) {
     int n = 0;
-    auto push = [&](int bn, int bk, int bm, int wsk, int ws, int r3 = 0) {
+    auto push = [&](int bn, int bk, int bm, int wsk, int ws) {
         for (int i = 0; i < n; ++i)
-            if (out[i].bn == bn && out[i].bk == bk && out[i].bm == bm && out[i].wsk == wsk && out[i].ws == ws && out[i].r3 == r3) return;
-        if (n < max_out) out[n++] = ConvTactic{bn, bk, bm, wsk, ws, r3};
+            if (out[i].bn == bn && out[i].bk == bk && out[i].bm == bm && out[i].wsk == wsk && out[i].ws == ws) return;
+        if (n < max_out) out[n++] = ConvTactic{bn, bk, bm, wsk, ws};
     };
     ConvArgs a = a0;
-    a.bm = 0; a.t_wsk = 0; a.t_ws = 0; a.t_r3 = 0;
+    a.bm = 0; a.t_wsk = WSK_RULE; a.t_ws = WS_AUTO;
     if (!conv_igemm_supported(a)) return 0;
     const bool fp16 = !a.in_i8 && !a.out_i8 && !a.res_i8;
     const bool pinned = a0.k_pinned != 0;   // one summation order whatever the tuner measures: no wave-split-K, no weight-stationary candidate
@@ -526,10 +515,10 @@ int conv_tactics(const ConvArgs& a0, ConvTactic* out, int max_out, bool work_eff
     // 0: the default.  Work-efficient sets (engines whose contexts share the chip) never split K over the waves, not even as the
     // starting point: measured on YOLOv8n b32 with three contexts in flight it is worth nothing there (33.0k img/s with, 33.1k without,
     // two runs each on one box), and "one summation order per plan" is the simpler contract.
-    if (ws_ok) push(a.bn, a.bk, 128, 1, 2);
-    else push(a.bn, a.bk, 128, (wsk_default(a) && !work_efficient_only && !pinned) ? 2 : 1, 1);
+    if (ws_ok) push(a.bn, a.bk, 128, WSK_OFF, WS_ON);
+    else push(a.bn, a.bk, 128, (wsk_default(a) && !work_efficient_only && !pinned) ? WSK_ON : WSK_OFF, WS_OFF);
     // the 256 x 256 x 64 role-alternating tile for large plain GEMMs (conv_gemm256.hip): more work-efficient than any 128-row tile
-    if (fp16 && options().gemm256 && conv_gemm256_worthwhile(a)) push(256, 64, 256, 1, 1);
+    if (fp16 && options().gemm256 && conv_gemm256_worthwhile(a)) push(256, 64, 256, WSK_OFF, WS_OFF);
     const int bks[2] = {a.bk, (fp16 && a.CinK % 64 == 0 && a.CinK != 16 && a.Kpad % 64 == 0) ? (a.bk == 32 ? 64 : 32) : a.bk};
     static const int bns[5] = {128, 80, 64, 32, 16};
     for (int bi = 0; bi < 5; ++bi) {
@@ -542,18 +531,18 @@ int conv_tactics(const ConvArgs& a0, ConvTactic* out, int max_out, bool work_eff
             t.bn = bn;
             t.bk = bks[ki];
             if (ki == 1 && bks[1] == bks[0]) continue;
-            push(bn, t.bk, 128, 1, 1);
-            if (bm64_possible(t) && !work_efficient_only) push(bn, t.bk, 64, 1, 1);
-            if (bm256_possible(t) && (long)((a.M + 255) / 256) * (a.Cout_pad / bn) >= 512) push(bn, t.bk, 256, 1, 1);  // >= 2 tiles per CU
-            if (wsk_possible(t) && !work_efficient_only && !pinned) push(bn, t.bk, 128, 2, 1);
-            // the resident-patch 3x3 kernel (ws == 3): the same bits, fewer bytes through the global -> LDS fill path (work-efficient: a candidate in every set)
-            if (fp16 && options().patch && patch_possible(t)) push(bn, t.bk, 128, 1, 3);
-            // the resident-operand kernels (ws == 7 / 8, conv_res.hip): the same bits again, nothing fetched inside the k-loop.  Measured on YOLOv8n b32
+            push(bn, t.bk, 128, WSK_OFF, WS_OFF);
+            if (bm64_possible(t) && !work_efficient_only) push(bn, t.bk, 64, WSK_OFF, WS_OFF);
+            if (bm256_possible(t) && (long)((a.M + 255) / 256) * (a.Cout_pad / bn) >= 512) push(bn, t.bk, 256, WSK_OFF, WS_OFF);  // >= 2 tiles per CU
+            if (wsk_possible(t) && !work_efficient_only && !pinned) push(bn, t.bk, 128, WSK_ON, WS_OFF);
+            // the resident-patch 3x3 kernel (WS_PATCH): the same bits, fewer bytes through the global -> LDS fill path (work-efficient: a candidate in every set)
+            if (fp16 && options().patch && patch_possible(t)) push(bn, t.bk, 128, WSK_OFF, WS_PATCH);
+            // the resident-operand kernels (WS_RES3 / WS_RES1, conv_res.hip): the same bits again, nothing fetched inside the k-loop.  Measured on YOLOv8n b32
             // (profiles/r06_engine_ab.txt, same box, alternating): the 3x3 kernel alone - one context 1.208 -> 1.188 ms, three contexts in flight 37.7-38.2k ->
             // 37.9k img/s; with the 1x1 kernel too - one context 1.174 ms, three contexts 37.1-37.2k: its 16-wave persistent workgroups leave another context's
             // kernels less room on a CU than they gain, so engines built for contexts in flight (work_efficient_only) list the 3x3 kernel only
-            if (fp16 && (options().res & 1) && conv_res_possible(t)) push(bn, t.bk, 128, 1, 7);
-            if (fp16 && (options().res & 2) && !work_efficient_only && conv_res1_possible(t)) push(bn, t.bk, 128, 1, 8);   // ... and its 1x1 sibling (ws == 8)
+            if (fp16 && (options().res & 1) && conv_res_possible(t)) push(bn, t.bk, 128, WSK_OFF, WS_RES3);
+            if (fp16 && (options().res & 2) && !work_efficient_only && conv_res1_possible(t)) push(bn, t.bk, 128, WSK_OFF, WS_RES1);   // ... and its 1x1 sibling
         }
     }
     return n;
@@ -565,17 +554,16 @@ void conv_apply_tactic(ConvArgs* a, const ConvTactic& t) {
     a->bm = t.bm;
     a->t_wsk = t.wsk;
     a->t_ws = t.ws;
-    a->t_r3 = t.r3;
 }
 
 int32_t conv_igemm_f16(const ConvArgs& a0, hipStream_t s) {
     if (!conv_igemm_supported(a0) || (a0.in_i8 && !a0.cscale)) return TRTX_ERR_UNSUPPORTED;
     const bool fp16 = !a0.in_i8 && !a0.out_i8 && !a0.res_i8;
     if (a0.bn == 256) return conv_gemm256_f16(a0, s);
-    if (fp16 && a0.t_ws == 7 && conv_res_possible(a0)) return conv_res_f16(&a0, 1, s);
-    if (fp16 && a0.t_ws == 8 && conv_res1_possible(a0)) return conv_res1_f16(a0, s);
-    // small-channel 3x3 / 1x1 fp16 layers: weight-stationary persistent kernel (t_ws: 0 = where supported, 1 = never, 2 = asked for)
-    if (fp16 && a0.t_ws != 1 && a0.t_ws != 3 && a0.t_ws != 7 && a0.t_ws != 8 && conv_ws_supported(a0)) return conv_ws_f16(a0, s);   // (3 = the resident-patch kernel, below)
+    if (fp16 && a0.t_ws == WS_RES3 && conv_res_possible(a0)) return conv_res_f16(&a0, 1, s);
+    if (fp16 && a0.t_ws == WS_RES1 && conv_res1_possible(a0)) return conv_res1_f16(a0, s);
+    // small-channel 3x3 / 1x1 fp16 layers: weight-stationary persistent kernel (WS_AUTO, WS_ON)
+    if (fp16 && a0.t_ws != WS_OFF && a0.t_ws != WS_PATCH && a0.t_ws != WS_RES3 && a0.t_ws != WS_RES1 && conv_ws_supported(a0)) return conv_ws_f16(a0, s);   // (the resident-patch kernel: below)
     // The buffer descriptor addresses 32-bit byte offsets: launch over groups of images whose slice stays below 2 GB.
     const size_t img_in = (size_t)a0.H * a0.W * a0.ld_in * 2;
     const int per = (int)std::max<size_t>(1, (size_t)2000000000 / img_in);
@@ -590,14 +578,13 @@ int32_t conv_igemm_f16(const ConvArgs& a0, hipStream_t s) {
         if (a0.up_C) a.up_in = static_cast<const char*>(a0.up_in) + (size_t)n0 * a.up_H * a.up_W * a.up_ld * 2;
         // extent of the addressed slice: last pixel's first byte + the channels this conv reads
         const unsigned in_bytes = (unsigned)((((size_t)a.N * a.H * a.W - 1) * a.ld_in + a.Cin) * 2);
-        // few tiles and a long k-chain: the wave-split-K variant (see conv_igemm_wsk_f16_kernel); t_wsk: 0 = that rule, 1 = never,
-        // 2 = wherever the variant exists
-        const bool wsk = a.t_wsk == 1 ? false : (a.t_wsk == 2 ? wsk_possible(a) : wsk_default(a));
+        // few tiles and a long k-chain: the wave-split-K variant (see conv_igemm_wsk_f16_kernel)
+        const bool wsk = a.t_wsk == WSK_OFF ? false : (a.t_wsk == WSK_ON ? wsk_possible(a) : wsk_default(a));
         const bool bm64 = a.bm == 64, bm256 = a.bm == 256;
         int32_t st = TRTX_OK;
         if (a.in_i8) {
             st = launch_bn<32, 1, true>(a, in_bytes, w_bytes, s);
-        } else if (a.t_ws == 3 && patch_possible(a)) {
+        } else if (a.t_ws == WS_PATCH && patch_possible(a)) {
             st = launch_patch(a, in_bytes, w_bytes, s);
         } else if (wsk) {
             if (a.bn == 64) launch_wsk<4>(a, in_bytes, w_bytes, s);
@@ -618,18 +605,14 @@ int32_t conv_igemm_f16(const ConvArgs& a0, hipStream_t s) {
 
 // ---- grouped launch ------------------------------------------------------------------------------------------------------
 namespace {
-bool plain_gemm(const ConvArgs& a) {   // the ONE instantiation's condition (launch<> above)
-    return a.kh == 1 && a.kw == 1 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 0 && a.pad_w == 0 && a.Cin == a.CinK && a.Kpad == a.K;
-}
 // what the single-problem dispatch would run for this layer must be the plain 128-row / 32-wide-step main kernel
 bool group_member_ok(const ConvArgs& a) {
     return conv_igemm_supported(a) && (a.in_i8 || (!a.out_i8 && !a.res_i8)) && !a.up_C && !a.scalar_out && a.CinK != 16 && a.bk == 32 && (a.bn == 64 || a.bn == 80) &&
-           (a.bm == 0 || a.bm == 128) && a.t_r3 == 0 && a.t_wsk != 2 && a.t_ws != 3 && (double)a.N * a.H * a.W * a.ld_in * 2.0 < 2.0e9;
+           (a.bm == 0 || a.bm == 128) && a.t_wsk != WSK_ON && a.t_ws != WS_PATCH && (double)a.N * a.H * a.W * a.ld_in * 2.0 < 2.0e9;
 }
 template <int NFRAG, bool RS, bool ONE, bool I8 = false>
 void launch_group(const ConvGroupArgs& g, hipStream_t s) {
-    const int dbg = options().conv_dbg;
-    TRTX_LAUNCH((conv_igemm_group_f16_kernel<NFRAG, 32, RS, ONE, I8>), dim3(g.slot_start[g.n] * 8), dim3(256), 0, s, g, dbg);
+    TRTX_LAUNCH((conv_igemm_group_f16_kernel<NFRAG, 32, RS, ONE, I8>), dim3(g.slot_start[g.n] * 8), dim3(256), 0, s, g);
 }
 }  // namespace
 
@@ -637,7 +620,7 @@ bool conv_igemm_group_supported(const ConvArgs* a, int n) {
     if (n < 2 || n > kMaxConvGroup) return false;
     for (int k = 0; k < n; ++k) {
         if (!group_member_ok(a[k])) return false;
-        if (a[k].t_ws != 1 && conv_ws_supported(a[k])) return false;   // that layer belongs to the weight-stationary kernel
+        if (a[k].t_ws != WS_OFF && conv_ws_supported(a[k])) return false;   // that layer belongs to the weight-stationary kernel
         if (a[k].bn != a[0].bn || a[k].in_i8 != a[0].in_i8 || (a[k].t_rs != 0) != (a[0].t_rs != 0) || plain_gemm(a[k]) != plain_gemm(a[0])) return false;
     }
     return true;

@@ -36,7 +36,7 @@ bool plain_gemm_f32(const ConvArgs& a) {
     return a.kh == 1 && a.kw == 1 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 0 && a.pad_w == 0 && a.Cin == a.CinK && a.Kpad == a.K && a.up_C == 0;
 }
 
-// operands through registers (global -> VGPR -> ds_write, two LDS stages) instead of LDS-DMA (three stages): ConvArgs::t_ws == 5, same bits.  Instantiated for
+// operands through registers (global -> VGPR -> ds_write, two LDS stages) instead of LDS-DMA (three stages): ConvArgs::t_ws == WS_F32_REGS, same bits.  Instantiated for
 // the 64- and 128-row tiles of the general and the plain-GEMM walk
 bool rs_exists(const ConvArgs& a, int bn, int bm) { return a.CinK != 8 && a.up_C == 0 && bm <= 128 && bn >= 32; }
 
@@ -45,7 +45,7 @@ bool rs_exists(const ConvArgs& a, int bn, int bm) { return a.CinK != 8 && a.up_C
 // plain-GEMM walk and of the folded upsample
 bool wide_exists(const ConvArgs& a, int bn, int bm) { return a.CinK % 32 == 0 && a.Kpad % 32 == 0 && bm <= 128 && bn >= 32 && (a.up_C % 32) == 0; }
 
-// roles (ConvArgs::t_ws == 6; igemm_tile.h ROLES): four fetching + four multiplying waves per workgroup, 16-channel steps through LDS-DMA, same bits.
+// roles (ConvArgs::t_ws == WS_F32_ROLES; igemm_tile.h ROLES): four fetching + four multiplying waves per workgroup, 16-channel steps through LDS-DMA, same bits.
 // Instantiated for the 64- and 128-row tiles, 32..128 columns wide, of the general walk, the plain-GEMM walk and the folded upsample
 bool roles_exist(const ConvArgs& a, int bn, int bm) { return a.CinK != 8 && bm <= 128 && bn >= 32; }
 
@@ -58,58 +58,47 @@ void launch_f32(const ConvArgs& a, const ConvArgs& k, unsigned in_bytes, unsigne
     if constexpr (MI <= 2 && NFRAG >= 2) {
         if (a.bk == 32) {
             if (a.up_C > 0)
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 64, 1, false, MI, 1, 0, false, 4, false, true, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 64, 1, false, MI, false, true, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             else if (plain_gemm_f32(a))
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 64, 1, false, MI, 1, 0, false, 4, false, false, true, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 64, 1, false, MI, false, false, true, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             else
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 64, 1, false, MI, 1, 0, false, 4, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 64, 1, false, MI, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             return;
         }
     }
-#ifdef TRTX_CONV_ABLATE   // timing experiments only (tools/f32_ablation.sh): TRTX_CONV_DBG as in the fp16 kernel, TRTX_F32_NST = 4 / 6 LDS stages (128 x 64 tile)
-    const int dbg = options().conv_dbg, nst = options().f32_stages;
-    if constexpr (MI == 2 && NFRAG == 4) {
-        if (a.CinK != 8 && !a.up_C && !plain_gemm_f32(a) && a.t_ws != 5) {
-            if (nst == 4) TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 4, false, 4, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, dbg);
-            else if (nst == 6) TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 6, false, 4, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, dbg);
-            else TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, dbg);
-            return;
-        }
-    }
-#endif
     if constexpr (MI <= 2 && NFRAG >= 2) {
-        if (a.t_ws == 6 && roles_exist(a, BN, BMT)) {
+        if (a.t_ws == WS_F32_ROLES && roles_exist(a, BN, BMT)) {
             const dim3 block2(512);
             if (a.up_C > 0)
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, true, false, true, true>), grid, block2, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, false, true, false, true, true>), grid, block2, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             else if (plain_gemm_f32(a))
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, false, true, true, true>), grid, block2, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, false, false, true, true, true>), grid, block2, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             else
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, false, false, true, true>), grid, block2, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, false, false, false, true, true>), grid, block2, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             return;
         }
-        if (a.t_ws == 5 && rs_exists(a, BN, BMT)) {
+        if (a.t_ws == WS_F32_REGS && rs_exists(a, BN, BMT)) {
             if (plain_gemm_f32(a))
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, true, false, true, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, true, false, true, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             else
-                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, true, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+                TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, true, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
             return;
         }
     }
     if (a.CinK == 8) {   // two filter taps per k-step (the 3-channel stems, padded to 4)
         if constexpr (MI == 2 && NFRAG <= 4)
-            TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 2, false, MI, 1, 0, false, 4, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+            TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 2, false, MI, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
     } else if (a.up_C > 0) {
         if constexpr (MI <= 2)
-            TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, true, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+            TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, false, true, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
     } else if (plain_gemm_f32(a)) {
-        TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, false, true, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+        TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, false, false, true, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
     } else {
-        TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, 1, 0, false, 4, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk, 0);
+        TRTX_LAUNCH((conv_igemm_f16_kernel<NFRAG, 32, 1, false, MI, false, false, false, true>), grid, block, 0, s, k, in_bytes, w_bytes, tiles_n, total, chunk);
     }
 }
 
-// ---- the resident-patch kernel with fp32 operands (ConvArgs::t_ws == 3; patch_tile.h): 3x3 stride 1 pad 1, the input of a TH x 16 output block lies in LDS
+// ---- the resident-patch kernel with fp32 operands (ConvArgs::t_ws == WS_PATCH; patch_tile.h): 3x3 stride 1 pad 1, the input of a TH x 16 output block lies in LDS
 // once as Cin / 16 planes, only the weight tile streams per k-step.  Planes: 16 / 32 / 48 / 64 / 80 / 128 input channels (1 .. 8 planes of an 8-row patch:
 // 15 KB each; 16-row patches up to two planes), column tiles 16 .. 80 wide.  Same K order, same two-level sum: the implicit-GEMM kernel's bits.
 bool patch_possible_f32(const ConvArgs& a, int bn) {
@@ -222,12 +211,12 @@ bool conv_igemm_f32_supported(const ConvArgs& a) {
     if ((double)a.H * a.W * a.ld_in * 4.0 >= 2.0e9 || (double)a.Cout_pad * a.Kpad * 4.0 >= 2.0e9) return false;
     if (a.bn || a.bm) {   // a tactic was named
         const int bm = a.bm ? a.bm : 128;
-        if (a.t_ws == 7) return a.bn && conv_res_possible(a);    // the resident-operand kernels (conv_res.hip) have their own shape tables
-        if (a.t_ws == 8) return a.bn && conv_res1_possible(a);
+        if (a.t_ws == WS_RES3) return a.bn && conv_res_possible(a);    // the resident-operand kernels (conv_res.hip) have their own shape tables
+        if (a.t_ws == WS_RES1) return a.bn && conv_res1_possible(a);
         if (!a.bn || a.Cout_pad % a.bn || !tile_exists(a, a.bn, bm)) return false;
-        if (a.t_ws == 5 && (!rs_exists(a, a.bn, bm) || a.bk != 16)) return false;
-        if (a.t_ws == 6 && (!roles_exist(a, a.bn, bm) || a.bk != 16)) return false;
-        if (a.t_ws == 3 && (!patch_possible_f32(a, a.bn) || a.bk != 16)) return false;
+        if (a.t_ws == WS_F32_REGS && (!rs_exists(a, a.bn, bm) || a.bk != 16)) return false;
+        if (a.t_ws == WS_F32_ROLES && (!roles_exist(a, a.bn, bm) || a.bk != 16)) return false;
+        if (a.t_ws == WS_PATCH && (!patch_possible_f32(a, a.bn) || a.bk != 16)) return false;
         if (a.bk == 32 && !wide_exists(a, a.bn, bm)) return false;
     } else {   // the launcher's own choice must exist (a folded upsample into 16 output channels has no instantiation)
         int bn = 0, bm = 0;
@@ -242,10 +231,10 @@ int conv_tactics_f32(const ConvArgs& a0, ConvTactic* out, int max_out) {
     a.bn = 0; a.bm = 0;
     if (!conv_igemm_f32_supported(a)) return 0;
     int n = 0;
-    auto push = [&](int bn, int bm, int ws = 1, int bk = 16) {
+    auto push = [&](int bn, int bm, int ws = WS_OFF, int bk = 16) {
         for (int i = 0; i < n; ++i)
             if (out[i].bn == bn && out[i].bm == bm && out[i].ws == ws && out[i].bk == bk) return;
-        if (n < max_out) out[n++] = ConvTactic{bn, bk, bm, 1, ws, 0};
+        if (n < max_out) out[n++] = ConvTactic{bn, bk, bm, WSK_OFF, ws};
     };
     int bn0, bm0;
     default_tile(a, &bn0, &bm0);
@@ -254,21 +243,21 @@ int conv_tactics_f32(const ConvArgs& a0, ConvTactic* out, int max_out) {
     static const int bms[3] = {128, 64, 256};
     for (int bn : bns)   // the resident-patch kernel at the widest column tile
         if (patch_possible_f32(a, bn)) {
-            push(bn, 128, 3);
+            push(bn, 128, WS_PATCH);
             break;
         }
-    // the resident-operand 3x3 kernel (conv_res.hip, round 6; ws == 7): weights of a column tile resident in LDS, role-rotating wave groups - the same bits
+    // the resident-operand 3x3 kernel (conv_res.hip, round 6; WS_RES3): weights of a column tile resident in LDS, role-rotating wave groups - the same bits
     if (options().res & 1)
         for (int bn : bns) {
             ConvArgs t = a;
-            t.bn = bn; t.bm = 128; t.t_ws = 7;
-            if (a.Cout_pad % bn == 0 && conv_res_possible(t)) push(bn, 128, 7);
+            t.bn = bn; t.bm = 128; t.t_ws = WS_RES3;
+            if (a.Cout_pad % bn == 0 && conv_res_possible(t)) push(bn, 128, WS_RES3);
         }
-    if (options().res & 2)   // ... and its 1x1 form (ws == 8)
+    if (options().res & 2)   // ... and its 1x1 form (WS_RES1)
         for (int bn : bns) {
             ConvArgs t = a;
-            t.bn = bn; t.bm = 128; t.t_ws = 8;
-            if (a.Cout_pad % bn == 0 && conv_res1_possible(t)) push(bn, 128, 8);
+            t.bn = bn; t.bm = 128; t.t_ws = WS_RES1;
+            if (a.Cout_pad % bn == 0 && conv_res1_possible(t)) push(bn, 128, WS_RES1);
         }
     for (int bn : bns) {
         if (a.Cout_pad % bn) continue;
@@ -276,9 +265,9 @@ int conv_tactics_f32(const ConvArgs& a0, ConvTactic* out, int max_out) {
         for (int bm : bms)
             if (tile_exists(a, bn, bm)) {
                 push(bn, bm);
-                if (wide_exists(a, bn, bm)) push(bn, bm, 1, 32);
-                if (rs_exists(a, bn, bm)) push(bn, bm, 5);
-                if (options().roles && roles_exist(a, bn, bm)) push(bn, bm, 6);
+                if (wide_exists(a, bn, bm)) push(bn, bm, WS_OFF, 32);
+                if (rs_exists(a, bn, bm)) push(bn, bm, WS_F32_REGS);
+                if (options().roles && roles_exist(a, bn, bm)) push(bn, bm, WS_F32_ROLES);
             }
     }
     return n;
@@ -286,8 +275,8 @@ int conv_tactics_f32(const ConvArgs& a0, ConvTactic* out, int max_out) {
 
 int32_t conv_igemm_f32(const ConvArgs& a0, hipStream_t s) {
     if (!conv_igemm_f32_supported(a0)) return TRTX_ERR_UNSUPPORTED;
-    if (a0.t_ws == 7 && a0.bn) return conv_res_f16(&a0, 1, s);   // (whole batch in one launch: its slice stays below 2 GB by conv_res_possible)
-    if (a0.t_ws == 8 && a0.bn) return conv_res1_f16(a0, s);
+    if (a0.t_ws == WS_RES3 && a0.bn) return conv_res_f16(&a0, 1, s);   // (whole batch in one launch: its slice stays below 2 GB by conv_res_possible)
+    if (a0.t_ws == WS_RES1 && a0.bn) return conv_res1_f16(a0, s);
     const size_t img_in = (size_t)a0.H * a0.W * a0.ld_in * 4;
     const int per = (int)std::max<size_t>(1, (size_t)2000000000 / img_in);
     const unsigned w_bytes = (unsigned)((size_t)a0.Cout_pad * a0.Kpad * 4);
@@ -304,7 +293,7 @@ int32_t conv_igemm_f32(const ConvArgs& a0, hipStream_t s) {
         const ConvArgs k = kernel_units(a);
         const unsigned in_bytes = (unsigned)((((size_t)a.N * a.H * a.W - 1) * a.ld_in + a.Cin) * 4);
         int32_t st;
-        if (a.t_ws == 3) st = launch_patch_f32(a, k, in_bytes, w_bytes, s);
+        if (a.t_ws == WS_PATCH) st = launch_patch_f32(a, k, in_bytes, w_bytes, s);
         else if (a.bm == 64) st = launch_f32_bn<1>(a, k, in_bytes, w_bytes, s);
         else if (a.bm == 256) st = launch_f32_bn<4>(a, k, in_bytes, w_bytes, s);
         else st = launch_f32_bn<2>(a, k, in_bytes, w_bytes, s);

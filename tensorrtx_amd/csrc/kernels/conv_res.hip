@@ -1,4 +1,4 @@
-// Resident-operand 3x3 convolution for gfx950 (MI355X), tactic ConvArgs::t_ws == 7 (round 6).  The kernel behind the 3x3 stride-1 layers of YOLOv8n's C2f
+// Resident-operand 3x3 convolution for gfx950 (MI355X), tactic ConvArgs::t_ws == WS_RES3 (round 6).  The kernel behind the 3x3 stride-1 layers of YOLOv8n's C2f
 // bottlenecks and detect head (yolov8/src/block.cpp:79-155, model.cpp:188-251) whose whole weight slab fits in LDS: 32 -> 32, 64 -> 64, 64 -> 80.
 //
 // Why (profiles/r05_igemm_f16_residency.txt, r04_lds_fill_model.txt): the implicit-GEMM kernels re-fill the weight tile of every k-step of every output tile
@@ -22,9 +22,6 @@
 #include "../options.h"
 #include "igemm_tile.h"
 
-#ifndef TRTX_RES_ABLATE  // the probe's ablation word (1 no stores, 2 no patch DMA after the prologue, 4 no MFMAs, 8 no activation); the constant 0 in the product
-#define TRTX_RES_ABLATE 0
-#endif
 #ifndef TRTX_RES_STAMP   // phase anatomy (tools/hip/res3_anatomy.hip): 0 phase entry, 1 k-loop done / patch DMA issued, 2 epilogue done, 3 waited, 4 past the barrier
 #define TRTX_RES_STAMP(ph, i)
 #endif
@@ -116,20 +113,15 @@ __device__ __forceinline__ void res_epilogue_slab(const ResP& p, const floatx4 (
             v[k] = j < NFRAG ? acc[j < NFRAG ? j : 0][k & 3] + bias[j < NFRAG ? j : 0][k & 3] : 0.f;   // (no bias: the registers hold -0.0f, the additive identity of every float)
         }
         if constexpr (ACT1 == ACT_SILU) {
-            if (TRTX_RES_ABLATE & 8) {
 #pragma unroll
-                for (int k = 0; k < GV; ++k) t[k] = 1.0f;
-            } else {
+            for (int k = 0; k < GV; ++k) t[k] = __expf(-v[k]);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = 0; k < GV; ++k) t[k] = __expf(-v[k]);
-                __builtin_amdgcn_sched_barrier(0);
+            for (int k = 0; k < GV; ++k) t[k] = 1.0f + t[k];
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = 0; k < GV; ++k) t[k] = 1.0f + t[k];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < GV; ++k) t[k] = __builtin_amdgcn_rcpf(t[k]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            for (int k = 0; k < GV; ++k) t[k] = __builtin_amdgcn_rcpf(t[k]);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < GV; ++k)
                 if (j0 * 4 + k < NV) h[j0 * 4 + k] = round_to_half(v[k] * t[k]);
@@ -170,7 +162,7 @@ __device__ __forceinline__ void res_epilogue_slab(const ResP& p, const floatx4 (
             }
         }
         const int co = 32 * jp + cpair;
-        if (okpix & (co < p.Cout) & !(TRTX_RES_ABLATE & 1)) *reinterpret_cast<__attribute__((address_space(1))) half8*>(orow + co) = o;
+        if (okpix & (co < p.Cout)) *reinterpret_cast<__attribute__((address_space(1))) half8*>(orow + co) = o;
     }
     if constexpr (ODD) {
         const uintx2 q = {pk[NFRAG - 1][0], pk[NFRAG - 1][1]};
@@ -249,7 +241,7 @@ __device__ __forceinline__ void res_epilogue_slab_f32(const ResP& p, const float
     for (int j = 0; j < NFRAG; ++j) {
         const int co = 16 * j + 4 * grp;
         const floatx4 xv = {v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
-        if (okpix & (co < p.Cout) & !(TRTX_RES_ABLATE & 1)) *reinterpret_cast<__attribute__((address_space(1))) floatx4*>(orow + co) = xv;
+        if (okpix & (co < p.Cout)) *reinterpret_cast<__attribute__((address_space(1))) floatx4*>(orow + co) = xv;
     }
 }
 
@@ -466,7 +458,7 @@ __global__ __launch_bounds__(NG * 256, WPS) void conv_res3_f16_kernel(const Conv
     for (int ph = 0; ph < T + NG - 1; ++ph) {
         TRTX_RES_STAMP(ph, 0);
         if (role == 0) {
-            if (ph < T && !(TRTX_RES_ABLATE & 4)) {
+            if (ph < T) {
                 const char* patch = patches + (ph & 1) * PATCH_BYTES;
                 if (p.res) {   // (unconditional loads from clamped addresses: a conditional load waits where it stands)
                     const px::Tile Tc = tile_of_coord(cw[2]);
@@ -571,7 +563,7 @@ __global__ __launch_bounds__(NG * 256, WPS) void conv_res3_f16_kernel(const Conv
             // a finishing role: request its share of the next tile's patch, finish its share of the row slabs, write the patch pieces
             auto other = [&](auto PART) {
                 constexpr int part = decltype(PART)::value, NPARTS = NG - 1, MINE = (NPW - part + NPARTS - 1) / NPARTS;
-                const bool fetch = ph + 1 < T && !(TRTX_RES_ABLATE & 2);
+                const bool fetch = ph + 1 < T;
                 const px::Tile Tn = tile_of_coord(cw[3]);
                 const int origin = patch_origin(Tn);
                 char* dst = patches + ((ph + 1) & 1) * PATCH_BYTES;
@@ -603,7 +595,7 @@ __global__ __launch_bounds__(NG * 256, WPS) void conv_res3_f16_kernel(const Conv
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
-// 1x1 stride-1 convolutions (plain GEMMs over NHWC rows), tactic ConvArgs::t_ws == 8: YOLOv8n's C2f / SPPF / head projections (block.cpp:79-155, model.cpp:188-251).
+// 1x1 stride-1 convolutions (plain GEMMs over NHWC rows), tactic ConvArgs::t_ws == WS_RES1: YOLOv8n's C2f / SPPF / head projections (block.cpp:79-155, model.cpp:188-251).
 // These layers are HBM-bound by a wide margin (128 -> 64 at 80 x 80, batch 32: 79 MB against 3.4 GFLOP - 12.5 us of memory time next to 1.3 us of MFMA and
 // ~1 us of epilogue VALU at full rate), and what the implicit-GEMM kernel spends on them is structure: a workgroup barrier, LDS-DMA pieces and a refill of the
 // weight tile per k-step.  Here: persistent workgroups of 16 INDEPENDENT waves (four per SIMD: the vector ALU needs that many to issue every 2 cycles - a lone
@@ -906,7 +898,7 @@ bool conv_res_possible(const ConvArgs& a) {
     }
     if (a.bk != 32 || a.CinK % 32 || a.Cin % 8 || a.Cin > a.CinK || a.Kpad != 9 * a.CinK || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.Cout % 8 || a.ld_out % 8 || a.ld_in % 8 || (a.residual && a.ld_res % 8)) return false;
-    if (!(a.bm == 0 || a.bm == 128) || a.t_r3 != 0) return false;
+    if (!(a.bm == 0 || a.bm == 128)) return false;
     if (!(a.act1 == ACT_NONE || a.act1 == ACT_RELU || a.act1 == ACT_SILU) || !(a.act2 == ACT_NONE || a.act2 == ACT_RELU)) return false;
     if ((double)a.N * a.H * a.W * a.ld_in * 2.0 >= 2.0e9 || (double)a.N * a.H * a.W * a.ld_out * 2.0 >= 4.0e9) return false;
     return res_shape(a).nfrag != 0;
@@ -1000,7 +992,7 @@ bool conv_res1_possible(const ConvArgs& a) {
     if (a.up_C || a.in_i8 || a.out_i8 || a.res_i8 || a.scalar_out) return false;
     if (res1_taps2(a)) {
         if (a.Cout % 8 || a.ld_out % 8 || a.ld_in % 8 || (a.residual && a.ld_res % 8)) return false;
-        if (!(a.bm == 0 || a.bm == 128) || a.t_r3 != 0) return false;
+        if (!(a.bm == 0 || a.bm == 128)) return false;
         if (!(a.act1 == ACT_NONE || a.act1 == ACT_RELU || a.act1 == ACT_SILU) || !(a.act2 == ACT_NONE || a.act2 == ACT_RELU)) return false;
         if (!(a.bn == 16 || a.bn == 32) || a.Cout_pad % a.bn) return false;
         const double pin = (double)a.N * a.H * a.W, pout = (double)a.N * a.Ho * a.Wo;
@@ -1017,7 +1009,7 @@ bool conv_res1_possible(const ConvArgs& a) {
     }
     if (a.bk != 32 || a.CinK % 32 || a.Cin % 8 || a.Cin > a.CinK || a.Kpad != a.CinK || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.Cout % 8 || a.ld_out % 8 || a.ld_in % 8 || (a.residual && a.ld_res % 8)) return false;
-    if (!(a.bm == 0 || a.bm == 128) || a.t_r3 != 0) return false;
+    if (!(a.bm == 0 || a.bm == 128)) return false;
     if (!(a.act1 == ACT_NONE || a.act1 == ACT_RELU || a.act1 == ACT_SILU) || !(a.act2 == ACT_NONE || a.act2 == ACT_RELU)) return false;
     if (!(a.bn == 32 || a.bn == 64 || a.bn == 80 || a.bn == 128) || a.Cout_pad % a.bn) return false;
     if ((long)a.Kpad * a.bn * 2 > 98304) return false;   // the column tile's weights in LDS

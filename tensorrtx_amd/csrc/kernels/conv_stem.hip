@@ -20,24 +20,11 @@
 #include <string.h>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 
 namespace trtx {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float stem_act(float v, int act, float alpha) {
-    switch (act) {
-        case ACT_RELU: return v > 0.f ? v : 0.f;
-        case ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        case ACT_SILU: return v / (1.0f + __expf(-v));
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
-}
 
 template <int COUT>
 __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvArgs p) {
@@ -84,13 +71,11 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvArgs p) {
     for (int c8 = 0; c8 < COUT / 8; ++c8) {
         half8 v;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = round_to_half(stem_act(acc[c8 * 8 + e], p.act1, p.alpha1));
+        for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_stem(acc[c8 * 8 + e], p.act1, p.alpha1));
         *reinterpret_cast<half8*>(out + c8 * 8) = v;
     }
 }
 
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int kStemTW = 64, kStemTH = 4;  // output tile of a workgroup: 4 rows x 64 columns = 16 MFMA groups of 16 pixels
@@ -356,7 +341,7 @@ __device__ __forceinline__ void stem_compute(const ConvArgs& p, const StemGeom& 
         for (int j = 0; j < NFRAG; ++j) {
             const int co = j * 16 + ch4;
             if (co >= p.Cout) continue;
-            half4_t o;
+            half4 o;
             if (p.act1 == ACT_SILU) {  // wave-uniform: pick the activation once, not per element
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -371,9 +356,9 @@ __device__ __forceinline__ void stem_compute(const ConvArgs& p, const StemGeom& 
                 }
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = round_to_half(stem_act(acc[j][e] + bias4[j][e], p.act1, p.alpha1));
+                for (int e = 0; e < 4; ++e) o[e] = round_to_half(act_stem(acc[j][e] + bias4[j][e], p.act1, p.alpha1));
             }
-            *reinterpret_cast<half4_t*>(out + m * p.ld_out + co) = o;
+            *reinterpret_cast<half4*>(out + m * p.ld_out + co) = o;
         }
     }
 }

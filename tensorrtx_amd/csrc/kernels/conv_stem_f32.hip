@@ -9,24 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 
 namespace trtx {
 namespace {
 
 constexpr int kCo = 16;   // output channels per lane
-
-__device__ __forceinline__ float stem_act(float v, int act, float alpha) {
-    if (act == ACT_NONE) return v;
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACT_SILU || act == ACT_SIGMOID) {
-        const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));   // as conv_epilogue_f32
-        return act == ACT_SILU ? v * sg : sg;
-    }
-    if (act == ACT_LEAKY) return v > 0.f ? v : v * alpha;
-    if (act == ACT_TANH) return tanhf(v);
-    return mish_ref(v);
-}
 
 // KS: filter size when square and known (3, 7), 0 = runtime kh x kw
 template <int KS>
@@ -71,10 +60,10 @@ __global__ __launch_bounds__(256) void conv_stem_f32_kernel(const ConvArgs p) {
 #pragma unroll
     for (int j = 0; j < kCo; j += 4) {
         float4 v;
-        v.x = stem_act(acc[j], p.act1, p.alpha1);
-        v.y = stem_act(acc[j + 1], p.act1, p.alpha1);
-        v.z = stem_act(acc[j + 2], p.act1, p.alpha1);
-        v.w = stem_act(acc[j + 3], p.act1, p.alpha1);
+        v.x = act_f32(acc[j], p.act1, p.alpha1);
+        v.y = act_f32(acc[j + 1], p.act1, p.alpha1);
+        v.z = act_f32(acc[j + 2], p.act1, p.alpha1);
+        v.w = act_f32(acc[j + 3], p.act1, p.alpha1);
         *reinterpret_cast<float4*>(o + j) = v;
     }
 }

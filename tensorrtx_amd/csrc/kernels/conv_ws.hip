@@ -32,15 +32,13 @@
 
 #include "../common.h"
 #include "../options.h"
+#include "act.h"
 #include "kernels.h"
 #include "launch.h"
 
 namespace trtx {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr unsigned kOOB = 0x80000000u;  // beyond any num_records: the buffer load returns 0 and touches no memory
@@ -54,24 +52,8 @@ struct WsGeom {
     int xcd_chunk;       // tiles per XCD in the XCD-aware tile order
     int grid;            // workgroups launched
     float inv_tw, inv_pwp, inv_tpi;  // reciprocals for the exact small-integer divisions
-    int dbg;             // timing experiments (TRTX_WS_DBG): 1 no patch DMA, 2 no MFMA loop, 4 no stores, 8 no weight loads
 };
 
-__device__ __forceinline__ float act_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-// the rare activation kinds, out of line (one copy in the kernel instead of one per call site: code size is a cost here)
-__device__ __attribute__((noinline)) float ws_act_rare(float v, int act, float alpha) {
-    if (act == ACT_LEAKY) return v > 0.f ? v : v * alpha;
-    if (act == ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (act == ACT_TANH) return tanhf(v);
-    if (act == ACT_MISH) return mish_ref(v);
-    return v;
-}
-__device__ __forceinline__ float ws_act_any(float v, int act, float alpha) {
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACT_SILU) return act_silu(v);
-    if (act == ACT_NONE) return v;
-    return ws_act_rare(v, act, alpha);
-}
 // exact x / d for 0 <= x < 2^22 with a float reciprocal estimate fixed up by one step
 __device__ __forceinline__ int div_small(int x, int d, float inv) {
     int q = (int)((float)x * inv);
@@ -121,7 +103,6 @@ __global__ __launch_bounds__(256, ws_min_waves(ws_regs(TAPS, KC, NFW, WC, NF, RO
     const int tpi = g.tiles_x * g.tiles_y;
 
     auto issue_patch = [&](int t, int b) {
-        if (g.dbg & 1) return;
         // tile -> (image, tile row, tile column); wave-uniform
         const int n = div_small(t, tpi, g.inv_tpi);
         const int r = t - n * tpi;
@@ -160,7 +141,7 @@ __global__ __launch_bounds__(256, ws_min_waves(ws_regs(TAPS, KC, NFW, WC, NF, RO
             const _Float16* wr = w + (size_t)(live ? row : 0) * p.Kpad + (lane >> 4) * 8;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                half8 v = (g.dbg & 8) ? half8{1, 1, 1, 1, 1, 1, 1, 1} : *reinterpret_cast<const half8*>(wr + ks * 32);
+                half8 v = *reinterpret_cast<const half8*>(wr + ks * 32);
                 if (!live) v = half8{0, 0, 0, 0, 0, 0, 0, 0};
                 breg[ks][j] = v;
             }
@@ -219,7 +200,7 @@ __global__ __launch_bounds__(256, ws_min_waves(ws_regs(TAPS, KC, NFW, WC, NF, RO
             return *reinterpret_cast<const half8*>(buf + a_addr[f][tap] + kc * g.plane_bytes);
         };
 #pragma unroll
-        for (int f0 = 0; f0 < AFW && !(g.dbg & 2); f0 += FG) {
+        for (int f0 = 0; f0 < AFW; f0 += FG) {
             half8 a_cur[FG], a_nxt[FG];
 #pragma unroll
             for (int i = 0; i < FG; ++i) a_cur[i] = a_load(f0 + i, 0);
@@ -262,13 +243,13 @@ __global__ __launch_bounds__(256, ws_min_waves(ws_regs(TAPS, KC, NFW, WC, NF, RO
                 half4 o;
                 if (p.act1 == ACT_SILU) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = round_to_half(act_silu(acc[f][j][e] + b4[e]));
+                    for (int e = 0; e < 4; ++e) o[e] = round_to_half(act_fast(acc[f][j][e] + b4[e], ACT_SILU, 0.f));
                 } else if (p.act1 == ACT_NONE) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = round_to_half(acc[f][j][e] + b4[e]);
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = round_to_half(ws_act_any(acc[f][j][e] + b4[e], p.act1, p.alpha1));
+                    for (int e = 0; e < 4; ++e) o[e] = round_to_half(act_fast(acc[f][j][e] + b4[e], p.act1, p.alpha1));
                 }
                 *reinterpret_cast<half4*>(stg + (lane & 15) * RS + j * 32 + (lane >> 4) * 8) = o;
             }
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(256, ws_min_waves(ws_regs(TAPS, KC, NFW, WC, NF, RO
                 }
                 const int ho = ty * g.TH + oy, wo = tx * g.TW + ox;
                 const int co = wc * NFW * 16 + cc * 8;
-                if (oy >= g.TH || ho >= p.Ho || wo >= p.Wo || co >= p.Cout || (g.dbg & 4)) continue;
+                if (oy >= g.TH || ho >= p.Ho || wo >= p.Wo || co >= p.Cout) continue;
                 const size_t m = (size_t)(n * p.Ho + ho) * p.Wo + wo;
                 half8 v = *reinterpret_cast<const half8*>(stg + row * RS + cc * 16);
                 if (second) {
@@ -298,7 +279,7 @@ __global__ __launch_bounds__(256, ws_min_waves(ws_regs(TAPS, KC, NFW, WC, NF, RO
                         for (int e = 0; e < 8; ++e) v[e] = round_to_half((float)v[e] + (float)rv[e]);
                     } else {
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = round_to_half(ws_act_any((float)v[e] + (float)rv[e], p.act2, p.alpha2));
+                        for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_fast((float)v[e] + (float)rv[e], p.act2, p.alpha2));
                     }
                 }
                 *reinterpret_cast<half8*>(out + m * p.ld_out + co) = v;
@@ -437,7 +418,6 @@ int32_t launch_ws(const ConvArgs& a, const WsGeom& g, unsigned in_bytes, hipStre
         *occ_cache = occ;
     }
     WsGeom gg = g;
-    gg.dbg = 0;
     gg.grid = (std::min(g.total_tiles, 256 * occ) + 7) / 8 * 8;
     TRTX_LAUNCH(kern, dim3(gg.grid), dim3(256), lds, s, a, gg, in_bytes);
     return TRTX_OK;

@@ -25,7 +25,7 @@
 // translation units that instantiate it: conv_igemm.hip (fp16 and - I8 - int8 operands), conv_igemm_f32.hip (F32: fp32 operands on v_mfma_f32_16x16x4_f32,
 // round 5) and, through patch_tile.h, the resident-patch 3x3 kernels.  Template switches of conv_igemm_tile, all compile-time: NFRAG / MI tile width and
 // height, BKT / TPS k-step width and taps per step, I8 / F32 operand type, RS operands through registers instead of LDS-DMA, UP folded nearest upsample,
-// ONE plain-GEMM addressing, ROLES fetching + multiplying waves (instantiated for F32), WN / NW / NSTO / PRE wave grid, waves, stages, read-ahead.
+// ONE plain-GEMM addressing, ROLES fetching + multiplying waves (instantiated for F32).
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 #include "launch.h"
 #include "patch_index.h"
@@ -47,43 +48,17 @@
 #ifndef TRTX_MARK   // launch anatomy (tools/hip/igemm_launch_anatomy.hip): 0 entry, 1 first tile issued, 2 k-loop done, 3 epilogue done
 #define TRTX_MARK(i)
 #endif
-// Ablation switches for the timing experiments of tools/conv_dbg.sh (build with -DTRTX_CONV_ABLATE to get them from the
-// TRTX_CONV_DBG environment variable: 1 A loads range-checked away, 2 B loads, 4 no ds_read/MFMA, 8 no epilogue, 16 no
-// k-loop).  In the product build the flag word is the constant 0 and every test on it folds away.
-#ifdef TRTX_CONV_ABLATE
-#define TRTX_DBG(flags) (flags)
-#else
-#define TRTX_DBG(flags) 0
-#endif
 
 namespace trtx {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef int intx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int NSTAGE = 3;
+constexpr int kWaves = 4;                    // waves per workgroup of the implicit-GEMM tile (under ROLES: multiplying waves, and as many fetching)
 constexpr unsigned kOOB = 0x80000000u;  // offset beyond any num_records: the buffer load returns 0
 constexpr int kMaxTaps = 30;            // tap-validity mask is one 32-bit word (+2 bits of run-out past the last tap)
 
-__device__ __attribute__((noinline)) float act_slow(float v, int act, float alpha) {
-    switch (act) {
-        case ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
-}
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    if (act == ACT_NONE) return v;
-    if (act == ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-    return act_slow(v, act, alpha);
-}
 
 // bit t set iff 0 <= x0 + t < extent, for t in [0, k), k <= 30
 __device__ __forceinline__ unsigned tap_range_mask(int x0, int k, int extent) {
@@ -192,7 +167,7 @@ __device__ __forceinline__ void conv_epilogue_fast(const ConvArgs& p, floatx4 (&
 // stores) exists ONCE, in a rolled loop with wave-uniform branches, instead of once per accumulator fragment and activation
 // kind.  Unrolled, that code was 80 % of a 45-90 KB kernel against a 64 KB instruction cache shared by two CUs
 // (profiles/r02_code_size.txt).  `pixel_of(t)` maps row t of the tile (0 .. 64 * MI) to the output pixel index, or -1.
-template <int NFRAG, int MI, bool I8, int LDS_BYTES, int NWAVES = 4, typename PixelOf>
+template <int NFRAG, int MI, bool I8, int LDS_BYTES, typename PixelOf>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[MI][NFRAG], intx4 (&acci)[MI][NFRAG], char* smem, int wave, int lane,
                                               int n0, PixelOf&& pixel_of, int row0 = -1) {
     constexpr int BN = 16 * NFRAG;
@@ -203,7 +178,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[
     const int ch_in = (lane >> 4) * 4;
     const bool second = res || p.act2 != ACT_NONE;
     constexpr int PS = BN * 4 + 16;   // fp32 row stride of the staging tile (padded: 16 consecutive rows start in distinct bank groups)
-    static_assert(NWAVES * 16 * PS <= LDS_BYTES, "epilogue tile must fit in the stage buffers");
+    static_assert(kWaves * 16 * PS <= LDS_BYTES, "epilogue tile must fit in the stage buffers");
     constexpr int CPR = BN / 8;       // 8-channel items per row
     constexpr int ITEMS = 16 * CPR;   // items of one 16-row slab of this wave
     // A lane's items q = lane, lane + 64, ... all sit in the same 8-channel column when CPR divides 64 (every tile width but 80): its bias
@@ -213,7 +188,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[
     // private LDS strip behind the staging tiles; an item reads its eight from there (an LDS read where an L2 round trip stood).
     constexpr bool BIAS_FIXED = (64 % CPR) == 0;
     constexpr int BIAS_LDS = BIAS_FIXED ? 0 : BN * 4;
-    static_assert(NWAVES * (16 * PS + BIAS_LDS) <= LDS_BYTES, "epilogue tile + bias strip must fit in the stage buffers");
+    static_assert(kWaves * (16 * PS + BIAS_LDS) <= LDS_BYTES, "epilogue tile + bias strip must fit in the stage buffers");
     float4 bf0 = make_float4(0.f, 0.f, 0.f, 0.f), bf1 = bf0;
     if (BIAS_FIXED && p.bias) {
         const int co0 = n0 + (lane % CPR) * 8;
@@ -224,9 +199,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[
     if (!BIAS_FIXED && p.bias) bf0 = *reinterpret_cast<const float4*>(p.bias + n0 + (lane < BN / 4 ? lane * 4 : 0));   // (n0 + BN <= Cout_pad)
     __syncthreads();  // every wave is done reading the last stage
     char* mine = smem + wave * 16 * PS;
-    char* bias_lds = smem + NWAVES * 16 * PS + wave * BIAS_LDS;
+    char* bias_lds = smem + kWaves * 16 * PS + wave * BIAS_LDS;
     if (!BIAS_FIXED && p.bias && lane < BN / 4) *reinterpret_cast<float4*>(bias_lds + lane * 16) = bf0;   // wave-private: ordered with this wave's reads
-    const int rbase = row0 < 0 ? wave * WR : row0;   // first tile row of this wave (waves may also be split along N: WN below)
+    const int rbase = row0 < 0 ? wave * WR : row0;   // first tile row of this wave
     // The common case - 16-byte fp16 stores, ReLU / SiLU / no activation, fp16 residual - has its own item loop (round 4).  In the general
     // loop below the rare paths (int8 residual, element-wise ragged loads and stores, the slow activations) put global LOADS into the loop
     // body; the compiler's wait for them (`s_waitcnt vmcnt(0)`, merged at the loop header) then also waits for the previous item's STORE
@@ -289,7 +264,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[
                 for (int e = 0; e < 8; ++e) v[e] = round_to_half(x[e]);
             } else {
 #pragma nounroll
-                for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_slow(x[e], p.act1, p.alpha1));
+                for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_fast_rare(x[e], p.act1, p.alpha1));
             }
             const bool vec = !p.scalar_out;
             if (second) {
@@ -318,7 +293,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[
                     }
                 } else {
 #pragma nounroll
-                    for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_apply((float)v[e] + (float)rv[e], p.act2, p.alpha2));
+                    for (int e = 0; e < 8; ++e) v[e] = round_to_half(act_fast((float)v[e] + (float)rv[e], p.act2, p.alpha2));
                 }
             }
             if (p.out_i8) {  // requantise: round to nearest even, clamp to +-127, 8 channels = one 8-byte store
@@ -343,28 +318,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, floatx4 (&acc)[
 
 // ---- epilogue of the fp32 kernels (conv_igemm_f32.hip).  The accumulator fragment of a lane is already what an NHWC fp32 store wants: four consecutive
 // channels (16j + 4 (lane >> 4) + [0, 4)) of one pixel = 16 bytes, the four lane groups of a pixel cover 64 contiguous bytes.  No staging through LDS, no
-// barrier: activation / shortcut / store straight from the registers (the bias is where the sums started).  SiLU / sigmoid are v * rcp(1 + exp2(-v log2 e)) on the hardware's v_exp_f32 /
-// v_rcp_f32 (1 ulp each): 5 instructions per element where expf + an IEEE division are ~30.  Measured on the first build (round 5): with the accurate
-// forms a 128 x 80 tile's epilogue was ~7k cycles of VALU issue per wave - 12 % of a 45-step 3x3 and MORE than the whole k-loop of a 4-step 1x1 - for an
-// error 60x below what 63 layers of fp32 summation leave on a logit (7e-5 at 640 x 640, against BASELINE's 1e-4).  The row slabs are walked by a rolled
-// loop: one copy of the activation code per column fragment, not per accumulator.
-__device__ __attribute__((noinline)) float act_slow_f32(float v, int act, float alpha) {
-    switch (act) {
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
-}
-__device__ __forceinline__ float act_f32(float v, int act, float alpha) {
-    if (act == ACT_NONE) return v;
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == ACT_SILU || act == ACT_SIGMOID) {
-        const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
-        return act == ACT_SILU ? v * sg : sg;
-    }
-    return act_slow_f32(v, act, alpha);
-}
+// barrier: activation / shortcut / store straight from the registers (the bias is where the sums started).  The activations are act.h's fp32
+// family (act_f32).  The row slabs are walked by a rolled loop: one copy of the activation code per column fragment, not per accumulator.
 template <int NFRAG, int MI, typename PixelOf>
 __device__ __forceinline__ void conv_epilogue_f32(const ConvArgs& p, floatx4 (&acc)[MI][NFRAG], int lane, int n0, PixelOf&& pixel_of, int rbase) {
     float* __restrict__ out = static_cast<float*>(p.out);
@@ -421,12 +376,8 @@ __device__ __forceinline__ void conv_epilogue_f32(const ConvArgs& p, floatx4 (&a
 // MI = 16-row MFMA fragments per wave along M: 2 -> a 128-row tile (the default), 1 -> a 64-row tile (twice the workgroups for
 // layers whose 128-row tiling leaves most of the 256 CUs idle), 4 -> a 256-row tile (half the tiles, prologues and weight
 // traffic for the large maps); chosen per layer by the tactic tuner, runtime/tune.cpp.
-// WN = waves along N: 1 -> the four waves stack along M and each reads ALL of the B tile (fine up to 128 x 128: 40 LDS bytes per
-// wave-cycle at most); 2 -> a 2 x 2 wave grid, each wave owns (BM / 2) x (BN / 2).  The large-GEMM configuration is <NFRAG 8, BKT 64,
-// MI 8, WN 2, three stages>: a 256 x 128 tile of 128 x 64 wave tiles - 12 ds_read_b128 per 32 MFMAs (24 LDS bytes per wave-cycle, 75 %
-// of what the CU's LDS delivers when all four SIMDs keep their MFMA pipe full; the 128 x 128 / WN 1 tile needs 160 B/clk for that and
-// cannot), 43 MACs per operand byte fetched into LDS, accumulators 128 VGPRs.  Its three stages are 144 KB of LDS: one workgroup per
-// CU, which the 64 independent MFMAs per k-step of every wave tolerate.  NSTO overrides the stage count.
+// The four waves stack along M and each reads ALL of the B tile (fine up to 128 x 128: 40 LDS bytes per wave-cycle at most); the large plain GEMMs have their own
+// 256 x 256 x 64 tile in conv_gemm256.hip.
 // RS = register-staged operands: global memory -> VGPRs (buffer_load_dwordx4) -> LDS (ds_write_b128, the same lane-linear rows the
 // DMA writes) instead of buffer_load ... lds.  One LDS-DMA piece (1 KiB per wave-instruction) costs the issuing wave 60-185 cycles
 // of issue (MI355X_MICROARCH.md; ablation of this kernel, profiles/r03_gemm_ablation.txt: the k-loop with the MFMAs removed is 72 % of
@@ -443,59 +394,53 @@ __device__ __forceinline__ void conv_epilogue_f32(const ConvArgs& p, floatx4 (&a
 // Measured (round 3, same box): the 1x1 layers of YOLOv8n b32 3-10 % faster one at a time (34-layer sum 715 vs 724 us), res5's 1x1
 // 2048 -> 512 GEMM 497 vs 509 us; bench.py within run-to-run noise (35.0-35.2k vs 34.4-35.3k img/s).  Same bits.
 // LDS bytes of one instantiation (the stage buffers, or the epilogue's staging tiles if those are larger)
-template <int NFRAG, int BKT, int MI, int WN, int NSTO, int NW, bool RS>
+template <int NFRAG, int BKT, int MI, bool RS>
 constexpr int igemm_lds_bytes() {
-    constexpr int BN = 16 * NFRAG, WM = NW / WN, NFW = NFRAG / WN, BM = WM * 16 * MI, ROW_B = BKT * 2, CH = BKT / 8, RPI = 64 / CH;
-    constexpr int B_PASSES = (BN + NW * RPI - 1) / (NW * RPI), B_ROWS = B_PASSES * NW * RPI;
+    constexpr int BN = 16 * NFRAG, BM = kWaves * 16 * MI, ROW_B = BKT * 2, CH = BKT / 8, RPI = 64 / CH;
+    constexpr int B_PASSES = (BN + kWaves * RPI - 1) / (kWaves * RPI), B_ROWS = B_PASSES * kWaves * RPI;
     constexpr int STAGE_BYTES = BM * ROW_B + B_ROWS * ROW_B;
-    constexpr int NST = RS ? 2 : NSTO ? NSTO : (BKT == 64 ? 2 : 3);
-    constexpr int EPI_BYTES = NW * 16 * (16 * NFW * 4 + 16);
+    constexpr int NST = RS ? 2 : (BKT == 64 ? 2 : 3);
+    constexpr int EPI_BYTES = kWaves * 16 * (16 * NFRAG * 4 + 16);
     return NST * STAGE_BYTES > EPI_BYTES ? NST * STAGE_BYTES : EPI_BYTES;
 }
 
 // One (BM x BN) output tile at (m0, n0) of the convolution `p`: the whole kernel but for the blockIdx -> tile mapping, which the two
 // entry points below do differently (one problem per launch / several problems per launch, round 4).
-// ROLES (round 5): the workgroup is 2 * NW waves; waves NW .. 2NW-1 only FETCH (address arithmetic, the LDS-DMA pieces, the counted wait, the barrier) and
-// waves 0 .. NW-1 only MULTIPLY (barrier, fragment reads, MFMAs, epilogue).  A DMA piece holds its wave's issue port for 60-200 cycles and the tap / address
+// ROLES (round 5): the workgroup is 2 * kWaves waves; waves kWaves .. 2 kWaves - 1 only FETCH (address arithmetic, the LDS-DMA pieces, the counted wait, the barrier) and
+// waves 0 .. kWaves - 1 only MULTIPLY (barrier, fragment reads, MFMAs, epilogue).  A DMA piece holds its wave's issue port for 60-200 cycles and the tap / address
 // arithmetic in front of it for a few dozen more; in the one-role kernel that is time the same wave's MFMAs are not being issued (a wave issues in order), and
 // with 3-4 waves per SIMD the others cover it only partly: tools/hip/mfma_f32_rate.hip measures the bare skeleton at 0.66 / 0.77 / 0.82 of the fp32 MFMA peak
 // with 1 / 2 / 4 workgroups per CU, and the same skeleton with roles at 0.80 / 0.89 / 0.89 (profiles/r05_mfma_f32_rate_roles.txt).  Same tiles, same LDS
-// contents, same K order: the same bits as the one-role kernel.  Instantiated for the fp32 tiles (conv_igemm_f32.hip, tactic ws == 6: the tuner takes it on the
+// contents, same K order: the same bits as the one-role kernel.  Instantiated for the fp32 tiles (conv_igemm_f32.hip, tactic WS_F32_ROLES: the tuner takes it on the
 // 80-wide detect-head layers, -8..-16 % there).  On the fp16 128-row tiles it was measured too: -3..-17 % on small maps alone, nothing on the three-context
 // bench line (profiles/r05_fp16_roles_*) - not instantiated there.
-template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2, int WN = 1, int NSTO = 0, bool PRE = false, int NW = 4, bool RS = false, bool UP = false,
-          bool ONE = false, bool F32 = false, bool ROLES = false>
-__device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_bytes, unsigned w_bytes, const int m0, const int n0, int dbg_flags,
-                                                char* __restrict__ smem) {
-    const int dbg = TRTX_DBG(dbg_flags);
+template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2, bool RS = false, bool UP = false, bool ONE = false, bool F32 = false, bool ROLES = false>
+__device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_bytes, unsigned w_bytes, const int m0, const int n0, char* __restrict__ smem) {
     TRTX_MARK(0);
     constexpr int BN = 16 * NFRAG;
-    constexpr int WM = NW / WN;                    // waves along M (NW = waves per workgroup: 4, or 8 for the large-GEMM tile)
-    constexpr int NFW = NFRAG / WN;                // 16-column fragments per wave
-    static_assert(NFRAG % WN == 0 && (WN == 1 || WN == 2), "wave grid");
-    constexpr int BM = WM * 16 * MI;               // rows per tile: every wave owns 16 * MI of them
+    constexpr int BM = kWaves * 16 * MI;               // rows per tile: every wave owns 16 * MI of them
     constexpr int WR = 16 * MI;                    // rows per wave
     constexpr int ROW_B = BKT * 2;                 // bytes per LDS row
     constexpr int CH = BKT / 8;                    // 16-byte chunks per row
     constexpr int RPI = 64 / CH;                   // rows filled by one wave-instruction (16 / 8)
-    constexpr int A_LOADS = BM / (NW * RPI);       // per wave per k-step (2 / 4)
-    constexpr int B_PASSES = (BN + NW * RPI - 1) / (NW * RPI);
-    constexpr int B_ROWS = B_PASSES * NW * RPI;    // rows beyond BN are dummy targets
+    constexpr int A_LOADS = BM / (kWaves * RPI);       // per wave per k-step (2 / 4)
+    constexpr int B_PASSES = (BN + kWaves * RPI - 1) / (kWaves * RPI);
+    constexpr int B_ROWS = B_PASSES * kWaves * RPI;    // rows beyond BN are dummy targets
     constexpr int A_BYTES = BM * ROW_B;
     constexpr int STAGE_BYTES = A_BYTES + B_ROWS * ROW_B;
     constexpr int LOADS_PER_TILE = A_LOADS + B_PASSES;
     constexpr int KSUB = BKT / 32;                 // MFMA k-slices per k-step
-    constexpr int NST = RS ? 2 : NSTO ? NSTO : (BKT == 64 ? 2 : 3);  // pipeline stages (64-wide stages are double-buffered to keep occupancy)
-    constexpr int EPI_BYTES = NW * 16 * (16 * NFW * 4 + 16);   // the epilogue's wave-private staging tiles (conv_epilogue)
+    constexpr int NST = RS ? 2 : (BKT == 64 ? 2 : 3);  // pipeline stages (64-wide stages are double-buffered to keep occupancy)
+    constexpr int EPI_BYTES = kWaves * 16 * (16 * NFRAG * 4 + 16);   // the epilogue's wave-private staging tiles (conv_epilogue)
     constexpr int LDS_BYTES = NST * STAGE_BYTES > EPI_BYTES ? NST * STAGE_BYTES : EPI_BYTES;
-    static_assert(LDS_BYTES == igemm_lds_bytes<NFRAG, BKT, MI, WN, NSTO, NW, RS>(), "the entry points allocate what the tile function uses");
+    static_assert(LDS_BYTES == igemm_lds_bytes<NFRAG, BKT, MI, RS>(), "the entry points allocate what the tile function uses");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool fetcher = ROLES && wave_all >= NW;            // wave-uniform
-    const int wave = ROLES ? (wave_all & (NW - 1)) : wave_all;   // a fetching wave fills the LDS rows the one-role kernel's wave of the same index fills
-    static_assert(!ROLES || (!RS && NW == 4), "roles: LDS-DMA operands, 4 + 4 waves");
+    const bool fetcher = ROLES && wave_all >= kWaves;            // wave-uniform
+    const int wave = ROLES ? (wave_all & (kWaves - 1)) : wave_all;   // a fetching wave fills the LDS rows the one-role kernel's wave of the same index fills
+    static_assert(!ROLES || !RS, "roles: LDS-DMA operands, 4 + 4 waves");
 
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.in), 0, in_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wgt), 0, w_bytes, 0x00020000);
@@ -517,7 +462,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     unsigned a_up[UP ? A_LOADS : 1];   // UP: byte offset of (n, ho >> 1, wo >> 1, channel lchunk*8) in the half-resolution tensor
 #pragma unroll
     for (int i = 0; i < A_LOADS; ++i) {
-        const int m = m0 + (NW * i + wave) * RPI + lrow;
+        const int m = m0 + (kWaves * i + wave) * RPI + lrow;
         const bool ok = m < p.M;
         const int mm = ok ? m : 0;
         // quotients are small (image index, output row): a float estimate is within +-1, fixed up exactly
@@ -542,15 +487,15 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     unsigned b_off[B_PASSES];
 #pragma unroll
     for (int j = 0; j < B_PASSES; ++j) {
-        const int row = (NW * j + wave) * RPI + lrow;
+        const int row = (kWaves * j + wave) * RPI + lrow;
         b_off[j] = row < BN ? (unsigned)(((n0 + row) * p.Kpad + lchunk * 8) * 2) : kOOB;  // weights < 2 GB
     }
     // Column tiles that are not a whole number of DMA passes (BN = 16 / 32 / 80 with 32-wide steps, 80 with 64-wide ones): in the LAST pass
     // some waves' pieces lie wholly beyond the tile - rows nobody reads.  Those waves skip the instruction (round 4: a DMA piece costs its
     // wave 60-185 cycles of issue and the loop is bound by exactly that; on the 80-wide detect-head arms three of four waves issued a
     // dead piece per k-step) and wait on one load fewer per tile in flight.  Same LDS contents wherever anything is read: same bits.
-    constexpr bool B_PARTIAL = !RS && (BN % (NW * RPI) != 0);
-    const bool b_last_live = !B_PARTIAL || (NW * (B_PASSES - 1) + wave) * RPI < BN;   // wave-uniform
+    constexpr bool B_PARTIAL = !RS && (BN % (kWaves * RPI) != 0);
+    const bool b_last_live = !B_PARTIAL || (kWaves * (B_PASSES - 1) + wave) * RPI < BN;   // wave-uniform
 
     // wave-uniform walk over K.  TPS == 1: the (tap, channel offset, byte offset) of k-step e is precomputed by lane e & 63 into
     // two VGPRs (a 64-step window, rebuilt every 64 steps) and fetched with v_readlane: the kernel is instruction-issue bound
@@ -607,14 +552,14 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     intx4 ra[RS ? A_LOADS : 1], rb[RS ? B_PASSES : 1];   // RS: the operand tile in flight (registers)
     auto issue_tile = [&](int stage) {
         char* sbase = smem + stage * STAGE_BYTES;
-        const bool live = s_kt < nk && !(dbg & 1);
+        const bool live = s_kt < nk;
         if constexpr (ONE) {
             const unsigned koff = (unsigned)s_kt * (unsigned)(BKT * 2);   // scalar
 #pragma unroll
             for (int i = 0; i < A_LOADS; ++i) {
                 const unsigned voff = a_base[i] + koff;
                 if constexpr (RS) ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(sbase + (NW * i + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
+                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(sbase + (kWaves * i + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
             }
         } else if (TPS == 1) {
             const unsigned add = (unsigned)__builtin_amdgcn_readlane((int)t_add, s_kt & 63);
@@ -629,7 +574,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
                 unsigned voff = ok ? a_base[i] + add : kOOB;
                 if constexpr (UP) voff = from_up ? (ok ? a_up[i] + (unsigned)uc * 2u : kOOB) : voff;   // 1x1: `add` is the channel offset alone
                 if constexpr (RS) ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, voff, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_ptr_t)(sbase + (NW * i + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
+                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_ptr_t)(sbase + (kWaves * i + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
             }
         } else {
             const int r = tsel ? s_r[TPS - 1] : s_r[0];
@@ -640,15 +585,15 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
                 const bool ok = ((a_rows[i] >> r) & (a_cols[i] >> q) & 1u) && s_uc < cmax && live;
                 const unsigned voff = ok ? a_base[i] + add : kOOB;
                 if constexpr (RS) ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(sbase + (NW * i + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
+                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(sbase + (kWaves * i + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
             }
         }
 #pragma unroll
         for (int j = 0; j < B_PASSES; ++j) {
             if (B_PARTIAL && j == B_PASSES - 1 && !b_last_live) continue;   // this wave's piece of the last pass lies beyond the column tile
-            const unsigned voff = ONE ? b_off[j] : ((s_kt < nk && !(dbg & 2)) ? b_off[j] : kOOB);
+            const unsigned voff = ONE ? b_off[j] : (s_kt < nk ? b_off[j] : kOOB);
             if constexpr (RS) rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, voff, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_ptr_t)(sbase + A_BYTES + (NW * j + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
+            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_ptr_t)(sbase + A_BYTES + (kWaves * j + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
             b_off[j] += BKT * 2;  // kOOB stays out of range for any K < 2^30
         }
         ++s_kt;
@@ -668,18 +613,18 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     auto commit = [&](int stage) {
         char* sbase = smem + stage * STAGE_BYTES + lane * 16;
 #pragma unroll
-        for (int i = 0; i < A_LOADS; ++i) *reinterpret_cast<intx4*>(sbase + (NW * i + wave) * RPI * ROW_B) = ra[i];
+        for (int i = 0; i < A_LOADS; ++i) *reinterpret_cast<intx4*>(sbase + (kWaves * i + wave) * RPI * ROW_B) = ra[i];
 #pragma unroll
-        for (int j = 0; j < B_PASSES; ++j) *reinterpret_cast<intx4*>(sbase + A_BYTES + (NW * j + wave) * RPI * ROW_B) = rb[j];
+        for (int j = 0; j < B_PASSES; ++j) *reinterpret_cast<intx4*>(sbase + A_BYTES + (kWaves * j + wave) * RPI * ROW_B) = rb[j];
     };
 
-    floatx4 acc[MI][NFW];
-    intx4 acci[MI][NFW];
-    floatx4 part[F32 ? MI : 1][F32 ? NFW : 1];   // fp32: the running k-step's partial sum (two-level sum, see compute())
+    floatx4 acc[MI][NFRAG];
+    intx4 acci[MI][NFRAG];
+    floatx4 part[F32 ? MI : 1][F32 ? NFRAG : 1];   // fp32: the running k-step's partial sum (two-level sum, see compute())
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < NFW; ++j) {
+        for (int j = 0; j < NFRAG; ++j) {
             acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
             acci[i][j] = intx4{0, 0, 0, 0};
             if constexpr (F32) part[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -689,8 +634,8 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
         // the fetch passes under the first tiles' round trip to memory instead of standing, a full L2 latency, in front of the epilogue's first store
         if (p.bias) {
 #pragma unroll
-            for (int j = 0; j < NFW; ++j) {
-                const floatx4 b4 = *reinterpret_cast<const floatx4*>(p.bias + n0 + (WN == 1 ? 0 : (wave & 1)) * NFW * 16 + j * 16 + (lane >> 4) * 4);   // [Cout_pad] values
+            for (int j = 0; j < NFRAG; ++j) {
+                const floatx4 b4 = *reinterpret_cast<const floatx4*>(p.bias + n0 + j * 16 + (lane >> 4) * 4);   // [Cout_pad] values
 #pragma unroll
                 for (int i = 0; i < MI; ++i) acc[i][j] = b4;
             }
@@ -703,10 +648,8 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     int f_off[KSUB];
 #pragma unroll
     for (int h = 0; h < KSUB; ++h) f_off[h] = frow * ROW_B + ((((lane >> 4) + 4 * h) ^ fswz) * 16);
-    const int wave_m = WN == 1 ? wave : (wave >> 1), wave_n = WN == 1 ? 0 : (wave & 1);
-    static_assert(NW == 4 || NW == 8, "waves per workgroup");
-    const int a_frag = wave_m * WR * ROW_B;
-    const int b_frag = A_BYTES + wave_n * NFW * 16 * ROW_B;
+    const int a_frag = wave * WR * ROW_B;
+    const int b_frag = A_BYTES;
 
     auto compute = [&](int stage) {
         const char* sb = smem + stage * STAGE_BYTES;
@@ -726,18 +669,18 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
             // BKT == 64: a 32-channel step = 128-byte rows, whole cache lines per row (half the line requests per byte of the fill path - what bounds this
             // kernel, DESIGN 5 "round 5"); computed as its two 16-channel halves one after the other, each with its own partial: the arithmetic of two
             // 16-channel steps, so both step widths return the same bits.
-            static_assert(!F32 || (!I8 && !PRE), "fp32 operands");
+            static_assert(!F32 || !I8, "fp32 operands");
             __builtin_amdgcn_s_setprio(1);   // a wave in its MFMA phase goes first: the matrix pipe is what this kernel is priced on, and co-resident waves in
                                              // their set-up / epilogue (VALU, transcendentals on the same issue port) otherwise open bubbles in it
 #pragma unroll
             for (int h = 0; h < KSUB; ++h) {
-                floatx4 af[MI], bf[NFW];
+                floatx4 af[MI], bf[NFRAG];
 #pragma unroll
                 for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const floatx4*>(sb + a_frag + i * 16 * ROW_B + f_off[h]);
 #pragma unroll
-                for (int j = 0; j < NFW; ++j) bf[j] = *reinterpret_cast<const floatx4*>(sb + b_frag + j * 16 * ROW_B + f_off[h]);
+                for (int j = 0; j < NFRAG; ++j) bf[j] = *reinterpret_cast<const floatx4*>(sb + b_frag + j * 16 * ROW_B + f_off[h]);
 #pragma unroll
-                for (int j = 0; j < NFW; ++j)
+                for (int j = 0; j < NFRAG; ++j)
 #pragma unroll
                     for (int i = 0; i < MI; ++i) {
                         acc[i][j] += part[i][j];
@@ -746,7 +689,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
 #pragma unroll
                 for (int s4 = 1; s4 < 4; ++s4)
 #pragma unroll
-                    for (int j = 0; j < NFW; ++j)
+                    for (int j = 0; j < NFRAG; ++j)
 #pragma unroll
                         for (int i = 0; i < MI; ++i) part[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j][s4], af[i][s4], part[i][j], 0, 0, 0);
             }
@@ -760,43 +703,22 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
 #pragma unroll
                 for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const intx4*>(sb + a_frag + i * 16 * ROW_B + f_off[h]);
 #pragma unroll
-                for (int j = 0; j < NFW; ++j) {
+                for (int j = 0; j < NFRAG; ++j) {
                     const intx4 bf = *reinterpret_cast<const intx4*>(sb + b_frag + j * 16 * ROW_B + f_off[h]);
 #pragma unroll
                     for (int i = 0; i < MI; ++i) acci[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bf, af[i], acci[i][j], 0, 0, 0);
                 }
-            } else if constexpr (!PRE) {
+            } else {
                 half8 af[MI];
 #pragma unroll
                 for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const half8*>(sb + a_frag + i * 16 * ROW_B + f_off[h]);
 #pragma unroll
-                for (int j = 0; j < NFW; ++j) {
+                for (int j = 0; j < NFRAG; ++j) {
                     const half8 bf = *reinterpret_cast<const half8*>(sb + b_frag + j * 16 * ROW_B + f_off[h]);
 #pragma unroll
                     for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf, af[i], acc[i][j], 0, 0, 0);
                 }
             }
-        }
-        if constexpr (PRE && !I8) {
-            // every fragment read of the k-step is issued before its first MFMA (B fragment 0 first, then the A fragments, then the
-            // rest): the LDS returns in order, so the first MFMA waits for two reads and the later ones find theirs landed - with one
-            // workgroup per CU there is no other wave to cover a read issued right before its use
-            half8 af[KSUB][MI], bf[KSUB][NFW];
-#pragma unroll
-            for (int h = 0; h < KSUB; ++h) {
-                bf[h][0] = *reinterpret_cast<const half8*>(sb + b_frag + f_off[h]);
-#pragma unroll
-                for (int i = 0; i < MI; ++i) af[h][i] = *reinterpret_cast<const half8*>(sb + a_frag + i * 16 * ROW_B + f_off[h]);
-#pragma unroll
-                for (int j = 1; j < NFW; ++j) bf[h][j] = *reinterpret_cast<const half8*>(sb + b_frag + j * 16 * ROW_B + f_off[h]);
-            }
-            __builtin_amdgcn_sched_barrier(0);   // the scheduler otherwise sinks every read next to its MFMA again (two live B fragments)
-#pragma unroll
-            for (int h = 0; h < KSUB; ++h)
-#pragma unroll
-                for (int j = 0; j < NFW; ++j)
-#pragma unroll
-                    for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[h][j], af[h][i], acc[i][j], 0, 0, 0);
         }
     };
 
@@ -818,7 +740,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
         TRTX_STAMP(2, kt);                                                    \
         issue_tile(((S) + NST - 1) % NST);                                    \
         TRTX_STAMP(3, kt);                                                    \
-        if (!(dbg & 4)) compute(S);                                           \
+        compute(S);                                                           \
         TRTX_STAMP(4, kt);                                                    \
     }
 
@@ -864,22 +786,22 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
         issue_tile(0);
         commit(0);
         issue_tile(0);
-        for (int kt = 0; !(dbg & 16);) {
+        for (int kt = 0;;) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if (!(dbg & 4)) compute(kt & 1);
+            compute(kt & 1);
             commit((kt + 1) & 1);
             issue_tile(0);
             if (++kt == nk) break;
         }
     } else {
-    // NST - 1 tiles in flight (two normally; the deep variants of the short, latency-bound layers keep five), then one k-step per stage in turn
+    // NST - 1 tiles in flight, then one k-step per stage in turn
 #pragma unroll
     for (int st = 0; st < NST - 1; ++st) {
         issue_tile(st);
         if (st == 0) TRTX_MARK(1);
     }
-    for (int kt = 0; !(dbg & 16);) {
+    for (int kt = 0;;) {
         bool done = false;
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
@@ -895,38 +817,36 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TRTX_MARK(2);
 
-    if (dbg & 8) return;
     if constexpr (F32) {
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
-            for (int j = 0; j < NFW; ++j) acc[i][j] += part[i][j];   // the last step's partial
-        conv_epilogue_f32<NFW, MI>(p, acc, lane, n0 + wave_n * NFW * 16, [&](int t) {
+            for (int j = 0; j < NFRAG; ++j) acc[i][j] += part[i][j];   // the last step's partial
+        conv_epilogue_f32<NFRAG, MI>(p, acc, lane, n0, [&](int t) {
             const int m = m0 + t;
             return m < p.M ? m : -1;
-        }, wave_m * WR);
+        }, wave * WR);
     } else {
-    conv_epilogue<NFW, MI, I8, LDS_BYTES, NW>(p, acc, acci, smem, wave, lane, n0 + wave_n * NFW * 16, [&](int t) {
+    conv_epilogue<NFRAG, MI, I8, LDS_BYTES>(p, acc, acci, smem, wave, lane, n0, [&](int t) {
         const int m = m0 + t;
         return m < p.M ? m : -1;
-    }, wave_m * WR);
+    }, wave * WR);
     }
     TRTX_MARK(3);
 }
 
-template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2, int WN = 1, int NSTO = 0, bool PRE = false, int NW = 4, bool RS = false, bool UP = false,
-          bool ONE = false, bool F32 = false, bool ROLES = false>
-__global__ __launch_bounds__(NW * 64 * (ROLES ? 2 : 1)) void conv_igemm_f16_kernel(const ConvArgs p, unsigned in_bytes, unsigned w_bytes, int tiles_n,
-                                                             int total_tiles, int xcd_chunk, int dbg_flags) {
-    __shared__ __attribute__((aligned(16))) char smem[igemm_lds_bytes<NFRAG, BKT, MI, WN, NSTO, NW, RS>()];   // up to 144 KB of the CU's 160 KB
+template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2, bool RS = false, bool UP = false, bool ONE = false, bool F32 = false, bool ROLES = false>
+__global__ __launch_bounds__(kWaves * 64 * (ROLES ? 2 : 1)) void conv_igemm_f16_kernel(const ConvArgs p, unsigned in_bytes, unsigned w_bytes, int tiles_n,
+                                                             int total_tiles, int xcd_chunk) {
+    __shared__ __attribute__((aligned(16))) char smem[igemm_lds_bytes<NFRAG, BKT, MI, RS>()];
     int tile = blockIdx.x;
     if (xcd_chunk) {  // XCD-aware order: id -> (xcd = id % 8, slot = id / 8) -> contiguous tile range per XCD
         tile = (tile & 7) * xcd_chunk + (tile >> 3);
         if (tile >= total_tiles) return;
     }
-    const int m0 = (tile / tiles_n) * ((NW / WN) * 16 * MI);
+    const int m0 = (tile / tiles_n) * (kWaves * 16 * MI);
     const int n0 = (tile % tiles_n) * (16 * NFRAG);
-    conv_igemm_tile<NFRAG, BKT, TPS, I8, MI, WN, NSTO, PRE, NW, RS, UP, ONE, F32, ROLES>(p, in_bytes, w_bytes, m0, n0, dbg_flags, smem);
+    conv_igemm_tile<NFRAG, BKT, TPS, I8, MI, RS, UP, ONE, F32, ROLES>(p, in_bytes, w_bytes, m0, n0, smem);
 }
 
 // Several INDEPENDENT convolutions in one launch (round 4).  The YOLOv8 detect head is six chains of depth three over
@@ -949,8 +869,8 @@ struct ConvGroupArgs {
     ConvArgs p[kMaxConvGroup];
 };
 template <int NFRAG, int BKT, bool RS, bool ONE, bool I8 = false>   // I8 (round 5): int8 operands - the members of an INT8 plan's sibling layers
-__global__ __launch_bounds__(256) void conv_igemm_group_f16_kernel(const ConvGroupArgs g, int dbg_flags) {
-    __shared__ __attribute__((aligned(16))) char smem[igemm_lds_bytes<NFRAG, BKT, 2, 1, 0, 4, RS>()];
+__global__ __launch_bounds__(256) void conv_igemm_group_f16_kernel(const ConvGroupArgs g) {
+    __shared__ __attribute__((aligned(16))) char smem[igemm_lds_bytes<NFRAG, BKT, 2, RS>()];
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     int pid = 0;
 #pragma unroll
@@ -961,7 +881,7 @@ __global__ __launch_bounds__(256) void conv_igemm_group_f16_kernel(const ConvGro
     const int tn = g.tiles_n[pid];
     const int m0 = (local / tn) * 128;
     const int n0 = (local % tn) * (16 * NFRAG);
-    conv_igemm_tile<NFRAG, BKT, 1, I8, 2, 1, 0, false, 4, RS, false, ONE>(g.p[pid], g.in_bytes[pid], g.w_bytes[pid], m0, n0, dbg_flags, smem);
+    conv_igemm_tile<NFRAG, BKT, 1, I8, 2, RS, false, ONE>(g.p[pid], g.in_bytes[pid], g.w_bytes[pid], m0, n0, smem);
 }
 
 }  // namespace

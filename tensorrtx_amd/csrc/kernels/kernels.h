@@ -15,6 +15,25 @@ inline size_t dtype_size(int dt) { return dt == DT_F16 ? 2 : (dt == DT_I8 ? 1 : 
 enum EwOp : int { EW_SUM = 0, EW_PROD = 1, EW_MAX = 2, EW_MIN = 3, EW_SUB = 4, EW_DIV = 5, EW_POW = 6 };
 enum PoolOp : int { POOL_MAX = 0, POOL_AVG = 1 };
 
+// Values of ConvArgs::t_ws / ConvTactic::ws: which kernel of the implicit-GEMM family runs the layer.  The numbers are stored in plans and tactic caches and
+// cross the C ABI (trtx_op_conv2d_tactics), so they stay what they are; the fields stay int.
+enum Ws : int {
+    WS_AUTO = 0,       // the weight-stationary kernel (conv_ws.hip) where it is supported, else the implicit-GEMM kernel
+    WS_OFF = 1,        // never the weight-stationary kernel
+    WS_ON = 2,         // the weight-stationary kernel asked for (still only where supported)
+    WS_PATCH = 3,      // the resident-patch 3x3 kernel (patch_tile.h)
+    WS_F32_REGS = 5,   // (fp32 launches) operands through registers
+    WS_F32_ROLES = 6,  // (fp32 launches) fetching + multiplying wave roles
+    WS_RES3 = 7,       // the resident-operand 3x3 kernel (conv_res.hip)
+    WS_RES1 = 8,       // ... and its 1x1 sibling
+};
+// Values of ConvArgs::t_wsk / ConvTactic::wsk: the wave-split-K variant (conv_igemm_wsk_f16_kernel)
+enum Wsk : int {
+    WSK_RULE = 0,  // by the static rule (few tiles, a long k-chain)
+    WSK_OFF = 1,   // never
+    WSK_ON = 2,    // wherever it exists
+};
+
 // One fused convolution launch.  Activations are NHWC; `in`/`out`/`residual` already point at the
 // first channel of the slice they address and ld_* is the channel stride of the underlying buffer.
 struct ConvArgs {
@@ -44,11 +63,9 @@ struct ConvArgs {
     float out_inv_scale, res_scale;
     // Tactic (see ConvTactic): 0 everywhere = the untuned dispatch.
     int bm;     // igemm rows per tile: 0 / 128, 64 or 256
-    int t_wsk;  // wave-split-K variant: 0 = by the static rule, 1 = never, 2 = wherever it exists
-    int t_ws;   // weight-stationary kernel: 0 = where supported, 1 = never, 2 = asked for (still only where supported); 5 = (fp32 launches) operands through registers; 6 = (fp32 launches) fetching + multiplying wave roles; 3 = the resident-patch 3x3; 7 / 8 = the resident-operand 3x3 / 1x1 kernels (conv_res.hip)
-                // kernel instead (conv_igemm.hip, builds with -DTRTX_EXPERIMENTAL_PATCH only)
+    int t_wsk;  // a Wsk value
+    int t_ws;   // a Ws value
     int t_rs;   // implicit-GEMM operands through registers (global -> VGPR -> ds_write) instead of LDS-DMA: 0 = no, 1 = yes (same bits)
-    int t_r3;   // 3x3 stride-1 row-reuse kernel (conv_igemm_r3_f16_kernel, only where it exists): 0 = no, 1 = three LDS stages, 2 = two
     // Folded nearest 2x upsample (conv_igemm main kernel, 1x1 stride-1 convolutions only): input channels [0, up_C) are not read from
     // `in` but from `up_in`, an NHWC fp16 tensor of HALF the resolution ([N][up_H][up_W][up_ld], H = 2 up_H, W = 2 up_W), at pixel
     // (h >> 1, w >> 1); channels >= up_C come from `in` as usual.  This is Upsample -> Concat -> Conv1x1 (YOLOv8 head, model.cpp:130-160)
@@ -68,8 +85,7 @@ struct ConvArgs {
 // the same with its tactics; here it happens at deserializeCudaEngine because plans store the network, not kernels).
 struct ConvTactic {
     int bn, bk, bm;  // column-tile width, k-step width, rows per tile
-    int wsk, ws;     // values of ConvArgs::t_wsk / t_ws
-    int r3;          // value of ConvArgs::t_r3
+    int wsk, ws;     // values of ConvArgs::t_wsk / t_ws (Wsk / Ws)
 };
 
 // Launch probe (IProfiler-style per-layer timing): while one is set for the calling thread, the first MFMA / stem convolution
@@ -115,13 +131,13 @@ bool conv_igemm_f32_supported(const ConvArgs& a);
 int32_t conv_igemm_f32(const ConvArgs& a, hipStream_t s);
 int conv_tactics_f32(const ConvArgs& a, ConvTactic* out, int max_out);   // (bn, bm) pairs; out[0] = the untuned choice; every pair returns the same bits
 void conv_pack_weights_igemm_f32(const float* w_kcrs, int cout, int cin, int kh, int kw, int cink, int kpad, int cout_pad, const float* ch_scale, float* packed);
-// Resident-operand 3x3 stride-1 kernel (conv_res.hip, round 6; tactic ConvArgs::t_ws == 7): persistent workgroups keep the layer's whole weight slab in LDS, two
+// Resident-operand 3x3 stride-1 kernel (conv_res.hip, round 6; tactic WS_RES3): persistent workgroups keep the layer's whole weight slab in LDS, two
 // role-alternating halves of 4 waves (k-loop | register epilogue + next patch fetch); same packed weights, same K order, same bits as the main kernel.
 // a[0..n): 1..kMaxConvGroup independent layers of one instantiation in one launch (a workgroup is bound to one of them).
 bool conv_res_possible(const ConvArgs& a);
 bool conv_res_group_possible(const ConvArgs* a, int n);
 int32_t conv_res_f16(const ConvArgs* a, int n, hipStream_t s);
-// ... and its 1x1 stride-1 sibling (tactic t_ws == 8): the column tile's weights resident in LDS, 16 independent waves per workgroup, the A operand global -> VGPR
+// ... and its 1x1 stride-1 sibling (tactic WS_RES1): the column tile's weights resident in LDS, 16 independent waves per workgroup, the A operand global -> VGPR
 bool conv_res1_possible(const ConvArgs& a);
 int32_t conv_res1_f16(const ConvArgs& a, hipStream_t s);
 // weight-stationary persistent kernel for small-channel 3x3 (stride 1, pad 1) and 1x1 layers (conv_ws.hip): weights in

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 
 namespace trtx {
@@ -22,18 +23,6 @@ inline int grid_for(long work) {
     long b = (work + kThreads - 1) / kThreads;
     if (b < 1) b = 1;
     return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
-
-__device__ __forceinline__ float act_f(float v, int act, float alpha) {
-    switch (act) {
-        case ACT_RELU: return v > 0.f ? v : 0.f;
-        case ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
-        case ACT_SILU: return v / (1.0f + expf(-v));
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
 }
 
 __device__ __forceinline__ float ew_f(float a, float b, int op) {
@@ -91,7 +80,7 @@ __global__ void ew_kernel(const float* __restrict__ a, const float* __restrict__
 
 __global__ void act_kernel(const float* __restrict__ in, float* __restrict__ out, int act, float alpha, long n) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        out[i] = act_f(in[i], act, alpha);
+        out[i] = act_exact(in[i], act, alpha);
 }
 
 // one thread per (outer, inner) pair, sequential over the (short) softmax axis

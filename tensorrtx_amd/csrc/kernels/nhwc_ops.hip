@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 
 namespace trtx {
@@ -41,18 +42,6 @@ __device__ __forceinline__ float to_f(T x) {
 template <typename T>
 __device__ __forceinline__ T from_f(float x) {
     return (T)x;
-}
-
-__device__ __forceinline__ float act_f(float v, int act, float alpha) {
-    switch (act) {
-        case ACT_RELU: return v > 0.f ? v : 0.f;
-        case ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
-        case ACT_SILU: return v / (1.0f + expf(-v));
-        case ACT_LEAKY: return v > 0.f ? v : v * alpha;
-        case ACT_TANH: return tanhf(v);
-        case ACT_MISH: return mish_ref(v);
-        default: return v;
-    }
 }
 
 __device__ __forceinline__ float ew_f(float a, float b, int op) {
@@ -271,7 +260,7 @@ __global__ void activation_kernel(const T* __restrict__ in, T* __restrict__ out,
         const Pack<T, V> x = *reinterpret_cast<const Pack<T, V>*>(in + px * ld_in + cv * V);
         Pack<T, V> o;
 #pragma unroll
-        for (int e = 0; e < V; ++e) o.v[e] = from_f<T>(act_f(to_f(x.v[e]), act, alpha));
+        for (int e = 0; e < V; ++e) o.v[e] = from_f<T>(act_exact(to_f(x.v[e]), act, alpha));
         *reinterpret_cast<Pack<T, V>*>(out + px * ld_out + cv * V) = o;
     }
 }
@@ -391,9 +380,9 @@ __global__ void conv_direct_kernel(const ConvArgs p) {
                 for (int c = 0; c < cin_g; ++c) acc = fmaf(to_f(ip[c]), wp[c], acc);
             }
         }
-        acc = act_f(acc, p.act1, p.alpha1);
+        acc = act_exact(acc, p.act1, p.alpha1);
         if (res) acc += to_f(res[m * p.ld_res + co]);
-        acc = act_f(acc, p.act2, p.alpha2);
+        acc = act_exact(acc, p.act2, p.alpha2);
         out[m * p.ld_out + co] = from_f<T>(acc);
     }
 }
@@ -432,7 +421,7 @@ __global__ void deconv_direct_kernel(const ConvArgs p) {
                 for (int c = 0; c < cin_g; ++c) acc = fmaf(to_f(ip[c]), wp[c], acc);
             }
         }
-        acc = act_f(acc, p.act1, p.alpha1);
+        acc = act_exact(acc, p.act1, p.alpha1);
         out[m * p.ld_out + co] = from_f<T>(acc);
     }
 }

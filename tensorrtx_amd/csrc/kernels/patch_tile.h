@@ -7,7 +7,7 @@ namespace trtx {
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
-// 3x3 stride-1 pad-1 variant with a RESIDENT INPUT PATCH ("patch", tactic ConvArgs::t_ws == 3; a product tactic since round 5).  The kernels
+// 3x3 stride-1 pad-1 variant with a RESIDENT INPUT PATCH ("patch", tactic ConvArgs::t_ws == WS_PATCH; a product tactic since round 5).  The kernels
 // above bring an A tile from global memory to LDS for every (tile, tap, channel slice): a 3x3 layer's input crosses the global -> LDS path
 // nine times per column tile, and on YOLOv8n / ResNet-50 that path - not HBM, not the MFMA pipe - is the largest term of a step
 // (tools/lds_fill_model.py: 5.6 GB per b32 step for 2.3 GB of HBM bytes).  Here an output tile is a TH x 16 block of ONE image, its
@@ -15,7 +15,7 @@ namespace {
 // their A fragments from it at shifted addresses, and only the weight tile of a k-step (BN x 32) streams through the three-stage ring:
 // per 128 output pixels and 64 -> 64 channels 30 + 73 KB instead of 147 + 73 KB through the fill path (16 rows: 27 + 37 per 128 pixels).
 // K is walked (tap, channel slice) as in the main kernel and every output element accumulates in the same order with the same MFMA: results
-// are bit-identical to the main kernel's (tests/test_gpu_conv.py treats it as one more exchangeable tile shape, ConvArgs::t_ws == 3).
+// are bit-identical to the main kernel's (tests/test_gpu_conv.py treats it as one more exchangeable tile shape, ConvArgs::t_ws == WS_PATCH).
 // All index arithmetic lives in patch_index.h and is replayed lane by lane on the CPU (tests/test_patch_index_cpu.py).
 // Written at the end of round 4 without GPU minutes (CPU replay of its index arithmetic, ISA scan); first run in round 5 (profiles/r05_patch_shape_ab.txt,
 // r05_patch_r3_first_run.txt): bit-identical to the main kernel on every shape on the first launch, 64 -> 64 @ 80x80 34 vs 39-44 us, 64 -> 80 42 vs 48-53,

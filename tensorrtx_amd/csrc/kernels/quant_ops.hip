@@ -8,12 +8,12 @@
 #include <algorithm>
 
 #include "../common.h"
+#include "act.h"
 #include "kernels.h"
 
 namespace trtx {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr int kBins = 8192;   // == runtime/int8.h kCalibBins (32 KB of LDS per workgroup)
 
 // max |x| over [pixels][C] (channel stride ld), C % 8 == 0: one atomicMax of the float bits (non-negative floats order as ints)

@@ -88,8 +88,9 @@ static bool g_force_tactic = false;
 static ConvTactic g_forced{};
 
 extern "C" int32_t trtx_op_conv_force_tactic(const int32_t* t) {
+    if (t && t[5] != 0) return TRTX_ERR_UNSUPPORTED;   // the sixth word (the row-reuse kernel's, which left the library) is always 0
     g_force_tactic = t != nullptr;
-    if (t) g_forced = ConvTactic{t[0], t[1], t[2], t[3], t[4], t[5]};
+    if (t) g_forced = ConvTactic{t[0], t[1], t[2], t[3], t[4]};
     return TRTX_OK;
 }
 
@@ -102,7 +103,7 @@ extern "C" int32_t trtx_op_conv2d_tactics(int N, int H, int W, int Cin, int ld_i
     const int n = conv_tactics(a, t.data(), max_out);
     for (int i = 0; i < n; ++i) {
         out6[6 * i + 0] = t[i].bn; out6[6 * i + 1] = t[i].bk; out6[6 * i + 2] = t[i].bm; out6[6 * i + 3] = t[i].wsk; out6[6 * i + 4] = t[i].ws;
-        out6[6 * i + 5] = t[i].r3;
+        out6[6 * i + 5] = 0;   // kept by the ABI
     }
     return n;
 }

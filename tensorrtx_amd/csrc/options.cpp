@@ -42,8 +42,6 @@ Options read_options() {
     o.roialign_fold_stride = !env_is("TRTX_ROIALIGN_FOLD_STRIDE", 0);
     o.profile_kernel_events = !env_set("TRTX_PROFILE_NO_KERNEL_EVENTS");
     o.op_reps = env_int("TRTX_OP_REPS", 1);
-    o.conv_dbg = env_int("TRTX_CONV_DBG", 0);
-    o.f32_stages = env_int("TRTX_F32_NST", 0);
     return o;
 }
 

@@ -37,8 +37,6 @@ struct Options {
     bool roialign_fold_stride = true;   // TRTX_ROIALIGN_FOLD_STRIDE=0: RoIAlign emits all 14 x 14 bins
     bool profile_kernel_events = true;  // TRTX_PROFILE_NO_KERNEL_EVENTS=1: trtx_context_profile without per-launch start / stop events
     int op_reps = 1;             // TRTX_OP_REPS=<n>: timing tools, launches per single-op C-ABI call
-    int conv_dbg = 0;            // TRTX_CONV_DBG=<mask>: ablation builds (-DTRTX_CONV_ABLATE) only; the product kernels ignore it
-    int f32_stages = 0;          // TRTX_F32_NST: ablation builds only
 };
 
 // the switches as the environment has them NOW (lowering and engine creation: tests flip them inside one process)

@@ -492,7 +492,7 @@ Ancestors ancestors(const Plan& plan, const std::vector<std::vector<int>>& deps,
 // exactly as its own launch computes it: bit-identical outputs.  TRTX_GROUP_CONVS=0 keeps one launch per convolution (A/B, tests).
 void group_convs(Plan& plan, const PassInputs& e) {
     if (e.dt != DT_F16 || CalibrationLowering::active()) return;   // (INT8 plans group too since round 5: members of one storage mix - same in / out / shortcut int8 flags)
-    const bool mark_only = !e.opt.group_convs;   // TRTX_GROUP_CONVS=0: one launch per convolution, but the would-be members keep the group's K order (t_wsk = 1): same bits
+    const bool mark_only = !e.opt.group_convs;   // TRTX_GROUP_CONVS=0: one launch per convolution, but the would-be members keep the group's K order (WSK_OFF): same bits
     const int n = (int)plan.ops.size();
     if (n < 2 || n > 4096) return;
     const std::vector<std::vector<int>> deps = op_dependencies(plan);   // in the current order
@@ -601,7 +601,7 @@ void group_convs(Plan& plan, const PassInputs& e) {
     if (mark_only) {
         for (const auto& mem : groups)
             for (int m : mem) {
-                plan.ops[m].conv.t_wsk = 1;
+                plan.ops[m].conv.t_wsk = WSK_OFF;
                 plan.ops[m].conv.k_pinned = 1;   // ... and the tuner keeps it that way (its candidates for a pinned layer all walk K as the main kernel does)
             }
         return;
@@ -641,7 +641,7 @@ void group_convs(Plan& plan, const PassInputs& e) {
             // ONE summation order per member, grouped or not: the grouped kernel walks K as the main kernel does, so the member's own launch -
             // the fallback the executor takes at a batch where the members no longer share an instantiation, and TRTX_GROUP_CONVS=0 - must not pick
             // the wave-split-K variant (different K order: the same engine rounded differently depending on batch size and on the switch)
-            mo.conv.t_wsk = 1;
+            mo.conv.t_wsk = WSK_OFF;
             mo.conv.k_pinned = 1;
             g.group.push_back(mo);
             g.name += (g.name.empty() ? "" : " + ") + mo.name;

@@ -100,7 +100,8 @@ void cache_load_locked() {
         for (int i = 0; i < 28 && ok; ++i) ok = fscanf(f, "%d", &k.v[i]) == 1;
         for (int i = 0; i < 8 && ok; ++i) ok = fscanf(f, "%d", &t[i]) == 1;
         if (!ok) break;
-        g_choice[k] = Choice{ConvTactic{t[0], t[1], t[2], t[3], t[4], t[5]}, {t[6], t[7]}};
+        if (t[5] != 0) continue;   // the sixth word named the row-reuse kernel, which left the library: such a line matches no candidate
+        g_choice[k] = Choice{ConvTactic{t[0], t[1], t[2], t[3], t[4]}, {t[6], t[7]}};
     }
     fclose(f);
 }
@@ -111,20 +112,20 @@ void cache_append_locked(const SigKey& k, const Choice& c) {
     if (!f) return;
     if (ftell(f) == 0) fprintf(f, "%s\n", kCacheHeader);
     for (int i = 0; i < 28; ++i) fprintf(f, "%d ", k.v[i]);
-    fprintf(f, "%d %d %d %d %d %d %d %d\n", c.t.bn, c.t.bk, c.t.bm, c.t.wsk, c.t.ws, c.t.r3, c.ns[0], c.ns[1]);
+    fprintf(f, "%d %d %d %d %d %d %d %d\n", c.t.bn, c.t.bk, c.t.bm, c.t.wsk, c.t.ws, 0, c.ns[0], c.ns[1]);   // (the sixth word: always 0, kept by the format)
     fclose(f);
 }
 
 bool same(const ConvTactic& a, const ConvTactic& b) {
-    return a.bn == b.bn && a.bk == b.bk && a.bm == b.bm && a.wsk == b.wsk && a.ws == b.ws && a.r3 == b.r3;
+    return a.bn == b.bn && a.bk == b.bk && a.bm == b.bm && a.wsk == b.wsk && a.ws == b.ws;
 }
 
 std::string tactic_name(const ConvTactic& t) {
     std::ostringstream o;
-    if (t.ws == 2) {
+    if (t.ws == WS_ON) {
         o << "ws";
     } else {
-        o << (t.r3 == 2 ? "r3s2" : (t.r3 ? "r3" : (t.wsk == 2 ? "wsk" : (t.ws == 3 ? "patch" : (t.ws == 7 ? "res3" : (t.ws == 8 ? "res1" : (t.ws == 5 ? "igemm/regs" : (t.ws == 6 ? "igemm/roles" : "igemm")))))))) << " " << (t.wsk == 2 ? 64 : t.bm) << "x" << t.bn << "x" << t.bk;
+        o << (t.wsk == WSK_ON ? "wsk" : (t.ws == WS_PATCH ? "patch" : (t.ws == WS_RES3 ? "res3" : (t.ws == WS_RES1 ? "res1" : (t.ws == WS_F32_REGS ? "igemm/regs" : (t.ws == WS_F32_ROLES ? "igemm/roles" : "igemm")))))) << " " << (t.wsk == WSK_ON ? 64 : t.bm) << "x" << t.bn << "x" << t.bk;
     }
     return o.str();
 }
@@ -185,8 +186,8 @@ int32_t tune_engine(trtx_engine* e, bool time_now) {
             int pick = 0;
             int32_t ns[2] = {-1, -1};
             for (const Network::TacticEntry& te : stored) {
-                if (memcmp(te.sig, it.key.v, sizeof(te.sig)) != 0) continue;
-                const ConvTactic want{te.tac[0], te.tac[1], te.tac[2], te.tac[3], te.tac[4], te.tac[5]};
+                if (memcmp(te.sig, it.key.v, sizeof(te.sig)) != 0 || te.tac[5] != 0) continue;   // (a non-zero sixth word matches no candidate)
+                const ConvTactic want{te.tac[0], te.tac[1], te.tac[2], te.tac[3], te.tac[4]};
                 for (int i = 0; i < it.n; ++i)
                     if (same(it.cand[i], want)) pick = i;
                 ns[0] = te.ns[0];
@@ -274,7 +275,7 @@ int32_t tune_engine(trtx_engine* e, bool time_now) {
                 for (const Item& it : items) {
                     int pick = 0;
                     for (int i = 1; i < it.n; ++i)
-                        if (it.cand[i].bn == P.bn && it.cand[i].bm == P.bm && it.cand[i].bk == P.bk && it.cand[i].wsk == 1 && it.cand[i].ws == 1 && !it.cand[i].r3) pick = i;
+                        if (it.cand[i].bn == P.bn && it.cand[i].bm == P.bm && it.cand[i].bk == P.bk && it.cand[i].wsk == WSK_OFF && it.cand[i].ws == WS_OFF) pick = i;
                     hits += pick != 0;
                     conv_apply_tactic(&plan.ops[it.op].conv, it.cand[pick]);
                 }
@@ -291,7 +292,7 @@ int32_t tune_engine(trtx_engine* e, bool time_now) {
                 const Palette& P = palettes[best_p];
                 for (Item& it : items)
                     for (int i = 1; i < it.n; ++i)
-                        if (it.cand[i].bn == P.bn && it.cand[i].bm == P.bm && it.cand[i].bk == P.bk && it.cand[i].wsk == 1 && it.cand[i].ws == 1 && !it.cand[i].r3)
+                        if (it.cand[i].bn == P.bn && it.cand[i].bm == P.bm && it.cand[i].bk == P.bk && it.cand[i].wsk == WSK_OFF && it.cand[i].ws == WS_OFF)
                         {
                             std::swap(it.cand[0], it.cand[i]);
                             it.static_idx = i;
@@ -476,7 +477,7 @@ int32_t tune_engine(trtx_engine* e, bool time_now) {
             Network::TacticEntry te{};
             memcpy(te.sig, it.key.v, sizeof(te.sig));
             const ConvTactic& c = it.cand[pick];
-            const int32_t tv[6] = {c.bn, c.bk, c.bm, c.wsk, c.ws, c.r3};
+            const int32_t tv[6] = {c.bn, c.bk, c.bm, c.wsk, c.ws, 0};
             memcpy(te.tac, tv, sizeof(tv));
             te.ns[0] = ns[0];
             te.ns[1] = ns[1];

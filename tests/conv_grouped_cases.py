@@ -5,7 +5,9 @@ Reference and bound: torch fp64 on the fp16-rounded inputs with fp16-rounded wei
 fp32_bound(Out) + fp16_walk(1 site) with 9 * Cin_g + 2 terms (k * k * Cin_g products, the bias, the shortcut) and ONE fp16 site, the store of
 the fused result.  The weights are GENERATED on the fp16 grid, so that the MFMA kernel (fp16 weights) and the direct kernel (fp32 weights) multiply
 the same numbers and one reference serves both.  SiLU has a slope of at most 1.0998, so the fp32 part of the bound, an error of SiLU's argument, is
-carried as Out.amp = 0.1 x that part; |SiLU(z)| <= |z| keeps the magnitude."""
+carried as Out.amp = 0.1 x that part; |SiLU(z)| <= |z| keeps the magnitude.  LeakyReLU (slope 0.1f, the C ABI's and the builder's alpha here) has a
+slope of at most 1 and |leaky(z)| <= |z|: the bound of its argument holds for it, with one more term for the product z * 0.1f; the reference multiplies
+by the same float32 slope."""
 import math
 import zlib
 from dataclasses import dataclass
@@ -70,8 +72,14 @@ PATH_CASES = [
     GCase("g2_1x1_64to32", 128, 64, 2, 1, 9, 19, 2, what="<1, 4, 1>"),
     GCase("g2_1x1_64per", 128, 128, 2, 1, 9, 19, 2, what="<1, 4, 2>"),
 ]
+# A rare activation kind (the out-of-line branch of the kernel's activation) on both forms, at the shape of the path cases.
+RARE_ACT_CASES = [
+    GCase("g4_3x3_leaky", 64, 64, 4, 3, 9, 19, 2, act="leaky", what="<9, 1, 1>, LeakyReLU 0.1"),
+    GCase("g4_1x1_leaky", 64, 64, 4, 1, 9, 19, 2, act="leaky", what="<1, 1, 1>, LeakyReLU 0.1"),
+]
+LEAKY_ALPHA = 0.1
 ISSUE_CASES = list(CASES)
-CASES = CASES + PATH_CASES
+CASES = CASES + PATH_CASES + RARE_ACT_CASES
 BY_NAME = {c.name: c for c in CASES}
 
 
@@ -110,8 +118,10 @@ def reference(case):
         w, b = torch.from_numpy(d["w"]).double(), torch.from_numpy(d["b"]).double()
         z = F.conv2d(x, w, b, 1, case.pad, 1, case.groups)
         mag = F.conv2d(x.abs(), w.abs(), b.abs(), 1, case.pad, 1, case.groups)
-        n = case.k * case.k * case.cin_g + 2
+        n = case.k * case.k * case.cin_g + 2 + (case.act == "leaky")
         y = z * torch.sigmoid(z) if case.act == "silu" else z
+        if case.act == "leaky":
+            y = torch.where(z > 0, z, z * float(np.float32(LEAKY_ALPHA)))
         amp = 0.1 * (1e-5 + n * lc.U32) if case.act == "silu" else 0.0
         if case.res:
             r = torch.from_numpy(d["r"]).double()
@@ -135,6 +145,8 @@ def build_plan(case, fp16=True, max_batch=None):
         y = net.out(net.conv(x, d["w"], d["b"], 1, case.pad, groups=case.groups))
         if case.act == "silu":
             y = net.out(net.elementwise(y, net.out(net.activation(y, "sigmoid")), "prod"))
+        elif case.act == "leaky":
+            y = net.out(net.activation(y, "leaky", LEAKY_ALPHA))
         if case.res:
             y = net.out(net.elementwise(y, lc.nhwc(net, net.input("r", (case.Cout, case.H, case.W))), "sum"))
         if case.out_view:

@@ -21,7 +21,7 @@ def test_fp16_plan_marks_the_layer_grouped_with_its_whole_epilogue(case):
     ops = engine.describe_plan(plan, lowered=True)["ops"]
     c = _the_conv(plan)
     assert c.get("grouped") is True and not c["igemm"] and not c["stem"] and "dw" not in c, c
-    assert c["act1"] == (3 if case.act == "silu" else 0) and c["act2"] == 0 and c["residual"] == case.res
+    assert c["act1"] == {"silu": 3, "leaky": 4}.get(case.act, 0) and c["act2"] == 0 and c["residual"] == case.res
     assert not {o["kind"] for o in ops} & {"act_nhwc", "ew_nhwc"}, [o["kind"] for o in ops]
     if case.in_view:
         assert c["ld_in"] == case.in_view[1]

@@ -146,7 +146,12 @@ TACTIC_CASES = [
     (8, 160, 160, 16, 16, 3, 1, 1, "silu", True, "none"),     # YOLOv8n model.2.m.0.cv2 (+ shortcut): one column fragment, borders on every side, many fragments per wave
     (5, 50, 64, 16, 32, 3, 2, 1, "silu", False, "none"),      # stride 2 (model.1: 16 -> 32): output rows of 32 pixels, odd output height
     (3, 21, 48, 16, 16, 3, 1, 1, "none", False, "relu"),      # fewer fragments than waves on most workgroups
+    # the rare activation kinds (the out-of-line branch of the epilogue's activation) on the weight-stationary kernel: 32 -> 32, 3x3, a 19 x 17 map at the
+    # smallest batch at which that kernel is a candidate (it wants 1024 tiles of 64 pixels: six per image here) - asserted in the test
+    (171, 19, 17, 32, 32, 3, 1, 1, "leaky", True, "relu"),
+    (171, 19, 17, 32, 32, 3, 1, 1, "sigmoid", False, "none"),
 ]
+WS_RARE_ACT_CASES = TACTIC_CASES[-2:]
 
 
 def test_the_256x256_tile_chosen_at_the_build_batch_runs_at_a_smaller_batch(gpu):
@@ -199,6 +204,8 @@ def test_every_conv_tactic_is_the_same_convolution(gpu, case):
         assert (256, 64, 256, 1, 1, 0) in tactics   # conv_gemm256_possible
     if Cin == 16 and k == 3 and p == 1 and Wo % 16 == 0:
         assert any(t[4] == 8 for t in tactics), "the A-direct kernel's thin 3x3 form is a candidate for 16-channel 3x3 layers with whole 16-pixel output rows"
+    if case in WS_RARE_ACT_CASES:
+        assert any(t[4] == 2 for t in tactics), "the weight-stationary kernel is a candidate at this shape"
     exact = None
     try:
         for t in tactics:

@@ -15,27 +15,14 @@ __device__ int g_grid;
 #include "../../tensorrtx_amd/csrc/kernels/conv_igemm.hip"
 using namespace trtx;
 
-// variant 0: the host dispatch's default (128-row tile, four waves); 1: its 64-row tile (four waves of 16 rows, twice the workgroups);
-// 2: a 128-row tile on EIGHT waves of 16 rows (two waves per SIMD: half the epilogue items and DMA pieces per wave)
-template <int NFRAG, bool ONE>
-static void launch8(const ConvArgs& a) {
-    const int tiles_n = a.Cout_pad / (16 * NFRAG), total = ((a.M + 127) / 128) * tiles_n, chunk = (total + 7) / 8;
-    const unsigned in_bytes = (unsigned)((((size_t)a.N * a.H * a.W - 1) * a.ld_in + a.Cin) * 2), w_bytes = (unsigned)((size_t)a.Cout_pad * a.Kpad * 2);
-    hipLaunchKernelGGL((conv_igemm_f16_kernel<NFRAG, 32, 1, false, 1, 1, 0, false, 8, false, false, ONE>), dim3(chunk * 8), dim3(512), 0, 0, a, in_bytes, w_bytes, tiles_n, total, chunk, 0);
-}
-// variants 3 / 4: the default 128-row four-wave tile with SIX / EIGHT LDS stages (five / seven tiles in flight instead of two)
-template <int NFRAG, bool ONE, int NST>
-static void launch_deep(const ConvArgs& a) {
-    const int tiles_n = a.Cout_pad / (16 * NFRAG), total = ((a.M + 127) / 128) * tiles_n, chunk = (total + 7) / 8;
-    const unsigned in_bytes = (unsigned)((((size_t)a.N * a.H * a.W - 1) * a.ld_in + a.Cin) * 2), w_bytes = (unsigned)((size_t)a.Cout_pad * a.Kpad * 2);
-    hipLaunchKernelGGL((conv_igemm_f16_kernel<NFRAG, 32, 1, false, 2, 1, NST, false, 4, false, false, ONE>), dim3(chunk * 8), dim3(256), 0, 0, a, in_bytes, w_bytes, tiles_n, total, chunk, 0);
-}
+// variant 0: the host dispatch's default (128-row tile, four waves); 1: its 64-row tile (four waves of 16 rows, twice the workgroups).
+// (Variants 2-4 - eight waves, six / eight LDS stages - left with the template parameters they needed: profiles/r04_launch_anatomy.txt has their results.)
 static void run(const char* name, int N, int H, int Cin, int Cout, int k, int bk, int variant = 0) {
     ConvArgs a{};
     a.N = N; a.H = a.W = H; a.Cin = Cin; a.ld_in = Cin; a.Ho = a.Wo = H; a.Cout = Cout; a.ld_out = Cout;
     a.kh = a.kw = k; a.stride_h = a.stride_w = 1; a.pad_h = a.pad_w = k / 2; a.dil_h = a.dil_w = 1; a.groups = 1;
     a.bk = bk; a.CinK = Cin; a.K = k * k * Cin; a.Kpad = a.K; a.M = N * H * H; a.act1 = ACT_SILU;
-    a.bn = conv_igemm_pick_bn(Cout); a.Cout_pad = (Cout + a.bn - 1) / a.bn * a.bn; a.t_wsk = 1; a.t_ws = 1;
+    a.bn = conv_igemm_pick_bn(Cout); a.Cout_pad = (Cout + a.bn - 1) / a.bn * a.bn; a.t_wsk = WSK_OFF; a.t_ws = WS_OFF;
     void *in, *w, *out; float* bias;
     hipMalloc(&in, (size_t)a.M * Cin * 2); hipMalloc(&w, (size_t)a.Cout_pad * a.Kpad * 2); hipMalloc(&out, (size_t)a.M * Cout * 2); hipMalloc(&bias, a.Cout_pad * 4);
     hipMemset(in, 0x11, (size_t)a.M * Cin * 2); hipMemset(w, 0x11, (size_t)a.Cout_pad * a.Kpad * 2); hipMemset(bias, 0, a.Cout_pad * 4);
@@ -49,19 +36,8 @@ static void run(const char* name, int N, int H, int Cin, int Cout, int k, int bk
         hipDeviceSynchronize();
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
         hipEventRecord(e0);
-        if (variant == 2) {
-            if (a.bn == 128) { if (k == 1) launch8<8, true>(a); else launch8<8, false>(a); }
-            else { if (k == 1) launch8<4, true>(a); else launch8<4, false>(a); }
-        } else if (variant == 3) {
-            if (a.bn == 128) { if (k == 1) launch_deep<8, true, 6>(a); else launch_deep<8, false, 6>(a); }
-            else { if (k == 1) launch_deep<4, true, 6>(a); else launch_deep<4, false, 6>(a); }
-        } else if (variant == 4) {
-            if (a.bn == 128) { if (k == 1) launch_deep<8, true, 8>(a); else launch_deep<8, false, 8>(a); }
-            else { if (k == 1) launch_deep<4, true, 8>(a); else launch_deep<4, false, 8>(a); }
-        } else {
-            a.bm = variant == 1 ? 64 : 0;
-            conv_igemm_f16(a, 0);
-        }
+        a.bm = variant == 1 ? 64 : 0;
+        conv_igemm_f16(a, 0);
         hipEventRecord(e1); hipDeviceSynchronize();
         float ms; hipEventElapsedTime(&ms, e0, e1);
         if (rep < 2) continue;
@@ -86,7 +62,7 @@ static void run(const char* name, int N, int H, int Cin, int Cout, int k, int bk
 int main() {
     hipDeviceProp_t prop; hipGetDeviceProperties(&prop, 0);
     printf("# igemm_launch_anatomy on %s, clock64() stamps (shader clock, %d kHz reported)\n", prop.gcnArchName, prop.clockRate);
-    for (int v = 0; v < 5; ++v) {
+    for (int v = 0; v < 2; ++v) {
         run("model.9.cv1-like", 32, 20, 256, 128, 1, 32, v);
         run("C2f m.cv1 @20", 32, 20, 128, 128, 3, 32, v);
         run("C2f m.cv1 @40", 32, 40, 64, 64, 3, 32, v);

@@ -9,19 +9,16 @@ __device__ long long g_st[kWG][3][kPh][8];
 __device__ long long g_t0[kWG];
 #define PROBE_SLOT() ((int)blockIdx.x == 0 ? 0 : (int)blockIdx.x == 9 ? 1 : (int)blockIdx.x == 100 ? 2 : (int)blockIdx.x == 201 ? 3 : -1)
 #define TRTX_RES_STAMP(ph, i) do { const int s__ = PROBE_SLOT(); if (s__ >= 0 && (threadIdx.x & 255) == 0 && (ph) < kPh) g_st[s__][threadIdx.x >> 8][ph][i] = clock64(); } while (0)
-__device__ int g_ablate;
-#define TRTX_RES_ABLATE g_ablate
 #include "../../tensorrtx_amd/csrc/kernels/conv_res.hip"
 namespace trtx { LaunchProbe* conv_launch_probe() { return nullptr; } const Options& options() { static Options o; return o; } }
 using namespace trtx;
 
-static void run(const char* name, int N, int H, int Cin, int Cout, bool res, bool flushed = true, int ablate = 0) {
-    hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &ablate, 4);
+static void run(const char* name, int N, int H, int Cin, int Cout, bool res, bool flushed = true) {
     ConvArgs a{};
     a.N = N; a.H = a.W = H; a.Cin = Cin; a.ld_in = Cin; a.Ho = a.Wo = H; a.Cout = Cout; a.ld_out = Cout; a.ld_res = Cout;
     a.kh = a.kw = 3; a.stride_h = a.stride_w = 1; a.pad_h = a.pad_w = 1; a.dil_h = a.dil_w = 1; a.groups = 1;
     a.bk = 32; a.CinK = (Cin + 31) / 32 * 32; a.K = 9 * a.CinK; a.Kpad = a.K; a.M = N * H * H; a.act1 = ACT_SILU;
-    a.bn = Cout; a.Cout_pad = Cout; a.t_wsk = 1; a.t_ws = 7;
+    a.bn = Cout; a.Cout_pad = Cout; a.t_wsk = WSK_OFF; a.t_ws = WS_RES3;
     void *in, *w, *out, *rs; float* bias;
     hipMalloc(&in, (size_t)a.M * Cin * 2); hipMalloc(&w, (size_t)a.Cout_pad * a.Kpad * 2); hipMalloc(&out, (size_t)a.M * Cout * 2); hipMalloc(&rs, (size_t)a.M * Cout * 2); hipMalloc(&bias, a.Cout_pad * 4);
     hipMemset(in, 0x11, (size_t)a.M * Cin * 2); hipMemset(w, 0x11, (size_t)a.Cout_pad * a.Kpad * 2); hipMemset(bias, 0, a.Cout_pad * 4); hipMemset(rs, 0x11, (size_t)a.M * Cout * 2);
@@ -42,7 +39,6 @@ static void run(const char* name, int N, int H, int Cin, int Cout, bool res, boo
     }
     static long long st[kWG][3][kPh][8];
     hipMemcpyFromSymbol(st, HIP_SYMBOL(g_st), sizeof(st));
-    if (ablate) printf("[ablate %d: %s%s%s%s] ", ablate, ablate & 1 ? "no stores " : "", ablate & 2 ? "no patch DMA " : "", ablate & 4 ? "no k-loop " : "", ablate & 8 ? "no activation" : "");
     printf("%s%s: event interval %.1f us (best of 3, input %s)\n", name, res ? " + shortcut" : "", best * 1e3f, flushed ? "flushed" : "warm: the previous run's");
     for (int s = 0; s < kWG; ++s) {
         const long long t0 = st[s][0][0][0];
@@ -64,14 +60,12 @@ static void run(const char* name, int N, int H, int Cin, int Cout, bool res, boo
 }
 // fp32 operands (ConvArgs::f32, conv_igemm_f32.hip's layouts): column tile `bn`
 static void run_f32(const char* name, int N, int H, int Cin, int Cout, int bn) {
-    int ablate = 0;
-    hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &ablate, 4);
     ConvArgs a{};
     a.f32 = 1;
     a.N = N; a.H = a.W = H; a.Cin = Cin; a.ld_in = Cin; a.Ho = a.Wo = H; a.Cout = Cout; a.ld_out = Cout; a.ld_res = Cout;
     a.kh = a.kw = 3; a.stride_h = a.stride_w = 1; a.pad_h = a.pad_w = 1; a.dil_h = a.dil_w = 1; a.groups = 1;
     a.bk = 16; a.CinK = (Cin + 15) / 16 * 16; a.K = 9 * a.CinK; a.Kpad = a.K; a.M = N * H * H; a.act1 = ACT_SILU;
-    a.bn = bn; a.bm = 128; a.Cout_pad = (Cout + 15) / 16 * 16; a.t_ws = 7;
+    a.bn = bn; a.bm = 128; a.Cout_pad = (Cout + 15) / 16 * 16; a.t_ws = WS_RES3;
     void *in, *w, *out; float* bias;
     hipMalloc(&in, (size_t)a.M * Cin * 4); hipMalloc(&w, (size_t)a.Cout_pad * a.Kpad * 4); hipMalloc(&out, (size_t)a.M * Cout * 4); hipMalloc(&bias, a.Cout_pad * 4);
     hipMemset(in, 0x3c, (size_t)a.M * Cin * 4); hipMemset(w, 0x3c, (size_t)a.Cout_pad * a.Kpad * 4); hipMemset(bias, 0, a.Cout_pad * 4);
@@ -117,7 +111,6 @@ int main(int argc, char** argv) {
     }
     run("64->64 3x3 @80 b32", 32, 80, 64, 64, false);
     run("64->64 3x3 @80 b32", 32, 80, 64, 64, false, false);
-    for (int ab : {4, 7, 15}) run("64->64 3x3 @80 b32", 32, 80, 64, 64, false, false, ab);
     run("64->64 3x3 @80 b32", 32, 80, 64, 64, true);
     run("64->64 3x3 @40 b32", 32, 40, 64, 64, false);
     run("32->32 3x3 @80 b32", 32, 80, 32, 32, false);
