@@ -343,6 +343,23 @@ int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int ci
 int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out,
                                         int Cout, int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2,
                                         trtx_stream_t stream);
+/* Depthwise convolution (tests / tools; kernels/conv_dw.hip: YOLO11's DWConv and the attention's positional conv): groups == C, square k of 3 / 5 / 7 with
+ * pad == k / 2, stride 1 or 2, dilation 1 (anything else: TRTX_ERR_UNSUPPORTED, nothing is launched).  dtype: TRTX_DTYPE_FLOAT or TRTX_DTYPE_HALF, the type of
+ * in / out / residual, each an NHWC channel slice with its own pixel stride ld_*; the filter is fp32 [k * k][C] (tap-major), bias C floats or NULL, residual
+ * (out's geometry) or NULL.  out = act2(act1(conv + bias) + residual), the activation kinds as in trtx_op_conv2d_nhwc_f16, alpha the leaky slope.  Whole
+ * 16-byte vectors of channels where C, every ld and every base pointer allow them, element-wise otherwise: the same sums in the same order. */
+int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int H, int W, int C, int ld_in, const float* w_taps_c, const float* bias, void* out, int ld_out,
+                               const void* residual, int ld_res, int k, int stride, int pad, int dilation, int act1, float alpha1, int act2, float alpha2,
+                               trtx_stream_t stream);
+/* The fused attention kernels (tests / tools).  qkv: NHWC fp16 [B][N][ld_qkv], head h's channels start at h * (2 kd + hd): q (kd), k (kd), v (hd).
+ * out[b][n][h * hd + d] = sum_m softmax_m(scale * q_n . k_m) v[m][d] and vimg[b][n][h * hd + d] = v[n][d], fp16 with pixel strides ld_out / ld_v.
+ * psa: kd 32, hd 64, every pixel of the image is a key (kernels/attention.hip).  area: kd 32, hd 32, the N pixels split into `area` contiguous ranges of
+ * N / area that attend within themselves (kernels/attention_mfma.hip); pointers or strides that rule out 16-byte loads / 8-byte stores take element-wise ones.
+ * TRTX_ERR_UNSUPPORTED, nothing launched: another kd / hd, N % area != 0, ld_qkv < heads * (2 kd + hd), ld_out or ld_v < heads * hd. */
+int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd, float scale,
+                                  trtx_stream_t stream);
+int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd, int hd,
+                                   float scale, trtx_stream_t stream);
 int32_t trtx_op_poison_lds(void* device_word, trtx_stream_t stream); /* test support: NaN patterns into every CU's LDS */
 int32_t trtx_op_nchw_f32_to_nhwc_f16(const float* in, void* out, int N, int C, int H, int W, int Cpad, int ld_out,
                                      trtx_stream_t stream);

@@ -292,7 +292,7 @@ def yolo_postprocess_gpu(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0
     return out
 
 
-ACT = {"none": 0, "relu": 1, "sigmoid": 2, "silu": 3, "leaky": 4, "tanh": 5}
+ACT = {"none": 0, "relu": 1, "sigmoid": 2, "silu": 3, "leaky": 4, "tanh": 5, "mish": 6}
 
 
 def _hw(v):
@@ -371,6 +371,58 @@ def conv2d_grouped_nhwc_f16(x, wpacked, bias, cout, groups, k, pad, act1="none",
                                                 pad, ACT[act1], _p(residual), residual.stride(2) if residual is not None else 0, ACT[act2], _stream()),
           "trtx_op_conv2d_grouped_nhwc_f16")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- depthwise conv and the attention kernels (tests / tools)
+def conv2d_dw_nhwc(x, w, bias, k, stride, act1="none", residual=None, act2="none", out=None, out_ld=None, alpha1=0.1, alpha2=0.1, pad=None, dilation=1):
+    """Single depthwise-convolution launch (kernels/conv_dw.hip) on NHWC fp16 or fp32 tensors.  x: [N,H,W,C] CUDA, or a channel slice of a wider
+    tensor (its pixel stride is x.stride(2)); residual likewise; out / out_ld: a channel slice of a wider buffer.  w: the filter as a host
+    array [C, k, k] (or [C, 1, k, k]) - transposed here into the device layout, fp32 [k * k][C]; bias: a CUDA fp32 tensor [C] or None.
+    pad: k // 2 unless given (the kernel takes nothing else: TrtxError with status 4)."""
+    import numpy as np
+    import torch
+    N, H, W, C = x.shape
+    assert x.dtype in (torch.float16, torch.float32) and (residual is None or residual.dtype == x.dtype)
+    pad = k // 2 if pad is None else pad
+    Ho, Wo = (H + 2 * pad - dilation * (k - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (k - 1) - 1) // stride + 1
+    taps = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(C, k * k).T)
+    wg = torch.from_numpy(taps).to(x.device)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    assert out.dtype == x.dtype
+    check(lib().trtx_op_conv2d_dw_nhwc(_p(x), 1 if x.dtype == torch.float16 else 0, N, H, W, C, x.stride(2), _p(wg), _p(bias), _p(out),
+                                       out_ld or out.shape[-1], _p(residual), residual.stride(2) if residual is not None else 0, k, stride, pad, dilation,
+                                       ACT[act1], ctypes.c_float(alpha1), ACT[act2], ctypes.c_float(alpha2), _stream()), "trtx_op_conv2d_dw_nhwc")
+    return out
+
+
+def _attention(fn, what, qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, extra):
+    import torch
+    B, N, _ = qkv.shape
+    for t in (qkv, out, vimg):
+        assert t.is_cuda and t.dtype == torch.float16
+    check(fn(_p(qkv), qkv_ld or qkv.stride(1), _p(out), out_ld or out.stride(1), _p(vimg), v_ld or vimg.stride(1), B, heads, N, *extra, kd, hd,
+             ctypes.c_float(scale), _stream()), what)
+    return out, vimg
+
+
+def psa_attention(qkv, heads, scale, out=None, vimg=None, out_ld=None, v_ld=None, qkv_ld=None, kd=32, hd=64):
+    """The fused PSA attention (kernels/attention.hip).  qkv: CUDA fp16 [B, N, heads * (2 kd + hd)] or a channel slice of a wider tensor (pixel
+    stride qkv.stride(1)); out / vimg: [B, N, heads * hd] tensors or channel slices (out_ld / v_ld: their pixel strides).  -> (O, V image)"""
+    import torch
+    B, N, _ = qkv.shape
+    out = torch.empty((B, N, heads * hd), dtype=torch.float16, device=qkv.device) if out is None else out
+    vimg = torch.empty((B, N, heads * hd), dtype=torch.float16, device=qkv.device) if vimg is None else vimg
+    return _attention(lib().trtx_op_psa_attention_f16, "trtx_op_psa_attention_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, ())
+
+
+def area_attention(qkv, heads, area, scale, out=None, vimg=None, out_ld=None, v_ld=None, qkv_ld=None, kd=32, hd=32):
+    """The area attention on MFMA (kernels/attention_mfma.hip): as psa_attention, the N pixels of an image split into `area` contiguous ranges."""
+    import torch
+    B, N, _ = qkv.shape
+    out = torch.empty((B, N, heads * hd), dtype=torch.float16, device=qkv.device) if out is None else out
+    vimg = torch.empty((B, N, heads * hd), dtype=torch.float16, device=qkv.device) if vimg is None else vimg
+    return _attention(lib().trtx_op_area_attention_f16, "trtx_op_area_attention_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, (area,))
 
 
 # ---------------------------------------------------------------------------------------------------- fp32 engines: conv on the fp32 MFMA (tests / tools)

@@ -81,7 +81,9 @@ bool psa_attention_supported(int kd, int hd) { return kd == KD && hd == HD; }
 
 int32_t psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
                           float scale, hipStream_t s) {
-    if (!psa_attention_supported(kd, hd) || B < 1 || heads < 1 || N < 1 || B > 65535 || heads > 65535) return TRTX_ERR_UNSUPPORTED;
+    if (!psa_attention_supported(kd, hd) || B < 1 || heads < 1 || N < 1 || B > 65535 || heads > 65535 || ld_qkv < heads * (2 * kd + hd) ||
+        ld_out < heads * hd || ld_v < heads * hd)
+        return TRTX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(psa_attention_kernel, dim3((N + QB - 1) / QB, heads, B), dim3(QB), 0, s, static_cast<const _Float16*>(qkv), ld_qkv,
                        static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, heads, scale);
     return check_launch("psa_attention");

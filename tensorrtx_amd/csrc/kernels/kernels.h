@@ -219,7 +219,8 @@ int32_t nhwc_reduce_hw_avg(const void* in, void* out, int dtype, int N, int HW, 
 
 // --- INT8 support (quant_ops.hip): calibration statistics over NHWC fp16 tensors, int8 resize with requantisation
 int32_t nhwc_absmax_f16(const void* x, long pixels, int C, int ld, unsigned* out_float_bits, hipStream_t s);  // atomicMax of the float bits
-int32_t nhwc_hist_f16(const void* x, long pixels, int C, int ld, float range, unsigned long long* hist2048, hipStream_t s);
+// hist[bin] += 1 with bin = |x| / range * 8192 (runtime/int8.h kCalibBins; values beyond the range go to the last bin)
+int32_t nhwc_hist_f16(const void* x, long pixels, int C, int ld, float range, unsigned long long* hist8192, hipStream_t s);
 int32_t nhwc_resize_nearest_i8(const void* in, void* out, int N, int H, int W, int C, int ld_in, int Ho, int Wo, int ld_out, float ratio,
                                hipStream_t s);
 

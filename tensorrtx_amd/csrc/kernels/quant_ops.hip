@@ -1,4 +1,4 @@
-// INT8 support kernels for gfx950: calibration statistics over NHWC fp16 tensors (per-tensor |x| maximum and 2048-bin
+// INT8 support kernels for gfx950: calibration statistics over NHWC fp16 tensors (per-tensor |x| maximum and 8192-bin
 // histogram, what IInt8EntropyCalibrator2 needs - yolov8/src/calibrator.cpp:9-74 feeds the batches, TensorRT collects the
 // statistics; this is that collector) and the int8 nearest-neighbour resize with requantisation.
 #include <hip/hip_fp16.h>
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void absmax_f16_kernel(const _Float16* __restr
     if (threadIdx.x == 0) atomicMax(out, __float_as_uint(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]))));
 }
 
-// hist[bin(|x|)] += 1 with bin = |x| / range * 2048 (values beyond the range go to the last bin); LDS-private histogram per block
+// hist[bin(|x|)] += 1 with bin = |x| / range * kBins (values beyond the range go to the last bin); LDS-private histogram per block
 __global__ __launch_bounds__(256) void hist_f16_kernel(const _Float16* __restrict__ x, long pixels, int C, int ld, float inv_bin,
                                                       unsigned long long* __restrict__ hist) {
     __shared__ unsigned s_h[kBins];

@@ -159,6 +159,41 @@ extern "C" int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H,
     return st;
 }
 
+// --- depthwise convolution (kernels/conv_dw.hip) and the two attention kernels (kernels/attention.hip, kernels/attention_mfma.hip), test / tool entry points
+extern "C" int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int H, int W, int C, int ld_in, const float* w_taps_c, const float* bias, void* out,
+                                          int ld_out, const void* residual, int ld_res, int k, int stride, int pad, int dilation, int act1, float alpha1,
+                                          int act2, float alpha2, trtx_stream_t stream) {
+    if (!in || !w_taps_c || !out || N < 1 || H < 1 || W < 1 || C < 1 || k < 1 || stride < 1 || pad < 0 || dilation < 1) return TRTX_ERR_INVALID;
+    if (dtype != DT_F16 && dtype != DT_F32) return TRTX_ERR_UNSUPPORTED;
+    if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return TRTX_ERR_INVALID;
+    ConvArgs a{};
+    a.in = in; a.wgt = w_taps_c; a.bias = bias; a.out = out; a.residual = residual;
+    a.N = N; a.H = H; a.W = W; a.Cin = C; a.ld_in = ld_in;
+    a.Ho = (H + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
+    a.Wo = (W + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
+    a.Cout = C; a.Cout_pad = C; a.ld_out = ld_out; a.ld_res = ld_res;
+    a.kh = k; a.kw = k; a.stride_h = stride; a.stride_w = stride; a.pad_h = pad; a.pad_w = pad; a.dil_h = dilation; a.dil_w = dilation;
+    a.groups = C;
+    a.K = k * k;
+    a.Kpad = a.K;
+    a.M = N * a.Ho * a.Wo;
+    a.act1 = act1; a.act2 = act2; a.alpha1 = alpha1; a.alpha2 = alpha2;
+    a.f32 = dtype == DT_F32;
+    return conv_dw(a, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
+                                             float scale, trtx_stream_t stream) {
+    if (!qkv || !out || !vimg) return TRTX_ERR_INVALID;
+    return psa_attention_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, kd, hd, scale, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area,
+                                              int kd, int hd, float scale, trtx_stream_t stream) {
+    if (!qkv || !out || !vimg) return TRTX_ERR_INVALID;
+    return area_attention_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, area, kd, hd, scale, static_cast<hipStream_t>(stream));
+}
+
 // --- fp32 engines: the implicit-GEMM convolution on the fp32 MFMA (kernels/conv_igemm_f32.hip), test / tool entry points
 static ConvArgs op_conv_args_f32(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw,
                                  int act1, int has_res, int ld_res, int act2) {

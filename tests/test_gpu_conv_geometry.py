@@ -15,22 +15,15 @@ EXPECT_WS, the same sets the host test demands of the lists.
 
 Every launch runs under a time limit of its own (a watchdog that ends the process), and a HIP error ends the session: nothing more is
 launched on a device that has hung or faulted."""
-import contextlib
-import faulthandler
-
 import numpy as np
 import pytest
 import torch
 
 from tensorrtx_amd import capi
 from tests import conv_cases as cc
+from tests.util import SENTINEL, STEP_LIMIT, sync as _sync, time_limit as _time_limit  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -1234.0
-
-
-STEP_LIMIT = 60   # seconds for one launch and its synchronisation (they take milliseconds)
 
 
 def _layouts(case):
@@ -38,27 +31,10 @@ def _layouts(case):
     return [(8, (8 + case.Cout + 8 + 7) // 8 * 8), (6, (6 + case.Cout + 8 + 7) // 8 * 8 + 6)]
 
 
-@contextlib.contextmanager
-def _time_limit(seconds=STEP_LIMIT):
-    """a launch that hangs must not hold the device: the watchdog thread dumps the stack and ends the process"""
-    faulthandler.dump_traceback_later(seconds, exit=True)
-    try:
-        yield
-    finally:
-        faulthandler.cancel_dump_traceback_later()
-
-
 def _buffer(case, off, ld, dtype, gpu, sentinel=SENTINEL):
     Ho, Wo = case.out_hw
     buf = torch.full((case.N + 2, Ho, Wo, ld), sentinel, dtype=dtype, device=gpu)
     return buf, buf[1:case.N + 1, :, :, off:off + case.Cout]
-
-
-def _sync(what):
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:   # the device has faulted: every later launch would run on a broken context
-        pytest.exit(f"HIP error after {what}: {e}", returncode=3)
 
 
 def _untouched(case, buf, off, sentinel=SENTINEL):

@@ -2,8 +2,8 @@
 YOLO11 engines against the oracle's interpreter (fp32) and against the fp32 engine (fp16).
 
 fp16 bounds come from parity.fp16_walk(sites, magnitude) with the rounding sites of each path counted:
-  * depthwise op: the input and the residual are stored in fp16, the fp32 sums have at most 49 terms (< u^2), the output is rounded once:
-    3 sites on a magnitude of L * (|w| * |x|) + |r| per element (L = 1.1 bounds SiLU's slope);
+  * depthwise op: the site count (3, against the unrounded fp32 input and residual) is derived next to the kernel-level bound in tests/dw_cases.py,
+    on a magnitude of L * (|w| * |x|) + |r| per element (L = 1.1 bounds SiLU's slope);
   * attention op: the reference is computed from the qkv tensor rounded to fp16 (the storage site the engine has by design); the kernel
     then adds fp32 arithmetic and ONE rounding at the O store (P and O stay fp32): 1 site on |O|, plus the first-order effect of a one-ulp
     disagreement between the fp32 and the fp64 rounding of q / k (u * scale * sum_j |q_j k_j| on the scores, times max |v|);

@@ -1,4 +1,7 @@
-"""Shared helpers for the tests: seeded synthetic .wts files (cached under /tmp) and plan building."""
+"""Shared helpers for the tests: seeded synthetic .wts files (cached under /tmp) and plan building; for the single-kernel GPU tests the guarded
+channel slices, the per-launch watchdog and the synchronisation that ends the session after a HIP error."""
+import contextlib
+import faulthandler
 import functools
 import hashlib
 import os
@@ -34,3 +37,42 @@ def synth_wts(model: str, seed: int = 0, dialect: str = "double", **kw):
         wts_writer.write_wts(tmp, {k: v.numpy() for k, v in tensors.items()}, dialect=dialect)
         os.replace(tmp, path)
     return path, tensors
+
+
+# ---- single-kernel GPU tests (tests/test_gpu_conv_geometry.py, test_gpu_depthwise_op.py, test_gpu_attention_op.py) -----------------------------------------
+SENTINEL = -1234.0
+STEP_LIMIT = 60   # seconds for one launch and its synchronisation (they take milliseconds)
+
+
+@contextlib.contextmanager
+def time_limit(seconds=STEP_LIMIT):
+    """a launch that hangs must not hold the device: the watchdog thread dumps the stack and ends the process"""
+    faulthandler.dump_traceback_later(seconds, exit=True)
+    try:
+        yield
+    finally:
+        faulthandler.cancel_dump_traceback_later()
+
+
+def sync(what):
+    import pytest
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as e:   # the device has faulted: every later launch would run on a broken context
+        pytest.exit(f"HIP error after {what}: {e}", returncode=3)
+
+
+def guarded_slice(shape, off, ld, dtype, device, fill=SENTINEL):
+    """(buffer, view): a tensor of `shape` = [n, ..., C] as the channel slice [off, off + C) of a buffer [n + 2, ..., ld] filled with `fill` -
+    one guard image in front and one behind, and the neighbouring channels of every pixel"""
+    assert off + shape[-1] <= ld
+    buf = torch.full((shape[0] + 2, *shape[1:-1], ld), fill, dtype=dtype, device=device)
+    return buf, buf[1:-1, ..., off:off + shape[-1]]
+
+
+def outside_untouched(buf, off, C, fill=SENTINEL):
+    """(whether everything outside the slice still holds `fill`, the slice's content on the host)"""
+    b = buf.cpu()
+    inside = b[1:-1, ..., off:off + C].clone()
+    b[1:-1, ..., off:off + C] = fill
+    return bool((b == fill).all()), inside
