@@ -310,6 +310,16 @@ int32_t trtx_op_conv2d_nhwc_f16(const void* in, int N, int H, int W, int Cin, in
 int32_t trtx_op_conv2d_tactics(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw,
                                int has_residual, int ld_res, int32_t* out6, int32_t max_out);
 int32_t trtx_op_conv_force_tactic(const int32_t* tactic6);
+/* The first layer of an fp16 engine (kernels/conv_stem.hip): fp32 NCHW input with 1..4 channels -> NHWC fp16, k x k filter, fp32 weights laid out
+ * [tap = (c*k + r)*k + q][Cout] (folded BatchNorm scale included), bias [Cout] or NULL; Cout 8 / 16 / 32 / 64, ld_out a multiple of 8, out 16-byte aligned. */
+int32_t trtx_op_conv_stem_nchw_f16(const float* in, int N, int C, int H, int W, const float* w_taps_cout, const float* bias, void* out, int Cout,
+                                   int ld_out, int k, int stride, int pad, int act, trtx_stream_t stream);
+/* That layer (C <= 4 -> 16, 3x3 stride 2 pad 1) and the 16 -> 32 3x3 stride 2 pad 1 convolution behind it in ONE launch (kernels/conv_stem_pair.hip): the
+ * stem's weights and bias as above, the second convolution's as trtx_conv_pack_weights_f16 packs them ([32][160] fp16, cin_pad 16) with bias [32] or NULL,
+ * out NHWC fp16 [N][Ho][Wo] with channel stride ld_out (a multiple of 8; a concat slice works as a destination).  The intermediate tensor is never written.
+ * Same bits as trtx_op_conv_stem_nchw_f16 followed by trtx_op_conv2d_nhwc_f16 on its default tactic.  conv_act: none, ReLU or SiLU. */
+int32_t trtx_op_conv_stem_pair_f16(const float* in, int N, int C, int H, int W, const float* stem_w_taps_cout, const float* stem_bias, int stem_act,
+                                   const void* conv_wpacked, const float* conv_bias, int conv_act, void* out, int ld_out, trtx_stream_t stream);
 /* The same launch in an fp32 engine (builds without BuilderFlag::kFP16: yolov8/include/config.h:1-3 USE_FP32, yolov8/src/model.cpp:314-324):
  * NHWC fp32 in / out / residual, fp32 weights packed [cout_pad][kpad] (k = tap * cink + c, cink = Cin rounded up to the 16-channel k-step, or 8 for
  * Cin <= 8; Cin itself a multiple of 4), fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products and sums).  trtx_op_conv2d_tactics_f32 lists the tile

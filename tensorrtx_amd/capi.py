@@ -342,6 +342,40 @@ def conv2d_nhwc_f16(x, wpacked, bias, cout, kh, kw, stride, pad, act1="none", re
     return out
 
 
+def stem_weights(w_kcrs):
+    """Host: KCRS fp32 numpy -> the stem kernels' layout [tap = (c*k + r)*k + q][Cout] (fp32)."""
+    import numpy as np
+    w = np.ascontiguousarray(w_kcrs, dtype=np.float32)
+    return np.ascontiguousarray(w.reshape(w.shape[0], -1).T)
+
+
+def conv_stem_nchw_f16(x, w_taps_cout, bias, k, stride, pad, act="none", out=None, out_ld=None):
+    """The first layer of an fp16 engine: x [N,C,H,W] CUDA float (C <= 4), w_taps_cout [C*k*k, Cout] CUDA float -> NHWC half."""
+    import torch
+    N, C, H, W = x.shape
+    cout = w_taps_cout.shape[1]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if out is None:
+        out = torch.empty((N, Ho, Wo, cout), dtype=torch.float16, device=x.device)
+    check(lib().trtx_op_conv_stem_nchw_f16(_p(x), N, C, H, W, _p(w_taps_cout), _p(bias), _p(out), cout, out_ld or out.shape[-1], k, stride, pad,
+                                           ACT[act], _stream()), "trtx_op_conv_stem_nchw_f16")
+    return out
+
+
+def conv_stem_pair_f16(x, stem_w_taps_cout, stem_bias, conv_wpacked, conv_bias, stem_act="silu", conv_act="silu", out=None, out_ld=None):
+    """The 3x3 / 2 stem (C <= 4 -> 16) and the 16 -> 32 3x3 / 2 convolution behind it in one launch: x [N,C,H,W] CUDA float -> NHWC half [N,Ho,Wo,32]
+    (or into `out` with channel stride out_ld)."""
+    import torch
+    N, C, H, W = x.shape
+    Hi, Wi = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((N, Ho, Wo, 32), dtype=torch.float16, device=x.device)
+    check(lib().trtx_op_conv_stem_pair_f16(_p(x), N, C, H, W, _p(stem_w_taps_cout), _p(stem_bias), ACT[stem_act], _p(conv_wpacked), _p(conv_bias),
+                                           ACT[conv_act], _p(out), out_ld or out.shape[-1], _stream()), "trtx_op_conv_stem_pair_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- grouped conv on the matrix pipe (tests / tools)
 def pack_conv_weights_grouped_f16(w_kcrs, ch_scale=None):
     """Host: KCRS fp32 numpy [Cout, Cin / groups, k, k] -> packed uint16 [Cout, Kpad] for conv2d_grouped_nhwc_f16."""

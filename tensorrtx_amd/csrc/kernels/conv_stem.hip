@@ -22,6 +22,7 @@
 #include "../common.h"
 #include "act.h"
 #include "kernels.h"
+#include "stem_tile.h"
 
 namespace trtx {
 namespace {
@@ -76,15 +77,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvArgs p) {
     }
 }
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int kStemTW = 64, kStemTH = 4;  // output tile of a workgroup: 4 rows x 64 columns = 16 MFMA groups of 16 pixels
-
-struct StemGeom {
-    int PR, PCA;            // input patch rows / 4-float-aligned columns staged in LDS per channel
-    int tiles_x, tiles_y;
-    int chunks;             // 16-byte chunks of the patch (Cin * PR * PCA / 4)
-};
 
 // NFRAG = Cout / 16, KS = 32-wide slices of K (K = kh*kw*Cin <= 32*KS).
 // Stage 1: the fp32 input patch of the tile (Cin x PR x PCA) goes HBM -> LDS with 16-byte LDS-DMA loads, rows and
@@ -145,15 +138,7 @@ __device__ __forceinline__ void frame_pixel(const StemFrame& im, const AxisSampl
     b = c0 / 255.0f;
 }
 
-// what a workgroup keeps in registers for all of its tiles: the weights as MFMA A fragments, the patch offsets of its taps, its bias
-template <int NFRAG, int KS>
-struct StemRegs {
-    half8 wf[NFRAG][KS];
-    int l_off[KS][8];   // float index inside the patch of tap (c, r, q) relative to the pixel's top-left corner
-    float bias4[NFRAG][4];
-};
-template <int NFRAG, int KS>
-__device__ __forceinline__ void stem_setup(const ConvArgs& p, const StemGeom& g, StemRegs<NFRAG, KS>& R);
+// (StemRegs, stem_setup, the patch fetch: stem_tile.h, shared with conv_stem_pair.hip)
 template <int NFRAG, int KS>
 __device__ __forceinline__ void stem_compute(const ConvArgs& p, const StemGeom& g, const StemRegs<NFRAG, KS>& R, const float* s_patch, int n, int tx0, int ty0, int shift);
 template <int NFRAG, int KS>
@@ -204,8 +189,6 @@ __global__ __launch_bounds__(256) void conv_stem_frames_kernel(const ConvArgs p,
 template <int NFRAG, int KS>
 __global__ __launch_bounds__(256) void conv_stem_lds_kernel(const ConvArgs p, const StemGeom g, unsigned in_bytes, int total_tiles) {
     extern __shared__ __attribute__((aligned(16))) float s_patch[];
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6;
     StemRegs<NFRAG, KS> R;
     stem_setup<NFRAG, KS>(p, g, R);
     for (int tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
@@ -219,92 +202,14 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(const ConvArgs p, co
     const int wi_start = tx0 * p.stride_w - p.pad_w;
     const int al_start = (wi_start >= 0 ? wi_start : wi_start - 3) / 4 * 4;  // floor to a multiple of 4
     const int shift = wi_start - al_start;
-    // ---- stage 1
-    {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.in), 0, in_bytes, 0x00020000);
-        const int cpr = g.PCA / 4;                  // chunks per patch row
-        const float inv_cpr = 1.0f / (float)cpr, inv_pr = 1.0f / (float)g.PR;
-        for (int base = 0; base < g.chunks; base += 256) {
-            const int ci = base + tid;
-            int row = (int)((float)ci * inv_cpr);   // (c * PR + pr); estimate within +-1, fixed up exactly
-            int cq = ci - row * cpr;
-            if (cq < 0) { --row; cq += cpr; }
-            if (cq >= cpr) { ++row; cq -= cpr; }
-            int c = (int)((float)row * inv_pr);
-            int pr = row - c * g.PR;
-            if (pr < 0) { --c; pr += g.PR; }
-            if (pr >= g.PR) { ++c; pr -= g.PR; }
-            const int hi = hi_start + pr, wi = al_start + cq * 4;
-            const bool ok = ci < g.chunks && (unsigned)hi < (unsigned)p.H && wi >= 0 && wi + 3 < p.W;
-            const unsigned off = ok ? (unsigned)(((((long)n * p.Cin + c) * p.H + hi) * p.W + wi) * 4) : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(s_patch + (size_t)(base + wave * 64) * 4), 16, off, 0, 0, 0);
-        }
-    }
+    // ---- stage 1 (stem_tile.h)
+    stem_patch_fetch(p, g, in_bytes, s_patch, n, hi_start, al_start);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (p.W & 3) {
-        // Ragged width (Faster R-CNN's 1333): the 16-byte chunk that straddles the end of an image row was range-checked away whole
-        // above; its 1..3 real pixels are fetched here, one patch row per thread (right-edge tiles only have any)
-        const int cpr = g.PCA / 4, rows = p.Cin * g.PR, wtail = p.W & ~3;
-        const int cq = (wtail - al_start) >> 2;
-        if (cq >= 0 && cq < cpr && wtail >= al_start) {
-            const float* __restrict__ src = static_cast<const float*>(p.in);
-            for (int rrow = tid; rrow < rows; rrow += 256) {
-                const int c = rrow / g.PR, pr = rrow - c * g.PR, hi = hi_start + pr;
-                if ((unsigned)hi >= (unsigned)p.H) continue;
-                const size_t base = (((size_t)n * p.Cin + c) * p.H + hi) * p.W;
-                for (int e = 0; e < 4; ++e)
-                    if (wtail + e < p.W) s_patch[((size_t)rrow * cpr + cq) * 4 + e] = src[base + wtail + e];
-            }
-        }
-        __syncthreads();
-    }
+    stem_patch_tail(p, g, s_patch, n, hi_start, al_start);
     stem_compute<NFRAG, KS>(p, g, R, s_patch, n, tx0, ty0, shift);
     __syncthreads();   // every wave is done with the patch before the next tile's DMA overwrites it
     }
-}
-
-// weights, tap tables and bias of a lane.  EVERY load is issued unconditionally from a clamped index and masked afterwards: written as
-// `cond ? w[i] : 0` the compiler put each of the 160 loads of the 7x7 stem (176 with the bias) into its own exec-masked branch with an
-// s_waitcnt vmcnt(0) behind it - 176 dependent round trips of ~700 cycles per workgroup, which is where conv_stem_lds_kernel<4, 5> spent its
-// 148 us on ResNet-50's 224 x 224 batch 32 (12x its byte floor; profiles/r04_kernel_stats_c2_1ctx_lanes1.txt) and 888 us on RetinaFace's 1280 x 1280.
-template <int NFRAG, int KS>
-__device__ __forceinline__ void stem_setup(const ConvArgs& p, const StemGeom& g, StemRegs<NFRAG, KS>& R) {
-    const int lane = threadIdx.x & 63;
-    const int khw = p.kh * p.kw;
-    const int K = khw * p.Cin;
-    const float* __restrict__ w = static_cast<const float*>(p.wgt);  // [tap = (c*kh + r)*kw + q][Cout]
-    const int kq = (lane >> 4) * 8;
-    auto& wf = R.wf;
-    auto& l_off = R.l_off;
-    auto& bias4 = R.bias4;
-    const float inv_khw = 1.0f / (float)khw, inv_kw = 1.0f / (float)p.kw;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int k = ks * 32 + kq + e;
-            // k < 160, khw <= 49: (k + 0.5) / d is never within rounding distance of an integer, the floor is exact
-            const int c = (int)(((float)k + 0.5f) * inv_khw), rem = k - c * khw;
-            const int r = (int)(((float)rem + 0.5f) * inv_kw), q = rem - r * p.kw;
-            l_off[ks][e] = k < K ? (c * g.PR + r) * g.PCA + q : 0;  // padded taps: zero weights, any valid address
-#pragma unroll
-            for (int j = 0; j < NFRAG; ++j) {
-                const int co = j * 16 + (lane & 15);
-                const float wv = w[(size_t)(k < K ? k : K - 1) * p.Cout + (co < p.Cout ? co : p.Cout - 1)];
-                wf[j][ks][e] = (k < K && co < p.Cout) ? (_Float16)wv : (_Float16)0.f;
-            }
-        }
-    const int ch4 = (lane >> 4) * 4;
-    const float* __restrict__ bsrc = p.bias ? p.bias : w;   // (wave-uniform; without a bias the loaded values are masked away)
-#pragma unroll
-    for (int j = 0; j < NFRAG; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int co = j * 16 + ch4 + e;
-            const float bv = bsrc[co < p.Cout ? co : p.Cout - 1];
-            bias4[j][e] = (p.bias && co < p.Cout) ? bv : 0.f;
-        }
 }
 
 // stage 2 of both stem kernels: the patch is in LDS, wave w owns tile row w (64 pixels = 4 groups)
@@ -315,8 +220,6 @@ __device__ __forceinline__ void stem_compute(const ConvArgs& p, const StemGeom& 
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int ch4 = (lane >> 4) * 4;
-    const auto& wf = R.wf;
-    const auto& l_off = R.l_off;
     const auto& bias4 = R.bias4;
     _Float16* __restrict__ out = static_cast<_Float16*>(p.out);
 #pragma nounroll   // (unrolled, the <4, 5> instantiation is ~100 KB of code against a 64 KB instruction cache, walked once per tile)
@@ -325,39 +228,14 @@ __device__ __forceinline__ void stem_compute(const ConvArgs& p, const StemGeom& 
         const int ho = ty0 + ty, wo = tx0 + tx;
         const float* src = s_patch + (ty * p.stride_h) * g.PCA + tx * p.stride_w + shift;
         floatx4 acc[NFRAG];
-#pragma unroll
-        for (int j = 0; j < NFRAG; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            half8 xf;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) xf[e] = (_Float16)src[l_off[ks][e]];
-#pragma unroll
-            for (int j = 0; j < NFRAG; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[j][ks], xf, acc[j], 0, 0, 0);
-        }
+        stem_group_mfma<NFRAG, KS>(R, src, acc);
         if (ho >= p.Ho || wo >= p.Wo) continue;
         const long m = ((long)n * p.Ho + ho) * p.Wo + wo;
 #pragma unroll
         for (int j = 0; j < NFRAG; ++j) {
             const int co = j * 16 + ch4;
             if (co >= p.Cout) continue;
-            half4 o;
-            if (p.act1 == ACT_SILU) {  // wave-uniform: pick the activation once, not per element
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float x = acc[j][e] + bias4[j][e];
-                    o[e] = round_to_half(x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)));
-                }
-            } else if (p.act1 == ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float x = acc[j][e] + bias4[j][e];
-                    o[e] = (_Float16)(x > 0.f ? x : 0.f);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = round_to_half(act_stem(acc[j][e] + bias4[j][e], p.act1, p.alpha1));
-            }
+            const half4 o = stem_finish4(p, acc[j], bias4[j]);
             *reinterpret_cast<half4*>(out + m * p.ld_out + co) = o;
         }
     }

@@ -162,6 +162,11 @@ struct StemFrame {
     float d2s[6];
 };
 int32_t conv_stem_frames_f32(const ConvArgs& a, const StemFrame* frames, hipStream_t s);
+// The stem and the stride-2 3x3 convolution behind it in one launch (conv_stem_pair.hip): stem Cin <= 4 -> 16, then 16 -> 32, both 3x3 / 2 pad 1, fp16.
+// `stem` as conv_stem_nchw_f32 takes it (its `out` is not written), `conv` as conv_igemm_f16 takes it (its `in` is not read): the same packed weights,
+// the same bits as the stem followed by the implicit-GEMM kernel's main K order.  _possible(): geometry, and the alignment of whatever pointers are set.
+bool conv_stem_pair_possible(const ConvArgs& stem, const ConvArgs& conv);
+int32_t conv_stem_pair_f16(const ConvArgs& stem, const ConvArgs& conv, hipStream_t s);
 // generic direct convolution (any groups / dilation / channel count), T = activation dtype, fp32 weights
 int32_t conv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 // depthwise convolution (conv_dw.hip): groups == Cin == Cout, k 3 / 5 / 7 with pad k/2, stride 1 / 2, no dilation; weights fp32 [kh*kw][C]

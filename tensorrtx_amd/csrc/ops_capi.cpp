@@ -127,6 +127,42 @@ extern "C" int32_t trtx_op_conv2d_nhwc_f16(const void* in, int N, int H, int W, 
     return st;
 }
 
+// --- the first layer (kernels/conv_stem.hip) and the stem pair in one launch (kernels/conv_stem_pair.hip), test / tool entry points
+static ConvArgs op_stem_args(const float* in, int N, int C, int H, int W, const float* w_taps_cout, const float* bias, int Cout, int k, int stride, int pad, int act) {
+    ConvArgs a{};
+    a.in = in; a.wgt = w_taps_cout; a.bias = bias;
+    a.N = N; a.H = H; a.W = W; a.Cin = C; a.ld_in = C;
+    a.Ho = (H + 2 * pad - k) / stride + 1;
+    a.Wo = (W + 2 * pad - k) / stride + 1;
+    a.Cout = Cout; a.Cout_pad = Cout;
+    a.kh = k; a.kw = k; a.stride_h = stride; a.stride_w = stride; a.pad_h = pad; a.pad_w = pad; a.dil_h = 1; a.dil_w = 1;
+    a.groups = 1;
+    a.K = k * k * C; a.Kpad = a.K;
+    a.M = N * a.Ho * a.Wo;
+    a.act1 = act; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    return a;
+}
+
+extern "C" int32_t trtx_op_conv_stem_nchw_f16(const float* in, int N, int C, int H, int W, const float* w_taps_cout, const float* bias, void* out, int Cout,
+                                              int ld_out, int k, int stride, int pad, int act, trtx_stream_t stream) {
+    if (!in || !w_taps_cout || !out || N < 1 || C < 1 || H < 1 || W < 1 || k < 1 || stride < 1 || pad < 0 || H + 2 * pad < k || W + 2 * pad < k) return TRTX_ERR_INVALID;
+    ConvArgs a = op_stem_args(in, N, C, H, W, w_taps_cout, bias, Cout, k, stride, pad, act);
+    a.out = out;
+    a.ld_out = ld_out;
+    return conv_stem_nchw_f32(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trtx_op_conv_stem_pair_f16(const float* in, int N, int C, int H, int W, const float* stem_w_taps_cout, const float* stem_bias, int stem_act,
+                                              const void* conv_wpacked, const float* conv_bias, int conv_act, void* out, int ld_out, trtx_stream_t stream) {
+    if (!in || !stem_w_taps_cout || !conv_wpacked || !out || N < 1 || C < 1 || H < 1 || W < 1) return TRTX_ERR_INVALID;
+    const ConvArgs s = op_stem_args(in, N, C, H, W, stem_w_taps_cout, stem_bias, 16, 3, 2, 1, stem_act);
+    ConvArgs c = op_conv_args(N, s.Ho, s.Wo, 16, 16, 32, ld_out, 3, 3, 2, 2, 1, 1, conv_act, 0, 0, 0);
+    c.wgt = conv_wpacked;
+    c.bias = conv_bias;
+    c.out = out;
+    return conv_stem_pair_f16(s, c, static_cast<hipStream_t>(stream));
+}
+
 // --- grouped convolution on the matrix pipe (kernels/conv_grouped.hip), test / tool entry points
 extern "C" int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale, uint16_t* packed,
                                                       int32_t* kpad_out) {

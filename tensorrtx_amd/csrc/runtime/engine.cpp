@@ -133,6 +133,8 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         return st;
     };
     if (lanes && hipEventRecord(c->start_event, user_stream) != hipSuccess) return bail(TRTX_ERR_HIP);
+    ConvArgs pair_stem{};        // the stem's arguments, kept for the fused launch the next op issues
+    bool pair_pending = false;
     for (size_t k = 0; k < plan.ops.size(); ++k) {
         const POp& op = plan.ops[k];
         hipStream_t stream = user_stream;  // shadows the parameter: the stream THIS op is issued on
@@ -166,6 +168,31 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 // (the stem reads the LINEAR network input: in an explicit-batch plan its leading dimension is the image count)
                 a.N = op.stem ? (plan.explicit_batch ? (int)t0.dims.d[0] : batch) : nb(t0);
                 a.M = a.N * a.Ho * a.Wo;
+                // The stem pair (POp::stem_pair on the next op; kernels/conv_stem_pair.hip): the stem launches nothing, the marked op issues the one fused
+                // launch from the stem's arguments and its own - so its profile row carries the launch and the stem's reports 0.  Camera frames and the
+                // calibration observer (which reads the tensor between the two) keep the two launches, as does a pointer the kernel cannot take - and the tactic
+                // timing (tune.cpp), so that the marked op still gets a timed tactic of its own for those launches.
+                if (op.stem && !c->frames && !c->observer && !c->tuning && k + 1 < plan.ops.size() && plan.ops[k + 1].stem_pair && plan.ops[k + 1].lane == op.lane) {
+                    const POp& nx = plan.ops[k + 1];
+                    ConvArgs b = nx.conv;
+                    b.out = R.ptr(nx.out[0]);
+                    b.wgt = W + nx.w_off;
+                    b.bias = reinterpret_cast<const float*>(W + nx.b_off);
+                    b.N = nb(to);
+                    b.M = b.N * b.Ho * b.Wo;
+                    if (conv_stem_pair_possible(a, b)) {
+                        pair_stem = a;
+                        pair_pending = true;
+                        break;
+                    }
+                }
+                if (op.stem_pair && pair_pending) {
+                    pair_pending = false;
+                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
+                    st = conv_stem_pair_f16(pair_stem, a, stream);
+                    conv_set_launch_probe(nullptr);
+                    break;
+                }
                 if (op.kind == OP_DECONV)
                     st = deconv_direct(a, op.dtype, stream);
                 else if (op.stem && c->frames)

@@ -657,6 +657,45 @@ void group_convs(Plan& plan, const PassInputs& e) {
     plan.ops = std::move(out);
 }
 
+// The stem and the stride-2 3x3 convolution behind it in one launch (kernels/conv_stem_pair.hip): marks the convolution (POp::stem_pair); the op list, the
+// tensors and the arena stay what they are - the executor issues the fused launch at the marked op and nothing at the stem, and the tensor between them
+// keeps its block, unwritten.  Marked when the stem is the op right before, the tensor between them has no other reader or writer and is not a binding,
+// the plan is fp16 without an int8 side, and conv_stem_pair_possible() takes the two layers at the largest batch.  Not part of the serialized network:
+// re-derived wherever a plan is lowered.  TRTX_STEM_PAIR=0 marks nothing (A/B, tests): every launch is then the two-kernel form's.
+void mark_stem_pair(Plan& plan, const PassInputs& e) {
+    if (!e.opt.stem_pair || e.dt != DT_F16 || e.int8 || CalibrationLowering::active()) return;   // (the calibration engine's observer reads every tensor an op writes)
+    const int n = (int)plan.ops.size();
+    for (int k = 0; k + 1 < n; ++k) {
+        const POp& st = plan.ops[k];
+        POp& cv = plan.ops[k + 1];
+        if (st.kind != OP_CONV || !st.stem || st.conv.f32 || st.out.size() != 1) continue;
+        if (cv.kind != OP_CONV || !cv.igemm || cv.stem || cv.from_deconv || cv.in.size() != 1 || !cv.extra_in.empty() || cv.in[0] != st.out[0]) continue;
+        const PTensor& mid = plan.tensors[st.out[0]];
+        if (mid.storage < 0 || plan.storages[mid.storage].kind != ST_ARENA || is_binding_tensor(plan, mid.id) || is_binding_tensor(plan, owner_of(plan, mid.id))) continue;
+        bool shared = false;   // any other op (or member of a grouped launch) that touches the block the intermediate lives in
+        auto touches = [&](const POp& op) {
+            for (const std::vector<int>* v : {&op.in, &op.out, &op.extra_in})
+                for (int t : *v)
+                    if (plan.tensors[t].storage == mid.storage) return true;
+            return false;
+        };
+        for (int j = 0; j < n && !shared; ++j) {
+            if (j == k || j == k + 1) continue;
+            shared = touches(plan.ops[j]);
+            for (const POp& m : plan.ops[j].group) shared = shared || touches(m);
+        }
+        if (shared) continue;
+        ConvArgs a = st.conv, b = cv.conv;   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
+        const PTensor& t_in = plan.tensors[st.in[0]];
+        a.N = plan.explicit_batch ? (int)t_in.dims.d[0] : plan.max_batch;
+        a.M = a.N * a.Ho * a.Wo;
+        b.N = (mid.nfix ? mid.nfix : plan.max_batch) * mid.nmul;
+        b.M = b.N * b.Ho * b.Wo;
+        if (!conv_stem_pair_possible(a, b)) continue;
+        cv.stem_pair = true;
+    }
+}
+
 // Lanes (= HIP streams at run time): an op continues the lane of a dependency that is still that lane's tail,
 // otherwise it opens a free lane, otherwise it queues behind the lane that went idle first.  Independent branches
 // (the six cv2/cv3 head chains of YOLOv8, model.cpp:224-291; FPN/SSH branches of RetinaFace) end up on different
@@ -782,6 +821,7 @@ bool finalize_plan(Plan& plan, const PassInputs& e, std::string* err) {
     if (!select_conv_kernels(plan, e, err) || !configure_plugins(plan, err)) return false;
     chain_sppf_pools(plan, e);
     group_convs(plan, e);
+    mark_stem_pair(plan, e);
     const std::vector<std::vector<int>> deps = op_dependencies(plan);   // (group_convs reordered and merged ops: not its list)
     assign_lanes(plan, e, deps);
     plan_arena(plan, ancestors(plan, deps, true));
