@@ -147,6 +147,34 @@ int32_t trtx_yolov5_head_decode_nhwc(const void* const* heads, const int* ld, in
 int32_t trtx_yolov5_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
                                          const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
                                          void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * YOLOv9 YoloLayer - the reference's yolov9/plugin/yololayer.cu:133-197 (CalDetection + forwardGpu).
+ *   inputs     3 device pointers (strides 8 / 16 / 32), fp32 [batch][4 + classes (+ 32 if is_segmentation)][(net_h / s) * (net_w / s)]
+ *   output     device, fp32 [batch][1 + max_out * 38]: count (clamped to max_out), then Detection records of 38 floats
+ *              (yolov9/include/types.h): x1, y1, x2, y2, conf, class_id, mask[32]
+ * Candidates with max sigmoid(class) >= 0.1 in canonical (level, cell) order (the reference: atomicAdd race).
+ */
+size_t trtx_yolov9_decode_workspace(int batch, int net_h, int net_w);
+int32_t trtx_yolov9_decode(const float* const* inputs, int batch, int classes, int net_h, int net_w, int max_out, int is_segmentation,
+                           float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Fused DDetect / DualDDetect head: DFL + trtx_yolov9_decode (detection) on the NHWC outputs of the head's last convolutions, what the
+ * engine uses instead of the shuffle / softmax / conv / shuffle chain, the class reshape and the concat of yolov9/src/block.cpp:380-399,
+ * 441-453 followed by YoloLayerPlugin::enqueue (yolov9/plugin/yololayer.cu:124-197).
+ *   box[l]     device fp16 [batch][cells_l][box_ld[l]], channels [0, 64) = 4 sides x 16 DFL bins (the grouped 1x1 cv2.l.2)
+ *   cls[l]     device fp16 [batch][cells_l][cls_ld[l]], channels [0, classes) = class logits (cv3.l.2); any classes >= 1
+ *   Channels beyond those are padding and never reach a result.  dfl_weights: device fp32[16] (<detect>.dfl.conv.weight).
+ *   `box`, `box_ld`, `cls`, `cls_ld` are HOST arrays of 3.  Bases and strides that are no multiples of 16 bytes, box_ld < 64 and
+ *   cls_ld < classes: TRTX_ERR_UNSUPPORTED, nothing is written.  Output, candidate order and decode arithmetic: trtx_yolov9_decode.
+ */
+size_t trtx_yolov9_head_decode_workspace(int batch, int net_h, int net_w);
+int32_t trtx_yolov9_head_decode_nhwc(const void* const* box, const int* box_ld, const void* const* cls, const int* cls_ld, int batch, int classes,
+                                     int net_h, int net_w, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                     size_t workspace_bytes, trtx_stream_t stream);
+/* The same on the NHWC fp32 tensors of an fp32 engine: ld in floats; the DFL is the un-fused chain's arithmetic to the bit. */
+int32_t trtx_yolov9_head_decode_nhwc_f32(const void* const* box, const int* box_ld, const void* const* cls, const int* cls_ld, int batch, int classes,
+                                         int net_h, int net_w, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                         size_t workspace_bytes, trtx_stream_t stream);
 /* Oriented boxes (yolov8 obb): host nms_obb() on the GPU (yolov8/src/postprocess.cpp:303-393, ProbIoU, "conf <= thresh" dropped,
  * erased when probiou >= nms_thresh); keep_det is [batch][max_out][7] = cx, cy, w, h, conf, class, angle.  And the reference's
  * GPU mode for oriented boxes, cuda_decode_obb + cuda_nms_obb (yolov8/src/postprocess.cu:7-40, 113-166): out [batch][1 + max_out*8]. */
@@ -157,6 +185,11 @@ int32_t trtx_yolo_postprocess_gpu_obb(const float* decode_out, int batch, int ma
 /* YOLOv5 host nms() / batch_nms() on the GPU (yolov5/src/postprocess.cpp:30-80): centre-format IoU, conf <= thresh dropped,
  * class-wise greedy suppression in conf-descending order.  Same outputs / workspace as trtx_yolo_nms; records are 38 floats. */
 int32_t trtx_yolov5_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
+                        int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* YOLOv9 host nms() / batch_nms() on the GPU (yolov9/src/postprocess.cpp:48-83): records of 38 floats with corner boxes; conf <= thresh
+ * dropped, each box turned into centre format by the reference's four fp32 operations (:59-62), then the YOLOv5 iou and conf-descending
+ * class-wise suppression.  Same outputs / workspace as trtx_yolov5_nms; keep_det holds the centre-format boxes, as the reference's res. */
+int32_t trtx_yolov9_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
                         int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /*
  * Mask assembly of the seg programs: the coefficient x prototype loop of the host process_mask with its get_downscale_rect

@@ -260,6 +260,66 @@ def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
     return keep_idx, keep_cnt, keep_det
 
 
+def yolov9_decode(inputs, classes, net_h, net_w, max_out=1000, is_seg=False, out=None):
+    """YOLOv9 YoloLayerPlugin::enqueue replacement (yolov9/plugin/yololayer.cu:124-197).
+    inputs: three CUDA fp32 [B, 4 + classes (+ 32), gh * gw] (strides 8 / 16 / 32).  -> [B, 1 + max_out * 38]"""
+    import torch
+    L = lib()
+    ins = [x.contiguous() for x in inputs]
+    assert len(ins) == 3 and all(x.is_cuda and x.dtype == torch.float32 for x in ins)
+    B, dev = ins[0].shape[0], ins[0].device
+    arr = (ctypes.c_void_p * 3)(*[x.data_ptr() for x in ins])
+    L.trtx_yolov9_decode_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolov9_decode_workspace(B, net_h, net_w)
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros((B, 1 + max_out * DET5_FLOATS), dtype=torch.float32, device=dev)
+    check(L.trtx_yolov9_decode(arr, B, classes, net_h, net_w, max_out, 1 if is_seg else 0, _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()),
+          "trtx_yolov9_decode")
+    return out
+
+
+def yolov9_head_decode_nhwc(box, cls, classes, net_h, net_w, dfl_w, max_out=1000, out=None, batch=None, box_ld=None, cls_ld=None, ws=None):
+    """The fused DDetect head (trtx_yolov9_head_decode_nhwc{,_f32}) on the NHWC outputs of cv2.l.2 and cv3.l.2, three levels:
+    box[l] [B, cells_l, box_ld] (channels [0, 64) = DFL bins), cls[l] [B, cells_l, cls_ld] (channels [0, classes) = logits), fp16 or
+    fp32.  `out` (rows of 1 + max_out * 38), `batch`, the strides and the workspace can be given.  -> [B, 1 + max_out * 38]"""
+    import torch
+    L = lib()
+    assert len(box) == 3 and len(cls) == 3
+    B = box[0].shape[0] if batch is None else batch
+    dev = box[0].device
+    bp = (ctypes.c_void_p * 3)(*[x.data_ptr() for x in box])
+    cp = (ctypes.c_void_p * 3)(*[x.data_ptr() for x in cls])
+    bl = (ctypes.c_int * 3)(*(box_ld if box_ld is not None else [x.shape[-1] for x in box]))
+    cl = (ctypes.c_int * 3)(*(cls_ld if cls_ld is not None else [x.shape[-1] for x in cls]))
+    L.trtx_yolov9_head_decode_workspace.restype = ctypes.c_size_t
+    if ws is None:
+        ws = torch.empty(max(L.trtx_yolov9_head_decode_workspace(B, net_h, net_w), 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros((B, 1 + max_out * DET5_FLOATS), dtype=torch.float32, device=dev)
+    fn = L.trtx_yolov9_head_decode_nhwc_f32 if box[0].dtype == torch.float32 else L.trtx_yolov9_head_decode_nhwc
+    check(fn(bp, bl, cp, cl, B, classes, net_h, net_w, _p(dfl_w), max_out, _p(out), _p(ws), ctypes.c_size_t(ws.numel()), _stream()),
+          "trtx_yolov9_head_decode_nhwc")
+    return out
+
+
+def yolov9_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
+    """yolov9 batch_nms replacement (yolov9/src/postprocess.cpp:48-91) on 38-float records with corner boxes.  Returns keep_idx, keep_cnt,
+    keep_det [B, max_out, 6] = cx, cy, w, h, conf, class: the centre format the reference's nms() leaves in `res`."""
+    import torch
+    L = lib()
+    B, dev = decode_out.shape[0], decode_out.device
+    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
+    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
+    keep_det = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
+    L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolo_nms_workspace(B)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    check(L.trtx_yolov9_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
+                            _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov9_nms")
+    return keep_idx, keep_cnt, keep_det
+
+
 def seg_masks(decode_out, keep_idx, keep_cnt, proto, net_h, net_w, max_keep, box_format=0, out=None):
     """process_mask's coefficient loop on the GPU (yolov5/src/postprocess.cpp:94-120, yolov8/yolov8_seg.cpp:17-53).
     decode_out [B, 1 + max_out * 38 | 90] (the record length follows from keep_idx's max_out), keep_idx [B, max_out] and keep_cnt [B]

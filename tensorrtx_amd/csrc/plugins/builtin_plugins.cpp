@@ -1,5 +1,5 @@
 // Built-in HIP plugins, registered under the names the reference host code asks the registry for.
-//   "YoloLayer_TRT"/"1"  — yolov8/plugin/yololayer.{h,cu} (creator: yololayer.cu:320-369)
+//   "YoloLayer_TRT"/"1"  — yolov8/plugin/yololayer.{h,cu} (creator: yololayer.cu:320-369); the yolov5 and yolov9 plugins of that name too
 // Each plugin is a small host object exposed through the C v-table of include/trtx_hip.h; its
 // enqueue calls the HIP operator entry points of section 1.  Serialization blobs keep the reference's
 // field order so a plan round-trips byte for byte.
@@ -278,10 +278,114 @@ int32_t yolo5_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The YOLOv9 form of "YoloLayer_TRT"/"1" (yolov9/plugin/yololayer.{h,cu}; the same registered name again): ONE creator field "netinfo" =
+// int32[5] {classes, W, H, maxOut, isSeg} (yololayer.cu:220-232); blob int classCount, threadCount, netW, netH, maxOut, bool isSeg
+// = 21 bytes (yololayer.cu:36-60).  Three inputs on the strides 8 / 16 / 32 with grids H / s x W / s (:185-186), each
+// (4 + classes (+ 32), cells); output 1 + maxOut * 38 floats.
+struct Yolo9Layer {
+    int class_count = 80, thread_count = 256, net_w = 640, net_h = 640, max_out = 1000;
+    bool seg = false;
+
+    std::vector<uint8_t> blob() const {
+        std::vector<uint8_t> b;
+        put(b, class_count);
+        put(b, thread_count);
+        put(b, net_w);
+        put(b, net_h);
+        put(b, max_out);
+        put(b, seg);
+        return b;
+    }
+    static Yolo9Layer* from_blob(const void* data, size_t len) {
+        const uint8_t* p = static_cast<const uint8_t*>(data);
+        const uint8_t* end = p + len;
+        auto* y = new Yolo9Layer();
+        const bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, y->net_w) && get(p, end, y->net_h) &&
+                        get(p, end, y->max_out) && get(p, end, y->seg) && p == end;
+        if (!ok || y->class_count < 1 || y->max_out < 1 || y->net_w < 32 || y->net_h < 32) {
+            delete y;
+            return nullptr;
+        }
+        return y;
+    }
+};
+
+void yolo9_fill(trtx_plugin_vtbl* v, Yolo9Layer* y);
+int32_t yolo9_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
+    auto* y = static_cast<Yolo9Layer*>(s);
+    out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yololayer.cu:70-73
+    out->d[0] = (int64_t)y->max_out * 38 + 1;
+    out->d[1] = 1;
+    out->d[2] = 1;
+    return 0;
+}
+int32_t yolo9_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
+    auto* y = static_cast<Yolo9Layer*>(s);
+    if (nb_in != 3) return 1;
+    const int info = 4 + y->class_count + (y->seg ? 32 : 0);
+    for (int i = 0; i < nb_in; ++i) {
+        int64_t vol = 1;
+        for (int k = 0; k < in[i].nb; ++k) vol *= in[i].d[k];
+        if (vol != (int64_t)info * (y->net_h / (8 << i)) * (y->net_w / (8 << i))) return 1;
+    }
+    return 0;
+}
+size_t yolo9_workspace(void* s, int32_t max_batch) {
+    auto* y = static_cast<Yolo9Layer*>(s);
+    return trtx_yolov9_decode_workspace(max_batch, y->net_h, y->net_w);
+}
+int32_t yolo9_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
+    auto* y = static_cast<Yolo9Layer*>(s);
+    return trtx_yolov9_decode(reinterpret_cast<const float* const*>(inputs), batch, y->class_count, y->net_h, y->net_w, y->max_out, y->seg ? 1 : 0,
+                              static_cast<float*>(outputs[0]), ws, trtx_yolov9_decode_workspace(batch, y->net_h, y->net_w), stream);
+}
+size_t yolo9_ser_size(void* s) { return static_cast<Yolo9Layer*>(s)->blob().size(); }
+void yolo9_serialize(void* s, void* buf) {
+    const auto b = static_cast<Yolo9Layer*>(s)->blob();
+    memcpy(buf, b.data(), b.size());
+}
+int32_t yolo9_clone(void* s, trtx_plugin_vtbl* out) {
+    yolo9_fill(out, new Yolo9Layer(*static_cast<Yolo9Layer*>(s)));
+    return 0;
+}
+void yolo9_destroy(void* s) { delete static_cast<Yolo9Layer*>(s); }
+void yolo9_fill(trtx_plugin_vtbl* v, Yolo9Layer* y) {
+    v->self = y;
+    v->get_nb_outputs = yolo_nb_outputs;
+    v->get_output_dims = yolo9_output_dims;
+    v->configure = yolo9_configure;
+    v->initialize = yolo5_initialize;
+    v->terminate = yolo_terminate;
+    v->workspace_size = yolo9_workspace;
+    v->enqueue = yolo9_enqueue;
+    v->serialization_size = yolo9_ser_size;
+    v->serialize = yolo9_serialize;
+    v->plugin_type = yolo_type;
+    v->plugin_version = yolo_version;
+    v->clone = yolo9_clone;
+    v->destroy = yolo9_destroy;
+}
+int32_t yolo9_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
+    if (!f[0].data || f[0].length != 5) return 1;
+    const int* ni = static_cast<const int*>(f[0].data);
+    if (ni[0] < 1 || ni[1] < 32 || ni[2] < 32 || ni[3] < 1) return 1;
+    auto* y = new Yolo9Layer();
+    y->class_count = ni[0];
+    y->net_w = ni[1];
+    y->net_h = ni[2];
+    y->max_out = ni[3];
+    y->seg = ni[4] != 0;
+    yolo9_fill(out, y);
+    return 0;
+}
+
 // creator: one field "combinedInfo" = int32[9 + nStrides] (yolov8/src/block.cpp:267-293, yololayer.cu:339-360)
 int32_t yolo_create(void*, const char*, const trtx_plugin_field* f, int32_t nb, trtx_plugin_vtbl* out) {
     // the anchor-based plugin shares the registered name: told apart by its two fields "netinfo" + "kernels"
     if (nb == 2 && f && f[0].name && f[1].name && !strcmp(f[0].name, "netinfo") && !strcmp(f[1].name, "kernels")) return yolo5_create(f, out);
+    // ... and so does the YOLOv9 one: its single field is "netinfo"
+    if (nb == 1 && f && f[0].name && !strcmp(f[0].name, "netinfo")) return yolo9_create(f, out);
     if (nb != 1 || !f || !f[0].name || strcmp(f[0].name, "combinedInfo") != 0 || f[0].length < 10) return 1;
     const int* ci = static_cast<const int*>(f[0].data);
     auto* y = new YoloLayer();
@@ -306,8 +410,14 @@ int32_t yolo_deserialize(void*, const char*, const void* data, size_t len, trtx_
     }
     // not the YOLOv8 layout (both parsers check the exact length): the anchor-based blob
     Yolo5Layer* y5 = Yolo5Layer::from_blob(data, len);
-    if (!y5) return 1;
-    yolo5_fill(out, y5);
+    if (y5) {
+        yolo5_fill(out, y5);
+        return 0;
+    }
+    // ... nor the anchor-based one: the YOLOv9 blob, 21 bytes
+    Yolo9Layer* y9 = Yolo9Layer::from_blob(data, len);
+    if (!y9) return 1;
+    yolo9_fill(out, y9);
     return 0;
 }
 const char* yolo_creator_name(void*) { return "YoloLayer_TRT"; }
@@ -509,9 +619,20 @@ bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
     return true;
 }
 
+bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
+    if (v.enqueue != yolo9_enqueue || !v.self) return false;
+    const auto* y = static_cast<const Yolo9Layer*>(v.self);
+    out->classes = y->class_count;
+    out->net_w = y->net_w;
+    out->net_h = y->net_h;
+    out->max_out = y->max_out;
+    out->seg = y->seg;
+    return true;
+}
+
 // built-in plugins only enqueue kernels and stream-ordered memsets on the caller's stream: safe inside a stream capture
 bool builtin_plugin_capturable(const trtx_plugin_vtbl& v) {
-    return v.enqueue == yolo_enqueue || v.enqueue == yolo5_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
+    return v.enqueue == yolo_enqueue || v.enqueue == yolo5_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
 }
 
 void register_builtin_plugins(PluginRegistry& r) {

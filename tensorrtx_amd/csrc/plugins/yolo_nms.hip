@@ -135,6 +135,8 @@ inline NmsWs nms_ws_carve(void* base, int batch) {
 //         cmp() orders by conf only -> ties by slot (the reference's unstable std::sort leaves them unspecified).
 // MODE 2: YOLOv8 host nms_obb() (postprocess.cpp:357-385): (cx, cy, w, h, angle) boxes, "conf <= thresh" dropped, same cmp() as
 //         MODE 0, a later box is erased when probiou(item, box) >= thresh.
+// MODE 3: YOLOv9 host nms() (yolov9/src/postprocess.cpp:48-83): MODE 1 on corner boxes that are first turned into centre format by the
+//         reference's four fp32 operations (:59-62); the sorted records, and so keep_det, hold the centre format like its `res`.
 template <int MODE>
 __global__ __launch_bounds__(kCap) void yolo_nms_sort_kernel(const float* __restrict__ decode, int out_elem, int det_floats,
                                                              int max_out, float conf_thresh, NmsWs ws) {
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(kCap) void yolo_nms_sort_kernel(const float* __rest
         // MODE 0: false for NaN, as "conf <= thresh || isnan" drops (postprocess.cpp:99); MODE 1: only "conf <= thresh" drops
         if (MODE == 0 ? (conf > conf_thresh) : !(conf <= conf_thresh)) {
             hi = ((uint64_t)trtx::ord_f32(det[5]) << 32) | (uint32_t)~trtx::ord_f32(conf);
-            lo = ((uint64_t)(MODE != 1 ? trtx::ord_f32(det[0]) : 0u) << 32) | (uint32_t)tid;
+            lo = ((uint64_t)((MODE == 0 || MODE == 2) ? trtx::ord_f32(det[0]) : 0u) << 32) | (uint32_t)tid;
         }
     }
     // bitonic sort, ascending, 1024 keys
@@ -192,6 +194,7 @@ __global__ __launch_bounds__(kCap) void yolo_nms_sort_kernel(const float* __rest
     if (valid) {
         const float* det = img + 1 + (size_t)orig * det_floats;
         box = make_float4(det[0], det[1], det[2], det[3]);
+        if (MODE == 3) box = make_float4((det[0] + det[2]) / 2, (det[1] + det[3]) / 2, det[2] - det[0], det[3] - det[1]);   // x1x2y1y2 -> xywh
         conf = det[4];
         cls = det[5];
         if (MODE == 2) ang = det[det_floats - 1];  // Detection::angle is the last float of the record
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(kCap) void yolo_nms_mask_kernel(NmsWs ws, float nms
                 if (s_cls[c][k] != my_cls) continue;
                 bool hit;
                 if (MODE == 0) hit = iou_xyxy(s_box[c][k], mine) > nms_thresh;
-                else if (MODE == 1) hit = iou_cxcywh(s_box[c][k], mine) > nms_thresh;
+                else if (MODE == 1 || MODE == 3) hit = iou_cxcywh(s_box[c][k], mine) > nms_thresh;
                 else hit = probiou_host(s_box[c][k], s_ang[c][k], mine, my_ang) >= nms_thresh;
                 if (hit) bits |= 1ull << k;
             }
@@ -501,6 +504,13 @@ extern "C" int32_t trtx_yolov5_nms(const float* decode_out, int batch, int max_o
                                    hipStream_t stream) {
     return run_nms<1>(decode_out, batch, max_out, 38, conf_thresh, nms_thresh, keep_idx, keep_cnt, keep_det, workspace, workspace_bytes,
                       stream, "trtx_yolov5_nms");
+}
+
+extern "C" int32_t trtx_yolov9_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh,
+                                   int32_t* keep_idx, int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes,
+                                   hipStream_t stream) {
+    return run_nms<3>(decode_out, batch, max_out, 38, conf_thresh, nms_thresh, keep_idx, keep_cnt, keep_det, workspace, workspace_bytes,
+                      stream, "trtx_yolov9_nms");
 }
 
 // nms_obb / batch_nms_obb (yolov8/src/postprocess.cpp:357-393): oriented boxes, ProbIoU.  keep_det: [batch][max_out][7] =

@@ -153,7 +153,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
         int32_t st = TRTX_OK;
-        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_ROI_ALIGN);
+        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
@@ -419,6 +419,22 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 }
                 st = (t0.dtype == DT_F32 ? trtx_yolov5_head_decode_nhwc_f32 : trtx_yolov5_head_decode_nhwc)(
                         heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], gw, gh, op.fv.data(), op.i[3],
+                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+                break;
+            }
+            case OP_YOLO9_HEAD: {
+                const void* box[3];
+                const void* cls[3];
+                int box_ld[3], cls_ld[3];
+                if (op.i[4] != 3 || op.in.size() != 3 || op.extra_in.size() != 3) { st = TRTX_ERR_STATE; break; }
+                for (int k = 0; k < 3; ++k) {
+                    box[k] = R.ptr(op.in[k]);
+                    box_ld[k] = plan.tensors[op.in[k]].ld;
+                    cls[k] = R.ptr(op.extra_in[k]);
+                    cls_ld[k] = plan.tensors[op.extra_in[k]].ld;
+                }
+                st = (t0.dtype == DT_F32 ? trtx_yolov9_head_decode_nhwc_f32 : trtx_yolov9_head_decode_nhwc)(
+                        box, box_ld, cls, cls_ld, batch, op.i[0], op.i[1], op.i[2], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
                 break;
             }

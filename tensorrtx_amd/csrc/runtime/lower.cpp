@@ -240,6 +240,31 @@ struct Lowerer {
         return true;
     }
 
+    // The DDetect head at its plugin's layer: the box and class convolutions' NHWC tensors in (`in` = boxes, `extra_in` = classes), the
+    // plugin's LINEAR output out; the DFL weights come from src_layer like OP_YOLO_HEAD's.
+    bool emit_yolo9_head(const Yolo9HeadFuse& f) {
+        const LayerDef& l = net.layers[f.plugin_layer];
+        const Yolo9LayerParams& pr = f.params;
+        std::vector<int> boxes, clss;
+        for (int t : f.box_tensor) boxes.push_back(need_nhwc(t));
+        for (int t : f.cls_tensor) clss.push_back(need_nhwc(t));
+        const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
+        POp& op = add_op(OP_YOLO9_HEAD, l.name + " [fused DFL+decode, 38-float records]", boxes, {out});
+        op.extra_in = clss;
+        op.src_layer = f.dfl_conv_layer;
+        op.i[0] = pr.classes;
+        op.i[1] = pr.net_h;
+        op.i[2] = pr.net_w;
+        op.i[3] = pr.max_out;
+        op.i[4] = (int)boxes.size();
+        op.ws_bytes = trtx_yolov9_head_decode_workspace(plan.max_batch, pr.net_h, pr.net_w);
+        // what it must read: every class logit, the box bins of the survivors only (not counted), and what it writes
+        for (int t : clss) op.bytes += (double)dtype_size(dt) * plan.tensors[t].H * plan.tensors[t].W * pr.classes;
+        op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
+        pt_of[l.outputs[0]] = out;
+        return true;
+    }
+
     // ---- per-kind emission ----------------------------------------------------------------------------
     bool emit_conv(const FusedConv& c) {
         const LayerDef& l = net.layers[c.conv_layer];
@@ -838,6 +863,10 @@ struct Lowerer {
             }
             if (fu.yolo5_at[li] >= 0) {
                 if (!emit_yolo5_head(fu.yolo5_heads[fu.yolo5_at[li]])) return false;
+                continue;
+            }
+            if (fu.yolo9_at[li] >= 0) {
+                if (!emit_yolo9_head(fu.yolo9_heads[fu.yolo9_at[li]])) return false;
                 continue;
             }
             if (fu.attn_at[li] >= 0) {

@@ -306,6 +306,99 @@ void match_yolo5_heads(const NetView& g, Fusions& f) {
     }
 }
 
+// ---- YOLOv9 / GELAN detect tail (yolov9/src/block.cpp:424-489): per level the concat of [DFL chain on the grouped 1x1 convolution's
+// (64, gh, gw) output, reshape (classes, gh * gw) of the class convolution's output] into the YOLOv9 YoloLayer_TRT.  Unlike YOLOv8's tail
+// the two branches end in two different convolutions, so there is no flatten and no slice to match.  When the plugin is the built-in one
+// without mask coefficients, every intermediate tensor has no other reader and is no network output, the DFL convolution has 16 weights
+// (the same on every level) and no bias, and the grids are the tensors', the whole tail becomes one OP_YOLO9_HEAD on the two NHWC tensors
+// per level (fp16 and fp32 engines).  pad_cout marks the class convolutions, so that a class count that is no 16-byte multiple keeps their
+// vector stores.  Anything else keeps the plugin: marked heads, a second reader, a kINT8 engine, TRTX_YOLO9_HEAD=0.  Implicit batch, as the reference builds.
+void match_yolo9_heads(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    // kINT8 engines keep the plugin route too: the fused op reads fp16 or fp32 tensors, and the int8 assignment does not see its class
+    // tensors (they are extra inputs), so a calibrated class convolution would hand it int8 values
+    if (!g.opt.yolo9_head || net.explicit_batch || net.int8) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li] || !l.plugin) continue;
+        Yolo9HeadFuse h;
+        if (!builtin_yolo9_params(l.plugin->v, &h.params)) continue;
+        const Yolo9LayerParams& pr = h.params;
+        if (pr.seg || pr.classes < 1 || l.inputs.size() != 3) continue;
+        std::vector<int> used;
+        bool ok = true;
+        for (size_t k = 0; ok && k < l.inputs.size(); ++k) {
+            ok = false;
+            const int64_t gh = pr.net_h / (8 << k), gw = pr.net_w / (8 << k), ng = gh * gw;
+            const int t_in = l.inputs[k];
+            const int lc = g.producer(t_in);
+            if (lc < 0 || net.layers[lc].kind != L_CONCAT || net.layers[lc].inputs.size() != 2 || net.layers[lc].axis != 0 ||
+                !g.only_used_by(t_in, {(int)li}))
+                break;
+            const int ta = net.layers[lc].inputs[0], tb = net.layers[lc].inputs[1];
+            // box branch, from the concat back to the convolution: shuffle (4, ng) <- 1x1 conv <- softmax <- shuffle (16, 4, ng)
+            const int lsh2 = g.producer(ta);
+            if (lsh2 < 0 || net.layers[lsh2].kind != L_SHUFFLE || !g.only_used_by(ta, {lc})) break;
+            const LayerDef& sh2 = net.layers[lsh2];
+            const Dims& d2 = net.tensors[ta].dims;
+            if (d2.nb != 2 || d2.d[0] != 4 || d2.d[1] != ng || !ident(sh2.perm1, 3) || !ident(sh2.perm2, 2)) break;
+            const int tconv = sh2.inputs[0];
+            const int lconv = g.producer(tconv);
+            if (lconv < 0 || net.layers[lconv].kind != L_CONV || !g.only_used_by(tconv, {lsh2})) break;
+            const LayerDef& cv = net.layers[lconv];
+            if (cv.nb_out != 1 || cv.kernel[0] != 1 || cv.kernel[1] != 1 || cv.groups != 1 || cv.stride[0] != 1 || cv.stride[1] != 1 ||
+                cv.padding[0] != 0 || cv.padding[1] != 0 || cv.w0.size() != 16 || !cv.w1.empty())
+                break;
+            if (h.dfl_conv_layer >= 0 && cv.w0 != net.layers[h.dfl_conv_layer].w0) break;   // one DFL kernel for all levels
+            const int tsm = cv.inputs[0];
+            const int lsm = g.producer(tsm);
+            if (lsm < 0 || net.layers[lsm].kind != L_SOFTMAX || !g.only_used_by(tsm, {lconv})) break;
+            if (!(net.layers[lsm].axis < 0 || net.layers[lsm].axis == 1)) break;
+            const int tsh1 = net.layers[lsm].inputs[0];
+            const int lsh1 = g.producer(tsh1);
+            if (lsh1 < 0 || net.layers[lsh1].kind != L_SHUFFLE || !g.only_used_by(tsh1, {lsm})) break;
+            const LayerDef& sh1 = net.layers[lsh1];
+            const Dims& d1 = net.tensors[tsh1].dims;
+            if (d1.nb != 3 || d1.d[0] != 16 || d1.d[1] != 4 || d1.d[2] != ng || !ident(sh1.perm1, 3) || sh1.reshape.nb != 3 ||
+                !perm_is(sh1.perm2, {1, 0, 2}))
+                break;
+            const int tbox = sh1.inputs[0];
+            const int lbox = g.producer(tbox);
+            const Dims& db = net.tensors[tbox].dims;
+            if (lbox < 0 || net.layers[lbox].kind != L_CONV || !g.only_used_by(tbox, {lsh1}) || db.nb != 3 || db.d[0] != 64 || db.d[1] != gh ||
+                db.d[2] != gw)
+                break;
+            // class branch: a reshape-only shuffle of a convolution's (classes, gh, gw) output
+            const int lshc = g.producer(tb);
+            if (lshc < 0 || net.layers[lshc].kind != L_SHUFFLE || !g.only_used_by(tb, {lc})) break;
+            const LayerDef& shc = net.layers[lshc];
+            const Dims& dc = net.tensors[tb].dims;
+            if (dc.nb != 2 || dc.d[0] != pr.classes || dc.d[1] != ng || !ident(shc.perm1, 3) || !ident(shc.perm2, 2)) break;
+            const int tcls = shc.inputs[0];
+            const int lcls = g.producer(tcls);
+            const Dims& dk = net.tensors[tcls].dims;
+            if (lcls < 0 || net.layers[lcls].kind != L_CONV || !g.only_used_by(tcls, {lshc}) || dk.nb != 3 || dk.d[0] != pr.classes ||
+                dk.d[1] != gh || dk.d[2] != gw || net.layers[lcls].nb_out != pr.classes || tcls == tbox)
+                break;
+            h.dfl_conv_layer = lconv;
+            h.box_tensor.push_back(tbox);
+            h.cls_tensor.push_back(tcls);
+            h.cls_conv.push_back(lcls);
+            for (int u : {lc, lsh2, lconv, lsm, lsh1, lshc}) used.push_back(u);
+            if (f.absorbed[lbox] || f.absorbed[lcls]) break;
+            ok = true;
+        }
+        for (int u : used) ok = ok && !f.absorbed[u];
+        if (!ok) continue;
+        for (int u : used) f.absorbed[u] = true;
+        h.plugin_layer = (int)li;
+        f.absorbed[li] = true;
+        for (int lc : h.cls_conv) f.pad_cout[lc] = true;
+        f.yolo9_at[li] = (int)f.yolo9_heads.size();
+        f.yolo9_heads.push_back(h);
+    }
+}
+
 // ---- attention: what the YOLO11 PSA block and the YOLOv12 area attention share, from the first matmul to the second one:
 // x (B', heads, 2kd+hd, N') -> q / k / v slices of rows -> q^T k -> uniform scale -> softmax over the keys -> v @ attn^T.
 // Every shape, permutation, slice and the scale are checked and q, k and the scores must have no other reader.  How the qkv image
@@ -480,16 +573,17 @@ void match_area_attention(const NetView& g, Fusions& f) {
 }  // namespace
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
-// (before conv fusion: they claim the DFL 1x1 convolutions), the anchor head (it claims its plugin layer only), PSA attention, area
+// and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor head (it claims its plugin layer only), PSA attention, area
 // attention, convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
     f.pad_cout.assign(nl, false);
-    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = std::vector<int>(nl, -1);
+    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
+    match_yolo9_heads(g, f);
     match_yolo5_heads(g, f);
     match_psa_attention(g, f);
     match_area_attention(g, f);

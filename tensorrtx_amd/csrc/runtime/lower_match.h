@@ -38,6 +38,15 @@ struct Yolo5HeadFuse {
     Yolo5LayerParams params;
 };
 
+struct Yolo9HeadFuse {
+    int plugin_layer = -1;
+    std::vector<int> box_tensor;    // network tensor per level: the grouped 1x1 convolution's output (64, gh, gw)
+    std::vector<int> cls_tensor;    // ... and the class convolution's output (classes, gh, gw)
+    std::vector<int> cls_conv;      // the layers that produce the class tensors
+    int dfl_conv_layer = -1;
+    Yolo9LayerParams params;
+};
+
 struct AttentionFuse {
     int qkv = -1;                    // network tensor: the qkv convolution's output (B, heads*(2kd+hd), H, W)
     int out_o = -1, out_v = -1;      // network tensors: O reshaped to (B, heads*hd, H, W), and v reshaped the same way
@@ -52,8 +61,9 @@ struct Fusions {
     std::vector<YoloHeadFuse> yolo_heads;
     std::vector<AttentionFuse> attns;
     std::vector<Yolo5HeadFuse> yolo5_heads;
-    std::vector<int> group_at, yolo_at, attn_at, yolo5_at;
-    std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor head: its output channels round up to 16 bytes
+    std::vector<Yolo9HeadFuse> yolo9_heads;
+    std::vector<int> group_at, yolo_at, attn_at, yolo5_at, yolo9_at;
+    std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor or DDetect head: its output channels round up to 16 bytes
     std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own
     std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src
 };

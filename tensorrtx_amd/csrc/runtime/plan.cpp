@@ -10,8 +10,8 @@ const char* op_kind_name(int k) {
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
-                              "yolo_task_head", "yolo5_head"};
-    return (k >= 0 && k <= OP_YOLO5_HEAD) ? n[k] : "?";
+                              "yolo_task_head", "yolo5_head", "yolo9_head"};
+    return (k >= 0 && k <= OP_YOLO9_HEAD) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -64,6 +64,17 @@ std::string Plan::describe_json() const {
             for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]";
             o << "],\"ld\":[";
             for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
+            o << "]";
+        }
+        if (op.kind == OP_YOLO9_HEAD) {
+            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"grids\":[";
+            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.i[2] / (8 << j) << "," << op.i[1] / (8 << j) << "]";
+            o << "],\"strides\":[";
+            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << (8 << j);
+            o << "],\"box_ld\":[";
+            for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
+            o << "],\"cls_ld\":[";
+            for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
             o << "]";
         }
         if (op.kind == OP_CONV_GROUP) {

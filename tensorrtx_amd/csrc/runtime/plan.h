@@ -52,6 +52,9 @@ enum OpKind : int {
                         // i as OP_YOLO_HEAD with at most 4 strides in i[5..8], i[9] = 1 seg / 2 pose / 3 obb, i[10] = keypoints, f[0] = kpt_conf
     OP_YOLO5_HEAD,      // fused anchor-based YoloLayer decode (YOLOv5) on the detect convolutions' NHWC output (plugins/yolo5_head.hip): i[0] = classes,
                         // i[1] / i[2] = net h / w, i[3] = max_out, i[4] = levels, i[11] as OP_YOLO_HEAD; iv = (grid_w, grid_h) per level, fv = 6 anchors per level
+    OP_YOLO9_HEAD,      // fused DFL + YOLOv9 YoloLayer decode (38-float records) on the NHWC outputs of the head's last convolutions (plugins/yolo9_head.hip):
+                        // `in` = the three box tensors (64 DFL bins), `extra_in` = the three class tensors; i[0] = classes, i[1] / i[2] = net h / w,
+                        // i[3] = max_out, i[4] = levels (3: strides 8 / 16 / 32); src_layer = the DFL 1x1 convolution
 };
 const char* op_kind_name(int k);
 

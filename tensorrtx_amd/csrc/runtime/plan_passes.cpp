@@ -67,7 +67,9 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
         // two-taps-per-step form (CinK = 16; its second tap lies outside the 1x1 filter and loads zeros) streams with 16-byte accesses.
         // Wider outputs over 16 channels (the qkv convolutions of the attention test graphs) keep the direct kernel: nothing measured
         // says otherwise.  Not in kINT8 engines either, where such a layer stays the fp16 island it has been.
-        ok = ok && (a.kh * a.kw * cin_eff >= 32 || (!e.int8 && a.kh == 1 && a.kw == 1 && a.Cin == 16 && a.Cout == 16));
+        // The square 1x1 over 24 channels is the same case one k-step wider (CinK = 32, channels 24 .. 31 load zeros like the last channels of
+        // any Cin that is no multiple of the step): the 1x1 branch of YOLOv9t's RepConvN on its 24-channel RepNCSP blocks, 18 layers.
+        ok = ok && (a.kh * a.kw * cin_eff >= 32 || (!e.int8 && a.kh == 1 && a.kw == 1 && (a.Cin == 16 || a.Cin == 24) && a.Cout == a.Cin));
         if (ok) {
             ConvArgs t = a;
             t.scalar_out = vec_out ? 0 : 1;
@@ -766,7 +768,7 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
     for (int k = 0; k < nops; ++k) {
         const int kind = plan.ops[k].kind;
-        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD && kind != OP_YOLO5_HEAD) || plan.ops[k].ws_bytes == 0) continue;
+        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD && kind != OP_YOLO5_HEAD && kind != OP_YOLO9_HEAD) || plan.ops[k].ws_bytes == 0) continue;
         Storage s;
         s.kind = ST_ARENA;
         s.bytes = plan.ops[k].ws_bytes;

@@ -98,6 +98,13 @@ struct Yolo5LayerParams {
     std::vector<float> anchors;        // per level 6 floats
 };
 bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
+// parameters of a *built-in* YOLOv9 YoloLayer_TRT instance (the single field "netinfo"; false for anything else): lets the lowering pass
+// replace the DFL chains, layout passes and the plugin by the fused DDetect head.  Three levels, strides 8 / 16 / 32.
+struct Yolo9LayerParams {
+    int classes, net_w, net_h, max_out;
+    bool seg;
+};
+bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out);
 // true for the built-in "Mish_TRT" (plugins/builtin_plugins.cpp; yolov4/mish.{h,cu}): a pointwise activation, which the lowering pass
 // folds into the producing convolution's epilogue (ACT_MISH) or runs as an activation op in the tensor's own layout
 bool builtin_is_mish(const trtx_plugin_vtbl& v);

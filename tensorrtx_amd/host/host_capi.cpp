@@ -44,6 +44,8 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
     std::unique_ptr<IBuilder> builder(createInferBuilder(logger));
     std::unique_ptr<IBuilderConfig> config(builder->createBuilderConfig());
     std::unique_ptr<IInt8Calibrator> calibrator;
+    const bool yolov9 = trtx_host::yolov9_model_valid(model, false);   // yolov9t / s / m / c, gelanc
+    if (yolov9 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;      // no INT8 YOLOv9 is built
     if (geti(o, "int8", 0)) {  // USE_INT8 of the reference builders (yolov8/src/model.cpp:317-324, retinaface/retina_r50.cpp:219-225)
         if (!builder->platformHasFastInt8()) return TRTX_ERR_UNSUPPORTED;
         config->setFlag(BuilderFlag::kINT8);
@@ -135,6 +137,22 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < top || cfg.input_w < top || cfg.input_h % top || cfg.input_w % top)
             return TRTX_ERR_INVALID;
         plan.reset(trtx_host::buildEngineYolov5(builder.get(), config.get(), wts_path, cfg));
+    } else if (yolov9) {
+        trtx_host::Yolov9Config cfg;
+        cfg.model = m;
+        cfg.max_batch = geti(o, "batch", 1);
+        cfg.fp16 = geti(o, "fp16", 1) != 0;
+        cfg.input_h = geti(o, "h", 640);
+        cfg.input_w = geti(o, "w", 640);
+        cfg.num_class = geti(o, "classes", 80);
+        cfg.max_out_bbox = geti(o, "max_out", 1000);
+        cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
+        cfg.converted = geti(o, "converted", 0) != 0;   // isConvert: t / s / m only
+        if (geti(o, "task", 0) != 0 || !trtx_host::yolov9_model_valid(m, cfg.converted)) return TRTX_ERR_INVALID;
+        // the three pyramid levels (strides 8 / 16 / 32) meet only on sizes that 32 divides
+        if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < 32 || cfg.input_w < 32 || cfg.input_h % 32 || cfg.input_w % 32)
+            return TRTX_ERR_INVALID;
+        plan.reset(trtx_host::buildEngineYolov9(builder.get(), config.get(), wts_path, cfg));
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);

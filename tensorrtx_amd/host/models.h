@@ -116,6 +116,27 @@ inline nvinfer1::IHostMemory* buildEngineYolov5Det(nvinfer1::IBuilder* builder, 
     return buildEngineYolov5(builder, config, wts, cfg);
 }
 
+// yolov9/include/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
+// setMaxBatchSize).  Detection only.
+struct Yolov9Config {
+    std::string model = "yolov9t";      // "yolov9t" / "yolov9s" / "yolov9m" / "yolov9c" / "gelanc": the build_engine_* function (yolov9/src/model.cpp)
+    int input_h = 640, input_w = 640;   // kInputH / kInputW
+    int num_class = 80;                 // kNumClass
+    int max_batch = 1;                  // kBatchSize
+    int max_out_bbox = 1000;            // kMaxNumOutputBbox
+    bool fp16 = true;                   // USE_FP16
+    bool converted = false;             // isConvert (t / s / m): the re-parameterised checkpoint without the auxiliary branch: its "model.N"
+                                        // numbering and DDetect instead of DualDDetect
+    bool mark_heads = false;            // debugging: also expose the three plugin inputs (4 + classes, cells) as outputs "head0..2"
+};
+// what the builder accepts: the five names, `converted` on t / s / m only (trtx_host_build answers TRTX_ERR_INVALID where it is false)
+bool yolov9_model_valid(const std::string& name, bool converted);
+// yolov9/src/model.cpp:25-176 (t), 178-320 (s), 321-555 (m), 557-740 (c), 1160-1286 (gelan-c) with yolov9/src/block.cpp.  Input "images",
+// output "output": 1 + max_out * 38 floats.  Layers the reference creates and never connects to the output are not created
+// (host/yolov9.cpp).  Returns null where yolov9_model_valid is false.
+nvinfer1::IHostMemory* buildEngineYolov9(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                         const Yolov9Config& cfg);
+
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {
     int input_h = 800, input_w = 1067;      // INPUT_H / INPUT_W: 480x640 resized by calculateSize() (rcnn.cpp:349-366)

@@ -747,3 +747,144 @@ def yolov5_state(scale="n", seed=0, num_class=80, p6=False, task=0):
 
 
 STATE["yolov8n"] = yolov8n_state
+
+
+# The arguments of the reference's builders (yolov9/src/model.cpp:35-109 t, 188-254 s, 334-435 m, 568-645 c, 1171-1248 gelan-c), in the
+# order of the main branch.  "L<k>" is the layer whose weights are model.<k + first>.  rep = (c2, c3, c4, n) of RepNCSPELAN4.
+YOLOV9_SPECS = {
+    "yolov9t": dict(stem=(16, 32), elan1=True, b2=(32, 32, 16, 0), adown=False, down=(64, 96, 128), rep=((64, 64, 32, 3), (96, 96, 48, 3), (128, 128, 64, 3)),
+                    spp=(128, 64), r12=(96, 96, 48, 3), r15=(64, 64, 32, 3), d16=48, r18=(96, 96, 48, 3), d19=64, r21=(128, 128, 64, 3), aux=False),
+    "yolov9s": dict(stem=(32, 64), elan1=True, b2=(64, 64, 32, 0), adown=False, down=(128, 192, 256), rep=((128, 128, 64, 3), (192, 192, 96, 3), (256, 256, 128, 3)),
+                    spp=(256, 128), r12=(192, 192, 96, 3), r15=(128, 128, 64, 3), d16=96, r18=(192, 192, 96, 3), d19=128, r21=(256, 256, 128, 1), aux=False),
+    "yolov9m": dict(stem=(32, 64), elan1=False, b2=(128, 128, 64, 1), adown=False, down=(240, 360, 480), rep=((240, 240, 120, 1), (360, 360, 180, 1), (480, 480, 240, 1)),
+                    spp=(480, 240), r12=(360, 360, 180, 1), r15=(240, 240, 120, 1), d16=184, r18=(360, 360, 180, 1), d19=240, r21=(480, 480, 240, 1), aux=True),
+    "yolov9c": dict(stem=(64, 128), elan1=False, b2=(256, 128, 64, 1), adown=True, down=(256, 512, 512), rep=((512, 256, 128, 1), (512, 512, 256, 1), (512, 512, 256, 1)),
+                    spp=(512, 256), r12=(512, 512, 256, 1), r15=(256, 256, 128, 1), d16=256, r18=(512, 512, 256, 1), d19=512, r21=(512, 512, 256, 1), aux=True),
+}
+YOLOV9_SPECS["gelanc"] = dict(YOLOV9_SPECS["yolov9c"], aux=False)
+YOLOV9_CLS_GAIN = 800.0   # He gain of the class rows (yolo11_state's): these random backbones give features that vary little over an image
+YOLOV9_CLS_BIAS = -9.5    # ... around this bias 4 - 36 % of the cells pass the plugin's 0.1 gate (counts: tests/test_gpu_yolov9.py)
+YOLOV9_CLS_BIAS_OF = {"gelanc": -11.5}   # ... but for gelan-c, whose largest logit per cell lies two units higher: -9.5 passes 70 % of its cells, -11.5 4 - 15 %
+
+
+def yolov9_state(name="yolov9t", seed=0, num_class=80, converted=False):
+    """Seeded synthetic weights of yolov9t / yolov9s / yolov9m / yolov9c / gelanc under the reference's `.wts` key names (the state_dict
+    keys gen_wts.py writes, read by yolov9/src/block.cpp / model.cpp): OrderedDict name -> fp32 array.  Only the layers the host builder
+    reads are there: the main branch and the head (model.29 DualDDetect, or model.22 DDetect when `converted`) for t / s, the backbone,
+    the auxiliary branch and model.38 for unconverted m and for c, the main branch and model.22 for converted m and gelan-c.  `converted`
+    is the reference's isConvert (t / s / m).  He-scaled convolutions with near-identity BatchNorm statistics (the yolo11_state recipe);
+    the box rows have gain 4 around a bias of 1, the class rows YOLOV9_CLS_GAIN around YOLOV9_CLS_BIAS (YOLOV9_CLS_BIAS_OF for gelanc), so that every image keeps
+    candidates well above zero and well below the cell count."""
+    import math
+    from collections import OrderedDict
+
+    import torch
+    sp = YOLOV9_SPECS[name]
+    assert not (converted and name in ("yolov9c", "gelanc")), "converted: yolov9t / s / m only"
+    aux = sp["aux"] and not converted
+    first = 1 if aux else 0
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+    M = lambda k: f"model.{k + first}"                       # noqa: E731
+
+    def conv(key, cout, cin, k, gain=2.0):
+        sd[key + ".weight"] = (randn(cout, cin, k, k) * math.sqrt(gain / (cin * k * k))).float()
+
+    def cb(key, cout, cin, k, groups=1, gain=2.0):  # Conv + BatchNorm (+ SiLU)
+        conv(key + ".conv", cout, cin // groups, k, gain)
+        sd[key + ".bn.weight"] = (0.9 + 0.2 * rand(cout)).float()
+        sd[key + ".bn.bias"] = (0.1 * randn(cout)).float()
+        sd[key + ".bn.running_mean"] = (0.1 * randn(cout)).float()
+        sd[key + ".bn.running_var"] = (0.8 + 0.4 * rand(cout)).float()
+        sd[key + ".bn.num_batches_tracked"] = torch.zeros(1)
+
+    def repncsp(key, c1, c2, n):
+        c_ = c2 // 2
+        cb(key + ".cv1", c_, c1, 1)
+        for i in range(n):
+            cb(f"{key}.m.{i}.cv1.conv1", c_, c_, 3, gain=1.0)   # RepConvN: the two branches are summed before the SiLU
+            cb(f"{key}.m.{i}.cv1.conv2", c_, c_, 1, gain=1.0)
+            cb(f"{key}.m.{i}.cv2", c_, c_, 3)
+        cb(key + ".cv2", c_, c1, 1)
+        cb(key + ".cv3", c2, 2 * c_, 1)
+
+    def elan1(key, c1, c2, c3, c4):
+        cb(key + ".cv1", c3, c1, 1)
+        cb(key + ".cv2", c4, c3 // 2, 3)
+        cb(key + ".cv3", c4, c4, 3)
+        cb(key + ".cv4", c2, c3 + 2 * c4, 1)
+
+    def rep(key, c1, r):
+        c2, c3, c4, n = r
+        cb(key + ".cv1", c3, c1, 1)
+        repncsp(key + ".cv2.0", c3 // 2, c4, n)
+        cb(key + ".cv2.1", c4, c4, 3)
+        repncsp(key + ".cv3.0", c4, c4, n)
+        cb(key + ".cv3.1", c4, c4, 3)
+        cb(key + ".cv4", c2, c3 + 2 * c4, 1)
+        return c2
+
+    def down(key, c1, c2):
+        if sp["adown"]:
+            cb(key + ".cv1", c2 // 2, c1 // 2, 3)
+            cb(key + ".cv2", c2 // 2, c1 // 2, 1)
+        else:
+            cb(key + ".cv1", c2, c1, 3)
+        return c2
+
+    def block2(key, c1):
+        if sp["elan1"]:
+            elan1(key, c1, *sp["b2"][:3])
+            return sp["b2"][0]
+        return rep(key, c1, sp["b2"])
+
+    def cblinear(key, c1, c2s):
+        conv(key + ".conv", sum(c2s), c1, 1, gain=1.0)
+        sd[key + ".conv.bias"] = (0.1 * randn(sum(c2s))).float()
+
+    d3, d5, d7 = sp["down"]
+    cb(M(0), sp["stem"][0], 3, 3)
+    cb(M(1), sp["stem"][1], sp["stem"][0], 3)
+    c = block2(M(2), sp["stem"][1])
+    c4 = rep(M(4), down(M(3), c, d3), sp["rep"][0])
+    c6 = rep(M(6), down(M(5), c4, d5), sp["rep"][1])
+    c8 = rep(M(8), down(M(7), c6, d7), sp["rep"][2])
+    if not aux:
+        cb(M(9) + ".cv1", sp["spp"][1], c8, 1)
+        cb(M(9) + ".cv5", sp["spp"][0], 4 * sp["spp"][1], 1)
+        c9 = sp["spp"][0]
+        c12 = rep(M(12), c9 + c6, sp["r12"])
+        c15 = rep(M(15), c12 + c4, sp["r15"])
+        c18 = rep(M(18), down(M(16), c15, sp["d16"]) + c12, sp["r18"])
+        c21 = rep(M(21), down(M(19), c18, sp["d19"]) + c9, sp["r21"])
+        feats = (c15, c18, c21)
+        dual = sp["elan1"] and not converted
+        det = "model.29" if dual else "model.22"
+    else:
+        cblinear(M(22), c4, [d3])
+        cblinear(M(23), c6, [d3, d5])
+        cblinear(M(24), c8, [d3, d5, d7])
+        cb(M(25), sp["stem"][0], 3, 3)
+        cb(M(26), sp["stem"][1], sp["stem"][0], 3)
+        c = rep(M(27), sp["stem"][1], sp["b2"])
+        a31 = rep(M(30), down(M(28), c, d3), sp["rep"][0])
+        a34 = rep(M(33), down(M(31), a31, d5), sp["rep"][1])
+        a37 = rep(M(36), down(M(34), a34, d7), sp["rep"][2])
+        feats = (a31, a34, a37)
+        dual = True
+        det = M(37)
+    c2 = max(feats[0] // 4, 64)
+    c3 = max(feats[0], min(num_class * 2 if dual else num_class, 128))
+    for lv, cin in enumerate(feats):
+        cb(f"{det}.cv2.{lv}.0", c2, cin, 3)
+        cb(f"{det}.cv2.{lv}.1", c2, c2, 3, groups=4)
+        conv(f"{det}.cv2.{lv}.2", 64, c2 // 4, 1, gain=4.0)
+        sd[f"{det}.cv2.{lv}.2.bias"] = (1.0 + 0.1 * randn(64)).float()
+        cb(f"{det}.cv3.{lv}.0", c3, cin, 3)
+        cb(f"{det}.cv3.{lv}.1", c3, c3, 3)
+        conv(f"{det}.cv3.{lv}.2", num_class, c3, 1, gain=YOLOV9_CLS_GAIN)
+        sd[f"{det}.cv3.{lv}.2.bias"] = (YOLOV9_CLS_BIAS_OF.get(name, YOLOV9_CLS_BIAS) + 0.1 * randn(num_class)).float()
+    sd[det + ".dfl.conv.weight"] = torch.arange(16.0).reshape(1, 16, 1, 1)
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
