@@ -120,7 +120,8 @@ int32_t trtx_yolo_nms(const float* decode_out, int batch, int max_out, float con
 
 
 /*
- * Anchor-based YoloLayer (YOLOv5 / v7 / v3 / v4 family) - the reference's yolov5/plugin/yololayer.cu:161-227.
+ * Anchor-based YoloLayer (YOLOv5 / v3 / v4 family; YOLOv7's 6-float records: trtx_yolov7_decode below) - the reference's
+ * yolov5/plugin/yololayer.cu:161-227.
  *   inputs     n_levels device pointers, fp32 [batch][3 * (5 + classes (+ 32 if is_segmentation))][grid_h * grid_w]
  *   grid_w/h   per level (YoloKernel::width / height, yolov5/src/types.h:5-9); anchors: n_levels x 6 floats (w0,h0,w1,h1,w2,h2)
  *   output     device, fp32 [batch][1 + max_out * 38]: count (clamped to max_out), then Detection records of 38 floats
@@ -145,6 +146,36 @@ int32_t trtx_yolov5_head_decode_nhwc(const void* const* heads, const int* ld, in
                                      void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /* The same on the NHWC fp32 head tensors of an fp32 engine: ld in floats. */
 int32_t trtx_yolov5_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                         const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                         void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * YOLOv7 YoloLayer - the reference's yolov7/plugin/yololayer.cu:152-207 (CalDetection + forwardGpu).  The arithmetic is the YOLOv5
+ * plugin's; the record is not: Detection is bbox[4], conf, class_id (yolov7/include/types.h), 6 floats, and there is no mask branch.
+ *   inputs     n_levels (1..8) device pointers, fp32 [batch][3 * (5 + classes)][grid_h * grid_w]
+ *   grid_w/h   per level (YoloKernel::width / height); anchors: n_levels x 6 floats (w0,h0,w1,h1,w2,h2)
+ *   output     device, fp32 [batch][1 + max_out * 6]: count (clamped to max_out), then records cx, cy, w, h, conf = obj * cls,
+ *              class_id at float 1 + 6 * slot.  Nothing of a row is written behind its records.
+ * Candidates with !(sigmoid(obj) < 0.1) in canonical (level, cell, anchor) order (the reference: atomicAdd race).
+ */
+size_t trtx_yolov7_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels);
+int32_t trtx_yolov7_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
+                           const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output, void* workspace,
+                           size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Fused YOLOv7 head: trtx_yolov7_decode on the detect convolutions' own NHWC output, what the engine uses instead of one layout pass
+ * per level followed by YoloLayerPlugin::enqueue (yolov7/src/block.cpp:220-255, yololayer.cu:152-207).
+ *   heads[l]   device fp16 [batch][grid_h[l] * grid_w[l]][ld[l]]; channel k * (5 + classes) + j of a pixel = value j of anchor k
+ *              (x, y, w, h, objectness, class logits); ld[l] >= 3 * (5 + classes), channels beyond that are padding and never read
+ *              into a result.  Rows whose base and ld are multiples of 16 bytes are read with 16-byte loads, others element-wise.
+ *   `heads`, `ld`, `grid_w`, `grid_h` and `anchors` are HOST arrays.  Output, candidate order and arithmetic: trtx_yolov7_decode.
+ *   A refused call (TRTX_ERR_INVALID, TRTX_ERR_WORKSPACE) writes neither the output nor the workspace.
+ */
+size_t trtx_yolov7_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels);
+int32_t trtx_yolov7_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                     const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                     void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* The same on the NHWC fp32 head tensors of an fp32 engine: ld in floats. */
+int32_t trtx_yolov7_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
                                          const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
                                          void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /*
@@ -190,6 +221,10 @@ int32_t trtx_yolov5_nms(const float* decode_out, int batch, int max_out, float c
  * dropped, each box turned into centre format by the reference's four fp32 operations (:59-62), then the YOLOv5 iou and conf-descending
  * class-wise suppression.  Same outputs / workspace as trtx_yolov5_nms; keep_det holds the centre-format boxes, as the reference's res. */
 int32_t trtx_yolov9_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
+                        int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* YOLOv7 host nms() / batch_nms() on the GPU (yolov7/src/postprocess.cpp:48-89): trtx_yolov5_nms on records of 6 floats
+ * ([batch][1 + max_out * 6], the YOLOv7 engines' "prob").  Same outputs / workspace: keep_idx, keep_cnt, keep_det[batch][max_out][6]. */
+int32_t trtx_yolov7_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
                         int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /*
  * Mask assembly of the seg programs: the coefficient x prototype loop of the host process_mask with its get_downscale_rect
@@ -360,6 +395,10 @@ int32_t trtx_op_conv_stem_pair_f16(const float* in, int N, int C, int H, int W, 
  * 7 / 8 = the resident-operand 3x3 / 1x1 kernels of conv_res.hip, channels per k-step: 16 / 32} - entry 0 the launcher's own choice, every entry the same bits -;
  * tile4 pins one for this call (NULL: the launcher's choice).  `bias` (may be NULL) holds cout_pad floats (trtx_conv_packed_dims_f32; Cout rounded up to 16), 16-byte
  * aligned: the tile starts its accumulators with 16-byte loads of it up to the padded width - a [Cout] array with Cout % 16 != 0 would be read past its end. */
+/* The filter of a convolution that absorbed the ReOrg in front of it (yolov7/src/block.cpp:106-114: four stride-2 slices of x
+ * concatenated, then a kh x kw stride-1 padding-p convolution): w_kcrs [cout][4 cin][kh][kw] -> folded [cout][cin][2kh][2kw], the filter
+ * of the equal stride-2 padding-2p convolution of x, folded[o][c][2i + dy][2j + dx] = w[o][q cin + c][i][j], q = 2 dx + dy.  Host arrays. */
+int32_t trtx_reorg_fold_weights(const float* w_kcrs, int cout, int cin, int kh, int kw, float* folded);
 int32_t trtx_conv_packed_dims_f32(int cout, int cin_pad, int kh, int kw, int32_t* cout_pad, int32_t* kpad, int32_t* cink);
 int32_t trtx_conv_pack_weights_f32(const float* w_kcrs, int cout, int cin, int kh, int kw, int cin_pad, const float* ch_scale, float* packed);
 int32_t trtx_op_conv2d_nhwc_f32(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out, int Cout,

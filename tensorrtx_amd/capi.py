@@ -260,6 +260,101 @@ def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
     return keep_idx, keep_cnt, keep_det
 
 
+def reorg_fold_weights(w):
+    """trtx_reorg_fold_weights: numpy KCRS [cout, 4 * cin, kh, kw] fp32 -> [cout, cin, 2 * kh, 2 * kw], the filter the lowering packs for a
+    convolution that absorbed the ReOrg in front of it."""
+    import numpy as np
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    cout, c4, kh, kw = w.shape
+    out = np.empty((cout, c4 // 4, 2 * kh, 2 * kw), dtype=np.float32)
+    check(lib().trtx_reorg_fold_weights(w.ctypes.data_as(ctypes.c_void_p), cout, c4 // 4, kh, kw, out.ctypes.data_as(ctypes.c_void_p)),
+          "trtx_reorg_fold_weights")
+    return out
+
+
+DET7_FLOATS = 6  # yolov7/include/types.h: bbox[4], conf, class_id
+
+
+def _grid_tables(grids, anchors, n):
+    import numpy as np
+    gw = (ctypes.c_int * max(n, 1))(*[g[0] for g in grids[:n]])
+    gh = (ctypes.c_int * max(n, 1))(*[g[1] for g in grids[:n]])
+    an = np.ascontiguousarray(anchors, dtype=np.float32).reshape(-1, 6)
+    return gw, gh, an
+
+
+def yolov7_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, out=None):
+    """YOLOv7 YoloLayerPlugin::enqueue replacement (yolov7/plugin/yololayer.cu:152-207).
+    inputs: CUDA fp32 [B, 3*(5+classes), gh*gw] per level; grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1+max_out*6]
+    `out`: a caller's buffer of at least B rows (rows beyond B are not touched)."""
+    import torch
+    L = lib()
+    n = len(inputs)
+    ins = [x.contiguous() for x in inputs]
+    B, dev = ins[0].shape[0], ins[0].device
+    arr = (ctypes.c_void_p * n)(*[x.data_ptr() for x in ins])
+    gw, gh, an = _grid_tables(grids, anchors, n)
+    L.trtx_yolov7_decode_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolov7_decode_workspace(B, gw, gh, n)
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros((B, 1 + max_out * DET7_FLOATS), dtype=torch.float32, device=dev)
+    check(L.trtx_yolov7_decode(arr, n, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out), _p(ws),
+                               ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov7_decode")
+    return out
+
+
+def yolov7_head_decode_workspace(batch, grids):
+    L = lib()
+    n = len(grids)
+    gw, gh, _ = _grid_tables(grids, [0.0] * 6 * n, n)
+    L.trtx_yolov7_head_decode_workspace.restype = ctypes.c_size_t
+    return L.trtx_yolov7_head_decode_workspace(batch, gw, gh, n)
+
+
+def yolov7_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_out=1000, out=None, ws=None, ld=None, n_levels=None,
+                            status_only=False):
+    """The fused YOLOv7 head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32; ld >= 3 * (5 + classes), the rest is padding):
+    trtx_yolov7_head_decode_nhwc{,_f32}.  grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1 + max_out * 6].
+    `out` / `ws`: the caller's buffers; `ld`, `n_levels`: what is passed instead of the tensors' own; `status_only`: return the
+    status code instead of raising (the refusal tests)."""
+    import torch
+    L = lib()
+    B, n, dev = heads[0].shape[0], len(heads), heads[0].device
+    hp, hl = _head_table(heads)
+    if ld is not None:
+        hl = (ctypes.c_int * n)(*ld)
+    gw, gh, an = _grid_tables(grids, anchors, n)
+    if ws is None:
+        ws = torch.empty(max(yolov7_head_decode_workspace(B, grids), 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros((B, 1 + max_out * DET7_FLOATS), dtype=torch.float32, device=dev)
+    fn = L.trtx_yolov7_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolov7_head_decode_nhwc
+    st = fn(hp, hl, n if n_levels is None else n_levels, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out),
+            _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    if status_only:
+        return st
+    check(st, "trtx_yolov7_head_decode_nhwc")
+    return out
+
+
+def yolov7_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
+    """yolov7 batch_nms replacement (yolov7/src/postprocess.cpp:48-89) on 6-float records.  Returns keep_idx, keep_cnt,
+    keep_det [B, max_out, 6]."""
+    import torch
+    L = lib()
+    B, dev = decode_out.shape[0], decode_out.device
+    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
+    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
+    keep_det = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
+    L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
+    ws_bytes = L.trtx_yolo_nms_workspace(B)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    check(L.trtx_yolov7_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
+                            _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov7_nms")
+    return keep_idx, keep_cnt, keep_det
+
+
 def yolov9_decode(inputs, classes, net_h, net_w, max_out=1000, is_seg=False, out=None):
     """YOLOv9 YoloLayerPlugin::enqueue replacement (yolov9/plugin/yololayer.cu:124-197).
     inputs: three CUDA fp32 [B, 4 + classes (+ 32), gh * gw] (strides 8 / 16 / 32).  -> [B, 1 + max_out * 38]"""

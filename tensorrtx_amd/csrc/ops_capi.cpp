@@ -366,3 +366,9 @@ extern "C" int32_t trtx_op_poison_lds(void* device_word, trtx_stream_t stream) {
     return poison_lds(static_cast<unsigned*>(device_word), static_cast<hipStream_t>(stream));
 }
 
+
+extern "C" int32_t trtx_reorg_fold_weights(const float* w_kcrs, int cout, int cin, int kh, int kw, float* folded) {
+    if (!w_kcrs || !folded || cout < 1 || cin < 1 || kh < 1 || kw < 1) return TRTX_ERR_INVALID;
+    reorg_fold_weights(w_kcrs, cout, cin, kh, kw, folded);
+    return TRTX_OK;
+}

@@ -39,6 +39,9 @@ Options read_options() {
     o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);
+    o.yolo7_head = !env_is("TRTX_YOLO7_HEAD", 0);
+    o.reorg_fold = !env_is("TRTX_REORG_FOLD", 0);
+    o.spp_parallel_chain = !env_is("TRTX_SPP_PARALLEL_CHAIN", 0);
     o.yolo9_head = !env_is("TRTX_YOLO9_HEAD", 0);
     o.roialign_fused = !env_set("TRTX_ROIALIGN_PLUGIN");
     o.roialign_fold_stride = !env_is("TRTX_ROIALIGN_FOLD_STRIDE", 0);

@@ -380,10 +380,137 @@ int32_t yolo9_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The YOLOv7 form of "YoloLayer_TRT"/"1" (yolov7/plugin/yololayer.{h,cu}): the anchor-based plugin without the segmentation flag and
+// with Detection records of 6 floats.  Creator fields "netinfo" = int32[4] {classes, W, H, maxOut} - exactly four, five and more are
+// YOLOv5's - and "kernels" = YoloKernel[n] (yolov7/src/block.cpp:220-255); blob int classCount, threadCount, kernelCount, netW, netH,
+// maxOut, YoloKernel[n] = 24 + 32 n bytes (yololayer.cu:40-78), one byte less than YOLOv5's.
+struct Yolo7Layer {
+    int class_count = 80, thread_count = 256, net_w = 640, net_h = 640, max_out = 1000;
+    std::vector<Yolo5Kernel> kernels;
+
+    std::vector<uint8_t> blob() const {
+        std::vector<uint8_t> b;
+        put(b, class_count);
+        put(b, thread_count);
+        put(b, (int)kernels.size());
+        put(b, net_w);
+        put(b, net_h);
+        put(b, max_out);
+        for (const auto& k : kernels) put(b, k);
+        return b;
+    }
+    // accepted by its exact length and a kernelCount that agrees with it only
+    static Yolo7Layer* from_blob(const void* data, size_t len) {
+        const uint8_t* p = static_cast<const uint8_t*>(data);
+        const uint8_t* end = p + len;
+        auto* y = new Yolo7Layer();
+        int nk = 0;
+        bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, nk) && get(p, end, y->net_w) &&
+                  get(p, end, y->net_h) && get(p, end, y->max_out) && nk >= 1 && nk <= 8 &&
+                  (size_t)(end - p) == (size_t)nk * sizeof(Yolo5Kernel);
+        for (int i = 0; ok && i < nk; ++i) {
+            Yolo5Kernel k{};
+            ok = get(p, end, k) && k.width > 0 && k.height > 0;
+            y->kernels.push_back(k);
+        }
+        if (!ok || y->class_count < 1 || y->max_out < 1 || y->net_w < 1 || y->net_h < 1) {
+            delete y;
+            return nullptr;
+        }
+        return y;
+    }
+    void geometry(std::vector<int>* gw, std::vector<int>* gh, std::vector<float>* an) const {
+        for (const auto& k : kernels) {
+            gw->push_back(k.width);
+            gh->push_back(k.height);
+            an->insert(an->end(), k.anchors, k.anchors + 6);
+        }
+    }
+};
+
+void yolo7_fill(trtx_plugin_vtbl* v, Yolo7Layer* y);
+int32_t yolo7_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
+    auto* y = static_cast<Yolo7Layer*>(s);
+    out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yololayer.cu:90-94
+    out->d[0] = (int64_t)y->max_out * 6 + 1;
+    out->d[1] = 1;
+    out->d[2] = 1;
+    return 0;
+}
+int32_t yolo7_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
+    auto* y = static_cast<Yolo7Layer*>(s);
+    if (nb_in != (int)y->kernels.size()) return 1;
+    for (int i = 0; i < nb_in; ++i) {
+        int64_t vol = 1;
+        for (int k = 0; k < in[i].nb; ++k) vol *= in[i].d[k];
+        if (vol != (int64_t)3 * (5 + y->class_count) * y->kernels[i].width * y->kernels[i].height) return 1;
+    }
+    return 0;
+}
+size_t yolo7_workspace(void* s, int32_t max_batch) {
+    auto* y = static_cast<Yolo7Layer*>(s);
+    std::vector<int> gw, gh;
+    std::vector<float> an;
+    y->geometry(&gw, &gh, &an);
+    return trtx_yolov7_decode_workspace(max_batch, gw.data(), gh.data(), (int)gw.size());
+}
+int32_t yolo7_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
+    auto* y = static_cast<Yolo7Layer*>(s);
+    std::vector<int> gw, gh;
+    std::vector<float> an;
+    y->geometry(&gw, &gh, &an);
+    const size_t ws_bytes = trtx_yolov7_decode_workspace(batch, gw.data(), gh.data(), (int)gw.size());
+    return trtx_yolov7_decode(reinterpret_cast<const float* const*>(inputs), (int)gw.size(), batch, y->class_count, y->net_h, y->net_w,
+                              gw.data(), gh.data(), an.data(), y->max_out, static_cast<float*>(outputs[0]), ws, ws_bytes, stream);
+}
+size_t yolo7_ser_size(void* s) { return static_cast<Yolo7Layer*>(s)->blob().size(); }
+void yolo7_serialize(void* s, void* buf) {
+    const auto b = static_cast<Yolo7Layer*>(s)->blob();
+    memcpy(buf, b.data(), b.size());
+}
+int32_t yolo7_clone(void* s, trtx_plugin_vtbl* out) {
+    yolo7_fill(out, new Yolo7Layer(*static_cast<Yolo7Layer*>(s)));
+    return 0;
+}
+void yolo7_destroy(void* s) { delete static_cast<Yolo7Layer*>(s); }
+void yolo7_fill(trtx_plugin_vtbl* v, Yolo7Layer* y) {
+    v->self = y;
+    v->get_nb_outputs = yolo_nb_outputs;
+    v->get_output_dims = yolo7_output_dims;
+    v->configure = yolo7_configure;
+    v->initialize = yolo5_initialize;
+    v->terminate = yolo_terminate;
+    v->workspace_size = yolo7_workspace;
+    v->enqueue = yolo7_enqueue;
+    v->serialization_size = yolo7_ser_size;
+    v->serialize = yolo7_serialize;
+    v->plugin_type = yolo_type;
+    v->plugin_version = yolo_version;
+    v->clone = yolo7_clone;
+    v->destroy = yolo7_destroy;
+}
+int32_t yolo7_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
+    if (!f[0].data || !f[1].data || f[0].length != 4 || f[1].length < 1 || f[1].length > 8) return 1;
+    const int* ni = static_cast<const int*>(f[0].data);
+    if (ni[0] < 1 || ni[1] < 1 || ni[2] < 1 || ni[3] < 1) return 1;
+    auto* y = new Yolo7Layer();
+    y->class_count = ni[0];
+    y->net_w = ni[1];
+    y->net_h = ni[2];
+    y->max_out = ni[3];
+    y->kernels.resize(f[1].length);  // counted in YoloKernel elements (block.cpp:241-242)
+    memcpy(y->kernels.data(), f[1].data, sizeof(Yolo5Kernel) * f[1].length);
+    yolo7_fill(out, y);
+    return 0;
+}
+
 // creator: one field "combinedInfo" = int32[9 + nStrides] (yolov8/src/block.cpp:267-293, yololayer.cu:339-360)
 int32_t yolo_create(void*, const char*, const trtx_plugin_field* f, int32_t nb, trtx_plugin_vtbl* out) {
     // the anchor-based plugin shares the registered name: told apart by its two fields "netinfo" + "kernels"
-    if (nb == 2 && f && f[0].name && f[1].name && !strcmp(f[0].name, "netinfo") && !strcmp(f[1].name, "kernels")) return yolo5_create(f, out);
+    // (four netinfo ints: YOLOv7's, which has no is_segmentation; five and more: YOLOv5's; fewer are refused by either)
+    if (nb == 2 && f && f[0].name && f[1].name && !strcmp(f[0].name, "netinfo") && !strcmp(f[1].name, "kernels"))
+        return f[0].length == 4 ? yolo7_create(f, out) : yolo5_create(f, out);
     // ... and so does the YOLOv9 one: its single field is "netinfo"
     if (nb == 1 && f && f[0].name && !strcmp(f[0].name, "netinfo")) return yolo9_create(f, out);
     if (nb != 1 || !f || !f[0].name || strcmp(f[0].name, "combinedInfo") != 0 || f[0].length < 10) return 1;
@@ -416,8 +543,14 @@ int32_t yolo_deserialize(void*, const char*, const void* data, size_t len, trtx_
     }
     // ... nor the anchor-based one: the YOLOv9 blob, 21 bytes
     Yolo9Layer* y9 = Yolo9Layer::from_blob(data, len);
-    if (!y9) return 1;
-    yolo9_fill(out, y9);
+    if (y9) {
+        yolo9_fill(out, y9);
+        return 0;
+    }
+    // ... and last the YOLOv7 blob, 24 + 32 n bytes: no earlier parser takes that length (35 + 4 n, 25 + 32 n, 21)
+    Yolo7Layer* y7 = Yolo7Layer::from_blob(data, len);
+    if (!y7) return 1;
+    yolo7_fill(out, y7);
     return 0;
 }
 const char* yolo_creator_name(void*) { return "YoloLayer_TRT"; }
@@ -619,6 +752,21 @@ bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
     return true;
 }
 
+bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
+    if (v.enqueue != yolo7_enqueue || !v.self) return false;
+    const auto* y = static_cast<const Yolo7Layer*>(v.self);
+    out->classes = y->class_count;
+    out->net_w = y->net_w;
+    out->net_h = y->net_h;
+    out->max_out = y->max_out;
+    out->seg = false;
+    out->grid_w.clear();
+    out->grid_h.clear();
+    out->anchors.clear();
+    y->geometry(&out->grid_w, &out->grid_h, &out->anchors);
+    return true;
+}
+
 bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
     if (v.enqueue != yolo9_enqueue || !v.self) return false;
     const auto* y = static_cast<const Yolo9Layer*>(v.self);
@@ -632,7 +780,7 @@ bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
 
 // built-in plugins only enqueue kernels and stream-ordered memsets on the caller's stream: safe inside a stream capture
 bool builtin_plugin_capturable(const trtx_plugin_vtbl& v) {
-    return v.enqueue == yolo_enqueue || v.enqueue == yolo5_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
+    return v.enqueue == yolo_enqueue || v.enqueue == yolo5_enqueue || v.enqueue == yolo7_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
 }
 
 void register_builtin_plugins(PluginRegistry& r) {

@@ -219,7 +219,7 @@ struct Lowerer {
             ins.push_back(pt_of[t]);
         }
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
-        POp& op = add_op(OP_YOLO5_HEAD, l.name + " [fused anchor decode]", ins, {out});
+        POp& op = add_op(f.v7 ? OP_YOLO7_HEAD : OP_YOLO5_HEAD, l.name + (f.v7 ? " [fused anchor decode, 6-float records]" : " [fused anchor decode]"), ins, {out});
         op.i[0] = pr.classes;
         op.i[1] = pr.net_h;
         op.i[2] = pr.net_w;
@@ -232,7 +232,7 @@ struct Lowerer {
         op.fv = pr.anchors;
         // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
         if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
-        op.ws_bytes = trtx_yolov5_head_decode_workspace(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
+        op.ws_bytes = (f.v7 ? trtx_yolov7_head_decode_workspace : trtx_yolov5_head_decode_workspace)(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
         // what it must read: the three objectness values of every pixel (nothing else of a pixel without a candidate), and what it writes
         for (int t : ins) op.bytes += (double)dtype_size(dt) * plan.tensors[t].H * plan.tensors[t].W * 3;
         op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
@@ -268,23 +268,27 @@ struct Lowerer {
     // ---- per-kind emission ----------------------------------------------------------------------------
     bool emit_conv(const FusedConv& c) {
         const LayerDef& l = net.layers[c.conv_layer];
+        // a folded ReOrg (match_reorg_fold): the convolution reads the slices' input with a 2k x 2k stride-2 padding-2p filter
+        const int reorg = fu.reorg_src[c.conv_layer];
+        const int tin = reorg >= 0 ? reorg : l.inputs[0];
+        const int kmul = reorg >= 0 ? 2 : 1;
         // stem: a few-channel fp32 LINEAR input (the image) feeds conv_stem directly, no layout pass
         bool stem = false;
         {
-            const PTensor& src = plan.tensors[pt_of[l.inputs[0]]];
-            const Dims& di = net.tensors[l.inputs[0]].dims;
+            const PTensor& src = plan.tensors[pt_of[tin]];
+            const Dims& di = net.tensors[tin].dims;
             const int cin = (int)di.d[di.nb - 3];
-            const bool image = l.kind == L_CONV && di.nb == (net.explicit_batch ? 4 : 3) && src.layout == LAY_LINEAR && pt_nhwc[l.inputs[0]] < 0 && cin <= 4 &&
+            const bool image = l.kind == L_CONV && di.nb == (net.explicit_batch ? 4 : 3) && src.layout == LAY_LINEAR && pt_nhwc[tin] < 0 && cin <= 4 &&
                                c.residual < 0 && c.act2 == ACT_NONE && l.groups == 1 && l.dilation[0] == 1 && l.dilation[1] == 1;
             stem = dt == DT_F16 && image && (l.nb_out == 8 || l.nb_out == 16 || l.nb_out == 32 || l.nb_out == 64) &&
-                   (size_t)l.kernel[0] * l.kernel[1] * cin * l.nb_out * 4 <= 48 * 1024;
+                   (size_t)l.kernel[0] * kmul * l.kernel[1] * kmul * cin * l.nb_out * 4 <= 48 * 1024;
             // fp32 engines (round 5): kernels/conv_stem_f32.hip, the same idea on the vector ALU - the layer is HBM-bound and 3x padding on the MFMA path
             if (dt == DT_F32 && opt.f32_mfma) stem = image && l.nb_out % 16 == 0 && l.nb_out <= 256;
         }
-        const int in = stem ? pt_of[l.inputs[0]] : need_nhwc(l.inputs[0]);
+        const int in = stem ? pt_of[tin] : need_nhwc(tin);
         PTensor ti = plan.tensors[in];
         if (stem) {  // geometry of the LINEAR tensor viewed as an image
-            const Dims& di = net.tensors[l.inputs[0]].dims;
+            const Dims& di = net.tensors[tin].dims;
             ti.C = (int)di.d[di.nb - 3];
             ti.H = (int)di.d[di.nb - 2];
             ti.W = (int)di.d[di.nb - 1];
@@ -330,6 +334,15 @@ struct Lowerer {
             a.dil_h = l.dilation[0];
             a.dil_w = l.dilation[1];
             a.groups = l.groups;
+            if (reorg >= 0) {
+                op.name += " [ReOrg folded]";
+                op.reorg_cin = ti.C;
+                a.kh *= 2;
+                a.kw *= 2;
+                a.stride_h = a.stride_w = 2;
+                a.pad_h *= 2;
+                a.pad_w *= 2;
+            }
         }
         a.act1 = c.act1;
         a.alpha1 = c.alpha1;

@@ -271,15 +271,20 @@ void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
 // OP_YOLO5_HEAD on the convolutions' NHWC tensors (fp16 and fp32 engines).  The convolutions stay ordinary convolutions; pad_cout marks
 // them so that a channel count that is no 16-byte multiple (255) does not cost them their vector stores.  Anything else keeps the
 // plugin: marked heads, a second reader, another kernel or channel count, a grid that is not the tensor's, TRTX_YOLO5_HEAD=0.
-void match_yolo5_heads(const NetView& g, Fusions& f) {
+//
+// YOLOv7's tail (yolov7/src/block.cpp:220-255) is the same graph in front of the 6-float plugin (`v7`): the same conditions, one
+// OP_YOLO7_HEAD, TRTX_YOLO7_HEAD=0.  A plugin instance is one form or the other, so the two calls cannot claim the same layer.
+void match_anchor_heads(const NetView& g, bool v7, Fusions& f) {
     const Network& net = g.net;
     const int e = net.explicit_batch ? 1 : 0;
-    if (!g.opt.yolo5_head) return;
+    if (!(v7 ? g.opt.yolo7_head : g.opt.yolo5_head)) return;
+    if (v7 && net.int8) return;   // kINT8 YOLOv7 networks keep the plugin route: the 6-float head was never run behind a calibrated convolution
     for (size_t li = 0; li < net.layers.size(); ++li) {
         const LayerDef& l = net.layers[li];
         if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li] || !l.plugin) continue;
         Yolo5HeadFuse h;
-        if (!builtin_yolo5_params(l.plugin->v, &h.params)) continue;
+        h.v7 = v7;
+        if (!(v7 ? builtin_yolo7_params : builtin_yolo5_params)(l.plugin->v, &h.params)) continue;
         const Yolo5LayerParams& pr = h.params;
         if (pr.seg || pr.classes < 1 || l.inputs.empty() || l.inputs.size() > 8 || l.inputs.size() != pr.grid_w.size()) continue;
         bool ok = true;
@@ -305,6 +310,64 @@ void match_yolo5_heads(const NetView& g, Fusions& f) {
         f.yolo5_heads.push_back(h);
     }
 }
+
+void match_yolo5_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, false, f); }
+
+// ---- ReOrg (yolov7/src/block.cpp:106-114; YOLOv5's Focus is the same graph): four slices of one image tensor with step (1, 2, 2) and
+// starts (0,0,0), (0,1,0), (0,0,1), (0,1,1), whole-channel, concatenated in that order on the channel axis, read by nothing but one
+// k x k stride-1, dilation-1, groups-1 convolution with padding p.  Slice q = 2 dx + dy holds x[c][2 y + dy][2 x + dx], so the
+// convolution is one 2k x 2k stride-2 padding-2p convolution of the slices' input with W'[o][c][2 i + dy][2 j + dx] = W[o][q Cin + c][i][j]
+// (reorg_fold_weights, pack.cpp): tap (i, j) of slice q reads x[c][2 (y + i - p) + dy][2 (x + j - p) + dx], and a padded tap of the
+// slices is a padded tap of x.  The slices and the concat emit nothing (on the linear layout they would be four gathers over the
+// network's largest tensor, a concat and a layout pass); reorg_src names the convolution's new input.  Misses: odd H or W, other
+// starts, steps, sizes or order, a second reader of a slice or of the concat, a network output among them.  TRTX_REORG_FOLD=0.
+void match_reorg_fold(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    // kINT8 networks keep the gathers: the folded convolution would quantise the slices' input with a scale calibrated for another tensor
+    // (the concat's), and no INT8 engine with a ReOrg has been run
+    if (!g.opt.reorg_fold || net.int8) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& cat = net.layers[li];
+        if (cat.kind != L_CONCAT || f.absorbed[li] || cat.inputs.size() != 4 || cat.outputs.size() != 1) continue;
+        const Dims& dc = net.tensors[cat.outputs[0]].dims;
+        if (!g.spatial(dc) || cat.axis != dc.nb - 3) continue;
+        int lcv;
+        if (!g.sole_consumer(cat.outputs[0], &lcv) || f.absorbed[lcv]) continue;
+        const LayerDef& cv = net.layers[lcv];
+        if (cv.kind != L_CONV || cv.inputs.size() != 1 || cv.groups != 1 || cv.stride[0] != 1 || cv.stride[1] != 1 || cv.dilation[0] != 1 ||
+            cv.dilation[1] != 1)
+            continue;
+        static const int want[4][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}};   // (dy, dx) in concat order
+        int src = -1;
+        bool ok = true;
+        std::vector<int> slices;
+        for (int q = 0; ok && q < 4; ++q) {
+            const int t = cat.inputs[q];
+            const int ls = g.producer(t);
+            ok = ls >= 0 && net.layers[ls].kind == L_SLICE && !f.absorbed[ls] && g.only_used_by(t, {(int)li});
+            if (!ok) break;
+            const LayerDef& s = net.layers[ls];
+            const Dims& di = net.tensors[s.inputs[0]].dims;
+            const int n = di.nb;
+            ok = g.spatial(di) && (src < 0 || src == s.inputs[0]) && di.d[n - 2] % 2 == 0 && di.d[n - 1] % 2 == 0 && s.start.nb == n &&
+                 s.size.nb == n && s.step.nb == n;
+            if (!ok) break;
+            src = s.inputs[0];
+            for (int k = 0; k < n - 2; ++k) ok = ok && s.start.d[k] == 0 && s.step.d[k] == 1 && s.size.d[k] == di.d[k];
+            ok = ok && s.start.d[n - 2] == want[q][0] && s.start.d[n - 1] == want[q][1] && s.step.d[n - 2] == 2 && s.step.d[n - 1] == 2 &&
+                 s.size.d[n - 2] == di.d[n - 2] / 2 && s.size.d[n - 1] == di.d[n - 1] / 2;
+            for (int p : slices) ok = ok && p != ls;
+            slices.push_back(ls);
+        }
+        if (!ok) continue;
+        const Dims& dx = net.tensors[src].dims;
+        if ((size_t)cv.w0.size() != (size_t)cv.nb_out * 4 * dx.d[dx.nb - 3] * cv.kernel[0] * cv.kernel[1]) continue;
+        for (int ls : slices) f.absorbed[ls] = true;
+        f.absorbed[li] = true;
+        f.reorg_src[lcv] = src;
+    }
+}
+void match_yolo7_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, true, f); }
 
 // ---- YOLOv9 / GELAN detect tail (yolov9/src/block.cpp:424-489): per level the concat of [DFL chain on the grouped 1x1 convolution's
 // (64, gh, gw) output, reshape (classes, gh * gw) of the class convolution's output] into the YOLOv9 YoloLayer_TRT.  Unlike YOLOv8's tail
@@ -573,20 +636,23 @@ void match_area_attention(const NetView& g, Fusions& f) {
 }  // namespace
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
-// and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor head (it claims its plugin layer only), PSA attention, area
-// attention, convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
+// attention, the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
     f.pad_cout.assign(nl, false);
+    f.reorg_src.assign(nl, -1);
     f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
     match_yolo9_heads(g, f);
     match_yolo5_heads(g, f);
+    match_yolo7_heads(g, f);
     match_psa_attention(g, f);
     match_area_attention(g, f);
+    match_reorg_fold(g, f);
     match_conv_fusion(g, f);
     match_concat_activation(g, f);
     return f;

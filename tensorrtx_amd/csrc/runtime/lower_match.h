@@ -36,6 +36,7 @@ struct Yolo5HeadFuse {
     std::vector<int> head_tensor;   // network tensor per level: a detect convolution's output (3 * (5 + classes), gh, gw)
     std::vector<int> conv_layer;    // ... and the layer that produces it
     Yolo5LayerParams params;
+    bool v7 = false;                // the YOLOv7 plugin: 6-float records, OP_YOLO7_HEAD
 };
 
 struct Yolo9HeadFuse {
@@ -64,6 +65,7 @@ struct Fusions {
     std::vector<Yolo9HeadFuse> yolo9_heads;
     std::vector<int> group_at, yolo_at, attn_at, yolo5_at, yolo9_at;
     std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor or DDetect head: its output channels round up to 16 bytes
+    std::vector<int> reorg_src;                // per layer: >= 0 for a convolution that absorbed the ReOrg in front of it - the network tensor the four slices read
     std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own
     std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src
 };

@@ -106,6 +106,20 @@ void pack_deconv_weights_f32(const float* w, int cin, int cout, int groups, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// W'[o][c][2 i + dy][2 j + dx] = W[o][q cin + c][i][j], q = 2 dx + dy: the k x k filter over ReOrg's 4 cin channels as the 2kh x 2kw
+// stride-2 filter over the cin channels ReOrg read (match_reorg_fold).  Every element of `out` is written once.
+void reorg_fold_weights(const float* w, int cout, int cin, int kh, int kw, float* out) {
+    for (int o = 0; o < cout; ++o)
+        for (int q = 0; q < 4; ++q) {
+            const int dy = q & 1, dx = q >> 1;
+            for (int c = 0; c < cin; ++c)
+                for (int i = 0; i < kh; ++i)
+                    for (int j = 0; j < kw; ++j)
+                        out[(((size_t)o * cin + c) * 2 * kh + 2 * i + dy) * 2 * kw + 2 * j + dx] =
+                                w[(((size_t)o * 4 * cin + (size_t)q * cin + c) * kh + i) * kw + j];
+        }
+}
+
 bool pack_weights(const Network& net, Plan* plan) {
     std::vector<uint8_t>& blob = plan->weight_blob;
     blob.clear();
@@ -148,11 +162,16 @@ bool pack_weights(const Network& net, Plan* plan) {
                 }
             }
             const TensorDef& tin = net.tensors[l.inputs[0]];
-            const int cin_logical = (int)tin.dims.d[tin.dims.nb - 3];
+            const int cin_logical = op.reorg_cin > 0 ? op.reorg_cin : (int)tin.dims.d[tin.dims.nb - 3];
             std::vector<float> w0_padded;
             const float* w0 = l.w0.data();
+            if (op.reorg_cin > 0) {   // before any packing: every branch below sees an ordinary 2k x 2k filter over the slices' input
+                w0_padded.resize(l.w0.size());   // [cout][cin][2kh][2kw]: as many elements as [cout][4 cin][kh][kw]
+                reorg_fold_weights(l.w0.data(), l.nb_out, op.reorg_cin, l.kernel[0], l.kernel[1], w0_padded.data());
+                w0 = w0_padded.data();
+            }
             if (cout_real < cout) {
-                w0_padded = l.w0;
+                if (w0_padded.empty()) w0_padded = l.w0;
                 w0_padded.resize((size_t)cout * a.kh * a.kw * (cin_logical / a.groups), 0.f);
                 w0 = w0_padded.data();
             }
@@ -166,7 +185,7 @@ bool pack_weights(const Network& net, Plan* plan) {
                 float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
                 for (int co = 0; co < cout; ++co)
                     for (int t = 0; t < cin_logical * a.kh * a.kw; ++t)
-                        dst[(size_t)t * cout + co] = l.w0[(size_t)co * cin_logical * a.kh * a.kw + t] * sc[co];
+                        dst[(size_t)t * cout + co] = w0[(size_t)co * cin_logical * a.kh * a.kw + t] * sc[co];
             } else if (op.from_deconv) {
                 // CKRS [Cin][Cout][kh][kw] -> KCRS of the stand-in 1x1 conv: output channel (r*kw + q)*Cout + co.  The re-layout
                 // (and the per-sub-position bias) does not depend on which conv kernel runs the stand-in: the kernel choice may refuse

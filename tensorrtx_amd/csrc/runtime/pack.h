@@ -23,6 +23,10 @@ void pack_conv_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int
 // deconv_direct is [Cout][kh][kw][Cin/groups].
 void pack_deconv_weights_f32(const float* w_ckrs, int cin, int cout, int groups, int kh, int kw, float* packed);
 
+// ReOrg (four stride-2 slices + concat) in front of a kh x kw stride-1 convolution over 4 cin channels, as one 2kh x 2kw stride-2
+// convolution over cin channels (runtime/lower_match.cpp, match_reorg_fold): out [cout][cin][2kh][2kw] from KCRS w [cout][4 cin][kh][kw]
+void reorg_fold_weights(const float* w, int cout, int cin, int kh, int kw, float* out);
+
 uint16_t f32_to_f16_bits(float f);
 float f16_bits_to_f32(uint16_t h);
 

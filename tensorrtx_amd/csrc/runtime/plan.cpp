@@ -10,8 +10,8 @@ const char* op_kind_name(int k) {
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
-                              "yolo_task_head", "yolo5_head", "yolo9_head"};
-    return (k >= 0 && k <= OP_YOLO9_HEAD) ? n[k] : "?";
+                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head"};
+    return (k >= 0 && k <= OP_YOLO7_HEAD) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -49,6 +49,7 @@ std::string Plan::describe_json() const {
             if (op.dw) o << ",\"dw\":true";
             if (op.grouped) o << ",\"grouped\":true";
             if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
+            if (op.reorg_cin) o << ",\"reorg_cin\":" << op.reorg_cin;
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
@@ -59,7 +60,9 @@ std::string Plan::describe_json() const {
             for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
             o << "]";
         }
-        if (op.kind == OP_YOLO5_HEAD) {
+        if (op.kind == OP_POOL || op.kind == OP_POOL_CHAIN)
+            o << ",\"k\":[" << op.i[1] << "," << op.i[2] << "],\"stride\":[" << op.i[3] << "," << op.i[4] << "],\"outputs\":" << op.out.size();
+        if (op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO7_HEAD) {
             o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"anchor_levels\":" << op.fv.size() / 6 << ",\"grids\":[";
             for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]";
             o << "],\"ld\":[";

@@ -55,6 +55,7 @@ enum OpKind : int {
     OP_YOLO9_HEAD,      // fused DFL + YOLOv9 YoloLayer decode (38-float records) on the NHWC outputs of the head's last convolutions (plugins/yolo9_head.hip):
                         // `in` = the three box tensors (64 DFL bins), `extra_in` = the three class tensors; i[0] = classes, i[1] / i[2] = net h / w,
                         // i[3] = max_out, i[4] = levels (3: strides 8 / 16 / 32); src_layer = the DFL 1x1 convolution
+    OP_YOLO7_HEAD,      // OP_YOLO5_HEAD with YOLOv7's 6-float records (plugins/yolo7_head.hip): the same i / iv / fv
 };
 const char* op_kind_name(int k);
 
@@ -108,6 +109,8 @@ struct POp {
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
     bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
     bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one
+    int reorg_cin = 0;         // > 0: a convolution that absorbed the ReOrg in front of it (match_reorg_fold): conv is the 2k x 2k stride-2 form over this
+                               // many channels and pack_weights re-indexes the layer's k x k filter over 4 x as many (reorg_fold_weights)
     int cout_real = 0;         // > 0: conv.Cout is this channel count rounded up to a 16-byte multiple; the filter rows and biases beyond it are zero
                                // and the output tensor's padding channels take the zeros (a detect convolution under OP_YOLO5_HEAD)
     // OP_CONV_GROUP: the member convolutions, each a complete OP_CONV record (its own in / out tensors, ConvArgs, weights); the group's

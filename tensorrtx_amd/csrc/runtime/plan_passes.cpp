@@ -422,6 +422,74 @@ void chain_sppf_pools(Plan& plan, const PassInputs& e) {
     }
 }
 
+// SPP / SPPCSPC (yolov7/src/block.cpp:140-148, model.cpp:1905-1916): y1 = maxpool_k(x), y2 = maxpool_{2k-1}(x), y3 = maxpool_{3k-2}(x),
+// stride 1, 'same' padding, all three reading x.  A max-pool that skips its padding (pool_kernel: -inf start, out-of-range taps
+// skipped) composes - the k-window of k-window maxima is the (2k-1)-window maximum over the in-range taps, no rounding anywhere - so
+// the three are bit for bit the three outputs of the chained kernel on x.  The pools may come in any order; between the first and the
+// last of them no other op may write x (or one of the three outputs: it would have to run between two of them).  The three-in-a-row
+// form of chain_sppf_pools has run before this pass and has k, k, k; no network that it or this pass takes is taken by the other.
+void chain_spp_parallel_pools(Plan& plan, const PassInputs& e) {
+    if (!e.opt.spp_parallel_chain || e.int8 || (e.dt != DT_F16 && e.dt != DT_F32)) return;
+    auto same_max = [&](const POp& o) {
+        return o.kind == OP_POOL && o.i[0] == POOL_MAX && o.i[1] == o.i[2] && (o.i[1] & 1) && o.i[3] == 1 && o.i[4] == 1 &&
+               o.i[5] == o.i[1] / 2 && o.i[6] == o.i[1] / 2 && o.in.size() == 1 && o.out.size() == 1;
+    };
+    auto overlaps = [&](int ta, int tb) {   // NHWC tensors sharing channels of one storage
+        const PTensor &a = plan.tensors[ta], &b = plan.tensors[tb];
+        if (ta == tb) return true;
+        if (a.storage != b.storage || a.layout != LAY_NHWC || b.layout != LAY_NHWC) return a.storage == b.storage;
+        return a.rcoff < b.rcoff + std::max(b.C, 1) && b.rcoff < a.rcoff + std::max(a.C, 1);
+    };
+    for (size_t k = 0; k + 2 < plan.ops.size(); ++k) {
+        if (!same_max(plan.ops[k])) continue;
+        const int x = plan.ops[k].in[0];
+        // the other two pools of x, within a short window (the builders emit them back to back)
+        std::vector<size_t> idx{k};
+        const size_t last = std::min(plan.ops.size(), k + 8);
+        for (size_t j = k + 1; j < last && idx.size() < 3; ++j)
+            if (same_max(plan.ops[j]) && plan.ops[j].in[0] == x) idx.push_back(j);
+        if (idx.size() != 3) continue;
+        // by kernel size: k, 2k - 1, 3k - 2
+        std::vector<size_t> by = idx;
+        std::sort(by.begin(), by.end(), [&](size_t p, size_t q) { return plan.ops[p].i[1] < plan.ops[q].i[1]; });
+        const int k1 = plan.ops[by[0]].i[1];
+        if (k1 < 3 || plan.ops[by[1]].i[1] != 2 * k1 - 1 || plan.ops[by[2]].i[1] != 3 * k1 - 2) continue;
+        const PTensor& tx = plan.tensors[x];
+        const int cv = e.dt == DT_F16 ? 8 : 4;
+        bool ok = tx.layout == LAY_NHWC && tx.dtype == e.dt && tx.C % cv == 0 && tx.ld % cv == 0 && tx.rcoff % cv == 0 &&
+                  (long)(tx.H + k1 - 1) * (tx.W + k1 - 1) * 32 <= 64 * 1024 && tx.nmul == 1;
+        for (size_t p : by) {
+            const PTensor& ty = plan.tensors[plan.ops[p].out[0]];
+            ok = ok && ty.layout == LAY_NHWC && ty.dtype == e.dt && ty.ld % cv == 0 && ty.rcoff % cv == 0 && ty.H == tx.H && ty.W == tx.W &&
+                 ty.C == tx.C && !overlaps(plan.ops[p].out[0], x);
+        }
+        ok = ok && !overlaps(plan.ops[by[0]].out[0], plan.ops[by[1]].out[0]) && !overlaps(plan.ops[by[0]].out[0], plan.ops[by[2]].out[0]) &&
+             !overlaps(plan.ops[by[1]].out[0], plan.ops[by[2]].out[0]);
+        // an op between them: it must neither write x nor touch an output of the three
+        for (size_t j = k + 1; ok && j < idx[2]; ++j) {
+            if (j == idx[1]) continue;
+            const POp& o = plan.ops[j];
+            for (int t : o.out) ok = ok && !overlaps(t, x);
+            for (size_t p : by) {
+                const int y = plan.ops[p].out[0];
+                for (int t : o.out) ok = ok && !overlaps(t, y);
+                for (int t : o.in) ok = ok && !overlaps(t, y);
+                for (int t : o.extra_in) ok = ok && !overlaps(t, y);
+            }
+        }
+        if (!ok) continue;
+        const int y1 = plan.ops[by[0]].out[0], y2 = plan.ops[by[1]].out[0], y3 = plan.ops[by[2]].out[0];
+        POp& a = plan.ops[k];
+        a.kind = OP_POOL_CHAIN;
+        a.name += " [x3 parallel, chained]";
+        a.i[1] = a.i[2] = k1;
+        a.i[5] = a.i[6] = k1 / 2;
+        a.out = {y1, y2, y3};
+        plan.ops.erase(plan.ops.begin() + idx[2]);
+        plan.ops.erase(plan.ops.begin() + idx[1]);
+    }
+}
+
 // Per op, the earlier ops it must run after: RAW, WAR and WAW at (storage, channel / element range) granularity, sorted.
 std::vector<std::vector<int>> op_dependencies(const Plan& plan) {
     const int nops = (int)plan.ops.size();
@@ -768,7 +836,7 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
     for (int k = 0; k < nops; ++k) {
         const int kind = plan.ops[k].kind;
-        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD && kind != OP_YOLO5_HEAD && kind != OP_YOLO9_HEAD) || plan.ops[k].ws_bytes == 0) continue;
+        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD && kind != OP_YOLO5_HEAD && kind != OP_YOLO9_HEAD && kind != OP_YOLO7_HEAD) || plan.ops[k].ws_bytes == 0) continue;
         Storage s;
         s.kind = ST_ARENA;
         s.bytes = plan.ops[k].ws_bytes;
@@ -822,6 +890,7 @@ bool finalize_plan(Plan& plan, const PassInputs& e, std::string* err) {
     assign_storages(plan);
     if (!select_conv_kernels(plan, e, err) || !configure_plugins(plan, err)) return false;
     chain_sppf_pools(plan, e);
+    chain_spp_parallel_pools(plan, e);
     group_convs(plan, e);
     mark_stem_pair(plan, e);
     const std::vector<std::vector<int>> deps = op_dependencies(plan);   // (group_convs reordered and merged ops: not its list)

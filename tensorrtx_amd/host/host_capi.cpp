@@ -46,6 +46,8 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
     std::unique_ptr<IInt8Calibrator> calibrator;
     const bool yolov9 = trtx_host::yolov9_model_valid(model, false);   // yolov9t / s / m / c, gelanc
     if (yolov9 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;      // no INT8 YOLOv9 is built
+    const bool yolov7 = trtx_host::yolov7_model_valid(model);          // yolov7tiny / yolov7 / yolov7x / yolov7w6 / yolov7e6
+    if (yolov7 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;      // ... nor INT8 YOLOv7
     if (geti(o, "int8", 0)) {  // USE_INT8 of the reference builders (yolov8/src/model.cpp:317-324, retinaface/retina_r50.cpp:219-225)
         if (!builder->platformHasFastInt8()) return TRTX_ERR_UNSUPPORTED;
         config->setFlag(BuilderFlag::kINT8);
@@ -153,6 +155,22 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < 32 || cfg.input_w < 32 || cfg.input_h % 32 || cfg.input_w % 32)
             return TRTX_ERR_INVALID;
         plan.reset(trtx_host::buildEngineYolov9(builder.get(), config.get(), wts_path, cfg));
+    } else if (yolov7) {
+        trtx_host::Yolov7Config cfg;
+        cfg.model = m;
+        cfg.max_batch = geti(o, "batch", 1);
+        cfg.fp16 = geti(o, "fp16", 1) != 0;
+        cfg.input_h = geti(o, "h", 640);
+        cfg.input_w = geti(o, "w", 640);
+        cfg.num_class = geti(o, "classes", 80);
+        cfg.max_out_bbox = geti(o, "max_out", 1000);
+        cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
+        if (geti(o, "task", 0) != 0) return TRTX_ERR_INVALID;
+        const int top = trtx_host::yolov7_model_p6(m) ? 64 : 32;   // the largest stride: the pyramid levels meet only on sizes it divides
+        if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < top || cfg.input_w < top || cfg.input_h % top || cfg.input_w % top)
+            return TRTX_ERR_INVALID;
+        plan.reset(trtx_host::buildEngineYolov7(builder.get(), config.get(), wts_path, cfg));
+        if (!plan) return TRTX_ERR_INVALID;   // anchor_grid does not describe one level per detect convolution
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);

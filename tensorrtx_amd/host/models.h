@@ -137,6 +137,26 @@ bool yolov9_model_valid(const std::string& name, bool converted);
 nvinfer1::IHostMemory* buildEngineYolov9(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
                                          const Yolov9Config& cfg);
 
+// yolov7/include/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
+// setMaxBatchSize).  Detection, which is all the reference's yolov7 builds.
+struct Yolov7Config {
+    std::string model = "yolov7";       // "yolov7tiny" / "yolov7" / "yolov7x" / "yolov7w6" / "yolov7e6": the build_engine_* function (yolov7/src/model.cpp)
+    int input_h = 640, input_w = 640;   // kInputH / kInputW (ReOrg slices to input_h / 2, input_w / 2)
+    int num_class = 80;                 // kNumClass
+    int max_batch = 1;                  // kBatchSize
+    int max_out_bbox = 1000;            // kMaxNumOutputBbox
+    bool fp16 = true;                   // USE_FP16
+    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes), gh, gw) as "head0..N-1"
+};
+// the five names the builder accepts (yolov7d6 and yolov7e6e are not built), and which of them have four levels (strides 8 .. 64)
+bool yolov7_model_valid(const std::string& name);
+bool yolov7_model_p6(const std::string& name);
+// yolov7/src/model.cpp:1775-2100 (tiny), 1567-1773 (v7), 1284-1565 (x), 1046-1282 (w6), 775-1044 (e6) with yolov7/src/block.cpp.  Input
+// "data", output "prob": 1 + max_out * 6 floats (Detection is bbox[4], conf, class_id).  Returns null for another name and when
+// <detect>.anchor_grid does not describe one level per detect convolution.
+nvinfer1::IHostMemory* buildEngineYolov7(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                         const Yolov7Config& cfg);
+
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {
     int input_h = 800, input_w = 1067;      // INPUT_H / INPUT_W: 480x640 resized by calculateSize() (rcnn.cpp:349-366)

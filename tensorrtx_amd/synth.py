@@ -888,3 +888,252 @@ def yolov9_state(name="yolov9t", seed=0, num_class=80, converted=False):
         sd[f"{det}.cv3.{lv}.2.bias"] = (YOLOV9_CLS_BIAS_OF.get(name, YOLOV9_CLS_BIAS) + 0.1 * randn(num_class)).float()
     sd[det + ".dfl.conv.weight"] = torch.arange(16.0).reshape(1, 16, 1, 1)
     return OrderedDict((k, v.numpy()) for k, v in sd.items())
+
+
+# YOLOv7 (tiny, v7, x, w6, e6), after the models' published deploy yamls: one row per yaml layer, "model.<row>" its weights.  The anchors are
+# the yamls'; yolov7x shares yolov7's and yolov7e6 shares yolov7w6's.
+YOLOV7_ANCHORS = [[12, 16, 19, 36, 40, 28], [36, 75, 76, 55, 72, 146], [142, 110, 192, 243, 459, 401]]
+YOLOV7_TINY_ANCHORS = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]
+YOLOV7_P6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542], [436, 615, 739, 380, 925, 792]]
+YOLOV7_MODELS = ("yolov7tiny", "yolov7", "yolov7x", "yolov7w6", "yolov7e6")
+YOLOV7_OBJ_SCALE = 24.0   # objectness rows of the detect convolutions (the yolov5_state recipe): He rows times the scale, around a bias
+# ... but the SiLU models' random backbones give features that vary little over an image and from image to image (the objectness logits of
+# a model spread by 2 - 3 around an offset of the same size that depends on the draw), so the bias that lets between 2 and 20 % of the anchors pass
+# the 0.1 gate is set per model, from the logits measured with the fp64 twin for 80 classes (counts: tests/test_gpu_yolov7.py); another class
+# count draws other detect rows, and nothing is promised for it
+YOLOV7_OBJ_BIAS_OF = {"yolov7tiny": -24.0, "yolov7": -1.7, "yolov7x": -5.7, "yolov7w6": -8.3, "yolov7e6": -3.7}
+YOLOV7_CLS_BIAS, YOLOV7_CLS_MARGIN = -2.0, 2.5
+# yolov7-tiny's LeakyReLU backbone keeps its features' spread (class logits of std 1 over 80 classes: the largest of 79 reaches the favoured
+# class's margin, and a fifth of the candidates had their two best classes within 0.1 - fp16 rounding flips those): its class rows are scaled down
+YOLOV7_TINY_CLS_ROW_SCALE = 0.1
+# ... and so are its box rows: box logits of std 1.2 carry an absolute fp16 error that moved a box's IoU against the fp32 engine to 0.936
+YOLOV7_TINY_BOX_ROW_SCALE = 0.1
+
+
+def yolov7_rows(name):
+    """The yaml of a YOLOv7 model as rows (from, module, args): `from` an int or a list (negative: relative), module one of "Conv" (args
+    c2, k, s), "MP", "SP" (k), "Concat", "Upsample", "ReOrg", "DownC" (c2), "SPPCSPC" (c2), "RepConv" (c2) and, last, "Detect"."""
+    rows = []
+
+    def conv(f, c, k=1, s=1):
+        rows.append((f, "Conv", (c, k, s)))
+        return len(rows) - 1
+
+    def cat(f):
+        rows.append((list(f), "Concat", ()))
+
+    def elan(c1, c3, n, picks, out):   # two 1x1 of one input, n 3x3 behind the second, `picks` joined, 1x1
+        conv(-1, c1)
+        conv(-2, c1)
+        for _ in range(n):
+            conv(-1, c3, 3)
+        cat(picks)
+        return conv(-1, out)
+
+    def mpdown(c, extra=None):   # [MP, 1x1] beside [1x1, 3x3 stride 2]
+        rows.append((-1, "MP", ()))
+        conv(-1, c)
+        conv(-3, c)
+        conv(-1, c, 3, 2)
+        cat([-1, -3] + ([extra] if extra is not None else []))
+
+    def downc(c2, extra=None):
+        rows.append((-1, "DownC", (c2,)))
+        if extra is not None:
+            cat([-1, extra])
+
+    def upjoin(c, lateral):
+        conv(-1, c)
+        rows.append((-1, "Upsample", ()))
+        conv(lateral, c)
+        cat([-1, -2])
+
+    if name == "yolov7tiny":
+        p4 = [-1, -2, -3, -4]
+        conv(-1, 32, 3, 2)
+        conv(-1, 64, 3, 2)
+        elan(32, 32, 2, p4, 64)
+        rows.append((-1, "MP", ()))
+        b3 = elan(64, 64, 2, p4, 128)
+        rows.append((-1, "MP", ()))
+        b4 = elan(128, 128, 2, p4, 256)
+        rows.append((-1, "MP", ()))
+        elan(256, 256, 2, p4, 512)
+        conv(-1, 256)
+        conv(-2, 256)
+        rows.extend([(-1, "SP", (5,)), (-2, "SP", (9,)), (-3, "SP", (13,))])
+        cat(p4)
+        conv(-1, 256)
+        cat([-1, -7])
+        b5 = conv(-1, 256)
+        upjoin(128, b4)
+        n4 = elan(64, 64, 2, p4, 128)
+        upjoin(64, b3)
+        n3 = elan(32, 32, 2, p4, 64)
+        conv(-1, 128, 3, 2)
+        cat([-1, n4])
+        m4 = elan(64, 64, 2, p4, 128)
+        conv(-1, 256, 3, 2)
+        cat([-1, b5])
+        m5 = elan(128, 128, 2, p4, 256)
+        feats = [conv(n3, 128, 3), conv(m4, 256, 3), conv(m5, 512, 3)]
+    elif name in ("yolov7", "yolov7x"):
+        x = name == "yolov7x"
+        w = (lambda c: c * 5 // 4) if x else (lambda c: c)   # the x model's transition widths are 1.25 times v7's; its ELAN widths are not
+        n = 6 if x else 4
+        back = [-1, -3, -5, -7, -8] if x else [-1, -3, -5, -6]
+        head = back if x else [-1, -2, -3, -4, -5, -6]
+        h3 = (lambda c: c) if x else (lambda c: c // 2)      # v7's head ELANs halve the 3x3 width
+        conv(-1, w(32), 3, 1)
+        conv(-1, w(64), 3, 2)
+        conv(-1, w(64), 3, 1)
+        conv(-1, w(128), 3, 2)
+        elan(64, 64, n, back, w(256))
+        mpdown(w(128))
+        b3 = elan(128, 128, n, back, w(512))
+        mpdown(w(256))
+        b4 = elan(256, 256, n, back, w(1024))
+        mpdown(w(512))
+        elan(256, 256, n, back, w(1024))
+        rows.append((-1, "SPPCSPC", (w(512),)))
+        b5 = len(rows) - 1
+        upjoin(w(256), b4)
+        n4 = elan(256, h3(256), n, head, w(256))
+        upjoin(w(128), b3)
+        n3 = elan(128, h3(128), n, head, w(128))
+        mpdown(w(128), n4)
+        m4 = elan(256, h3(256), n, head, w(256))
+        mpdown(w(256), b5)
+        m5 = elan(512, h3(512), n, head, w(512))
+        feats = []
+        for f, c in ((n3, 256), (m4, 512), (m5, 1024)):
+            rows.append((f, "Conv", (w(c), 3, 1)) if x else (f, "RepConv", (c,)))
+            feats.append(len(rows) - 1)
+    else:
+        e6 = name == "yolov7e6"
+        assert e6 or name == "yolov7w6", name
+        w = (lambda c: c * 5 // 4) if e6 else (lambda c: c)
+        n = 6 if e6 else 4
+        back = [-1, -3, -5, -7, -8] if e6 else [-1, -3, -5, -6]
+        head = list(range(-1, -n - 3, -1))
+
+        def down(c, extra=None):   # w6: 3x3 stride 2; e6: DownC
+            if e6:
+                downc(w(c), extra)
+            else:
+                conv(-1, c, 3, 2)
+                if extra is not None:
+                    cat([-1, extra])
+
+        rows.append((-1, "ReOrg", ()))
+        conv(-1, w(64), 3, 1)
+        down(128)
+        elan(64, 64, n, back, w(128))
+        down(256)
+        b3 = elan(128, 128, n, back, w(256))
+        down(512)
+        b4 = elan(256, 256, n, back, w(512))
+        down(768)
+        b5 = elan(384, 384, n, back, w(768))
+        down(1024)
+        elan(512, 512, n, back, w(1024))
+        rows.append((-1, "SPPCSPC", (w(512),)))
+        b6 = len(rows) - 1
+        upjoin(w(384), b5)
+        n5 = elan(384, 192, n, head, w(384))
+        upjoin(w(256), b4)
+        n4 = elan(256, 128, n, head, w(256))
+        upjoin(w(128), b3)
+        n3 = elan(128, 64, n, head, w(128))
+        down(256, n4)
+        m4 = elan(256, 128, n, head, w(256))
+        down(384, n5)
+        m5 = elan(384, 192, n, head, w(384))
+        down(512, b6)
+        m6 = elan(512, 256, n, head, w(512))
+        feats = [conv(n3, w(256), 3), conv(m4, w(512), 3), conv(m5, w(768), 3), conv(m6, w(1024), 3)]
+    rows.append((feats, "Detect", ()))
+    return rows
+
+
+def yolov7_state(name="yolov7", seed=0, num_class=80):
+    """Seeded synthetic weights of yolov7tiny / yolov7 / yolov7x / yolov7w6 / yolov7e6 under the reference's `.wts` key names (the state_dict
+    keys of the deploy model, read by yolov7/src/block.cpp / model.cpp): OrderedDict name -> fp32 array.  Only what the host builder reads
+    is there: Conv + BatchNorm per convolution row, the two branches of RepConv (no identity branch: its c1 != c2), the biased detect
+    convolutions `m.i` and <detect>.anchor_grid - no implicit `ia` / `im` tensors, no strides.  He-scaled convolutions (gain 2 under SiLU,
+    2 / (1 + 0.1^2) under LeakyReLU(0.1), 1 for each of RepConv's summed branches) with near-identity BatchNorm statistics.  The detect
+    rows follow yolov5_state: objectness rows scaled by YOLOV7_OBJ_SCALE around YOLOV7_OBJ_BIAS_OF[name] so that 2 - 20 % of the anchors
+    of a small image pass the plugin's 0.1 gate (7 - 9 % for the SiLU models, 10 - 19 % for yolov7tiny at 128 x 128), class rows around YOLOV7_CLS_BIAS with one favoured class per (level, anchor)."""
+    import math
+    from collections import OrderedDict
+
+    import torch
+    assert name in YOLOV7_MODELS, name
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+    gain = 2.0 / 1.01 if name == "yolov7tiny" else 2.0
+
+    def bn(key, c):
+        sd[key + ".weight"] = (0.9 + 0.2 * rand(c)).float()
+        sd[key + ".bias"] = (0.1 * randn(c)).float()
+        sd[key + ".running_mean"] = (0.1 * randn(c)).float()
+        sd[key + ".running_var"] = (0.8 + 0.4 * rand(c)).float()
+        sd[key + ".num_batches_tracked"] = torch.zeros(1)
+
+    def cb(key, cout, cin, k):
+        sd[key + ".conv.weight"] = (randn(cout, cin, k, k) * math.sqrt(gain / (cin * k * k))).float()
+        bn(key + ".bn", cout)
+
+    ch = []   # output channels per row
+    rows = yolov7_rows(name)
+    for i, (f, mod, args) in enumerate(rows):
+        src = [(ch[j] if j >= 0 else (ch[i + j] if i + j >= 0 else 3)) for j in (f if isinstance(f, list) else [f])]
+        key = f"model.{i}"
+        if mod == "Conv":
+            cb(key, args[0], src[0], args[1])
+            ch.append(args[0])
+        elif mod in ("MP", "SP", "Upsample"):
+            ch.append(src[0])
+        elif mod == "Concat":
+            ch.append(sum(src))
+        elif mod == "ReOrg":
+            ch.append(4 * src[0])
+        elif mod == "DownC":
+            c2 = args[0]
+            cb(key + ".cv1", src[0], src[0], 1)
+            cb(key + ".cv2", c2 // 2, src[0], 3)
+            cb(key + ".cv3", c2 // 2, src[0], 1)
+            ch.append(c2)
+        elif mod == "SPPCSPC":
+            c_ = args[0]
+            for cv, cin, k in (("cv1", src[0], 1), ("cv2", src[0], 1), ("cv3", c_, 3), ("cv4", c_, 1), ("cv5", 4 * c_, 1), ("cv6", c_, 3), ("cv7", 2 * c_, 1)):
+                cb(f"{key}.{cv}", c_, cin, k)
+            ch.append(c_)
+        elif mod == "RepConv":
+            c2 = args[0]
+            sd[key + ".rbr_dense.0.weight"] = (randn(c2, src[0], 3, 3) * math.sqrt(1.0 / (src[0] * 9))).float()
+            bn(key + ".rbr_dense.1", c2)
+            sd[key + ".rbr_1x1.0.weight"] = (randn(c2, src[0], 1, 1) * math.sqrt(1.0 / src[0])).float()
+            bn(key + ".rbr_1x1.1", c2)
+            ch.append(c2)
+        else:
+            assert mod == "Detect" and i == len(rows) - 1
+            info = 5 + num_class
+            for lv, cin in enumerate(src):
+                w = randn(3 * info, cin, 1, 1) * math.sqrt(2.0 / cin)
+                b = 0.1 * randn(3 * info)
+                for k in range(3):
+                    w[k * info + 4] *= YOLOV7_OBJ_SCALE
+                    b[k * info + 4] += YOLOV7_OBJ_BIAS_OF[name]
+                    b[k * info + 5:(k + 1) * info] += YOLOV7_CLS_BIAS
+                    b[k * info + 5 + (7 * lv + 29 * k + 3) % num_class] += YOLOV7_CLS_MARGIN
+                    if name == "yolov7tiny":
+                        w[k * info + 5:(k + 1) * info] *= YOLOV7_TINY_CLS_ROW_SCALE
+                        w[k * info:k * info + 4] *= YOLOV7_TINY_BOX_ROW_SCALE
+                sd[f"{key}.m.{lv}.weight"] = w.float()
+                sd[f"{key}.m.{lv}.bias"] = b.float()
+            anchors = YOLOV7_TINY_ANCHORS if name == "yolov7tiny" else (YOLOV7_P6_ANCHORS if len(src) == 4 else YOLOV7_ANCHORS)
+            sd[key + ".anchor_grid"] = torch.tensor(anchors, dtype=torch.float32).reshape(len(src), 1, 3, 1, 1, 2)
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
