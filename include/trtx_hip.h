@@ -442,6 +442,23 @@ int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld
                                   trtx_stream_t stream);
 int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd, int hd,
                                    float scale, trtx_stream_t stream);
+/* YOLOv13's adaptive hypergraph convolution (tests / tools; kernels/hgconv.hip): AdaHyperedgeGen (yolov13/src/block.cpp:607-700) and AdaHGConv
+ * (block.cpp:746-790) with the eleven-layer tanh GELU (block.cpp:702-744), per image on x: NHWC fp16 [B][N][ld_x], D channels = the token image of
+ * AdaHGComputation (block.cpp:792-812), E hyperedges:
+ *   P = prototype_base + context_net([mean_n x, max_n x]);  A = softmax over the N NODES of logit_scale * (x W_pre^T + b_pre) . P;
+ *   out[b][n] = GELU((A GELU(A^T x W_edge^T + b_edge)) W_node^T + b_node) + x[b][n], fp16 with pixel stride ld_out.
+ * logit_scale = 1 / (heads * scaling) (the mean over the heads and the division by sqrt(head_dim)).  The weights are the layers' own fp32 device arrays:
+ * w_ctx [E D][2 D], b_ctx [E D], proto [E][D], w_pre / w_edge / w_node [D][D], b_pre / b_edge / b_node [D] (b_pre cancels in the node softmax: never read).
+ * workspace: at least trtx_op_hgconv_workspace_bytes(B, N, D, E) bytes of device memory, 16-byte aligned (a pure function of its four arguments; 0 for
+ * what the op does not implement).  TRTX_ERR_INVALID, nothing launched: a null pointer, ld_x or ld_out < D, a short workspace, a count < 1.
+ * TRTX_ERR_UNSUPPORTED, nothing launched: D % 16 != 0, D > 384, E > 16, x or out not 16-byte aligned or a pixel stride that is no multiple of 8.
+ * trtx_op_hgconv_geometry: the launcher's node-tile sizes, ascending, into tiles[0 .. max_tiles) and their count into *n_tiles (an image's result depends on N
+ * through these alone, never on B). */
+size_t trtx_op_hgconv_workspace_bytes(int B, int N, int D, int E);
+int32_t trtx_op_hgconv_geometry(int32_t* tiles, int max_tiles, int32_t* n_tiles);
+int32_t trtx_op_hgconv_f16(const void* x, int ld_x, void* out, int ld_out, int B, int N, int D, int E, float logit_scale, const float* w_ctx, const float* b_ctx,
+                           const float* proto, const float* w_pre, const float* b_pre, const float* w_edge, const float* b_edge, const float* w_node,
+                           const float* b_node, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 int32_t trtx_op_poison_lds(void* device_word, trtx_stream_t stream); /* test support: NaN patterns into every CU's LDS */
 int32_t trtx_op_nchw_f32_to_nhwc_f16(const float* in, void* out, int N, int C, int H, int W, int Cpad, int ld_out,
                                      trtx_stream_t stream);

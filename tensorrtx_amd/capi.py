@@ -614,6 +614,45 @@ def area_attention(qkv, heads, area, scale, out=None, vimg=None, out_ld=None, v_
     return _attention(lib().trtx_op_area_attention_f16, "trtx_op_area_attention_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, (area,))
 
 
+HGCONV_WEIGHTS = ("w_ctx", "b_ctx", "proto", "w_pre", "b_pre", "w_edge", "b_edge", "w_node", "b_node")   # trtx_op_hgconv_f16's nine fp32 arrays, in its order
+
+
+def hgconv_workspace_bytes(B, N, D, E):
+    """Bytes of device workspace trtx_op_hgconv_f16 needs: a pure function of its arguments (host only); 0 = (D, E) is not implemented."""
+    L = lib()
+    L.trtx_op_hgconv_workspace_bytes.restype = ctypes.c_size_t
+    return int(L.trtx_op_hgconv_workspace_bytes(int(B), int(N), int(D), int(E)))
+
+
+def hgconv_geometry():
+    """The node-tile sizes of the hypergraph convolution's launcher, ascending (host only)."""
+    arr, n = (ctypes.c_int32 * 8)(), ctypes.c_int32()
+    check(lib().trtx_op_hgconv_geometry(arr, 8, ctypes.byref(n)), "trtx_op_hgconv_geometry")
+    return [int(arr[i]) for i in range(min(n.value, 8))]
+
+
+def hgconv(x, E, logit_scale, weights, out=None, x_ld=None, out_ld=None, D=None, workspace=None):
+    """YOLOv13's hypergraph convolution (kernels/hgconv.hip).  x: CUDA fp16 [B, N, D] or a channel slice of a wider tensor (pixel stride x.stride(1));
+    out: likewise (allocated [B, N, D] when None); weights: a dict of CUDA fp32 tensors keyed by HGCONV_WEIGHTS (the layers' own layouts);
+    workspace: a CUDA uint8 tensor of at least hgconv_workspace_bytes() bytes (allocated when None).  -> out"""
+    import torch
+    L = lib()
+    B, N, Dx = x.shape
+    D = Dx if D is None else D
+    assert x.is_cuda and x.dtype == torch.float16
+    out = torch.empty((B, N, D), dtype=torch.float16, device=x.device) if out is None else out
+    assert out.is_cuda and out.dtype == torch.float16
+    ws = workspace if workspace is not None else torch.empty(max(hgconv_workspace_bytes(B, N, D, E), 256), dtype=torch.uint8, device=x.device)
+    ws_arr = [weights[k].contiguous() for k in HGCONV_WEIGHTS]
+    for w in ws_arr:
+        assert w.is_cuda and w.dtype == torch.float32
+    L.trtx_op_hgconv_f16.argtypes = ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.c_float] +
+                                     [ctypes.c_void_p] * 9 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p])
+    check(L.trtx_op_hgconv_f16(_p(x), x_ld or x.stride(1), _p(out), out_ld or out.stride(1), B, N, D, E, float(logit_scale), *[_p(w) for w in ws_arr],
+                               _p(ws), ws.numel(), _stream()), "trtx_op_hgconv_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- fp32 engines: conv on the fp32 MFMA (tests / tools)
 def pack_conv_weights_f32(w_kcrs, cin_pad=None, ch_scale=None):
     """Host: KCRS fp32 numpy -> (packed float32 [Cout_pad, Kpad], cout_pad, kpad, cink) for conv2d_nhwc_f32."""

@@ -24,6 +24,12 @@ __device__ __forceinline__ float mish_ref(float x) {
     const float sp = x > 20.f ? x : (x < -20.f ? expf(x) : logf(expf(x) + 1.f));
     return x * (2.f / (1.f + expf(-2.f * sp)) - 1.f);
 }
+// tanh-GELU as the reference spells it in eleven layers (yolov13/src/block.cpp:702-744), with its two rounded constants (0.797885f for
+// sqrt(2 / pi), 0.044715f) and in its order: ((x x) x) kappa, + x, * c, tanh, + 1, * x, * 0.5.  The accurate tanhf.  Not the erf form.
+__device__ __forceinline__ float gelu_tanh_ref(float x) {
+    const float inner = x + ((x * x) * x) * 0.044715f;
+    return (x * (tanhf(inner * 0.797885f) + 1.0f)) * 0.5f;
+}
 #endif
 
 constexpr int kYoloDetFloats = 90;  // sizeof(Detection)/4, yolov8/include/types.h:4-12

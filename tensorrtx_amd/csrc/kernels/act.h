@@ -1,6 +1,7 @@
 // The epilogue activations of the convolution and layer kernels, one definition per NUMERIC FAMILY, and the vector types the kernels share.
 // Which family a kernel uses is part of its contract: the parity bounds of the tests rest on it, and kernels that must return the same bits
 // (the exchangeable tactics of one layer) must use the same one.  A new activation kind is added here, once per family.
+// ACT_GELU_TANH (gelu_tanh_ref, common.h: the reference's constants, the accurate tanhf) is the same expression in every family.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,7 @@ __device__ __attribute__((noinline)) float act_fast_rare(float v, int act, float
         case ACT_LEAKY: return v > 0.f ? v : v * alpha;
         case ACT_TANH: return tanhf(v);
         case ACT_MISH: return mish_ref(v);
+        case ACT_GELU_TANH: return gelu_tanh_ref(v);
         default: return v;
     }
 }
@@ -45,6 +47,7 @@ __device__ __attribute__((noinline)) float act_f32_rare(float v, int act, float 
         case ACT_LEAKY: return v > 0.f ? v : v * alpha;
         case ACT_TANH: return tanhf(v);
         case ACT_MISH: return mish_ref(v);
+        case ACT_GELU_TANH: return gelu_tanh_ref(v);
         default: return v;
     }
 }
@@ -68,6 +71,7 @@ __device__ __forceinline__ float act_exact(float v, int act, float alpha) {
         case ACT_LEAKY: return v > 0.f ? v : v * alpha;
         case ACT_TANH: return tanhf(v);
         case ACT_MISH: return mish_ref(v);
+        case ACT_GELU_TANH: return gelu_tanh_ref(v);
         default: return v;
     }
 }
@@ -82,6 +86,7 @@ __device__ __forceinline__ float act_stem(float v, int act, float alpha) {
         case ACT_LEAKY: return v > 0.f ? v : v * alpha;
         case ACT_TANH: return tanhf(v);
         case ACT_MISH: return mish_ref(v);
+        case ACT_GELU_TANH: return gelu_tanh_ref(v);
         default: return v;
     }
 }

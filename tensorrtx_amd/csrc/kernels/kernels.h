@@ -9,7 +9,8 @@
 namespace trtx {
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_SILU = 3, ACT_LEAKY = 4, ACT_TANH = 5,
-                 ACT_MISH = 6 /* x * tanh(softplus(x)), the reference's Mish_TRT plugin (yolov4/mish.cu:113-135) */ };
+                 ACT_MISH = 6 /* x * tanh(softplus(x)), the reference's Mish_TRT plugin (yolov4/mish.cu:113-135) */,
+                 ACT_GELU_TANH = 7 /* 0.5 x (1 + tanh(0.797885 (x + 0.044715 x^3))), the reference's eleven-layer GELU() (yolov13/src/block.cpp:702-744) */ };
 enum DType : int { DT_F32 = 0, DT_F16 = 1, DT_I8 = 2 };
 inline size_t dtype_size(int dt) { return dt == DT_F16 ? 2 : (dt == DT_I8 ? 1 : 4); }
 enum EwOp : int { EW_SUM = 0, EW_PROD = 1, EW_MAX = 2, EW_MIN = 3, EW_SUB = 4, EW_DIV = 5, EW_POW = 6 };
@@ -183,6 +184,26 @@ bool area_attention_supported(int kd, int hd);
 int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd,
                            int hd, float scale, hipStream_t s);
 int32_t conv_dw(const ConvArgs& a, int dtype, hipStream_t s);
+// YOLOv13's adaptive hypergraph convolution (hgconv.hip; AdaHyperedgeGen + AdaHGConv, yolov13/src/block.cpp:607-790): NHWC fp16 x [B][N][ld_x] (D channels)
+// -> out [B][N][ld_out] = GELU((A He') W_node^T + b_node) + x with A the softmax over the N nodes of an image.  D % 16 == 0, D <= 384, 1 <= E <= 16; x and out
+// 16-byte aligned with pixel strides that are multiples of 8 (TRTX_ERR_UNSUPPORTED otherwise).  The weights are the layers' own fp32 arrays; `workspace`
+// holds at least hgconv_workspace_bytes(B, N, D, E) bytes (a pure function of its arguments; 0 = unsupported), 16-byte aligned.
+struct HgconvWeights {
+    const float* w_ctx;    // context_net.weight [E D][2 D]
+    const float* b_ctx;    // context_net.bias [E D]
+    const float* proto;    // prototype_base [E][D]
+    const float* w_pre;    // pre_head_proj.weight [D][D]
+    const float* b_pre;    // pre_head_proj.bias [D]: constant over the nodes, cancels in the node softmax (never read; may be null)
+    const float* w_edge;   // edge_proj.0.weight [D][D]
+    const float* b_edge;   // edge_proj.0.bias [D]
+    const float* w_node;   // node_proj.0.weight [D][D]
+    const float* b_node;   // node_proj.0.bias [D]
+};
+bool hgconv_supported(int D, int E);
+size_t hgconv_workspace_bytes(int B, int N, int D, int E);
+int hgconv_geometry(int32_t* tiles, int max_tiles);   // the node-tile sizes of the launcher (ascending); returns how many there are
+int32_t hgconv_f16(const void* x, int ld_x, void* out, int ld_out, int B, int N, int D, int E, float logit_scale, const HgconvWeights& w, void* workspace,
+                   size_t workspace_bytes, hipStream_t s);
 // grouped convolution on the matrix pipe (conv_grouped.hip): fp16, 2 <= groups <= 8, Cin / groups and Cout / groups multiples of 16 up to 64,
 // Cout <= 128, 1x1 pad 0 or 3x3 pad 1, stride 1, no dilation, channel strides multiples of 8.  Weights fp16 [group][Cout_g][Kpad],
 // k = tap * Cin_g + c, Kpad = conv_grouped_kpad() = K rounded up to 32 (ConvArgs::Kpad must say so); bias fp32 [Cout]

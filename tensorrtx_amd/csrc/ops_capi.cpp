@@ -230,6 +230,23 @@ extern "C" int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void*
     return area_attention_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, area, kd, hd, scale, static_cast<hipStream_t>(stream));
 }
 
+// --- YOLOv13's hypergraph convolution (kernels/hgconv.hip), test / tool entry points
+extern "C" size_t trtx_op_hgconv_workspace_bytes(int B, int N, int D, int E) { return hgconv_workspace_bytes(B, N, D, E); }
+
+extern "C" int32_t trtx_op_hgconv_geometry(int32_t* tiles, int max_tiles, int32_t* n_tiles) {
+    if (!tiles || !n_tiles || max_tiles < 1) return TRTX_ERR_INVALID;
+    *n_tiles = hgconv_geometry(tiles, max_tiles);
+    return TRTX_OK;
+}
+
+extern "C" int32_t trtx_op_hgconv_f16(const void* x, int ld_x, void* out, int ld_out, int B, int N, int D, int E, float logit_scale, const float* w_ctx,
+                                      const float* b_ctx, const float* proto, const float* w_pre, const float* b_pre, const float* w_edge, const float* b_edge,
+                                      const float* w_node, const float* b_node, void* workspace, size_t workspace_bytes, trtx_stream_t stream) {
+    if (!x || !out || !w_ctx || !b_ctx || !proto || !w_pre || !b_pre || !w_edge || !b_edge || !w_node || !b_node || !workspace) return TRTX_ERR_INVALID;
+    const HgconvWeights w{w_ctx, b_ctx, proto, w_pre, b_pre, w_edge, b_edge, w_node, b_node};
+    return hgconv_f16(x, ld_x, out, ld_out, B, N, D, E, logit_scale, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 // --- fp32 engines: the implicit-GEMM convolution on the fp32 MFMA (kernels/conv_igemm_f32.hip), test / tool entry points
 static ConvArgs op_conv_args_f32(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw,
                                  int act1, int has_res, int ld_res, int act2) {

@@ -452,6 +452,24 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                                            op.i[3], op.f[0], stream);
                 break;
             }
+            case OP_HGCONV: {
+                // the nine fp32 arrays in HgconvWeights' order, as pack_weights laid them out
+                const size_t D = (size_t)op.i[1], ED = (size_t)op.i[2] * D;
+                const float* p = reinterpret_cast<const float*>(W + op.w_off);
+                HgconvWeights w{};
+                w.w_ctx = p;  p += ED * 2 * D;
+                w.b_ctx = p;  p += ED;
+                w.proto = p;  p += ED;
+                w.w_pre = p;  p += D * D;
+                w.b_pre = p;  p += D;
+                w.w_edge = p; p += D * D;
+                w.b_edge = p; p += D;
+                w.w_node = p; p += D * D;
+                w.b_node = p;
+                st = hgconv_f16(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, nb(t0), op.i[0], op.i[1], op.i[2], op.f[0], w,
+                                static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+                break;
+            }
             case OP_ROI_ALIGN: {
                 const PTensor& ft = plan.tensors[op.in[1]];
                 st = trtx_roi_align_nhwc_f16_strided(batch, static_cast<const float*>(R.ptr(op.in[0])), R.ptr(op.in[1]), ft.ld, op.i[0], op.f[0], op.i[1],

@@ -177,6 +177,37 @@ struct Lowerer {
         return true;
     }
 
+    // The hypergraph convolution at its x_out shuffle: the NHWC image AdaHGComputation read in, the NHWC image it produced out (a concat behind it
+    // takes the op's output as a channel slice like any other NHWC tensor); the weights stay in their layers until pack_weights.
+    bool emit_hgconv(const HgconvFuse& f) {
+        const int in = need_nhwc(f.x);
+        const int out = new_tensor(f.out, net.tensors[f.out].dims, LAY_NHWC, true);
+        POp& op = add_op(OP_HGCONV, "hgconv:" + net.tensors[f.x].name, {in}, {out});
+        op.i[0] = f.N; op.i[1] = f.D; op.i[2] = f.E;
+        op.f[0] = f.logit_scale;
+        op.iv = {f.l_ctx, f.l_proto, f.l_pre, f.l_edge, f.l_node};
+        const int B = plan.tensors[in].nfix;
+        op.ws_bytes = hgconv_workspace_bytes(B, f.N, f.D, f.E);
+        if (op.ws_bytes == 0) return fail(op.name + ": no workspace size for a matched hypergraph convolution");
+        const double ed = (double)f.E * f.D;
+        // context_net, Q, the edge and node projections per image, and the three E-wide passes over the N x D tokens
+        op.flops = 2.0 * B * (ed * 2 * f.D + 3.0 * ed * f.D + 3.0 * f.N * ed);
+        op.bytes = 2.0 * B * f.N * f.D * 4;   // X read three times and written once, fp16 (pack_weights adds the weights)
+        pt_of[f.out] = out;
+        return true;
+    }
+
+    // A GELU chain standing alone: one activation op in the layout its input already has
+    bool emit_gelu(const GeluFuse& f) {
+        const int p = pt_of[f.in];
+        const bool nhwc = plan.tensors[p].layout == LAY_NHWC;
+        const int out = new_tensor(f.out, net.tensors[f.out].dims, nhwc ? LAY_NHWC : LAY_LINEAR, plan.tensors[p].batched);
+        POp& op = add_op(nhwc ? OP_ACT_NHWC : OP_ACT_LIN, net.layers[f.layers.back()].name + " [tanh GELU chain]", {p}, {out});
+        op.i[0] = ACT_GELU_TANH;
+        pt_of[f.out] = out;
+        return true;
+    }
+
     bool emit_yolo_head(const YoloHeadFuse& f) {
         const LayerDef& l = net.layers[f.plugin_layer];
         std::vector<int> ins, branches;
@@ -884,6 +915,15 @@ struct Lowerer {
             }
             if (fu.attn_at[li] >= 0) {
                 if (!emit_attention(fu.attns[fu.attn_at[li]])) return false;
+                continue;
+            }
+            if (fu.hgconv_at[li] >= 0) {
+                if (!emit_hgconv(fu.hgconvs[fu.hgconv_at[li]])) return false;
+                continue;
+            }
+            if (fu.gelu_at[li] >= 0) {
+                if (!emit_gelu(fu.gelus[fu.gelu_at[li]])) return false;
+                apply_aliases();
                 continue;
             }
             if (fu.group_at[li] >= 0) {

@@ -633,18 +633,297 @@ void match_area_attention(const NetView& g, Fusions& f) {
     }
 }
 
+// ---- YOLOv13's adaptive hypergraph convolution: AdaHGComputation (yolov13/src/block.cpp:792-812) from its `tokens` shuffle
+// ((B, D, H, W) -> (B, N, D)) to its `x_out` shuffle, i.e. AdaHyperedgeGen (607-700), AdaHGConv (746-790) and both GELU chains, walked
+// backwards from x_out.  Checked: every reshape and permutation, both reduces of the context and their axis, the concat axis, the three
+// Linear shapes and the prototype constant's, the head split (heads * head_dim == D), the scalar divisor, the mean over the heads, the
+// softmax axis (the NODES: 1 << 1 on (B, N, E)), both matmul transposes, both GELU chains, that the residual is the tokens tensor,
+// hgconv_supported, and that no tensor inside has a reader outside or is a network output.  Two spellings of AdaHGConv's reshapes:
+//  (a) batch-correct: He (B, E, D) -> (B E, D, 1, 1) for edge_proj, x_new = matmul(A (B, N, E), He' (B, E, D)) -> (B N, D, 1, 1);
+//  (b) the reference's literal ones, (E, B, D, 1) and a 2-d matmul of (N B, E) with (E, D), which are that network only at B == 1.
+// fp16 explicit-batch engines only, not kINT8, and not with TRTX_HGCONV=0; anything else keeps the generic linear path.
+bool match_hgconv_at(const NetView& g, int li, HgconvFuse* h, std::vector<int>* used) {
+    const Network& net = g.net;
+    auto dims = [&](int t) -> const Dims& { return net.tensors[t].dims; };
+    auto is = [](const Dims& d, std::initializer_list<int64_t> want) {
+        if (d.nb != (int)want.size()) return false;
+        int k = 0;
+        for (int64_t v : want)
+            if (d.d[k++] != v) return false;
+        return true;
+    };
+    auto layer_of = [&](int t, int kind) {   // the layer of `kind` that produces tensor t, or -1
+        const int l = g.producer(t);
+        return l >= 0 && net.layers[l].kind == kind ? l : -1;
+    };
+    auto view_src = [&](int t, int* l) {   // t = a reshape-only shuffle of the returned tensor, or -1
+        *l = layer_of(t, L_SHUFFLE);
+        if (*l < 0) return -1;
+        const LayerDef& s = net.layers[*l];
+        return ident(s.perm1, dims(s.inputs[0]).nb) && ident(s.perm2, dims(t).nb) ? s.inputs[0] : -1;
+    };
+    auto linear = [&](int l, int64_t out, int64_t in) {   // a fully connected layer out x in, with a bias of `out` values or none
+        const LayerDef& fc = net.layers[l];
+        return fc.nb_out == out && (int64_t)fc.w0.size() == out * in && (fc.w1.empty() || (int64_t)fc.w1.size() == out);
+    };
+    // x_out and the residual add
+    const LayerDef& xo = net.layers[li];
+    if (xo.kind != L_SHUFFLE || xo.reshape.nb != 4 || !perm_is(xo.perm1, {0, 2, 1}) || !ident(xo.perm2, 4)) return false;
+    const Dims& dimg = dims(xo.outputs[0]);
+    if (dimg.nb != 4) return false;
+    const int64_t B = dimg.d[0], D = dimg.d[1], N = dimg.d[2] * dimg.d[3];
+    const int l_add = layer_of(xo.inputs[0], L_ELEMENTWISE);
+    if (l_add < 0 || net.layers[l_add].op != TRTX_ELEMENTWISE_SUM || !is(dims(xo.inputs[0]), {B, N, D})) return false;
+    int l_tok = -1, t_fin = -1;
+    for (int s = 0; s < 2 && l_tok < 0; ++s) {
+        const int l = layer_of(net.layers[l_add].inputs[s], L_SHUFFLE);
+        if (l < 0) continue;
+        const LayerDef& tk = net.layers[l];
+        if (ident(tk.perm1, 4) && tk.reshape.nb == 3 && perm_is(tk.perm2, {0, 2, 1}) && dims(tk.inputs[0]) == dimg) {
+            l_tok = l;
+            t_fin = net.layers[l_add].inputs[1 - s];
+        }
+    }
+    if (l_tok < 0) return false;
+    const int T = net.layers[l_tok].outputs[0];
+    if (!is(dims(T), {B, N, D})) return false;
+    // back from the residual's other operand: reshape <- GELU <- node_proj <- reshape <- x_new = matmul(A, He')
+    int l_fin, l_xn4, l_a2 = -1, l_he2, l_he4, l_lgv, l_xhf, l_in4, l_po, l_ctx4;
+    GeluFuse g1, g2;
+    const int t_g2 = view_src(t_fin, &l_fin);
+    if (t_g2 < 0 || !(is(dims(t_fin), {B, N, D}) || (B == 1 && is(dims(t_fin), {1, N, D}))) || !is(dims(t_g2), {B * N, D, 1, 1}) ||
+        !match_tanh_gelu(g, g.producer(t_g2), &g2))
+        return false;
+    const int l_node = layer_of(g2.in, L_FULLY_CONNECTED);
+    if (l_node < 0 || !linear(l_node, D, D) || !is(dims(net.layers[l_node].inputs[0]), {B * N, D, 1, 1})) return false;
+    const int t_xnew = view_src(net.layers[l_node].inputs[0], &l_xn4);
+    if (t_xnew < 0) return false;
+    const int l_m2 = layer_of(t_xnew, L_MATMUL);
+    if (l_m2 < 0 || !plain_matmul(net.layers[l_m2])) return false;
+    int t_a = net.layers[l_m2].inputs[0];
+    const int t_he2 = net.layers[l_m2].inputs[1];
+    const bool literal = dims(t_xnew).nb == 2;   // spelling (b)
+    if (literal) {
+        if (B != 1 || !is(dims(t_xnew), {N, D}) || !is(dims(t_he2), {dims(t_he2).d[0], D})) return false;
+        const int64_t E2 = dims(t_he2).d[0];
+        if (!is(dims(t_a), {N, E2})) return false;
+        t_a = view_src(t_a, &l_a2);
+        if (t_a < 0) return false;
+    } else if (!is(dims(t_xnew), {B, N, D})) {
+        return false;
+    }
+    if (dims(t_a).nb != 3) return false;
+    const int64_t E = dims(t_a).d[2];
+    if (!is(dims(t_a), {B, N, E}) || !(literal ? is(dims(t_he2), {E, D}) : is(dims(t_he2), {B, E, D}))) return false;
+    // He' = reshape <- GELU <- edge_proj <- reshape <- He = matmul(A^T, tokens)
+    const int t_g1 = view_src(t_he2, &l_he2);
+    if (t_g1 < 0 || !is(dims(t_g1), {B * E, D, 1, 1}) || !match_tanh_gelu(g, g.producer(t_g1), &g1)) return false;
+    const int l_edge = layer_of(g1.in, L_FULLY_CONNECTED);
+    if (l_edge < 0 || !linear(l_edge, D, D)) return false;
+    const int t_he4 = net.layers[l_edge].inputs[0];
+    if (!(is(dims(t_he4), {B * E, D, 1, 1}) || (B == 1 && is(dims(t_he4), {E, 1, D, 1})))) return false;
+    const int t_he = view_src(t_he4, &l_he4);
+    if (t_he < 0 || !is(dims(t_he), {B, E, D})) return false;
+    const int l_m1 = layer_of(t_he, L_MATMUL);
+    if (l_m1 < 0 || net.layers[l_m1].mm_op[0] != TRTX_MATMUL_TRANSPOSE || net.layers[l_m1].mm_op[1] != TRTX_MATMUL_NONE ||
+        net.layers[l_m1].inputs[0] != t_a || net.layers[l_m1].inputs[1] != T)
+        return false;
+    // A = softmax over the nodes of the mean over the heads of (X_heads P_heads^T) / scaling
+    const int l_sm = layer_of(t_a, L_SOFTMAX);
+    if (l_sm < 0 || net.layers[l_sm].axis != (1 << 1)) return false;
+    const int l_red = layer_of(net.layers[l_sm].inputs[0], L_REDUCE);
+    if (l_red < 0 || net.layers[l_red].op != TRTX_REDUCE_AVG || net.layers[l_red].axis != (1 << 1) || net.layers[l_red].keep_dims) return false;
+    const int t_lgv = net.layers[l_red].inputs[0];
+    if (dims(t_lgv).nb != 4) return false;
+    const int64_t heads = dims(t_lgv).d[1];
+    if (heads < 1 || D % heads != 0 || !is(dims(t_lgv), {B, heads, N, E})) return false;
+    const int64_t hd = D / heads;
+    const int t_lgs = view_src(t_lgv, &l_lgv);
+    if (t_lgs < 0 || !is(dims(t_lgs), {B * heads, N, E})) return false;
+    const int l_div = layer_of(t_lgs, L_ELEMENTWISE);
+    if (l_div < 0 || net.layers[l_div].op != TRTX_ELEMENTWISE_DIV) return false;
+    const int l_sc = layer_of(net.layers[l_div].inputs[1], L_CONSTANT);
+    if (l_sc < 0 || net.layers[l_sc].w0.size() != 1 || !(net.layers[l_sc].w0[0] > 0.f)) return false;
+    const int l_m0 = layer_of(net.layers[l_div].inputs[0], L_MATMUL);
+    if (l_m0 < 0 || !plain_matmul(net.layers[l_m0])) return false;
+    const int t_xhf = net.layers[l_m0].inputs[0], t_phf = net.layers[l_m0].inputs[1];
+    if (!is(dims(t_xhf), {B * heads, N, hd}) || !is(dims(t_phf), {B * heads, hd, E})) return false;
+    // the node side: tokens -> (B N, D, 1, 1) -> pre_head_proj -> (B, N, heads, hd) -> {0, 2, 1, 3} -> (B heads, N, hd)
+    const int t_xh = view_src(t_xhf, &l_xhf);
+    if (t_xh < 0 || !is(dims(t_xh), {B, heads, N, hd})) return false;
+    const int l_xh = layer_of(t_xh, L_SHUFFLE);
+    if (l_xh < 0 || !ident(net.layers[l_xh].perm1, 4) || net.layers[l_xh].reshape.nb != 4 || !perm_is(net.layers[l_xh].perm2, {0, 2, 1, 3})) return false;
+    const int l_pre = layer_of(net.layers[l_xh].inputs[0], L_FULLY_CONNECTED);
+    if (l_pre < 0 || !linear(l_pre, D, D) || !is(dims(net.layers[l_pre].inputs[0]), {B * N, D, 1, 1})) return false;
+    if (view_src(net.layers[l_pre].inputs[0], &l_in4) != T) return false;
+    // the prototype side: (B, E, D) -> (B, E, heads, hd) -> {0, 2, 1, 3} -> (B heads, E, hd) -> {0, 2, 1}
+    const int l_phf = layer_of(t_phf, L_SHUFFLE);
+    if (l_phf < 0 || !ident(net.layers[l_phf].perm1, 4) || net.layers[l_phf].reshape.nb != 3 || !perm_is(net.layers[l_phf].perm2, {0, 2, 1})) return false;
+    const int t_ph = net.layers[l_phf].inputs[0];
+    const int l_ph = layer_of(t_ph, L_SHUFFLE);
+    if (l_ph < 0 || !is(dims(t_ph), {B, heads, E, hd}) || !ident(net.layers[l_ph].perm1, 3) || net.layers[l_ph].reshape.nb != 4 ||
+        !perm_is(net.layers[l_ph].perm2, {0, 2, 1, 3}))
+        return false;
+    const int t_protos = net.layers[l_ph].inputs[0];
+    const int l_protos = layer_of(t_protos, L_ELEMENTWISE);
+    if (l_protos < 0 || net.layers[l_protos].op != TRTX_ELEMENTWISE_SUM || !is(dims(t_protos), {B, E, D})) return false;
+    int l_base = -1, t_po = -1;
+    for (int s = 0; s < 2 && l_base < 0; ++s) {
+        l_base = layer_of(net.layers[l_protos].inputs[s], L_CONSTANT);
+        t_po = net.layers[l_protos].inputs[1 - s];
+    }
+    if (l_base < 0 || !is(dims(net.layers[l_base].outputs[0]), {1, E, D}) || !is(dims(t_po), {B, E, D})) return false;
+    const int t_fcc = view_src(t_po, &l_po);
+    if (t_fcc < 0 || !is(dims(t_fcc), {B, E * D, 1, 1})) return false;
+    const int l_ctx = layer_of(t_fcc, L_FULLY_CONNECTED);
+    if (l_ctx < 0 || !linear(l_ctx, E * D, 2 * D) || !is(dims(net.layers[l_ctx].inputs[0]), {B, 2 * D, 1, 1})) return false;
+    const int t_cat = view_src(net.layers[l_ctx].inputs[0], &l_ctx4);
+    if (t_cat < 0 || !is(dims(t_cat), {B, 2 * D})) return false;
+    const int l_cat = layer_of(t_cat, L_CONCAT);
+    if (l_cat < 0 || net.layers[l_cat].axis != 1 || net.layers[l_cat].inputs.size() != 2) return false;
+    const int l_mean = layer_of(net.layers[l_cat].inputs[0], L_REDUCE), l_max = layer_of(net.layers[l_cat].inputs[1], L_REDUCE);
+    auto node_reduce = [&](int l, int op) {
+        return l >= 0 && net.layers[l].op == op && net.layers[l].axis == (1 << 1) && !net.layers[l].keep_dims && net.layers[l].inputs[0] == T;
+    };
+    if (!node_reduce(l_mean, TRTX_REDUCE_AVG) || !node_reduce(l_max, TRTX_REDUCE_MAX)) return false;
+    if (!hgconv_supported((int)D, (int)E) || B * N > INT32_MAX) return false;
+    // the claim: every layer once, and nothing inside is read from outside or is a network output
+    *used = {l_tok, l_mean, l_max, l_cat, l_ctx4, l_ctx, l_po, l_base, l_protos, l_in4, l_pre, l_xh, l_ph, l_xhf, l_phf, l_m0, l_sc, l_div, l_lgv, l_red,
+             l_sm, l_m1, l_he4, l_edge, l_he2, l_m2, l_xn4, l_node, l_fin, l_add, li};
+    if (l_a2 >= 0) used->push_back(l_a2);
+    for (const GeluFuse* c : {&g1, &g2}) used->insert(used->end(), c->layers.begin(), c->layers.end());
+    std::vector<int> sorted(*used);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return false;
+    for (int u : *used) {
+        if (u == li) continue;
+        const int t = net.layers[u].outputs[0];
+        if (net.tensors[t].is_output) return false;
+        for (int r : g.consumers[t])
+            if (!std::binary_search(sorted.begin(), sorted.end(), r)) return false;
+    }
+    h->x = net.layers[l_tok].inputs[0];
+    h->out = xo.outputs[0];
+    h->N = (int)N;
+    h->D = (int)D;
+    h->E = (int)E;
+    h->logit_scale = 1.0f / ((float)heads * net.layers[l_sc].w0[0]);
+    h->l_ctx = l_ctx;
+    h->l_proto = l_base;
+    h->l_pre = l_pre;
+    h->l_edge = l_edge;
+    h->l_node = l_node;
+    return true;
+}
+
+void match_hgconv(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (!net.explicit_batch || g.dt != DT_F16 || net.int8 || !g.opt.hgconv) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        HgconvFuse h;
+        std::vector<int> used;
+        if (f.absorbed[li] || !match_hgconv_at(g, (int)li, &h, &used)) continue;
+        bool free = true;
+        for (int u : used) free = free && !f.absorbed[u];
+        if (!free) continue;
+        for (int u : used) f.absorbed[u] = true;
+        f.hgconv_at[li] = (int)f.hgconvs.size();
+        f.hgconvs.push_back(h);
+    }
+}
+
+// A GELU chain that no hypergraph convolution claimed becomes one activation op (ACT_GELU_TANH) at its last layer, in the layout its input has.
+void match_gelu_chains(const NetView& g, Fusions& f) {
+    for (size_t li = 0; li < g.net.layers.size(); ++li) {
+        GeluFuse c;
+        if (f.absorbed[li] || !match_tanh_gelu(g, (int)li, &c)) continue;
+        bool free = true;
+        for (int u : c.layers) free = free && !f.absorbed[u];
+        if (!free) continue;
+        for (int u : c.layers) f.absorbed[u] = true;
+        f.gelu_at[li] = (int)f.gelus.size();
+        f.gelus.push_back(c);
+    }
+}
+
 }  // namespace
+
+bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
+    const Network& net = g.net;
+    auto ew = [&](int l, int op) { return l >= 0 && net.layers[l].kind == L_ELEMENTWISE && net.layers[l].op == op && net.layers[l].inputs.size() == 2; };
+    // layer l = `op` of a tensor and a one-element constant of value v (either order): the tensor, or -1
+    auto with_const = [&](int l, int op, float v, int* cl) {
+        if (!ew(l, op)) return -1;
+        for (int s = 0; s < 2; ++s) {
+            const int c = g.producer(net.layers[l].inputs[s]);
+            if (c >= 0 && net.layers[c].kind == L_CONSTANT && net.layers[c].w0.size() == 1 && net.layers[c].w0[0] == v) {
+                *cl = c;
+                return net.layers[l].inputs[1 - s];
+            }
+        }
+        return -1;
+    };
+    int c_half, c_one, c_sqrt, c_kappa;
+    const int t_hx = with_const(last, TRTX_ELEMENTWISE_PROD, 0.5f, &c_half);
+    if (t_hx < 0) return false;
+    const int l_hx = g.producer(t_hx);
+    if (!ew(l_hx, TRTX_ELEMENTWISE_PROD)) return false;
+    int x = -1, l_add = -1, t_tanh = -1;
+    for (int s = 0; s < 2 && l_add < 0; ++s) {
+        const int la = g.producer(net.layers[l_hx].inputs[s]);
+        const int tt = with_const(la, TRTX_ELEMENTWISE_SUM, 1.0f, &c_one);
+        if (tt >= 0) {
+            l_add = la;
+            t_tanh = tt;
+            x = net.layers[l_hx].inputs[1 - s];
+        }
+    }
+    if (l_add < 0) return false;
+    const int l_tanh = g.producer(t_tanh);
+    if (l_tanh < 0 || net.layers[l_tanh].kind != L_ACTIVATION || net.layers[l_tanh].op != TRTX_ACTIVATION_TANH) return false;
+    const int l_si = g.producer(net.layers[l_tanh].inputs[0]);
+    const int t_inner = with_const(l_si, TRTX_ELEMENTWISE_PROD, 0.797885f, &c_sqrt);
+    if (t_inner < 0) return false;
+    const int l_inner = g.producer(t_inner);
+    if (!ew(l_inner, TRTX_ELEMENTWISE_SUM)) return false;
+    const LayerDef& in = net.layers[l_inner];
+    if (in.inputs[0] != x && in.inputs[1] != x) return false;
+    const int t_sx3 = in.inputs[0] == x ? in.inputs[1] : in.inputs[0];
+    const int l_sx3 = g.producer(t_sx3);
+    const int t_x3 = with_const(l_sx3, TRTX_ELEMENTWISE_PROD, 0.044715f, &c_kappa);
+    if (t_x3 < 0) return false;
+    const int l_x3 = g.producer(t_x3);
+    if (!ew(l_x3, TRTX_ELEMENTWISE_PROD)) return false;
+    const LayerDef& c3 = net.layers[l_x3];
+    if (c3.inputs[0] != x && c3.inputs[1] != x) return false;
+    const int l_x2 = g.producer(c3.inputs[0] == x ? c3.inputs[1] : c3.inputs[0]);
+    if (!ew(l_x2, TRTX_ELEMENTWISE_PROD) || net.layers[l_x2].inputs[0] != x || net.layers[l_x2].inputs[1] != x) return false;
+    f->layers = {l_x2, l_x3, c_kappa, l_sx3, l_inner, c_sqrt, l_si, l_tanh, c_one, l_add, l_hx, c_half, last};
+    std::vector<int> sorted(f->layers);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return false;
+    for (int u : f->layers) {
+        if (u == last) continue;
+        const int t = net.layers[u].outputs[0];
+        if (net.tensors[t].is_output) return false;
+        for (int r : g.consumers[t])
+            if (!std::binary_search(sorted.begin(), sorted.end(), r)) return false;
+    }
+    f->in = x;
+    f->out = net.layers[last].outputs[0];
+    return true;
+}
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
 // and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
-// attention, the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// attention, the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
     f.pad_cout.assign(nl, false);
     f.reorg_src.assign(nl, -1);
-    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = std::vector<int>(nl, -1);
+    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
     match_yolo9_heads(g, f);
@@ -652,6 +931,8 @@ Fusions match_fusions(const NetView& g) {
     match_yolo7_heads(g, f);
     match_psa_attention(g, f);
     match_area_attention(g, f);
+    match_hgconv(g, f);
+    match_gelu_chains(g, f);
     match_reorg_fold(g, f);
     match_conv_fusion(g, f);
     match_concat_activation(g, f);

@@ -56,8 +56,28 @@ struct AttentionFuse {
     int area = 0;                    // 0: YOLO11 PSA (psa_attention_kernel); >= 1: YOLOv12 area attention (area_attention_mfma_kernel), N / area keys per query
 };
 
+struct HgconvFuse {
+    int x = -1, out = -1;            // network tensors: the image AdaHGComputation reads (B, D, H, W) and the one its x_out shuffle produces
+    int N = 0, D = 0, E = 0;
+    float logit_scale = 0.f;         // 1 / (heads * the scaling constant)
+    int l_ctx = -1, l_proto = -1, l_pre = -1, l_edge = -1, l_node = -1;   // the layers that hold the weights: context_net, the prototype constant, three Linears
+};
+
+struct GeluFuse {
+    int in = -1, out = -1;           // network tensors: the chain's input and the result of its last product
+    std::vector<int> layers;         // the chain's nine computing layers and its four constants; back() is the last product
+};
+// The reference's tanh GELU (yolov13/src/block.cpp:702-744) ending in layer `last`: x2 = x x, x3 = x2 x, x3 kappa, + x, * sqrt(2 / pi), tanh, + 1, * x,
+// * 0.5, with the constants 0.044715f, 0.797885f, 1 and 0.5 as one-element constant layers.  Fills `f` when every layer is that chain's and none of the
+// tensors inside it has a reader outside it or is a network output (the last product's result is the chain's own).
+struct NetView;
+bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f);
+
 // What the matchers found.  *_at[layer] = index of the record whose op is emitted at that layer, or -1.
 struct Fusions {
+    std::vector<HgconvFuse> hgconvs;
+    std::vector<GeluFuse> gelus;
+    std::vector<int> hgconv_at, gelu_at;
     std::vector<FusedConv> groups;
     std::vector<YoloHeadFuse> yolo_heads;
     std::vector<AttentionFuse> attns;

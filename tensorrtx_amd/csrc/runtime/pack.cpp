@@ -244,6 +244,27 @@ bool pack_weights(const Network& net, Plan* plan) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);
             memcpy(blob.data() + op.w_off, l.w0.data(), 16 * 4);
+        } else if (op.kind == OP_HGCONV) {
+            // nine fp32 arrays in HgconvWeights' order, each as its layer holds it: context_net (weight, bias), the prototype constant,
+            // pre_head_proj, edge_proj, node_proj (weight, bias each); a Linear without a bias gets zeros
+            const size_t D = (size_t)op.i[1], ED = (size_t)op.i[2] * D;
+            const LayerDef &lc = net.layers[op.iv[0]], &lp = net.layers[op.iv[1]];
+            std::vector<float> all;
+            auto put = [&](const std::vector<float>& v, size_t n) {
+                const size_t at = all.size();
+                all.resize(at + n, 0.f);
+                std::copy(v.begin(), v.begin() + std::min(n, v.size()), all.begin() + at);
+            };
+            put(lc.w0, ED * 2 * D);
+            put(lc.w1, ED);
+            put(lp.w0, ED);
+            for (int k = 2; k < 5; ++k) {
+                put(net.layers[op.iv[k]].w0, D * D);
+                put(net.layers[op.iv[k]].w1, D);
+            }
+            op.w_off = reserve(all.size() * 4);
+            memcpy(blob.data() + op.w_off, all.data(), all.size() * 4);
+            op.bytes += 4.0 * all.size();
         } else if (op.kind == OP_SCALE_NHWC || op.kind == OP_SCALE_LIN) {
             const LayerDef& l = net.layers[op.src_layer];
             const int C = op.kind == OP_SCALE_NHWC ? plan->tensors[op.in[0]].C : (op.i[0] == 1 ? op.i[2] : 1);

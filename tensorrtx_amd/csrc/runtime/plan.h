@@ -56,6 +56,9 @@ enum OpKind : int {
                         // `in` = the three box tensors (64 DFL bins), `extra_in` = the three class tensors; i[0] = classes, i[1] / i[2] = net h / w,
                         // i[3] = max_out, i[4] = levels (3: strides 8 / 16 / 32); src_layer = the DFL 1x1 convolution
     OP_YOLO7_HEAD,      // OP_YOLO5_HEAD with YOLOv7's 6-float records (plugins/yolo7_head.hip): the same i / iv / fv
+    OP_HGCONV,          // YOLOv13's adaptive hypergraph convolution (kernels/hgconv.hip) on the NHWC fp16 token image: i[0] = N, i[1] = D, i[2] = E,
+                        // f[0] = the logit scale 1 / (heads * scaling); iv = the five network layers that hold the weights (context_net, the prototype
+                        // constant, pre_head_proj, edge_proj, node_proj), packed at w_off as nine fp32 arrays in HgconvWeights' order; ws = its workspace
 };
 const char* op_kind_name(int k);
 
