@@ -43,6 +43,11 @@ enum class ElementWiseOperation : int32_t { kSUM = 0, kPROD = 1, kMAX = 2, kMIN 
 enum class ScaleMode : int32_t { kUNIFORM = 0, kCHANNEL = 1, kELEMENTWISE = 2 };
 enum class ReduceOperation : int32_t { kSUM = 0, kPROD = 1, kMAX = 2, kMIN = 3, kAVG = 4 };
 enum class MatrixOperation : int32_t { kNONE = 0, kTRANSPOSE = 1, kVECTOR = 2 };
+// TensorRT's values.  The runtime has a kernel for kEXP only (yolov13/src/block.cpp:389); building a network with another one fails with its name.
+enum class UnaryOperation : int32_t {
+    kEXP = 0, kLOG = 1, kSQRT = 2, kRECIP = 3, kABS = 4, kNEG = 5, kSIN = 6, kCOS = 7, kTAN = 8, kSINH = 9, kCOSH = 10, kASIN = 11, kACOS = 12,
+    kATAN = 13, kASINH = 14, kACOSH = 15, kATANH = 16, kCEIL = 17, kFLOOR = 18, kERF = 19, kNOT = 20, kSIGN = 21, kROUND = 22, kISINF = 23
+};
 enum class ResizeMode : int32_t { kNEAREST = 0, kLINEAR = 1 };
 enum class BuilderFlag : int32_t { kFP16 = 0, kINT8 = 1 };
 enum class NetworkDefinitionCreationFlag : int32_t { kEXPLICIT_BATCH = 0, kSTRONGLY_TYPED = 1 };
@@ -312,6 +317,10 @@ class IReduceLayer : public ILayer {
 class IIdentityLayer : public ILayer {
    public:
     TRTX_LAYER_CTOR(IIdentityLayer)
+};
+class IUnaryLayer : public ILayer {
+   public:
+    TRTX_LAYER_CTOR(IUnaryLayer)
 };
 class IPluginV2Layer : public ILayer {
    public:
@@ -686,6 +695,7 @@ class INetworkDefinition {
         return layer<IReduceLayer>(trtx_add_reduce(mNet, in.id(), (int32_t)op, axes, keepDims ? 1 : 0));
     }
     IIdentityLayer* addIdentity(ITensor& in) noexcept { return layer<IIdentityLayer>(trtx_add_identity(mNet, in.id())); }
+    IUnaryLayer* addUnary(ITensor& in, UnaryOperation op) noexcept { return layer<IUnaryLayer>(trtx_network_add_unary(mNet, in.id(), (int32_t)op)); }
     IPluginV2Layer* addPluginV2(ITensor* const* inputs, int32_t nb, IPluginV2& plugin) noexcept {
         std::vector<int32_t> ids(nb > 0 ? nb : 0);
         for (int i = 0; i < nb; ++i) ids[i] = inputs[i]->id();

@@ -524,6 +524,9 @@ typedef struct trtx_dims {
 #define TRTX_MATMUL_NONE 0
 #define TRTX_MATMUL_TRANSPOSE 1
 #define TRTX_MATMUL_VECTOR 2
+/* nvinfer1::UnaryOperation: kEXP .. kISINF are 0 .. 23; only kEXP has a kernel, a network with another one is refused when it is built */
+#define TRTX_UNARY_EXP 0
+#define TRTX_UNARY_LAST 23
 /* nvinfer1::ResizeMode */
 #define TRTX_RESIZE_NEAREST 0
 #define TRTX_RESIZE_LINEAR 1
@@ -666,6 +669,8 @@ int32_t trtx_add_matrix_multiply(trtx_network* n, int32_t a, int32_t op_a, int32
 int32_t trtx_add_constant(trtx_network* n, const trtx_dims* dims, const float* values, int64_t count);
 int32_t trtx_add_reduce(trtx_network* n, int32_t input, int32_t op, uint32_t axes, int32_t keep_dims);
 int32_t trtx_add_identity(trtx_network* n, int32_t input);
+/* addUnary (yolov13/src/block.cpp:389: the exp of AAttn's spelled-out softmax); op: a TRTX_UNARY_* / nvinfer1::UnaryOperation value */
+int32_t trtx_network_add_unary(trtx_network* n, int32_t input, int32_t op);
 /* addPluginV2: the runtime clones the plugin through vtbl->clone (as TensorRT does) */
 int32_t trtx_add_plugin_v2(trtx_network* n, const int32_t* inputs, int32_t nb_inputs, const trtx_plugin_vtbl* plugin);
 

@@ -14,6 +14,7 @@ TRTX_P_AXIS, TRTX_P_RESHAPE, TRTX_P_FIRST_TRANSPOSE, TRTX_P_SECOND_TRANSPOSE = 7
 ACT = {"relu": 0, "sigmoid": 1, "tanh": 2, "leaky": 3}
 EW = {"sum": 0, "prod": 1, "max": 2, "min": 3, "sub": 4, "div": 5, "pow": 6}
 REDUCE = {"sum": 0, "max": 2, "avg": 4}
+UNARY = {"exp": 0, "log": 1, "sqrt": 2, "recip": 3, "abs": 4, "neg": 5}
 FLAG_FP16, FLAG_INT8 = 0, 1
 
 
@@ -174,6 +175,11 @@ class Network:
 
     def identity(self, x):
         return self._layer(self.L.trtx_add_identity(self.n, x), "add_identity")
+
+    def unary(self, x, op="exp"):
+        """IUnaryLayer; op: a UnaryOperation code or its name in UNARY (only kEXP has a kernel: build() refuses the others by name)"""
+        self.L.trtx_network_add_unary.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+        return self._layer(self.L.trtx_network_add_unary(self.n, x, UNARY.get(op, op)), "add_unary")
 
     def slice_channels(self, x, start, size, chw):
         """ISliceLayer over the channel axis of a (C, H, W) tensor: channels [start, start + size) (block.cpp:134-149, the C2f split)"""

@@ -72,6 +72,7 @@ __device__ __forceinline__ float act_exact(float v, int act, float alpha) {
         case ACT_TANH: return tanhf(v);
         case ACT_MISH: return mish_ref(v);
         case ACT_GELU_TANH: return gelu_tanh_ref(v);
+        case ACT_EXP: return expf(v);   // IUnaryLayer kEXP: the accurate expf in fp32, rounded once by the caller's store
         default: return v;
     }
 }

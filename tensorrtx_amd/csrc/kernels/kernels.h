@@ -10,7 +10,8 @@ namespace trtx {
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_SILU = 3, ACT_LEAKY = 4, ACT_TANH = 5,
                  ACT_MISH = 6 /* x * tanh(softplus(x)), the reference's Mish_TRT plugin (yolov4/mish.cu:113-135) */,
-                 ACT_GELU_TANH = 7 /* 0.5 x (1 + tanh(0.797885 (x + 0.044715 x^3))), the reference's eleven-layer GELU() (yolov13/src/block.cpp:702-744) */ };
+                 ACT_GELU_TANH = 7 /* 0.5 x (1 + tanh(0.797885 (x + 0.044715 x^3))), the reference's eleven-layer GELU() (yolov13/src/block.cpp:702-744) */,
+                 ACT_EXP = 8 /* e^x, IUnaryLayer kEXP (yolov13/src/block.cpp:389); an op of its own in the generic kernels (act_exact), never a convolution's epilogue */ };
 enum DType : int { DT_F32 = 0, DT_F16 = 1, DT_I8 = 2 };
 inline size_t dtype_size(int dt) { return dt == DT_F16 ? 2 : (dt == DT_I8 ? 1 : 4); }
 enum EwOp : int { EW_SUM = 0, EW_PROD = 1, EW_MAX = 2, EW_MIN = 3, EW_SUB = 4, EW_DIV = 5, EW_POW = 6 };
@@ -236,6 +237,9 @@ int32_t nhwc_elementwise(const void* a, const void* b, void* out, int dtype, int
                          int ld_b, int ld_out, hipStream_t s);
 int32_t nhwc_activation(const void* in, void* out, int dtype, int act, float alpha, long pixels, int C, int ld_in,
                         int ld_out, hipStream_t s);
+// out = a + gate (.) b, gate = C fp32 values (a one-element gate repeated); fp32 arithmetic, one rounding to `dtype` (DT_F16 / DT_F32)
+int32_t nhwc_gated_add(const void* a, const void* b, const float* gate, void* out, int dtype, long pixels, int C, int ld_a, int ld_b, int ld_out,
+                       hipStream_t s);
 int32_t nhwc_scale(const void* in, void* out, int dtype, const float* scale, const float* shift, long pixels, int C,
                    int ld_in, int ld_out, hipStream_t s);
 int32_t nhwc_copy(const void* in, void* out, int dtype, long pixels, int C, int ld_in, int ld_out, hipStream_t s);

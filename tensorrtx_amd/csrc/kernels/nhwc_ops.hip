@@ -249,6 +249,25 @@ __global__ void elementwise_kernel(const T* __restrict__ a, const T* __restrict_
     }
 }
 
+// out = a + g (.) b with one fp32 gate per channel (YOLOv13's FullPad_Tunnel and A2C2f's gamma residual, yolov13/src/block.cpp:889-900, 473-484):
+// fp32 product and sum, one rounding to the storage type.
+template <typename T, int V>
+__global__ void gated_add_kernel(const T* __restrict__ a, const T* __restrict__ b, const float* __restrict__ gate, T* __restrict__ out, long pixels,
+                                 int C, int ld_a, int ld_b, int ld_out) {
+    const int CV = C / V;
+    const long total = pixels * CV;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int cv = (int)(i % CV);
+        const long px = i / CV;
+        const Pack<T, V> x = *reinterpret_cast<const Pack<T, V>*>(a + px * ld_a + cv * V);
+        const Pack<T, V> y = *reinterpret_cast<const Pack<T, V>*>(b + px * ld_b + cv * V);
+        Pack<T, V> o;
+#pragma unroll
+        for (int e = 0; e < V; ++e) o.v[e] = from_f<T>(to_f(x.v[e]) + gate[cv * V + e] * to_f(y.v[e]));
+        *reinterpret_cast<Pack<T, V>*>(out + px * ld_out + cv * V) = o;
+    }
+}
+
 template <typename T, int V>
 __global__ void activation_kernel(const T* __restrict__ in, T* __restrict__ out, int act, float alpha, long pixels,
                                   int C, int ld_in, int ld_out) {
@@ -558,6 +577,20 @@ int32_t nhwc_elementwise(const void* a, const void* b, void* out, int dtype, int
     DISPATCH_T_V(dtype, vec, CALL);
 #undef CALL
     return check_launch("nhwc_elementwise");
+}
+
+int32_t nhwc_gated_add(const void* a, const void* b, const float* gate, void* out, int dtype, long pixels, int C, int ld_a, int ld_b, int ld_out,
+                       hipStream_t s) {
+    if (!a || !b || !gate || !out || pixels < 1 || C < 1 || ld_a < C || ld_b < C || ld_out < C || (dtype != DT_F16 && dtype != DT_F32)) return TRTX_ERR_INVALID;
+    // 16 bytes per lane wherever the channel count, the pixel strides and the bases allow it; a slice or a concat offset that rules it out (known only
+    // once the plan's buffers are laid out) takes the element-wise instantiation, as in every other op of this file
+    const bool vec = can_vec(dtype, C, {ld_a, ld_b, ld_out}, {a, b, out});
+#define CALL(T, V)                                                                                                                   \
+    hipLaunchKernelGGL((gated_add_kernel<T, V>), dim3(grid_for(pixels * (C / V))), dim3(kThreads), 0, s, static_cast<const T*>(a), \
+                       static_cast<const T*>(b), gate, static_cast<T*>(out), pixels, C, ld_a, ld_b, ld_out)
+    DISPATCH_T_V(dtype, vec, CALL);
+#undef CALL
+    return check_launch("nhwc_gated_add");
 }
 
 int32_t nhwc_activation(const void* in, void* out, int dtype, int act, float alpha, long pixels, int C, int ld_in,

@@ -39,6 +39,7 @@ Options read_options() {
     o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.hgconv = !env_is("TRTX_HGCONV", 0);
+    o.gated_add = !env_is("TRTX_GATED_ADD", 0);
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);
     o.yolo7_head = !env_is("TRTX_YOLO7_HEAD", 0);
     o.reorg_fold = !env_is("TRTX_REORG_FOLD", 0);

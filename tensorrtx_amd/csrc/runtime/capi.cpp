@@ -232,6 +232,18 @@ extern "C" int32_t trtx_add_identity(trtx_network* n, int32_t input) {
     l.inputs = {input};
     return n->net.add_layer(std::move(l));
 }
+extern "C" int32_t trtx_network_add_unary(trtx_network* n, int32_t input, int32_t op) {
+    if (!valid_tensor(n, input)) return -1;
+    if (op < TRTX_UNARY_EXP || op > TRTX_UNARY_LAST) {
+        n->net.error = "addUnary: " + std::to_string(op) + " is no UnaryOperation";
+        return -1;
+    }
+    LayerDef l;
+    l.kind = L_UNARY;
+    l.inputs = {input};
+    l.op = op;
+    return n->net.add_layer(std::move(l));
+}
 extern "C" int32_t trtx_add_plugin_v2(trtx_network* n, const int32_t* inputs, int32_t nb, const trtx_plugin_vtbl* plugin) {
     if (!n || !inputs || nb < 1 || !plugin || !plugin->clone) return -1;
     trtx_plugin_vtbl copy{};

@@ -267,6 +267,12 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                                       (long)nb(t0) * t0.H * t0.W, t0.C, t0.ld, t1.ld, to.ld, stream);
                 break;
             }
+            case OP_GATED_ADD: {
+                const PTensor& t1 = plan.tensors[op.in[1]];
+                st = nhwc_gated_add(R.ptr(op.in[0]), R.ptr(op.in[1]), reinterpret_cast<const float*>(W + op.w_off), R.ptr(op.out[0]), op.dtype,
+                                    (long)nb(t0) * t0.H * t0.W, t0.C, t0.ld, t1.ld, to.ld, stream);
+                break;
+            }
             case OP_ACT_NHWC:
                 st = nhwc_activation(R.ptr(op.in[0]), R.ptr(op.out[0]), op.dtype, op.i[0], op.f[0],
                                      (long)nb(t0) * t0.H * t0.W, t0.C, t0.ld, to.ld, stream);

@@ -154,6 +154,10 @@ bool Network::infer(int li) {
         case L_SOFTMAX:
             set_out(0, in(0));
             return true;
+        case L_UNARY:
+            if (l.op < TRTX_UNARY_EXP || l.op > TRTX_UNARY_LAST) return fail(this, l.name + ": not a unary operation (" + std::to_string(l.op) + ")");
+            set_out(0, in(0));
+            return true;
         case L_SCALE: {
             const Dims& x = in(0);
             const int64_t c = l.op == TRTX_SCALE_CHANNEL ? x.d[chan_axis(*this, x)] : (l.op == TRTX_SCALE_UNIFORM ? 1 : x.volume());

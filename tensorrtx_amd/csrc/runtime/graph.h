@@ -48,6 +48,7 @@ enum LayerKind : int32_t {
     L_REDUCE = 15,
     L_PLUGIN = 16,
     L_IDENTITY = 17,
+    L_UNARY = 18,  // appended: plans written before it deserialize unchanged
 };
 
 struct PluginHolder;  // runtime/plugin.h
@@ -75,7 +76,7 @@ struct LayerDef {
     int32_t padding[2] = {0, 0};
     int32_t dilation[2] = {1, 1};
     int32_t groups = 1;
-    int32_t op = 0;      // activation type / pooling type / elementwise op / scale mode / reduce op / resize mode
+    int32_t op = 0;      // activation type / pooling type / elementwise op / scale mode / reduce op / resize mode / unary op
     float alpha = 0.f;   // activation alpha
     float beta = 0.f;
     int32_t axis = -1;   // concat axis / softmax axes bitmask / reduce axes bitmask

@@ -208,6 +208,18 @@ struct Lowerer {
         return true;
     }
 
+    // a + gate (.) b at the sum: three NHWC images; the gate stays in its constant layer until pack_weights.  A concat behind it takes the output as a channel
+    // slice like any other NHWC tensor (try_place), and the op then writes at that slice's pixel stride.
+    bool emit_gated_add(int li, const GatedAddFuse& f) {
+        const int a = need_nhwc(f.a), b = need_nhwc(f.b);
+        const int out = new_tensor(f.out, net.tensors[f.out].dims, LAY_NHWC, true);
+        POp& op = add_op(OP_GATED_ADD, net.layers[li].name + " [a + gate * b]", {a, b}, {out});
+        op.src_layer = f.gate_layer;
+        op.bytes = 3.0 * dtype_size(dt) * net.tensors[f.out].dims.volume();
+        pt_of[f.out] = out;
+        return true;
+    }
+
     bool emit_yolo_head(const YoloHeadFuse& f) {
         const LayerDef& l = net.layers[f.plugin_layer];
         std::vector<int> ins, branches;
@@ -395,6 +407,16 @@ struct Lowerer {
         return true;
     }
 
+    bool emit_softmax(const std::string& name, int t_in, int t_out, int ax) {   // the LINEAR softmax op over dim `ax` of network tensor t_in
+        const Dims& di = net.tensors[t_in].dims;
+        const int in = need_lin(t_in);
+        const int out = new_tensor(t_out, net.tensors[t_out].dims, LAY_LINEAR, plan.tensors[in].batched);
+        POp& op = add_op(OP_SOFTMAX, name, {in}, {out});
+        op.i[0] = (int)extent(di, 0, ax); op.i[1] = (int)di.d[ax]; op.i[2] = (int)extent(di, ax + 1, di.nb);
+        pt_of[t_out] = out;
+        return true;
+    }
+
     bool emit_layer(int li) {
         const LayerDef& l = net.layers[li];
         auto out_dims = [&](int s = 0) -> const Dims& { return net.tensors[l.outputs[s]].dims; };
@@ -487,6 +509,14 @@ struct Lowerer {
                 if (code < 0) return fail(l.name + ": unsupported activation type");
                 return emit_activation(l, code, l.alpha);
             }
+            case L_UNARY: {
+                static const char* const names[] = {"kEXP", "kLOG", "kSQRT", "kRECIP", "kABS", "kNEG", "kSIN", "kCOS", "kTAN", "kSINH", "kCOSH", "kASIN",
+                                                    "kACOS", "kATAN", "kASINH", "kACOSH", "kATANH", "kCEIL", "kFLOOR", "kERF", "kNOT", "kSIGN", "kROUND", "kISINF"};
+                if (l.op != TRTX_UNARY_EXP)
+                    return fail(l.name + ": unary operation " + (l.op > 0 && l.op <= TRTX_UNARY_LAST ? std::string(names[l.op]) : std::to_string(l.op)) +
+                                " is not implemented (only kEXP is)");
+                return emit_activation(l, ACT_EXP, 0.f);
+            }
             case L_SCALE: {
                 bool pow1 = true;
                 for (float p : l.w2) pow1 = pow1 && p == 1.0f;
@@ -559,12 +589,7 @@ struct Lowerer {
                         }
                     if (ax < 0) return fail(l.name + ": softmax without axis");
                 }
-                const int in = need_lin(l.inputs[0]);
-                const int out = new_tensor(l.outputs[0], out_dims(), LAY_LINEAR, plan.tensors[in].batched);
-                POp& op = add_op(OP_SOFTMAX, l.name, {in}, {out});
-                op.i[0] = (int)extent(di, 0, ax); op.i[1] = (int)di.d[ax]; op.i[2] = (int)extent(di, ax + 1, di.nb);
-                pt_of[l.outputs[0]] = out;
-                return true;
+                return emit_softmax(l.name, l.inputs[0], l.outputs[0], ax);
             }
             case L_MATMUL: {
                 const Dims &da = net.tensors[l.inputs[0]].dims, &db = net.tensors[l.inputs[1]].dims;
@@ -923,6 +948,17 @@ struct Lowerer {
             }
             if (fu.gelu_at[li] >= 0) {
                 if (!emit_gelu(fu.gelus[fu.gelu_at[li]])) return false;
+                apply_aliases();
+                continue;
+            }
+            if (fu.softmax_at[li] >= 0) {   // a spelled-out softmax standing alone: the softmax op at its division
+                const SoftmaxChainFuse& c = fu.softmax_chains[fu.softmax_at[li]];
+                if (!emit_softmax(net.layers[li].name + " [max / sub / exp / sum / div chain]", c.in, c.out, c.axis)) return false;
+                apply_aliases();
+                continue;
+            }
+            if (fu.gated_at[li] >= 0) {
+                if (!emit_gated_add((int)li, fu.gated_adds[fu.gated_at[li]])) return false;
                 apply_aliases();
                 continue;
             }

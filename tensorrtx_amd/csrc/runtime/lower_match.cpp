@@ -846,7 +846,98 @@ void match_gelu_chains(const NetView& g, Fusions& f) {
     }
 }
 
+// a + gate (.) b on images with a constant gate of one element (FullPad_Tunnel, yolov13/src/block.cpp:889-900) or one element per channel (the gamma
+// residual of A2C2f, block.cpp:473-484), the product in either operand order on either side of the sum: one gated-add op at the sum instead of a broadcast
+// product on the LINEAR path (two layout passes) and an element-wise sum.  The product must have no other reader and the map more than one pixel.  fp32 and fp16 engines, not kINT8, and
+// not with TRTX_GATED_ADD=0.  Runs before the convolution fusion, which would otherwise take the sum as a residual epilogue.
+void match_gated_add(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (!g.opt.gated_add || net.int8) return;
+    auto ew = [&](int l, int op) { return l >= 0 && !f.absorbed[l] && net.layers[l].kind == L_ELEMENTWISE && net.layers[l].op == op && net.layers[l].inputs.size() == 2; };
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        if (!ew((int)li, TRTX_ELEMENTWISE_SUM)) continue;
+        const LayerDef& sum = net.layers[li];
+        const Dims& d = net.tensors[sum.outputs[0]].dims;
+        // feature maps only: a (rows, D, 1, 1) tensor is a token matrix of the linear path (the Linears of AdaHGConv and the GELU chains behind them,
+        // whose x + 0.044715 x^3 has this very shape); those keep their element-wise ops
+        if (d.nb != (net.explicit_batch ? 4 : 3) || d.d[d.nb - 2] * d.d[d.nb - 1] == 1) continue;
+        const int ca = d.nb - 3;
+        for (int s = 0; s < 2 && f.gated_at[li] < 0; ++s) {
+            const int t_prod = sum.inputs[s], l_prod = g.producer(t_prod), a = sum.inputs[1 - s];
+            if (!ew(l_prod, TRTX_ELEMENTWISE_PROD) || !g.only_used_by(t_prod, {(int)li}) || !(net.tensors[a].dims == d)) continue;
+            for (int q = 0; q < 2; ++q) {
+                const int l_gate = g.producer(net.layers[l_prod].inputs[q]), b = net.layers[l_prod].inputs[1 - q];
+                if (l_gate < 0 || net.layers[l_gate].kind != L_CONSTANT || f.absorbed[l_gate] || !(net.tensors[b].dims == d)) continue;
+                const Dims& cd = net.layers[l_gate].out_dims;
+                bool ok = cd.nb == d.nb;
+                for (int k = 0; ok && k < d.nb; ++k) ok = cd.d[k] == 1 || (k == ca && cd.d[k] == d.d[k]);
+                if (!ok) continue;
+                GatedAddFuse r;
+                r.a = a;
+                r.b = b;
+                r.out = sum.outputs[0];
+                r.gate_layer = l_gate;
+                f.absorbed[l_prod] = f.absorbed[li] = true;
+                if (g.only_used_by(net.layers[l_gate].outputs[0], {l_prod})) f.absorbed[l_gate] = true;   // (a gate with another reader stays a constant tensor)
+                f.gated_at[li] = (int)f.gated_adds.size();
+                f.gated_adds.push_back(r);
+                break;
+            }
+        }
+    }
+}
+
+// A spelled-out softmax that no attention claimed becomes the softmax op at its division (LINEAR fp32, like ISoftMaxLayer's).
+void match_softmax_chains(const NetView& g, Fusions& f) {
+    for (size_t li = 0; li < g.net.layers.size(); ++li) {
+        SoftmaxChainFuse c;
+        if (f.absorbed[li] || !match_exp_softmax(g, (int)li, &c)) continue;
+        bool free = true;
+        for (int u : c.layers) free = free && !f.absorbed[u];
+        if (!free) continue;
+        for (int u : c.layers) f.absorbed[u] = true;
+        f.softmax_at[li] = (int)f.softmax_chains.size();
+        f.softmax_chains.push_back(c);
+    }
+}
+
 }  // namespace
+
+bool match_exp_softmax(const NetView& g, int last, SoftmaxChainFuse* f) {
+    const Network& net = g.net;
+    auto ew = [&](int l, int op) { return l >= 0 && net.layers[l].kind == L_ELEMENTWISE && net.layers[l].op == op && net.layers[l].inputs.size() == 2; };
+    // layer l = a keepDims reduction `op` of tensor `of` over exactly one axis: that axis, or -1
+    auto reduce_of = [&](int l, int op, int of) {
+        if (l < 0 || net.layers[l].kind != L_REDUCE || net.layers[l].op != op || !net.layers[l].keep_dims || net.layers[l].inputs[0] != of) return -1;
+        const int32_t mask = net.layers[l].axis;
+        const int nb = net.tensors[of].dims.nb;
+        for (int k = 0; k < nb; ++k)
+            if (mask == (1 << k)) return k;
+        return -1;
+    };
+    if (!ew(last, TRTX_ELEMENTWISE_DIV)) return false;
+    const int t_exp = net.layers[last].inputs[0], l_sum = g.producer(net.layers[last].inputs[1]);
+    const int axis = reduce_of(l_sum, TRTX_REDUCE_SUM, t_exp);
+    if (axis < 0) return false;
+    const int l_exp = g.producer(t_exp);
+    if (l_exp < 0 || net.layers[l_exp].kind != L_UNARY || net.layers[l_exp].op != TRTX_UNARY_EXP) return false;
+    const int l_sub = g.producer(net.layers[l_exp].inputs[0]);
+    if (!ew(l_sub, TRTX_ELEMENTWISE_SUB)) return false;
+    const int x = net.layers[l_sub].inputs[0], l_max = g.producer(net.layers[l_sub].inputs[1]);
+    if (reduce_of(l_max, TRTX_REDUCE_MAX, x) != axis) return false;
+    f->layers = {l_max, l_sub, l_exp, l_sum, last};
+    for (int u : f->layers) {
+        if (u == last) continue;
+        const int t = net.layers[u].outputs[0];
+        if (net.tensors[t].is_output) return false;
+        for (int r : g.consumers[t])
+            if (std::find(f->layers.begin(), f->layers.end(), r) == f->layers.end()) return false;
+    }
+    f->in = x;
+    f->out = net.layers[last].outputs[0];
+    f->axis = axis;
+    return true;
+}
 
 bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
     const Network& net = g.net;
@@ -916,14 +1007,14 @@ bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
 // and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
-// attention, the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// attention, the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
     f.pad_cout.assign(nl, false);
     f.reorg_src.assign(nl, -1);
-    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = std::vector<int>(nl, -1);
+    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = f.softmax_at = f.gated_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
     match_yolo9_heads(g, f);
@@ -933,6 +1024,8 @@ Fusions match_fusions(const NetView& g) {
     match_area_attention(g, f);
     match_hgconv(g, f);
     match_gelu_chains(g, f);
+    match_softmax_chains(g, f);
+    match_gated_add(g, f);
     match_reorg_fold(g, f);
     match_conv_fusion(g, f);
     match_concat_activation(g, f);

@@ -73,11 +73,29 @@ struct GeluFuse {
 struct NetView;
 bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f);
 
+struct SoftmaxChainFuse {
+    int in = -1, out = -1;           // network tensors: the scores and the result of the division
+    int axis = -1;                   // the dim both reductions run over
+    std::vector<int> layers;         // reduce-max, sub, exp, reduce-sum, div; back() is the division
+};
+// The reference's spelled-out softmax (AAttn, yolov13/src/block.cpp:384-394) ending in the division `last`: m = reduce-max(x) over one axis with keepDims,
+// x - m, exp, s = reduce-sum of the exp over the same axis with keepDims, exp / s.  Fills `f` when every layer is that chain's and none of the tensors inside
+// it has a reader outside it or is a network output.
+bool match_exp_softmax(const NetView& g, int last, SoftmaxChainFuse* f);
+
+struct GatedAddFuse {
+    int a = -1, b = -1, out = -1;    // network tensors: out = a + gate (.) b, three images of the same dims
+    int gate_layer = -1;             // the constant layer that holds the gate: one element, or one per channel
+};
+
 // What the matchers found.  *_at[layer] = index of the record whose op is emitted at that layer, or -1.
 struct Fusions {
+    std::vector<GatedAddFuse> gated_adds;
+    std::vector<int> gated_at;
     std::vector<HgconvFuse> hgconvs;
     std::vector<GeluFuse> gelus;
-    std::vector<int> hgconv_at, gelu_at;
+    std::vector<SoftmaxChainFuse> softmax_chains;
+    std::vector<int> hgconv_at, gelu_at, softmax_at;
     std::vector<FusedConv> groups;
     std::vector<YoloHeadFuse> yolo_heads;
     std::vector<AttentionFuse> attns;

@@ -265,6 +265,12 @@ bool pack_weights(const Network& net, Plan* plan) {
             op.w_off = reserve(all.size() * 4);
             memcpy(blob.data() + op.w_off, all.data(), all.size() * 4);
             op.bytes += 4.0 * all.size();
+        } else if (op.kind == OP_GATED_ADD) {
+            const std::vector<float>& g = net.layers[op.src_layer].w0;   // one value, or one per channel (match_gated_add)
+            const int C = plan->tensors[op.in[0]].C;
+            op.w_off = reserve((size_t)C * 4);
+            float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
+            for (int c = 0; c < C; ++c) dst[c] = g.size() == 1 ? g[0] : g[c];
         } else if (op.kind == OP_SCALE_NHWC || op.kind == OP_SCALE_LIN) {
             const LayerDef& l = net.layers[op.src_layer];
             const int C = op.kind == OP_SCALE_NHWC ? plan->tensors[op.in[0]].C : (op.i[0] == 1 ? op.i[2] : 1);

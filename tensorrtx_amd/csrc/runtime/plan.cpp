@@ -10,8 +10,8 @@ const char* op_kind_name(int k) {
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
-                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv"};
-    return (k >= 0 && k <= OP_HGCONV) ? n[k] : "?";
+                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add"};
+    return (k >= 0 && k <= OP_GATED_ADD) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -52,6 +52,7 @@ std::string Plan::describe_json() const {
             if (op.reorg_cin) o << ",\"reorg_cin\":" << op.reorg_cin;
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
+        if (op.kind == OP_ACT_NHWC || op.kind == OP_ACT_LIN) o << ",\"act\":" << op.i[0];
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
         if (op.kind == OP_ATTENTION && op.i[4] > 0) o << ",\"area\":" << op.i[4] << ",\"kernel\":\"mfma\"";
         if (op.kind == OP_HGCONV)

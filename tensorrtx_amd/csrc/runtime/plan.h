@@ -59,6 +59,8 @@ enum OpKind : int {
     OP_HGCONV,          // YOLOv13's adaptive hypergraph convolution (kernels/hgconv.hip) on the NHWC fp16 token image: i[0] = N, i[1] = D, i[2] = E,
                         // f[0] = the logit scale 1 / (heads * scaling); iv = the five network layers that hold the weights (context_net, the prototype
                         // constant, pre_head_proj, edge_proj, node_proj), packed at w_off as nine fp32 arrays in HgconvWeights' order; ws = its workspace
+    OP_GATED_ADD,       // out = in[0] + gate (.) in[1] on NHWC tensors (nhwc_gated_add): src_layer = the constant layer that holds the gate (one value, or one per
+                        // channel), packed at w_off as C fp32 values
 };
 const char* op_kind_name(int k);
 
