@@ -73,6 +73,9 @@ int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels, int batch,
  * YoloLayerPlugin::enqueue).  heads[l]: device fp16 [batch][cells_l][ld[l]], channels [0,64) = 4x16 DFL
  * bins, [64, 64+classes) = class logits; dfl_weights: device fp32[16] (model.22.dfl.conv.weight).
  * Output format and candidate order are those of trtx_yolo_decode.  classes % 8 == 0.
+ * Refused with nothing written: TRTX_ERR_INVALID for a null pointer, n_levels outside 1..8, batch / max_out / net_h / net_w < 1, a
+ * stride < 1 or a class count that is no positive multiple of 8; TRTX_ERR_WORKSPACE; TRTX_ERR_UNSUPPORTED for a base or an ld[l] that
+ * is no 16-byte multiple, or ld[l] < 64 + classes.  The workspace size of a geometry refused here is 0.
  */
 size_t trtx_yolo_head_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels);
 int32_t trtx_yolo_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes,

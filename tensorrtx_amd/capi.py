@@ -136,40 +136,62 @@ def _head_table(tensors):
     return (ctypes.c_void_p * n)(*[x.data_ptr() for x in tensors]), (ctypes.c_int * n)(*[x.shape[-1] for x in tensors])
 
 
-def yolo_head_decode_nhwc(heads, classes, net_h, net_w, strides, dfl_w, max_out=1000):
-    """The fused det head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32): trtx_yolo_head_decode_nhwc{,_f32}."""
+def yolo_head_decode_workspace(batch, net_h, net_w, strides):
+    L = lib()
+    L.trtx_yolo_head_decode_workspace.restype = ctypes.c_size_t
+    return L.trtx_yolo_head_decode_workspace(batch, net_h, net_w, (ctypes.c_int * len(strides))(*strides), len(strides))
+
+
+def _head_call(heads, net_h, net_w, strides, max_out, out, ws, batch, n_levels):
+    """What the two fused-head wrappers share: the batch, the stride table (None: a null pointer), the level count passed, `out` and `ws`"""
+    import torch
+    B, n, dev = heads[0].shape[0] if batch is None else batch, len(heads), heads[0].device
+    st = None if strides is None else (ctypes.c_int * len(strides))(*strides)
+    if ws is None:
+        ws = torch.empty(max(yolo_head_decode_workspace(B, net_h, net_w, strides), 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros(B, 1 + max_out * DET_FLOATS, dtype=torch.float32, device=dev)
+    return B, n if n_levels is None else n_levels, st, out, ws
+
+
+def yolo_head_decode_nhwc(heads, classes, net_h, net_w, strides, dfl_w, max_out=1000, out=None, ws=None, batch=None, ld=None, n_levels=None,
+                          status_only=False):
+    """The fused det head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32): trtx_yolo_head_decode_nhwc{,_f32}.
+    `out` / `ws`: the caller's buffers; `batch`, `ld`, `n_levels`: what is passed instead of the tensors' own; `strides` / `dfl_w` None: a
+    null pointer; `status_only`: return the status code instead of raising (the refusal tests; a failure otherwise raises TrtxError)."""
     import torch
     L = lib()
-    B, n = heads[0].shape[0], len(heads)
     hp, hl = _head_table(heads)
-    st = (ctypes.c_int * n)(*strides)
-    L.trtx_yolo_head_decode_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_head_decode_workspace(B, net_h, net_w, st, n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=heads[0].device)
-    out = torch.zeros(B, 1 + max_out * DET_FLOATS, dtype=torch.float32, device=heads[0].device)
+    if ld is not None:
+        hl = (ctypes.c_int * len(ld))(*ld)
+    B, n, st, out, ws = _head_call(heads, net_h, net_w, strides, max_out, out, ws, batch, n_levels)
     fn = L.trtx_yolo_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolo_head_decode_nhwc
-    check(fn(hp, hl, n, B, classes, net_h, net_w, st, _p(dfl_w), max_out, _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()),
-          "trtx_yolo_head_decode_nhwc")
+    status = fn(hp, hl, n, B, classes, net_h, net_w, st, _p(dfl_w), max_out, _p(out), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    if status_only:
+        return status
+    check(status, "trtx_yolo_head_decode_nhwc")
     return out
 
 
 def yolo_task_head_decode_nhwc(heads, branches, classes, net_h, net_w, strides, dfl_w, max_out=1000, nk=17, kpt_conf=0.0, seg=False,
-                               pose=False, obb=False):
+                               pose=False, obb=False, out=None, ws=None, batch=None, ld=None, branch_ld=None, n_levels=None, status_only=False):
     """The fused YOLO11 task head (trtx_yolo_task_head_decode_nhwc{,_f32}): NHWC head tensors [B, gh, gw, ld] and branch tensors
-    [B, gh, gw, branch_ld], fp16 or fp32; output rows as yolo_decode_ex."""
+    [B, gh, gw, branch_ld], fp16 or fp32; output rows as yolo_decode_ex.  The keyword arguments behind `obb` as in yolo_head_decode_nhwc."""
     import torch
     L = lib()
-    B, n = heads[0].shape[0], len(heads)
     hp, hl = _head_table(heads)
     bp, bl = _head_table(branches)
-    st = (ctypes.c_int * n)(*strides)
-    L.trtx_yolo_head_decode_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_head_decode_workspace(B, net_h, net_w, st, n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=heads[0].device)
-    out = torch.zeros(B, 1 + max_out * DET_FLOATS, dtype=torch.float32, device=heads[0].device)
+    if ld is not None:
+        hl = (ctypes.c_int * len(ld))(*ld)
+    if branch_ld is not None:
+        bl = (ctypes.c_int * len(branch_ld))(*branch_ld)
+    B, n, st, out, ws = _head_call(heads, net_h, net_w, strides, max_out, out, ws, batch, n_levels)
     fn = L.trtx_yolo_task_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolo_task_head_decode_nhwc
-    check(fn(hp, hl, bp, bl, n, B, classes, net_h, net_w, st, _p(dfl_w), max_out, int(seg), int(pose), int(obb), nk, ctypes.c_float(kpt_conf),
-             _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolo_task_head_decode_nhwc")
+    status = fn(hp, hl, bp, bl, n, B, classes, net_h, net_w, st, _p(dfl_w), max_out, int(seg), int(pose), int(obb), nk, ctypes.c_float(kpt_conf),
+                _p(out), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    if status_only:
+        return status
+    check(status, "trtx_yolo_task_head_decode_nhwc")
     return out
 
 

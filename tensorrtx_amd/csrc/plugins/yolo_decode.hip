@@ -559,7 +559,18 @@ static LevelTable make_levels(int n_levels, int net_h, int net_w, const int* str
     return t;
 }
 
+// the level geometry every entry path divides by: a null table, a stride below 1 or an empty net would be a host division by zero or a
+// launch over no cells
+static bool bad_geometry(int n_levels, int net_h, int net_w, const int* strides) {
+    if (n_levels < 1 || n_levels > kMaxLevels || !strides || net_h < 1 || net_w < 1) return true;
+    for (int i = 0; i < n_levels; ++i)
+        if (strides[i] < 1) return true;
+    return false;
+}
+
+// 0 for a geometry no entry path accepts (bad_geometry, or no level holds a cell)
 static size_t count_cells(int net_h, int net_w, const int* strides, int n_levels) {
+    if (bad_geometry(n_levels, net_h, net_w, strides)) return 0;
     size_t cells = 0;
     for (int i = 0; i < n_levels; ++i) cells += (size_t)(net_h / strides[i]) * (net_w / strides[i]);
     return cells;
@@ -615,7 +626,7 @@ extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels,
                                        const int* strides, int max_out, int n_kpt, float kpt_conf, int is_seg, int is_pose, int is_obb,
                                        float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !inputs || !output ||
-        !workspace || n_kpt < 0 || n_kpt > 17)
+        !workspace || n_kpt < 0 || n_kpt > 17 || count_cells(net_h, net_w, strides, n_levels) == 0)
         return TRTX_ERR_INVALID;
     if (workspace_bytes < trtx_yolo_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
     const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, n_kpt, kpt_conf};
@@ -686,11 +697,13 @@ static int32_t launch_head(const LevelTable& t, const HeadTable& h, const Branch
 static int32_t head_decode(const void* const* heads, const int* ld, int elem_bytes, int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
                            const float* dfl_weights, int max_out, float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 8 || classes % 8 || max_out < 1 || !heads ||
-        !ld || !dfl_weights || !output || !workspace)
+        !ld || !dfl_weights || !output || !workspace || count_cells(net_h, net_w, strides, n_levels) == 0)
         return TRTX_ERR_INVALID;
     if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
     for (int i = 0; i < n_levels; ++i)
-        if (ld[i] % (16 / elem_bytes) || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
+        // the 16-byte loads read channels [0, 64 + classes) of every pixel: a shorter stride would read the next pixel's (and, at the
+        // tensor's last pixel, past it)
+        if (ld[i] % (16 / elem_bytes) || ld[i] < 64 + classes || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
     const LevelTable t = make_levels(n_levels, net_h, net_w, strides);
     return launch_head(t, make_head(t, heads, ld), nullptr, elem_bytes, batch, classes, dfl_weights, max_out, YoloBranches{0, 0, 0, 0, 0.f},
                        output, workspace, stream, "trtx_yolo_head_decode_nhwc");
@@ -718,7 +731,8 @@ static int32_t task_head_decode(const void* const* heads, const int* ld, const v
                                 int max_out, int is_seg, int is_pose, int is_obb, int n_kpt, float kpt_conf, float* output, void* workspace,
                                 size_t workspace_bytes, hipStream_t stream) {
     if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !heads || !ld || !branches || !branch_ld ||
-        !dfl_weights || !output || !workspace || (is_seg != 0) + (is_pose != 0) + (is_obb != 0) != 1 || (is_pose && (n_kpt < 1 || n_kpt > 17)))
+        !dfl_weights || !output || !workspace || (is_seg != 0) + (is_pose != 0) + (is_obb != 0) != 1 || (is_pose && (n_kpt < 1 || n_kpt > 17)) ||
+        count_cells(net_h, net_w, strides, n_levels) == 0)
         return TRTX_ERR_INVALID;
     if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
     const int extra = is_seg ? 32 : (is_pose ? 3 * n_kpt : 1);

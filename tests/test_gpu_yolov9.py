@@ -212,6 +212,60 @@ def test_head_nan_logits_and_extreme_dfl_bins(gpu):
         assert any(r[5] == 33 and abs(r[4] - 1 / (1 + np.exp(-1.0))) < 1e-6 for r in rows(got, 0))
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32], ids=["f16", "f32"])
+def test_head_gate_and_the_pre_filter_in_front_of_it(gpu, dtype):
+    """The score kernel flags a cell when its largest raw logit is above -2.3 and settles it with the exact sigmoid against 0.1 (logit
+    -2.19722).  One cell per value of tests/yolo_head_cases.py's family (c) - below the pre-filter, between it and the gate (flagged, then
+    dropped) and just above the gate (kept) - at the first and the last lane of a wave, the last cell of a level and the first of the next,
+    on 160 x 160 (525 cells, three workgroups); all other classes of those cells at -30.  Against the oracle: count, order and class
+    equal, conf within 2e-7, no record left out; boxes under the bound derived in tests/yolo_head_cases.py."""
+    from tests import yolo_head_cases as hc
+    dt = "f16" if dtype == torch.float16 else "f32"
+    B, H, W, nc = 3, 160, 160, 80
+    pl = [(b.copy(), c.copy()) for b, c in planes(B, H, W, nc, dtype, seed=9)]
+    off, pos, th = hc.level_offsets("160x160"), hc.positions("160x160"), hc.thresholds(dt)
+    placed = {}
+    for k, kind in enumerate(hc.KINDS):   # every value at every kind of position, as far as three images have such cells (two boundaries each)
+        for j in (range(len(th)) if k % 2 == 0 else reversed(range(len(th)))):
+            free = [(b, g) for t in range(B) for b in [(j + k + t) % B] for g in pos[kind] if (b, g) not in placed]
+            if free:
+                placed[free[0]] = j
+    for (b, g), j in placed.items():
+        l = int(np.searchsorted(off, g, side="right")) - 1
+        pl[l][1][b, :, g - off[l]] = -30.0
+        pl[l][1][b, (7 * j + 3) % nc, g - off[l]] = th[j][0]
+    at = {(j, k) for (b, g), j in placed.items() for k in hc.KINDS if g in pos[k]}
+    assert at >= {(j, k) for j in range(len(th)) for k in hc.KINDS[:2]}
+    assert all((j, "level_last") in at or (j, "level_first") in at for j in range(len(th)))
+    logits = np.concatenate([c for _, c in pl], 2).astype(np.float64)                    # [B, classes, cells]
+    p = 1 / (1 + np.exp(-logits.max(1)))
+    kept = [np.nonzero(p[b] >= 0.1)[0] for b in range(B)]
+    others = np.ones_like(p, bool)
+    for b, g in placed:
+        others[b, g] = False
+    assert (np.abs(1 / (1 + np.exp(-logits)) - 0.1).min(1)[others] > 1e-6).all()        # nothing else sits at the gate
+    for (b, g), j in placed.items():
+        assert (g in kept[b]) == th[j][2]
+    mo = 526
+    ref = yp.decode_c(chw_of(pl), nc, H, W, list(STRIDES), mo)
+    assert np.array_equal(ref[:, 0], [len(k) for k in kept])
+    got = fused(pl, nc, H, W, mo, dtype, gpu)
+    compare(got, ref, "the gate")
+    # boxes: the derived bound instead of compare()'s rtol 1e-5 / atol 1e-4
+    bins = np.concatenate([b for b, _ in pl], 2).transpose(0, 2, 1).reshape(B, 525, 4, 16)
+    w = np.arange(16, dtype=np.float32)
+    d, S, A = hc.dfl_terms(bins, w)
+    bd = hc.bound_of(d, S, A, w)
+    stride = hc.cell_geometry("160x160")[2]
+    worst = 0.0
+    for b in range(B):
+        G, R = rows(got, b), rows(ref, b, yp.DET_FLOATS)
+        bound = hc.coord_bound(bd[b][kept[b]], d[b][kept[b]], stride[kept[b]][:, None], R[:, :4].astype(np.float64))
+        worst = max(worst, float((np.abs(G[:, :4].astype(np.float64) - R[:, :4]) / bound).max()))
+    print(f"yolov9 head at the gate, {dt}: records {ref[:, 0].astype(int).tolist()} of 525, max err / bound {worst:.3f}")
+    assert worst <= 1.0, worst
+
+
 def test_head_is_batch_invariant(gpu):
     """image 0 of a batch decodes bit-equal when run alone"""
     pl = planes(3, 640, 640, 80, torch.float16)
