@@ -445,6 +445,14 @@ int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld
                                   trtx_stream_t stream);
 int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd, int hd,
                                    float scale, trtx_stream_t stream);
+/* The area attention on separate operands (tests / tools; kernels/attention_mfma.hip), as YOLOv13's AAttn has them (yolov13/src/block.cpp:303-423: q | k
+ * come from one 1x1 convolution, v from another).  q, k, v: NHWC fp16 [B][N][ld_q / ld_k / ld_v]; head h reads q channels h * kd .., k channels h * kd ..
+ * and v channels h * hd ..; out[b][n][h * hd + d] as trtx_op_area_attention_f16 and, given the same values, bit-equal to it.  No V image is written.
+ * For YOLOv13 k = q + heads * kd halves and ld_k = ld_q; the entry point does not assume that.  Each operand takes 16-byte loads (O: 8-byte stores) where its
+ * base pointer and stride allow them and element-wise accesses otherwise.  TRTX_ERR_UNSUPPORTED, nothing launched: kd != 32 or hd != 32, a count < 1,
+ * N % area != 0, B > 65535, heads * area > 65535, ld_q or ld_k < heads * kd, ld_v or ld_out < heads * hd. */
+int32_t trtx_op_area_attention_split_f16(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, void* out, int ld_out, int B, int heads,
+                                         int N, int area, int kd, int hd, float scale, trtx_stream_t stream);
 /* YOLOv13's adaptive hypergraph convolution (tests / tools; kernels/hgconv.hip): AdaHyperedgeGen (yolov13/src/block.cpp:607-700) and AdaHGConv
  * (block.cpp:746-790) with the eleven-layer tanh GELU (block.cpp:702-744), per image on x: NHWC fp16 [B][N][ld_x], D channels = the token image of
  * AdaHGComputation (block.cpp:792-812), E hyperedges:

@@ -636,6 +636,20 @@ def area_attention(qkv, heads, area, scale, out=None, vimg=None, out_ld=None, v_
     return _attention(lib().trtx_op_area_attention_f16, "trtx_op_area_attention_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, (area,))
 
 
+def area_attention_split(q, k, v, heads, area, scale, out=None, q_ld=None, k_ld=None, v_ld=None, out_ld=None, kd=32, hd=32):
+    """The area attention on separate operands (kernels/attention_mfma.hip; YOLOv13's AAttn): q, k: CUDA fp16 [B, N, heads * kd], v: [B, N, heads * hd],
+    each a tensor of its own or a channel slice of a wider one (pixel stride t.stride(1), or the *_ld given); out likewise (allocated when None).  -> O"""
+    import torch
+    B, N, _ = q.shape
+    out = torch.empty((B, N, heads * hd), dtype=torch.float16, device=q.device) if out is None else out
+    for t in (q, k, v, out):
+        assert t.is_cuda and t.dtype == torch.float16
+    check(lib().trtx_op_area_attention_split_f16(_p(q), q_ld or q.stride(1), _p(k), k_ld or k.stride(1), _p(v), v_ld or v.stride(1), _p(out),
+                                                 out_ld or out.stride(1), B, heads, N, area, kd, hd, ctypes.c_float(scale), _stream()),
+          "trtx_op_area_attention_split_f16")
+    return out
+
+
 HGCONV_WEIGHTS = ("w_ctx", "b_ctx", "proto", "w_pre", "b_pre", "w_edge", "b_edge", "w_node", "b_node")   # trtx_op_hgconv_f16's nine fp32 arrays, in its order
 
 

@@ -20,6 +20,10 @@
 // Keys beyond the area are never read: their LDS rows are zero-filled and their scores set to -inf (a 32-key group with no key in range
 // is skipped, so every processed group has a finite max).  Queries beyond the area read nothing and store nothing.
 // HD is a template parameter (HD / 16 accumulator tiles); 32 is the instantiation AAttn needs.
+//
+// YOLOv13's AAttn (yolov13/src/block.cpp:303-423) takes q | k from one 1x1 convolution and v from another.  SPLIT is that form of the same body: three
+// operands with their own base, pixel stride and vector flag, head h's q and k at channel h * KD and its v at h * HD, and no V image (v is a tensor that
+// `pe` reads as it is).  Only the addresses differ, so on equal values O is bit-equal between the two instantiations.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -61,10 +65,13 @@ __device__ inline void store8(_Float16* p, h8 v, bool vec) {
     for (int i = 0; i < 8; ++i) p[i] = v[i];
 }
 
-template <int HD>
-__global__ __launch_bounds__(THREADS) void area_attention_mfma_kernel(const _Float16* __restrict__ qkv, int ld_qkv, _Float16* __restrict__ out,
-                                                                         int ld_out, _Float16* __restrict__ vimg, int ld_v, int N, int Na, int heads,
-                                                                         float scale, int vec_in, int vec_o, int vec_v) {
+// Where a head's q, k and v rows are.  Packed: one qkv tensor, head h's channels at h * (2 KD + HD) as q, k, v, and the V image is written.
+// Split: three operands, each with its own base, pixel stride and vector flag; head h's q and k at h * KD, its v at h * HD; no V image.
+template <int HD, bool SPLIT>
+__global__ __launch_bounds__(THREADS) void area_attention_mfma_kernel(const _Float16* __restrict__ q, int ld_q, const _Float16* __restrict__ k, int ld_k,
+                                                                         const _Float16* __restrict__ v, int ld_vin, _Float16* __restrict__ out, int ld_out,
+                                                                         _Float16* __restrict__ vimg, int ld_v, int N, int Na, int heads, float scale,
+                                                                         int vec_q, int vec_k, int vec_vin, int vec_o, int vec_v) {
     constexpr int T = THREADS;
     constexpr int VG = HD / 8;       // 8-channel groups of a V row
     constexpr int VL = KC * VG / T;  // V groups a thread stages per chunk
@@ -76,27 +83,39 @@ __global__ __launch_bounds__(THREADS) void area_attention_mfma_kernel(const _Flo
     const int i16 = lane & 15, g = lane >> 4;
     const int a = blockIdx.y / heads, h = blockIdx.y - a * heads, b = blockIdx.z;
     const long pix0 = (long)b * N + (long)a * Na;   // first pixel of the area
-    const int cq = h * (2 * KD + HD), ck = cq + KD, cv = cq + 2 * KD;
+    const _Float16 *qh, *kh, *vh;   // the head's first q, k and v channel of pixel 0
+    if constexpr (SPLIT) {
+        qh = q + h * KD;
+        kh = k + h * KD;
+        vh = v + h * HD;
+    } else {
+        qh = q + h * (2 * KD + HD);
+        kh = qh + KD;
+        vh = qh + 2 * KD;
+        ld_k = ld_vin = ld_q;
+        vec_k = vec_vin = vec_q;
+    }
     const int q0 = blockIdx.x * QB;
     const h8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
-    // the V image of this workgroup's own 64 query pixels
-    for (int i = t; i < QB * VG; i += T) {
-        const int n = q0 + i / VG, dg = i % VG;
-        if (n < Na) store8(vimg + (pix0 + n) * ld_v + h * HD + 8 * dg, load8(qkv + (pix0 + n) * ld_qkv + cv + 8 * dg, vec_in), vec_v);
+    if constexpr (!SPLIT) {   // the V image of this workgroup's own 64 query pixels
+        for (int i = t; i < QB * VG; i += T) {
+            const int n = q0 + i / VG, dg = i % VG;
+            if (n < Na) store8(vimg + (pix0 + n) * ld_v + h * HD + 8 * dg, load8(vh + (pix0 + n) * ld_vin + 8 * dg, vec_vin), vec_v);
+        }
     }
     // Q^T fragment: query i16 of the wave, channels 8 g .. 8 g + 7
     const int qn = q0 + wave * QW + i16;
-    const h8 qf = qn < Na ? load8(qkv + (pix0 + qn) * ld_qkv + cq + 8 * g, vec_in) : zero8;
+    const h8 qf = qn < Na ? load8(qh + (pix0 + qn) * ld_q + 8 * g, vec_q) : zero8;
 
     h8 kreg, vreg[VL];
     auto fetch = [&](int c0) {   // global -> registers; rows beyond the area become zeros without a read
         const int key = c0 + (t >> 2);
-        kreg = key < Na ? load8(qkv + (pix0 + key) * ld_qkv + ck + 8 * (t & 3), vec_in) : zero8;
+        kreg = key < Na ? load8(kh + (pix0 + key) * ld_k + 8 * (t & 3), vec_k) : zero8;
 #pragma unroll
         for (int u = 0; u < VL; ++u) {
             const int idx = t + u * T, kv = c0 + idx / VG;
-            vreg[u] = kv < Na ? load8(qkv + (pix0 + kv) * ld_qkv + cv + 8 * (idx % VG), vec_in) : zero8;
+            vreg[u] = kv < Na ? load8(vh + (pix0 + kv) * ld_vin + 8 * (idx % VG), vec_vin) : zero8;
         }
     };
     auto stage = [&]() {         // registers -> LDS: K rows as they are, V transposed
@@ -194,10 +213,28 @@ int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, v
         return TRTX_ERR_UNSUPPORTED;
     const int Na = N / area;
     // 16-byte loads of qkv and stores of the V image, 8-byte stores of O where base and channel stride allow; element-wise otherwise
-    hipLaunchKernelGGL(area_attention_mfma_kernel<32>, dim3((Na + QB - 1) / QB, heads * area, B), dim3(THREADS), 0, s,
-                       static_cast<const _Float16*>(qkv), ld_qkv, static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, Na, heads,
-                       scale, (int)aligned(qkv, ld_qkv, 16), (int)aligned(out, ld_out, 8), (int)aligned(vimg, ld_v, 16));
+    const _Float16* in = static_cast<const _Float16*>(qkv);
+    const int vec_in = aligned(qkv, ld_qkv, 16);
+    hipLaunchKernelGGL((area_attention_mfma_kernel<32, false>), dim3((Na + QB - 1) / QB, heads * area, B), dim3(THREADS), 0, s, in, ld_qkv, in, ld_qkv, in,
+                       ld_qkv, static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, Na, heads, scale, vec_in, vec_in, vec_in,
+                       (int)aligned(out, ld_out, 8), (int)aligned(vimg, ld_v, 16));
     return check_launch("area_attention");
+}
+
+bool area_attention_split_supported(int kd, int hd) { return area_attention_supported(kd, hd); }
+
+int32_t area_attention_split_f16(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, void* out, int ld_out, int B, int heads, int N,
+                                 int area, int kd, int hd, float scale, hipStream_t s) {
+    if (!area_attention_split_supported(kd, hd) || B < 1 || heads < 1 || N < 1 || area < 1 || N % area != 0 || B > 65535 || (long)heads * area > 65535 ||
+        ld_q < heads * kd || ld_k < heads * kd || ld_v < heads * hd || ld_out < heads * hd)
+        return TRTX_ERR_UNSUPPORTED;
+    const int Na = N / area;
+    // per operand: 16-byte loads of q, k and v, 8-byte stores of O where its base and channel stride allow; element-wise otherwise
+    hipLaunchKernelGGL((area_attention_mfma_kernel<32, true>), dim3((Na + QB - 1) / QB, heads * area, B), dim3(THREADS), 0, s, static_cast<const _Float16*>(q),
+                       ld_q, static_cast<const _Float16*>(k), ld_k, static_cast<const _Float16*>(v), ld_v, static_cast<_Float16*>(out), ld_out,
+                       static_cast<_Float16*>(nullptr), 0, N, Na, heads, scale, (int)aligned(q, ld_q, 16), (int)aligned(k, ld_k, 16), (int)aligned(v, ld_v, 16),
+                       (int)aligned(out, ld_out, 8), 0);
+    return check_launch("area_attention_split");
 }
 
 }  // namespace trtx

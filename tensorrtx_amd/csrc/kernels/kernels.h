@@ -184,6 +184,12 @@ int32_t psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, vo
 bool area_attention_supported(int kd, int hd);
 int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd,
                            int hd, float scale, hipStream_t s);
+// the same kernel body on separate operands (YOLOv13's AAttn, yolov13/src/block.cpp:303-423: q | k from one convolution, v from another): q, k, v
+// are NHWC fp16 [B][N][ld], head h reads q and k channels h*kd .. and v channels h*hd ..; O as above, no V image (v is a tensor already).  Given the
+// same values O is bit-equal to area_attention_f16's.  16-byte loads / 8-byte stores per operand where its base and stride allow, element-wise otherwise.
+bool area_attention_split_supported(int kd, int hd);
+int32_t area_attention_split_f16(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, void* out, int ld_out, int B, int heads, int N,
+                                 int area, int kd, int hd, float scale, hipStream_t s);
 int32_t conv_dw(const ConvArgs& a, int dtype, hipStream_t s);
 // YOLOv13's adaptive hypergraph convolution (hgconv.hip; AdaHyperedgeGen + AdaHGConv, yolov13/src/block.cpp:607-790): NHWC fp16 x [B][N][ld_x] (D channels)
 // -> out [B][N][ld_out] = GELU((A He') W_node^T + b_node) + x with A the softmax over the N nodes of an image.  D % 16 == 0, D <= 384, 1 <= E <= 16; x and out

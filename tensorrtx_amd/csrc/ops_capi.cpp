@@ -230,6 +230,12 @@ extern "C" int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void*
     return area_attention_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, area, kd, hd, scale, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int32_t trtx_op_area_attention_split_f16(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, void* out, int ld_out, int B,
+                                                    int heads, int N, int area, int kd, int hd, float scale, trtx_stream_t stream) {
+    if (!q || !k || !v || !out) return TRTX_ERR_INVALID;
+    return area_attention_split_f16(q, ld_q, k, ld_k, v, ld_v, out, ld_out, B, heads, N, area, kd, hd, scale, static_cast<hipStream_t>(stream));
+}
+
 // --- YOLOv13's hypergraph convolution (kernels/hgconv.hip), test / tool entry points
 extern "C" size_t trtx_op_hgconv_workspace_bytes(int B, int N, int D, int E) { return hgconv_workspace_bytes(B, N, D, E); }
 

@@ -38,6 +38,7 @@ Options read_options() {
     o.f32_mfma = !env_set("TRTX_F32_DIRECT");
     o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
+    o.aattn_split = !env_is("TRTX_AATTN_SPLIT", 0);
     o.hgconv = !env_is("TRTX_HGCONV", 0);
     o.gated_add = !env_is("TRTX_GATED_ADD", 0);
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);

@@ -33,7 +33,8 @@ struct Options {
     bool f32_mfma = true;        // TRTX_F32_DIRECT=1: fp32 engines on the scalar direct kernel of rounds 1-4 (no fp32 MFMA, no fp32 stem kernel)
     bool conv_grouped = true;    // TRTX_CONV_GROUPED=0: grouped (not depthwise) convolutions stay on the scalar direct kernel (no kernels/conv_grouped.hip)
     bool area_attention = true;  // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
-    bool hgconv = true;          // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
+    bool aattn_split = true;     // TRTX_AATTN_SPLIT=0: YOLOv13 area attention (q | k and v from two convolutions) stays on the generic linear path (shuffles, slices, matmul, softmax)
+    bool hgconv = true;         // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
     bool gated_add = true;       // TRTX_GATED_ADD=0: a + gate * b with a constant gate (YOLOv13's FullPad_Tunnel, A2C2f's gamma residual) stays a product and a sum
     bool yolo9_head = true;      // TRTX_YOLO9_HEAD=0: the YOLOv9 / GELAN detect tail keeps the plugin route (layout passes, the DFL chain, concat scatters + YoloLayer_TRT)
     bool yolo5_head = true;      // TRTX_YOLO5_HEAD=0: the anchor-based (YOLOv5) detect tail keeps the plugin route (layout passes to fp32 planes + YoloLayer_TRT)

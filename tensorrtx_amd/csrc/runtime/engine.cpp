@@ -458,6 +458,13 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                                            op.i[3], op.f[0], stream);
                 break;
             }
+            case OP_ATTENTION_SPLIT: {   // q and k are two channel ranges of in[0]
+                const PTensor& tv = plan.tensors[op.in[1]];
+                const char* qk = static_cast<const char*>(R.ptr(op.in[0]));
+                st = area_attention_split_f16(qk, t0.ld, qk + (size_t)op.i[5] * dtype_size(t0.dtype), t0.ld, R.ptr(op.in[1]), tv.ld, R.ptr(op.out[0]), to.ld,
+                                              nb(t0), op.i[0], op.i[1], op.i[4], op.i[2], op.i[3], op.f[0], stream);
+                break;
+            }
             case OP_HGCONV: {
                 // the nine fp32 arrays in HgconvWeights' order, as pack_weights laid them out
                 const size_t D = (size_t)op.i[1], ED = (size_t)op.i[2] * D;

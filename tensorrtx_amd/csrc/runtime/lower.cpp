@@ -177,6 +177,23 @@ struct Lowerer {
         return true;
     }
 
+    // YOLOv13's area attention at its last shuffle: the qk and v convolutions' NHWC images in, O out as one NHWC image of its own (a residual epilogue or a
+    // concat behind it takes it like any other); v is read where it is, no V image is written.
+    bool emit_attention_split(const AttentionSplitFuse& f) {
+        const int qk = need_nhwc(f.qk), v = need_nhwc(f.v);
+        const int o = new_tensor(f.out, net.tensors[f.out].dims, LAY_NHWC, true);
+        POp& op = add_op(OP_ATTENTION_SPLIT, "attention_split:" + net.tensors[f.qk].name, {qk, v}, {o});
+        op.i[0] = f.heads; op.i[1] = f.N; op.i[2] = f.hd; op.i[3] = f.hd;   // kd == hd: q, k and v are hd channels per head
+        op.i[4] = f.area;
+        op.i[5] = f.heads * f.hd;   // k's first channel within the qk tensor
+        op.f[0] = f.scale;
+        const double B = plan.tensors[qk].nfix;
+        op.flops = 2.0 * B * f.heads * (double)f.N * (f.N / f.area) * (2 * f.hd);   // as emit_attention
+        op.bytes = 2.0 * B * f.N * 4.0 * f.heads * f.hd;                             // q, k, v read, O written
+        pt_of[f.out] = o;
+        return true;
+    }
+
     // The hypergraph convolution at its x_out shuffle: the NHWC image AdaHGComputation read in, the NHWC image it produced out (a concat behind it
     // takes the op's output as a channel slice like any other NHWC tensor); the weights stay in their layers until pack_weights.
     bool emit_hgconv(const HgconvFuse& f) {
@@ -940,6 +957,10 @@ struct Lowerer {
             }
             if (fu.attn_at[li] >= 0) {
                 if (!emit_attention(fu.attns[fu.attn_at[li]])) return false;
+                continue;
+            }
+            if (fu.attn_split_at[li] >= 0) {
+                if (!emit_attention_split(fu.attn_splits[fu.attn_split_at[li]])) return false;
                 continue;
             }
             if (fu.hgconv_at[li] >= 0) {

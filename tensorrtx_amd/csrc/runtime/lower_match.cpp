@@ -633,6 +633,166 @@ void match_area_attention(const NetView& g, Fusions& f) {
     }
 }
 
+// ---- YOLOv13 area attention (yolov13/src/block.cpp:303-423), walked from the first matmul.  q | k come from one convolution and v from another:
+//   qk (B, 2C, H, W) -> flatten {reshape (B, -1, N), second transpose {0,2,1}} -> [reshape (B', N', 2C)] -> slices [0, C) = q and [C, 2C) = k of the last axis,
+//   each -> reshape (B', N', heads, hd) -> transpose {0,2,3,1}, q once more {0,1,3,2};  v (B, C, H, W) -> the same flatten -> [reshape (B', N', C)] ->
+//   reshape (B', N', heads, hd) -> transpose {0,2,3,1};  matmul(q^T, k) -> uniform scale (shift 0, power 1) -> softmax over axis 3, as the five-layer chain
+//   (match_exp_softmax) or one ISoftMaxLayer -> transpose {0,1,3,2} -> matmul(v, p^T) -> transpose {0,3,1,2} -> [reshape (B, N, C)] -> {reshape (B, H, W, C),
+//   second transpose {0,3,1,2}}, whose output is the op's.  B' = B area, N' = N / area; the bracketed reshapes are absent where the reference has area == 1.
+// Checked: every shape, permutation and slice, heads * hd == C, area_attention_split_supported, and that no tensor between the two images and the result has
+// a reader outside the match or is a network output.  The qk and v images may have any other readers (v's is `pe`): the op reads them where they are.
+// The scale layer becomes the op's scale.  fp16 explicit-batch engines only, not kINT8, and not with TRTX_AATTN_SPLIT=0; anything else keeps the generic ops.
+bool match_aattn_split_at(const NetView& g, int li, AttentionSplitFuse* a, std::vector<int>* used) {
+    const Network& net = g.net;
+    auto dims = [&](int t) -> const Dims& { return net.tensors[t].dims; };
+    auto is = [](const Dims& d, std::initializer_list<int64_t> want) {
+        if (d.nb != (int)want.size()) return false;
+        int k = 0;
+        for (int64_t v : want)
+            if (d.d[k++] != v) return false;
+        return true;
+    };
+    auto reshape_only = [&](int l, int nb_out) {   // a shuffle that only reshapes, to nb_out dims
+        if (l < 0 || net.layers[l].kind != L_SHUFFLE) return false;
+        const LayerDef& s = net.layers[l];
+        return s.reshape.nb == nb_out && ident(s.perm1, dims(s.inputs[0]).nb) && ident(s.perm2, nb_out);
+    };
+    auto keep = [&](int l) { used->push_back(l); return net.layers[l].inputs[0]; };   // claims layer l, returns what it reads
+    const LayerDef& m1 = net.layers[li];
+    if (!plain_matmul(m1)) return false;
+    used->push_back(li);
+    // (B', N', X) <- [reshape] <- flatten <- image (B, X, H, W): the image, or -1
+    int64_t B = 0, Ba = 0, Na = 0, H = 0, W = 0;
+    auto image_of = [&](int t3, int64_t X) -> int {
+        int l = g.producer(t3);
+        if (reshape_only(l, 3) && dims(net.layers[l].inputs[0]).nb == 3) t3 = keep(l), l = g.producer(t3);
+        if (l < 0 || net.layers[l].kind != L_SHUFFLE) return -1;
+        const LayerDef& fl = net.layers[l];
+        const Dims& di = dims(fl.inputs[0]);
+        if (fl.reshape.nb != 3 || di.nb != 4 || !ident(fl.perm1, 4) || !perm_is(fl.perm2, {0, 2, 1}) || di.d[1] != X) return -1;
+        if (B == 0) B = di.d[0], H = di.d[2], W = di.d[3];
+        if (di.d[0] != B || di.d[2] != H || di.d[3] != W || !is(dims(t3), {B, H * W, X})) return -1;
+        return keep(l);
+    };
+    // (B', heads, hd, N') <- transpose {0,2,3,1} <- reshape (B', N', heads, hd) <- t3 (B', N', C): t3, or -1
+    int64_t heads = 0, hd = 0;
+    auto heads_of = [&](int t4) -> int {
+        const int lt = g.producer(t4);
+        if (lt < 0 || !transpose_only(net.layers[lt], {0, 2, 3, 1})) return -1;
+        const int tr = keep(lt), lr = g.producer(tr);
+        if (!reshape_only(lr, 4)) return -1;
+        const Dims& d = dims(tr);
+        if (heads == 0) Ba = d.d[0], Na = d.d[1], heads = d.d[2], hd = d.d[3];
+        const int t3 = keep(lr);
+        if (!is(d, {Ba, Na, heads, hd}) || !is(dims(t3), {Ba, Na, heads * hd})) return -1;
+        return t3;
+    };
+    // q and k: two slices of the last axis of one (B', N', 2C) tensor
+    const int lqt = g.producer(m1.inputs[0]);
+    if (lqt < 0 || !transpose_only(net.layers[lqt], {0, 1, 3, 2})) return false;
+    const int tq3 = heads_of(keep(lqt)), tk3 = heads_of(m1.inputs[1]);
+    if (tq3 < 0 || tk3 < 0) return false;
+    const int lq = g.producer(tq3), lk = g.producer(tk3);
+    if (lq < 0 || lk < 0 || net.layers[lq].kind != L_SLICE || net.layers[lk].kind != L_SLICE) return false;
+    const int64_t C = heads * hd;
+    const int tqk3 = keep(lq);
+    if (keep(lk) != tqk3 || !is(dims(tqk3), {Ba, Na, 2 * C})) return false;
+    auto slice_last = [&](const LayerDef& sl, int64_t c0) {
+        return is(sl.start, {0, 0, c0}) && is(sl.size, {Ba, Na, C}) && is(sl.step, {1, 1, 1});
+    };
+    if (!slice_last(net.layers[lq], 0) || !slice_last(net.layers[lk], C)) return false;
+    a->qk = image_of(tqk3, 2 * C);
+    if (a->qk < 0) return false;
+    const int64_t N = H * W;
+    if (B < 1 || Na < 1 || Ba % B != 0 || Ba / B * Na != N) return false;
+    // scores -> uniform scale -> softmax over the keys
+    int lsc, lsm;
+    if (!g.sole_consumer(m1.outputs[0], &lsc) || net.layers[lsc].kind != L_SCALE || net.layers[lsc].op != TRTX_SCALE_UNIFORM) return false;
+    const LayerDef& sc = net.layers[lsc];
+    if (sc.w1.size() != 1 || (!sc.w0.empty() && (sc.w0.size() != 1 || sc.w0[0] != 0.f)) || (!sc.w2.empty() && (sc.w2.size() != 1 || sc.w2[0] != 1.f)))
+        return false;
+    used->push_back(lsc);
+    int tp = -1;
+    if (g.sole_consumer(sc.outputs[0], &lsm) && net.layers[lsm].kind == L_SOFTMAX) {
+        if (net.layers[lsm].axis != (1 << 3)) return false;
+        used->push_back(lsm);
+        tp = net.layers[lsm].outputs[0];
+    } else {   // the spelled-out chain: found from the scores' subtraction
+        SoftmaxChainFuse c;
+        for (int r : g.consumers[sc.outputs[0]]) {
+            int lexp;
+            if (net.layers[r].kind != L_ELEMENTWISE || net.layers[r].op != TRTX_ELEMENTWISE_SUB || !g.sole_consumer(net.layers[r].outputs[0], &lexp)) continue;
+            for (int d : g.consumers[net.layers[lexp].outputs[0]]) {
+                SoftmaxChainFuse at_d;
+                if (match_exp_softmax(g, d, &at_d) && at_d.in == sc.outputs[0] && at_d.axis == 3) c = at_d;
+            }
+        }
+        if (c.out < 0) return false;
+        tp = c.out;
+        used->insert(used->end(), c.layers.begin(), c.layers.end());
+    }
+    // p^T and the value product
+    int lat, m2;
+    if (!g.sole_consumer(tp, &lat) || !transpose_only(net.layers[lat], {0, 1, 3, 2}) || !g.sole_consumer(net.layers[lat].outputs[0], &m2)) return false;
+    const LayerDef& mm2 = net.layers[m2];
+    if (!plain_matmul(mm2) || mm2.inputs[1] != net.layers[lat].outputs[0]) return false;
+    used->push_back(lat);
+    used->push_back(m2);
+    const int tv3 = heads_of(mm2.inputs[0]);
+    if (tv3 < 0) return false;
+    a->v = image_of(tv3, C);
+    if (a->v < 0) return false;
+    // the way out
+    int lo, lx;
+    if (!g.sole_consumer(mm2.outputs[0], &lo) || !transpose_only(net.layers[lo], {0, 3, 1, 2}) || !g.sole_consumer(net.layers[lo].outputs[0], &lx)) return false;
+    used->push_back(lo);
+    if (reshape_only(lx, 3)) {
+        if (!is(dims(net.layers[lx].outputs[0]), {B, N, C})) return false;
+        used->push_back(lx);
+        if (!g.sole_consumer(net.layers[lx].outputs[0], &lx)) return false;
+    }
+    const LayerDef& x = net.layers[lx];
+    if (x.kind != L_SHUFFLE || x.reshape.nb != 4 || !ident(x.perm1, dims(x.inputs[0]).nb) || !perm_is(x.perm2, {0, 3, 1, 2}) ||
+        !is(x.reshape, {B, H, W, C}) || !is(dims(x.outputs[0]), {B, C, H, W}))
+        return false;
+    used->push_back(lx);
+    // no claimed layer twice, the result's shuffle is the last of them, and nothing inside is read from outside or is a network output
+    std::vector<int> sorted(*used);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end() || sorted.back() != lx) return false;
+    for (int u : sorted) {
+        if (u == lx) continue;
+        const int t = net.layers[u].outputs[0];
+        if (net.tensors[t].is_output) return false;
+        for (int r : g.consumers[t])
+            if (!std::binary_search(sorted.begin(), sorted.end(), r)) return false;
+    }
+    if (!area_attention_split_supported((int)hd, (int)hd)) return false;
+    a->out = x.outputs[0];
+    a->heads = (int)heads;
+    a->N = (int)N;
+    a->hd = (int)hd;
+    a->area = (int)(Ba / B);
+    a->scale = sc.w1[0];
+    return true;
+}
+
+void match_aattn_split(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (!net.explicit_batch || g.dt != DT_F16 || net.int8 || !g.opt.aattn_split) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        AttentionSplitFuse a;
+        std::vector<int> used;
+        if (f.absorbed[li] || !match_aattn_split_at(g, (int)li, &a, &used)) continue;
+        bool free = true;
+        for (int u : used) free = free && !f.absorbed[u];
+        if (!free) continue;
+        for (int u : used) f.absorbed[u] = true;
+        f.attn_split_at[used.back()] = (int)f.attn_splits.size();
+        f.attn_splits.push_back(a);
+    }
+}
+
 // ---- YOLOv13's adaptive hypergraph convolution: AdaHGComputation (yolov13/src/block.cpp:792-812) from its `tokens` shuffle
 // ((B, D, H, W) -> (B, N, D)) to its `x_out` shuffle, i.e. AdaHyperedgeGen (607-700), AdaHGConv (746-790) and both GELU chains, walked
 // backwards from x_out.  Checked: every reshape and permutation, both reduces of the context and their axis, the concat axis, the three
@@ -1007,14 +1167,14 @@ bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
 // and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
-// attention, the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
     f.pad_cout.assign(nl, false);
     f.reorg_src.assign(nl, -1);
-    f.group_at = f.yolo_at = f.attn_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = f.softmax_at = f.gated_at = std::vector<int>(nl, -1);
+    f.group_at = f.yolo_at = f.attn_at = f.attn_split_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = f.softmax_at = f.gated_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
     match_yolo9_heads(g, f);
@@ -1022,6 +1182,7 @@ Fusions match_fusions(const NetView& g) {
     match_yolo7_heads(g, f);
     match_psa_attention(g, f);
     match_area_attention(g, f);
+    match_aattn_split(g, f);
     match_hgconv(g, f);
     match_gelu_chains(g, f);
     match_softmax_chains(g, f);

@@ -56,6 +56,12 @@ struct AttentionFuse {
     int area = 0;                    // 0: YOLO11 PSA (psa_attention_kernel); >= 1: YOLOv12 area attention (area_attention_mfma_kernel), N / area keys per query
 };
 
+struct AttentionSplitFuse {
+    int qk = -1, v = -1, out = -1;   // network tensors: the qk convolution's output (B, 2 heads*hd, H, W), the v convolution's (B, heads*hd, H, W), O as an image
+    int heads = 0, N = 0, hd = 0, area = 1;
+    float scale = 0.f;
+};
+
 struct HgconvFuse {
     int x = -1, out = -1;            // network tensors: the image AdaHGComputation reads (B, D, H, W) and the one its x_out shuffle produces
     int N = 0, D = 0, E = 0;
@@ -101,7 +107,8 @@ struct Fusions {
     std::vector<AttentionFuse> attns;
     std::vector<Yolo5HeadFuse> yolo5_heads;
     std::vector<Yolo9HeadFuse> yolo9_heads;
-    std::vector<int> group_at, yolo_at, attn_at, yolo5_at, yolo9_at;
+    std::vector<AttentionSplitFuse> attn_splits;
+    std::vector<int> group_at, yolo_at, attn_at, attn_split_at, yolo5_at, yolo9_at;
     std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor or DDetect head: its output channels round up to 16 bytes
     std::vector<int> reorg_src;                // per layer: >= 0 for a convolution that absorbed the ReOrg in front of it - the network tensor the four slices read
     std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own

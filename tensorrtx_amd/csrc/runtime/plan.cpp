@@ -10,8 +10,8 @@ const char* op_kind_name(int k) {
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
-                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add"};
-    return (k >= 0 && k <= OP_GATED_ADD) ? n[k] : "?";
+                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add", "attention_split"};
+    return (k >= 0 && k <= OP_ATTENTION_SPLIT) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -55,6 +55,8 @@ std::string Plan::describe_json() const {
         if (op.kind == OP_ACT_NHWC || op.kind == OP_ACT_LIN) o << ",\"act\":" << op.i[0];
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
         if (op.kind == OP_ATTENTION && op.i[4] > 0) o << ",\"area\":" << op.i[4] << ",\"kernel\":\"mfma\"";
+        if (op.kind == OP_ATTENTION_SPLIT)
+            o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3] << ",\"area\":" << op.i[4] << ",\"k_offset\":" << op.i[5];
         if (op.kind == OP_HGCONV)
             o << ",\"n\":" << op.i[0] << ",\"d\":" << op.i[1] << ",\"e\":" << op.i[2] << ",\"logit_scale\":" << op.f[0] << ",\"ld\":[" << tensors[op.in[0]].ld << ","
               << tensors[op.out[0]].ld << "],\"ws_bytes\":" << op.ws_bytes;

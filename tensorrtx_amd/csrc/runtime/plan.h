@@ -61,6 +61,8 @@ enum OpKind : int {
                         // constant, pre_head_proj, edge_proj, node_proj), packed at w_off as nine fp32 arrays in HgconvWeights' order; ws = its workspace
     OP_GATED_ADD,       // out = in[0] + gate (.) in[1] on NHWC tensors (nhwc_gated_add): src_layer = the constant layer that holds the gate (one value, or one per
                         // channel), packed at w_off as C fp32 values
+    OP_ATTENTION_SPLIT, // YOLOv13 area attention (kernels/attention_mfma.hip, area_attention_split_f16): in[0] = the NHWC fp16 q | k tensor (head h's q at channel
+                        // h*kd, its k at i[5] + h*kd), in[1] = the NHWC fp16 v tensor, out[0] = O; i = heads, N, kd, hd, area, the k channel offset; f[0] = scale
 };
 const char* op_kind_name(int k);
 
