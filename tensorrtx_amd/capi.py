@@ -97,20 +97,27 @@ def yolo_decode(inputs, classes, net_h, net_w, strides, max_out=1000, out=None):
     return out
 
 
-def yolo_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, with_dets=True):
-    """batch_nms replacement (yolov8/src/postprocess.cpp:71-129). Returns keep_idx, keep_cnt, keep_det."""
+def _nms_buffers(B, max_out, det_out, dev, out, ws, with_dets=True):
+    """keep_idx, keep_cnt, keep_det and the workspace of an NMS call: the caller's (`out` = the three tensors, `ws` = a uint8 tensor) or new ones"""
     import torch
     L = lib()
-    B = decode_out.shape[0]
-    dev = decode_out.device
-    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
-    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
-    keep_det = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev) if with_dets else None
     L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_nms_workspace(B)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.full((B, max_out), -1, dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+               torch.zeros((B, max_out, det_out), dtype=torch.float32, device=dev) if with_dets else None)
+    if ws is None:
+        ws = torch.empty((L.trtx_yolo_nms_workspace(B),), dtype=torch.uint8, device=dev)
+    keep_idx, keep_cnt, keep_det = out
+    return keep_idx, keep_cnt, keep_det, ws
+
+
+def yolo_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, with_dets=True, out=None, ws=None):
+    """batch_nms replacement (yolov8/src/postprocess.cpp:71-129). Returns keep_idx, keep_cnt, keep_det."""
+    L = lib()
+    B = decode_out.shape[0]
+    keep_idx, keep_cnt, keep_det, ws = _nms_buffers(B, max_out, 6, decode_out.device, out, ws, with_dets)
     check(L.trtx_yolo_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh),
-                          _p(keep_idx), _p(keep_cnt), _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()),
+                          _p(keep_idx), _p(keep_cnt), _p(keep_det), _p(ws), ctypes.c_size_t(ws.numel()), _stream()),
           "trtx_yolo_nms")
     return keep_idx, keep_cnt, keep_det
 
@@ -195,26 +202,22 @@ def yolo_task_head_decode_nhwc(heads, branches, classes, net_h, net_w, strides, 
     return out
 
 
-def yolo_nms_obb(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
+def yolo_nms_obb(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
     """nms_obb replacement (yolov8/src/postprocess.cpp:303-393).  keep_det: [B, max_out, 7] = cx, cy, w, h, conf, cls, angle."""
-    import torch
     L = lib()
-    B, dev = decode_out.shape[0], decode_out.device
-    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
-    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
-    keep_det = torch.zeros((B, max_out, 7), dtype=torch.float32, device=dev)
-    L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_nms_workspace(B)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    B = decode_out.shape[0]
+    keep_idx, keep_cnt, keep_det, ws = _nms_buffers(B, max_out, 7, decode_out.device, out, ws)
     check(L.trtx_yolo_nms_obb(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
-                              _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolo_nms_obb")
+                              _p(keep_det), _p(ws), ctypes.c_size_t(ws.numel()), _stream()), "trtx_yolo_nms_obb")
     return keep_idx, keep_cnt, keep_det
 
 
-def yolo_postprocess_gpu_obb(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
-    """The reference's GPU mode for oriented boxes (yolov8/src/postprocess.cu: decode_kernel_obb + nms_kernel_obb): [B, 1 + max_out*8]."""
+def yolo_postprocess_gpu_obb(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
+    """The reference's GPU mode for oriented boxes (yolov8/src/postprocess.cu: decode_kernel_obb + nms_kernel_obb): [B, 1 + max_out*8].
+    `out`: the caller's buffer; `ws`: accepted like the NMS wrappers' and not used (this entry point takes no workspace)."""
     import torch
-    out = torch.empty((decode_out.shape[0], 1 + max_out * 8), dtype=torch.float32, device=decode_out.device)
+    if out is None:
+        out = torch.empty((decode_out.shape[0], 1 + max_out * 8), dtype=torch.float32, device=decode_out.device)
     check(lib().trtx_yolo_postprocess_gpu_obb(_p(decode_out), decode_out.shape[0], max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh),
                                               _p(out), _stream()), "trtx_yolo_postprocess_gpu_obb")
     return out
@@ -266,19 +269,13 @@ def yolov5_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_ou
     return out
 
 
-def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
+def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
     """yolov5 batch_nms replacement (yolov5/src/postprocess.cpp:30-80). Returns keep_idx, keep_cnt, keep_det [B, max_out, 6]."""
-    import torch
     L = lib()
-    B, dev = decode_out.shape[0], decode_out.device
-    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
-    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
-    keep_det = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
-    L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_nms_workspace(B)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    B = decode_out.shape[0]
+    keep_idx, keep_cnt, keep_det, ws = _nms_buffers(B, max_out, 6, decode_out.device, out, ws)
     check(L.trtx_yolov5_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
-                            _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov5_nms")
+                            _p(keep_det), _p(ws), ctypes.c_size_t(ws.numel()), _stream()), "trtx_yolov5_nms")
     return keep_idx, keep_cnt, keep_det
 
 
@@ -360,20 +357,14 @@ def yolov7_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_ou
     return out
 
 
-def yolov7_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
+def yolov7_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
     """yolov7 batch_nms replacement (yolov7/src/postprocess.cpp:48-89) on 6-float records.  Returns keep_idx, keep_cnt,
     keep_det [B, max_out, 6]."""
-    import torch
     L = lib()
-    B, dev = decode_out.shape[0], decode_out.device
-    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
-    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
-    keep_det = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
-    L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_nms_workspace(B)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    B = decode_out.shape[0]
+    keep_idx, keep_cnt, keep_det, ws = _nms_buffers(B, max_out, 6, decode_out.device, out, ws)
     check(L.trtx_yolov7_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
-                            _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov7_nms")
+                            _p(keep_det), _p(ws), ctypes.c_size_t(ws.numel()), _stream()), "trtx_yolov7_nms")
     return keep_idx, keep_cnt, keep_det
 
 
@@ -420,20 +411,14 @@ def yolov9_head_decode_nhwc(box, cls, classes, net_h, net_w, dfl_w, max_out=1000
     return out
 
 
-def yolov9_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
+def yolov9_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
     """yolov9 batch_nms replacement (yolov9/src/postprocess.cpp:48-91) on 38-float records with corner boxes.  Returns keep_idx, keep_cnt,
     keep_det [B, max_out, 6] = cx, cy, w, h, conf, class: the centre format the reference's nms() leaves in `res`."""
-    import torch
     L = lib()
-    B, dev = decode_out.shape[0], decode_out.device
-    keep_idx = torch.full((B, max_out), -1, dtype=torch.int32, device=dev)
-    keep_cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
-    keep_det = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
-    L.trtx_yolo_nms_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolo_nms_workspace(B)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    B = decode_out.shape[0]
+    keep_idx, keep_cnt, keep_det, ws = _nms_buffers(B, max_out, 6, decode_out.device, out, ws)
     check(L.trtx_yolov9_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
-                            _p(keep_det), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov9_nms")
+                            _p(keep_det), _p(ws), ctypes.c_size_t(ws.numel()), _stream()), "trtx_yolov9_nms")
     return keep_idx, keep_cnt, keep_det
 
 
@@ -459,11 +444,13 @@ def seg_masks(decode_out, keep_idx, keep_cnt, proto, net_h, net_w, max_keep, box
     return out
 
 
-def yolo_postprocess_gpu(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45):
-    """The reference's GPU post-processing mode "g" (yolov8/src/postprocess.cu:42-111): [B, 1 + max_out*7]."""
+def yolo_postprocess_gpu(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
+    """The reference's GPU post-processing mode "g" (yolov8/src/postprocess.cu:42-111): [B, 1 + max_out*7].
+    `out`: the caller's buffer; `ws`: accepted like the NMS wrappers' and not used (this entry point takes no workspace)."""
     import torch
     B = decode_out.shape[0]
-    out = torch.empty((B, 1 + max_out * 7), dtype=torch.float32, device=decode_out.device)
+    if out is None:
+        out = torch.empty((B, 1 + max_out * 7), dtype=torch.float32, device=decode_out.device)
     check(lib().trtx_yolo_postprocess_gpu(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh),
                                           _p(out), _stream()), "trtx_yolo_postprocess_gpu")
     return out
