@@ -391,6 +391,21 @@ int32_t trtx_op_conv_stem_nchw_f16(const float* in, int N, int C, int H, int W, 
  * Same bits as trtx_op_conv_stem_nchw_f16 followed by trtx_op_conv2d_nhwc_f16 on its default tactic.  conv_act: none, ReLU or SiLU. */
 int32_t trtx_op_conv_stem_pair_f16(const float* in, int N, int C, int H, int W, const float* stem_w_taps_cout, const float* stem_bias, int stem_act,
                                    const void* conv_wpacked, const float* conv_bias, int conv_act, void* out, int ld_out, trtx_stream_t stream);
+/* The two 3x3 stride-1 pad-1 convolutions of a 16-channel bottleneck in ONE launch (kernels/conv_bneck_pair.hip): in NHWC fp16 [N][H][W] with channel stride
+ * ld_in, the 16 input channels starting at channel in_coff (a concat slice works as a source: ld_in and in_coff multiples of 8, in 16-byte aligned); both
+ * weight sets as trtx_conv_pack_weights_f16 packs them ([16][160] fp16, cin_pad 16) with biases [16] or NULL; act1 / act2: none, ReLU or SiLU; shortcut != 0
+ * adds the input to the second convolution's result, act_after (none, or ReLU with a shortcut) follows; out NHWC fp16 with channel stride ld_out (a multiple
+ * of 8).  The output may be another 16-channel slice of the input's buffer (same channel stride) or memory apart from it; an output that lies on the input
+ * channels is TRTX_ERR_INVALID: the kernel cannot run in place.  The tensor between the two is never written.  Same bits as two trtx_op_conv2d_nhwc_f16
+ * launches on the default tactic, the second with the input as residual. */
+int32_t trtx_op_conv_bneck_pair_f16(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1,
+                                    const void* w2_packed, const float* bias2, int act2, int shortcut, int act_after, void* out, int ld_out,
+                                    trtx_stream_t stream);
+/* What the executor issues for such a pair: that launch where it is possible, otherwise the two implicit-GEMM launches through `mid` (NHWC fp16 [N][H][W][16],
+ * 16-byte aligned, written only then) - an output that lies on the input included, which two launches compute correctly. */
+int32_t trtx_op_conv_bneck_pair_or_two_f16(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1,
+                                           const void* w2_packed, const float* bias2, int act2, int shortcut, int act_after, void* mid, void* out,
+                                           int ld_out, trtx_stream_t stream);
 /* The same launch in an fp32 engine (builds without BuilderFlag::kFP16: yolov8/include/config.h:1-3 USE_FP32, yolov8/src/model.cpp:314-324):
  * NHWC fp32 in / out / residual, fp32 weights packed [cout_pad][kpad] (k = tap * cink + c, cink = Cin rounded up to the 16-channel k-step, or 8 for
  * Cin <= 8; Cin itself a multiple of 4), fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products and sums).  trtx_op_conv2d_tactics_f32 lists the tile

@@ -540,6 +540,26 @@ def conv_stem_pair_f16(x, stem_w_taps_cout, stem_bias, conv_wpacked, conv_bias, 
     return out
 
 
+def conv_bneck_pair_f16(x, w1_packed, bias1, w2_packed, bias2, act1="silu", act2="silu", shortcut=True, act_after="none", out=None, out_ld=None, in_coff=None,
+                        mid=None):
+    """The two 3x3 convolutions of a 16-channel bottleneck (16 -> 16 -> 16, stride 1, pad 1) in one launch: x [N,H,W,16] CUDA half or a 16-channel slice of
+    a wider tensor (pixel stride x.stride(2)) -> NHWC half [N,H,W,16] (or into `out` with channel stride out_ld); shortcut: x is added to the result.
+    in_coff: x is the WHOLE wider tensor and the 16 input channels start at this channel.  mid (NHWC half [N,H,W,16]): the executor's form - the fused
+    launch where it is possible, the two launches through `mid` where it is not (an `out` that lies on the input channels, which the fused launch refuses)."""
+    import torch
+    N, H, W, C = x.shape
+    assert x.dtype == torch.float16 and x.stride(3) == 1 and (C == 16 if in_coff is None else in_coff + 16 <= C)
+    if out is None:
+        out = torch.empty((N, H, W, 16), dtype=torch.float16, device=x.device)
+    head = (_p(x), N, H, W, x.stride(2), in_coff or 0, _p(w1_packed), _p(bias1), ACT[act1], _p(w2_packed), _p(bias2), ACT[act2], 1 if shortcut else 0, ACT[act_after])
+    if mid is None:
+        check(lib().trtx_op_conv_bneck_pair_f16(*head, _p(out), out_ld or out.shape[-1], _stream()), "trtx_op_conv_bneck_pair_f16")
+    else:
+        assert mid.dtype == torch.float16 and mid.is_contiguous() and tuple(mid.shape) == (N, H, W, 16)
+        check(lib().trtx_op_conv_bneck_pair_or_two_f16(*head, _p(mid), _p(out), out_ld or out.shape[-1], _stream()), "trtx_op_conv_bneck_pair_or_two_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- grouped conv on the matrix pipe (tests / tools)
 def pack_conv_weights_grouped_f16(w_kcrs, ch_scale=None):
     """Host: KCRS fp32 numpy [Cout, Cin / groups, k, k] -> packed uint16 [Cout, Kpad] for conv2d_grouped_nhwc_f16."""

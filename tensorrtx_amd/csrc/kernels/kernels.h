@@ -169,6 +169,15 @@ int32_t conv_stem_frames_f32(const ConvArgs& a, const StemFrame* frames, hipStre
 // the same bits as the stem followed by the implicit-GEMM kernel's main K order.  _possible(): geometry, and the alignment of whatever pointers are set.
 bool conv_stem_pair_possible(const ConvArgs& stem, const ConvArgs& conv);
 int32_t conv_stem_pair_f16(const ConvArgs& stem, const ConvArgs& conv, hipStream_t s);
+// The two 3x3 convolutions of a 16-channel bottleneck in one launch (conv_bneck_pair.hip): 16 -> 16 -> 16, both 3x3 / 1 pad 1, fp16, the second with or
+// without the first one's input as shortcut.  `first` and `second` as conv_igemm_f16 takes them (first.out is not written, second.in is not read;
+// second.residual, if set, is first.in with ld_res == ld_in): the same packed weights, the same bits as two launches of the implicit-GEMM kernel's main
+// K order.  _possible(): geometry, and the alignment / identity of whatever pointers are set (a residual below 4096 only says "there is one").
+bool conv_bneck_pair_possible(const ConvArgs& first, const ConvArgs& second);
+int32_t conv_bneck_pair_f16(const ConvArgs& first, const ConvArgs& second, hipStream_t s);
+// ... where _possible() holds (it refuses an output that lies on the input other than as a different channel slice of one buffer: the fused kernel cannot run
+// in place), otherwise the two launches: first.out, the tensor between them, is then written and second.in must be it.  What the executor issues at a marked op.
+int32_t conv_bneck_pair_or_two_f16(const ConvArgs& first, const ConvArgs& second, hipStream_t s);
 // generic direct convolution (any groups / dilation / channel count), T = activation dtype, fp32 weights
 int32_t conv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 // depthwise convolution (conv_dw.hip): groups == Cin == Cout, k 3 / 5 / 7 with pad k/2, stride 1 / 2, no dilation; weights fp32 [kh*kw][C]

@@ -163,6 +163,40 @@ extern "C" int32_t trtx_op_conv_stem_pair_f16(const float* in, int N, int C, int
     return conv_stem_pair_f16(s, c, static_cast<hipStream_t>(stream));
 }
 
+// --- the two 3x3 convolutions of a 16-channel bottleneck in one launch (kernels/conv_bneck_pair.hip), test / tool entry points
+static int32_t op_bneck_pair(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1, const void* w2_packed,
+                             const float* bias2, int act2, int shortcut, int act_after, void* mid, void* out, int ld_out, bool or_two, trtx_stream_t stream) {
+    if (!in || !w1_packed || !w2_packed || !out || N < 1 || H < 1 || W < 1 || ld_in < 16 || ld_in % 8 || in_coff < 0 || in_coff % 8 || in_coff + 16 > ld_in ||
+        ld_out < 16 || ld_out % 8 || (or_two && !mid))
+        return TRTX_ERR_INVALID;
+    ConvArgs a = op_conv_args(N, H, W, 16, ld_in, 16, 16, 3, 3, 1, 1, 1, 1, act1, 0, 0, 0);
+    ConvArgs b = op_conv_args(N, H, W, 16, 16, 16, ld_out, 3, 3, 1, 1, 1, 1, act2, shortcut ? 1 : 0, shortcut ? ld_in : 0, act_after);
+    a.in = static_cast<const uint16_t*>(in) + in_coff;
+    a.wgt = w1_packed;
+    a.bias = bias1;
+    a.out = mid;
+    b.in = mid;
+    b.wgt = w2_packed;
+    b.bias = bias2;
+    b.out = out;
+    b.residual = shortcut ? a.in : nullptr;
+    if (or_two) return conv_bneck_pair_or_two_f16(a, b, static_cast<hipStream_t>(stream));
+    if (!conv_bneck_pair_possible(a, b)) return TRTX_ERR_INVALID;   // (an output that lies on the input channels among the reasons)
+    return conv_bneck_pair_f16(a, b, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trtx_op_conv_bneck_pair_f16(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1,
+                                               const void* w2_packed, const float* bias2, int act2, int shortcut, int act_after, void* out, int ld_out,
+                                               trtx_stream_t stream) {
+    return op_bneck_pair(in, N, H, W, ld_in, in_coff, w1_packed, bias1, act1, w2_packed, bias2, act2, shortcut, act_after, nullptr, out, ld_out, false, stream);
+}
+
+extern "C" int32_t trtx_op_conv_bneck_pair_or_two_f16(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1,
+                                                      const void* w2_packed, const float* bias2, int act2, int shortcut, int act_after, void* mid, void* out,
+                                                      int ld_out, trtx_stream_t stream) {
+    return op_bneck_pair(in, N, H, W, ld_in, in_coff, w1_packed, bias1, act1, w2_packed, bias2, act2, shortcut, act_after, mid, out, ld_out, true, stream);
+}
+
 // --- grouped convolution on the matrix pipe (kernels/conv_grouped.hip), test / tool entry points
 extern "C" int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale, uint16_t* packed,
                                                       int32_t* kpad_out) {

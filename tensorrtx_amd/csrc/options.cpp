@@ -29,6 +29,7 @@ Options read_options() {
     o.group_convs = !env_is("TRTX_GROUP_CONVS", 0);
     o.fold_upsample = !env_is("TRTX_FOLD_UPSAMPLE", 0);
     o.stem_pair = !env_is("TRTX_STEM_PAIR", 0);
+    o.bneck_pair = !env_is("TRTX_BNECK_PAIR", 0);
     o.ws = !env_set("TRTX_CONV_NOWS");
     o.wsk = !env_set("TRTX_CONV_NOWSK");
     o.gemm256 = !env_is("TRTX_GEMM256", 0);

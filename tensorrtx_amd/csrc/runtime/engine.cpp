@@ -135,6 +135,15 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
     if (lanes && hipEventRecord(c->start_event, user_stream) != hipSuccess) return bail(TRTX_ERR_HIP);
     ConvArgs pair_stem{};        // the stem's arguments, kept for the fused launch the next op issues
     bool pair_pending = false;
+    // The bottleneck pair (POp::bneck_pair on op k + 1; kernels/conv_bneck_pair.hip): op k launches nothing and the marked op issues BOTH convolutions - as the
+    // one fused launch where the kernel takes the run-time pointers, as the two launches otherwise (conv_bneck_pair_or_two_f16) - so nothing is kept between
+    // the two ops that could be dropped.  A function of the plan and the context alone: both ops ask it and get the same answer.  The calibration observer
+    // (which reads the tensor between the two) and the tactic timing (both ops keep a timed tactic of their own) keep one launch per op.
+    auto defers_to_next = [&](size_t k) {
+        if (c->observer || c->tuning || k + 1 >= plan.ops.size()) return false;
+        const POp &o = plan.ops[k], &nx = plan.ops[k + 1];
+        return nx.bneck_pair && nx.kind == OP_CONV && o.kind == OP_CONV && o.igemm && nx.lane == o.lane && nx.in[0] == o.out[0];
+    };
     for (size_t k = 0; k < plan.ops.size(); ++k) {
         const POp& op = plan.ops[k];
         hipStream_t stream = user_stream;  // shadows the parameter: the stream THIS op is issued on
@@ -190,6 +199,21 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     pair_pending = false;
                     if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
                     st = conv_stem_pair_f16(pair_stem, a, stream);
+                    conv_set_launch_probe(nullptr);
+                    break;
+                }
+                if (defers_to_next(k)) break;   // the first convolution of a bottleneck pair: issued by the marked op behind it
+                if (op.bneck_pair && k > 0 && defers_to_next(k - 1)) {   // ... here: its profile row carries the launch and the first op's reports 0
+                    const POp& fo = plan.ops[k - 1];
+                    ConvArgs f = fo.conv;
+                    f.in = R.ptr(fo.in[0]);
+                    f.out = R.ptr(fo.out[0]);
+                    f.wgt = W + fo.w_off;
+                    f.bias = reinterpret_cast<const float*>(W + fo.b_off);
+                    f.N = nb(plan.tensors[fo.in[0]]);
+                    f.M = f.N * f.Ho * f.Wo;
+                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
+                    st = conv_bneck_pair_or_two_f16(f, a, stream);
                     conv_set_launch_probe(nullptr);
                     break;
                 }

@@ -39,7 +39,8 @@ std::string Plan::describe_json() const {
         o << "\",\"flops\":" << op.flops << ",\"bytes\":" << op.bytes;
         auto conv_fields = [&](const POp& op) {
             const ConvArgs& a = op.conv;
-            o << ",\"igemm\":" << (op.igemm ? "true" : "false") << ",\"stem\":" << (op.stem ? "true" : "false") << (op.stem_pair ? ",\"stem_pair\":true" : "") << ",\"cin\":" << (a.in_i8 ? 2 * a.Cin : a.Cin) << ",\"cout\":" << a.Cout
+            o << ",\"igemm\":" << (op.igemm ? "true" : "false") << ",\"stem\":" << (op.stem ? "true" : "false") << (op.stem_pair ? ",\"stem_pair\":true" : "")
+              << (op.bneck_pair ? ",\"bneck_pair\":true" : "") << ",\"cin\":" << (a.in_i8 ? 2 * a.Cin : a.Cin) << ",\"cout\":" << a.Cout
               << ",\"k\":[" << a.kh << "," << a.kw << "],\"stride\":[" << a.stride_h << "," << a.stride_w << "],\"hw_in\":["
               << a.H << "," << a.W << "],\"hw_out\":[" << a.Ho << "," << a.Wo << "],\"act1\":" << a.act1
               << ",\"act2\":" << a.act2 << ",\"alpha1\":" << a.alpha1 << ",\"alpha2\":" << a.alpha2 << ",\"up_c\":" << a.up_C << ",\"residual\":" << (op.in.size() > 1 ? "true" : "false")

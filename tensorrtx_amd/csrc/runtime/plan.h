@@ -113,6 +113,8 @@ struct POp {
     bool stem = false;         // conv_stem kernel: reads the LINEAR fp32 input directly
     bool stem_pair = false;    // the op right after the stem: the engine computes it straight from the network input in ONE launch with the stem
                                // (kernels/conv_stem_pair.hip); the stem op before it then launches nothing and the tensor between them stays unwritten
+    bool bneck_pair = false;   // the second 3x3 convolution of a 16-channel bottleneck: the engine computes it in ONE launch with the convolution right before it
+                               // (kernels/conv_bneck_pair.hip); that op then launches nothing and the tensor between them stays unwritten
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
     bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
     bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one

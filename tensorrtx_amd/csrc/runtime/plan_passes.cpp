@@ -766,6 +766,55 @@ void mark_stem_pair(Plan& plan, const PassInputs& e) {
     }
 }
 
+// The two 3x3 convolutions of a 16-channel bottleneck in one launch (kernels/conv_bneck_pair.hip; YOLOv8n's first C2f block): marks the SECOND convolution
+// (POp::bneck_pair); the op list, the tensors and the arena stay what they are - the executor issues the fused launch at the marked op and nothing at the op
+// before it, and the tensor between them keeps its block, unwritten.  Marked when both are plain implicit-GEMM convolutions right behind each other, the first
+// without a shortcut, the second with none or with exactly the first one's input; the tensor between them is an arena tensor of its own (no view, no binding)
+// that no other op or member of a grouped launch touches; the output is not a view that overlaps the input (other workgroups still read it as halo - and
+// plan_arena() keeps the output's BLOCK off the input's by counting the first op's inputs as live at the marked op); the plan is fp16
+// without an int8 side; and conv_bneck_pair_possible() takes the two layers at the largest batch.  Wider pairs (32 channels and up) are not taken: their
+// weights do not fit registers beside four workgroups per CU.  finalize_plan() drops a mark whose two ops ended up on different lanes.
+// Not part of the serialized network: re-derived wherever a plan is lowered.  TRTX_BNECK_PAIR=0 marks nothing (A/B, tests): every launch is then the
+// two-kernel form's.
+void mark_bneck_pair(Plan& plan, const PassInputs& e) {
+    if (!e.opt.bneck_pair || e.dt != DT_F16 || e.int8 || CalibrationLowering::active()) return;   // (the calibration engine's observer reads every tensor an op writes)
+    const int n = (int)plan.ops.size();
+    auto plain = [](const POp& op) { return op.kind == OP_CONV && op.igemm && !op.stem && !op.stem_pair && !op.bneck_pair && !op.from_deconv && op.extra_in.empty() && op.out.size() == 1; };
+    for (int k = 0; k + 1 < n; ++k) {
+        const POp& c0 = plan.ops[k];
+        POp& c1 = plan.ops[k + 1];
+        if (!plain(c0) || !plain(c1) || c0.in.size() != 1 || c1.in.empty() || c1.in.size() > 2 || c1.in[0] != c0.out[0]) continue;
+        if (c1.in.size() == 2 && c1.in[1] != c0.in[0]) continue;   // a shortcut from anywhere else
+        const PTensor& mid = plan.tensors[c0.out[0]];
+        if (mid.parent >= 0 || mid.storage < 0 || plan.storages[mid.storage].kind != ST_ARENA || is_binding_tensor(plan, mid.id)) continue;
+        bool shared = false;   // any other op (or member of a grouped launch) that touches the block the intermediate lives in
+        auto touches = [&](const POp& op) {
+            for (const std::vector<int>* v : {&op.in, &op.out, &op.extra_in})
+                for (int t : *v)
+                    if (plan.tensors[t].storage == mid.storage) return true;
+            return false;
+        };
+        for (int j = 0; j < n && !shared; ++j) {
+            if (j == k || j == k + 1) continue;
+            shared = touches(plan.ops[j]);
+            for (const POp& m : plan.ops[j].group) shared = shared || touches(m);
+        }
+        const PTensor &t_in = plan.tensors[c0.in[0]], &t_out = plan.tensors[c1.out[0]];
+        if (shared || t_in.storage == mid.storage || t_out.storage == mid.storage) continue;
+        if (t_in.layout != LAY_NHWC || t_out.layout != LAY_NHWC) continue;
+        if (t_in.storage == t_out.storage && t_in.rcoff < t_out.rcoff + std::max(t_out.C, 1) && t_out.rcoff < t_in.rcoff + std::max(t_in.C, 1)) continue;
+        ConvArgs a = c0.conv, b = c1.conv;   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
+        a.N = (t_in.nfix ? t_in.nfix : plan.max_batch) * t_in.nmul;
+        a.M = a.N * a.Ho * a.Wo;
+        b.N = (mid.nfix ? mid.nfix : plan.max_batch) * mid.nmul;
+        b.M = b.N * b.Ho * b.Wo;
+        b.residual = c1.in.size() > 1 ? reinterpret_cast<const void*>(1) : nullptr;   // presence only
+        if (!conv_bneck_pair_possible(a, b)) continue;
+        c1.bneck_pair = true;
+        ++k;   // (the marked op starts no pair of its own)
+    }
+}
+
 // Lanes (= HIP streams at run time): an op continues the lane of a dependency that is still that lane's tail,
 // otherwise it opens a free lane, otherwise it queues behind the lane that went idle first.  Independent branches
 // (the six cv2/cv3 head chains of YOLOv8, model.cpp:224-291; FPN/SSH branches of RetinaFace) end up on different
@@ -831,6 +880,10 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
         for (int t : op.in) mark(t);
         for (int t : op.extra_in) mark(t);
         for (int t : op.out) mark(t);
+        // a marked bottleneck pair is ONE launch, issued at this op, that reads the first convolution's input while it writes this op's output: that input is
+        // live here too, so the output's block can never be placed on it (two launches may run in place, the fused kernel may not)
+        if (op.bneck_pair && k > 0)
+            for (int t : plan.ops[k - 1].in) mark(t);
     }
     // plugin workspaces are short-lived arena blocks
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
@@ -893,8 +946,13 @@ bool finalize_plan(Plan& plan, const PassInputs& e, std::string* err) {
     chain_spp_parallel_pools(plan, e);
     group_convs(plan, e);
     mark_stem_pair(plan, e);
+    mark_bneck_pair(plan, e);
     const std::vector<std::vector<int>> deps = op_dependencies(plan);   // (group_convs reordered and merged ops: not its list)
     assign_lanes(plan, e, deps);
+    // a bottleneck pair is one launch on one stream, issued at its second op: not where the two sit on different lanes, nor where another lane waits for
+    // the first op alone (its event would fire before the launch that reads its input)
+    for (size_t k = 1; k < plan.ops.size(); ++k)
+        if (plan.ops[k].bneck_pair && (plan.ops[k].lane != plan.ops[k - 1].lane || plan.ops[k - 1].signal)) plan.ops[k].bneck_pair = false;
     plan_arena(plan, ancestors(plan, deps, true));
     return true;
 }
