@@ -224,49 +224,85 @@ def yolo_postprocess_gpu_obb(decode_out, max_out=1000, conf_thresh=0.5, nms_thre
 
 
 DET5_FLOATS = 38  # yolov5/src/types.h:11-16
+DET7_FLOATS = 6   # yolov7/include/types.h: bbox[4], conf, class_id
 
 
-def yolov5_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, is_seg=False):
-    """Anchor-based YoloLayerPlugin::enqueue replacement (yolov5/plugin/yololayer.cu:161-233).
-    inputs: CUDA fp32 [B, 3*(5+classes(+32)), gh*gw] per level; grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1+max_out*38]"""
+def _grid_tables(grids, anchors, n):
     import numpy as np
+    gw = (ctypes.c_int * max(n, 1))(*[g[0] for g in grids[:n]])
+    gh = (ctypes.c_int * max(n, 1))(*[g[1] for g in grids[:n]])
+    an = np.ascontiguousarray(anchors, dtype=np.float32).reshape(-1, 6)
+    return gw, gh, an
+
+
+# The anchor-based families share their kernels (plugins/anchor_decode.hip, anchor_head.hip); a family is its record length and the
+# prefix of its entry points: (38, "trtx_yolov5") or (6, "trtx_yolov7").
+def _anchor_decode(det, prefix, inputs, classes, net_h, net_w, grids, anchors, max_out, out, seg_args=()):
     import torch
     L = lib()
     n = len(inputs)
     ins = [x.contiguous() for x in inputs]
     B, dev = ins[0].shape[0], ins[0].device
     arr = (ctypes.c_void_p * n)(*[x.data_ptr() for x in ins])
-    gw = (ctypes.c_int * n)(*[g[0] for g in grids])
-    gh = (ctypes.c_int * n)(*[g[1] for g in grids])
-    an = np.ascontiguousarray(anchors, dtype=np.float32).reshape(n, 6)
-    L.trtx_yolov5_decode_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolov5_decode_workspace(B, gw, gh, n)
+    gw, gh, an = _grid_tables(grids, anchors, n)
+    ws_fn = getattr(L, prefix + "_decode_workspace")
+    ws_fn.restype = ctypes.c_size_t
+    ws_bytes = ws_fn(B, gw, gh, n)
     ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-    out = torch.zeros((B, 1 + max_out * DET5_FLOATS), dtype=torch.float32, device=dev)
-    check(L.trtx_yolov5_decode(arr, n, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, 1 if is_seg else 0,
-                               _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov5_decode")
+    if out is None:
+        out = torch.zeros((B, 1 + max_out * det), dtype=torch.float32, device=dev)
+    check(getattr(L, prefix + "_decode")(arr, n, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, *seg_args,
+                                         _p(out), _p(ws), ctypes.c_size_t(ws_bytes), _stream()), prefix + "_decode")
     return out
 
 
-def yolov5_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_out=1000):
-    """The fused anchor head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32; ld >= 3 * (5 + classes), the rest is padding):
-    trtx_yolov5_head_decode_nhwc{,_f32}.  grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1 + max_out * 38]"""
-    import numpy as np
+def _anchor_head_workspace(prefix, batch, grids):
+    n = len(grids)
+    gw, gh, _ = _grid_tables(grids, [0.0] * 6 * n, n)
+    fn = getattr(lib(), prefix + "_head_decode_workspace")
+    fn.restype = ctypes.c_size_t
+    return fn(batch, gw, gh, n)
+
+
+def _anchor_head(det, prefix, heads, classes, net_h, net_w, grids, anchors, max_out, out, ws, ld, n_levels, status_only):
     import torch
     L = lib()
     B, n, dev = heads[0].shape[0], len(heads), heads[0].device
     hp, hl = _head_table(heads)
-    gw = (ctypes.c_int * n)(*[g[0] for g in grids])
-    gh = (ctypes.c_int * n)(*[g[1] for g in grids])
-    an = np.ascontiguousarray(anchors, dtype=np.float32).reshape(n, 6)
-    L.trtx_yolov5_head_decode_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolov5_head_decode_workspace(B, gw, gh, n)
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-    out = torch.zeros((B, 1 + max_out * DET5_FLOATS), dtype=torch.float32, device=dev)
-    fn = L.trtx_yolov5_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolov5_head_decode_nhwc
-    check(fn(hp, hl, n, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out), _p(ws), ctypes.c_size_t(ws_bytes),
-             _stream()), "trtx_yolov5_head_decode_nhwc")
+    if ld is not None:
+        hl = (ctypes.c_int * n)(*ld)
+    gw, gh, an = _grid_tables(grids, anchors, n)
+    if ws is None:
+        ws = torch.empty(max(_anchor_head_workspace(prefix, B, grids), 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros((B, 1 + max_out * det), dtype=torch.float32, device=dev)
+    fn = getattr(L, prefix + ("_head_decode_nhwc_f32" if heads[0].dtype == torch.float32 else "_head_decode_nhwc"))
+    st = fn(hp, hl, n if n_levels is None else n_levels, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out),
+            _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    if status_only:
+        return st
+    check(st, prefix + "_head_decode_nhwc")
     return out
+
+
+def yolov5_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, is_seg=False, out=None):
+    """Anchor-based YoloLayerPlugin::enqueue replacement (yolov5/plugin/yololayer.cu:161-233).
+    inputs: CUDA fp32 [B, 3*(5+classes(+32)), gh*gw] per level; grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1+max_out*38]
+    `out`: a caller's buffer of at least B rows (rows beyond B are not touched)."""
+    return _anchor_decode(DET5_FLOATS, "trtx_yolov5", inputs, classes, net_h, net_w, grids, anchors, max_out, out, (1 if is_seg else 0,))
+
+
+def yolov5_head_decode_workspace(batch, grids):
+    return _anchor_head_workspace("trtx_yolov5", batch, grids)
+
+
+def yolov5_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_out=1000, out=None, ws=None, ld=None, n_levels=None,
+                            status_only=False):
+    """The fused anchor head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32; ld >= 3 * (5 + classes), the rest is padding):
+    trtx_yolov5_head_decode_nhwc{,_f32}.  grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1 + max_out * 38].
+    `out` / `ws`: the caller's buffers; `ld`, `n_levels`: what is passed instead of the tensors' own; `status_only`: return the
+    status code instead of raising (the refusal tests)."""
+    return _anchor_head(DET5_FLOATS, "trtx_yolov5", heads, classes, net_h, net_w, grids, anchors, max_out, out, ws, ld, n_levels, status_only)
 
 
 def yolov5_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):
@@ -291,70 +327,21 @@ def reorg_fold_weights(w):
     return out
 
 
-DET7_FLOATS = 6  # yolov7/include/types.h: bbox[4], conf, class_id
-
-
-def _grid_tables(grids, anchors, n):
-    import numpy as np
-    gw = (ctypes.c_int * max(n, 1))(*[g[0] for g in grids[:n]])
-    gh = (ctypes.c_int * max(n, 1))(*[g[1] for g in grids[:n]])
-    an = np.ascontiguousarray(anchors, dtype=np.float32).reshape(-1, 6)
-    return gw, gh, an
-
-
 def yolov7_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, out=None):
     """YOLOv7 YoloLayerPlugin::enqueue replacement (yolov7/plugin/yololayer.cu:152-207).
     inputs: CUDA fp32 [B, 3*(5+classes), gh*gw] per level; grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1+max_out*6]
     `out`: a caller's buffer of at least B rows (rows beyond B are not touched)."""
-    import torch
-    L = lib()
-    n = len(inputs)
-    ins = [x.contiguous() for x in inputs]
-    B, dev = ins[0].shape[0], ins[0].device
-    arr = (ctypes.c_void_p * n)(*[x.data_ptr() for x in ins])
-    gw, gh, an = _grid_tables(grids, anchors, n)
-    L.trtx_yolov7_decode_workspace.restype = ctypes.c_size_t
-    ws_bytes = L.trtx_yolov7_decode_workspace(B, gw, gh, n)
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.zeros((B, 1 + max_out * DET7_FLOATS), dtype=torch.float32, device=dev)
-    check(L.trtx_yolov7_decode(arr, n, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out), _p(ws),
-                               ctypes.c_size_t(ws_bytes), _stream()), "trtx_yolov7_decode")
-    return out
+    return _anchor_decode(DET7_FLOATS, "trtx_yolov7", inputs, classes, net_h, net_w, grids, anchors, max_out, out)
 
 
 def yolov7_head_decode_workspace(batch, grids):
-    L = lib()
-    n = len(grids)
-    gw, gh, _ = _grid_tables(grids, [0.0] * 6 * n, n)
-    L.trtx_yolov7_head_decode_workspace.restype = ctypes.c_size_t
-    return L.trtx_yolov7_head_decode_workspace(batch, gw, gh, n)
+    return _anchor_head_workspace("trtx_yolov7", batch, grids)
 
 
 def yolov7_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_out=1000, out=None, ws=None, ld=None, n_levels=None,
                             status_only=False):
-    """The fused YOLOv7 head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32; ld >= 3 * (5 + classes), the rest is padding):
-    trtx_yolov7_head_decode_nhwc{,_f32}.  grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1 + max_out * 6].
-    `out` / `ws`: the caller's buffers; `ld`, `n_levels`: what is passed instead of the tensors' own; `status_only`: return the
-    status code instead of raising (the refusal tests)."""
-    import torch
-    L = lib()
-    B, n, dev = heads[0].shape[0], len(heads), heads[0].device
-    hp, hl = _head_table(heads)
-    if ld is not None:
-        hl = (ctypes.c_int * n)(*ld)
-    gw, gh, an = _grid_tables(grids, anchors, n)
-    if ws is None:
-        ws = torch.empty(max(yolov7_head_decode_workspace(B, grids), 256), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.zeros((B, 1 + max_out * DET7_FLOATS), dtype=torch.float32, device=dev)
-    fn = L.trtx_yolov7_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolov7_head_decode_nhwc
-    st = fn(hp, hl, n if n_levels is None else n_levels, B, classes, net_h, net_w, gw, gh, an.ctypes.data_as(ctypes.c_void_p), max_out, _p(out),
-            _p(ws), ctypes.c_size_t(ws.numel()), _stream())
-    if status_only:
-        return st
-    check(st, "trtx_yolov7_head_decode_nhwc")
-    return out
+    """The fused YOLOv7 head: yolov5_head_decode_nhwc with 6-float records, trtx_yolov7_head_decode_nhwc{,_f32}.  -> [B, 1 + max_out * 6]."""
+    return _anchor_head(DET7_FLOATS, "trtx_yolov7", heads, classes, net_h, net_w, grids, anchors, max_out, out, ws, ld, n_levels, status_only)
 
 
 def yolov7_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=None, ws=None):

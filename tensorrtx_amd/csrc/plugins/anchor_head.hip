@@ -1,24 +1,28 @@
-// Fused YOLOv7 anchor head for gfx950 (MI355X): the two passes of yolo7_decode.hip reading the detect convolutions' own NHWC output -
-// what the engine uses instead of one layout pass per level to fp32 planes followed by the plugin.
+// Fused anchor head (YOLOv5 and YOLOv7 families) for gfx950 (MI355X): the two passes of anchor_decode.hip reading the detect
+// convolutions' own NHWC output - what the engine uses instead of one layout pass per level to fp32 planes followed by the plugin.
 //
 // heads[l]: [batch][cells_l][ld_l], T = _Float16 (fp16 engines) or float (fp32 engines).  Channel k * info + j of a pixel is value j of
 // anchor k (info = 5 + classes): x, y, w, h, objectness, class logits.  Channels [3 * info, ld) are padding and hold whatever the
-// convolution wrote: no lane reads one into a result.  The arithmetic is yolo7_score_kernel / yolo7_emit_kernel's, operation for
-// operation (yolov7/plugin/yololayer.cu:152-207); the 6-float records, their canonical (level, cell, anchor) order and the clamped
-// count are those of trtx_yolov7_decode.
+// convolution wrote: no lane reads one into a result.  The arithmetic is that of anchor_decode.hip's two kernels, operation for
+// operation (yolov5/plugin/yololayer.cu:161-227, yolov7/plugin/yololayer.cu:152-207); the records, their canonical (level, cell, anchor)
+// order and the clamped count are those of trtx_yolov5_decode and trtx_yolov7_decode.  The families differ in the record alone: kDet
+// floats, 38 for YOLOv5 (bbox[4], conf, class_id, mask[32]) and 6 for YOLOv7 (no mask).  Pass 1 never sees a record, so the two share its
+// kernels; pass 2 is one template on kDet.
 //
-// Mapping (that of yolo5_head.hip, restated here so that that unit stays as it is).  A pixel is one contiguous row, so lanes run along
-// the CHANNEL axis:
+// Mapping.  A pixel is one contiguous row (510 B of 512 for 80 classes in fp16), so lanes run along the CHANNEL axis:
 //   step 1  a wave takes 16 consecutive cells; lane 3 p + k loads the objectness of anchor k of cell p (48 loads in one instruction,
 //           one 64-B sector each) and the ballot of `!(box_prob < 0.1f)` is the wave's candidate mask.  A cell without a candidate is
-//           done here: its class logits are neither loaded nor put through expf, so most rows cost three sectors.
+//           done here: its class logits are neither loaded nor put through expf.  That is the common case by far (the gate drops
+//           > 99 % of the anchors of a trained model), so the kernel reads three sectors of most rows, not the rows.
 //   step 2  cells with a candidate are taken two at a time, one per half-wave.  32 lanes cover a 256-channel fp16 row with one 16-byte
 //           load each (two for fp32); a lane scans its 8 (4) channels in ascending order into one (best, class) pair per anchor, for
 //           the anchors that passed only, and a 5-step xor butterfly over the half-wave joins the pairs.  The join keeps the lower
 //           class index on equal probability, which is what the reference's strict-'>' scan from (0.0, class 0) returns.
 //           Rows whose base or stride is not 16-byte aligned take element loads (lane s reads channels s, s + 32, ...).
-// Pass 2 counts records, one per kept (cell, anchor); a record is 6 floats at float 1 + 6 * slot of its row - 4-byte aligned at a
-// 24-byte stride - and is written with six float stores.
+// One thread per cell (the channel-major kernel's mapping) would read 2-byte elements 512 B apart here.
+// Pass 2 counts records, one per kept (cell, anchor); a record starts at float 1 + kDet * slot of its row - 4-byte aligned only - and its
+// six floats are written with six float stores.  Floats 6 .. 37 of a YOLOv5 record (the mask coefficients of the segmentation plugin
+// route) are not written here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,14 +34,13 @@ namespace {
 using trtx::logist;
 
 constexpr int kMaxLevels = 8;
-constexpr int kAnchors = 3;     // kNumAnchor, yolov7/include/config.h
-constexpr int kChunk = 512;     // cells per chunk counter and per emit workgroup (as yolo7_decode.hip)
-constexpr int kDet7 = 6;        // sizeof(Detection) / 4: bbox[4], conf, class_id
+constexpr int kAnchors = 3;     // kNumAnchor, yolov5/src/config.h:35 and yolov7/include/config.h
+constexpr int kChunk = 512;     // cells per chunk counter and per emit workgroup (as anchor_decode.hip)
 constexpr int kWaveCells = 16;  // cells per wave in the score pass: 48 objectness loads in one instruction
 constexpr int kScoreBlock = 256;
 constexpr int kBlockCells = kWaveCells * kScoreBlock / 64;   // 64: divides kChunk, so a workgroup feeds one chunk counter
 
-struct Head7Table {
+struct HeadTable {
     const void* in[kMaxLevels];
     int ld[kMaxLevels];
     int vec[kMaxLevels];   // base and ld are multiples of 16 bytes
@@ -77,7 +80,7 @@ __device__ __forceinline__ void scan_channel(float v, int ch, int info, int nch,
 
 // Pass 1: conf / class of every (cell, anchor); -1 marks a dropped candidate.  score / cls: [batch][cells][3].
 template <typename T>
-__global__ __launch_bounds__(kScoreBlock) void yolo7_head_score_kernel(Head7Table t, int info, int total_cells, float* __restrict__ score,
+__global__ __launch_bounds__(kScoreBlock) void anchor_head_score_kernel(HeadTable t, int info, int total_cells, float* __restrict__ score,
                                                                        int* __restrict__ cls_out, int* __restrict__ chunk_cnt, int n_chunks) {
     using V = typename Vec16<T>::type;
     constexpr int VN = Vec16<T>::N;
@@ -174,12 +177,13 @@ __global__ __launch_bounds__(kScoreBlock) void yolo7_head_score_kernel(Head7Tabl
     if (threadIdx.x == 0 && s_cnt) atomicAdd(&chunk_cnt[b * n_chunks + (blockIdx.x * kBlockCells) / kChunk], s_cnt);
 }
 
-// Pass 2: yolo7_emit_kernel's ordered compaction, one thread per cell (0..3 records each); the box values come from the cell's row.
-template <typename T>
-__global__ __launch_bounds__(kChunk) void yolo7_head_emit_kernel(Head7Table t, int info, int total_cells, int net_w, int net_h,
-                                                                 const float* __restrict__ score, const int* __restrict__ cls_in,
-                                                                 const int* __restrict__ chunk_cnt, int n_chunks, int max_out, int out_elem,
-                                                                 float* __restrict__ output) {
+// Pass 2: anchor_emit_kernel's ordered compaction, one thread per cell (0..3 records each); the box values come from the cell's row.
+// kDet: floats per record, 38 (YOLOv5) or 6 (YOLOv7); floats 0 .. 5 are written.
+template <typename T, int kDet>
+__global__ __launch_bounds__(kChunk) void anchor_head_emit_kernel(HeadTable t, int info, int total_cells, int net_w, int net_h,
+                                                                  const float* __restrict__ score, const int* __restrict__ cls_in,
+                                                                  const int* __restrict__ chunk_cnt, int n_chunks, int max_out, int out_elem,
+                                                                  float* __restrict__ output) {
     const int b = blockIdx.y;
     const int chunk = blockIdx.x;
     const int lane = threadIdx.x & 63;
@@ -229,8 +233,8 @@ __global__ __launch_bounds__(kChunk) void yolo7_head_emit_kernel(Head7Table t, i
             if (!(sc[k] >= 0.0f || sc[k] != sc[k])) continue;
             if (slot < max_out) {
                 const T* a = cur + k * info;
-                float* det = out + 1 + (size_t)slot * kDet7;
-                // yololayer.cu:196-203, operation for operation
+                float* det = out + 1 + (size_t)slot * kDet;
+                // yolov5 yololayer.cu:199-206, yolov7 yololayer.cu:196-203, operation for operation
                 det[0] = (col - 0.5f + 2.0f * logist((float)a[0])) * net_w / gw;
                 det[1] = (row - 0.5f + 2.0f * logist((float)a[1])) * net_h / gh;
                 float bw = 2.0f * logist((float)a[2]);
@@ -252,9 +256,15 @@ __global__ __launch_bounds__(kChunk) void yolo7_head_emit_kernel(Head7Table t, i
     }
 }
 
-int32_t head7_decode(const void* const* heads, const int* ld, int elem_bytes, int n_levels, int batch, int classes, int net_h, int net_w,
-                     const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output, void* workspace,
-                     size_t workspace_bytes, hipStream_t stream) {
+// the planar plugin's planes: the same for both families
+size_t head_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels) {
+    return trtx_yolov5_decode_workspace(batch, grid_w, grid_h, n_levels);
+}
+
+template <int kDet>
+int32_t head_decode(const char* entry, const void* const* heads, const int* ld, int elem_bytes, int n_levels, int batch, int classes, int net_h,
+                    int net_w, const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output, void* workspace,
+                    size_t workspace_bytes, hipStream_t stream) {
     if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !heads || !ld || !grid_w || !grid_h || !anchors ||
         !output || !workspace)
         return TRTX_ERR_INVALID;
@@ -262,8 +272,8 @@ int32_t head7_decode(const void* const* heads, const int* ld, int elem_bytes, in
     // every refusal comes before the first write to the workspace
     for (int i = 0; i < n_levels; ++i)
         if (grid_w[i] < 1 || grid_h[i] < 1 || !heads[i] || ld[i] < kAnchors * info) return TRTX_ERR_INVALID;
-    if (workspace_bytes < trtx_yolov7_head_decode_workspace(batch, grid_w, grid_h, n_levels)) return TRTX_ERR_WORKSPACE;
-    Head7Table t{};
+    if (workspace_bytes < head_workspace(batch, grid_w, grid_h, n_levels)) return TRTX_ERR_WORKSPACE;
+    HeadTable t{};
     t.n_levels = n_levels;
     int off = 0;
     for (int i = 0; i < n_levels; ++i) {
@@ -285,35 +295,55 @@ int32_t head7_decode(const void* const* heads, const int* ld, int elem_bytes, in
     int* cls = reinterpret_cast<int*>(ws + plane);
     int* chunk_cnt = reinterpret_cast<int*>(ws + 2 * plane);
     if (hipMemsetAsync(chunk_cnt, 0, (size_t)batch * n_chunks * sizeof(int), stream) != hipSuccess) return TRTX_ERR_HIP;
-    const int out_elem = 1 + max_out * kDet7;
+    const int out_elem = 1 + max_out * kDet;
     const dim3 sgrid((total_cells + kBlockCells - 1) / kBlockCells, batch), egrid(n_chunks, batch);
     if (elem_bytes == 2) {
-        hipLaunchKernelGGL(yolo7_head_score_kernel<_Float16>, sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
-        hipLaunchKernelGGL(yolo7_head_emit_kernel<_Float16>, egrid, dim3(kChunk), 0, stream, t, info, total_cells, net_w, net_h, score, cls, chunk_cnt,
+        hipLaunchKernelGGL(anchor_head_score_kernel<_Float16>, sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
+        hipLaunchKernelGGL((anchor_head_emit_kernel<_Float16, kDet>), egrid, dim3(kChunk), 0, stream, t, info, total_cells, net_w, net_h, score, cls, chunk_cnt,
                            n_chunks, max_out, out_elem, output);
     } else {
-        hipLaunchKernelGGL(yolo7_head_score_kernel<float>, sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
-        hipLaunchKernelGGL(yolo7_head_emit_kernel<float>, egrid, dim3(kChunk), 0, stream, t, info, total_cells, net_w, net_h, score, cls, chunk_cnt,
+        hipLaunchKernelGGL(anchor_head_score_kernel<float>, sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
+        hipLaunchKernelGGL((anchor_head_emit_kernel<float, kDet>), egrid, dim3(kChunk), 0, stream, t, info, total_cells, net_w, net_h, score, cls, chunk_cnt,
                            n_chunks, max_out, out_elem, output);
     }
-    return trtx::check_launch("trtx_yolov7_head_decode_nhwc");
+    return trtx::check_launch(entry);
 }
 
 }  // namespace
 
 // score / class planes [batch][cells][3] and one candidate count per 512 cells: the plugin's workspace
+extern "C" size_t trtx_yolov5_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels) {
+    return head_workspace(batch, grid_w, grid_h, n_levels);
+}
+
 extern "C" size_t trtx_yolov7_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels) {
-    return trtx_yolov7_decode_workspace(batch, grid_w, grid_h, n_levels);
+    return head_workspace(batch, grid_w, grid_h, n_levels);
+}
+
+extern "C" int32_t trtx_yolov5_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                                void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return head_decode<38>("trtx_yolov5_head_decode_nhwc", heads, ld, 2, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
+                            workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_yolov5_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                    const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                                    void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return head_decode<38>("trtx_yolov5_head_decode_nhwc", heads, ld, 4, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
+                            workspace_bytes, stream);
 }
 
 extern "C" int32_t trtx_yolov7_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
                                                 const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
                                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    return head7_decode(heads, ld, 2, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace, workspace_bytes, stream);
+    return head_decode<6>("trtx_yolov7_head_decode_nhwc", heads, ld, 2, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
+                            workspace_bytes, stream);
 }
 
-extern "C" int32_t trtx_yolov7_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h,
-                                                    int net_w, const int* grid_w, const int* grid_h, const float* anchors, int max_out,
-                                                    float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    return head7_decode(heads, ld, 4, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace, workspace_bytes, stream);
+extern "C" int32_t trtx_yolov7_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                    const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                                    void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return head_decode<6>("trtx_yolov7_head_decode_nhwc", heads, ld, 4, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
+                            workspace_bytes, stream);
 }

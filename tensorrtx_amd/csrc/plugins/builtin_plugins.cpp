@@ -146,19 +146,26 @@ void yolo_fill(trtx_plugin_vtbl* v, YoloLayer* y) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The anchor-based form of "YoloLayer_TRT"/"1" (yolov5/plugin/yololayer.{h,cu}; same registered name as the YOLOv8 plugin in
-// the reference, a different parameter set): creator fields "netinfo" = int32[5] {classes, W, H, maxOut, isSeg} and "kernels" =
-// YoloKernel[n] {int width, height; float anchors[6]} (yolov5/src/model.cpp:246-275, yololayer.cu:250-266); blob
-// int classCount, threadCount, kernelCount, netW, netH, maxOut, bool isSeg, YoloKernel[n] (yololayer.cu:49-89).
-struct Yolo5Kernel {
+// The anchor-based forms of "YoloLayer_TRT"/"1" (the same registered name as the YOLOv8 plugin in the reference, other parameter sets),
+// one state for both:
+//   YOLOv5 (yolov5/plugin/yololayer.{h,cu}): creator fields "netinfo" = int32[5] {classes, W, H, maxOut, isSeg} and "kernels" =
+//     YoloKernel[n] {int width, height; float anchors[6]} (yolov5/src/model.cpp:246-275, yololayer.cu:250-266); blob int classCount,
+//     threadCount, kernelCount, netW, netH, maxOut, bool isSeg, YoloKernel[n] = 25 + 32 n bytes (yololayer.cu:49-89); Detection
+//     records of 38 floats.
+//   YOLOv7 (yolov7/plugin/yololayer.{h,cu}): the same without the segmentation flag and with records of 6 floats.  "netinfo" =
+//     int32[4] {classes, W, H, maxOut} - exactly four, five and more are YOLOv5's - and "kernels" (yolov7/src/block.cpp:220-255); the
+//     blob has no isSeg byte, 24 + 32 n bytes (yololayer.cu:40-78).
+struct AnchorKernel {
     int width, height;
     float anchors[6];
 };
-struct Yolo5Layer {
+struct AnchorLayer {
+    bool v7 = false;   // the YOLOv7 form; never serialised, the blob's length tells
     int class_count = 80, thread_count = 256, net_w = 640, net_h = 640, max_out = 1000;
-    bool seg = false;
-    std::vector<Yolo5Kernel> kernels;
+    bool seg = false;  // YOLOv5 only
+    std::vector<AnchorKernel> kernels;
 
+    int det_floats() const { return v7 ? 6 : 38; }
     std::vector<uint8_t> blob() const {
         std::vector<uint8_t> b;
         put(b, class_count);
@@ -167,24 +174,26 @@ struct Yolo5Layer {
         put(b, net_w);
         put(b, net_h);
         put(b, max_out);
-        put(b, seg);
+        if (!v7) put(b, seg);
         for (const auto& k : kernels) put(b, k);
         return b;
     }
-    static Yolo5Layer* from_blob(const void* data, size_t len) {
+    // accepted by its exact length and a kernelCount that agrees with it only
+    static AnchorLayer* from_blob(const void* data, size_t len, bool v7) {
         const uint8_t* p = static_cast<const uint8_t*>(data);
         const uint8_t* end = p + len;
-        auto* y = new Yolo5Layer();
+        auto* y = new AnchorLayer();
+        y->v7 = v7;
         int nk = 0;
         bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, nk) && get(p, end, y->net_w) &&
-                  get(p, end, y->net_h) && get(p, end, y->max_out) && get(p, end, y->seg) && nk >= 1 && nk <= 8 &&
-                  (size_t)(end - p) == (size_t)nk * sizeof(Yolo5Kernel);
+                  get(p, end, y->net_h) && get(p, end, y->max_out) && (v7 || get(p, end, y->seg)) && nk >= 1 && nk <= 8 &&
+                  (size_t)(end - p) == (size_t)nk * sizeof(AnchorKernel);
         for (int i = 0; ok && i < nk; ++i) {
-            Yolo5Kernel k{};
+            AnchorKernel k{};
             ok = get(p, end, k) && k.width > 0 && k.height > 0;
             y->kernels.push_back(k);
         }
-        if (!ok || y->class_count < 1 || y->max_out < 1) {
+        if (!ok || y->class_count < 1 || y->max_out < 1 || (v7 && (y->net_w < 1 || y->net_h < 1))) {
             delete y;
             return nullptr;
         }
@@ -199,17 +208,17 @@ struct Yolo5Layer {
     }
 };
 
-void yolo5_fill(trtx_plugin_vtbl* v, Yolo5Layer* y);
-int32_t yolo5_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
-    auto* y = static_cast<Yolo5Layer*>(s);
-    out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yololayer.cu:101-105
-    out->d[0] = (int64_t)y->max_out * 38 + 1;
+void anchor_fill(trtx_plugin_vtbl* v, AnchorLayer* y);
+int32_t anchor_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
+    auto* y = static_cast<AnchorLayer*>(s);
+    out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yolov5 yololayer.cu:101-105, yolov7 yololayer.cu:90-94
+    out->d[0] = (int64_t)y->max_out * y->det_floats() + 1;
     out->d[1] = 1;
     out->d[2] = 1;
     return 0;
 }
-int32_t yolo5_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
-    auto* y = static_cast<Yolo5Layer*>(s);
+int32_t anchor_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
+    auto* y = static_cast<AnchorLayer*>(s);
     if (nb_in != (int)y->kernels.size()) return 1;
     const int info = 5 + y->class_count + (y->seg ? 32 : 0);
     for (int i = 0; i < nb_in; ++i) {
@@ -219,62 +228,70 @@ int32_t yolo5_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_
     }
     return 0;
 }
-int32_t yolo5_initialize(void*) { return 0; }
-size_t yolo5_workspace(void* s, int32_t max_batch) {
-    auto* y = static_cast<Yolo5Layer*>(s);
+int32_t no_initialize(void*) { return 0; }
+size_t anchor_workspace(void* s, int32_t max_batch) {
+    auto* y = static_cast<AnchorLayer*>(s);
     std::vector<int> gw, gh;
     std::vector<float> an;
     y->geometry(&gw, &gh, &an);
-    return trtx_yolov5_decode_workspace(max_batch, gw.data(), gh.data(), (int)gw.size());
+    return trtx_yolov5_decode_workspace(max_batch, gw.data(), gh.data(), (int)gw.size());   // the same for both forms
 }
-int32_t yolo5_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
-    auto* y = static_cast<Yolo5Layer*>(s);
+int32_t anchor_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
+    auto* y = static_cast<AnchorLayer*>(s);
     std::vector<int> gw, gh;
     std::vector<float> an;
     y->geometry(&gw, &gh, &an);
     const size_t ws_bytes = trtx_yolov5_decode_workspace(batch, gw.data(), gh.data(), (int)gw.size());
-    return trtx_yolov5_decode(reinterpret_cast<const float* const*>(inputs), (int)gw.size(), batch, y->class_count, y->net_h, y->net_w,
-                              gw.data(), gh.data(), an.data(), y->max_out, y->seg ? 1 : 0, static_cast<float*>(outputs[0]), ws, ws_bytes,
-                              stream);
+    const auto* in = reinterpret_cast<const float* const*>(inputs);
+    float* out = static_cast<float*>(outputs[0]);
+    if (y->v7)
+        return trtx_yolov7_decode(in, (int)gw.size(), batch, y->class_count, y->net_h, y->net_w, gw.data(), gh.data(), an.data(), y->max_out, out,
+                                  ws, ws_bytes, stream);
+    return trtx_yolov5_decode(in, (int)gw.size(), batch, y->class_count, y->net_h, y->net_w, gw.data(), gh.data(), an.data(), y->max_out,
+                              y->seg ? 1 : 0, out, ws, ws_bytes, stream);
 }
-size_t yolo5_ser_size(void* s) { return static_cast<Yolo5Layer*>(s)->blob().size(); }
-void yolo5_serialize(void* s, void* buf) {
-    const auto b = static_cast<Yolo5Layer*>(s)->blob();
+size_t anchor_ser_size(void* s) { return static_cast<AnchorLayer*>(s)->blob().size(); }
+void anchor_serialize(void* s, void* buf) {
+    const auto b = static_cast<AnchorLayer*>(s)->blob();
     memcpy(buf, b.data(), b.size());
 }
-int32_t yolo5_clone(void* s, trtx_plugin_vtbl* out) {
-    yolo5_fill(out, new Yolo5Layer(*static_cast<Yolo5Layer*>(s)));
+int32_t anchor_clone(void* s, trtx_plugin_vtbl* out) {
+    anchor_fill(out, new AnchorLayer(*static_cast<AnchorLayer*>(s)));
     return 0;
 }
-void yolo5_destroy(void* s) { delete static_cast<Yolo5Layer*>(s); }
-void yolo5_fill(trtx_plugin_vtbl* v, Yolo5Layer* y) {
+void anchor_destroy(void* s) { delete static_cast<AnchorLayer*>(s); }
+void anchor_fill(trtx_plugin_vtbl* v, AnchorLayer* y) {
     v->self = y;
     v->get_nb_outputs = yolo_nb_outputs;
-    v->get_output_dims = yolo5_output_dims;
-    v->configure = yolo5_configure;
-    v->initialize = yolo5_initialize;
+    v->get_output_dims = anchor_output_dims;
+    v->configure = anchor_configure;
+    v->initialize = no_initialize;
     v->terminate = yolo_terminate;
-    v->workspace_size = yolo5_workspace;
-    v->enqueue = yolo5_enqueue;
-    v->serialization_size = yolo5_ser_size;
-    v->serialize = yolo5_serialize;
+    v->workspace_size = anchor_workspace;
+    v->enqueue = anchor_enqueue;
+    v->serialization_size = anchor_ser_size;
+    v->serialize = anchor_serialize;
     v->plugin_type = yolo_type;
     v->plugin_version = yolo_version;
-    v->clone = yolo5_clone;
-    v->destroy = yolo5_destroy;
+    v->clone = anchor_clone;
+    v->destroy = anchor_destroy;
 }
-int32_t yolo5_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
-    if (!f[0].data || !f[1].data || f[0].length < 5 || f[1].length < 1 || f[1].length > 8) return 1;
+// netinfo of exactly four ints, all >= 1: YOLOv7's; of five and more, taken as they come: YOLOv5's
+int32_t anchor_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
+    if (!f[0].data || !f[1].data || f[0].length < 4 || f[1].length < 1 || f[1].length > 8) return 1;
+    const bool v7 = f[0].length == 4;
     const int* ni = static_cast<const int*>(f[0].data);
-    auto* y = new Yolo5Layer();
+    if (v7 && (ni[0] < 1 || ni[1] < 1 || ni[2] < 1 || ni[3] < 1)) return 1;
+    auto* y = new AnchorLayer();
+    y->v7 = v7;
     y->class_count = ni[0];
     y->net_w = ni[1];
     y->net_h = ni[2];
     y->max_out = ni[3];
-    y->seg = ni[4] != 0;
-    y->kernels.resize(f[1].length);  // the reference counts this field in YoloKernel elements (model.cpp:272-273)
-    memcpy(y->kernels.data(), f[1].data, sizeof(Yolo5Kernel) * f[1].length);
-    yolo5_fill(out, y);
+    y->seg = !v7 && ni[4] != 0;
+    y->kernels.resize(f[1].length);  // the reference counts this field in YoloKernel elements (model.cpp:272-273, block.cpp:241-242)
+    memcpy(y->kernels.data(), f[1].data, sizeof(AnchorKernel) * f[1].length);
+    anchor_fill(out, y);
     return 0;
 }
 
@@ -355,7 +372,7 @@ void yolo9_fill(trtx_plugin_vtbl* v, Yolo9Layer* y) {
     v->get_nb_outputs = yolo_nb_outputs;
     v->get_output_dims = yolo9_output_dims;
     v->configure = yolo9_configure;
-    v->initialize = yolo5_initialize;
+    v->initialize = no_initialize;
     v->terminate = yolo_terminate;
     v->workspace_size = yolo9_workspace;
     v->enqueue = yolo9_enqueue;
@@ -380,137 +397,12 @@ int32_t yolo9_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// The YOLOv7 form of "YoloLayer_TRT"/"1" (yolov7/plugin/yololayer.{h,cu}): the anchor-based plugin without the segmentation flag and
-// with Detection records of 6 floats.  Creator fields "netinfo" = int32[4] {classes, W, H, maxOut} - exactly four, five and more are
-// YOLOv5's - and "kernels" = YoloKernel[n] (yolov7/src/block.cpp:220-255); blob int classCount, threadCount, kernelCount, netW, netH,
-// maxOut, YoloKernel[n] = 24 + 32 n bytes (yololayer.cu:40-78), one byte less than YOLOv5's.
-struct Yolo7Layer {
-    int class_count = 80, thread_count = 256, net_w = 640, net_h = 640, max_out = 1000;
-    std::vector<Yolo5Kernel> kernels;
-
-    std::vector<uint8_t> blob() const {
-        std::vector<uint8_t> b;
-        put(b, class_count);
-        put(b, thread_count);
-        put(b, (int)kernels.size());
-        put(b, net_w);
-        put(b, net_h);
-        put(b, max_out);
-        for (const auto& k : kernels) put(b, k);
-        return b;
-    }
-    // accepted by its exact length and a kernelCount that agrees with it only
-    static Yolo7Layer* from_blob(const void* data, size_t len) {
-        const uint8_t* p = static_cast<const uint8_t*>(data);
-        const uint8_t* end = p + len;
-        auto* y = new Yolo7Layer();
-        int nk = 0;
-        bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, nk) && get(p, end, y->net_w) &&
-                  get(p, end, y->net_h) && get(p, end, y->max_out) && nk >= 1 && nk <= 8 &&
-                  (size_t)(end - p) == (size_t)nk * sizeof(Yolo5Kernel);
-        for (int i = 0; ok && i < nk; ++i) {
-            Yolo5Kernel k{};
-            ok = get(p, end, k) && k.width > 0 && k.height > 0;
-            y->kernels.push_back(k);
-        }
-        if (!ok || y->class_count < 1 || y->max_out < 1 || y->net_w < 1 || y->net_h < 1) {
-            delete y;
-            return nullptr;
-        }
-        return y;
-    }
-    void geometry(std::vector<int>* gw, std::vector<int>* gh, std::vector<float>* an) const {
-        for (const auto& k : kernels) {
-            gw->push_back(k.width);
-            gh->push_back(k.height);
-            an->insert(an->end(), k.anchors, k.anchors + 6);
-        }
-    }
-};
-
-void yolo7_fill(trtx_plugin_vtbl* v, Yolo7Layer* y);
-int32_t yolo7_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
-    auto* y = static_cast<Yolo7Layer*>(s);
-    out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yololayer.cu:90-94
-    out->d[0] = (int64_t)y->max_out * 6 + 1;
-    out->d[1] = 1;
-    out->d[2] = 1;
-    return 0;
-}
-int32_t yolo7_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
-    auto* y = static_cast<Yolo7Layer*>(s);
-    if (nb_in != (int)y->kernels.size()) return 1;
-    for (int i = 0; i < nb_in; ++i) {
-        int64_t vol = 1;
-        for (int k = 0; k < in[i].nb; ++k) vol *= in[i].d[k];
-        if (vol != (int64_t)3 * (5 + y->class_count) * y->kernels[i].width * y->kernels[i].height) return 1;
-    }
-    return 0;
-}
-size_t yolo7_workspace(void* s, int32_t max_batch) {
-    auto* y = static_cast<Yolo7Layer*>(s);
-    std::vector<int> gw, gh;
-    std::vector<float> an;
-    y->geometry(&gw, &gh, &an);
-    return trtx_yolov7_decode_workspace(max_batch, gw.data(), gh.data(), (int)gw.size());
-}
-int32_t yolo7_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
-    auto* y = static_cast<Yolo7Layer*>(s);
-    std::vector<int> gw, gh;
-    std::vector<float> an;
-    y->geometry(&gw, &gh, &an);
-    const size_t ws_bytes = trtx_yolov7_decode_workspace(batch, gw.data(), gh.data(), (int)gw.size());
-    return trtx_yolov7_decode(reinterpret_cast<const float* const*>(inputs), (int)gw.size(), batch, y->class_count, y->net_h, y->net_w,
-                              gw.data(), gh.data(), an.data(), y->max_out, static_cast<float*>(outputs[0]), ws, ws_bytes, stream);
-}
-size_t yolo7_ser_size(void* s) { return static_cast<Yolo7Layer*>(s)->blob().size(); }
-void yolo7_serialize(void* s, void* buf) {
-    const auto b = static_cast<Yolo7Layer*>(s)->blob();
-    memcpy(buf, b.data(), b.size());
-}
-int32_t yolo7_clone(void* s, trtx_plugin_vtbl* out) {
-    yolo7_fill(out, new Yolo7Layer(*static_cast<Yolo7Layer*>(s)));
-    return 0;
-}
-void yolo7_destroy(void* s) { delete static_cast<Yolo7Layer*>(s); }
-void yolo7_fill(trtx_plugin_vtbl* v, Yolo7Layer* y) {
-    v->self = y;
-    v->get_nb_outputs = yolo_nb_outputs;
-    v->get_output_dims = yolo7_output_dims;
-    v->configure = yolo7_configure;
-    v->initialize = yolo5_initialize;
-    v->terminate = yolo_terminate;
-    v->workspace_size = yolo7_workspace;
-    v->enqueue = yolo7_enqueue;
-    v->serialization_size = yolo7_ser_size;
-    v->serialize = yolo7_serialize;
-    v->plugin_type = yolo_type;
-    v->plugin_version = yolo_version;
-    v->clone = yolo7_clone;
-    v->destroy = yolo7_destroy;
-}
-int32_t yolo7_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
-    if (!f[0].data || !f[1].data || f[0].length != 4 || f[1].length < 1 || f[1].length > 8) return 1;
-    const int* ni = static_cast<const int*>(f[0].data);
-    if (ni[0] < 1 || ni[1] < 1 || ni[2] < 1 || ni[3] < 1) return 1;
-    auto* y = new Yolo7Layer();
-    y->class_count = ni[0];
-    y->net_w = ni[1];
-    y->net_h = ni[2];
-    y->max_out = ni[3];
-    y->kernels.resize(f[1].length);  // counted in YoloKernel elements (block.cpp:241-242)
-    memcpy(y->kernels.data(), f[1].data, sizeof(Yolo5Kernel) * f[1].length);
-    yolo7_fill(out, y);
-    return 0;
-}
-
 // creator: one field "combinedInfo" = int32[9 + nStrides] (yolov8/src/block.cpp:267-293, yololayer.cu:339-360)
 int32_t yolo_create(void*, const char*, const trtx_plugin_field* f, int32_t nb, trtx_plugin_vtbl* out) {
     // the anchor-based plugin shares the registered name: told apart by its two fields "netinfo" + "kernels"
     // (four netinfo ints: YOLOv7's, which has no is_segmentation; five and more: YOLOv5's; fewer are refused by either)
     if (nb == 2 && f && f[0].name && f[1].name && !strcmp(f[0].name, "netinfo") && !strcmp(f[1].name, "kernels"))
-        return f[0].length == 4 ? yolo7_create(f, out) : yolo5_create(f, out);
+        return anchor_create(f, out);
     // ... and so does the YOLOv9 one: its single field is "netinfo"
     if (nb == 1 && f && f[0].name && !strcmp(f[0].name, "netinfo")) return yolo9_create(f, out);
     if (nb != 1 || !f || !f[0].name || strcmp(f[0].name, "combinedInfo") != 0 || f[0].length < 10) return 1;
@@ -536,9 +428,9 @@ int32_t yolo_deserialize(void*, const char*, const void* data, size_t len, trtx_
         return 0;
     }
     // not the YOLOv8 layout (both parsers check the exact length): the anchor-based blob
-    Yolo5Layer* y5 = Yolo5Layer::from_blob(data, len);
+    AnchorLayer* y5 = AnchorLayer::from_blob(data, len, false);
     if (y5) {
-        yolo5_fill(out, y5);
+        anchor_fill(out, y5);
         return 0;
     }
     // ... nor the anchor-based one: the YOLOv9 blob, 21 bytes
@@ -548,9 +440,9 @@ int32_t yolo_deserialize(void*, const char*, const void* data, size_t len, trtx_
         return 0;
     }
     // ... and last the YOLOv7 blob, 24 + 32 n bytes: no earlier parser takes that length (35 + 4 n, 25 + 32 n, 21)
-    Yolo7Layer* y7 = Yolo7Layer::from_blob(data, len);
+    AnchorLayer* y7 = AnchorLayer::from_blob(data, len, true);
     if (!y7) return 1;
-    yolo7_fill(out, y7);
+    anchor_fill(out, y7);
     return 0;
 }
 const char* yolo_creator_name(void*) { return "YoloLayer_TRT"; }
@@ -737,9 +629,10 @@ bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out) {
     return true;
 }
 
-bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
-    if (v.enqueue != yolo5_enqueue || !v.self) return false;
-    const auto* y = static_cast<const Yolo5Layer*>(v.self);
+static bool anchor_params(const trtx_plugin_vtbl& v, bool v7, Yolo5LayerParams* out) {
+    if (v.enqueue != anchor_enqueue || !v.self) return false;
+    const auto* y = static_cast<const AnchorLayer*>(v.self);
+    if (y->v7 != v7) return false;
     out->classes = y->class_count;
     out->net_w = y->net_w;
     out->net_h = y->net_h;
@@ -751,21 +644,8 @@ bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
     y->geometry(&out->grid_w, &out->grid_h, &out->anchors);
     return true;
 }
-
-bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) {
-    if (v.enqueue != yolo7_enqueue || !v.self) return false;
-    const auto* y = static_cast<const Yolo7Layer*>(v.self);
-    out->classes = y->class_count;
-    out->net_w = y->net_w;
-    out->net_h = y->net_h;
-    out->max_out = y->max_out;
-    out->seg = false;
-    out->grid_w.clear();
-    out->grid_h.clear();
-    out->anchors.clear();
-    y->geometry(&out->grid_w, &out->grid_h, &out->anchors);
-    return true;
-}
+bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, false, out); }
+bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, true, out); }
 
 bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
     if (v.enqueue != yolo9_enqueue || !v.self) return false;
@@ -780,7 +660,7 @@ bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
 
 // built-in plugins only enqueue kernels and stream-ordered memsets on the caller's stream: safe inside a stream capture
 bool builtin_plugin_capturable(const trtx_plugin_vtbl& v) {
-    return v.enqueue == yolo_enqueue || v.enqueue == yolo5_enqueue || v.enqueue == yolo7_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
+    return v.enqueue == yolo_enqueue || v.enqueue == anchor_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
 }
 
 void register_builtin_plugins(PluginRegistry& r) {

@@ -1,8 +1,11 @@
-// Device pieces shared by the decode plugins (yolo_decode.hip, yolo5_decode.hip, the RetinaFace decode of det_plugins.hip): the
-// sigmoid and the level lookup every one of them needs, and pass 1 of their deterministic two-pass compaction, in which every workgroup
-// leaves its candidate count in chunk_cnt[image][chunk].  Pass 2 (slot = candidates of earlier chunks + earlier waves + earlier lanes)
-// stays written out in each emit kernel: every shared form of it that was tried moved those kernels' instruction streams, and they
-// are kept instruction for instruction.  All kernels here are wave64.
+// Device pieces shared by the decode plugins (yolo_decode.hip, anchor_decode.hip, anchor_head.hip, yolo9_decode.hip, yolo9_head.hip, the
+// RetinaFace decode of det_plugins.hip): the sigmoid and the level lookup every one of them needs, and pass 1 of their deterministic
+// two-pass compaction, in which every workgroup leaves its candidate count in chunk_cnt[image][chunk].  Pass 2 (slot = candidates of
+// earlier chunks + earlier waves + earlier lanes) stays written out in each emit kernel: every form of it shared as a helper across
+// DIFFERENT kernels that was tried moved those kernels' instruction streams, and they are kept instruction for instruction.  One kernel
+// as a template on its record length is another matter: anchor_decode.hip and anchor_head.hip serve YOLOv5 (38 floats) and YOLOv7 (6)
+// from one source each, and the instantiations kept the streams of the copies they replaced (profiles/anchor_units_isa.txt).  All
+// kernels here are wave64.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -50,12 +50,12 @@ enum OpKind : int {
                       // i[4] = 0.  With i[4] = area >= 1: YOLOv12 area attention on the same tensors (kernels/attention_mfma.hip), N / area keys per query
     OP_YOLO_TASK_HEAD,  // fused DFL + YoloLayer seg / pose / obb decode (explicit batch): `in` = NHWC heads, `extra_in` = NHWC task branches;
                         // i as OP_YOLO_HEAD with at most 4 strides in i[5..8], i[9] = 1 seg / 2 pose / 3 obb, i[10] = keypoints, f[0] = kpt_conf
-    OP_YOLO5_HEAD,      // fused anchor-based YoloLayer decode (YOLOv5) on the detect convolutions' NHWC output (plugins/yolo5_head.hip): i[0] = classes,
+    OP_YOLO5_HEAD,      // fused anchor-based YoloLayer decode (YOLOv5) on the detect convolutions' NHWC output (plugins/anchor_head.hip): i[0] = classes,
                         // i[1] / i[2] = net h / w, i[3] = max_out, i[4] = levels, i[11] as OP_YOLO_HEAD; iv = (grid_w, grid_h) per level, fv = 6 anchors per level
     OP_YOLO9_HEAD,      // fused DFL + YOLOv9 YoloLayer decode (38-float records) on the NHWC outputs of the head's last convolutions (plugins/yolo9_head.hip):
                         // `in` = the three box tensors (64 DFL bins), `extra_in` = the three class tensors; i[0] = classes, i[1] / i[2] = net h / w,
                         // i[3] = max_out, i[4] = levels (3: strides 8 / 16 / 32); src_layer = the DFL 1x1 convolution
-    OP_YOLO7_HEAD,      // OP_YOLO5_HEAD with YOLOv7's 6-float records (plugins/yolo7_head.hip): the same i / iv / fv
+    OP_YOLO7_HEAD,      // OP_YOLO5_HEAD with YOLOv7's 6-float records (plugins/anchor_head.hip): the same i / iv / fv
     OP_HGCONV,          // YOLOv13's adaptive hypergraph convolution (kernels/hgconv.hip) on the NHWC fp16 token image: i[0] = N, i[1] = D, i[2] = E,
                         // f[0] = the logit scale 1 / (heads * scaling); iv = the five network layers that hold the weights (context_net, the prototype
                         // constant, pre_head_proj, edge_proj, node_proj), packed at w_off as nine fp32 arrays in HgconvWeights' order; ws = its workspace

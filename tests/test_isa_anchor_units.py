@@ -1,5 +1,5 @@
-"""tools/isa_barrier_reads.py on the YOLOv7 units (the fused anchor head and the planar decode keep their counters and wave prefixes in LDS
-between barriers): no barrier is reached with an LDS read in flight.  Compiled the way tests/test_isa_yolo9_units.py compiles its units,
+"""tools/isa_barrier_reads.py on the anchor units of YOLOv5 and YOLOv7 (the fused anchor head and the planar decode keep their counters and
+wave prefixes in LDS between barriers): no barrier is reached with an LDS read in flight.  Compiled the way tests/test_isa_yolo9_units.py compiles its units,
 with the plugins' -ffp-contract=off."""
 import os
 import subprocess
@@ -17,8 +17,8 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-@pytest.mark.parametrize("unit", ["yolo7_head", "yolo7_decode"])
-def test_yolo7_units_pass_no_barrier_with_lds_reads_in_flight(unit):
+@pytest.mark.parametrize("unit", ["anchor_head", "anchor_decode"])
+def test_anchor_units_pass_no_barrier_with_lds_reads_in_flight(unit):
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, unit + ".s")
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}",
