@@ -322,6 +322,10 @@ class IUnaryLayer : public ILayer {
    public:
     TRTX_LAYER_CTOR(IUnaryLayer)
 };
+class IPaddingLayer : public ILayer {   // zero fill; pre- and post-padding are what addPaddingNd was given
+   public:
+    TRTX_LAYER_CTOR(IPaddingLayer)
+};
 class IPluginV2Layer : public ILayer {
    public:
     TRTX_LAYER_CTOR(IPluginV2Layer)
@@ -696,6 +700,12 @@ class INetworkDefinition {
     }
     IIdentityLayer* addIdentity(ITensor& in) noexcept { return layer<IIdentityLayer>(trtx_add_identity(mNet, in.id())); }
     IUnaryLayer* addUnary(ITensor& in, UnaryOperation op) noexcept { return layer<IUnaryLayer>(trtx_network_add_unary(mNet, in.id(), (int32_t)op)); }
+    // yolov3-tiny/yolov3-tiny.cpp:248; a negative (cropping) value is refused when the network is built
+    IPaddingLayer* addPaddingNd(ITensor& in, const Dims& prePadding, const Dims& postPadding) noexcept {
+        const trtx_dims a = shim::to_c(prePadding), b = shim::to_c(postPadding);
+        return layer<IPaddingLayer>(trtx_add_padding(mNet, in.id(), &a, &b));
+    }
+    IPaddingLayer* addPadding(ITensor& in, DimsHW prePadding, DimsHW postPadding) noexcept { return addPaddingNd(in, prePadding, postPadding); }
     IPluginV2Layer* addPluginV2(ITensor* const* inputs, int32_t nb, IPluginV2& plugin) noexcept {
         std::vector<int32_t> ids(nb > 0 ? nb : 0);
         for (int i = 0; i < nb; ++i) ids[i] = inputs[i]->id();

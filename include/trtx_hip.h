@@ -182,6 +182,33 @@ int32_t trtx_yolov7_head_decode_nhwc_f32(const void* const* heads, const int* ld
                                          const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
                                          void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /*
+ * Darknet YoloLayer (YOLOv3 / YOLOv3-tiny / YOLOv4) - the reference's yolov4/yololayer.cu:154-219 (Logist + CalDetection + forwardGpu; equal
+ * in yolov3 and yolov3-tiny).
+ *   inputs     n_levels (1..8) device pointers, fp32 [batch][3 * (5 + classes)][grid_h * grid_w]
+ *   grid_w/h   per level; anchors: n_levels x 6 floats (w0,h0,w1,h1,w2,h2)
+ *   output     device, fp32 [batch][1 + max_out * 7]: count (clamped to max_out), then Detection records (yolov4/yololayer.h:41-47)
+ *              cx, cy, w, h, det_confidence, class_id, class_confidence at float 1 + 7 * slot.  Nothing of a row is written behind its records.
+ * Logist(x) = 1./(1. + exp(-x)) with a float exp and a double add and divide; an anchor is dropped if max class prob < 0.1f or
+ * Logist(obj) < 0.1f; cx = (col + Logist(x)) * net_w / grid_w, w = exp(tw) * anchor_w; the two probabilities are stored apart.
+ * Canonical (level as passed, cell, anchor) order (the reference: atomicAdd race).
+ */
+size_t trtx_darknet_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels);
+int32_t trtx_darknet_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
+                            const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output, void* workspace,
+                            size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Fused Darknet head: trtx_darknet_decode on the detect convolutions' own NHWC output (heads, ld and refusals as
+ * trtx_yolov7_head_decode_nhwc); the same records in the same order.
+ */
+size_t trtx_darknet_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels);
+int32_t trtx_darknet_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                      const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                      void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* The same on the NHWC fp32 head tensors of an fp32 engine: ld in floats. */
+int32_t trtx_darknet_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                          const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                          void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
  * YOLOv9 YoloLayer - the reference's yolov9/plugin/yololayer.cu:133-197 (CalDetection + forwardGpu).
  *   inputs     3 device pointers (strides 8 / 16 / 32), fp32 [batch][4 + classes (+ 32 if is_segmentation)][(net_h / s) * (net_w / s)]
  *   output     device, fp32 [batch][1 + max_out * 38]: count (clamped to max_out), then Detection records of 38 floats
@@ -229,6 +256,11 @@ int32_t trtx_yolov9_nms(const float* decode_out, int batch, int max_out, float c
  * ([batch][1 + max_out * 6], the YOLOv7 engines' "prob").  Same outputs / workspace: keep_idx, keep_cnt, keep_det[batch][max_out][6]. */
 int32_t trtx_yolov7_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
                         int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/* Darknet host nms() on the GPU (yolov4/yolov4.cpp:81-124, equal in yolov3 and yolov3-tiny): trtx_yolov5_nms on records of 7 floats
+ * (det_confidence at float 4 is what is thresholded and sorted by, class_id at float 5).  keep_det[batch][max_out][6]: floats 0-5.
+ * The reference's thresholds are 0.5 / 0.4 (yolov3, yolov4) and 0.4 / 0.5 (yolov3-tiny). */
+int32_t trtx_darknet_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,
+                         int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 /*
  * Mask assembly of the seg programs: the coefficient x prototype loop of the host process_mask with its get_downscale_rect
  * (yolov5/src/postprocess.cpp:94-120; yolov8/yolov8_seg.cpp:17-53 and yolo11/yolo11_seg.cpp:17-53, one body), on the engine's
@@ -695,6 +727,9 @@ int32_t trtx_add_matrix_multiply(trtx_network* n, int32_t a, int32_t op_a, int32
 int32_t trtx_add_constant(trtx_network* n, const trtx_dims* dims, const float* values, int64_t count);
 int32_t trtx_add_reduce(trtx_network* n, int32_t input, int32_t op, uint32_t axes, int32_t keep_dims);
 int32_t trtx_add_identity(trtx_network* n, int32_t input);
+/* addPaddingNd (yolov3-tiny/yolov3-tiny.cpp:248: Pad(0,0;1,1) in front of the stride-1 max-pool): pre and post are DimsHW, the fill is zero.
+ * A negative (cropping) value is refused when the network is built, with the reason in the build's error. */
+int32_t trtx_add_padding(trtx_network* n, int32_t input, const trtx_dims* pre, const trtx_dims* post);
 /* addUnary (yolov13/src/block.cpp:389: the exp of AAttn's spelled-out softmax); op: a TRTX_UNARY_* / nvinfer1::UnaryOperation value */
 int32_t trtx_network_add_unary(trtx_network* n, int32_t input, int32_t op);
 /* addPluginV2: the runtime clones the plugin through vtbl->clone (as TensorRT does) */

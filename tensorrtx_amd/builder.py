@@ -181,6 +181,12 @@ class Network:
         self.L.trtx_network_add_unary.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
         return self._layer(self.L.trtx_network_add_unary(self.n, x, UNARY.get(op, op)), "add_unary")
 
+    def padding(self, x, pre=(0, 0), post=(0, 0)):
+        """IPaddingLayer (addPaddingNd), zero fill: pre = (top, left), post = (bottom, right); build() refuses a negative (cropping) value"""
+        a, b = _dims(pre), _dims(post)
+        self.L.trtx_add_padding.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        return self._layer(self.L.trtx_add_padding(self.n, x, ctypes.byref(a), ctypes.byref(b)), "add_padding")
+
     def slice_channels(self, x, start, size, chw):
         """ISliceLayer over the channel axis of a (C, H, W) tensor: channels [start, start + size) (block.cpp:134-149, the C2f split)"""
         c, h, w = chw

@@ -355,6 +355,37 @@ def yolov7_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.45, out=N
     return keep_idx, keep_cnt, keep_det
 
 
+DARKNET_DET_FLOATS = 7   # yolov4/yololayer.h:41-47: bbox[4], det_confidence, class_id, class_confidence
+
+
+def darknet_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, out=None):
+    """Darknet YoloLayerPlugin::enqueue replacement (yolov4/yololayer.cu:154-219; YOLOv3, YOLOv3-tiny and YOLOv4).
+    inputs: CUDA fp32 [B, 3*(5+classes), gh*gw] per level; grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1+max_out*7]"""
+    return _anchor_decode(DARKNET_DET_FLOATS, "trtx_darknet", inputs, classes, net_h, net_w, grids, anchors, max_out, out)
+
+
+def darknet_head_decode_workspace(batch, grids):
+    return _anchor_head_workspace("trtx_darknet", batch, grids)
+
+
+def darknet_head_decode_nhwc(heads, classes, net_h, net_w, grids, anchors, max_out=1000, out=None, ws=None, ld=None, n_levels=None,
+                             status_only=False):
+    """The fused Darknet head: yolov5_head_decode_nhwc with the Darknet arithmetic and 7-float records,
+    trtx_darknet_head_decode_nhwc{,_f32}.  -> [B, 1 + max_out * 7]."""
+    return _anchor_head(DARKNET_DET_FLOATS, "trtx_darknet", heads, classes, net_h, net_w, grids, anchors, max_out, out, ws, ld, n_levels,
+                        status_only)
+
+
+def darknet_nms(decode_out, max_out=1000, conf_thresh=0.5, nms_thresh=0.4, out=None, ws=None):
+    """Darknet nms() replacement (yolov4/yolov4.cpp:81-124) on 7-float records.  Returns keep_idx, keep_cnt, keep_det [B, max_out, 6]."""
+    L = lib()
+    B = decode_out.shape[0]
+    keep_idx, keep_cnt, keep_det, ws = _nms_buffers(B, max_out, 6, decode_out.device, out, ws)
+    check(L.trtx_darknet_nms(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), ctypes.c_float(nms_thresh), _p(keep_idx), _p(keep_cnt),
+                             _p(keep_det), _p(ws), ctypes.c_size_t(ws.numel()), _stream()), "trtx_darknet_nms")
+    return keep_idx, keep_cnt, keep_det
+
+
 def yolov9_decode(inputs, classes, net_h, net_w, max_out=1000, is_seg=False, out=None):
     """YOLOv9 YoloLayerPlugin::enqueue replacement (yolov9/plugin/yololayer.cu:124-197).
     inputs: three CUDA fp32 [B, 4 + classes (+ 32), gh * gw] (strides 8 / 16 / 32).  -> [B, 1 + max_out * 38]"""

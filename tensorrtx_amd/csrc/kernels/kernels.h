@@ -248,6 +248,9 @@ int32_t nhwc_pool(const void* in, void* out, int dtype, int op, int N, int H, in
                   int ld_out, int kh, int kw, int sh, int sw, int ph, int pw, int avg_exclusive, hipStream_t s);
 int32_t nhwc_resize_nearest(const void* in, void* out, int dtype, int N, int H, int W, int C, int ld_in, int Ho,
                             int Wo, int ld_out, hipStream_t s);
+// IPaddingLayer: the H x W image at (top, left) of a Ho x Wo image of zeros; Ho >= H + top, Wo >= W + left
+int32_t nhwc_zero_pad(const void* in, void* out, int dtype, int N, int H, int W, int C, int ld_in, int Ho, int Wo, int ld_out, int top,
+                      int left, hipStream_t s);
 int32_t nhwc_elementwise(const void* a, const void* b, void* out, int dtype, int op, long pixels, int C, int ld_a,
                          int ld_b, int ld_out, hipStream_t s);
 int32_t nhwc_activation(const void* in, void* out, int dtype, int act, float alpha, long pixels, int C, int ld_in,

@@ -232,6 +232,30 @@ __global__ void resize_nearest_kernel(const T* __restrict__ in, T* __restrict__ 
     }
 }
 
+// IPaddingLayer, zero fill: out[n][ho][wo] = in[n][ho - top][wo - left] inside the image, 0 around it.  The zeros are values a reader sees
+// (yolov3-tiny's stride-1 max-pool behind it takes a max against them), so every pixel of the output is written.
+template <typename T, int V>
+__global__ void zero_pad_kernel(const T* __restrict__ in, T* __restrict__ out, int N, int H, int W, int C, int ld_in, int Ho, int Wo,
+                                int ld_out, int top, int left) {
+    const int CV = C / V;
+    const long total = (long)N * Ho * Wo * CV;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int cv = (int)(i % CV);
+        long px = i / CV;
+        const int wo = (int)(px % Wo);
+        px /= Wo;
+        const int ho = (int)(px % Ho);
+        const long n = px / Ho;
+        const int hi = ho - top, wi = wo - left;
+        Pack<T, V> v;
+#pragma unroll
+        for (int e = 0; e < V; ++e) v.v[e] = (T)0;
+        if ((unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W)
+            v = *reinterpret_cast<const Pack<T, V>*>(in + ((n * H + hi) * W + wi) * ld_in + cv * V);
+        *reinterpret_cast<Pack<T, V>*>(out + ((n * Ho + ho) * Wo + wo) * ld_out + cv * V) = v;
+    }
+}
+
 template <typename T, int V>
 __global__ void elementwise_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, int op,
                                    long pixels, int C, int ld_a, int ld_b, int ld_out) {
@@ -565,6 +589,20 @@ int32_t nhwc_resize_nearest(const void* in, void* out, int dtype, int N, int H, 
     DISPATCH_T_V(dtype, vec, CALL);
 #undef CALL
     return check_launch("nhwc_resize_nearest");
+}
+
+int32_t nhwc_zero_pad(const void* in, void* out, int dtype, int N, int H, int W, int C, int ld_in, int Ho, int Wo, int ld_out, int top,
+                      int left, hipStream_t s) {
+    if (!in || !out || (dtype != DT_F16 && dtype != DT_F32) || N < 1 || H < 1 || W < 1 || C < 1 || ld_in < C || ld_out < C || top < 0 || left < 0 ||
+        Ho < H + top || Wo < W + left)
+        return TRTX_ERR_INVALID;
+    const bool vec = can_vec(dtype, C, {ld_in, ld_out}, {in, out});
+#define CALL(T, V)                                                                                                                  \
+    hipLaunchKernelGGL((zero_pad_kernel<T, V>), dim3(grid_for((long)N * Ho * Wo * (C / V))), dim3(kThreads), 0, s, static_cast<const T*>(in), \
+                       static_cast<T*>(out), N, H, W, C, ld_in, Ho, Wo, ld_out, top, left)
+    DISPATCH_T_V(dtype, vec, CALL);
+#undef CALL
+    return check_launch("nhwc_zero_pad");
 }
 
 int32_t nhwc_elementwise(const void* a, const void* b, void* out, int dtype, int op, long pixels, int C, int ld_a,

@@ -44,6 +44,7 @@ Options read_options() {
     o.gated_add = !env_is("TRTX_GATED_ADD", 0);
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);
     o.yolo7_head = !env_is("TRTX_YOLO7_HEAD", 0);
+    o.darknet_head = !env_is("TRTX_DARKNET_HEAD", 0);
     o.reorg_fold = !env_is("TRTX_REORG_FOLD", 0);
     o.spp_parallel_chain = !env_is("TRTX_SPP_PARALLEL_CHAIN", 0);
     o.yolo9_head = !env_is("TRTX_YOLO9_HEAD", 0);

@@ -13,6 +13,15 @@
 // As in yolo_decode.hip the reference's atomicAdd slot race is replaced by a canonical order — (level, cell, anchor)
 // ascending, handed out by a prefix scan — and out[b][0] is clamped to max_out.  Nothing of a row is written behind its records.
 //
+// The Darknet form (YOLOv3 / YOLOv3-tiny / YOLOv4, yolov4/yololayer.cu:154-199, equal in the other two) is a third record, kDet = 7:
+// bbox[4], det_confidence, class_id, class_confidence (yolov4/yololayer.h:41-47), and other arithmetic in front of the same compaction:
+//   Logist(x) = 1./(1. + exp(-x)): a float exp, the add and the divide in double, rounded to float;
+//   dropped if max_cls_prob < 0.1f || box_prob < 0.1f (two gates; a NaN objectness passes, max_cls_prob is never NaN);
+//   bbox = [(col + Logist(x)) * netW / gridW, (row + Logist(y)) * netH / gridH, exp(w) * anchor_w, exp(h) * anchor_h];
+//   det_confidence = box_prob, class_confidence = max_cls_prob: no product.
+// The reference scans the classes of every anchor and tests both gates after; here the objectness gate comes first and spares the scan,
+// which keeps the same anchors.  Pass 1 leaves max_cls_prob (>= 0.1 where kept) in the score plane; pass 2 takes box_prob from the input again.
+//
 // Both passes are templates on kDet.  The 38-float kernels take two more int arguments than the 6-float ones, info_len and
 // is_segmentation, each at the place it has always had in the argument list; the pack Seg (one int, or empty) spells that, and with it
 // both instantiations keep the instruction streams of the kernels they replace (profiles/anchor_units_isa.txt).
@@ -29,6 +38,7 @@
 namespace {
 
 using trtx::logist;
+using trtx::logist_darknet;
 
 constexpr int kMaxLevels = 8;
 constexpr int kAnchors = 3;   // kNumAnchor, yolov5/src/config.h:35 and yolov7/include/config.h
@@ -48,7 +58,7 @@ template <int kDet, typename... Seg>
 __global__ __launch_bounds__(kChunk) void anchor_score_kernel(LevelTable t, int classes, Seg... seg_len, int total_cells,
                                                               float* __restrict__ score, int* __restrict__ cls_out,
                                                               int* __restrict__ chunk_cnt, int n_chunks) {
-    static_assert(sizeof...(Seg) == (kDet == 38 ? 1 : 0) && (kDet == 38 || kDet == 6));
+    static_assert(sizeof...(Seg) == (kDet == 38 ? 1 : 0) && (kDet == 38 || kDet == 6 || kDet == 7));
     const int info_len = sizeof...(Seg) ? (0 + ... + seg_len) : 5 + classes;
     const int b = blockIdx.y;
     const int g = blockIdx.x * kChunk + threadIdx.x;
@@ -61,10 +71,25 @@ __global__ __launch_bounds__(kChunk) void anchor_score_kernel(LevelTable t, int 
 #pragma unroll
         for (int k = 0; k < kAnchors; ++k) {
             const float* a = cur + (size_t)k * info_len * cells;
-            const float box_prob = logist(a[(size_t)4 * cells]);
             float conf = -1.0f;
             int best_c = 0;
-            if (!(box_prob < 0.1f)) {  // "if (box_prob < kIgnoreThresh) continue;": NaN is kept, as there
+            if constexpr (kDet == 7) {
+                const float box_prob = logist_darknet(a[(size_t)4 * cells]);
+                if (!(box_prob < 0.1f)) {  // "|| box_prob < IGNORE_THRESH": NaN is kept, as there
+                    float best = 0.0f;
+                    for (int c = 0; c < classes; ++c) {
+                        const float p = logist_darknet(a[(size_t)(5 + c) * cells]);
+                        if (p > best) {
+                            best = p;
+                            best_c = c;
+                        }
+                    }
+                    if (!(best < 0.1f)) {  // "max_cls_prob < IGNORE_THRESH ||": best is in [0.1, 1] here, never NaN
+                        conf = best;
+                        ++nkeep;
+                    }
+                }
+            } else if (const float box_prob = logist(a[(size_t)4 * cells]); !(box_prob < 0.1f)) {  // "if (box_prob < kIgnoreThresh) continue;": NaN is kept, as there
                 float best = 0.0f;
                 for (int c = 0; c < classes; ++c) {
                     const float p = logist(a[(size_t)(5 + c) * cells]);
@@ -97,7 +122,7 @@ __global__ __launch_bounds__(kChunk) void anchor_emit_kernel(LevelTable t, int c
                                                              Seg... is_seg, const float* __restrict__ score, const int* __restrict__ cls_in,
                                                              const int* __restrict__ chunk_cnt, int n_chunks, int max_out, int out_elem,
                                                              float* __restrict__ output) {
-    static_assert(sizeof...(Seg) == (kDet == 38 ? 1 : 0) && (kDet == 38 || kDet == 6));
+    static_assert(sizeof...(Seg) == (kDet == 38 ? 1 : 0) && (kDet == 38 || kDet == 6 || kDet == 7));
     const int info_len = sizeof...(Seg) ? (0 + ... + seg_len) : 5 + classes;
     const int b = blockIdx.y;
     const int chunk = blockIdx.x;
@@ -149,20 +174,31 @@ __global__ __launch_bounds__(kChunk) void anchor_emit_kernel(LevelTable t, int c
             if (slot < max_out) {
                 const float* a = cur + (size_t)k * info_len * cells;
                 float* det = out + 1 + (size_t)slot * kDet;
-                // yolov5 yololayer.cu:199-206, yolov7 yololayer.cu:196-203, operation for operation
-                det[0] = (col - 0.5f + 2.0f * logist(a[0])) * net_w / gw;
-                det[1] = (row - 0.5f + 2.0f * logist(a[(size_t)cells])) * net_h / gh;
-                float bw = 2.0f * logist(a[(size_t)2 * cells]);
-                bw = bw * bw * t.anchors[l][2 * k];
-                float bh = 2.0f * logist(a[(size_t)3 * cells]);
-                bh = bh * bh * t.anchors[l][2 * k + 1];
-                det[2] = bw;
-                det[3] = bh;
-                det[4] = sc[k];
-                det[5] = (float)cls_in[((size_t)b * total_cells + g) * kAnchors + k];
-                if constexpr (kDet == 6 + 32) {   // only a record with room for them takes the mask coefficients
-                    if ((0 + ... + is_seg))
-                        for (int i = 0; i < 32; ++i) det[6 + i] = a[(size_t)(5 + classes + i) * cells];
+                if constexpr (kDet == 7) {
+                    // yolov4 yololayer.cu:187-197, operation for operation
+                    det[0] = (col + logist_darknet(a[0])) * net_w / gw;
+                    det[1] = (row + logist_darknet(a[(size_t)cells])) * net_h / gh;
+                    det[2] = expf(a[(size_t)2 * cells]) * t.anchors[l][2 * k];
+                    det[3] = expf(a[(size_t)3 * cells]) * t.anchors[l][2 * k + 1];
+                    det[4] = logist_darknet(a[(size_t)4 * cells]);
+                    det[5] = (float)cls_in[((size_t)b * total_cells + g) * kAnchors + k];
+                    det[6] = sc[k];
+                } else {
+                    // yolov5 yololayer.cu:199-206, yolov7 yololayer.cu:196-203, operation for operation
+                    det[0] = (col - 0.5f + 2.0f * logist(a[0])) * net_w / gw;
+                    det[1] = (row - 0.5f + 2.0f * logist(a[(size_t)cells])) * net_h / gh;
+                    float bw = 2.0f * logist(a[(size_t)2 * cells]);
+                    bw = bw * bw * t.anchors[l][2 * k];
+                    float bh = 2.0f * logist(a[(size_t)3 * cells]);
+                    bh = bh * bh * t.anchors[l][2 * k + 1];
+                    det[2] = bw;
+                    det[3] = bh;
+                    det[4] = sc[k];
+                    det[5] = (float)cls_in[((size_t)b * total_cells + g) * kAnchors + k];
+                    if constexpr (kDet == 6 + 32) {   // only a record with room for them takes the mask coefficients
+                        if ((0 + ... + is_seg))
+                            for (int i = 0; i < 32; ++i) det[6 + i] = a[(size_t)(5 + classes + i) * cells];
+                    }
                 }
             }
             ++slot;
@@ -184,7 +220,7 @@ size_t anchor_workspace(int batch, const int* grid_w, const int* grid_h, int n_l
     return 2 * trtx::align_up((size_t)batch * cells * kAnchors * 4, 256) + trtx::align_up((size_t)batch * n_chunks * sizeof(int), 256);
 }
 
-// kDet 38 with is_segmentation as passed, or kDet 6 with is_segmentation 0
+// kDet 38 with is_segmentation as passed, or kDet 6 or 7 with is_segmentation 0
 template <int kDet>
 int32_t anchor_decode(const char* entry, const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
                       const int* grid_w, const int* grid_h, const float* anchors, int max_out, int is_segmentation, float* output,
@@ -224,8 +260,8 @@ int32_t anchor_decode(const char* entry, const float* const* inputs, int n_level
         hipLaunchKernelGGL((anchor_emit_kernel<38, int>), grid, dim3(kChunk), 0, stream, t, classes, info_len, total_cells, net_w, net_h, is_segmentation,
                            score, cls, chunk_cnt, n_chunks, max_out, out_elem, output);
     } else {
-        hipLaunchKernelGGL(anchor_score_kernel<6>, grid, dim3(kChunk), 0, stream, t, classes, total_cells, score, cls, chunk_cnt, n_chunks);
-        hipLaunchKernelGGL(anchor_emit_kernel<6>, grid, dim3(kChunk), 0, stream, t, classes, total_cells, net_w, net_h, score, cls, chunk_cnt,
+        hipLaunchKernelGGL(anchor_score_kernel<kDet>, grid, dim3(kChunk), 0, stream, t, classes, total_cells, score, cls, chunk_cnt, n_chunks);
+        hipLaunchKernelGGL(anchor_emit_kernel<kDet>, grid, dim3(kChunk), 0, stream, t, classes, total_cells, net_w, net_h, score, cls, chunk_cnt,
                            n_chunks, max_out, out_elem, output);
     }
     return trtx::check_launch(entry);
@@ -241,6 +277,10 @@ extern "C" size_t trtx_yolov7_decode_workspace(int batch, const int* grid_w, con
     return anchor_workspace(batch, grid_w, grid_h, n_levels);
 }
 
+extern "C" size_t trtx_darknet_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels) {
+    return anchor_workspace(batch, grid_w, grid_h, n_levels);
+}
+
 extern "C" int32_t trtx_yolov5_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
                                       const int* grid_w, const int* grid_h, const float* anchors, int max_out, int is_segmentation,
                                       float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -252,5 +292,12 @@ extern "C" int32_t trtx_yolov7_decode(const float* const* inputs, int n_levels, 
                                       const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
                                       void* workspace, size_t workspace_bytes, hipStream_t stream) {
     return anchor_decode<6>("trtx_yolov7_decode", inputs, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, 0, output,
+                            workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_darknet_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
+                                       const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                       void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return anchor_decode<7>("trtx_darknet_decode", inputs, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, 0, output,
                             workspace, workspace_bytes, stream);
 }

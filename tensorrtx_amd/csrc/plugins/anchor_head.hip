@@ -9,6 +9,12 @@
 // floats, 38 for YOLOv5 (bbox[4], conf, class_id, mask[32]) and 6 for YOLOv7 (no mask).  Pass 1 never sees a record, so the two share its
 // kernels; pass 2 is one template on kDet.
 //
+// The Darknet form (YOLOv3 / YOLOv3-tiny / YOLOv4; kDet = 7: bbox[4], det_confidence, class_id, class_confidence) runs the same mapping
+// with anchor_decode.hip's Darknet arithmetic (yolov4/yololayer.cu:154-199): the double-divide Logist, a second gate on the class maximum
+// after the scan (so pass 1 counts what passed both, not the ballot), the class maximum alone in the score plane, and in pass 2
+// (col + Logist(x)), exp(w) * anchor and the objectness taken from the row again.  The double divide runs for anchors past the objectness
+// gate only.
+//
 // Mapping.  A pixel is one contiguous row (510 B of 512 for 80 classes in fp16), so lanes run along the CHANNEL axis:
 //   step 1  a wave takes 16 consecutive cells; lane 3 p + k loads the objectness of anchor k of cell p (48 loads in one instruction,
 //           one 64-B sector each) and the ballot of `!(box_prob < 0.1f)` is the wave's candidate mask.  A cell without a candidate is
@@ -32,6 +38,7 @@
 namespace {
 
 using trtx::logist;
+using trtx::logist_darknet;
 
 constexpr int kMaxLevels = 8;
 constexpr int kAnchors = 3;     // kNumAnchor, yolov5/src/config.h:35 and yolov7/include/config.h
@@ -64,12 +71,13 @@ struct Vec16<float> {
 };
 
 // One channel of the row into the per-anchor running maxima: the reference's `if (p > best)` in ascending class order.
+template <bool kDarknet>
 __device__ __forceinline__ void scan_channel(float v, int ch, int info, int nch, int abits, float (&best)[kAnchors], int (&bcls)[kAnchors]) {
     if (ch >= nch) return;   // padding
     const int k = ch >= 2 * info ? 2 : (ch >= info ? 1 : 0);
     const int j = ch - k * info;
     if (j < 5 || !((abits >> k) & 1)) return;
-    const float p = logist(v);
+    const float p = kDarknet ? logist_darknet(v) : logist(v);
 #pragma unroll
     for (int kk = 0; kk < kAnchors; ++kk)
         if (kk == k && p > best[kk]) {
@@ -79,7 +87,8 @@ __device__ __forceinline__ void scan_channel(float v, int ch, int info, int nch,
 }
 
 // Pass 1: conf / class of every (cell, anchor); -1 marks a dropped candidate.  score / cls: [batch][cells][3].
-template <typename T>
+// kDarknet: the Darknet Logist, the second gate, and the class maximum as the score.
+template <typename T, bool kDarknet = false>
 __global__ __launch_bounds__(kScoreBlock) void anchor_head_score_kernel(HeadTable t, int info, int total_cells, float* __restrict__ score,
                                                                        int* __restrict__ cls_out, int* __restrict__ chunk_cnt, int n_chunks) {
     using V = typename Vec16<T>::type;
@@ -99,7 +108,7 @@ __global__ __launch_bounds__(kScoreBlock) void anchor_head_score_kernel(HeadTabl
         const int l = trtx::find_level(t.cell_off, t.n_levels, g);
         const int cells = t.cell_off[l + 1] - t.cell_off[l];
         const T* row = static_cast<const T*>(t.in[l]) + ((size_t)b * cells + (g - t.cell_off[l])) * t.ld[l];
-        box_prob = logist((float)row[k * info + 4]);
+        box_prob = kDarknet ? logist_darknet((float)row[k * info + 4]) : logist((float)row[k * info + 4]);
         pass = !(box_prob < 0.1f);  // "if (box_prob < kIgnoreThresh) continue;": NaN is kept, as there
         if (!pass) {
             const size_t o = ((size_t)b * total_cells + g) * kAnchors + k;
@@ -111,6 +120,7 @@ __global__ __launch_bounds__(kScoreBlock) void anchor_head_score_kernel(HeadTabl
 
     // ---- step 2: the class scan of the cells that hold a candidate, two per iteration (one per half-wave)
     const int half = lane >> 5, sub = lane & 31;
+    int nkept = 0;     // kDarknet: anchors of this wave past both gates
     unsigned pm = 0;   // cells with a candidate
     for (int q = 0; q < kWaveCells; ++q)
         if ((mask >> (kAnchors * q)) & 7ull) pm |= 1u << q;
@@ -134,10 +144,10 @@ __global__ __launch_bounds__(kScoreBlock) void anchor_head_score_kernel(HeadTabl
                 for (int c0 = sub * VN; c0 < nch; c0 += 32 * VN) {
                     const V v = *reinterpret_cast<const V*>(row + c0);
 #pragma unroll
-                    for (int i = 0; i < VN; ++i) scan_channel((float)v[i], c0 + i, info, nch, abits, best, bcls);
+                    for (int i = 0; i < VN; ++i) scan_channel<kDarknet>((float)v[i], c0 + i, info, nch, abits, best, bcls);
                 }
             } else {
-                for (int ch = sub; ch < nch; ch += 32) scan_channel((float)row[ch], ch, info, nch, abits, best, bcls);
+                for (int ch = sub; ch < nch; ch += 32) scan_channel<kDarknet>((float)row[ch], ch, info, nch, abits, best, bcls);
             }
         }
         // join over the half-wave; every lane of the wave is here (p0, p1 and the masks are wave-uniform)
@@ -155,30 +165,44 @@ __global__ __launch_bounds__(kScoreBlock) void anchor_head_score_kernel(HeadTabl
                 }
             }
         }
-        // lane kk of each half writes anchor kk of its cell; box_prob sits in lane 3 px + kk
-        const int src = px >= 0 && sub < kAnchors ? kAnchors * px + sub : 0;
-        const float bp = __shfl(box_prob, src);
-        if (px >= 0 && sub < kAnchors && ((abits >> sub) & 1)) {
+        // lane kk of each half writes anchor kk of its cell
+        const bool scanned = px >= 0 && sub < kAnchors && ((abits >> sub) & 1);
+        if constexpr (kDarknet) {
+            // "if (max_cls_prob < IGNORE_THRESH || box_prob < IGNORE_THRESH) continue;": the second half was the ballot
             const float bst = sub == 0 ? best[0] : (sub == 1 ? best[1] : best[2]);
             const int bc = sub == 0 ? bcls[0] : (sub == 1 ? bcls[1] : bcls[2]);
-            float conf = bp * bst;
-            // conf >= 0 marks "kept" in pass 2; a NaN product (NaN logits) must stay a kept record as in the reference
-            if (!(conf >= 0.0f)) conf = __builtin_nanf("");
-            const size_t o = ((size_t)b * total_cells + g0 + px) * kAnchors + sub;
-            score[o] = conf;
-            cls_out[o] = bc;
+            const bool keep = scanned && !(bst < 0.1f);
+            if (scanned) {
+                const size_t o = ((size_t)b * total_cells + g0 + px) * kAnchors + sub;
+                score[o] = keep ? bst : -1.0f;   // bst is in [0.1, 1] where kept, never NaN
+                cls_out[o] = bc;
+            }
+            nkept += __popcll(__ballot(keep));   // every lane of the wave is here
+        } else {
+            // box_prob sits in lane 3 px + kk; every lane of the wave takes part in the shuffle
+            const float bp = __shfl(box_prob, px >= 0 && sub < kAnchors ? kAnchors * px + sub : 0);
+            if (scanned) {
+                const float bst = sub == 0 ? best[0] : (sub == 1 ? best[1] : best[2]);
+                const int bc = sub == 0 ? bcls[0] : (sub == 1 ? bcls[1] : bcls[2]);
+                float conf = bp * bst;
+                // conf >= 0 marks "kept" in pass 2; a NaN product (NaN logits) must stay a kept record as in the reference
+                if (!(conf >= 0.0f)) conf = __builtin_nanf("");
+                const size_t o = ((size_t)b * total_cells + g0 + px) * kAnchors + sub;
+                score[o] = conf;
+                cls_out[o] = bc;
+            }
         }
     }
 
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    trtx::workgroup_count(&s_cnt, lane == 0 ? __popcll(mask) : 0);
+    trtx::workgroup_count(&s_cnt, lane == 0 ? (kDarknet ? nkept : __popcll(mask)) : 0);
     if (threadIdx.x == 0 && s_cnt) atomicAdd(&chunk_cnt[b * n_chunks + (blockIdx.x * kBlockCells) / kChunk], s_cnt);
 }
 
 // Pass 2: anchor_emit_kernel's ordered compaction, one thread per cell (0..3 records each); the box values come from the cell's row.
-// kDet: floats per record, 38 (YOLOv5) or 6 (YOLOv7); floats 0 .. 5 are written.
+// kDet: floats per record, 38 (YOLOv5) or 6 (YOLOv7), of which floats 0 .. 5 are written, or 7 (Darknet), all written.
 template <typename T, int kDet>
 __global__ __launch_bounds__(kChunk) void anchor_head_emit_kernel(HeadTable t, int info, int total_cells, int net_w, int net_h,
                                                                   const float* __restrict__ score, const int* __restrict__ cls_in,
@@ -234,17 +258,28 @@ __global__ __launch_bounds__(kChunk) void anchor_head_emit_kernel(HeadTable t, i
             if (slot < max_out) {
                 const T* a = cur + k * info;
                 float* det = out + 1 + (size_t)slot * kDet;
-                // yolov5 yololayer.cu:199-206, yolov7 yololayer.cu:196-203, operation for operation
-                det[0] = (col - 0.5f + 2.0f * logist((float)a[0])) * net_w / gw;
-                det[1] = (row - 0.5f + 2.0f * logist((float)a[1])) * net_h / gh;
-                float bw = 2.0f * logist((float)a[2]);
-                bw = bw * bw * t.anchors[l][2 * k];
-                float bh = 2.0f * logist((float)a[3]);
-                bh = bh * bh * t.anchors[l][2 * k + 1];
-                det[2] = bw;
-                det[3] = bh;
-                det[4] = sc[k];
-                det[5] = (float)cls_in[((size_t)b * total_cells + g) * kAnchors + k];
+                if constexpr (kDet == 7) {
+                    // yolov4 yololayer.cu:187-197, operation for operation
+                    det[0] = (col + logist_darknet((float)a[0])) * net_w / gw;
+                    det[1] = (row + logist_darknet((float)a[1])) * net_h / gh;
+                    det[2] = expf((float)a[2]) * t.anchors[l][2 * k];
+                    det[3] = expf((float)a[3]) * t.anchors[l][2 * k + 1];
+                    det[4] = logist_darknet((float)a[4]);
+                    det[5] = (float)cls_in[((size_t)b * total_cells + g) * kAnchors + k];
+                    det[6] = sc[k];
+                } else {
+                    // yolov5 yololayer.cu:199-206, yolov7 yololayer.cu:196-203, operation for operation
+                    det[0] = (col - 0.5f + 2.0f * logist((float)a[0])) * net_w / gw;
+                    det[1] = (row - 0.5f + 2.0f * logist((float)a[1])) * net_h / gh;
+                    float bw = 2.0f * logist((float)a[2]);
+                    bw = bw * bw * t.anchors[l][2 * k];
+                    float bh = 2.0f * logist((float)a[3]);
+                    bh = bh * bh * t.anchors[l][2 * k + 1];
+                    det[2] = bw;
+                    det[3] = bh;
+                    det[4] = sc[k];
+                    det[5] = (float)cls_in[((size_t)b * total_cells + g) * kAnchors + k];
+                }
             }
             ++slot;
         }
@@ -298,11 +333,11 @@ int32_t head_decode(const char* entry, const void* const* heads, const int* ld, 
     const int out_elem = 1 + max_out * kDet;
     const dim3 sgrid((total_cells + kBlockCells - 1) / kBlockCells, batch), egrid(n_chunks, batch);
     if (elem_bytes == 2) {
-        hipLaunchKernelGGL(anchor_head_score_kernel<_Float16>, sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
+        hipLaunchKernelGGL((anchor_head_score_kernel<_Float16, kDet == 7>), sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
         hipLaunchKernelGGL((anchor_head_emit_kernel<_Float16, kDet>), egrid, dim3(kChunk), 0, stream, t, info, total_cells, net_w, net_h, score, cls, chunk_cnt,
                            n_chunks, max_out, out_elem, output);
     } else {
-        hipLaunchKernelGGL(anchor_head_score_kernel<float>, sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
+        hipLaunchKernelGGL((anchor_head_score_kernel<float, kDet == 7>), sgrid, dim3(kScoreBlock), 0, stream, t, info, total_cells, score, cls, chunk_cnt, n_chunks);
         hipLaunchKernelGGL((anchor_head_emit_kernel<float, kDet>), egrid, dim3(kChunk), 0, stream, t, info, total_cells, net_w, net_h, score, cls, chunk_cnt,
                            n_chunks, max_out, out_elem, output);
     }
@@ -317,6 +352,10 @@ extern "C" size_t trtx_yolov5_head_decode_workspace(int batch, const int* grid_w
 }
 
 extern "C" size_t trtx_yolov7_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels) {
+    return head_workspace(batch, grid_w, grid_h, n_levels);
+}
+
+extern "C" size_t trtx_darknet_head_decode_workspace(int batch, const int* grid_w, const int* grid_h, int n_levels) {
     return head_workspace(batch, grid_w, grid_h, n_levels);
 }
 
@@ -346,4 +385,18 @@ extern "C" int32_t trtx_yolov7_head_decode_nhwc_f32(const void* const* heads, co
                                                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
     return head_decode<6>("trtx_yolov7_head_decode_nhwc", heads, ld, 4, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
                             workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_darknet_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                 const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return head_decode<7>("trtx_darknet_head_decode_nhwc", heads, ld, 2, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_darknet_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                     const int* grid_w, const int* grid_h, const float* anchors, int max_out, float* output,
+                                                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return head_decode<7>("trtx_darknet_head_decode_nhwc", heads, ld, 4, n_levels, batch, classes, net_h, net_w, grid_w, grid_h, anchors, max_out, output, workspace,
+                           workspace_bytes, stream);
 }

@@ -155,35 +155,70 @@ void yolo_fill(trtx_plugin_vtbl* v, YoloLayer* y) {
 //   YOLOv7 (yolov7/plugin/yololayer.{h,cu}): the same without the segmentation flag and with records of 6 floats.  "netinfo" =
 //     int32[4] {classes, W, H, maxOut} - exactly four, five and more are YOLOv5's - and "kernels" (yolov7/src/block.cpp:220-255); the
 //     blob has no isSeg byte, 24 + 32 n bytes (yololayer.cu:40-78).
+//   Darknet (yolov3, yolov3-tiny, yolov4 / yololayer.{h,cu}): the creator takes NO fields and the reference compiles classes, input size,
+//     the YoloKernel table and maxOut = 1000 in (yolov4/yololayer.h:10-38, yololayer.cu:9-27, 258-263).  Here the plugin learns them from
+//     its inputs (darknet_geometry below) when the layer is added and again in configurePlugin; records of 7 floats.  The blob is the
+//     reference's - int classCount, threadCount, kernelCount, YoloKernel[n] (yololayer.cu:58-75) - plus int netW, netH behind it, as
+//     Decode_TRT extends an empty blob: 20 + 32 n bytes, n = 0 for a plugin that has not seen its inputs.
 struct AnchorKernel {
     int width, height;
     float anchors[6];
 };
+enum AnchorForm { FORM_V5 = 0, FORM_V7 = 1, FORM_DARKNET = 2 };
+constexpr int kDarknetMaxOut = 1000;   // MAX_OUTPUT_BBOX_COUNT, yololayer.h:12 of all three
 struct AnchorLayer {
-    bool v7 = false;   // the YOLOv7 form; never serialised, the blob's length tells
+    int form = FORM_V5;   // never serialised, the blob's length tells
     int class_count = 80, thread_count = 256, net_w = 640, net_h = 640, max_out = 1000;
     bool seg = false;  // YOLOv5 only
     std::vector<AnchorKernel> kernels;
 
-    int det_floats() const { return v7 ? 6 : 38; }
+    int det_floats() const { return form == FORM_DARKNET ? 7 : (form == FORM_V7 ? 6 : 38); }
     std::vector<uint8_t> blob() const {
         std::vector<uint8_t> b;
         put(b, class_count);
         put(b, thread_count);
         put(b, (int)kernels.size());
+        if (form == FORM_DARKNET) {
+            for (const auto& k : kernels) put(b, k);
+            put(b, net_w);
+            put(b, net_h);
+            return b;
+        }
         put(b, net_w);
         put(b, net_h);
         put(b, max_out);
-        if (!v7) put(b, seg);
+        if (form == FORM_V5) put(b, seg);
         for (const auto& k : kernels) put(b, k);
         return b;
+    }
+    // the Darknet blob, by its exact length: 20 + 32 n bytes, n = 0 .. 8
+    static AnchorLayer* from_darknet_blob(const void* data, size_t len) {
+        const uint8_t* p = static_cast<const uint8_t*>(data);
+        const uint8_t* end = p + len;
+        auto* y = new AnchorLayer();
+        y->form = FORM_DARKNET;
+        y->max_out = kDarknetMaxOut;
+        int nk = 0;
+        bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, nk) && nk >= 0 && nk <= 8 &&
+                  (size_t)(end - p) == (size_t)nk * sizeof(AnchorKernel) + 2 * sizeof(int);
+        for (int i = 0; ok && i < nk; ++i) {
+            AnchorKernel k{};
+            ok = get(p, end, k) && k.width > 0 && k.height > 0;
+            y->kernels.push_back(k);
+        }
+        ok = ok && get(p, end, y->net_w) && get(p, end, y->net_h) && y->class_count >= 1 && (nk == 0 || (y->net_w >= 1 && y->net_h >= 1));
+        if (!ok) {
+            delete y;
+            return nullptr;
+        }
+        return y;
     }
     // accepted by its exact length and a kernelCount that agrees with it only
     static AnchorLayer* from_blob(const void* data, size_t len, bool v7) {
         const uint8_t* p = static_cast<const uint8_t*>(data);
         const uint8_t* end = p + len;
         auto* y = new AnchorLayer();
-        y->v7 = v7;
+        y->form = v7 ? FORM_V7 : FORM_V5;
         int nk = 0;
         bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, nk) && get(p, end, y->net_w) &&
                   get(p, end, y->net_h) && get(p, end, y->max_out) && (v7 || get(p, end, y->seg)) && nk >= 1 && nk <= 8 &&
@@ -208,9 +243,44 @@ struct AnchorLayer {
     }
 };
 
+// What the Darknet form reads off its inputs (CHW each, 3 * (5 + classes) channels): the family and with it the anchor table of that
+// family's yololayer.h, the grids, and the network size = grid x stride.
+//   two inputs, strides 32 and 16 (coarsest first): yolov3-tiny      {81,82, 135,169, 344,319}, {23,27, 37,58, 81,82}
+//   three inputs, strides 32, 16, 8 (coarsest first): yolov3         {116,90, 156,198, 373,326}, {30,61, 62,45, 59,119}, {10,13, 16,30, 33,23}
+//   three inputs, strides 8, 16, 32 (finest first): yolov4           {12,16, 19,36, 40,28}, {36,75, 76,55, 72,146}, {142,110, 192,243, 459,401}
+// Anything else is refused.
+bool darknet_geometry(const trtx_dims* in, int nb_in, AnchorLayer* y) {
+    static const float kTiny[2][6] = {{81, 82, 135, 169, 344, 319}, {23, 27, 37, 58, 81, 82}};
+    static const float kV3[3][6] = {{116, 90, 156, 198, 373, 326}, {30, 61, 62, 45, 59, 119}, {10, 13, 16, 30, 33, 23}};
+    static const float kV4[3][6] = {{12, 16, 19, 36, 40, 28}, {36, 75, 76, 55, 72, 146}, {142, 110, 192, 243, 459, 401}};
+    if (!in || (nb_in != 2 && nb_in != 3)) return false;
+    for (int i = 0; i < nb_in; ++i)
+        if (in[i].nb != 3 || in[i].d[0] != in[0].d[0] || in[i].d[1] < 1 || in[i].d[2] < 1) return false;
+    const int64_t ch = in[0].d[0];
+    if (ch % 3 || ch / 3 - 5 < 1) return false;
+    auto ratio = [&](int a, int b, int r) { return in[a].d[1] == r * in[b].d[1] && in[a].d[2] == r * in[b].d[2]; };
+    const float(*table)[6] = nullptr;
+    int coarsest = 0;
+    if (nb_in == 2 && ratio(1, 0, 2)) table = kTiny;
+    else if (nb_in == 3 && ratio(1, 0, 2) && ratio(2, 0, 4)) table = kV3;
+    else if (nb_in == 3 && ratio(1, 2, 2) && ratio(0, 2, 4)) table = kV4, coarsest = 2;
+    if (!table || in[coarsest].d[1] * 32 > INT32_MAX || in[coarsest].d[2] * 32 > INT32_MAX) return false;
+    y->class_count = (int)(ch / 3 - 5);
+    y->net_h = (int)in[coarsest].d[1] * 32;
+    y->net_w = (int)in[coarsest].d[2] * 32;
+    y->kernels.resize(nb_in);
+    for (int i = 0; i < nb_in; ++i) {
+        y->kernels[i].width = (int)in[i].d[2];
+        y->kernels[i].height = (int)in[i].d[1];
+        memcpy(y->kernels[i].anchors, table[i], sizeof(y->kernels[i].anchors));
+    }
+    return true;
+}
+
 void anchor_fill(trtx_plugin_vtbl* v, AnchorLayer* y);
-int32_t anchor_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
+int32_t anchor_output_dims(void* s, int32_t, const trtx_dims* in, int32_t nb_in, trtx_dims* out) {
     auto* y = static_cast<AnchorLayer*>(s);
+    if (y->form == FORM_DARKNET && !darknet_geometry(in, nb_in, y)) return 1;
     out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yolov5 yololayer.cu:101-105, yolov7 yololayer.cu:90-94
     out->d[0] = (int64_t)y->max_out * y->det_floats() + 1;
     out->d[1] = 1;
@@ -219,6 +289,7 @@ int32_t anchor_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dim
 }
 int32_t anchor_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
     auto* y = static_cast<AnchorLayer*>(s);
+    if (y->form == FORM_DARKNET) return darknet_geometry(in, nb_in, y) ? 0 : 1;
     if (nb_in != (int)y->kernels.size()) return 1;
     const int info = 5 + y->class_count + (y->seg ? 32 : 0);
     for (int i = 0; i < nb_in; ++i) {
@@ -234,7 +305,7 @@ size_t anchor_workspace(void* s, int32_t max_batch) {
     std::vector<int> gw, gh;
     std::vector<float> an;
     y->geometry(&gw, &gh, &an);
-    return trtx_yolov5_decode_workspace(max_batch, gw.data(), gh.data(), (int)gw.size());   // the same for both forms
+    return trtx_yolov5_decode_workspace(max_batch, gw.data(), gh.data(), (int)gw.size());   // the same for the three forms
 }
 int32_t anchor_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
     auto* y = static_cast<AnchorLayer*>(s);
@@ -244,7 +315,10 @@ int32_t anchor_enqueue(void* s, int32_t batch, const void* const* inputs, void* 
     const size_t ws_bytes = trtx_yolov5_decode_workspace(batch, gw.data(), gh.data(), (int)gw.size());
     const auto* in = reinterpret_cast<const float* const*>(inputs);
     float* out = static_cast<float*>(outputs[0]);
-    if (y->v7)
+    if (y->form == FORM_DARKNET)
+        return trtx_darknet_decode(in, (int)gw.size(), batch, y->class_count, y->net_h, y->net_w, gw.data(), gh.data(), an.data(), y->max_out, out,
+                                   ws, ws_bytes, stream);
+    if (y->form == FORM_V7)
         return trtx_yolov7_decode(in, (int)gw.size(), batch, y->class_count, y->net_h, y->net_w, gw.data(), gh.data(), an.data(), y->max_out, out,
                                   ws, ws_bytes, stream);
     return trtx_yolov5_decode(in, (int)gw.size(), batch, y->class_count, y->net_h, y->net_w, gw.data(), gh.data(), an.data(), y->max_out,
@@ -283,7 +357,7 @@ int32_t anchor_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
     const int* ni = static_cast<const int*>(f[0].data);
     if (v7 && (ni[0] < 1 || ni[1] < 1 || ni[2] < 1 || ni[3] < 1)) return 1;
     auto* y = new AnchorLayer();
-    y->v7 = v7;
+    y->form = v7 ? FORM_V7 : FORM_V5;
     y->class_count = ni[0];
     y->net_w = ni[1];
     y->net_h = ni[2];
@@ -399,6 +473,15 @@ int32_t yolo9_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
 
 // creator: one field "combinedInfo" = int32[9 + nStrides] (yolov8/src/block.cpp:267-293, yololayer.cu:339-360)
 int32_t yolo_create(void*, const char*, const trtx_plugin_field* f, int32_t nb, trtx_plugin_vtbl* out) {
+    // no fields at all: the Darknet form (yolov4/yololayer.cu:258-263 ignores its field collection, and the creator's own is empty)
+    if (nb == 0) {
+        auto* y = new AnchorLayer();
+        y->form = FORM_DARKNET;
+        y->max_out = kDarknetMaxOut;
+        y->kernels.clear();
+        anchor_fill(out, y);
+        return 0;
+    }
     // the anchor-based plugin shares the registered name: told apart by its two fields "netinfo" + "kernels"
     // (four netinfo ints: YOLOv7's, which has no is_segmentation; five and more: YOLOv5's; fewer are refused by either)
     if (nb == 2 && f && f[0].name && f[1].name && !strcmp(f[0].name, "netinfo") && !strcmp(f[1].name, "kernels"))
@@ -441,8 +524,14 @@ int32_t yolo_deserialize(void*, const char*, const void* data, size_t len, trtx_
     }
     // ... and last the YOLOv7 blob, 24 + 32 n bytes: no earlier parser takes that length (35 + 4 n, 25 + 32 n, 21)
     AnchorLayer* y7 = AnchorLayer::from_blob(data, len, true);
-    if (!y7) return 1;
-    anchor_fill(out, y7);
+    if (y7) {
+        anchor_fill(out, y7);
+        return 0;
+    }
+    // ... and the Darknet blob, 20 + 32 n bytes: even, so none of 35 + 4 n, 25 + 32 n and 21, and 4 short of YOLOv7's 24 + 32 n
+    AnchorLayer* yd = AnchorLayer::from_darknet_blob(data, len);
+    if (!yd) return 1;
+    anchor_fill(out, yd);
     return 0;
 }
 const char* yolo_creator_name(void*) { return "YoloLayer_TRT"; }
@@ -629,10 +718,10 @@ bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out) {
     return true;
 }
 
-static bool anchor_params(const trtx_plugin_vtbl& v, bool v7, Yolo5LayerParams* out) {
+static bool anchor_params(const trtx_plugin_vtbl& v, int form, Yolo5LayerParams* out) {
     if (v.enqueue != anchor_enqueue || !v.self) return false;
     const auto* y = static_cast<const AnchorLayer*>(v.self);
-    if (y->v7 != v7) return false;
+    if (y->form != form) return false;
     out->classes = y->class_count;
     out->net_w = y->net_w;
     out->net_h = y->net_h;
@@ -644,8 +733,10 @@ static bool anchor_params(const trtx_plugin_vtbl& v, bool v7, Yolo5LayerParams* 
     y->geometry(&out->grid_w, &out->grid_h, &out->anchors);
     return true;
 }
-bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, false, out); }
-bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, true, out); }
+bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, FORM_V5, out); }
+bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, FORM_V7, out); }
+// the Darknet form has them once it has seen its inputs (the layer's shape inference shows them to it): false before
+bool builtin_darknet_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out) { return anchor_params(v, FORM_DARKNET, out) && !out->grid_w.empty(); }
 
 bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
     if (v.enqueue != yolo9_enqueue || !v.self) return false;

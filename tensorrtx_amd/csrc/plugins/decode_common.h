@@ -15,6 +15,12 @@ __device__ __forceinline__ float logist(float x) {
     return 1.0f / (1.0f + expf(-x));
 }
 
+// The Darknet plugins' Logist (yolov4/yololayer.cu:154, equal in yolov3 and yolov3-tiny): "1./(1. + exp(-data))" on a float is a float
+// exp, then the add and the divide in double, rounded to float on return.
+__device__ __forceinline__ float logist_darknet(float x) {
+    return (float)(1.0 / (1.0 + (double)expf(-x)));
+}
+
 // level of global cell g; cell_off holds the cumulative cell offsets of the levels (cell_off[n_levels] = all cells)
 template <int N>
 __device__ __forceinline__ int find_level(const int (&cell_off)[N], int n_levels, int g) {

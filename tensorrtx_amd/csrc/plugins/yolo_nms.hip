@@ -521,6 +521,14 @@ extern "C" int32_t trtx_yolov7_nms(const float* decode_out, int batch, int max_o
                       stream, "trtx_yolov7_nms");
 }
 
+// yolov4/yolov4.cpp:81-124 (equal in yolov3 and yolov3-tiny): the YOLOv5 iou and nms() on Detection records of 7 floats
+extern "C" int32_t trtx_darknet_nms(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh,
+                                    int32_t* keep_idx, int32_t* keep_cnt, float* keep_det, void* workspace, size_t workspace_bytes,
+                                    hipStream_t stream) {
+    return run_nms<1>(decode_out, batch, max_out, 7, conf_thresh, nms_thresh, keep_idx, keep_cnt, keep_det, workspace, workspace_bytes,
+                      stream, "trtx_darknet_nms");
+}
+
 // nms_obb / batch_nms_obb (yolov8/src/postprocess.cpp:357-393): oriented boxes, ProbIoU.  keep_det: [batch][max_out][7] =
 // cx, cy, w, h, conf, class, angle.
 extern "C" int32_t trtx_yolo_nms_obb(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh, int32_t* keep_idx,

@@ -244,6 +244,15 @@ extern "C" int32_t trtx_network_add_unary(trtx_network* n, int32_t input, int32_
     l.op = op;
     return n->net.add_layer(std::move(l));
 }
+extern "C" int32_t trtx_add_padding(trtx_network* n, int32_t input, const trtx_dims* pre, const trtx_dims* post) {
+    if (!valid_tensor(n, input) || !pre || !post) return -1;
+    LayerDef l;
+    l.kind = L_PADDING;
+    l.inputs = {input};
+    l.start = from_c(*pre);
+    l.size = from_c(*post);
+    return n->net.add_layer(std::move(l));   // a negative (cropping) pad leaves the output shapeless: validate() refuses it at build time
+}
 extern "C" int32_t trtx_add_plugin_v2(trtx_network* n, const int32_t* inputs, int32_t nb, const trtx_plugin_vtbl* plugin) {
     if (!n || !inputs || nb < 1 || !plugin || !plugin->clone) return -1;
     trtx_plugin_vtbl copy{};

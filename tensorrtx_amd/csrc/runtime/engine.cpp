@@ -162,7 +162,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
         int32_t st = TRTX_OK;
-        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_ROI_ALIGN);
+        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
@@ -436,8 +436,12 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
                 break;
             }
+            case OP_PAD_NHWC:
+                st = nhwc_zero_pad(R.ptr(op.in[0]), R.ptr(op.out[0]), op.dtype, nb(t0), t0.H, t0.W, t0.C, t0.ld, to.H, to.W, to.ld, op.i[0], op.i[1], stream);
+                break;
             case OP_YOLO5_HEAD:
-            case OP_YOLO7_HEAD: {
+            case OP_YOLO7_HEAD:
+            case OP_DARKNET_HEAD: {
                 const int nl = op.i[4];
                 const void* heads[8];
                 int lds[8], gw[8], gh[8];
@@ -449,8 +453,9 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     gh[k] = op.iv[2 * k + 1];
                 }
                 const bool f32 = t0.dtype == DT_F32;
-                const auto decode = op.kind == OP_YOLO7_HEAD ? (f32 ? trtx_yolov7_head_decode_nhwc_f32 : trtx_yolov7_head_decode_nhwc)
-                                                             : (f32 ? trtx_yolov5_head_decode_nhwc_f32 : trtx_yolov5_head_decode_nhwc);
+                const auto decode = op.kind == OP_DARKNET_HEAD ? (f32 ? trtx_darknet_head_decode_nhwc_f32 : trtx_darknet_head_decode_nhwc)
+                                    : op.kind == OP_YOLO7_HEAD ? (f32 ? trtx_yolov7_head_decode_nhwc_f32 : trtx_yolov7_head_decode_nhwc)
+                                                               : (f32 ? trtx_yolov5_head_decode_nhwc_f32 : trtx_yolov5_head_decode_nhwc);
                 st = decode(
                         heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], gw, gh, op.fv.data(), op.i[3],
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);

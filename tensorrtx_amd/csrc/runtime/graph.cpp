@@ -158,6 +158,20 @@ bool Network::infer(int li) {
             if (l.op < TRTX_UNARY_EXP || l.op > TRTX_UNARY_LAST) return fail(this, l.name + ": not a unary operation (" + std::to_string(l.op) + ")");
             set_out(0, in(0));
             return true;
+        case L_PADDING: {
+            const Dims& x = in(0);
+            if (x.nb < 3) return fail(this, l.name + ": padding needs a CHW tensor");
+            if (l.start.nb != 2 || l.size.nb != 2) return fail(this, l.name + ": pre- and post-padding must be DimsHW");
+            Dims o = x;
+            for (int a = 0; a < 2; ++a) {
+                if (l.start.d[a] < 0 || l.size.d[a] < 0)
+                    return fail(this, l.name + ": negative (cropping) padding is not implemented (pre " + std::to_string(l.start.d[0]) + "," + std::to_string(l.start.d[1]) +
+                                          ", post " + std::to_string(l.size.d[0]) + "," + std::to_string(l.size.d[1]) + ")");
+                o.d[x.nb - 2 + a] = x.d[x.nb - 2 + a] + l.start.d[a] + l.size.d[a];
+            }
+            set_out(0, o);
+            return true;
+        }
         case L_SCALE: {
             const Dims& x = in(0);
             const int64_t c = l.op == TRTX_SCALE_CHANNEL ? x.d[chan_axis(*this, x)] : (l.op == TRTX_SCALE_UNIFORM ? 1 : x.volume());

@@ -49,6 +49,7 @@ enum LayerKind : int32_t {
     L_PLUGIN = 16,
     L_IDENTITY = 17,
     L_UNARY = 18,  // appended: plans written before it deserialize unchanged
+    L_PADDING = 19,  // IPaddingLayer, zero fill; appended likewise.  `start` = pre-padding (top, left), `size` = post-padding (bottom, right), both nb = 2
 };
 
 struct PluginHolder;  // runtime/plugin.h
@@ -86,7 +87,7 @@ struct LayerDef {
     Dims reshape;                             // shuffle (nb = 0 -> none)
     int32_t perm1[8] = {0, 1, 2, 3, 4, 5, 6, 7};
     int32_t perm2[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-    Dims start, size, step;                   // slice
+    Dims start, size, step;                   // slice | padding: start = pre-padding, size = post-padding (h, w)
     float scales[8] = {1, 1, 1, 1, 1, 1, 1, 1};  // resize
     int32_t nb_scales = 0;
     Dims out_dims;                            // resize explicit output dims / constant dims

@@ -279,7 +279,8 @@ struct Lowerer {
             ins.push_back(pt_of[t]);
         }
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
-        POp& op = add_op(f.v7 ? OP_YOLO7_HEAD : OP_YOLO5_HEAD, l.name + (f.v7 ? " [fused anchor decode, 6-float records]" : " [fused anchor decode]"), ins, {out});
+        POp& op = add_op(f.darknet ? OP_DARKNET_HEAD : (f.v7 ? OP_YOLO7_HEAD : OP_YOLO5_HEAD),
+                         l.name + (f.darknet ? " [fused Darknet anchor decode, 7-float records]" : (f.v7 ? " [fused anchor decode, 6-float records]" : " [fused anchor decode]")), ins, {out});
         op.i[0] = pr.classes;
         op.i[1] = pr.net_h;
         op.i[2] = pr.net_w;
@@ -292,7 +293,7 @@ struct Lowerer {
         op.fv = pr.anchors;
         // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
         if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
-        op.ws_bytes = (f.v7 ? trtx_yolov7_head_decode_workspace : trtx_yolov5_head_decode_workspace)(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
+        op.ws_bytes = (f.darknet ? trtx_darknet_head_decode_workspace : (f.v7 ? trtx_yolov7_head_decode_workspace : trtx_yolov5_head_decode_workspace))(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
         // what it must read: the three objectness values of every pixel (nothing else of a pixel without a candidate), and what it writes
         for (int t : ins) op.bytes += (double)dtype_size(dt) * plan.tensors[t].H * plan.tensors[t].W * 3;
         op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
@@ -507,6 +508,20 @@ struct Lowerer {
                 op.i[0] = l.op == TRTX_POOLING_MAX ? POOL_MAX : POOL_AVG;
                 op.i[1] = l.kernel[0]; op.i[2] = l.kernel[1]; op.i[3] = l.stride[0]; op.i[4] = l.stride[1];
                 op.i[5] = l.padding[0]; op.i[6] = l.padding[1]; op.i[7] = l.avg_exclusive;
+                pt_of[l.outputs[0]] = out;
+                return true;
+            }
+            case L_PADDING: {
+                // one zero-pad op, no fold into the reader: a max-pool here starts from -inf and skips its border, and yolov3-tiny's 2x2 stride-1 pool
+                // behind Pad(0,0;1,1) must see the zeros (its LeakyReLU inputs are negative in places)
+                if (net.int8) return fail(l.name + ": IPaddingLayer is not implemented in kINT8 networks");
+                if (!g.spatial(net.tensors[l.inputs[0]].dims)) return fail(l.name + ": IPaddingLayer needs an image tensor");
+                const int in = need_nhwc(l.inputs[0]);
+                const int out = new_tensor(l.outputs[0], out_dims(), LAY_NHWC, true);
+                POp& op = add_op(OP_PAD_NHWC, l.name, {in}, {out});
+                op.i[0] = (int)l.start.d[0];
+                op.i[1] = (int)l.start.d[1];
+                op.bytes = (double)dtype_size(dt) * (net.tensors[l.inputs[0]].dims.volume() + out_dims().volume());
                 pt_of[l.outputs[0]] = out;
                 return true;
             }

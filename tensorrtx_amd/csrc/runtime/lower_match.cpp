@@ -274,17 +274,22 @@ void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
 //
 // YOLOv7's tail (yolov7/src/block.cpp:220-255) is the same graph in front of the 6-float plugin (`v7`): the same conditions, one
 // OP_YOLO7_HEAD, TRTX_YOLO7_HEAD=0.  A plugin instance is one form or the other, so the two calls cannot claim the same layer.
-void match_anchor_heads(const NetView& g, bool v7, Fusions& f) {
+//
+// The Darknet tail (yolov3/yolov3.cpp:282-332, yolov3-tiny/yolov3-tiny.cpp:254-280, yolov4/yolov4.cpp:435-475) is that graph once more in front of
+// the zero-field plugin (`form` 2): two or three detect convolutions in the plugin's own order, one OP_DARKNET_HEAD, TRTX_DARKNET_HEAD=0.
+void match_anchor_heads(const NetView& g, int form, Fusions& f) {
     const Network& net = g.net;
     const int e = net.explicit_batch ? 1 : 0;
-    if (!(v7 ? g.opt.yolo7_head : g.opt.yolo5_head)) return;
-    if (v7 && net.int8) return;   // kINT8 YOLOv7 networks keep the plugin route: the 6-float head was never run behind a calibrated convolution
+    const bool v7 = form == 1, darknet = form == 2;
+    if (!(darknet ? g.opt.darknet_head : (v7 ? g.opt.yolo7_head : g.opt.yolo5_head))) return;
+    if ((v7 || darknet) && net.int8) return;   // kINT8 YOLOv7 networks keep the plugin route: the 6-float head was never run behind a calibrated convolution
     for (size_t li = 0; li < net.layers.size(); ++li) {
         const LayerDef& l = net.layers[li];
         if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li] || !l.plugin) continue;
         Yolo5HeadFuse h;
         h.v7 = v7;
-        if (!(v7 ? builtin_yolo7_params : builtin_yolo5_params)(l.plugin->v, &h.params)) continue;
+        h.darknet = darknet;
+        if (!(darknet ? builtin_darknet_params : (v7 ? builtin_yolo7_params : builtin_yolo5_params))(l.plugin->v, &h.params)) continue;
         const Yolo5LayerParams& pr = h.params;
         if (pr.seg || pr.classes < 1 || l.inputs.empty() || l.inputs.size() > 8 || l.inputs.size() != pr.grid_w.size()) continue;
         bool ok = true;
@@ -311,7 +316,7 @@ void match_anchor_heads(const NetView& g, bool v7, Fusions& f) {
     }
 }
 
-void match_yolo5_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, false, f); }
+void match_yolo5_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 0, f); }
 
 // ---- ReOrg (yolov7/src/block.cpp:106-114; YOLOv5's Focus is the same graph): four slices of one image tensor with step (1, 2, 2) and
 // starts (0,0,0), (0,1,0), (0,0,1), (0,1,1), whole-channel, concatenated in that order on the channel axis, read by nothing but one
@@ -367,7 +372,8 @@ void match_reorg_fold(const NetView& g, Fusions& f) {
         f.reorg_src[lcv] = src;
     }
 }
-void match_yolo7_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, true, f); }
+void match_yolo7_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 1, f); }
+void match_darknet_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 2, f); }
 
 // ---- YOLOv9 / GELAN detect tail (yolov9/src/block.cpp:424-489): per level the concat of [DFL chain on the grouped 1x1 convolution's
 // (64, gh, gw) output, reshape (classes, gh * gw) of the class convolution's output] into the YOLOv9 YoloLayer_TRT.  Unlike YOLOv8's tail
@@ -1180,6 +1186,7 @@ Fusions match_fusions(const NetView& g) {
     match_yolo9_heads(g, f);
     match_yolo5_heads(g, f);
     match_yolo7_heads(g, f);
+    match_darknet_heads(g, f);
     match_psa_attention(g, f);
     match_area_attention(g, f);
     match_aattn_split(g, f);

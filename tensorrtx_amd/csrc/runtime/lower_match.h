@@ -37,6 +37,7 @@ struct Yolo5HeadFuse {
     std::vector<int> conv_layer;    // ... and the layer that produces it
     Yolo5LayerParams params;
     bool v7 = false;                // the YOLOv7 plugin: 6-float records, OP_YOLO7_HEAD
+    bool darknet = false;           // the Darknet plugin (YOLOv3 / YOLOv3-tiny / YOLOv4): 7-float records, OP_DARKNET_HEAD
 };
 
 struct Yolo9HeadFuse {

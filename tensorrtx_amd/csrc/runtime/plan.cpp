@@ -10,8 +10,9 @@ const char* op_kind_name(int k) {
                               "copy_nhwc", "reduce_hw", "to_nhwc",   "to_linear",  "gather",  "scatter",  "ew_lin",
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
-                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add", "attention_split"};
-    return (k >= 0 && k <= OP_ATTENTION_SPLIT) ? n[k] : "?";
+                              "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add", "attention_split",
+                              "darknet_head", "pad_nhwc"};
+    return (k >= 0 && k <= OP_PAD_NHWC) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -69,7 +70,8 @@ std::string Plan::describe_json() const {
         }
         if (op.kind == OP_POOL || op.kind == OP_POOL_CHAIN)
             o << ",\"k\":[" << op.i[1] << "," << op.i[2] << "],\"stride\":[" << op.i[3] << "," << op.i[4] << "],\"outputs\":" << op.out.size();
-        if (op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO7_HEAD) {
+        if (op.kind == OP_PAD_NHWC) o << ",\"pre\":[" << op.i[0] << "," << op.i[1] << "]";
+        if (op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD) {
             o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"anchor_levels\":" << op.fv.size() / 6 << ",\"grids\":[";
             for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]";
             o << "],\"ld\":[";

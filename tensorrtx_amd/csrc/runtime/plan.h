@@ -63,6 +63,9 @@ enum OpKind : int {
                         // channel), packed at w_off as C fp32 values
     OP_ATTENTION_SPLIT, // YOLOv13 area attention (kernels/attention_mfma.hip, area_attention_split_f16): in[0] = the NHWC fp16 q | k tensor (head h's q at channel
                         // h*kd, its k at i[5] + h*kd), in[1] = the NHWC fp16 v tensor, out[0] = O; i = heads, N, kd, hd, area, the k channel offset; f[0] = scale
+    OP_DARKNET_HEAD,    // OP_YOLO5_HEAD with the Darknet plugin's arithmetic and 7-float records (YOLOv3 / YOLOv3-tiny / YOLOv4; plugins/anchor_head.hip):
+                        // the same i / iv / fv, levels in the plugin's input order
+    OP_PAD_NHWC,        // IPaddingLayer, zero fill (nhwc_zero_pad): i[0] / i[1] = rows above / columns left of the image; the output tensor's H x W say the rest
 };
 const char* op_kind_name(int k);
 

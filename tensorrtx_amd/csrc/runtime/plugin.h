@@ -100,6 +100,9 @@ struct Yolo5LayerParams {
 bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
 // the same for a built-in YOLOv7 YoloLayer_TRT instance ("netinfo" of four ints + "kernels"; 6-float records, seg is false)
 bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
+// ... and for a built-in Darknet YoloLayer_TRT instance (created with no fields; 7-float records, max_out 1000): the plugin reads classes,
+// grids, net size and its family's anchor table off its inputs when the layer is added; false until then
+bool builtin_darknet_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
 // parameters of a *built-in* YOLOv9 YoloLayer_TRT instance (the single field "netinfo"; false for anything else): lets the lowering pass
 // replace the DFL chains, layout passes and the plugin by the fused DDetect head.  Three levels, strides 8 / 16 / 32.
 struct Yolo9LayerParams {

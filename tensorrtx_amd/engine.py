@@ -39,6 +39,21 @@ def build_plan(model: str, wts_path: str, **options) -> bytes:
     return data
 
 
+def darknet_rows(model: str):
+    """The host builder's own module table of "yolov3" / "yolov3-tiny" / "yolov4" (host/darknet.cpp): rows
+    [module, kind, channels, k, s, p, [from ...]], the row's position being the module number of the weight keys."""
+    M = models_lib()
+    M.trtx_host_darknet_rows.restype = ctypes.c_void_p
+    M.trtx_host_free.argtypes = [ctypes.c_void_p]
+    p = M.trtx_host_darknet_rows(model.encode())
+    if not p:
+        raise ValueError(f"{model} is no Darknet model")
+    try:
+        return json.loads(ctypes.string_at(p).decode())
+    finally:
+        M.trtx_host_free(p)   # the string is malloc'd for the caller
+
+
 def describe_plan(plan: bytes, lowered: bool = False) -> dict:
     out = ctypes.c_char_p()
     L = lib()

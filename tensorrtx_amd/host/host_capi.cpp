@@ -48,6 +48,8 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
     if (yolov9 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;      // no INT8 YOLOv9 is built
     const bool yolov7 = trtx_host::yolov7_model_valid(model);          // yolov7tiny / yolov7 / yolov7x / yolov7w6 / yolov7e6
     if (yolov7 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;      // ... nor INT8 YOLOv7
+    const bool darknet = trtx_host::darknet_model_valid(model);        // yolov3 / yolov3-tiny / yolov4
+    if (darknet && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;     // ... nor INT8 Darknet models
     if (geti(o, "int8", 0)) {  // USE_INT8 of the reference builders (yolov8/src/model.cpp:317-324, retinaface/retina_r50.cpp:219-225)
         if (!builder->platformHasFastInt8()) return TRTX_ERR_UNSUPPORTED;
         config->setFlag(BuilderFlag::kINT8);
@@ -171,6 +173,20 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
             return TRTX_ERR_INVALID;
         plan.reset(trtx_host::buildEngineYolov7(builder.get(), config.get(), wts_path, cfg));
         if (!plan) return TRTX_ERR_INVALID;   // anchor_grid does not describe one level per detect convolution
+    } else if (darknet) {
+        trtx_host::DarknetConfig cfg;
+        cfg.model = m;
+        cfg.max_batch = geti(o, "batch", 1);
+        cfg.fp16 = geti(o, "fp16", 1) != 0;
+        cfg.input_h = geti(o, "h", 608);
+        cfg.input_w = geti(o, "w", 608);
+        cfg.num_class = geti(o, "classes", 80);
+        cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
+        // MAX_OUTPUT_BBOX_COUNT is compiled into the reference's plugin (yololayer.h:12 of all three): 1000 and nothing else
+        if (geti(o, "task", 0) != 0 || geti(o, "max_out", 1000) != 1000) return TRTX_ERR_INVALID;
+        // the pyramid levels (strides 8 / 16 / 32, tiny 16 / 32) meet only on sizes that 32 divides
+        if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.input_h < 32 || cfg.input_w < 32 || cfg.input_h % 32 || cfg.input_w % 32) return TRTX_ERR_INVALID;
+        plan.reset(trtx_host::buildEngineDarknet(builder.get(), config.get(), wts_path, cfg));
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);
@@ -196,3 +212,13 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
 }
 
 extern "C" void trtx_host_free(void* blob) { std::free(blob); }
+
+// the module table of a Darknet model as JSON (the tests compare the builder's own table with theirs); null for another name.
+// The string is malloc'd: the caller releases it with trtx_host_free.
+extern "C" char* trtx_host_darknet_rows(const char* model) {
+    const std::string s = model ? trtx_host::darknet_rows_json(model) : "";
+    if (s.empty()) return nullptr;
+    char* out = static_cast<char*>(std::malloc(s.size() + 1));
+    if (out) std::memcpy(out, s.c_str(), s.size() + 1);
+    return out;
+}

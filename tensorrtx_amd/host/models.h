@@ -157,6 +157,25 @@ bool yolov7_model_p6(const std::string& name);
 nvinfer1::IHostMemory* buildEngineYolov7(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
                                          const Yolov7Config& cfg);
 
+// yolov3/yololayer.h, yolov3-tiny/yololayer.h and yolov4/yololayer.h constants (INPUT_H / INPUT_W 608, CLASS_NUM 80) as run-time configuration.
+// Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W}, setMaxBatchSize).  MAX_OUTPUT_BBOX_COUNT (1000) and the anchors are
+// compiled into the reference's plugin and stay what they are there.
+struct DarknetConfig {
+    std::string model = "yolov4";       // "yolov3" / "yolov3-tiny" / "yolov4": the createEngine of that directory
+    int input_h = 608, input_w = 608;   // INPUT_H / INPUT_W: multiples of 32, not necessarily equal
+    int num_class = 80;                 // CLASS_NUM
+    int max_batch = 1;                  // BATCH_SIZE
+    bool fp16 = true;                   // USE_FP16
+    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes), gh, gw) as "head0..N-1", in the plugin's input order
+};
+bool darknet_model_valid(const std::string& name);
+// the model's module table as JSON rows [module, kind, channels, k, s, p, [from ...]] (host/darknet.cpp); "" for another name
+std::string darknet_rows_json(const std::string& name);
+// yolov3/yolov3.cpp:190-340, yolov3-tiny/yolov3-tiny.cpp:222-296, yolov4/yolov4.cpp:232-490.  Input "data", output "prob": 1 + 1000 * 7 floats
+// (Detection is bbox[4], det_confidence, class_id, class_confidence).  Returns null for another name.
+nvinfer1::IHostMemory* buildEngineDarknet(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                          const DarknetConfig& cfg);
+
 // The reference's file-scope constants (rcnn/rcnn.cpp:16-60) as run-time configuration.
 struct RcnnConfig {
     int input_h = 800, input_w = 1067;      // INPUT_H / INPUT_W: 480x640 resized by calculateSize() (rcnn.cpp:349-366)

@@ -1137,3 +1137,209 @@ def yolov7_state(name="yolov7", seed=0, num_class=80):
             anchors = YOLOV7_TINY_ANCHORS if name == "yolov7tiny" else (YOLOV7_P6_ANCHORS if len(src) == 4 else YOLOV7_ANCHORS)
             sd[key + ".anchor_grid"] = torch.tensor(anchors, dtype=torch.float32).reshape(len(src), 1, 3, 1, 1, 2)
     return OrderedDict((k, v.numpy()) for k, v in sd.items())
+
+
+# Darknet YOLO (YOLOv3, YOLOv3-tiny, YOLOv4), after the models' published cfg files: one row per cfg module, "module_list.<row>" its weights
+# (the reference's gen_wts.py writes the state_dict of a PyTorch port whose module_list follows the cfg).  The anchors are compiled into the
+# reference's plugins (yololayer.h of each directory) and are no part of a weight file; they are listed in the plugin's input order.
+DARKNET_MODELS = ("yolov3", "yolov3-tiny", "yolov4")
+DARKNET_ANCHORS = {
+    "yolov3": [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 13, 16, 30, 33, 23]],      # strides 32, 16, 8
+    "yolov3-tiny": [[81, 82, 135, 169, 344, 319], [23, 27, 37, 58, 81, 82]],                               # strides 32, 16
+    "yolov4": [[12, 16, 19, 36, 40, 28], [36, 75, 76, 55, 72, 146], [142, 110, 192, 243, 459, 401]],      # strides 8, 16, 32
+}
+DARKNET_STRIDES = {"yolov3": (32, 16, 8), "yolov3-tiny": (32, 16), "yolov4": (8, 16, 32)}
+DARKNET_BN_EPS = {"yolov3": 1e-5, "yolov3-tiny": 1e-4, "yolov4": 1e-4}   # what each reference file passes to addBatchNorm2d
+# The detect rows.  The plugin keeps an anchor whose objectness AND class maximum both reach 0.1.  Objectness rows are He rows times
+# DARKNET_OBJ_SCALE around a per-model bias, set with the fp64 twin so that some, but far from all, of the 252 (tiny: 60) anchors of a 64 x 64
+# image pass (counts: tests/test_gpu_darknet.py).  Class rows are scaled down around DARKNET_CLS_BIAS (sigmoid 0.047, below the gate) with one
+# favoured class per (level, anchor) lifted by DARKNET_CLS_MARGIN (sigmoid 0.62, above it), so the class gate passes by a margin that fp16
+# does not reach.  The width and height rows are scaled by DARKNET_WH_ROW_SCALE: the box is exp(t) * anchor, an absolute error e in t is a
+# relative error e in the width, and with |t| of a few tenths fp16's head error stays far from the IoU the parity constants ask for.
+DARKNET_OBJ_SCALE = 8.0
+DARKNET_OBJ_BIAS_OF = {"yolov3": -13.0, "yolov3-tiny": -9.0, "yolov4": -2.7}
+DARKNET_CLS_BIAS, DARKNET_CLS_MARGIN, DARKNET_CLS_ROW_SCALE = -3.0, 3.5, 0.1
+DARKNET_XY_ROW_SCALE, DARKNET_WH_ROW_SCALE = 0.5, 0.1
+DARKNET_BRANCH_GAIN = 0.25   # BatchNorm weight of the convolution that ends a residual branch
+
+
+def darknet_rows(name):
+    """The cfg of a Darknet model as rows [module, kind, channels, k, s, p, from]: kind "L" (conv + BN + LeakyReLU 0.1), "M" (conv + BN +
+    Mish), "D" (biased 1x1 detect convolution), "S" (shortcut of two modules), "R" (route: one module, or the concatenation of several in the
+    order given), "P" (max-pool), "Z" (zero pad right and bottom by one, then max-pool 2 stride 1), "U" (nearest upsample by 2), "Y" (yolo);
+    `from` lists module numbers, empty for the module in front.  Written from the cfg files, not from the host builder's table: the two are
+    compared in tests/test_darknet_cpu.py."""
+    rows = []
+
+    def add(kind, ch=0, k=0, s=0, p=0, frm=()):
+        rows.append([len(rows), kind, ch, k, s, p, list(frm)])
+        return len(rows) - 1
+
+    def conv(kind, ch, k, s=1):
+        return add(kind, ch, k, s, k // 2)
+
+    def res(kind, c1, c3):   # 1x1, 3x3, shortcut over the two
+        conv(kind, c1, 1)
+        conv(kind, c3, 3)
+        add("S", frm=(len(rows) - 1, len(rows) - 3))
+
+    def alternate(ch, n):    # 1x1 to ch, 3x3 to 2 ch, ...
+        for i in range(n):
+            conv("L", 2 * ch if i % 2 else ch, 3 if i % 2 else 1)
+
+    def head():
+        add("D")
+        add("Y")
+
+    if name == "yolov3":
+        conv("L", 32, 3)
+        for ch, n in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
+            conv("L", ch, 3, 2)
+            for _ in range(n):
+                res("L", ch // 2, ch)
+        alternate(512, 6)
+        head()
+        add("R", frm=(79,))
+        conv("L", 256, 1)
+        add("U")
+        add("R", frm=(85, 61))
+        alternate(256, 6)
+        head()
+        add("R", frm=(91,))
+        conv("L", 128, 1)
+        add("U")
+        add("R", frm=(97, 36))
+        alternate(128, 6)
+        head()
+    elif name == "yolov3-tiny":
+        for ch in (16, 32, 64, 128, 256):
+            conv("L", ch, 3)
+            add("P", 0, 2, 2, 0)
+        conv("L", 512, 3)
+        add("Z")
+        conv("L", 1024, 3)
+        conv("L", 256, 1)
+        conv("L", 512, 3)
+        head()
+        add("R", frm=(13,))
+        conv("L", 128, 1)
+        add("U")
+        add("R", frm=(19, 8))
+        conv("L", 256, 3)
+        head()
+    else:
+        assert name == "yolov4", name
+        conv("M", 32, 3)
+        for ch, n in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
+            first = ch == 64
+            half = ch if first else ch // 2
+            d = conv("M", ch, 3, 2)
+            aside = conv("M", half, 1)
+            add("R", frm=(d,))
+            conv("M", half, 1)
+            for _ in range(n):
+                res("M", ch // 2 if first else half, half)
+            last = conv("M", half, 1)
+            add("R", frm=(last, aside))
+            conv("M", ch, 1)
+        alternate(512, 3)
+        add("P", 0, 5, 1, 2)
+        add("R", frm=(107,))
+        add("P", 0, 9, 1, 4)
+        add("R", frm=(107,))
+        add("P", 0, 13, 1, 6)
+        add("R", frm=(112, 110, 108, 107))
+        alternate(512, 3)
+        conv("L", 256, 1)
+        add("U")
+        add("R", frm=(85,))
+        conv("L", 256, 1)
+        add("R", frm=(120, 118))
+        alternate(256, 5)
+        conv("L", 128, 1)
+        add("U")
+        add("R", frm=(54,))
+        conv("L", 128, 1)
+        add("R", frm=(130, 128))
+        alternate(128, 6)
+        head()
+        add("R", frm=(136,))
+        conv("L", 256, 3, 2)
+        add("R", frm=(141, 126))
+        alternate(256, 6)
+        head()
+        add("R", frm=(147,))
+        conv("L", 512, 3, 2)
+        add("R", frm=(152, 116))
+        alternate(512, 6)
+        head()
+    return rows
+
+
+def darknet_channels(rows, num_class):
+    """output channels per module of darknet_rows (None for a yolo module)"""
+    ch = []
+    for i, kind, c, k, s, p, frm in rows:
+        src = [ch[j] for j in frm] if frm else [ch[i - 1] if i else 3]
+        if kind in ("L", "M"):
+            ch.append(c)
+        elif kind == "D":
+            ch.append(3 * (5 + num_class))
+        elif kind == "R":
+            ch.append(sum(src))
+        elif kind == "Y":
+            ch.append(None)
+        else:
+            ch.append(src[0])
+    return ch
+
+
+def darknet_state(name="yolov4", seed=0, num_class=80):
+    """Seeded synthetic weights of yolov3 / yolov3-tiny / yolov4 under the reference's `.wts` key names: module_list.<i>.Conv2d.weight and
+    module_list.<i>.BatchNorm2d.{weight,bias,running_mean,running_var} per convolution module, module_list.<i>.Conv2d.{weight,bias} for the
+    detect convolutions.  OrderedDict name -> fp32 array.  He-scaled convolutions (gain 2 / (1 + 0.1^2) under LeakyReLU(0.1), 2 under Mish)
+    with near-identity BatchNorm statistics; the detect rows as described at DARKNET_OBJ_SCALE."""
+    import math
+    from collections import OrderedDict
+
+    import torch
+    assert name in DARKNET_MODELS, name
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+    rows = darknet_rows(name)
+    ch = darknet_channels(rows, num_class)
+    info = 5 + num_class
+    lv = 0
+    for i, kind, c, k, s, p, frm in rows:
+        cin = ch[frm[0]] if frm else (ch[i - 1] if i else 3)
+        key = f"module_list.{i}"
+        if kind in ("L", "M"):
+            gain = 2.0 if kind == "M" else 2.0 / 1.01
+            sd[key + ".Conv2d.weight"] = (randn(c, cin, k, k) * math.sqrt(gain / (cin * k * k))).float()
+            bn = key + ".BatchNorm2d"
+            # a convolution that ends a residual branch: Darknet-53 has 23 shortcuts in a row and CSPDarknet as many, and branches of unit gain would
+            # double the variance at each (head values of 3e4 with plain rows); a quarter of the gain keeps the trunk's scale
+            branch = DARKNET_BRANCH_GAIN if i + 1 < len(rows) and rows[i + 1][1] == "S" else 1.0
+            sd[bn + ".weight"] = (branch * (0.9 + 0.2 * rand(c))).float()
+            sd[bn + ".bias"] = (0.1 * randn(c)).float()
+            sd[bn + ".running_mean"] = (0.1 * randn(c)).float()
+            sd[bn + ".running_var"] = (0.8 + 0.4 * rand(c)).float()
+            sd[bn + ".num_batches_tracked"] = torch.zeros(1)
+        elif kind == "D":
+            w = randn(3 * info, cin, 1, 1) * math.sqrt(2.0 / cin)
+            b = 0.1 * randn(3 * info)
+            for a in range(3):
+                o = a * info
+                w[o:o + 2] *= DARKNET_XY_ROW_SCALE
+                w[o + 2:o + 4] *= DARKNET_WH_ROW_SCALE
+                w[o + 4] *= DARKNET_OBJ_SCALE
+                b[o + 4] += DARKNET_OBJ_BIAS_OF[name]
+                w[o + 5:o + info] *= DARKNET_CLS_ROW_SCALE
+                b[o + 5:o + info] += DARKNET_CLS_BIAS
+                b[o + 5 + (7 * lv + 29 * a + 3) % num_class] += DARKNET_CLS_MARGIN
+            sd[key + ".Conv2d.weight"] = w.float()
+            sd[key + ".Conv2d.bias"] = b.float()
+            lv += 1
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
