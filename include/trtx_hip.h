@@ -438,6 +438,20 @@ int32_t trtx_op_conv_bneck_pair_f16(const void* in, int N, int H, int W, int ld_
 int32_t trtx_op_conv_bneck_pair_or_two_f16(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1,
                                            const void* w2_packed, const float* bias2, int act2, int shortcut, int act_after, void* mid, void* out,
                                            int ld_out, trtx_stream_t stream);
+/* 1 <= n <= 3 pairs of convolutions that read the same input, in ONE launch (the dual tile of kernels/igemm_tile.h; the detect head's cv2.x.0 -> 64 and
+ * cv3.x.0 -> 80 over three pyramid levels): problem j reads in[j], NHWC fp16 with geom[5 j ..] = {N, H, W, Cin, ld_in}, through one k x k filter geometry
+ * (stride, pad) and writes out0[j] (side0[3 j ..] = {Cout, ld_out, act}: 57 .. 64 channels in steps of 8) and out1[j] (side1 likewise: 65 .. 80 channels); weights as
+ * trtx_conv_pack_weights_f16 packs them, biases [Cout_pad] or NULL arrays, act none / ReLU / SiLU.  Every output element has the bits of its own
+ * trtx_op_conv2d_nhwc_f16 launch on the tactic {bn, 32, 128, 1, 1}.  TRTX_ERR_INVALID: an output that overlaps an input or another output (channel slices side by
+ * side in one buffer do not overlap) - nothing is launched.  TRTX_ERR_UNSUPPORTED: what the dual tile does not take - Cin <= 16 (two taps per k-step), a shortcut
+ * (res1: per problem the second side's residual with channel stride ld_res1, or NULL), int8 operands (i8_1 != 0 declares the second side's so), other widths. */
+int32_t trtx_op_conv_dual_group_f16(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0, const float* const* bias0,
+                                    void* const* out0, const int32_t* side0, const void* const* w1, const float* const* bias1, void* const* out1,
+                                    const int32_t* side1, const void* const* res1, int ld_res1, int i8_1, trtx_stream_t stream);
+/* What the executor issues for such a pair of groups: that launch where it is possible, otherwise the launches of each side on its own (same bits). */
+int32_t trtx_op_conv_dual_group_or_two_f16(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0,
+                                           const float* const* bias0, void* const* out0, const int32_t* side0, const void* const* w1, const float* const* bias1,
+                                           void* const* out1, const int32_t* side1, const void* const* res1, int ld_res1, int i8_1, trtx_stream_t stream);
 /* The same launch in an fp32 engine (builds without BuilderFlag::kFP16: yolov8/include/config.h:1-3 USE_FP32, yolov8/src/model.cpp:314-324):
  * NHWC fp32 in / out / residual, fp32 weights packed [cout_pad][kpad] (k = tap * cink + c, cink = Cin rounded up to the 16-channel k-step, or 8 for
  * Cin <= 8; Cin itself a multiple of 4), fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products and sums).  trtx_op_conv2d_tactics_f32 lists the tile

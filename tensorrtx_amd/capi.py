@@ -578,6 +578,28 @@ def conv_bneck_pair_f16(x, w1_packed, bias1, w2_packed, bias2, act1="silu", act2
     return out
 
 
+def conv_dual_group_f16(xs, w0, b0, outs0, w1, b1, outs1, k=3, stride=1, pad=1, act0="silu", act1="silu", cout0=None, cout1=None, res1=None, i8_1=False,
+                        or_two=False, status_only=False):
+    """1..3 pairs of convolutions over shared inputs in one launch (the dual tile): xs[j] [N,H,W,Cin] CUDA half (or a channel slice: pixel stride
+    xs[j].stride(2)); w0[j] / w1[j] packed weights of the 64-wide and the 80-wide side, b0[j] / b1[j] their biases; outs0[j] / outs1[j] the outputs, whole tensors
+    or channel slices (pixel stride .stride(2)); cout0 / cout1: per-problem channel counts (default: the outputs' last dimension).  res1: a shortcut for the
+    second side (refused by the launch).  or_two: the executor's form, which computes what the launch refuses as the launches of each side.
+    status_only: return the status instead of raising."""
+    import torch
+    n = len(xs)
+    A = lambda seq: None if seq is None else (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in seq])
+    geom = (ctypes.c_int32 * (5 * n))(*[v for x in xs for v in (x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.stride(2))])
+    side = lambda outs, couts, act: (ctypes.c_int32 * (3 * n))(*[v for j, o in enumerate(outs) for v in (couts[j] if couts else o.shape[-1], o.stride(2), ACT[act])])
+    assert all(t.dtype == torch.float16 and t.stride(3) == 1 for t in list(xs) + list(outs0) + list(outs1))
+    fn = lib().trtx_op_conv_dual_group_or_two_f16 if or_two else lib().trtx_op_conv_dual_group_f16
+    st = fn(n, A(xs), geom, k, stride, pad, A(w0), A(b0), A(outs0), side(outs0, cout0, act0), A(w1), A(b1), A(outs1), side(outs1, cout1, act1),
+            A(res1), res1[0].stride(2) if res1 is not None else 0, 1 if i8_1 else 0, _stream())
+    if status_only:
+        return st
+    check(st, "trtx_op_conv_dual_group_f16")
+    return outs0, outs1
+
+
 # ---------------------------------------------------------------------------------------------------- grouped conv on the matrix pipe (tests / tools)
 def pack_conv_weights_grouped_f16(w_kcrs, ch_scale=None):
     """Host: KCRS fp32 numpy [Cout, Cin / groups, k, k] -> packed uint16 [Cout, Kpad] for conv2d_grouped_nhwc_f16."""

@@ -681,4 +681,91 @@ int32_t conv_igemm_group_f16(const ConvArgs* a, int n, hipStream_t s) {
     return check_launch("conv_igemm_group_f16");
 }
 
+// ---- two sibling groups over the same inputs in one launch (the dual tile) ------------------------------------------------
+namespace {
+// fp16 elements [p, p + rows * ld) of which every row holds C: do the two slices share an element?  Channel windows side by side in one buffer do not.
+bool slices_overlap(const void* pa, long rows_a, int ld_a, int c_a, const void* pb, long rows_b, int ld_b, int c_b) {
+    if (!pa || !pb || rows_a < 1 || rows_b < 1) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(pa), a1 = a0 + (((size_t)rows_a - 1) * ld_a + c_a) * 2;
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(pb), b1 = b0 + (((size_t)rows_b - 1) * ld_b + c_b) * 2;
+    if (a1 <= b0 || b1 <= a0) return false;
+    if (ld_a != ld_b) return true;
+    const size_t row = (size_t)ld_a * 2;
+    const size_t d = b0 >= a0 ? (b0 - a0) % row : (row - (a0 - b0) % row) % row;   // b's window starts d bytes into a's row
+    return !(d >= (size_t)c_a * 2 && d + (size_t)c_b * 2 <= row);
+}
+bool dual_member_ok(const ConvArgs& a, int bn) {
+    return group_member_ok(a) && !a.in_i8 && !a.residual && a.bn == bn && a.Cout_pad == bn && a.t_ws != WS_RES3 && a.t_ws != WS_RES1 &&
+           !(a.t_ws != WS_OFF && conv_ws_supported(a));
+}
+// TRTX_OK, TRTX_ERR_UNSUPPORTED, or TRTX_ERR_INVALID for an output that lies on an input or on another output
+int32_t dual_group_refusal(const ConvArgs* a0, const ConvArgs* a1, int n) {
+    if (n < 1 || n > kMaxDualGroup) return TRTX_ERR_UNSUPPORTED;
+    for (int k = 0; k < n; ++k) {
+        const ConvArgs &x = a0[k], &y = a1[k];
+        if (!dual_member_ok(x, 64) || !dual_member_ok(y, 80)) return TRTX_ERR_UNSUPPORTED;
+        if (x.in != y.in || x.N != y.N || x.H != y.H || x.W != y.W || x.Cin != y.Cin || x.CinK != y.CinK || x.ld_in != y.ld_in || x.Ho != y.Ho || x.Wo != y.Wo ||
+            x.kh != y.kh || x.kw != y.kw || x.stride_h != y.stride_h || x.stride_w != y.stride_w || x.pad_h != y.pad_h || x.pad_w != y.pad_w || x.Kpad != y.Kpad)
+            return TRTX_ERR_UNSUPPORTED;
+    }
+    for (int k = 0; k < 2 * n; ++k) {
+        const ConvArgs& o = k < n ? a0[k] : a1[k - n];
+        const long rows_o = (long)o.N * o.Ho * o.Wo;
+        for (int j = 0; j < n; ++j)
+            if (slices_overlap(o.out, rows_o, o.ld_out, o.Cout, a0[j].in, (long)a0[j].N * a0[j].H * a0[j].W, a0[j].ld_in, a0[j].Cin)) return TRTX_ERR_INVALID;
+        for (int j = k + 1; j < 2 * n; ++j) {
+            const ConvArgs& u = j < n ? a0[j] : a1[j - n];
+            if (slices_overlap(o.out, rows_o, o.ld_out, o.Cout, u.out, (long)u.N * u.Ho * u.Wo, u.ld_out, u.Cout)) return TRTX_ERR_INVALID;
+        }
+    }
+    return TRTX_OK;
+}
+}  // namespace
+
+bool conv_dual_group_possible(const ConvArgs* a0, const ConvArgs* a1, int n) { return dual_group_refusal(a0, a1, n) == TRTX_OK; }
+
+int32_t conv_dual_group_f16(const ConvArgs* a0, const ConvArgs* a1, int n, hipStream_t s) {
+    const int32_t why = dual_group_refusal(a0, a1, n);
+    if (why != TRTX_OK) return why;
+    ConvDualGroupArgs g{};
+    static_assert(sizeof(ConvDualGroupArgs) < 2048, "kernel arguments stay well under 4 KB");
+    g.n = n;
+    int order[kMaxDualGroup];   // falling k-steps per tile (ties: more rows first)
+    for (int k = 0; k < n; ++k) order[k] = k;
+    std::sort(order, order + n, [&](int x, int y) {
+        if (a0[x].Kpad != a0[y].Kpad) return a0[x].Kpad > a0[y].Kpad;
+        const long mx = (long)a0[x].N * a0[x].Ho * a0[x].Wo, my = (long)a0[y].N * a0[y].Ho * a0[y].Wo;
+        return mx != my ? mx > my : x < y;
+    });
+    int slots = 0;
+    for (int k = 0; k < n; ++k) {
+        const ConvArgs &x = a0[order[k]], &y = a1[order[k]];
+        g.p[k] = x;
+        g.p[k].M = x.N * x.Ho * x.Wo;
+        g.q[k] = ConvDualSide{y.wgt, y.bias, y.out, y.Cout, y.Cout_pad, y.ld_out, y.act1, y.act2, y.alpha1, y.alpha2, (unsigned)((size_t)y.Cout_pad * y.Kpad * 2)};
+        g.tiles[k] = (g.p[k].M + 127) / 128;
+        g.chunk[k] = (g.tiles[k] + 7) / 8;
+        g.slot_start[k] = slots;
+        slots += g.chunk[k];
+        g.in_bytes[k] = (unsigned)((((size_t)x.N * x.H * x.W - 1) * x.ld_in + x.Cin) * 2);
+        g.w_bytes[k] = (unsigned)((size_t)x.Cout_pad * x.Kpad * 2);
+    }
+    for (int k = n; k <= kMaxDualGroup; ++k) g.slot_start[k] = slots;
+    TRTX_LAUNCH((conv_igemm_dual_group_f16_kernel<4, 5>), dim3(slots * 8), dim3(256), 0, s, g);
+    return check_launch("conv_dual_group_f16");
+}
+
+int32_t conv_dual_group_or_two_f16(const ConvArgs* a0, const ConvArgs* a1, int n, hipStream_t s) {
+    if (conv_dual_group_possible(a0, a1, n)) return conv_dual_group_f16(a0, a1, n, s);
+    for (const ConvArgs* a : {a0, a1}) {
+        int32_t st = n >= 2 ? conv_igemm_group_f16(a, n, s) : TRTX_ERR_UNSUPPORTED;
+        if (st == TRTX_ERR_UNSUPPORTED) {   // (as the executor: members that share no instantiation take one launch each, same bits)
+            st = TRTX_OK;
+            for (int k = 0; k < n && st == TRTX_OK; ++k) st = conv_igemm_f16(a[k], s);
+        }
+        if (st != TRTX_OK) return st;
+    }
+    return TRTX_OK;
+}
+
 }  // namespace trtx

@@ -394,13 +394,13 @@ __device__ __forceinline__ void conv_epilogue_f32(const ConvArgs& p, floatx4 (&a
 // Measured (round 3, same box): the 1x1 layers of YOLOv8n b32 3-10 % faster one at a time (34-layer sum 715 vs 724 us), res5's 1x1
 // 2048 -> 512 GEMM 497 vs 509 us; bench.py within run-to-run noise (35.0-35.2k vs 34.4-35.3k img/s).  Same bits.
 // LDS bytes of one instantiation (the stage buffers, or the epilogue's staging tiles if those are larger)
-template <int NFRAG, int BKT, int MI, bool RS>
+template <int NFRAG, int BKT, int MI, bool RS, int NF1 = 0, int STAGES = 0>
 constexpr int igemm_lds_bytes() {
-    constexpr int BN = 16 * NFRAG, BM = kWaves * 16 * MI, ROW_B = BKT * 2, CH = BKT / 8, RPI = 64 / CH;
+    constexpr int BN = 16 * (NFRAG + NF1), BM = kWaves * 16 * MI, ROW_B = BKT * 2, CH = BKT / 8, RPI = 64 / CH;
     constexpr int B_PASSES = (BN + kWaves * RPI - 1) / (kWaves * RPI), B_ROWS = B_PASSES * kWaves * RPI;
     constexpr int STAGE_BYTES = BM * ROW_B + B_ROWS * ROW_B;
-    constexpr int NST = RS ? 2 : (BKT == 64 ? 2 : 3);
-    constexpr int EPI_BYTES = kWaves * 16 * (16 * NFRAG * 4 + 16);
+    constexpr int NST = STAGES ? STAGES : (RS ? 2 : (BKT == 64 ? 2 : 3));
+    constexpr int EPI_BYTES = kWaves * 16 * (16 * (NFRAG > NF1 ? NFRAG : NF1) * 4 + 16);
     return NST * STAGE_BYTES > EPI_BYTES ? NST * STAGE_BYTES : EPI_BYTES;
 }
 
@@ -414,10 +414,21 @@ constexpr int igemm_lds_bytes() {
 // contents, same K order: the same bits as the one-role kernel.  Instantiated for the fp32 tiles (conv_igemm_f32.hip, tactic WS_F32_ROLES: the tuner takes it on the
 // 80-wide detect-head layers, -8..-16 % there).  On the fp16 128-row tiles it was measured too: -3..-17 % on small maps alone, nothing on the three-context
 // bench line (profiles/r05_fp16_roles_*) - not instantiated there.
-template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2, bool RS = false, bool UP = false, bool ONE = false, bool F32 = false, bool ROLES = false>
-__device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_bytes, unsigned w_bytes, const int m0, const int n0, char* __restrict__ smem) {
+// NF1 > 0 = the DUAL tile (conv_igemm_dual_group_f16_kernel below): two convolutions p and *p1 that read the same input with the same filter geometry, Kpad and
+// k-step - the detect head's cv2.x.0 (-> 64) and cv3.x.0 (-> 80) - as ONE tile of 16 * (NFRAG + NF1) columns.  The A pieces, their tap walk and address
+// arithmetic, the barriers and the launch exist once; B rows [0, 16 NFRAG) are p's weight rows and the rows behind them p1's (own descriptor, own range; the seam
+// lies on a DMA pass boundary, so which side a pass fetches is a compile-time fact); the accumulators are acc[MI][NFRAG] and acc1[MI][NF1]; the epilogue runs once
+// per side with that side's own ConvArgs.  Every output element is still summed over K in the order of its own launch and finished by the same epilogue code:
+// the bits of two launches.  Per wave and k-step: 2 A + 3 B pieces for 18 MFMAs where the two launches issue 7 pieces.  STAGES: pipeline stages (0 = the default).
+template <int NFRAG, int BKT, int TPS, bool I8 = false, int MI = 2, bool RS = false, bool UP = false, bool ONE = false, bool F32 = false, bool ROLES = false,
+          int NF1 = 0, int STAGES = 0>
+__device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_bytes, unsigned w_bytes, const int m0, const int n0, char* __restrict__ smem,
+                                                const ConvArgs* p1 = nullptr, unsigned w1_bytes = 0) {
     TRTX_MARK(0);
-    constexpr int BN = 16 * NFRAG;
+    constexpr bool DUAL = NF1 > 0;
+    constexpr int BN = 16 * (NFRAG + NF1);             // columns the B stage holds (one side: the column tile)
+    static_assert(!DUAL || (BKT == 32 && TPS == 1 && !I8 && !RS && !UP && !ONE && !F32 && !ROLES && (16 * NFRAG) % (kWaves * 16) == 0),
+                  "dual tile: fp16, 32-wide k-steps, LDS-DMA operands, the seam on a DMA pass boundary");
     constexpr int BM = kWaves * 16 * MI;               // rows per tile: every wave owns 16 * MI of them
     constexpr int WR = 16 * MI;                    // rows per wave
     constexpr int ROW_B = BKT * 2;                 // bytes per LDS row
@@ -430,10 +441,10 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     constexpr int STAGE_BYTES = A_BYTES + B_ROWS * ROW_B;
     constexpr int LOADS_PER_TILE = A_LOADS + B_PASSES;
     constexpr int KSUB = BKT / 32;                 // MFMA k-slices per k-step
-    constexpr int NST = RS ? 2 : (BKT == 64 ? 2 : 3);  // pipeline stages (64-wide stages are double-buffered to keep occupancy)
-    constexpr int EPI_BYTES = kWaves * 16 * (16 * NFRAG * 4 + 16);   // the epilogue's wave-private staging tiles (conv_epilogue)
+    constexpr int NST = STAGES ? STAGES : (RS ? 2 : (BKT == 64 ? 2 : 3));  // pipeline stages (64-wide stages are double-buffered to keep occupancy)
+    constexpr int EPI_BYTES = kWaves * 16 * (16 * (NFRAG > NF1 ? NFRAG : NF1) * 4 + 16);   // the epilogue's wave-private staging tiles (conv_epilogue)
     constexpr int LDS_BYTES = NST * STAGE_BYTES > EPI_BYTES ? NST * STAGE_BYTES : EPI_BYTES;
-    static_assert(LDS_BYTES == igemm_lds_bytes<NFRAG, BKT, MI, RS>(), "the entry points allocate what the tile function uses");
+    static_assert(LDS_BYTES == igemm_lds_bytes<NFRAG, BKT, MI, RS, NF1, STAGES>(), "the entry points allocate what the tile function uses");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -444,6 +455,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
 
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.in), 0, in_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wgt), 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w1 = DUAL ? __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p1->wgt), 0, w1_bytes, 0x00020000) : rs_w;
     const unsigned up_bytes = UP ? (unsigned)((((size_t)p.N * p.up_H * p.up_W - 1) * p.up_ld + p.up_C) * 2) : 0u;
     const __amdgpu_buffer_rsrc_t rs_up = UP ? __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.up_in), 0, up_bytes, 0x00020000) : rs_in;
 
@@ -489,6 +501,8 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     for (int j = 0; j < B_PASSES; ++j) {
         const int row = (kWaves * j + wave) * RPI + lrow;
         b_off[j] = row < BN ? (unsigned)(((n0 + row) * p.Kpad + lchunk * 8) * 2) : kOOB;  // weights < 2 GB
+        if constexpr (DUAL)   // the second side's rows start at ITS row 0 (one column tile per side: n0 == 0)
+            if (row >= 16 * NFRAG && row < BN) b_off[j] = (unsigned)(((row - 16 * NFRAG) * p.Kpad + lchunk * 8) * 2);
     }
     // Column tiles that are not a whole number of DMA passes (BN = 16 / 32 / 80 with 32-wide steps, 80 with 64-wide ones): in the LAST pass
     // some waves' pieces lie wholly beyond the tile - rows nobody reads.  Those waves skip the instruction (round 4: a DMA piece costs its
@@ -593,6 +607,8 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
             if (B_PARTIAL && j == B_PASSES - 1 && !b_last_live) continue;   // this wave's piece of the last pass lies beyond the column tile
             const unsigned voff = ONE ? b_off[j] : (s_kt < nk ? b_off[j] : kOOB);
             if constexpr (RS) rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, voff, 0, 0);
+            else if (DUAL && j * kWaves * RPI >= 16 * NFRAG)   // (j is unrolled: a pass lies wholly on one side)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (lds_ptr_t)(sbase + A_BYTES + (kWaves * j + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_ptr_t)(sbase + A_BYTES + (kWaves * j + wave) * RPI * ROW_B), 16, voff, 0, 0, 0);
             b_off[j] += BKT * 2;  // kOOB stays out of range for any K < 2^30
         }
@@ -621,14 +637,18 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
     floatx4 acc[MI][NFRAG];
     intx4 acci[MI][NFRAG];
     floatx4 part[F32 ? MI : 1][F32 ? NFRAG : 1];   // fp32: the running k-step's partial sum (two-level sum, see compute())
+    floatx4 acc1[MI][DUAL ? NF1 : 1];               // dual tile: the second side's columns
 #pragma unroll
-    for (int i = 0; i < MI; ++i)
+    for (int i = 0; i < MI; ++i) {
 #pragma unroll
         for (int j = 0; j < NFRAG; ++j) {
             acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
             acci[i][j] = intx4{0, 0, 0, 0};
             if constexpr (F32) part[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
         }
+#pragma unroll
+        for (int j = 0; j < (DUAL ? NF1 : 1); ++j) acc1[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    }
     if constexpr (F32) {
         // fp32: the running total STARTS at the bias (a lane's fragment is four consecutive channels of one pixel, the same four for every row slab), so
         // the fetch passes under the first tiles' round trip to memory instead of standing, a full L2 latency, in front of the epilogue's first store
@@ -717,6 +737,14 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
                     const half8 bf = *reinterpret_cast<const half8*>(sb + b_frag + j * 16 * ROW_B + f_off[h]);
 #pragma unroll
                     for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf, af[i], acc[i][j], 0, 0, 0);
+                }
+                if constexpr (DUAL) {
+#pragma unroll
+                    for (int j = 0; j < NF1; ++j) {
+                        const half8 bf = *reinterpret_cast<const half8*>(sb + b_frag + (NFRAG + j) * 16 * ROW_B + f_off[h]);
+#pragma unroll
+                        for (int i = 0; i < MI; ++i) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf, af[i], acc1[i][j], 0, 0, 0);
+                    }
                 }
             }
         }
@@ -831,6 +859,13 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, unsigned in_b
         const int m = m0 + t;
         return m < p.M ? m : -1;
     }, wave * WR);
+    if constexpr (DUAL) {   // the second side: its own arguments, the same epilogue (its opening barrier keeps the two sides' staging tiles apart)
+        intx4 acci_b[MI][NF1];   // (int8 accumulators: not read by an fp16 epilogue)
+        conv_epilogue<NF1, MI, false, LDS_BYTES>(*p1, acc1, acci_b, smem, wave, lane, 0, [&](int t) {
+            const int m = m0 + t;
+            return m < p.M ? m : -1;
+        }, wave * WR);
+    }
     }
     TRTX_MARK(3);
 }
@@ -882,6 +917,46 @@ __global__ __launch_bounds__(256) void conv_igemm_group_f16_kernel(const ConvGro
     const int m0 = (local / tn) * 128;
     const int n0 = (local % tn) * (16 * NFRAG);
     conv_igemm_tile<NFRAG, BKT, 1, I8, 2, RS, false, ONE>(g.p[pid], g.in_bytes[pid], g.w_bytes[pid], m0, n0, smem);
+}
+
+// Up to kMaxDualGroup DUAL problems in one launch (the dual tile: see conv_igemm_tile): the detect head's cv2.{0,1,2}.0 and cv3.{0,1,2}.0, six
+// convolutions that read three tensors.  Tile -> problem mapping as above (per-problem XCD chunks, the host orders the problems by falling k-steps per
+// tile); every problem is one column tile wide on either side, so a tile is a run of 128 output pixels.  p[k] is the first side as its own launch
+// takes it; the second side differs from it only in what ConvDualSide holds (the kernel arguments stay near 1 KB).
+struct ConvDualSide {
+    const void* wgt;
+    const float* bias;
+    void* out;
+    int Cout, Cout_pad, ld_out, act1, act2;
+    float alpha1, alpha2;
+    unsigned w_bytes;
+};
+struct ConvDualGroupArgs {
+    int n;
+    int slot_start[kMaxDualGroup + 1];
+    int chunk[kMaxDualGroup], tiles[kMaxDualGroup];
+    unsigned in_bytes[kMaxDualGroup], w_bytes[kMaxDualGroup];
+    ConvArgs p[kMaxDualGroup];
+    ConvDualSide q[kMaxDualGroup];
+};
+constexpr int kDualStages = 2;   // two stages of 128 x 32 + 192 x 32: 40 960 B, four workgroups per CU (three stages: 61 440 B, two - measured slower)
+template <int NF0, int NF1>
+__global__ __launch_bounds__(256) void conv_igemm_dual_group_f16_kernel(const ConvDualGroupArgs g) {
+    __shared__ __attribute__((aligned(16))) char smem[igemm_lds_bytes<NF0, 32, 2, false, NF1, kDualStages>()];
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    int pid = 0;
+#pragma unroll
+    for (int k = 1; k < kMaxDualGroup; ++k) pid += (k < g.n && slot >= g.slot_start[k]) ? 1 : 0;
+    pid = __builtin_amdgcn_readfirstlane(pid);
+    const int local = xcd * g.chunk[pid] + (slot - g.slot_start[pid]);
+    if (local >= g.tiles[pid]) return;
+    const ConvDualSide& s1 = g.q[pid];
+    ConvArgs p1 = g.p[pid];
+    p1.wgt = s1.wgt; p1.bias = s1.bias; p1.out = s1.out;
+    p1.Cout = s1.Cout; p1.Cout_pad = s1.Cout_pad; p1.ld_out = s1.ld_out;
+    p1.act1 = s1.act1; p1.act2 = s1.act2; p1.alpha1 = s1.alpha1; p1.alpha2 = s1.alpha2;
+    conv_igemm_tile<NF0, 32, 1, false, 2, false, false, false, false, false, NF1, kDualStages>(g.p[pid], g.in_bytes[pid], g.w_bytes[pid], local * 128, 0, smem, &p1,
+                                                                                                s1.w_bytes);
 }
 
 }  // namespace

@@ -122,6 +122,17 @@ void conv_apply_tactic(ConvArgs* a, const ConvTactic& t);
 constexpr int kMaxConvGroup = 4;
 bool conv_igemm_group_supported(const ConvArgs* a, int n);
 int32_t conv_igemm_group_f16(const ConvArgs* a, int n, hipStream_t s);
+// Two such groups that read the SAME tensors in one launch (conv_igemm.hip conv_igemm_dual_group_f16_kernel; the detect head's cv2.x.0 and cv3.x.0): member k
+// of a0 (-> 64 channels) and member k of a1 (-> 80) share their input pointer, geometry, filter, Kpad and k-step, and run as one 144-column tile whose A operand is
+// fetched once; each output element is computed exactly as its own launch computes it (same K order, same epilogue: the same bits).  1 <= n <= kMaxDualGroup.
+// _possible(): fp16 without a shortcut or folded upsample, CinK != 16, the main kernel's 128-row / 32-wide-step form on both sides (no wave-split-K,
+// WS_PATCH or WS_RES* member; t_rs only chooses an operand path of the same bits - the dual tile always takes LDS-DMA), a per-problem input slice below 2 GB and - for whatever pointers are set - no output that overlaps an input or another output
+// (channel slices side by side in one buffer do not overlap).  conv_dual_group_f16: TRTX_ERR_INVALID for such an overlap, TRTX_ERR_UNSUPPORTED otherwise refused.
+constexpr int kMaxDualGroup = 3;
+bool conv_dual_group_possible(const ConvArgs* a0, const ConvArgs* a1, int n);
+int32_t conv_dual_group_f16(const ConvArgs* a0, const ConvArgs* a1, int n, hipStream_t s);
+// ... where _possible() holds, otherwise exactly the two launches of each group on its own (n == 1: of each convolution).  What the executor issues at a marked op.
+int32_t conv_dual_group_or_two_f16(const ConvArgs* a0, const ConvArgs* a1, int n, hipStream_t s);
 // Large plain-GEMM convolutions on the 256 x 256 x 64 role-alternating tile (conv_gemm256.hip): the tactic ConvArgs::bn == 256 of the
 // implicit-GEMM family (same packed weights, same bits); conv_igemm_f16 dispatches to it
 bool conv_gemm256_possible(const ConvArgs& a);     // may run (any batch up to the build batch)

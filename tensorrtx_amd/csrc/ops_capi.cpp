@@ -197,6 +197,43 @@ extern "C" int32_t trtx_op_conv_bneck_pair_or_two_f16(const void* in, int N, int
     return op_bneck_pair(in, N, H, W, ld_in, in_coff, w1_packed, bias1, act1, w2_packed, bias2, act2, shortcut, act_after, mid, out, ld_out, true, stream);
 }
 
+// --- two sibling groups over the same inputs in one launch (the dual tile of kernels/igemm_tile.h), test / tool entry points
+static int32_t op_dual_group(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0, const float* const* bias0,
+                             void* const* out0, const int32_t* side0, const void* const* w1, const float* const* bias1, void* const* out1, const int32_t* side1,
+                             const void* const* res1, int ld_res1, int i8_1, bool or_two, trtx_stream_t stream) {
+    if (n < 1 || n > kMaxDualGroup || !in || !geom || !w0 || !out0 || !side0 || !w1 || !out1 || !side1 || k < 1 || stride < 1 || pad < 0) return TRTX_ERR_INVALID;
+    ConvArgs a0[kMaxDualGroup], a1[kMaxDualGroup];
+    for (int j = 0; j < n; ++j) {
+        const int32_t *g = geom + 5 * j, *s0 = side0 + 3 * j, *s1 = side1 + 3 * j;
+        if (!in[j] || !w0[j] || !out0[j] || !w1[j] || !out1[j] || g[0] < 1 || g[1] + 2 * pad < k || g[2] + 2 * pad < k || g[3] < 1) return TRTX_ERR_INVALID;
+        const void* r1 = res1 ? res1[j] : nullptr;
+        a0[j] = op_conv_args(g[0], g[1], g[2], g[3], g[4], s0[0], s0[1], k, k, stride, stride, pad, pad, s0[2], 0, 0, 0);
+        a1[j] = op_conv_args(g[0], g[1], g[2], g[3], g[4], s1[0], s1[1], k, k, stride, stride, pad, pad, s1[2], r1 != nullptr, ld_res1, 0);
+        a0[j].in = a1[j].in = in[j];
+        a0[j].wgt = w0[j]; a0[j].bias = bias0 ? bias0[j] : nullptr; a0[j].out = out0[j];
+        a1[j].wgt = w1[j]; a1[j].bias = bias1 ? bias1[j] : nullptr; a1[j].out = out1[j];
+        a1[j].residual = r1;
+        a1[j].in_i8 = i8_1 ? 1 : 0;
+        a0[j].t_wsk = a1[j].t_wsk = WSK_OFF;   // as the members of a grouped launch: the main kernel's K order
+        a0[j].t_ws = a1[j].t_ws = WS_OFF;
+        a0[j].k_pinned = a1[j].k_pinned = 1;
+    }
+    return or_two ? conv_dual_group_or_two_f16(a0, a1, n, static_cast<hipStream_t>(stream)) : conv_dual_group_f16(a0, a1, n, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trtx_op_conv_dual_group_f16(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0,
+                                               const float* const* bias0, void* const* out0, const int32_t* side0, const void* const* w1, const float* const* bias1,
+                                               void* const* out1, const int32_t* side1, const void* const* res1, int ld_res1, int i8_1, trtx_stream_t stream) {
+    return op_dual_group(n, in, geom, k, stride, pad, w0, bias0, out0, side0, w1, bias1, out1, side1, res1, ld_res1, i8_1, false, stream);
+}
+
+extern "C" int32_t trtx_op_conv_dual_group_or_two_f16(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0,
+                                                      const float* const* bias0, void* const* out0, const int32_t* side0, const void* const* w1,
+                                                      const float* const* bias1, void* const* out1, const int32_t* side1, const void* const* res1, int ld_res1, int i8_1,
+                                                      trtx_stream_t stream) {
+    return op_dual_group(n, in, geom, k, stride, pad, w0, bias0, out0, side0, w1, bias1, out1, side1, res1, ld_res1, i8_1, true, stream);
+}
+
 // --- grouped convolution on the matrix pipe (kernels/conv_grouped.hip), test / tool entry points
 extern "C" int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale, uint16_t* packed,
                                                       int32_t* kpad_out) {

@@ -30,6 +30,7 @@ Options read_options() {
     o.fold_upsample = !env_is("TRTX_FOLD_UPSAMPLE", 0);
     o.stem_pair = !env_is("TRTX_STEM_PAIR", 0);
     o.bneck_pair = !env_is("TRTX_BNECK_PAIR", 0);
+    o.sibling_pair = !env_is("TRTX_SIBLING_PAIR", 0);
     o.ws = !env_set("TRTX_CONV_NOWS");
     o.wsk = !env_set("TRTX_CONV_NOWSK");
     o.gemm256 = !env_is("TRTX_GEMM256", 0);

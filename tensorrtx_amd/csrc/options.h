@@ -25,6 +25,7 @@ struct Options {
     bool fold_upsample = true;   // TRTX_FOLD_UPSAMPLE=0: Upsample -> Concat -> Conv1x1 keeps its resize launch
     bool stem_pair = true;       // TRTX_STEM_PAIR=0: the stem and the stride-2 3x3 convolution behind it stay two launches (no kernels/conv_stem_pair.hip; same bits)
     bool bneck_pair = true;      // TRTX_BNECK_PAIR=0: the two 3x3 convolutions of a 16-channel bottleneck stay two launches (no kernels/conv_bneck_pair.hip; same bits)
+    bool sibling_pair = true;    // TRTX_SIBLING_PAIR=0: two grouped launches that read the same tensors (the detect head's cv2.x.0 and cv3.x.0) stay two launches (no dual tile; same bits)
     bool ws = true;              // TRTX_CONV_NOWS=1: no weight-stationary kernel
     bool wsk = true;             // TRTX_CONV_NOWSK=1: no wave-split-K kernel
     bool gemm256 = true;         // TRTX_GEMM256=0: no 256 x 256 x 64 tile among the candidates

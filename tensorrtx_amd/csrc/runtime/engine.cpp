@@ -144,6 +144,14 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const POp &o = plan.ops[k], &nx = plan.ops[k + 1];
         return nx.bneck_pair && nx.kind == OP_CONV && o.kind == OP_CONV && o.igemm && nx.lane == o.lane && nx.in[0] == o.out[0];
     };
+    // The sibling pair (POp::sibling_pair on op k + 1; the dual tile of kernels/igemm_tile.h): the same shape - the first group launches nothing and the marked
+    // group issues both, as one launch where conv_dual_group_or_two_f16 takes the run-time pointers and as today's two otherwise.  Camera-frame contexts keep one
+    // launch per op as well.
+    auto group_defers_to_next = [&](size_t k) {
+        if (c->observer || c->tuning || c->frames || k + 1 >= plan.ops.size()) return false;
+        const POp &o = plan.ops[k], &nx = plan.ops[k + 1];
+        return nx.sibling_pair && nx.kind == OP_CONV_GROUP && o.kind == OP_CONV_GROUP && nx.lane == o.lane && nx.group.size() == o.group.size();
+    };
     for (size_t k = 0; k < plan.ops.size(); ++k) {
         const POp& op = plan.ops[k];
         hipStream_t stream = user_stream;  // shadows the parameter: the stream THIS op is issued on
@@ -239,9 +247,8 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 ConvArgs ga[kMaxConvGroup];
                 const int gn = (int)op.group.size();
                 if (gn < 2 || gn > kMaxConvGroup) { st = TRTX_ERR_STATE; break; }
-                for (int m = 0; m < gn; ++m) {
-                    const POp& mo = op.group[m];
-                    ConvArgs& a = ga[m];
+                if (group_defers_to_next(k)) break;   // the first group of a sibling pair: issued by the marked op behind it
+                auto member_args = [&](const POp& mo, ConvArgs& a) {
                     a = mo.conv;
                     a.in = R.ptr(mo.in[0]);
                     a.out = R.ptr(mo.out[0]);
@@ -252,6 +259,25 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     a.cscale = a.in_i8 ? reinterpret_cast<const float*>(W + mo.s_off) : nullptr;
                     a.N = nb(plan.tensors[mo.in[0]]);
                     a.M = a.N * a.Ho * a.Wo;
+                };
+                for (int m = 0; m < gn; ++m) member_args(op.group[m], ga[m]);
+                if (op.sibling_pair && k > 0 && group_defers_to_next(k - 1)) {   // ... here: its profile row carries the launch and the first group's reports 0
+                    const POp& fo = plan.ops[k - 1];
+                    ConvArgs fa[kMaxConvGroup], sa[kMaxConvGroup];   // the first group's members, and this group's in the order of the tensors those read
+                    bool paired = true;
+                    for (int m = 0; m < gn; ++m) {
+                        member_args(fo.group[m], fa[m]);
+                        int q = 0;
+                        while (q < gn && op.group[q].in[0] != fo.group[m].in[0]) ++q;
+                        if (q == gn) { paired = false; break; }
+                        sa[m] = ga[q];
+                    }
+                    if (!paired) { st = TRTX_ERR_STATE; break; }
+                    const bool first64 = fa[0].bn == 64;   // the dual tile's first side is the 64-wide one
+                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
+                    st = conv_dual_group_or_two_f16(first64 ? fa : sa, first64 ? sa : fa, gn, stream);
+                    conv_set_launch_probe(nullptr);
+                    break;
                 }
                 if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
                 st = conv_igemm_group_f16(ga, gn, stream);

@@ -101,7 +101,7 @@ std::string Plan::describe_json() const {
                 for (size_t q = 0; q < m.in.size(); ++q) o << (q ? "," : "") << m.in[q];
                 o << "],\"out\":[" << m.out[0] << "]}";
             }
-            o << "]";
+            o << "]" << (op.sibling_pair ? ",\"sibling_pair\":true" : "");
         }
         o << ",\"lane\":" << op.lane << ",\"waits\":[";
         for (size_t j = 0; j < op.wait_ops.size(); ++j) o << (j ? "," : "") << op.wait_ops[j];

@@ -128,6 +128,8 @@ struct POp {
     // OP_CONV_GROUP: the member convolutions, each a complete OP_CONV record (its own in / out tensors, ConvArgs, weights); the group's
     // in / out are the unions, so dependencies, lanes and buffer lifetimes see one op
     std::vector<POp> group;
+    bool sibling_pair = false; // OP_CONV_GROUP right behind another one whose members read the same tensors with the same geometry: the engine computes BOTH groups in
+                               // ONE launch at this op (kernels/igemm_tile.h, the dual tile); the op before it then launches nothing
     int src_layer = -1;        // network layer holding the kernel weights
     int scale_layer = -1;      // folded IScaleLayer (BatchNorm) or -1
     size_t w_off = 0, b_off = 0, s_off = 0;  // byte offsets into the device weight blob

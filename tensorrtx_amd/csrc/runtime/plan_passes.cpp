@@ -815,6 +815,80 @@ void mark_bneck_pair(Plan& plan, const PassInputs& e) {
     }
 }
 
+// Two grouped launches whose members read the same tensors in one launch (the dual tile of kernels/igemm_tile.h; YOLOv8's cv2.{0,1,2}.0 -> 64 and
+// cv3.{0,1,2}.0 -> 80 read the same three pyramid levels): marks the SECOND group (POp::sibling_pair); kinds, names, members, tensors and the arena's blocks stay what
+// they are - the executor issues the one launch at the marked op and nothing at the group before it.  Marked when both are OP_CONV_GROUP with the same member
+// count, every member of one has a member of the other that reads the same tensor view with the same geometry (no shortcut on either), neither group depends on
+// the other, no output shares channels of a block with an input or another output, and conv_dual_group_possible() takes the members at the largest batch.  A second
+// group that does not directly follow the first is moved there if nothing in between is one of its ancestors (RAW, WAR or WAW: the order stays topological);
+// otherwise the pair is left alone.  Only plans of ONE lane are looked at - engines built for several contexts in flight, setMaxAuxStreams(0): with auxiliary
+// streams assign_lanes() puts two independent groups on different streams, where they overlap, and the pair would lose its mark again (finalize_plan() drops a
+// mark whose two ops sit on different lanes or whose first op another lane waits for) after its second group was moved for nothing: such plans stay exactly
+// what they were.  Not part of the serialized network.  TRTX_SIBLING_PAIR=0 marks nothing (A/B, tests).
+int lane_limit(const PassInputs& e) {
+    int max_lanes = e.max_aux_streams >= 0 ? 1 + e.max_aux_streams : 4;  // IBuilderConfig::setMaxAuxStreams
+    if (e.opt.lanes > 0) max_lanes = std::max(1, std::min(16, e.opt.lanes));  // A/B override (TRTX_LANES)
+    return max_lanes;
+}
+void mark_sibling_pair(Plan& plan, const PassInputs& e) {
+    if (!e.opt.sibling_pair || e.dt != DT_F16 || e.int8 || CalibrationLowering::active()) return;
+    if (lane_limit(e) > 1) return;   // (see above: with several lanes the plan, its op order included, stays what it was)
+    const int n = (int)plan.ops.size();
+    if (n < 2 || n > 4096) return;
+    auto member_args = [&](const POp& m) {
+        ConvArgs a = m.conv;   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
+        const PTensor& ti = plan.tensors[m.in[0]];
+        a.N = (ti.nfix ? ti.nfix : plan.max_batch) * ti.nmul;
+        a.M = a.N * a.Ho * a.Wo;
+        return a;
+    };
+    auto shares_elements = [&](int t, int u) {
+        const PTensor &x = plan.tensors[t], &y = plan.tensors[u];
+        if (x.storage != y.storage) return false;
+        if (x.layout != LAY_NHWC || y.layout != LAY_NHWC) return true;
+        return x.rcoff < y.rcoff + std::max(y.C, 1) && y.rcoff < x.rcoff + std::max(x.C, 1);
+    };
+    auto mark_one = [&]() {   // (a move changes the op indices: dependencies are taken anew for every pair)
+        const std::vector<std::vector<int>> deps = op_dependencies(plan);
+        const Ancestors anc = ancestors(plan, deps, false);
+        for (int i = 0; i + 1 < n; ++i) {
+            const POp& a = plan.ops[i];
+            if (a.kind != OP_CONV_GROUP || a.sibling_pair || plan.ops[i + 1].sibling_pair || a.group.empty() || (int)a.group.size() > kMaxDualGroup) continue;
+            for (int j = i + 1; j < n; ++j) {
+                const POp& b = plan.ops[j];
+                if (b.kind != OP_CONV_GROUP || b.sibling_pair || (j + 1 < n && plan.ops[j + 1].sibling_pair) || b.group.size() != a.group.size()) continue;
+                // members pairwise on the same tensor view (b's in the order of a's), the 64-wide side first
+                std::vector<ConvArgs> xa, xb;
+                bool ok = true;
+                for (const POp& ma : a.group) {
+                    const POp* mb = nullptr;
+                    for (const POp& c : b.group)
+                        if (c.in.size() == 1 && ma.in.size() == 1 && c.in[0] == ma.in[0]) mb = &c;
+                    if (!mb || !ma.extra_in.empty() || !mb->extra_in.empty()) { ok = false; break; }
+                    xa.push_back(member_args(ma));
+                    xb.push_back(member_args(*mb));
+                }
+                if (!ok) continue;
+                const int gn = (int)xa.size();
+                if (!conv_dual_group_possible(xa.data(), xb.data(), gn) && !conv_dual_group_possible(xb.data(), xa.data(), gn)) continue;
+                for (int t : a.out) {
+                    for (int u : a.in) ok = ok && !shares_elements(t, u);
+                    for (int u : b.out) ok = ok && !shares_elements(t, u);
+                }
+                for (int t : b.out)
+                    for (int u : a.in) ok = ok && !shares_elements(t, u);
+                for (int k = i; k < j; ++k) ok = ok && !anc.has(k, j);   // independent of the first group, and free to move up behind it
+                if (!ok) continue;
+                if (j != i + 1) std::rotate(plan.ops.begin() + i + 1, plan.ops.begin() + j, plan.ops.begin() + j + 1);
+                plan.ops[i + 1].sibling_pair = true;
+                return true;
+            }
+        }
+        return false;
+    };
+    while (mark_one()) {}
+}
+
 // Lanes (= HIP streams at run time): an op continues the lane of a dependency that is still that lane's tail,
 // otherwise it opens a free lane, otherwise it queues behind the lane that went idle first.  Independent branches
 // (the six cv2/cv3 head chains of YOLOv8, model.cpp:224-291; FPN/SSH branches of RetinaFace) end up on different
@@ -825,8 +899,7 @@ void mark_bneck_pair(Plan& plan, const PassInputs& e) {
 // adds an H2D stream; ResNet-50 / RetinaFace / R-CNN are 0.5-1.3 % faster with 4.  (8 or 16 hardware queues: 2.2x slower.)
 void assign_lanes(Plan& plan, const PassInputs& e, const std::vector<std::vector<int>>& deps) {
     const int nops = (int)plan.ops.size();
-    int max_lanes = e.max_aux_streams >= 0 ? 1 + e.max_aux_streams : 4;  // IBuilderConfig::setMaxAuxStreams
-    if (e.opt.lanes > 0) max_lanes = std::max(1, std::min(16, e.opt.lanes));  // A/B override (TRTX_LANES)
+    const int max_lanes = lane_limit(e);
     std::vector<int> tail(max_lanes, -1);
     plan.num_lanes = 1;
     for (int k = 0; k < nops; ++k) {
@@ -884,6 +957,9 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
         // live here too, so the output's block can never be placed on it (two launches may run in place, the fused kernel may not)
         if (op.bneck_pair && k > 0)
             for (int t : plan.ops[k - 1].in) mark(t);
+        // a marked sibling pair is ONE launch, issued at this op, that also writes the first group's outputs: they are live here (and the inputs are this op's own)
+        if (op.sibling_pair && k > 0)
+            for (int t : plan.ops[k - 1].out) mark(t);
     }
     // plugin workspaces are short-lived arena blocks
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
@@ -945,6 +1021,7 @@ bool finalize_plan(Plan& plan, const PassInputs& e, std::string* err) {
     chain_sppf_pools(plan, e);
     chain_spp_parallel_pools(plan, e);
     group_convs(plan, e);
+    mark_sibling_pair(plan, e);
     mark_stem_pair(plan, e);
     mark_bneck_pair(plan, e);
     const std::vector<std::vector<int>> deps = op_dependencies(plan);   // (group_convs reordered and merged ops: not its list)
@@ -953,6 +1030,8 @@ bool finalize_plan(Plan& plan, const PassInputs& e, std::string* err) {
     // the first op alone (its event would fire before the launch that reads its input)
     for (size_t k = 1; k < plan.ops.size(); ++k)
         if (plan.ops[k].bneck_pair && (plan.ops[k].lane != plan.ops[k - 1].lane || plan.ops[k - 1].signal)) plan.ops[k].bneck_pair = false;
+    for (size_t k = 1; k < plan.ops.size(); ++k)   // ... and the same rule for the two groups of a sibling pair
+        if (plan.ops[k].sibling_pair && (plan.ops[k].lane != plan.ops[k - 1].lane || plan.ops[k - 1].signal)) plan.ops[k].sibling_pair = false;
     plan_arena(plan, ancestors(plan, deps, true));
     return true;
 }
