@@ -105,6 +105,44 @@ int32_t trtx_yolo_task_head_decode_nhwc_f32(const void* const* heads, const int*
                                             float kpt_conf, float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
 
 /*
+ * YOLOv10 YoloLayer.  Replaces YoloLayerPlugin::forwardGpu + CalDetection of yolov10/plugin/yololayer.cu:157-240.  The per-cell
+ * arithmetic is trtx_yolo_decode's (sigmoid, strict-'>' argmax from (0.0, class 0), dropped below 0.1, (col + .5 -/+ d) * stride); the
+ * record is Detection = bbox[4] (xyxy), conf, class_id (yolov10/include/types.h), 6 floats.
+ *   inputs[l]  device, fp32 [batch][4 + classes][(net_h / strides[l]) * (net_w / strides[l])]
+ *   output     device, fp32 [batch][1 + max_out * 6]: count (clamped to max_out), then the records in canonical (level, cell) order.
+ *              Nothing of a row is written behind its records.
+ * Workspace: trtx_yolo_decode_workspace.  TRTX_ERR_INVALID, before the device is touched, for a null pointer (a level's too),
+ * n_levels outside 1..8, batch / classes / max_out / net_h / net_w < 1 or a stride < 1; TRTX_ERR_WORKSPACE.
+ */
+int32_t trtx_yolov10_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                            int max_out, float* output, void* workspace, size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * Fused YOLOv10 head: the DFL chain (yolov10/src/block.cpp:214-233, model.cpp:202-252) and trtx_yolov10_decode on the detect head's own
+ * NHWC output, read exactly as trtx_yolo_head_decode_nhwc reads it (classes % 8 == 0) or as trtx_yolo_task_head_decode_nhwc does (any
+ * other class count >= 1: the last classes % 8 logits one by one, so the padding channels never reach the argmax).
+ *   heads[l]   device fp16 [batch][cells_l][ld[l]]: channels [0, 64) DFL bins, [64, 64 + classes) logits; ld[l] >= 64 + classes and,
+ *              like the base, a 16-byte multiple (else TRTX_ERR_UNSUPPORTED).  Output and order: trtx_yolov10_decode.
+ */
+size_t trtx_yolov10_head_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels);
+int32_t trtx_yolov10_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                      const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                      size_t workspace_bytes, trtx_stream_t stream);
+/* The same on the NHWC fp32 head tensors of an fp32 engine: ld in floats. */
+int32_t trtx_yolov10_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                          const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                          size_t workspace_bytes, trtx_stream_t stream);
+/*
+ * The device side of YOLOv10's get_topk / batch_topk (yolov10/src/postprocess.cpp:35-52), which is all the post-processing the
+ * NMS-free head has.  decode_out and out: device, fp32 [batch][1 + max_out * 6], two different buffers.
+ *   topk <= 0  the reference (its `topk` argument is unused): the records with conf > conf_thresh, in slot order
+ *   topk > 0   of those, the topk highest confidences, by descending conf, ties in slot order (a stable rank)
+ * out[b][0] = records written; nothing is written behind them.  A NaN conf fails the '>'; a header above max_out is clamped.
+ * max_out <= 1024, beyond it TRTX_ERR_UNSUPPORTED like trtx_yolov7_nms; TRTX_ERR_INVALID for a null pointer, out == decode_out,
+ * batch < 1 or max_out < 1.  No workspace.
+ */
+int32_t trtx_yolov10_topk(const float* decode_out, int batch, int max_out, float conf_thresh, int topk, float* out, trtx_stream_t stream);
+
+/*
  * Class-aware greedy NMS over the decode buffer.  Replaces host batch_nms()/nms()
  * (reference yolov8/src/postprocess.cpp:71-129; call site yolov8/yolov8_det.cpp:240).
  *   decode_out device, fp32 [batch][1 + max_out*90]  (output of trtx_yolo_decode)
@@ -463,6 +501,11 @@ int32_t trtx_op_conv_dual_group_or_two_f16(int n, const void* const* in, const i
  * concatenated, then a kh x kw stride-1 padding-p convolution): w_kcrs [cout][4 cin][kh][kw] -> folded [cout][cin][2kh][2kw], the filter
  * of the equal stride-2 padding-2p convolution of x, folded[o][c][2i + dy][2j + dx] = w[o][q cin + c][i][j], q = 2 dx + dy.  Host arrays. */
 int32_t trtx_reorg_fold_weights(const float* w_kcrs, int cout, int cin, int kh, int kw, float* folded);
+/* The filter and shift the lowering packs for RepVGGDW (yolov10/src/block.cpp:388-403: SiLU(dw7x7 + BN + dw3x3 + BN) on one tensor) as ONE
+ * depthwise 7x7 convolution: w_out[c] = scale7[c] * w7[c] with scale3[c] * w3[c] added into its centre, shift_out[c] = shift7[c] + shift3[c];
+ * double arithmetic, rounded once to fp32.  Host arrays: w7 [channels][7][7], w3 [channels][3][3], the rest [channels]. */
+int32_t trtx_repvggdw_fold_weights(const float* w7, const float* scale7, const float* shift7, const float* w3, const float* scale3,
+                                   const float* shift3, int channels, float* w_out, float* shift_out);
 int32_t trtx_conv_packed_dims_f32(int cout, int cin_pad, int kh, int kw, int32_t* cout_pad, int32_t* kpad, int32_t* cink);
 int32_t trtx_conv_pack_weights_f32(const float* w_kcrs, int cout, int cin, int kh, int kw, int cin_pad, const float* ch_scale, float* packed);
 int32_t trtx_op_conv2d_nhwc_f32(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out, int Cout,
@@ -499,7 +542,7 @@ int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int H, int W, i
                                trtx_stream_t stream);
 /* The fused attention kernels (tests / tools).  qkv: NHWC fp16 [B][N][ld_qkv], head h's channels start at h * (2 kd + hd): q (kd), k (kd), v (hd).
  * out[b][n][h * hd + d] = sum_m softmax_m(scale * q_n . k_m) v[m][d] and vimg[b][n][h * hd + d] = v[n][d], fp16 with pixel strides ld_out / ld_v.
- * psa: kd 32, hd 64, every pixel of the image is a key (kernels/attention.hip).  area: kd 32, hd 32, the N pixels split into `area` contiguous ranges of
+ * psa: kd 32, hd 64 (or kd 36, hd 72: yolov10m), every pixel of the image is a key (kernels/attention.hip).  area: kd 32, hd 32, the N pixels split into `area` contiguous ranges of
  * N / area that attend within themselves (kernels/attention_mfma.hip); pointers or strides that rule out 16-byte loads / 8-byte stores take element-wise ones.
  * TRTX_ERR_UNSUPPORTED, nothing launched: another kd / hd, N % area != 0, ld_qkv < heads * (2 kd + hd), ld_out or ld_v < heads * hd. */
 int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd, float scale,

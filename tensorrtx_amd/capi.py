@@ -327,6 +327,18 @@ def reorg_fold_weights(w):
     return out
 
 
+def repvggdw_fold_weights(w7, scale7, shift7, w3, scale3, shift3):
+    """trtx_repvggdw_fold_weights: numpy fp32 depthwise filters [C, 1, 7, 7] and [C, 1, 3, 3] with their per-channel scales and shifts ->
+    (w [C, 1, 7, 7], shift [C]), what the lowering packs for a folded RepVGGDW."""
+    import numpy as np
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (w7, scale7, shift7, w3, scale3, shift3)]
+    C = a[0].shape[0]
+    w, sh = np.empty((C, 1, 7, 7), np.float32), np.empty(C, np.float32)
+    ptr = lambda v: v.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    check(lib().trtx_repvggdw_fold_weights(*[ptr(v) for v in a], C, ptr(w), ptr(sh)), "trtx_repvggdw_fold_weights")
+    return w, sh
+
+
 def yolov7_decode(inputs, classes, net_h, net_w, grids, anchors, max_out=1000, out=None):
     """YOLOv7 YoloLayerPlugin::enqueue replacement (yolov7/plugin/yololayer.cu:152-207).
     inputs: CUDA fp32 [B, 3*(5+classes), gh*gw] per level; grids: [(gw, gh)]; anchors: [n_levels][6].  -> [B, 1+max_out*6]
@@ -848,4 +860,75 @@ def conv2d_nhwc_i8(x_i8, wpacked, cscale, bias, cout, kh, kw, stride, pad, act1=
                                        ctypes.c_float(1.0 / out_scale if out_scale else 0.0), cout, out_ld or out.shape[-1], kh, kw, sh, sw, ph, pw, ACT[act1],
                                        _p(residual), 1 if res_i8 else 0, ctypes.c_float(res_scale), residual.stride(2) if residual is not None else 0,
                                        ACT[act2], _stream()), "trtx_op_conv2d_nhwc_i8")
+    return out
+
+
+DET10_FLOATS = 6   # yolov10/include/types.h: bbox[4] (xyxy), conf, class_id
+
+
+def yolov10_decode(inputs, classes, net_h, net_w, strides, max_out=1000, out=None, ws=None, batch=None, n_levels=None, status_only=False):
+    """YOLOv10 YoloLayerPlugin::enqueue replacement (yolov10/plugin/yololayer.cu:157-240): trtx_yolov10_decode.
+    inputs: CUDA fp32 tensors [B, 4 + classes, gh * gw] (None: a null level pointer).  -> [B, 1 + max_out * 6].  `out` / `ws`: the caller's
+    buffers; `batch`, `n_levels`: what is passed instead of the tensors' own; `strides` None: a null pointer; `status_only`: the status code."""
+    import torch
+    L = lib()
+    first = next(x for x in inputs if x is not None)
+    B, n, dev = first.shape[0] if batch is None else batch, len(inputs), first.device
+    ins = [None if x is None else x.contiguous() for x in inputs]
+    arr = (ctypes.c_void_p * n)(*[0 if x is None else x.data_ptr() for x in ins])
+    st = None if strides is None else (ctypes.c_int * len(strides))(*strides)
+    if ws is None:
+        ws = torch.empty(max(L.trtx_yolo_decode_workspace(max(B, 1), net_h, net_w, st, len(strides or ())), 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros((max(B, 1), 1 + max_out * DET10_FLOATS), dtype=torch.float32, device=dev)
+    status = L.trtx_yolov10_decode(arr, n if n_levels is None else n_levels, B, classes, net_h, net_w, st, max_out, _p(out), _p(ws),
+                                   ctypes.c_size_t(ws.numel()), _stream())
+    if status_only:
+        return status
+    check(status, "trtx_yolov10_decode")
+    return out
+
+
+def yolov10_head_decode_workspace(batch, net_h, net_w, strides):
+    L = lib()
+    L.trtx_yolov10_head_decode_workspace.restype = ctypes.c_size_t
+    return L.trtx_yolov10_head_decode_workspace(batch, net_h, net_w, (ctypes.c_int * len(strides))(*strides), len(strides))
+
+
+def yolov10_head_decode_nhwc(heads, classes, net_h, net_w, strides, dfl_w, max_out=1000, out=None, ws=None, batch=None, ld=None, n_levels=None,
+                             status_only=False):
+    """The fused YOLOv10 head on NHWC head tensors [B, gh, gw, ld] (fp16 or fp32): trtx_yolov10_head_decode_nhwc{,_f32}, any class count.
+    -> [B, 1 + max_out * 6].  The keyword arguments as in yolo_head_decode_nhwc."""
+    import torch
+    L = lib()
+    hp, hl = _head_table(heads)
+    if ld is not None:
+        hl = (ctypes.c_int * len(ld))(*ld)
+    B, n, dev = heads[0].shape[0] if batch is None else batch, len(heads), heads[0].device
+    st = None if strides is None else (ctypes.c_int * len(strides))(*strides)
+    if ws is None:
+        ws = torch.empty(max(yolov10_head_decode_workspace(B, net_h, net_w, strides), 256), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros(B, 1 + max_out * DET10_FLOATS, dtype=torch.float32, device=dev)
+    fn = L.trtx_yolov10_head_decode_nhwc_f32 if heads[0].dtype == torch.float32 else L.trtx_yolov10_head_decode_nhwc
+    status = fn(hp, hl, n if n_levels is None else n_levels, B, classes, net_h, net_w, st, _p(dfl_w), max_out, _p(out), _p(ws),
+                ctypes.c_size_t(ws.numel()), _stream())
+    if status_only:
+        return status
+    check(status, "trtx_yolov10_head_decode_nhwc")
+    return out
+
+
+def yolov10_topk(decode_out, max_out=1000, conf_thresh=0.5, topk=0, out=None, batch=None, status_only=False):
+    """get_topk / batch_topk on the device (yolov10/src/postprocess.cpp:35-52): trtx_yolov10_topk.  decode_out [B, 1 + max_out * 6] ->
+    a buffer of the same shape: row[0] = records kept, then the records.  topk <= 0: conf > conf_thresh in slot order (the reference);
+    topk > 0: the topk highest of those by descending conf, ties in slot order.  `out`: the caller's buffer (None: zeros)."""
+    import torch
+    B = decode_out.shape[0] if batch is None else batch
+    if out is None:
+        out = torch.zeros((max(B, 1), 1 + max_out * DET10_FLOATS), dtype=torch.float32, device=decode_out.device)
+    status = lib().trtx_yolov10_topk(_p(decode_out), B, max_out, ctypes.c_float(conf_thresh), int(topk), _p(out), _stream())
+    if status_only:
+        return status
+    check(status, "trtx_yolov10_topk")
     return out

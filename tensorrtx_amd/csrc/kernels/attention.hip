@@ -1,5 +1,5 @@
-// Fused PSA attention of YOLO11's C2PSA (yolo11/src/block.cpp:287-339): per image b and head h, with q, k (kd = 32 channels) and v
-// (hd = 64 channels) read straight from the NHWC fp16 qkv tensor (head h's channels start at h * (2 kd + hd): q, then k, then v),
+// Fused PSA attention of YOLO11's C2PSA (yolo11/src/block.cpp:287-339) and YOLOv10's PSA (yolov10/src/block.cpp:297-386): per image b and
+// head h, with q, k (kd = 32 channels; 36 in yolov10m) and v (hd = 64 channels; 72 in yolov10m) read straight from the NHWC fp16 qkv tensor (head h's channels start at h * (2 kd + hd): q, then k, then v),
 //     O[b, n, h*hd + d] = sum_m v[d, m] * softmax_m(scale * sum_j q[j, n] k[j, m])
 // written NHWC fp16 with the consumer's channel stride, plus the gathered V image Vimg[b, n, h*hd + d] = v[d, n] that the positional
 // conv `pe` reads (its epilogue adds O as the residual).  Replaces the qkv view -> slices -> transpose -> matmul -> scale -> softmax ->
@@ -19,8 +19,11 @@
 namespace trtx {
 namespace {
 
-constexpr int KD = 32, HD = 64, QB = 64, KB = 64;
+constexpr int QB = 64, KB = 64;
 
+// KD / HD = key / value channels per head: 32 / 64 (YOLO11's C2PSA and YOLOv10's PSA with 64-channel heads) or 36 / 72 (yolov10m: its
+// 288-channel PSA half has 288 / 64 = 4 heads of 72, yolov10/src/block.cpp:297-303, 360-371)
+template <int KD, int HD>
 __global__ __launch_bounds__(QB) void psa_attention_kernel(const _Float16* __restrict__ qkv, int ld_qkv, _Float16* __restrict__ out,
                                                            int ld_out, _Float16* __restrict__ vimg, int ld_v, int N, int heads, float scale) {
     __shared__ float Ks[KB][KD + 1];
@@ -77,15 +80,20 @@ __global__ __launch_bounds__(QB) void psa_attention_kernel(const _Float16* __res
 
 }  // namespace
 
-bool psa_attention_supported(int kd, int hd) { return kd == KD && hd == HD; }
+bool psa_attention_supported(int kd, int hd) { return (kd == 32 && hd == 64) || (kd == 36 && hd == 72); }
 
 int32_t psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
                           float scale, hipStream_t s) {
     if (!psa_attention_supported(kd, hd) || B < 1 || heads < 1 || N < 1 || B > 65535 || heads > 65535 || ld_qkv < heads * (2 * kd + hd) ||
         ld_out < heads * hd || ld_v < heads * hd)
         return TRTX_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(psa_attention_kernel, dim3((N + QB - 1) / QB, heads, B), dim3(QB), 0, s, static_cast<const _Float16*>(qkv), ld_qkv,
-                       static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, heads, scale);
+    const dim3 grid((N + QB - 1) / QB, heads, B);
+    if (kd == 36)
+        hipLaunchKernelGGL((psa_attention_kernel<36, 72>), grid, dim3(QB), 0, s, static_cast<const _Float16*>(qkv), ld_qkv,
+                           static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, heads, scale);
+    else
+        hipLaunchKernelGGL((psa_attention_kernel<32, 64>), grid, dim3(QB), 0, s, static_cast<const _Float16*>(qkv), ld_qkv,
+                           static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, heads, scale);
     return check_launch("psa_attention");
 }
 

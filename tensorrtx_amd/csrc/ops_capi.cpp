@@ -461,6 +461,14 @@ extern "C" int32_t trtx_op_poison_lds(void* device_word, trtx_stream_t stream) {
 }
 
 
+extern "C" int32_t trtx_repvggdw_fold_weights(const float* w7, const float* scale7, const float* shift7, const float* w3, const float* scale3,
+                                              const float* shift3, int channels, float* w_out, float* shift_out) {
+    if (!w7 || !scale7 || !shift7 || !w3 || !scale3 || !shift3 || !w_out || !shift_out || channels < 1) return TRTX_ERR_INVALID;
+    const std::vector<float> zero(channels, 0.f);   // the reference's depthwise convolutions carry no bias of their own
+    repvggdw_fold_weights(w7, scale7, shift7, zero.data(), w3, scale3, shift3, zero.data(), channels, w_out, shift_out);
+    return TRTX_OK;
+}
+
 extern "C" int32_t trtx_reorg_fold_weights(const float* w_kcrs, int cout, int cin, int kh, int kw, float* folded) {
     if (!w_kcrs || !folded || cout < 1 || cin < 1 || kh < 1 || kw < 1) return TRTX_ERR_INVALID;
     reorg_fold_weights(w_kcrs, cout, cin, kh, kw, folded);

@@ -46,6 +46,8 @@ Options read_options() {
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);
     o.yolo7_head = !env_is("TRTX_YOLO7_HEAD", 0);
     o.darknet_head = !env_is("TRTX_DARKNET_HEAD", 0);
+    o.yolo10_head = !env_is("TRTX_YOLO10_HEAD", 0);
+    o.repvggdw_fold = !env_is("TRTX_REPVGGDW_FOLD", 0);
     o.reorg_fold = !env_is("TRTX_REORG_FOLD", 0);
     o.spp_parallel_chain = !env_is("TRTX_SPP_PARALLEL_CHAIN", 0);
     o.yolo9_head = !env_is("TRTX_YOLO9_HEAD", 0);

@@ -42,6 +42,8 @@ struct Options {
     bool yolo5_head = true;      // TRTX_YOLO5_HEAD=0: the anchor-based (YOLOv5) detect tail keeps the plugin route (layout passes to fp32 planes + YoloLayer_TRT)
     bool yolo7_head = true;      // TRTX_YOLO7_HEAD=0: the YOLOv7 detect tail keeps the plugin route (layout passes to fp32 planes + the 6-float YoloLayer_TRT)
     bool darknet_head = true;    // TRTX_DARKNET_HEAD=0: the Darknet (YOLOv3 / YOLOv3-tiny / YOLOv4) detect tail keeps the plugin route (layout passes to fp32 planes + the 7-float YoloLayer_TRT)
+    bool yolo10_head = true;     // TRTX_YOLO10_HEAD=0: the YOLOv10 detect tail keeps the plugin route (layout passes, the DFL chain, concat scatters + the 6-float YoloLayer_TRT)
+    bool repvggdw_fold = true;   // TRTX_REPVGGDW_FOLD=0: RepVGGDW (7x7 + 3x3 depthwise on one tensor, sum, SiLU) stays two depthwise launches, a sigmoid and a product
     bool reorg_fold = true;      // TRTX_REORG_FOLD=0: ReOrg (four stride-2 slices + concat) in front of a convolution stays four gathers, a concat and that convolution
     bool spp_parallel_chain = true;   // TRTX_SPP_PARALLEL_CHAIN=0: SPP's three parallel 'same' max-pools (k, 2k-1, 3k-2) of one tensor stay three pool launches
     bool roialign_fused = true;  // TRTX_ROIALIGN_PLUGIN=1: RoIAlign stays a plugin op (fp32 NCHW edge)

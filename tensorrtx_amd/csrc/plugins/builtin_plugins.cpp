@@ -471,6 +471,123 @@ int32_t yolo9_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The YOLOv10 form of "YoloLayer_TRT"/"1" (yolov10/plugin/yololayer.{h,cu}; the same registered name once more): ONE creator field
+// "combinedInfo" = int32[4 + n] {classes, W, H, maxOut, strides...} (yolov10/src/block.cpp:235-277, yololayer.cu:263-278) with n = 1..5,
+// i.e. 5 to 9 ints, all >= 1; ten and more are YOLOv8's.  Blob in the reference's order (yololayer.cu:64-79): int classCount,
+// threadCount (256), netW, netH, maxOut, nStrides, strides[n] = 24 + 4 n bytes.  One (4 + classes, cells) input per level; output
+// 1 + maxOut * 6 floats (Detection = bbox[4], conf, class_id).
+// The lengths 28, 32, 36, 40 and 44 belong to no other form: YOLOv8's 35 + 4 n and YOLOv5's 25 + 32 n are odd, YOLOv9's is 21, and the
+// smallest YOLOv7 (24 + 32 n, n >= 1) and non-empty Darknet (20 + 32 n) blobs are 56 and 52 bytes, the empty Darknet one 20.
+constexpr int kYolo10DetFloats = 6;
+struct Yolo10Layer {
+    int class_count = 80, thread_count = 256, net_w = 640, net_h = 640, max_out = 1000;
+    std::vector<int> strides;
+
+    std::vector<uint8_t> blob() const {
+        std::vector<uint8_t> b;
+        put(b, class_count);
+        put(b, thread_count);
+        put(b, net_w);
+        put(b, net_h);
+        put(b, max_out);
+        put(b, (int)strides.size());
+        for (int s : strides) put(b, s);
+        return b;
+    }
+    // accepted by its exact length and a stride count that agrees with it only
+    static Yolo10Layer* from_blob(const void* data, size_t len) {
+        if (len < 28 || len > 44 || len % 4) return nullptr;
+        const uint8_t* p = static_cast<const uint8_t*>(data);
+        const uint8_t* end = p + len;
+        auto* y = new Yolo10Layer();
+        int ns = 0;
+        bool ok = get(p, end, y->class_count) && get(p, end, y->thread_count) && get(p, end, y->net_w) && get(p, end, y->net_h) &&
+                  get(p, end, y->max_out) && get(p, end, ns) && ns >= 1 && ns <= 5 && (size_t)(end - p) == (size_t)ns * sizeof(int);
+        for (int i = 0; ok && i < ns; ++i) {
+            int s = 0;
+            ok = get(p, end, s) && s >= 1;
+            y->strides.push_back(s);
+        }
+        if (!ok || y->class_count < 1 || y->net_w < 1 || y->net_h < 1 || y->max_out < 1) {
+            delete y;
+            return nullptr;
+        }
+        return y;
+    }
+};
+void yolo10_fill(trtx_plugin_vtbl* v, Yolo10Layer* y);
+int32_t yolo10_output_dims(void* s, int32_t, const trtx_dims*, int32_t, trtx_dims* out) {
+    auto* y = static_cast<Yolo10Layer*>(s);
+    out->nb = 3;  // Dims3(maxOut * sizeof(Detection) / 4 + 1, 1, 1), yololayer.cu:90-94
+    out->d[0] = (int64_t)y->max_out * kYolo10DetFloats + 1;
+    out->d[1] = 1;
+    out->d[2] = 1;
+    return 0;
+}
+int32_t yolo10_configure(void* s, const trtx_dims* in, int32_t nb_in, const trtx_dims*, int32_t, int32_t) {
+    auto* y = static_cast<Yolo10Layer*>(s);
+    if (nb_in != (int)y->strides.size()) return 1;
+    for (int i = 0; i < nb_in; ++i) {
+        const int64_t cells = (int64_t)(y->net_h / y->strides[i]) * (y->net_w / y->strides[i]);
+        int64_t vol = 1;
+        for (int k = 0; k < in[i].nb; ++k) vol *= in[i].d[k];
+        if (cells < 1 || vol % (cells * (4 + y->class_count))) return 1;  // [batch][4 + classes][cells]
+    }
+    return 0;
+}
+size_t yolo10_workspace(void* s, int32_t max_batch) {
+    auto* y = static_cast<Yolo10Layer*>(s);
+    return trtx_yolo_decode_workspace(max_batch, y->net_h, y->net_w, y->strides.data(), (int)y->strides.size());
+}
+int32_t yolo10_enqueue(void* s, int32_t batch, const void* const* inputs, void* const* outputs, void* ws, trtx_stream_t stream) {
+    auto* y = static_cast<Yolo10Layer*>(s);
+    const size_t ws_bytes = trtx_yolo_decode_workspace(batch, y->net_h, y->net_w, y->strides.data(), (int)y->strides.size());
+    return trtx_yolov10_decode(reinterpret_cast<const float* const*>(inputs), (int)y->strides.size(), batch, y->class_count, y->net_h, y->net_w,
+                               y->strides.data(), y->max_out, static_cast<float*>(outputs[0]), ws, ws_bytes, stream);
+}
+size_t yolo10_ser_size(void* s) { return static_cast<Yolo10Layer*>(s)->blob().size(); }
+void yolo10_serialize(void* s, void* buf) {
+    const auto b = static_cast<Yolo10Layer*>(s)->blob();
+    memcpy(buf, b.data(), b.size());
+}
+int32_t yolo10_clone(void* s, trtx_plugin_vtbl* out) {
+    yolo10_fill(out, new Yolo10Layer(*static_cast<Yolo10Layer*>(s)));
+    return 0;
+}
+void yolo10_destroy(void* s) { delete static_cast<Yolo10Layer*>(s); }
+void yolo10_fill(trtx_plugin_vtbl* v, Yolo10Layer* y) {
+    v->self = y;
+    v->get_nb_outputs = yolo_nb_outputs;
+    v->get_output_dims = yolo10_output_dims;
+    v->configure = yolo10_configure;
+    v->initialize = no_initialize;
+    v->terminate = yolo_terminate;
+    v->workspace_size = yolo10_workspace;
+    v->enqueue = yolo10_enqueue;
+    v->serialization_size = yolo10_ser_size;
+    v->serialize = yolo10_serialize;
+    v->plugin_type = yolo_type;
+    v->plugin_version = yolo_version;
+    v->clone = yolo10_clone;
+    v->destroy = yolo10_destroy;
+}
+// "combinedInfo" of 5 to 9 ints, all >= 1
+int32_t yolo10_create(const trtx_plugin_field* f, trtx_plugin_vtbl* out) {
+    if (!f[0].data || f[0].length < 5 || f[0].length > 9) return 1;
+    const int* ci = static_cast<const int*>(f[0].data);
+    for (int i = 0; i < f[0].length; ++i)
+        if (ci[i] < 1) return 1;
+    auto* y = new Yolo10Layer();
+    y->class_count = ci[0];
+    y->net_w = ci[1];
+    y->net_h = ci[2];
+    y->max_out = ci[3];
+    y->strides.assign(ci + 4, ci + f[0].length);
+    yolo10_fill(out, y);
+    return 0;
+}
+
 // creator: one field "combinedInfo" = int32[9 + nStrides] (yolov8/src/block.cpp:267-293, yololayer.cu:339-360)
 int32_t yolo_create(void*, const char*, const trtx_plugin_field* f, int32_t nb, trtx_plugin_vtbl* out) {
     // no fields at all: the Darknet form (yolov4/yololayer.cu:258-263 ignores its field collection, and the creator's own is empty)
@@ -488,6 +605,8 @@ int32_t yolo_create(void*, const char*, const trtx_plugin_field* f, int32_t nb, 
         return anchor_create(f, out);
     // ... and so does the YOLOv9 one: its single field is "netinfo"
     if (nb == 1 && f && f[0].name && !strcmp(f[0].name, "netinfo")) return yolo9_create(f, out);
+    // "combinedInfo" of 5 to 9 ints is YOLOv10's (four ints + 1 to 5 strides); ten and more is YOLOv8's, fewer are refused
+    if (nb == 1 && f && f[0].name && !strcmp(f[0].name, "combinedInfo") && f[0].length >= 5 && f[0].length <= 9) return yolo10_create(f, out);
     if (nb != 1 || !f || !f[0].name || strcmp(f[0].name, "combinedInfo") != 0 || f[0].length < 10) return 1;
     const int* ci = static_cast<const int*>(f[0].data);
     auto* y = new YoloLayer();
@@ -530,8 +649,14 @@ int32_t yolo_deserialize(void*, const char*, const void* data, size_t len, trtx_
     }
     // ... and the Darknet blob, 20 + 32 n bytes: even, so none of 35 + 4 n, 25 + 32 n and 21, and 4 short of YOLOv7's 24 + 32 n
     AnchorLayer* yd = AnchorLayer::from_darknet_blob(data, len);
-    if (!yd) return 1;
-    anchor_fill(out, yd);
+    if (yd) {
+        anchor_fill(out, yd);
+        return 0;
+    }
+    // ... and the YOLOv10 blob, 24 + 4 n bytes with n = 1..5: a length no parser above accepts (see Yolo10Layer)
+    Yolo10Layer* y10 = Yolo10Layer::from_blob(data, len);
+    if (!y10) return 1;
+    yolo10_fill(out, y10);
     return 0;
 }
 const char* yolo_creator_name(void*) { return "YoloLayer_TRT"; }
@@ -749,9 +874,24 @@ bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out) {
     return true;
 }
 
+bool builtin_yolo10_params(const trtx_plugin_vtbl& v, YoloLayerParams* out) {
+    if (v.enqueue != yolo10_enqueue || !v.self) return false;
+    const auto* y = static_cast<const Yolo10Layer*>(v.self);
+    out->classes = y->class_count;
+    out->net_w = y->net_w;
+    out->net_h = y->net_h;
+    out->max_out = y->max_out;
+    out->strides = y->strides;
+    out->det_only = true;
+    out->seg = out->pose = out->obb = false;
+    out->nk = 0;
+    out->kpt_conf = 0.f;
+    return true;
+}
+
 // built-in plugins only enqueue kernels and stream-ordered memsets on the caller's stream: safe inside a stream capture
 bool builtin_plugin_capturable(const trtx_plugin_vtbl& v) {
-    return v.enqueue == yolo_enqueue || v.enqueue == anchor_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
+    return v.enqueue == yolo_enqueue || v.enqueue == anchor_enqueue || v.enqueue == yolo9_enqueue || v.enqueue == yolo10_enqueue || v.enqueue == rdec_enqueue || v.enqueue == mish_enqueue;
 }
 
 void register_builtin_plugins(PluginRegistry& r) {

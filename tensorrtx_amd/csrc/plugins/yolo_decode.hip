@@ -102,6 +102,9 @@ __global__ __launch_bounds__(kChunk / VEC) void yolo_score_kernel(LevelTable t, 
 
 // Pass 2: ordered compaction.  One thread per cell, kChunk threads per workgroup.
 // `boxes` != nullptr: ltrb distances were already produced by the fused DFL pass ([batch][cells][4]).
+// REC = floats per Detection record: kYoloDetFloats (YOLOv8 / YOLO11, with the task branches) or 6 (YOLOv10, yolov10/plugin/yololayer.cu:
+// 157-198: {x1, y1, x2, y2, conf, class_id} and no branches; the box, conf and class arithmetic is the same, operation for operation).
+template <int REC>
 __global__ __launch_bounds__(kChunk) void yolo_emit_kernel(LevelTable t, int classes, int total_cells,
                                                            const float* __restrict__ score,
                                                            const int* __restrict__ cls_in,
@@ -153,13 +156,14 @@ __global__ __launch_bounds__(kChunk) void yolo_emit_kernel(LevelTable t, int cla
             d = make_float4(cur[0], cur[(size_t)cells], cur[(size_t)2 * cells], cur[(size_t)3 * cells]);
         }
         const int row = e / gw, col = e - row * gw;
-        float* det = out + 1 + (size_t)slot * trtx::kYoloDetFloats;
+        float* det = out + 1 + (size_t)slot * REC;
         det[0] = (col + 0.5f - d.x) * stride;
         det[1] = (row + 0.5f - d.y) * stride;
         det[2] = (col + 0.5f + d.z) * stride;
         det[3] = (row + 0.5f + d.w) * stride;
         det[4] = sc;
         det[5] = (float)cls_in[(size_t)b * total_cells + g];
+        if constexpr (REC == trtx::kYoloDetFloats) {
         // ---- the seg / pose / obb branches of CalDetection (yololayer.cu:222-279); plugin-ABI form only
         if (cur && br.seg) {
             const float* m = cur + (size_t)(4 + classes + (br.pose ? br.nk * 3 : 0) + (br.obb ? 1 : 0)) * cells;
@@ -201,6 +205,7 @@ __global__ __launch_bounds__(kChunk) void yolo_emit_kernel(LevelTable t, int cla
             det[3] = (d.y + d.w) * istride;
             det[trtx::kYoloDetFloats - 1] = (float)angle;
         }
+        }   // REC == kYoloDetFloats
     }
     if (chunk == n_chunks - 1 && threadIdx.x == kChunk - 1) {
         int total = before + in_wave + (keep ? 1 : 0);  // last thread of the last chunk sees the full count
@@ -622,15 +627,17 @@ extern "C" size_t trtx_yolo_head_decode_workspace(int batch, int net_h, int net_
     return carve(nullptr, batch, count_cells(net_h, net_w, strides, n_levels), true).bytes;
 }
 
-extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
-                                       const int* strides, int max_out, int n_kpt, float kpt_conf, int is_seg, int is_pose, int is_obb,
-                                       float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// the plugin route of both record lengths: the score pass, then the emit pass of `rec` floats per record
+static int32_t decode_planar(int rec, const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w, const int* strides,
+                             int max_out, const YoloBranches& br, float* output, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                             const char* what) {
     if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !inputs || !output ||
-        !workspace || n_kpt < 0 || n_kpt > 17 || count_cells(net_h, net_w, strides, n_levels) == 0)
+        !workspace || br.nk < 0 || br.nk > 17 || count_cells(net_h, net_w, strides, n_levels) == 0)
         return TRTX_ERR_INVALID;
+    for (int i = 0; rec == 6 && i < n_levels; ++i)
+        if (!inputs[i]) return TRTX_ERR_INVALID;
     if (workspace_bytes < trtx_yolo_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
-    const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, n_kpt, kpt_conf};
-    const int info_len = 4 + classes + (br.seg ? 32 : 0) + (br.pose ? n_kpt * 3 : 0) + (br.obb ? 1 : 0);
+    const int info_len = 4 + classes + (br.seg ? 32 : 0) + (br.pose ? br.nk * 3 : 0) + (br.obb ? 1 : 0);
     LevelTable t = make_levels(n_levels, net_h, net_w, strides);
     bool vec4 = true;
     for (int i = 0; i < n_levels; ++i) {
@@ -639,7 +646,7 @@ extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels,
     }
     const int total_cells = t.cell_off[n_levels];
     const Workspace w = carve(workspace, batch, total_cells, false);
-    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
+    const int out_elem = 1 + max_out * rec;
     dim3 grid(w.n_chunks, batch);
     if (vec4)
         hipLaunchKernelGGL(yolo_score_kernel<4>, grid, dim3(kChunk / 4), 0, stream, t, classes, info_len, total_cells, w.score,
@@ -647,9 +654,29 @@ extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels,
     else
         hipLaunchKernelGGL(yolo_score_kernel<1>, grid, dim3(kChunk), 0, stream, t, classes, info_len, total_cells, w.score, w.cls,
                            w.chunk_cnt, w.n_chunks);
-    hipLaunchKernelGGL(yolo_emit_kernel, grid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls,
-                       w.chunk_cnt, w.n_chunks, max_out, out_elem, output, (const float4*)nullptr, br);
-    return trtx::check_launch("trtx_yolo_decode");
+    if (rec == 6)
+        hipLaunchKernelGGL(yolo_emit_kernel<6>, grid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls,
+                           w.chunk_cnt, w.n_chunks, max_out, out_elem, output, (const float4*)nullptr, br);
+    else
+        hipLaunchKernelGGL(yolo_emit_kernel<trtx::kYoloDetFloats>, grid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls,
+                           w.chunk_cnt, w.n_chunks, max_out, out_elem, output, (const float4*)nullptr, br);
+    return trtx::check_launch(what);
+}
+
+extern "C" int32_t trtx_yolo_decode_ex(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
+                                       const int* strides, int max_out, int n_kpt, float kpt_conf, int is_seg, int is_pose, int is_obb,
+                                       float* output, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const YoloBranches br{is_seg ? 1 : 0, is_pose ? 1 : 0, is_obb ? 1 : 0, n_kpt, kpt_conf};
+    return decode_planar(trtx::kYoloDetFloats, inputs, n_levels, batch, classes, net_h, net_w, strides, max_out, br, output, workspace,
+                         workspace_bytes, stream, "trtx_yolo_decode");
+}
+
+// YOLOv10's YoloLayerPlugin::forwardGpu + CalDetection (yolov10/plugin/yololayer.cu:157-240): the YOLOv8 score pass and 6-float records
+extern "C" int32_t trtx_yolov10_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h, int net_w,
+                                       const int* strides, int max_out, float* output, void* workspace, size_t workspace_bytes,
+                                       hipStream_t stream) {
+    return decode_planar(6, inputs, n_levels, batch, classes, net_h, net_w, strides, max_out, YoloBranches{0, 0, 0, 0, 0.f}, output, workspace,
+                         workspace_bytes, stream, "trtx_yolov10_decode");
 }
 
 extern "C" int32_t trtx_yolo_decode(const float* const* inputs, int n_levels, int batch, int classes, int net_h,
@@ -663,11 +690,11 @@ extern "C" int32_t trtx_yolo_decode(const float* const* inputs, int n_levels, in
 // the DFL boxes), otherwise the task head with the masked class tail and the branch tensors of `bt`.
 static int32_t launch_head(const LevelTable& t, const HeadTable& h, const BranchTable* bt, int elem_bytes, int batch, int classes,
                            const float* dfl_weights, int max_out, const YoloBranches& br, float* output, void* workspace, hipStream_t stream,
-                           const char* what) {
+                           const char* what, int rec = trtx::kYoloDetFloats) {
     const int total_cells = t.cell_off[t.n_levels];
     const Workspace w = carve(workspace, batch, total_cells, true);
     if (hipMemsetAsync(w.chunk_cnt, 0, (size_t)batch * w.n_chunks * sizeof(int), stream) != hipSuccess) return TRTX_ERR_HIP;
-    const int out_elem = 1 + max_out * trtx::kYoloDetFloats;
+    const int out_elem = 1 + max_out * rec;
     const dim3 sgrid((total_cells + 255) / 256, batch), egrid(w.n_chunks, batch);
     const auto score = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, sgrid, dim3(256), 0, stream, h, classes, total_cells, dfl_weights, w.score, w.cls, w.boxes, w.chunk_cnt,
@@ -677,12 +704,21 @@ static int32_t launch_head(const LevelTable& t, const HeadTable& h, const Branch
         hipLaunchKernelGGL(kernel, egrid, dim3(kChunk), 0, stream, t, *bt, total_cells, w.score, w.cls, w.chunk_cnt, w.n_chunks, max_out,
                            out_elem, output, (const float4*)w.boxes, br);
     };
-    if (!bt) {
+    if (!bt && rec == 6) {
+        // the YOLOv10 head: the det score pass (classes % 8 == 0) or the task head's masked class tail (any class count), 6-float records
+        const bool tail = classes % 8 != 0;
+        if (elem_bytes == 2)
+            tail ? score(yolo_task_score_kernel<_Float16>) : score(yolo_head_score_kernel<_Float16>);
+        else
+            tail ? score(yolo_task_score_kernel<float>) : score(yolo_head_score_kernel<float>);
+        hipLaunchKernelGGL(yolo_emit_kernel<6>, egrid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls, w.chunk_cnt,
+                           w.n_chunks, max_out, out_elem, output, (const float4*)w.boxes, br);
+    } else if (!bt) {
         if (elem_bytes == 2)
             score(yolo_head_score_kernel<_Float16>);
         else
             score(yolo_head_score_kernel<float>);
-        hipLaunchKernelGGL(yolo_emit_kernel, egrid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls, w.chunk_cnt,
+        hipLaunchKernelGGL(yolo_emit_kernel<trtx::kYoloDetFloats>, egrid, dim3(kChunk), 0, stream, t, classes, total_cells, w.score, w.cls, w.chunk_cnt,
                            w.n_chunks, max_out, out_elem, output, (const float4*)w.boxes, br);
     } else if (elem_bytes == 2) {
         score(yolo_task_score_kernel<_Float16>);
@@ -720,6 +756,42 @@ extern "C" int32_t trtx_yolo_head_decode_nhwc_f32(const void* const* heads, cons
                                                   const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
                                                   size_t workspace_bytes, hipStream_t stream) {
     return head_decode(heads, ld, 4, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
+}
+
+// Fused YOLOv10 head: the det head above for the 6-float plugin (yolov10/plugin/yololayer.cu:157-198 behind the DFL chain of
+// yolov10/src/block.cpp:214-233), any class count >= 1.  The head tensors are read as the det head reads them (classes % 8 == 0) or as
+// the task head does (the last classes % 8 logits one by one); the workspace is the det head's.
+extern "C" size_t trtx_yolov10_head_decode_workspace(int batch, int net_h, int net_w, const int* strides, int n_levels) {
+    return trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels);
+}
+
+static int32_t head10_decode(const void* const* heads, const int* ld, int elem_bytes, int n_levels, int batch, int classes, int net_h, int net_w,
+                             const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream) {
+    if (n_levels < 1 || n_levels > kMaxLevels || batch < 1 || classes < 1 || max_out < 1 || !heads || !ld || !dfl_weights || !output ||
+        !workspace || count_cells(net_h, net_w, strides, n_levels) == 0)
+        return TRTX_ERR_INVALID;
+    for (int i = 0; i < n_levels; ++i)
+        if (!heads[i]) return TRTX_ERR_INVALID;
+    if (workspace_bytes < trtx_yolo_head_decode_workspace(batch, net_h, net_w, strides, n_levels)) return TRTX_ERR_WORKSPACE;
+    for (int i = 0; i < n_levels; ++i)
+        // the 16-byte loads read channels [0, 64 + (classes & ~7)) of every pixel, the scalar ones up to 64 + classes
+        if (ld[i] % (16 / elem_bytes) || ld[i] < 64 + classes || (reinterpret_cast<uintptr_t>(heads[i]) & 15)) return TRTX_ERR_UNSUPPORTED;
+    const LevelTable t = make_levels(n_levels, net_h, net_w, strides);
+    return launch_head(t, make_head(t, heads, ld), nullptr, elem_bytes, batch, classes, dfl_weights, max_out, YoloBranches{0, 0, 0, 0, 0.f},
+                       output, workspace, stream, "trtx_yolov10_head_decode_nhwc", 6);
+}
+
+extern "C" int32_t trtx_yolov10_head_decode_nhwc(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                 const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                                 size_t workspace_bytes, hipStream_t stream) {
+    return head10_decode(heads, ld, 2, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t trtx_yolov10_head_decode_nhwc_f32(const void* const* heads, const int* ld, int n_levels, int batch, int classes, int net_h, int net_w,
+                                                     const int* strides, const float* dfl_weights, int max_out, float* output, void* workspace,
+                                                     size_t workspace_bytes, hipStream_t stream) {
+    return head10_decode(heads, ld, 4, n_levels, batch, classes, net_h, net_w, strides, dfl_weights, max_out, output, workspace, workspace_bytes, stream);
 }
 
 // Fused task head (YOLO11 seg / pose / obb, explicit batch): reads, besides the det head's tensors, the cell's task branch from its own

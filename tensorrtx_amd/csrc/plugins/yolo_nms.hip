@@ -37,6 +37,35 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// The rank machinery of the NMS sort and of YOLOv10's top-k: a bitonic network over kCap 128-bit keys, one per thread of a kCap-thread
+// workgroup, ascending; strides < 64 by wave shuffles, >= 64 through the two LDS arrays.  Every thread of the workgroup must call it.
+__device__ __forceinline__ void bitonic_sort_cap(uint64_t& hi, uint64_t& lo, uint64_t* s_hi, uint64_t* s_lo, int tid) {
+    for (int k = 2; k <= kCap; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            uint64_t ph, pl;
+            if (j >= 64) {
+                s_hi[tid] = hi;
+                s_lo[tid] = lo;
+                __syncthreads();
+                ph = s_hi[tid ^ j];
+                pl = s_lo[tid ^ j];
+                __syncthreads();
+            } else {
+                ph = shfl_xor_u64(hi, j);
+                pl = shfl_xor_u64(lo, j);
+            }
+            const bool up = (tid & k) == 0;
+            const bool lower = (tid & j) == 0;
+            const bool take_min = (up == lower);
+            const bool swap = take_min ? key_less(ph, pl, hi, lo) : key_less(hi, lo, ph, pl);
+            if (swap) {
+                hi = ph;
+                lo = pl;
+            }
+        }
+    }
+}
+
 // postprocess.cpp:71-85, operation for operation.
 __device__ __forceinline__ float iou_xyxy(const float4 l, const float4 r) {
     const float ib0 = l.x < r.x ? r.x : l.x;  // max(l[0], r[0])
@@ -161,31 +190,7 @@ __global__ __launch_bounds__(kCap) void yolo_nms_sort_kernel(const float* __rest
             lo = ((uint64_t)((MODE == 0 || MODE == 2) ? trtx::ord_f32(det[0]) : 0u) << 32) | (uint32_t)tid;
         }
     }
-    // bitonic sort, ascending, 1024 keys
-    for (int k = 2; k <= kCap; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            uint64_t ph, pl;
-            if (j >= 64) {
-                s_hi[tid] = hi;
-                s_lo[tid] = lo;
-                __syncthreads();
-                ph = s_hi[tid ^ j];
-                pl = s_lo[tid ^ j];
-                __syncthreads();
-            } else {
-                ph = shfl_xor_u64(hi, j);
-                pl = shfl_xor_u64(lo, j);
-            }
-            const bool up = (tid & k) == 0;
-            const bool lower = (tid & j) == 0;
-            const bool take_min = (up == lower);
-            const bool swap = take_min ? key_less(ph, pl, hi, lo) : key_less(hi, lo, ph, pl);
-            if (swap) {
-                hi = ph;
-                lo = pl;
-            }
-        }
-    }
+    bitonic_sort_cap(hi, lo, s_hi, s_lo, tid);
     // sorted record -> workspace (the decode buffer is re-read through L2: 24 B per record)
     const bool valid = !(hi == ~0ull && lo == ~0ull);
     const int orig = valid ? (int)(uint32_t)lo : 0;
@@ -459,7 +464,58 @@ __global__ __launch_bounds__(kCap) void yolo_gpu_post_obb_kernel(const float* __
     }
 }
 
+// ---- YOLOv10's get_topk / batch_topk (yolov10/src/postprocess.cpp:35-52) on the device: no NMS, the one-to-one head needs none.
+// One workgroup per image over the 6-float records of the decode buffer.  topk <= 0 is the reference (its `topk` argument is unused):
+// records with conf > conf_thresh (NaN fails the '>') in slot order.  topk > 0 keeps the topk highest confidences of those, ordered by
+// descending conf, ties in slot order: the key is (~conf | slot), so the rank is stable and the result unique.  `out` has the decode
+// buffer's shape; out[b][0] is the number of records written and nothing is written behind them.
+__global__ __launch_bounds__(kCap) void yolo10_topk_kernel(const float* __restrict__ decode, int max_out, float conf_thresh, int topk,
+                                                           float* __restrict__ out) {
+    __shared__ uint64_t s_hi[kCap];
+    __shared__ uint64_t s_lo[kCap];
+    __shared__ int s_wcnt[kBlocks];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t elem = 1 + (size_t)max_out * 6;
+    const float* img = decode + (size_t)b * elem;
+    int count = (int)img[0];
+    count = count < max_out ? count : max_out;
+    count = count < kCap ? count : kCap;
+    uint64_t hi = ~0ull, lo = ~0ull;
+    if (tid < count) {
+        const float conf = img[1 + (size_t)tid * 6 + 4];
+        if (conf > conf_thresh) {
+            hi = topk > 0 ? (uint64_t)(uint32_t)~trtx::ord_f32(conf) : 0ull;
+            lo = (uint64_t)(uint32_t)tid;
+        }
+    }
+    bitonic_sort_cap(hi, lo, s_hi, s_lo, tid);
+    const bool valid = !(hi == ~0ull && lo == ~0ull);   // the survivors hold the ranks [0, n)
+    const unsigned long long m = __ballot(valid);
+    if ((tid & 63) == 0) s_wcnt[tid >> 6] = __popcll(m);
+    __syncthreads();
+    float* dst = out + (size_t)b * elem;
+    if (valid && (topk <= 0 || tid < topk)) {
+        const float* det = img + 1 + (size_t)(uint32_t)lo * 6;
+        float* o = dst + 1 + (size_t)tid * 6;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) o[e] = det[e];
+    }
+    if (tid == 0) {
+        int n = 0;
+        for (int w = 0; w < kBlocks; ++w) n += s_wcnt[w];
+        dst[0] = (float)((topk > 0 && n > topk) ? topk : n);
+    }
+}
+
 }  // namespace
+
+extern "C" int32_t trtx_yolov10_topk(const float* decode_out, int batch, int max_out, float conf_thresh, int topk, float* out,
+                                     hipStream_t stream) {
+    if (!decode_out || !out || decode_out == out || batch < 1 || max_out < 1) return TRTX_ERR_INVALID;
+    if (max_out > kCap) return TRTX_ERR_UNSUPPORTED;   // the capacity of the NMS entry points
+    hipLaunchKernelGGL(yolo10_topk_kernel, dim3(batch), dim3(kCap), 0, stream, decode_out, max_out, conf_thresh, topk, out);
+    return trtx::check_launch("trtx_yolov10_topk");
+}
 
 extern "C" int32_t trtx_yolo_postprocess_gpu(const float* decode_out, int batch, int max_out, float conf_thresh, float nms_thresh,
                                              float* out, hipStream_t stream) {

@@ -170,7 +170,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
         int32_t st = TRTX_OK;
-        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD || op.kind == OP_ROI_ALIGN);
+        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD || op.kind == OP_YOLO10_HEAD || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
@@ -441,6 +441,20 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     lds[k] = plan.tensors[op.in[k]].ld;
                 }
                 st = (t0.dtype == DT_F32 ? trtx_yolo_head_decode_nhwc_f32 : trtx_yolo_head_decode_nhwc)(
+                        heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
+                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+                break;
+            }
+            case OP_YOLO10_HEAD: {
+                const int nl = op.i[4];
+                const void* heads[8];
+                int lds[8];
+                if (nl < 1 || nl > 5 || (int)op.in.size() != nl) { st = TRTX_ERR_STATE; break; }
+                for (int k = 0; k < nl; ++k) {
+                    heads[k] = R.ptr(op.in[k]);
+                    lds[k] = plan.tensors[op.in[k]].ld;
+                }
+                st = (t0.dtype == DT_F32 ? trtx_yolov10_head_decode_nhwc_f32 : trtx_yolov10_head_decode_nhwc)(
                         heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
                         static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
                 break;

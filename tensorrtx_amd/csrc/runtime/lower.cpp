@@ -244,7 +244,8 @@ struct Lowerer {
         for (int t : f.branch_tensor) branches.push_back(need_nhwc(t));
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
         const bool task = !f.branch_tensor.empty();
-        POp& op = add_op(task ? OP_YOLO_TASK_HEAD : OP_YOLO_HEAD, l.name + (task ? " [fused DFL+task decode]" : " [fused DFL+decode]"), ins, {out});
+        POp& op = add_op(task ? OP_YOLO_TASK_HEAD : (f.v10 ? OP_YOLO10_HEAD : OP_YOLO_HEAD),
+                         l.name + (task ? " [fused DFL+task decode]" : (f.v10 ? " [fused DFL+decode, 6-float records]" : " [fused DFL+decode]")), ins, {out});
         op.extra_in = branches;
         op.src_layer = f.dfl_conv_layer;
         op.i[0] = f.params.classes;
@@ -362,6 +363,9 @@ struct Lowerer {
         POp& op = add_op(OP_CONV, l.name, ins, {out});
         op.src_layer = c.conv_layer;
         op.scale_layer = c.scale_layer;
+        op.fold_layer = c.fold_conv;
+        op.fold_scale = c.fold_scale;
+        if (c.fold_conv >= 0) op.name += " [RepVGGDW folded]";
         op.stem = stem;
         ConvArgs& a = op.conv;
         const PTensor& to = plan.tensors[out];

@@ -56,6 +56,14 @@ void match_conv_fusion(const NetView& g, Fusions& f) {
                 take(nx, s.outputs[0]);
             }
         }
+        // RepVGGDW (match_repvggdw_fold): the 3x3 branch goes into this convolution's filter, so its result is the sum's
+        if (f.repdw_at[li] >= 0 && c.scale_layer >= 0) {
+            const RepDwFuse& r = f.repdws[f.repdw_at[li]];
+            c.fold_conv = r.conv3;
+            c.fold_scale = r.scale3;
+            t = net.layers[r.sum].outputs[0];
+            last = std::max(last, r.sum);
+        }
         // SiLU spelled as Sigmoid + Prod (block.cpp:91-94), or a plain activation
         if (!net.tensors[t].is_output && g.consumers[t].size() == 2) {
             int a = g.consumers[t][0], b = g.consumers[t][1];
@@ -216,11 +224,15 @@ void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
         const LayerDef& l = net.layers[li];
         if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li]) continue;
         YoloHeadFuse h;
-        if (!builtin_yolo_params(l.plugin->v, &h.params)) continue;
+        if (!builtin_yolo_params(l.plugin->v, &h.params)) {
+            // the YOLOv10 plugin (yolov10/src/model.cpp:202-255: the same tail in front of 6-float records), explicit batch only, any class count
+            if (task || !e || !g.opt.yolo10_head || !builtin_yolo10_params(l.plugin->v, &h.params)) continue;
+            h.v10 = true;
+        }
         const YoloLayerParams& pr = h.params;
         if (pr.strides.size() != l.inputs.size()) continue;
         if (task ? (pr.seg + pr.pose + pr.obb != 1 || l.inputs.size() > 4 || (pr.pose && (pr.nk < 1 || pr.nk > 17)))
-                 : (!pr.det_only || pr.classes % 8 || l.inputs.size() > 6))
+                 : (!pr.det_only || (!h.v10 && pr.classes % 8) || l.inputs.size() > 6))
             continue;
         const int64_t extra = pr.seg ? 32 : (pr.pose ? 3 * pr.nk : 1);
         std::vector<int> used;
@@ -372,6 +384,51 @@ void match_reorg_fold(const NetView& g, Fusions& f) {
         f.reorg_src[lcv] = src;
     }
 }
+// ---- RepVGGDW (yolov10/src/block.cpp:388-403): act(conv7(x) + conv3(x)) with both convolutions depthwise, stride 1, 'same' padding, no
+// dilation, each behind its own per-channel scale (the folded BatchNorm, power 1).  A 3x3 filter in the centre of a 7x7 one reads the same
+// pixels, so conv7 + conv3 is ONE 7x7 depthwise convolution whose filter is scale7 * w7 + scale3 * w3 (centre) and whose shift is the
+// two shifts' sum (pack_weights does that in double).  Applies only when neither convolution's, neither scale's output has another
+// reader or is a network output.  What follows the sum (the SiLU) is left to match_conv_fusion.  TRTX_REPVGGDW_FOLD=0 turns it off.
+void match_repvggdw_fold(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (!g.opt.repvggdw_fold || net.int8) return;
+    auto dw_same = [&](const LayerDef& l, int k) {
+        const Dims& di = net.tensors[l.inputs[0]].dims;
+        return l.kind == L_CONV && g.spatial(di) && l.kernel[0] == k && l.kernel[1] == k && l.stride[0] == 1 && l.stride[1] == 1 && l.padding[0] == k / 2 &&
+               l.padding[1] == k / 2 && l.dilation[0] == 1 && l.dilation[1] == 1 && l.nb_out == di.d[di.nb - 3] && l.groups == l.nb_out &&
+               (int64_t)l.w0.size() == (int64_t)l.nb_out * k * k;
+    };
+    // the per-channel scale behind convolution `lc`, read by `reader` only
+    auto scale_of = [&](int lc, int* ls) {
+        int nx;
+        if (!g.sole_consumer(net.layers[lc].outputs[0], &nx) || f.absorbed[nx] || net.layers[nx].kind != L_SCALE || net.layers[nx].op == TRTX_SCALE_ELEMENTWISE) return false;
+        for (float p : net.layers[nx].w2)
+            if (p != 1.0f) return false;
+        *ls = nx;
+        return true;
+    };
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l7 = net.layers[li];
+        if (f.absorbed[li] || !dw_same(l7, 7)) continue;
+        int s7 = -1, sum = -1;
+        if (!scale_of((int)li, &s7) || !g.sole_consumer(net.layers[s7].outputs[0], &sum) || f.absorbed[sum]) continue;
+        const LayerDef& ls = net.layers[sum];
+        if (ls.kind != L_ELEMENTWISE || ls.op != TRTX_ELEMENTWISE_SUM || ls.inputs.size() != 2) continue;
+        const int t7 = net.layers[s7].outputs[0];
+        const int t3 = ls.inputs[0] == t7 ? ls.inputs[1] : ls.inputs[0];
+        if (t3 == t7) continue;
+        const int s3 = g.producer(t3);
+        if (s3 < 0 || f.absorbed[s3] || net.layers[s3].kind != L_SCALE || !g.only_used_by(t3, {sum})) continue;
+        const int c3 = g.producer(net.layers[s3].inputs[0]);
+        int s3_again = -1;
+        if (c3 < 0 || c3 == (int)li || f.absorbed[c3] || !dw_same(net.layers[c3], 3) || !scale_of(c3, &s3_again) || s3_again != s3) continue;
+        if (net.layers[c3].inputs[0] != l7.inputs[0] || net.layers[c3].nb_out != l7.nb_out) continue;
+        f.absorbed[c3] = f.absorbed[s3] = f.absorbed[sum] = true;
+        f.repdw_at[li] = (int)f.repdws.size();
+        f.repdws.push_back(RepDwFuse{c3, s3, sum});
+    }
+}
+
 void match_yolo7_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 1, f); }
 void match_darknet_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 2, f); }
 
@@ -1173,13 +1230,14 @@ bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
 // and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
-// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), the RepVGGDW fold (it claims the 3x3 branch and the sum, and convolution fusion then continues the 7x7 convolution at the sum's output), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
     f.absorbed.assign(nl, false);
     f.pad_cout.assign(nl, false);
     f.reorg_src.assign(nl, -1);
+    f.repdw_at.assign(nl, -1);
     f.group_at = f.yolo_at = f.attn_at = f.attn_split_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = f.softmax_at = f.gated_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
@@ -1195,6 +1253,7 @@ Fusions match_fusions(const NetView& g) {
     match_softmax_chains(g, f);
     match_gated_add(g, f);
     match_reorg_fold(g, f);
+    match_repvggdw_fold(g, f);
     match_conv_fusion(g, f);
     match_concat_activation(g, f);
     return f;

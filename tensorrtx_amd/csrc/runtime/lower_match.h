@@ -21,6 +21,7 @@ struct FusedConv {
     int residual = -1;  // network tensor id
     int out_tensor = -1;  // network tensor the fused op produces
     int emit_at = -1;     // layer index at which the fused op is scheduled
+    int fold_conv = -1, fold_scale = -1;   // RepVGGDW (match_repvggdw_fold): the 3x3 depthwise branch and its scale, folded into this 7x7 one's filter
 };
 
 struct YoloHeadFuse {
@@ -29,6 +30,13 @@ struct YoloHeadFuse {
     std::vector<int> branch_tensor;  // task head: network tensor per level, the cv4 convolution's output (B, extra, gh, gw)
     int dfl_conv_layer = -1;
     YoloLayerParams params;
+    bool v10 = false;               // the YOLOv10 plugin: 6-float records, any class count, OP_YOLO10_HEAD
+};
+
+// RepVGGDW (yolov10/src/block.cpp:388-403) on one tensor: depthwise 7x7 s1 p3 + scale, depthwise 3x3 s1 p1 + scale, their sum; the SiLU
+// behind the sum is the 7x7 convolution's epilogue (match_conv_fusion continues at the sum's output)
+struct RepDwFuse {
+    int conv3 = -1, scale3 = -1, sum = -1;   // layers
 };
 
 struct Yolo5HeadFuse {
@@ -111,6 +119,8 @@ struct Fusions {
     std::vector<AttentionSplitFuse> attn_splits;
     std::vector<int> group_at, yolo_at, attn_at, attn_split_at, yolo5_at, yolo9_at;
     std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor or DDetect head: its output channels round up to 16 bytes
+    std::vector<RepDwFuse> repdws;
+    std::vector<int> repdw_at;                 // per layer: the record of a 7x7 depthwise convolution that takes a RepVGGDW's 3x3 branch into its filter, or -1
     std::vector<int> reorg_src;                // per layer: >= 0 for a convolution that absorbed the ReOrg in front of it - the network tensor the four slices read
     std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own
     std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src

@@ -120,6 +120,22 @@ void reorg_fold_weights(const float* w, int cout, int cin, int kh, int kw, float
         }
 }
 
+// RepVGGDW as one depthwise 7x7 filter: w[c] = scale7[c] * w7[c] with scale3[c] * w3[c] added into its 3x3 centre, shift[c] = (bias7[c] * scale7[c]
+// + shift7[c]) + (bias3[c] * scale3[c] + shift3[c]); every value in double, rounded once to fp32 (what the depthwise kernel reads).
+void repvggdw_fold_weights(const float* w7, const float* scale7, const float* shift7, const float* bias7, const float* w3, const float* scale3,
+                           const float* shift3, const float* bias3, int channels, float* w_out, float* shift_out) {
+    for (int c = 0; c < channels; ++c) {
+        const double s7 = scale7[c], s3 = scale3[c];
+        for (int r = 0; r < 7; ++r)
+            for (int q = 0; q < 7; ++q) {
+                double v = (double)w7[(size_t)c * 49 + r * 7 + q] * s7;
+                if (r >= 2 && r <= 4 && q >= 2 && q <= 4) v += (double)w3[(size_t)c * 9 + (r - 2) * 3 + (q - 2)] * s3;
+                w_out[(size_t)c * 49 + r * 7 + q] = (float)v;
+            }
+        shift_out[c] = (float)(((double)bias7[c] * s7 + (double)shift7[c]) + ((double)bias3[c] * s3 + (double)shift3[c]));
+    }
+}
+
 bool pack_weights(const Network& net, Plan* plan) {
     std::vector<uint8_t>& blob = plan->weight_blob;
     blob.clear();
@@ -168,6 +184,21 @@ bool pack_weights(const Network& net, Plan* plan) {
             if (op.reorg_cin > 0) {   // before any packing: every branch below sees an ordinary 2k x 2k filter over the slices' input
                 w0_padded.resize(l.w0.size());   // [cout][cin][2kh][2kw]: as many elements as [cout][4 cin][kh][kw]
                 reorg_fold_weights(l.w0.data(), l.nb_out, op.reorg_cin, l.kernel[0], l.kernel[1], w0_padded.data());
+                w0 = w0_padded.data();
+            }
+            if (op.fold_layer >= 0) {
+                // RepVGGDW (match_repvggdw_fold): one 7x7 filter and one shift for both branches; the scale that every packer below applies is 1
+                const LayerDef &l3 = net.layers[op.fold_layer], &s3 = net.layers[op.fold_scale], &s7 = net.layers[op.scale_layer];
+                auto per_channel = [&](const std::vector<float>& v, float dflt) {
+                    std::vector<float> o(cout, dflt);
+                    for (int c = 0; c < cout && !v.empty(); ++c) o[c] = v.size() == 1 ? v[0] : v[c];
+                    return o;
+                };
+                const auto sc7 = per_channel(s7.w1, 1.f), sh7 = per_channel(s7.w0, 0.f), sc3 = per_channel(s3.w1, 1.f), sh3 = per_channel(s3.w0, 0.f);
+                const auto b7 = per_channel(l.w1, 0.f), b3 = per_channel(l3.w1, 0.f);
+                w0_padded.resize((size_t)cout * 49);
+                repvggdw_fold_weights(l.w0.data(), sc7.data(), sh7.data(), b7.data(), l3.w0.data(), sc3.data(), sh3.data(), b3.data(), cout, w0_padded.data(), bias.data());
+                std::fill(sc.begin(), sc.end(), 1.f);
                 w0 = w0_padded.data();
             }
             if (cout_real < cout) {
@@ -231,7 +262,7 @@ bool pack_weights(const Network& net, Plan* plan) {
                 op.w_off = reserve((size_t)a.kh * a.kw * cout * 4);
                 float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
                 for (int co = 0; co < cout; ++co)
-                    for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = l.w0[(size_t)co * a.kh * a.kw + t] * sc[co];
+                    for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = w0[(size_t)co * a.kh * a.kw + t] * sc[co];
             } else {
                 op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
                 pack_conv_weights_f32(w0, cout, cin_logical / a.groups, a.kh, a.kw, sc.data(),
@@ -240,7 +271,7 @@ bool pack_weights(const Network& net, Plan* plan) {
             op.b_off = reserve(bias.size() * 4);
             memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
             op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (op.grouped ? (size_t)cout * a.Kpad * 2 : (size_t)cout * a.K * 4));
-        } else if (op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO9_HEAD) {
+        } else if (op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO10_HEAD) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);
             memcpy(blob.data() + op.w_off, l.w0.data(), 16 * 4);

@@ -26,6 +26,9 @@ void pack_deconv_weights_f32(const float* w_ckrs, int cin, int cout, int groups,
 // ReOrg (four stride-2 slices + concat) in front of a kh x kw stride-1 convolution over 4 cin channels, as one 2kh x 2kw stride-2
 // convolution over cin channels (runtime/lower_match.cpp, match_reorg_fold): out [cout][cin][2kh][2kw] from KCRS w [cout][4 cin][kh][kw]
 void reorg_fold_weights(const float* w, int cout, int cin, int kh, int kw, float* out);
+// RepVGGDW's two depthwise branches as one 7x7 filter [channels][7][7] and one shift per channel (pack.cpp)
+void repvggdw_fold_weights(const float* w7, const float* scale7, const float* shift7, const float* bias7, const float* w3, const float* scale3,
+                           const float* shift3, const float* bias3, int channels, float* w_out, float* shift_out);
 
 uint16_t f32_to_f16_bits(float f);
 float f16_bits_to_f32(uint16_t h);

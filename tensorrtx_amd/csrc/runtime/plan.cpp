@@ -11,8 +11,8 @@ const char* op_kind_name(int k) {
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
                               "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add", "attention_split",
-                              "darknet_head", "pad_nhwc"};
-    return (k >= 0 && k <= OP_PAD_NHWC) ? n[k] : "?";
+                              "darknet_head", "pad_nhwc", "yolo10_head"};
+    return (k >= 0 && k <= OP_YOLO10_HEAD) ? n[k] : "?";
 }
 
 std::string Plan::describe_json() const {
@@ -52,6 +52,7 @@ std::string Plan::describe_json() const {
             if (op.grouped) o << ",\"grouped\":true";
             if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
             if (op.reorg_cin) o << ",\"reorg_cin\":" << op.reorg_cin;
+            if (op.fold_layer >= 0) o << ",\"repvggdw_fold\":true";
         };
         if (op.kind == OP_CONV || op.kind == OP_DECONV) conv_fields(op);
         if (op.kind == OP_ACT_NHWC || op.kind == OP_ACT_LIN) o << ",\"act\":" << op.i[0];
@@ -74,6 +75,13 @@ std::string Plan::describe_json() const {
         if (op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD) {
             o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"anchor_levels\":" << op.fv.size() / 6 << ",\"grids\":[";
             for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]";
+            o << "],\"ld\":[";
+            for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
+            o << "]";
+        }
+        if (op.kind == OP_YOLO10_HEAD) {
+            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"strides\":[";
+            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << op.i[5 + j];
             o << "],\"ld\":[";
             for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
             o << "]";

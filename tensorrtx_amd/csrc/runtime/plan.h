@@ -66,6 +66,8 @@ enum OpKind : int {
     OP_DARKNET_HEAD,    // OP_YOLO5_HEAD with the Darknet plugin's arithmetic and 7-float records (YOLOv3 / YOLOv3-tiny / YOLOv4; plugins/anchor_head.hip):
                         // the same i / iv / fv, levels in the plugin's input order
     OP_PAD_NHWC,        // IPaddingLayer, zero fill (nhwc_zero_pad): i[0] / i[1] = rows above / columns left of the image; the output tensor's H x W say the rest
+    OP_YOLO10_HEAD,     // OP_YOLO_HEAD with YOLOv10's 6-float records and any class count >= 1 (plugins/yolo_decode.hip, trtx_yolov10_head_decode_nhwc): the
+                        // same i, at most 5 strides in i[5..9]
 };
 const char* op_kind_name(int k);
 
@@ -121,6 +123,8 @@ struct POp {
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
     bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
     bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one
+    int fold_layer = -1, fold_scale = -1;   // >= 0: a 7x7 depthwise convolution that took RepVGGDW's 3x3 branch (match_repvggdw_fold): the network layers
+                               // of that branch's convolution and scale; pack_weights adds its scaled filter into the centre and its shift to the shift
     int reorg_cin = 0;         // > 0: a convolution that absorbed the ReOrg in front of it (match_reorg_fold): conv is the 2k x 2k stride-2 form over this
                                // many channels and pack_weights re-indexes the layer's k x k filter over 4 x as many (reorg_fold_weights)
     int cout_real = 0;         // > 0: conv.Cout is this channel count rounded up to a 16-byte multiple; the filter rows and biases beyond it are zero

@@ -89,6 +89,8 @@ struct YoloLayerParams {
     float kpt_conf = 0.f;                         // keypoint confidence threshold (pose)
 };
 bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out);
+// the same for a *built-in* YOLOv10 YoloLayer_TRT instance ("combinedInfo" of 5 to 9 ints; 6-float records, det_only)
+bool builtin_yolo10_params(const trtx_plugin_vtbl& v, YoloLayerParams* out);
 // parameters of a *built-in* anchor-based YoloLayer_TRT instance (the yolov5 field set "netinfo" + "kernels"; false for anything else):
 // lets the lowering pass replace the layout passes + plugin tail by the fused anchor head
 struct Yolo5LayerParams {

@@ -50,6 +50,10 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
     if (yolov7 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;      // ... nor INT8 YOLOv7
     const bool darknet = trtx_host::darknet_model_valid(model);        // yolov3 / yolov3-tiny / yolov4
     if (darknet && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;     // ... nor INT8 Darknet models
+    const std::string m_in(model);
+    const bool yolov10 = m_in.size() == 8 && m_in.compare(0, 7, "yolov10") == 0;   // yolov10n / s / m / b / l / x
+    if (yolov10 && !trtx_host::yolov10_model_valid(m_in)) return TRTX_ERR_INVALID;   // another letter
+    if (yolov10 && geti(o, "int8", 0)) return TRTX_ERR_UNSUPPORTED;    // ... nor INT8 YOLOv10: no calibration for this family
     if (geti(o, "int8", 0)) {  // USE_INT8 of the reference builders (yolov8/src/model.cpp:317-324, retinaface/retina_r50.cpp:219-225)
         if (!builder->platformHasFastInt8()) return TRTX_ERR_UNSUPPORTED;
         config->setFlag(BuilderFlag::kINT8);
@@ -187,6 +191,21 @@ extern "C" int32_t trtx_host_build(const char* model, const char* wts_path, cons
         // the pyramid levels (strides 8 / 16 / 32, tiny 16 / 32) meet only on sizes that 32 divides
         if (cfg.max_batch < 1 || cfg.num_class < 1 || cfg.input_h < 32 || cfg.input_w < 32 || cfg.input_h % 32 || cfg.input_w % 32) return TRTX_ERR_INVALID;
         plan.reset(trtx_host::buildEngineDarknet(builder.get(), config.get(), wts_path, cfg));
+    } else if (yolov10) {
+        trtx_host::Yolov10Config cfg;
+        cfg.model = m;
+        cfg.max_batch = geti(o, "batch", 1);
+        cfg.fp16 = geti(o, "fp16", 1) != 0;
+        cfg.input_h = geti(o, "h", 640);
+        cfg.input_w = geti(o, "w", 640);
+        cfg.num_class = geti(o, "classes", 80);
+        cfg.max_out_bbox = geti(o, "max_out", 1000);
+        cfg.mark_heads = geti(o, "mark_heads", 0) != 0;
+        // the three pyramid levels (strides 8 / 16 / 32) meet only on sizes that 32 divides
+        if (geti(o, "task", 0) != 0 || cfg.max_batch < 1 || cfg.num_class < 1 || cfg.max_out_bbox < 1 || cfg.input_h < 32 || cfg.input_w < 32 ||
+            cfg.input_h % 32 || cfg.input_w % 32)
+            return TRTX_ERR_INVALID;
+        plan.reset(trtx_host::buildEngineYolov10(builder.get(), config.get(), wts_path, cfg));
     } else if (m == "rcnn_r50c4") {
         trtx_host::RcnnConfig cfg;
         cfg.max_batch = geti(o, "batch", 1);

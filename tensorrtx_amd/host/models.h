@@ -157,6 +157,25 @@ bool yolov7_model_p6(const std::string& name);
 nvinfer1::IHostMemory* buildEngineYolov7(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
                                          const Yolov7Config& cfg);
 
+// yolov10/include/config.h constants as run-time configuration.  Explicit batch like the reference (model.cpp:38-44): a plan serves exactly
+// max_batch images per enqueue.  Detection, which is all the reference's yolov10 builds.
+struct Yolov10Config {
+    std::string model = "yolov10n";     // "yolov10n" / "s" / "m" / "b" / "l" / "x": gd, gw, max_channels (yolov10_det.cpp:111-141) and the stage table
+    int input_h = 640, input_w = 640;   // kInputH / kInputW, multiples of 32
+    int num_class = 80;                 // kNumClass
+    int max_batch = 1;                  // kBatchSize (Dims4{kBatchSize, 3, kInputH, kInputW})
+    int max_out_bbox = 1000;            // kMaxNumOutputBbox
+    bool fp16 = true;                   // USE_FP16
+    bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
+};
+// the six names the builder accepts
+bool yolov10_model_valid(const std::string& name);
+// yolov10/src/model.cpp:33-283 (N), 285-535 (S), 537-787 (M), 789-1039 (B and L), 1041-1291 (X) with yolov10/src/block.cpp: one graph and a
+// per-model stage table (host/yolov10.cpp).  Input "images", output "output": 1 + max_out * 6 floats per image (Detection is bbox[4],
+// conf, class_id).  Returns null for another name.
+nvinfer1::IHostMemory* buildEngineYolov10(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
+                                          const Yolov10Config& cfg);
+
 // yolov3/yololayer.h, yolov3-tiny/yololayer.h and yolov4/yololayer.h constants (INPUT_H / INPUT_W 608, CLASS_NUM 80) as run-time configuration.
 // Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W}, setMaxBatchSize).  MAX_OUTPUT_BBOX_COUNT (1000) and the anchors are
 // compiled into the reference's plugin and stay what they are there.

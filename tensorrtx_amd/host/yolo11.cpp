@@ -7,7 +7,7 @@
 //   buildEngineYolo11Cls                                             yolo11/src/model.cpp:33-136
 // Graph, weight keys ("model.<n>...") and layer order are those of the reference.
 // The blocks that YOLOv12 restates with the same bodies (convBnSiLU, convBn, bottleneck, C3k, C3K2, DWConv, DFL, addYoLoLayer, get_width,
-// get_depth) live in yolo_blocks.h.
+// get_depth) live in yolo_blocks.h, and so do SPPF and Attention, which YOLOv10 restates.
 #include <cmath>
 #include <vector>
 
@@ -20,55 +20,6 @@ using namespace nvinfer1;
 namespace trtx_host {
 using namespace blocks;
 namespace {
-
-ITensor* SPPF(Ctx& c, ITensor& in, int c1, int c2, int k, const std::string& lname) {  // block.cpp:111-138
-    ITensor* x = convBnSiLU(c, in, c1 / 2, 1, 1, lname + ".cv1");
-    std::vector<ITensor*> parts{x};
-    for (int i = 0; i < 3; ++i) {
-        auto* pool = c.net->addPoolingNd(*parts.back(), PoolingType::kMAX, DimsHW{k, k});
-        pool->setStrideNd(DimsHW{1, 1});
-        pool->setPaddingNd(DimsHW{k / 2, k / 2});
-        parts.push_back(pool->getOutput(0));
-    }
-    return convBnSiLU(c, *c.net->addConcatenation(parts.data(), 4)->getOutput(0), c2, 1, 1, lname + ".cv2");
-}
-
-// Attention (block.cpp:287-339): qkv 1x1 conv+BN, view (B, heads, 2*kd + hd, N), split q / k / v, softmax(scale * q^T k) over the
-// keys, v @ attn^T viewed back as (B, dim, H, W), plus the depthwise positional conv pe(v), then proj 1x1 conv+BN
-ITensor* Attention(Ctx& c, ITensor& in, int dim, int num_heads, float attn_ratio, const std::string& lname) {
-    const int head_dim = dim / num_heads;
-    const int key_dim = (int)(head_dim * attn_ratio);
-    const float scale = (float)pow(key_dim, -0.5);
-    const int nh_kd = key_dim * num_heads;
-    const int h = dim + nh_kd * 2;
-    const Dims d = in.getDimensions();
-    const int B = (int)d.d[0], H = (int)d.d[2], W = (int)d.d[3], N = H * W;
-    ITensor* qkv = convBn(c, in, h, 1, 1, lname + ".qkv");
-    auto* sh = c.net->addShuffle(*qkv);
-    sh->setReshapeDimensions(Dims4{B, num_heads, -1, N});
-    ITensor* x = sh->getOutput(0);
-    const Dims d1 = x->getDimensions();
-    const Dims4 unit{1, 1, 1, 1};
-    ITensor* q = c.net->addSlice(*x, Dims4{0, 0, 0, 0}, Dims4{d1.d[0], d1.d[1], key_dim, d1.d[3]}, unit)->getOutput(0);
-    ITensor* k = c.net->addSlice(*x, Dims4{0, 0, key_dim, 0}, Dims4{d1.d[0], d1.d[1], key_dim, d1.d[3]}, unit)->getOutput(0);
-    ITensor* v = c.net->addSlice(*x, Dims4{0, 0, key_dim * 2, 0}, Dims4{d1.d[0], d1.d[1], head_dim, d1.d[3]}, unit)->getOutput(0);
-    auto* qT = c.net->addShuffle(*q);
-    qT->setFirstTranspose(Permutation{0, 1, 3, 2});
-    ITensor* attn = c.net->addMatrixMultiply(*qT->getOutput(0), MatrixOperation::kNONE, *k, MatrixOperation::kNONE)->getOutput(0);
-    attn = c.net->addScale(*attn, ScaleMode::kUNIFORM, c.scalar(0.f), c.scalar(scale), c.scalar(1.f))->getOutput(0);
-    auto* sm = c.net->addSoftMax(*attn);
-    sm->setAxes(1 << 3);
-    auto* attnT = c.net->addShuffle(*sm->getOutput(0));
-    attnT->setFirstTranspose(Permutation{0, 1, 3, 2});
-    ITensor* o = c.net->addMatrixMultiply(*v, MatrixOperation::kNONE, *attnT->getOutput(0), MatrixOperation::kNONE)->getOutput(0);
-    auto* re = c.net->addShuffle(*o);
-    re->setReshapeDimensions(Dims4{B, -1, H, W});
-    auto* vre = c.net->addShuffle(*v);
-    vre->setReshapeDimensions(Dims4{B, -1, H, W});
-    ITensor* pe = convBn(c, *vre->getOutput(0), dim, 3, 1, lname + ".pe", dim);
-    ITensor* sum = c.net->addElementWise(*re->getOutput(0), *pe, ElementWiseOperation::kSUM)->getOutput(0);
-    return convBn(c, *sum, dim, 1, 1, lname + ".proj");
-}
 
 ITensor* PSABlock(Ctx& c, ITensor& in, int dim, float attn_ratio, int num_heads, bool shortcut, const std::string& lname) {  // block.cpp:341-364
     ITensor* a = Attention(c, in, dim, num_heads, attn_ratio, lname + ".attn");

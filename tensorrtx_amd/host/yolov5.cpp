@@ -210,7 +210,7 @@ IHostMemory* buildEngineYolov5(IBuilder* builder, IBuilderConfig* config, const 
         if (!cfg.p6) {
             x = convBlock(c, *c6, W(1024), 3, 2, "model.7");
             x = C3(c, *x, W(1024), D(3), true, "model.8");
-            x = SPPF(c, *x, W(1024), W(1024), 5, "model.9");
+            x = trtx_host::SPPF(c, *x, W(1024), W(1024), 5, "model.9");   // this file's (qualified: blocks::SPPF is found through Ctx)
             // ---- head (model.cpp:308-341): the detect convolutions sit where the reference adds them
             ITensor* c10 = convBlock(c, *x, W(512), 1, 1, "model.10");
             ITensor* c13 = C3(c, *upcat(c, *c10, c6), W(512), D(3), false, "model.13");
@@ -231,7 +231,7 @@ IHostMemory* buildEngineYolov5(IBuilder* builder, IBuilderConfig* config, const 
             ITensor* c8 = C3(c, *x, W(768), D(3), true, "model.8");
             x = convBlock(c, *c8, W(1024), 3, 2, "model.9");
             x = C3(c, *x, W(1024), D(3), true, "model.10");
-            x = SPPF(c, *x, W(1024), W(1024), 5, "model.11");
+            x = trtx_host::SPPF(c, *x, W(1024), W(1024), 5, "model.11");   // this file's (qualified: blocks::SPPF is found through Ctx)
             ITensor* c12 = convBlock(c, *x, W(768), 1, 1, "model.12");
             ITensor* c15 = C3(c, *upcat(c, *c12, c8), W(768), D(3), false, "model.15");
             ITensor* c16 = convBlock(c, *c15, W(512), 1, 1, "model.16");

@@ -751,6 +751,148 @@ STATE["yolov8n"] = yolov8n_state
 
 # The arguments of the reference's builders (yolov9/src/model.cpp:35-109 t, 188-254 s, 334-435 m, 568-645 c, 1171-1248 gelan-c), in the
 # order of the main branch.  "L<k>" is the layer whose weights are model.<k + first>.  rep = (c2, c3, c4, n) of RepNCSPELAN4.
+YOLOV10_MODELS = ("yolov10n", "yolov10s", "yolov10m", "yolov10b", "yolov10l", "yolov10x")
+YOLOV10_SCALES = {  # yolov10_det.cpp:111-141: gd, gw, max_channels
+    "n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768), "b": (0.67, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.25, 512)}
+# which of the stages 6, 8, 13, 19, 22 are C2F ("f"), C2fCIB ("c") or C2fCIB with the large kernel ("l": RepVGGDW): yolov10/src/model.cpp, the
+# five buildEngineYolov10Det* functions (b and l share one)
+YOLOV10_STAGES = {"n": "ffffl", "s": "flffl", "m": "fcfcc", "b": "fcccc", "l": "fcccc", "x": "ccccc"}
+# The class head (the yolo11_state recipe: He rows of gain 800) around a bias, with one favoured class per level lifted by the margin.
+# These random backbones give features that vary little over an image: with a zero bias the largest logit of a cell lies within +- 0.5 of
+# 6.0 (yolov10n; 6.4 for yolov10m), so the bias puts the plugin's 0.1 gate (logit -2.197) inside that narrow band and a useful share of a
+# small image's cells, far from all of them, passes it.  Set with the fp64 twin for yolov10n and yolov10m at 80 classes (counts:
+# tests/test_gpu_yolov10.py); the other four models take yolov10n's bias untuned.
+YOLOV10_CLS_BIAS, YOLOV10_CLS_MARGIN = -8.25, 0.5
+YOLOV10_CLS_BIAS_OF = {"yolov10m": -8.7}
+
+
+def yolov10_state(name="yolov10n", seed=0, num_class=80):
+    """Seeded synthetic weights of yolov10n / s / m / b / l / x under the reference's `.wts` key names (the ultralytics state_dict keys that
+    yolov10/src/block.cpp / model.cpp read; the one-to-many head the reference never builds is absent): OrderedDict name -> fp32 array.
+    He-scaled convolutions with near-identity BatchNorm statistics (the yolo11_state recipe); the class head as described at YOLOV10_CLS_BIAS."""
+    import math
+    from collections import OrderedDict
+
+    import torch
+    assert name in YOLOV10_MODELS, name
+    letter = name[7]
+    gd, gw, mc = YOLOV10_SCALES[letter]
+    stages = YOLOV10_STAGES[letter]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    randn = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    rand = lambda *shape: torch.rand(*shape, generator=g)    # noqa: E731
+
+    def W(x):
+        return int(math.ceil(min(x, mc) * gw / 8)) * 8
+
+    def D(x):
+        if x == 1:
+            return 1
+        v = x * gd          # get_depth: round half away from zero, one less on an exact half with an even integer part
+        r = int(math.floor(v + 0.5))
+        if v - int(v) == 0.5 and int(v) % 2 == 0:
+            r -= 1
+        return max(r, 1)
+
+    def conv(name, cout, cin, k, gain=2.0):
+        sd[name + ".weight"] = (randn(cout, cin, k, k) * math.sqrt(gain / (cin * k * k))).float()
+
+    def cb(name, cout, cin, k, groups=1, gain=2.0):  # Conv + BatchNorm (+ SiLU)
+        conv(name + ".conv", cout, cin // groups, k, gain)
+        sd[name + ".bn.weight"] = (0.9 + 0.2 * rand(cout)).float()
+        sd[name + ".bn.bias"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_mean"] = (0.1 * randn(cout)).float()
+        sd[name + ".bn.running_var"] = (0.8 + 0.4 * rand(cout)).float()
+        sd[name + ".bn.num_batches_tracked"] = torch.zeros(1)
+
+    def c2f(name, c1, c2, n):
+        c_ = int(c2 * 0.5)
+        cb(name + ".cv1", 2 * c_, c1, 1)
+        for i in range(n):
+            cb(f"{name}.m.{i}.cv1", c_, c_, 3)
+            cb(f"{name}.m.{i}.cv2", c_, c_, 3)
+        cb(name + ".cv2", c2, (2 + n) * c_, 1)
+
+    def cib(name, c, lk):   # CIB with c1 == c2 == c and e = 1.0: 2 c_ = 2 c in the middle
+        cb(name + ".cv1.0", c, c, 3, groups=c, gain=1.0)
+        cb(name + ".cv1.1", 2 * c, c, 1)
+        if lk:
+            cb(name + ".cv1.2.conv", 2 * c, 2 * c, 7, groups=2 * c, gain=1.0)
+            cb(name + ".cv1.2.conv1", 2 * c, 2 * c, 3, groups=2 * c, gain=1.0)
+        else:
+            cb(name + ".cv1.2", 2 * c, 2 * c, 3, groups=2 * c, gain=1.0)
+        cb(name + ".cv1.3", c, 2 * c, 1)
+        cb(name + ".cv1.4", c, c, 3, groups=c, gain=1.0)
+
+    def c2fcib(name, c1, c2, n, lk):
+        c_ = int(c2 * 0.5)
+        cb(name + ".cv1", 2 * c_, c1, 1)
+        for i in range(n):
+            cib(f"{name}.m.{i}", c_, lk)
+        cb(name + ".cv2", c2, (2 + n) * c_, 1)
+
+    def stage(kind, name, c1, c2, n):
+        if kind == "f":
+            c2f(name, c1, c2, n)
+        else:
+            c2fcib(name, c1, c2, n, kind == "l")
+
+    def scdown(name, c1, c2):
+        cb(name + ".cv1", c2, c1, 1)
+        cb(name + ".cv2", c2, c2, 3, groups=c2, gain=1.0)
+
+    def psa(name, ch):
+        c = int(ch * 0.5)
+        cb(name + ".cv1", 2 * c, ch, 1)
+        heads = c // 64
+        kd = (c // heads) // 2
+        cb(name + ".attn.qkv", c + 2 * kd * heads, c, 1)
+        cb(name + ".attn.pe", c, c, 3, groups=c, gain=1.0)
+        cb(name + ".attn.proj", c, c, 1, gain=1.0)
+        cb(name + ".ffn.0", 2 * c, c, 1)
+        cb(name + ".ffn.1", c, 2 * c, 1, gain=1.0)
+        cb(name + ".cv2", ch, 2 * c, 1)
+
+    cb("model.0", W(64), 3, 3)
+    cb("model.1", W(128), W(64), 3)
+    c2f("model.2", W(128), W(128), D(3))
+    cb("model.3", W(256), W(128), 3)
+    c2f("model.4", W(256), W(256), D(6))
+    scdown("model.5", W(256), W(512))
+    stage(stages[0], "model.6", W(512), W(512), D(6))
+    scdown("model.7", W(512), W(1024))
+    stage(stages[1], "model.8", W(1024), W(1024), D(3))
+    cb("model.9.cv1", W(1024) // 2, W(1024), 1)
+    cb("model.9.cv2", W(1024), 2 * W(1024), 1)
+    psa("model.10", W(1024))
+    stage(stages[2], "model.13", W(1024) + W(512), W(512), D(3))
+    c2f("model.16", W(512) + W(256), W(256), D(3))
+    cb("model.17", W(256), W(256), 3)
+    stage(stages[3], "model.19", W(256) + W(512), W(512), D(3))
+    scdown("model.20", W(512), W(512))
+    stage(stages[4], "model.22", W(512) + W(1024), W(1024), D(3))
+    c2 = max(16, W(256) // 4, 64)
+    c3 = max(W(256), min(num_class, 100))
+    for lv, cin in enumerate((W(256), W(512), W(1024))):
+        a, b = f"model.23.one2one_cv2.{lv}", f"model.23.one2one_cv3.{lv}"
+        cb(a + ".0", c2, cin, 3)
+        cb(a + ".1", c2, c2, 3)
+        conv(a + ".2", 64, c2, 1, gain=4.0)
+        sd[a + ".2.bias"] = (1.0 + 0.1 * randn(64)).float()
+        cb(b + ".0.0", cin, cin, 3, groups=cin, gain=1.0)
+        cb(b + ".0.1", c3, cin, 1)
+        cb(b + ".1.0", c3, c3, 3, groups=c3, gain=1.0)
+        cb(b + ".1.1", c3, c3, 1)
+        conv(b + ".2", num_class, c3, 1, gain=800.0)
+        bias = YOLOV10_CLS_BIAS_OF.get(name, YOLOV10_CLS_BIAS) + 0.1 * randn(num_class)
+        bias[(7 * lv + 3) % num_class] += YOLOV10_CLS_MARGIN
+        sd[b + ".2.bias"] = bias.float()
+        if lv == 0:
+            sd["model.23.dfl.conv.weight"] = torch.arange(16.0).reshape(1, 16, 1, 1)
+    return OrderedDict((k, v.numpy()) for k, v in sd.items())
+
+
 YOLOV9_SPECS = {
     "yolov9t": dict(stem=(16, 32), elan1=True, b2=(32, 32, 16, 0), adown=False, down=(64, 96, 128), rep=((64, 64, 32, 3), (96, 96, 48, 3), (128, 128, 64, 3)),
                     spp=(128, 64), r12=(96, 96, 48, 3), r15=(64, 64, 32, 3), d16=48, r18=(96, 96, 48, 3), d19=64, r21=(128, 128, 64, 3), aux=False),
