@@ -61,6 +61,52 @@ struct Resolver {
     }
 };
 
+// The per-level device pointers and pixel strides of a fused head's tensors, one per level
+struct HeadLevels {
+    const void* p[8];
+    int ld[8];
+    bool gather(const Resolver& R, const std::vector<int>& ts, int nl) {
+        if ((int)ts.size() != nl) return false;
+        for (int k = 0; k < nl; ++k) {
+            p[k] = R.ptr(ts[k]);
+            ld[k] = R.plan.tensors[ts[k]].ld;
+        }
+        return true;
+    }
+};
+
+// One fused detect head (plan.h, HeadOp): `in` holds the head tensors, `extra_in` the task branches (OP_YOLO_TASK_HEAD) or the class tensors (OP_YOLO9_HEAD).
+// TRTX_ERR_STATE for a level count outside the kind's bounds or one that the op's tensors and tables do not agree with.
+int32_t run_head(const HeadOp& h, const POp& op, const Resolver& R, int batch, bool f32, const char* W, void* ws, hipStream_t stream) {
+    const int nl = op.i[4];
+    HeadLevels in, extra;
+    if (nl < h.min_levels || nl > h.max_levels || !in.gather(R, op.in, nl)) return TRTX_ERR_STATE;
+    const int images = op.i[11] > 0 ? op.i[11] : batch;   // explicit batch: the heads' leading dimension
+    const float* dfl = reinterpret_cast<const float*>(W + op.w_off);
+    float* out = static_cast<float*>(R.ptr(op.out[0]));
+    if (h.anchor_ws) {
+        int gw[8], gh[8];
+        if ((int)op.iv.size() != 2 * nl || (int)op.fv.size() != 6 * nl) return TRTX_ERR_STATE;
+        for (int k = 0; k < nl; ++k) {
+            gw[k] = op.iv[2 * k];
+            gh[k] = op.iv[2 * k + 1];
+        }
+        return h.anchor_decode[f32](in.p, in.ld, nl, images, op.i[0], op.i[1], op.i[2], gw, gh, op.fv.data(), op.i[3], out, ws, op.ws_bytes, stream);
+    }
+    if (h.kind == OP_YOLO_TASK_HEAD) {
+        if (!extra.gather(R, op.extra_in, nl)) return TRTX_ERR_STATE;
+        return (f32 ? trtx_yolo_task_head_decode_nhwc_f32 : trtx_yolo_task_head_decode_nhwc)(
+                in.p, in.ld, extra.p, extra.ld, nl, images, op.i[0], op.i[1], op.i[2], &op.i[5], dfl, op.i[3], op.i[9] == 1, op.i[9] == 2, op.i[9] == 3, op.i[10],
+                op.f[0], out, ws, op.ws_bytes, stream);
+    }
+    if (h.kind == OP_YOLO9_HEAD) {   // implicit batch only
+        if (!extra.gather(R, op.extra_in, nl)) return TRTX_ERR_STATE;
+        return (f32 ? trtx_yolov9_head_decode_nhwc_f32 : trtx_yolov9_head_decode_nhwc)(in.p, in.ld, extra.p, extra.ld, batch, op.i[0], op.i[1], op.i[2], dfl, op.i[3],
+                                                                                     out, ws, op.ws_bytes, stream);
+    }
+    return h.stride_decode[f32](in.p, in.ld, nl, images, op.i[0], op.i[1], op.i[2], &op.i[5], dfl, op.i[3], out, ws, op.ws_bytes, stream);
+}
+
 // add the runtime batch as outermost dimension of a per-sample strided view
 StridedView batch_view(const StridedView& v, int batch, long bs_in, long bs_in2) {
     StridedView o{};
@@ -170,7 +216,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
         int32_t st = TRTX_OK;
-        const bool skip = c->tuning && (op.kind == OP_PLUGIN || op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD || op.kind == OP_YOLO10_HEAD || op.kind == OP_ROI_ALIGN);
+        const bool skip = c->tuning && (op.kind == OP_PLUGIN || is_fused_head(op.kind) || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
@@ -432,91 +478,18 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 }
                 break;
             }
-            case OP_YOLO_HEAD: {
-                const int nl = op.i[4];
-                const void* heads[8];
-                int lds[8];
-                for (int k = 0; k < nl; ++k) {
-                    heads[k] = R.ptr(op.in[k]);
-                    lds[k] = plan.tensors[op.in[k]].ld;
-                }
-                st = (t0.dtype == DT_F32 ? trtx_yolo_head_decode_nhwc_f32 : trtx_yolo_head_decode_nhwc)(
-                        heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
-                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
+            case OP_YOLO_HEAD:
+            case OP_YOLO10_HEAD:
+            case OP_YOLO_TASK_HEAD:
+            case OP_YOLO5_HEAD:
+            case OP_YOLO7_HEAD:
+            case OP_DARKNET_HEAD:
+            case OP_YOLO9_HEAD:
+                st = run_head(*head_op(op.kind), op, R, batch, t0.dtype == DT_F32, W, static_cast<char*>(c->d_arena) + op.ws_off, stream);
                 break;
-            }
-            case OP_YOLO10_HEAD: {
-                const int nl = op.i[4];
-                const void* heads[8];
-                int lds[8];
-                if (nl < 1 || nl > 5 || (int)op.in.size() != nl) { st = TRTX_ERR_STATE; break; }
-                for (int k = 0; k < nl; ++k) {
-                    heads[k] = R.ptr(op.in[k]);
-                    lds[k] = plan.tensors[op.in[k]].ld;
-                }
-                st = (t0.dtype == DT_F32 ? trtx_yolov10_head_decode_nhwc_f32 : trtx_yolov10_head_decode_nhwc)(
-                        heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
-                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
-                break;
-            }
-            case OP_YOLO_TASK_HEAD: {
-                const int nl = op.i[4];
-                const void* heads[4];
-                const void* branches[4];
-                int lds[4], blds[4];
-                for (int k = 0; k < nl; ++k) {
-                    heads[k] = R.ptr(op.in[k]);
-                    lds[k] = plan.tensors[op.in[k]].ld;
-                    branches[k] = R.ptr(op.extra_in[k]);
-                    blds[k] = plan.tensors[op.extra_in[k]].ld;
-                }
-                st = (t0.dtype == DT_F32 ? trtx_yolo_task_head_decode_nhwc_f32 : trtx_yolo_task_head_decode_nhwc)(
-                        heads, lds, branches, blds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], &op.i[5],
-                        reinterpret_cast<const float*>(W + op.w_off), op.i[3], op.i[9] == 1, op.i[9] == 2, op.i[9] == 3, op.i[10], op.f[0],
-                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
-                break;
-            }
             case OP_PAD_NHWC:
                 st = nhwc_zero_pad(R.ptr(op.in[0]), R.ptr(op.out[0]), op.dtype, nb(t0), t0.H, t0.W, t0.C, t0.ld, to.H, to.W, to.ld, op.i[0], op.i[1], stream);
                 break;
-            case OP_YOLO5_HEAD:
-            case OP_YOLO7_HEAD:
-            case OP_DARKNET_HEAD: {
-                const int nl = op.i[4];
-                const void* heads[8];
-                int lds[8], gw[8], gh[8];
-                if (nl < 1 || nl > 8 || (int)op.iv.size() != 2 * nl || (int)op.fv.size() != 6 * nl) { st = TRTX_ERR_STATE; break; }
-                for (int k = 0; k < nl; ++k) {
-                    heads[k] = R.ptr(op.in[k]);
-                    lds[k] = plan.tensors[op.in[k]].ld;
-                    gw[k] = op.iv[2 * k];
-                    gh[k] = op.iv[2 * k + 1];
-                }
-                const bool f32 = t0.dtype == DT_F32;
-                const auto decode = op.kind == OP_DARKNET_HEAD ? (f32 ? trtx_darknet_head_decode_nhwc_f32 : trtx_darknet_head_decode_nhwc)
-                                    : op.kind == OP_YOLO7_HEAD ? (f32 ? trtx_yolov7_head_decode_nhwc_f32 : trtx_yolov7_head_decode_nhwc)
-                                                               : (f32 ? trtx_yolov5_head_decode_nhwc_f32 : trtx_yolov5_head_decode_nhwc);
-                st = decode(
-                        heads, lds, nl, op.i[11] > 0 ? op.i[11] : batch, op.i[0], op.i[1], op.i[2], gw, gh, op.fv.data(), op.i[3],
-                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
-                break;
-            }
-            case OP_YOLO9_HEAD: {
-                const void* box[3];
-                const void* cls[3];
-                int box_ld[3], cls_ld[3];
-                if (op.i[4] != 3 || op.in.size() != 3 || op.extra_in.size() != 3) { st = TRTX_ERR_STATE; break; }
-                for (int k = 0; k < 3; ++k) {
-                    box[k] = R.ptr(op.in[k]);
-                    box_ld[k] = plan.tensors[op.in[k]].ld;
-                    cls[k] = R.ptr(op.extra_in[k]);
-                    cls_ld[k] = plan.tensors[op.extra_in[k]].ld;
-                }
-                st = (t0.dtype == DT_F32 ? trtx_yolov9_head_decode_nhwc_f32 : trtx_yolov9_head_decode_nhwc)(
-                        box, box_ld, cls, cls_ld, batch, op.i[0], op.i[1], op.i[2], reinterpret_cast<const float*>(W + op.w_off), op.i[3],
-                        static_cast<float*>(R.ptr(op.out[0])), static_cast<char*>(c->d_arena) + op.ws_off, op.ws_bytes, stream);
-                break;
-            }
             case OP_ATTENTION: {
                 const PTensor &to2 = plan.tensors[op.out[1]];
                 if (op.i[4] > 0)

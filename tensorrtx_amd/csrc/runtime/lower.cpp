@@ -244,8 +244,8 @@ struct Lowerer {
         for (int t : f.branch_tensor) branches.push_back(need_nhwc(t));
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
         const bool task = !f.branch_tensor.empty();
-        POp& op = add_op(task ? OP_YOLO_TASK_HEAD : (f.v10 ? OP_YOLO10_HEAD : OP_YOLO_HEAD),
-                         l.name + (task ? " [fused DFL+task decode]" : (f.v10 ? " [fused DFL+decode, 6-float records]" : " [fused DFL+decode]")), ins, {out});
+        const HeadOp& head = task ? *head_op(OP_YOLO_TASK_HEAD) : head_op_of(f.params.form);
+        POp& op = add_op(head.kind, l.name + head.suffix, ins, {out});
         op.extra_in = branches;
         op.src_layer = f.dfl_conv_layer;
         op.i[0] = f.params.classes;
@@ -262,7 +262,7 @@ struct Lowerer {
         }
         // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
         if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
-        op.ws_bytes = trtx_yolo_head_decode_workspace(net.explicit_batch ? op.i[11] : plan.max_batch, f.params.net_h, f.params.net_w, f.params.strides.data(),
+        op.ws_bytes = head.stride_ws(net.explicit_batch ? op.i[11] : plan.max_batch, f.params.net_h, f.params.net_w, f.params.strides.data(),
                                                       (int)f.params.strides.size());
         for (int t : ins) op.bytes += (double)dtype_size(dt) * plan.tensors[t].dims.volume();
         op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
@@ -273,15 +273,15 @@ struct Lowerer {
     // The anchor head at its plugin's layer: the detect convolutions' NHWC tensors in, the plugin's LINEAR output out.
     bool emit_yolo5_head(const Yolo5HeadFuse& f) {
         const LayerDef& l = net.layers[f.plugin_layer];
-        const Yolo5LayerParams& pr = f.params;
+        const YoloParams& pr = f.params;
+        const HeadOp& head = head_op_of(pr.form);
         std::vector<int> ins;
         for (int t : f.head_tensor) {
             if (plan.tensors[pt_of[t]].layout != LAY_NHWC) return fail(l.name + ": fused anchor head on a tensor that is not NHWC");
             ins.push_back(pt_of[t]);
         }
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
-        POp& op = add_op(f.darknet ? OP_DARKNET_HEAD : (f.v7 ? OP_YOLO7_HEAD : OP_YOLO5_HEAD),
-                         l.name + (f.darknet ? " [fused Darknet anchor decode, 7-float records]" : (f.v7 ? " [fused anchor decode, 6-float records]" : " [fused anchor decode]")), ins, {out});
+        POp& op = add_op(head.kind, l.name + head.suffix, ins, {out});
         op.i[0] = pr.classes;
         op.i[1] = pr.net_h;
         op.i[2] = pr.net_w;
@@ -294,7 +294,7 @@ struct Lowerer {
         op.fv = pr.anchors;
         // explicit batch: the image count is the heads' leading dimension (op.i[11]; 0 = the enqueue's batch)
         if (net.explicit_batch) op.i[11] = plan.tensors[ins[0]].nfix;
-        op.ws_bytes = (f.darknet ? trtx_darknet_head_decode_workspace : (f.v7 ? trtx_yolov7_head_decode_workspace : trtx_yolov5_head_decode_workspace))(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
+        op.ws_bytes = head.anchor_ws(net.explicit_batch ? op.i[11] : plan.max_batch, pr.grid_w.data(), pr.grid_h.data(), (int)ins.size());
         // what it must read: the three objectness values of every pixel (nothing else of a pixel without a candidate), and what it writes
         for (int t : ins) op.bytes += (double)dtype_size(dt) * plan.tensors[t].H * plan.tensors[t].W * 3;
         op.bytes += 4.0 * net.tensors[l.outputs[0]].dims.volume();
@@ -306,12 +306,12 @@ struct Lowerer {
     // plugin's LINEAR output out; the DFL weights come from src_layer like OP_YOLO_HEAD's.
     bool emit_yolo9_head(const Yolo9HeadFuse& f) {
         const LayerDef& l = net.layers[f.plugin_layer];
-        const Yolo9LayerParams& pr = f.params;
+        const YoloParams& pr = f.params;
         std::vector<int> boxes, clss;
         for (int t : f.box_tensor) boxes.push_back(need_nhwc(t));
         for (int t : f.cls_tensor) clss.push_back(need_nhwc(t));
         const int out = new_tensor(l.outputs[0], net.tensors[l.outputs[0]].dims, LAY_LINEAR, true);
-        POp& op = add_op(OP_YOLO9_HEAD, l.name + " [fused DFL+decode, 38-float records]", boxes, {out});
+        POp& op = add_op(OP_YOLO9_HEAD, l.name + head_op_of(YOLO_V9).suffix, boxes, {out});
         op.extra_in = clss;
         op.src_layer = f.dfl_conv_layer;
         op.i[0] = pr.classes;

@@ -224,15 +224,14 @@ void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
         const LayerDef& l = net.layers[li];
         if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li]) continue;
         YoloHeadFuse h;
-        if (!builtin_yolo_params(l.plugin->v, &h.params)) {
-            // the YOLOv10 plugin (yolov10/src/model.cpp:202-255: the same tail in front of 6-float records), explicit batch only, any class count
-            if (task || !e || !g.opt.yolo10_head || !builtin_yolo10_params(l.plugin->v, &h.params)) continue;
-            h.v10 = true;
-        }
-        const YoloLayerParams& pr = h.params;
+        if (!builtin_yolo_params(l.plugin->v, &h.params)) continue;
+        const YoloParams& pr = h.params;
+        // the YOLOv10 plugin (yolov10/src/model.cpp:202-255: the same tail in front of 6-float records), explicit batch only, any class count
+        const bool v10 = pr.form == YOLO_V10;
+        if (v10 ? (task || !e || !g.opt.yolo10_head) : pr.form != YOLO_V8) continue;
         if (pr.strides.size() != l.inputs.size()) continue;
         if (task ? (pr.seg + pr.pose + pr.obb != 1 || l.inputs.size() > 4 || (pr.pose && (pr.nk < 1 || pr.nk > 17)))
-                 : (!pr.det_only || (!h.v10 && pr.classes % 8) || l.inputs.size() > 6))
+                 : (!pr.det_only() || (!v10 && pr.classes % 8) || l.inputs.size() > 6))
             continue;
         const int64_t extra = pr.seg ? 32 : (pr.pose ? 3 * pr.nk : 1);
         std::vector<int> used;
@@ -288,21 +287,19 @@ void match_yolo_heads(const NetView& g, bool task, Fusions& f) {
 // OP_YOLO7_HEAD, TRTX_YOLO7_HEAD=0.  A plugin instance is one form or the other, so the two calls cannot claim the same layer.
 //
 // The Darknet tail (yolov3/yolov3.cpp:282-332, yolov3-tiny/yolov3-tiny.cpp:254-280, yolov4/yolov4.cpp:435-475) is that graph once more in front of
-// the zero-field plugin (`form` 2): two or three detect convolutions in the plugin's own order, one OP_DARKNET_HEAD, TRTX_DARKNET_HEAD=0.
-void match_anchor_heads(const NetView& g, int form, Fusions& f) {
+// the zero-field plugin (`form` YOLO_DARKNET): two or three detect convolutions in the plugin's own order, one OP_DARKNET_HEAD, TRTX_DARKNET_HEAD=0.
+void match_anchor_heads(const NetView& g, YoloForm form, Fusions& f) {
     const Network& net = g.net;
     const int e = net.explicit_batch ? 1 : 0;
-    const bool v7 = form == 1, darknet = form == 2;
+    const bool v7 = form == YOLO_V7, darknet = form == YOLO_DARKNET;
     if (!(darknet ? g.opt.darknet_head : (v7 ? g.opt.yolo7_head : g.opt.yolo5_head))) return;
     if ((v7 || darknet) && net.int8) return;   // kINT8 YOLOv7 networks keep the plugin route: the 6-float head was never run behind a calibrated convolution
     for (size_t li = 0; li < net.layers.size(); ++li) {
         const LayerDef& l = net.layers[li];
         if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li] || !l.plugin) continue;
         Yolo5HeadFuse h;
-        h.v7 = v7;
-        h.darknet = darknet;
-        if (!(darknet ? builtin_darknet_params : (v7 ? builtin_yolo7_params : builtin_yolo5_params))(l.plugin->v, &h.params)) continue;
-        const Yolo5LayerParams& pr = h.params;
+        if (!builtin_yolo_params(l.plugin->v, &h.params) || h.params.form != form) continue;
+        const YoloParams& pr = h.params;
         if (pr.seg || pr.classes < 1 || l.inputs.empty() || l.inputs.size() > 8 || l.inputs.size() != pr.grid_w.size()) continue;
         bool ok = true;
         for (size_t k = 0; ok && k < l.inputs.size(); ++k) {
@@ -328,7 +325,7 @@ void match_anchor_heads(const NetView& g, int form, Fusions& f) {
     }
 }
 
-void match_yolo5_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 0, f); }
+void match_yolo5_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, YOLO_V5, f); }
 
 // ---- ReOrg (yolov7/src/block.cpp:106-114; YOLOv5's Focus is the same graph): four slices of one image tensor with step (1, 2, 2) and
 // starts (0,0,0), (0,1,0), (0,0,1), (0,1,1), whole-channel, concatenated in that order on the channel axis, read by nothing but one
@@ -429,8 +426,8 @@ void match_repvggdw_fold(const NetView& g, Fusions& f) {
     }
 }
 
-void match_yolo7_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 1, f); }
-void match_darknet_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, 2, f); }
+void match_yolo7_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, YOLO_V7, f); }
+void match_darknet_heads(const NetView& g, Fusions& f) { match_anchor_heads(g, YOLO_DARKNET, f); }
 
 // ---- YOLOv9 / GELAN detect tail (yolov9/src/block.cpp:424-489): per level the concat of [DFL chain on the grouped 1x1 convolution's
 // (64, gh, gw) output, reshape (classes, gh * gw) of the class convolution's output] into the YOLOv9 YoloLayer_TRT.  Unlike YOLOv8's tail
@@ -448,8 +445,8 @@ void match_yolo9_heads(const NetView& g, Fusions& f) {
         const LayerDef& l = net.layers[li];
         if (l.kind != L_PLUGIN || l.outputs.size() != 1 || f.absorbed[li] || !l.plugin) continue;
         Yolo9HeadFuse h;
-        if (!builtin_yolo9_params(l.plugin->v, &h.params)) continue;
-        const Yolo9LayerParams& pr = h.params;
+        if (!builtin_yolo_params(l.plugin->v, &h.params) || h.params.form != YOLO_V9) continue;
+        const YoloParams& pr = h.params;
         if (pr.seg || pr.classes < 1 || l.inputs.size() != 3) continue;
         std::vector<int> used;
         bool ok = true;

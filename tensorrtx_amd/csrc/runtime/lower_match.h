@@ -29,8 +29,7 @@ struct YoloHeadFuse {
     std::vector<int> head_tensor;  // network tensor per level: CHW (64 + classes, gh, gw)
     std::vector<int> branch_tensor;  // task head: network tensor per level, the cv4 convolution's output (B, extra, gh, gw)
     int dfl_conv_layer = -1;
-    YoloLayerParams params;
-    bool v10 = false;               // the YOLOv10 plugin: 6-float records, any class count, OP_YOLO10_HEAD
+    YoloParams params;              // form YOLO_V8, or YOLO_V10: 6-float records, any class count, OP_YOLO10_HEAD
 };
 
 // RepVGGDW (yolov10/src/block.cpp:388-403) on one tensor: depthwise 7x7 s1 p3 + scale, depthwise 3x3 s1 p1 + scale, their sum; the SiLU
@@ -43,9 +42,8 @@ struct Yolo5HeadFuse {
     int plugin_layer = -1;
     std::vector<int> head_tensor;   // network tensor per level: a detect convolution's output (3 * (5 + classes), gh, gw)
     std::vector<int> conv_layer;    // ... and the layer that produces it
-    Yolo5LayerParams params;
-    bool v7 = false;                // the YOLOv7 plugin: 6-float records, OP_YOLO7_HEAD
-    bool darknet = false;           // the Darknet plugin (YOLOv3 / YOLOv3-tiny / YOLOv4): 7-float records, OP_DARKNET_HEAD
+    YoloParams params;              // form YOLO_V5, YOLO_V7 (6-float records, OP_YOLO7_HEAD) or YOLO_DARKNET (YOLOv3 / YOLOv3-tiny / YOLOv4: 7-float
+                                    // records, OP_DARKNET_HEAD)
 };
 
 struct Yolo9HeadFuse {
@@ -54,7 +52,7 @@ struct Yolo9HeadFuse {
     std::vector<int> cls_tensor;    // ... and the class convolution's output (classes, gh, gw)
     std::vector<int> cls_conv;      // the layers that produce the class tensors
     int dfl_conv_layer = -1;
-    Yolo9LayerParams params;
+    YoloParams params;              // form YOLO_V9
 };
 
 struct AttentionFuse {

@@ -271,7 +271,7 @@ bool pack_weights(const Network& net, Plan* plan) {
             op.b_off = reserve(bias.size() * 4);
             memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
             op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (op.grouped ? (size_t)cout * a.Kpad * 2 : (size_t)cout * a.K * 4));
-        } else if (op.kind == OP_YOLO_HEAD || op.kind == OP_YOLO_TASK_HEAD || op.kind == OP_YOLO9_HEAD || op.kind == OP_YOLO10_HEAD) {
+        } else if (head_has_dfl(op.kind)) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);
             memcpy(blob.data() + op.w_off, l.w0.data(), 16 * 4);

@@ -15,6 +15,24 @@ const char* op_kind_name(int k) {
     return (k >= 0 && k <= OP_YOLO10_HEAD) ? n[k] : "?";
 }
 
+// In YoloForm's order, the task head behind them
+static const HeadOp kHeadOps[YOLO_FORMS + 1] = {
+        {OP_YOLO_HEAD, " [fused DFL+decode]", 0, 8, true, {trtx_yolo_head_decode_nhwc, trtx_yolo_head_decode_nhwc_f32}, trtx_yolo_head_decode_workspace, {}, nullptr},
+        {OP_YOLO5_HEAD, " [fused anchor decode]", 1, 8, false, {}, nullptr, {trtx_yolov5_head_decode_nhwc, trtx_yolov5_head_decode_nhwc_f32}, trtx_yolov5_head_decode_workspace},
+        {OP_YOLO9_HEAD, " [fused DFL+decode, 38-float records]", 3, 3, true, {}, nullptr, {}, nullptr},
+        {OP_YOLO7_HEAD, " [fused anchor decode, 6-float records]", 1, 8, false, {}, nullptr, {trtx_yolov7_head_decode_nhwc, trtx_yolov7_head_decode_nhwc_f32}, trtx_yolov7_head_decode_workspace},
+        {OP_DARKNET_HEAD, " [fused Darknet anchor decode, 7-float records]", 1, 8, false, {}, nullptr, {trtx_darknet_head_decode_nhwc, trtx_darknet_head_decode_nhwc_f32}, trtx_darknet_head_decode_workspace},
+        // the workspace is OP_YOLO_HEAD's: the same candidate lists
+        {OP_YOLO10_HEAD, " [fused DFL+decode, 6-float records]", 1, 5, true, {trtx_yolov10_head_decode_nhwc, trtx_yolov10_head_decode_nhwc_f32}, trtx_yolo_head_decode_workspace, {}, nullptr},
+        {OP_YOLO_TASK_HEAD, " [fused DFL+task decode]", 0, 4, true, {}, trtx_yolo_head_decode_workspace, {}, nullptr},
+};
+const HeadOp& head_op_of(YoloForm form) { return kHeadOps[form]; }
+const HeadOp* head_op(int kind) {
+    for (const HeadOp& h : kHeadOps)
+        if (h.kind == kind) return &h;
+    return nullptr;
+}
+
 std::string Plan::describe_json() const {
     std::ostringstream o;
     double flops = 0, bytes = 0;
@@ -63,39 +81,38 @@ std::string Plan::describe_json() const {
         if (op.kind == OP_HGCONV)
             o << ",\"n\":" << op.i[0] << ",\"d\":" << op.i[1] << ",\"e\":" << op.i[2] << ",\"logit_scale\":" << op.f[0] << ",\"ld\":[" << tensors[op.in[0]].ld << ","
               << tensors[op.out[0]].ld << "],\"ws_bytes\":" << op.ws_bytes;
-        if (op.kind == OP_YOLO_TASK_HEAD) {
-            o << ",\"task\":\"" << (op.i[9] == 1 ? "seg" : (op.i[9] == 2 ? "pose" : "obb")) << "\",\"classes\":" << op.i[0] << ",\"nk\":" << op.i[10]
-              << ",\"branch_ld\":[";
-            for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
-            o << "]";
-        }
         if (op.kind == OP_POOL || op.kind == OP_POOL_CHAIN)
             o << ",\"k\":[" << op.i[1] << "," << op.i[2] << "],\"stride\":[" << op.i[3] << "," << op.i[4] << "],\"outputs\":" << op.out.size();
         if (op.kind == OP_PAD_NHWC) o << ",\"pre\":[" << op.i[0] << "," << op.i[1] << "]";
-        if (op.kind == OP_YOLO5_HEAD || op.kind == OP_YOLO7_HEAD || op.kind == OP_DARKNET_HEAD) {
-            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"anchor_levels\":" << op.fv.size() / 6 << ",\"grids\":[";
-            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]";
-            o << "],\"ld\":[";
-            for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
+        // the fused heads, from shared pieces
+        auto list = [&](const char* key, int n, auto item) {
+            o << ",\"" << key << "\":[";
+            for (int j = 0; j < n; ++j) {
+                o << (j ? "," : "");
+                item(j);
+            }
             o << "]";
-        }
-        if (op.kind == OP_YOLO10_HEAD) {
-            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"strides\":[";
-            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << op.i[5 + j];
-            o << "],\"ld\":[";
-            for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
-            o << "]";
-        }
-        if (op.kind == OP_YOLO9_HEAD) {
-            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4] << ",\"grids\":[";
-            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << "[" << op.i[2] / (8 << j) << "," << op.i[1] / (8 << j) << "]";
-            o << "],\"strides\":[";
-            for (int j = 0; j < op.i[4]; ++j) o << (j ? "," : "") << (8 << j);
-            o << "],\"box_ld\":[";
-            for (size_t j = 0; j < op.in.size(); ++j) o << (j ? "," : "") << tensors[op.in[j]].ld;
-            o << "],\"cls_ld\":[";
-            for (size_t j = 0; j < op.extra_in.size(); ++j) o << (j ? "," : "") << tensors[op.extra_in[j]].ld;
-            o << "]";
+        };
+        auto lds = [&](const char* key, const std::vector<int>& ts) { list(key, (int)ts.size(), [&](int j) { o << tensors[ts[j]].ld; }); };
+        const HeadOp* head = head_op(op.kind);
+        if (op.kind == OP_YOLO_TASK_HEAD) {
+            o << ",\"task\":\"" << (op.i[9] == 1 ? "seg" : (op.i[9] == 2 ? "pose" : "obb")) << "\",\"classes\":" << op.i[0] << ",\"nk\":" << op.i[10];
+            lds("branch_ld", op.extra_in);
+        } else if (head && op.kind != OP_YOLO_HEAD) {
+            o << ",\"classes\":" << op.i[0] << ",\"levels\":" << op.i[4];
+            if (head->anchor_ws) {
+                o << ",\"anchor_levels\":" << op.fv.size() / 6;
+                list("grids", op.i[4], [&](int j) { o << "[" << op.iv[2 * j] << "," << op.iv[2 * j + 1] << "]"; });
+            }
+            if (op.kind == OP_YOLO9_HEAD) {
+                list("grids", op.i[4], [&](int j) { o << "[" << op.i[2] / (8 << j) << "," << op.i[1] / (8 << j) << "]"; });
+                list("strides", op.i[4], [&](int j) { o << (8 << j); });
+                lds("box_ld", op.in);
+                lds("cls_ld", op.extra_in);
+            } else {
+                if (head->stride_ws) list("strides", op.i[4], [&](int j) { o << op.i[5 + j]; });
+                lds("ld", op.in);
+            }
         }
         if (op.kind == OP_CONV_GROUP) {
             o << ",\"members\":[";

@@ -71,6 +71,25 @@ enum OpKind : int {
 };
 const char* op_kind_name(int k);
 
+// The fused detect heads: the op that stands in for one form of YoloLayer_TRT and the tail in front of it, and the YOLO11 task head.
+// One row each (plan.cpp): what the emission, the engine and describe_json would otherwise choose by comparing kinds.
+struct HeadOp {
+    int kind;                     // OP_*
+    const char* suffix;           // of the op's name, behind the plugin layer's
+    int min_levels, max_levels;   // the i[4] the engine runs
+    bool dfl;                     // carries the 16 DFL weights, packed from src_layer
+    // the entry points, [1] for fp32 tensors, and the workspace size, of the kinds whose levels are told by strides (i[5..]) ...
+    decltype(&trtx_yolo_head_decode_nhwc) stride_decode[2];
+    decltype(&trtx_yolo_head_decode_workspace) stride_ws;
+    // ... and of those told by grids and anchors (iv, fv); OP_YOLO_TASK_HEAD's and OP_YOLO9_HEAD's argument lists are their own
+    decltype(&trtx_yolov5_head_decode_nhwc) anchor_decode[2];
+    decltype(&trtx_yolov5_head_decode_workspace) anchor_ws;
+};
+const HeadOp* head_op(int kind);          // null for any other kind
+const HeadOp& head_op_of(YoloForm form);  // the detection head of that form
+inline bool is_fused_head(int kind) { return head_op(kind) != nullptr; }
+inline bool head_has_dfl(int kind) { return is_fused_head(kind) && head_op(kind)->dfl; }
+
 struct PTensor {
     int id = -1;
     int net_tensor = -1;

@@ -965,7 +965,7 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
     for (int k = 0; k < nops; ++k) {
         const int kind = plan.ops[k].kind;
-        if ((kind != OP_PLUGIN && kind != OP_YOLO_HEAD && kind != OP_YOLO_TASK_HEAD && kind != OP_YOLO5_HEAD && kind != OP_YOLO9_HEAD && kind != OP_YOLO7_HEAD && kind != OP_DARKNET_HEAD && kind != OP_YOLO10_HEAD && kind != OP_HGCONV) || plan.ops[k].ws_bytes == 0) continue;
+        if ((kind != OP_PLUGIN && !is_fused_head(kind) && kind != OP_HGCONV) || plan.ops[k].ws_bytes == 0) continue;
         Storage s;
         s.kind = ST_ARENA;
         s.bytes = plan.ops[k].ws_bytes;

@@ -78,40 +78,24 @@ class PluginRegistry {
 
 // built-in HIP plugins (plugins/builtin_plugins.cpp)
 void register_builtin_plugins(PluginRegistry& r);
-// parameters of a *built-in* YoloLayer_TRT instance (false for any other / user-provided plugin): lets the
-// lowering pass replace the DFL + plugin tail by the fused NHWC kernel
-struct YoloLayerParams {
+// The plugins of the reference that share the registered name "YoloLayer_TRT"/"1", in the order a blob is probed for them
+// (plugins/builtin_plugins.cpp, kYoloForms)
+enum YoloForm : int { YOLO_V8 = 0, YOLO_V5, YOLO_V9, YOLO_V7, YOLO_DARKNET, YOLO_V10, YOLO_FORMS };
+// parameters of a *built-in* YoloLayer_TRT instance (false for any other / user-provided plugin, and for a Darknet instance that has
+// not seen its inputs yet: it reads classes, grids, net size and its family's anchor table off them when the layer is added): lets the
+// lowering pass replace the plugin and the tail in front of it by that form's fused head
+struct YoloParams {
+    YoloForm form;
     int classes, net_w, net_h, max_out;
-    std::vector<int> strides;
-    bool det_only;
-    bool seg = false, pose = false, obb = false;   // the plugin's task branches (yololayer.cu:222-279)
+    bool seg = false, pose = false, obb = false;   // the plugin's task branches (yolov8 yololayer.cu:222-279; seg alone: YOLOv5, YOLOv9)
     int nk = 0;                                   // keypoints per record (pose)
     float kpt_conf = 0.f;                         // keypoint confidence threshold (pose)
+    std::vector<int> strides;                     // per level: YOLOv8, YOLOv10 (YOLOv9's are 8 / 16 / 32)
+    std::vector<int> grid_w, grid_h;              // per level (YoloKernel::width / height): YOLOv5, YOLOv7, Darknet
+    std::vector<float> anchors;                   // ... and per level 6 floats
+    bool det_only() const { return !(seg || pose || obb); }
 };
-bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloLayerParams* out);
-// the same for a *built-in* YOLOv10 YoloLayer_TRT instance ("combinedInfo" of 5 to 9 ints; 6-float records, det_only)
-bool builtin_yolo10_params(const trtx_plugin_vtbl& v, YoloLayerParams* out);
-// parameters of a *built-in* anchor-based YoloLayer_TRT instance (the yolov5 field set "netinfo" + "kernels"; false for anything else):
-// lets the lowering pass replace the layout passes + plugin tail by the fused anchor head
-struct Yolo5LayerParams {
-    int classes, net_w, net_h, max_out;
-    bool seg;
-    std::vector<int> grid_w, grid_h;   // per level (YoloKernel::width / height)
-    std::vector<float> anchors;        // per level 6 floats
-};
-bool builtin_yolo5_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
-// the same for a built-in YOLOv7 YoloLayer_TRT instance ("netinfo" of four ints + "kernels"; 6-float records, seg is false)
-bool builtin_yolo7_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
-// ... and for a built-in Darknet YoloLayer_TRT instance (created with no fields; 7-float records, max_out 1000): the plugin reads classes,
-// grids, net size and its family's anchor table off its inputs when the layer is added; false until then
-bool builtin_darknet_params(const trtx_plugin_vtbl& v, Yolo5LayerParams* out);
-// parameters of a *built-in* YOLOv9 YoloLayer_TRT instance (the single field "netinfo"; false for anything else): lets the lowering pass
-// replace the DFL chains, layout passes and the plugin by the fused DDetect head.  Three levels, strides 8 / 16 / 32.
-struct Yolo9LayerParams {
-    int classes, net_w, net_h, max_out;
-    bool seg;
-};
-bool builtin_yolo9_params(const trtx_plugin_vtbl& v, Yolo9LayerParams* out);
+bool builtin_yolo_params(const trtx_plugin_vtbl& v, YoloParams* out);
 // true for the built-in "Mish_TRT" (plugins/builtin_plugins.cpp; yolov4/mish.{h,cu}): a pointwise activation, which the lowering pass
 // folds into the producing convolution's epilogue (ACT_MISH) or runs as an activation op in the tensor's own layout
 bool builtin_is_mish(const trtx_plugin_vtbl& v);
