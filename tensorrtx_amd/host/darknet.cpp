@@ -21,12 +21,13 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
 #include "models.h"
+#include "yolo_blocks.h"
 
 using namespace nvinfer1;
 
 namespace trtx_host {
+using blocks::plugin_layer;
 namespace {
 
 enum Kind : char {
@@ -191,53 +192,28 @@ Table yolov4_table() {   // yolov4.cpp:243-469, modules 0 .. 160
 
 // One network under construction: y[i] is the output of module i (null for a yolo module).
 struct Build {
-    INetworkDefinition* net;
-    WeightMap& wm;
+    Ctx& c;
     const DarknetConfig& cfg;
     float eps;
     std::vector<ITensor*> y;
     std::vector<ITensor*> dets;
 
-    ITensor* convBn(ITensor& in, const Row& r, int i) {
+    ITensor* convBn(ITensor& in, const Row& r, int i) {   // the convolution layer is named module_list.<i>.Conv2d
         const std::string m = "module_list." + std::to_string(i);
-        auto* conv = net->addConvolutionNd(in, r.ch, DimsHW{r.k, r.k}, need(wm, m + ".Conv2d.weight"), noWeights());
-        assert(conv);
-        conv->setName((m + ".Conv2d").c_str());
-        conv->setStrideNd(DimsHW{r.s, r.s});
-        conv->setPaddingNd(DimsHW{r.p, r.p});
-        return addBatchNorm2d(net, wm, *conv->getOutput(0), m + ".BatchNorm2d", eps)->getOutput(0);
-    }
-    ITensor* leaky(ITensor& in) {
-        auto* act = net->addActivation(in, ActivationType::kLEAKY_RELU);
-        assert(act);
-        act->setAlpha(0.1f);
-        return act->getOutput(0);
+        return blocks::conv_bn(c, in, r.ch, r.k, r.s, r.p, m + ".Conv2d", m + ".BatchNorm2d", 1, false, eps, /*named=*/true);
     }
     ITensor* mish(ITensor& in, int i) {   // yolov4.cpp:208-212
-        auto* creator = getPluginRegistry()->getPluginCreator("Mish_TRT", "1");
-        assert(creator && "Mish_TRT creator not registered");
-        IPluginV2* plugin = creator->createPlugin(("mish" + std::to_string(i)).c_str(), creator->getFieldNames());
-        assert(plugin);
-        ITensor* ins[] = {&in};
-        auto* layer = net->addPluginV2(ins, 1, *plugin);
-        plugin->destroy();  // the network holds its own clone
+        auto* layer = plugin_layer(c, "Mish_TRT", "mish" + std::to_string(i), nullptr, {&in});
         assert(layer);
         return layer->getOutput(0);
-    }
-    ITensor* maxpool(ITensor& in, int k, int s, int p) {
-        auto* pool = net->addPoolingNd(in, PoolingType::kMAX, DimsHW{k, k});
-        assert(pool);
-        pool->setStrideNd(DimsHW{s, s});
-        pool->setPaddingNd(DimsHW{p, p});
-        return pool->getOutput(0);
     }
     ITensor* upsample(ITensor& in, int i) {   // yolov4.cpp:393-402
         const int ch = (int)in.getDimensions().d[0];
         float* ones = static_cast<float*>(std::malloc(sizeof(float) * ch * 4));
         for (int j = 0; j < ch * 4; ++j) ones[j] = 1.0f;
         const Weights w{DataType::kFLOAT, ones, (int64_t)ch * 4};
-        wm["deconv" + std::to_string(i)] = w;   // released with the map
-        auto* up = net->addDeconvolutionNd(in, ch, DimsHW{2, 2}, w, noWeights());
+        c.wm["deconv" + std::to_string(i)] = w;   // released with the map
+        auto* up = c.net->addDeconvolutionNd(in, ch, DimsHW{2, 2}, w, noWeights());
         assert(up);
         up->setStrideNd(DimsHW{2, 2});
         up->setNbGroups(ch);
@@ -250,32 +226,32 @@ struct Build {
             ITensor* in = r.from.empty() ? (i ? y[i - 1] : image) : y[r.from[0]];
             ITensor* out = nullptr;
             switch (r.kind) {
-                case LEAKY: out = leaky(*convBn(*in, r, i)); break;
+                case LEAKY: out = blocks::leaky(c, convBn(*in, r, i)); break;
                 case MISH: out = mish(*convBn(*in, r, i), i); break;
                 case DETECT: {
                     const std::string m = "module_list." + std::to_string(i) + ".Conv2d";
-                    auto* det = net->addConvolutionNd(*in, 3 * (cfg.num_class + 5), DimsHW{1, 1}, need(wm, m + ".weight"), need(wm, m + ".bias"));
+                    auto* det = c.net->addConvolutionNd(*in, 3 * (cfg.num_class + 5), DimsHW{1, 1}, need(c.wm, m + ".weight"), need(c.wm, m + ".bias"));
                     assert(det);
                     det->setName(m.c_str());
                     out = det->getOutput(0);
                     dets.push_back(out);
                     break;
                 }
-                case SHORTCUT: out = net->addElementWise(*y[r.from[0]], *y[r.from[1]], ElementWiseOperation::kSUM)->getOutput(0); break;
+                case SHORTCUT: out = blocks::sum(c, *y[r.from[0]], *y[r.from[1]]); break;
                 case ROUTE:
                     if (r.from.size() == 1) {
                         out = y[r.from[0]];
                     } else {
                         std::vector<ITensor*> v;
                         for (int f : r.from) v.push_back(y[f]);
-                        out = net->addConcatenation(v.data(), (int32_t)v.size())->getOutput(0);
+                        out = blocks::cat(c, v);
                     }
                     break;
-                case POOL: out = maxpool(*in, r.k, r.s, r.p); break;
+                case POOL: out = blocks::maxpool(c, *in, r.k, r.s, r.p); break;
                 case PADPOOL: {   // yolov3-tiny.cpp:248-250
-                    auto* pad = net->addPaddingNd(*in, DimsHW{0, 0}, DimsHW{1, 1});
+                    auto* pad = c.net->addPaddingNd(*in, DimsHW{0, 0}, DimsHW{1, 1});
                     assert(pad);
-                    out = maxpool(*pad->getOutput(0), 2, 1, 0);
+                    out = blocks::maxpool(c, *pad->getOutput(0), 2, 1, 0);
                     break;
                 }
                 case UPSAMPLE: out = upsample(*in, i); break;
@@ -307,38 +283,15 @@ std::string darknet_rows_json(const std::string& name) {
 IHostMemory* buildEngineDarknet(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const DarknetConfig& cfg) {
     if (!darknet_model_valid(cfg.model)) return nullptr;
     const Table t = cfg.model == "yolov3" ? yolov3_table() : (cfg.model == "yolov4" ? yolov4_table() : yolov3_tiny_table());
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    IHostMemory* plan = nullptr;
-    {
-        ITensor* data = net->addInput("data", DataType::kFLOAT, Dims3{3, cfg.input_h, cfg.input_w});
-        assert(data);
-        Build b{net, wm, cfg, cfg.model == "yolov3" ? 1e-5f : 1e-4f, {}, {}};
-        b.run(t, data);
-        if (cfg.mark_heads)
-            for (size_t i = 0; i < b.dets.size(); ++i) {
-                b.dets[i]->setName(("head" + std::to_string(i)).c_str());
-                net->markOutput(*b.dets[i]);
-            }
-        auto* creator = getPluginRegistry()->getPluginCreator("YoloLayer_TRT", "1");
-        assert(creator && "YoloLayer_TRT creator not registered");
-        // yolov4.cpp:471-473: created with the creator's own field collection, which is empty; that is what tells the registry's creator the Darknet form
-        IPluginV2* plugin = creator->createPlugin("yololayer", creator->getFieldNames());
-        if (plugin) {
-            auto* yolo = net->addPluginV2(b.dets.data(), (int32_t)b.dets.size(), *plugin);
-            plugin->destroy();  // the network holds its own clone
-            assert(yolo);
-            yolo->getOutput(0)->setName("prob");
-            net->markOutput(*yolo->getOutput(0));
-            builder->setMaxBatchSize(cfg.max_batch);
-            config->setMaxWorkspaceSize(16 * (1 << 20));
-            if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-            plan = builder->buildSerializedNetwork(*net, *config);
-        }
-    }
-    delete net;
-    freeWeights(wm);
-    return plan;
+    Session s(builder, wts);
+    Build b{s.c, cfg, cfg.model == "yolov3" ? 1e-5f : 1e-4f, {}, {}};
+    b.run(t, s.input("data", cfg.input_h, cfg.input_w));
+    if (cfg.mark_heads) s.mark_heads(b.dets);
+    // yolov4.cpp:471-473: created with the creator's own field collection, which is empty; that is what tells the registry's creator the Darknet form
+    auto* yolo = plugin_layer(s.c, "YoloLayer_TRT", "yololayer", nullptr, b.dets);
+    if (!yolo) return nullptr;
+    s.output(yolo->getOutput(0), "prob");
+    return s.finish(builder, config, cfg.max_batch, cfg.fp16);
 }
 
 }  // namespace trtx_host

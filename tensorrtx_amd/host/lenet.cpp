@@ -4,7 +4,7 @@
 // ElementWise(SUM), and a softmax.  PyTorch twin: lenet/gen_wts.py:10-45.
 #include <cmath>
 
-#include "common.h"
+#include "build.h"
 #include "models.h"
 
 using namespace nvinfer1;
@@ -12,11 +12,10 @@ using namespace nvinfer1;
 namespace trtx_host {
 
 IHostMemory* buildLenet(IBuilder* builder, IBuilderConfig* config, const std::string& wts, int32_t N) {
-    WeightMap wm = loadWeights(wts);
-    const uint32_t flag = 1U << static_cast<int>(NetworkDefinitionCreationFlag::kEXPLICIT_BATCH);
-    INetworkDefinition* net = builder->createNetworkV2(flag);
-    ITensor* x = net->addInput("data", DataType::kFLOAT, Dims4{N, 1, 32, 32});
-    assert(x);
+    Session s(builder, wts, N);
+    WeightMap& wm = s.wm;
+    INetworkDefinition* net = s.net;
+    ITensor* x = s.input("data", 32, 32, 1);
 
     // Layer creation order and layer names are the reference's, statement for statement (lenet/lenet.cpp:54-124): its own builder,
     // compiled against the shim, serializes the same bytes (tests/test_ref_builders.py).
@@ -67,14 +66,8 @@ IHostMemory* buildLenet(IBuilder* builder, IBuilderConfig* config, const std::st
     x = fc3sum->getOutput(0);
     ISoftMaxLayer* prob = net->addSoftMax(*x);
     assert(prob);
-    prob->getOutput(0)->setName("prob");
-    net->markOutput(*prob->getOutput(0));
-
-    config->setMemoryPoolLimit(MemoryPoolType::kWORKSPACE, 16 << 20);  // WORKSPACE_SIZE, lenet/utils.h:18
-    IHostMemory* plan = builder->buildSerializedNetwork(*net, *config);
-    delete net;
-    freeWeights(wm);
-    return plan;
+    s.output(prob->getOutput(0), "prob");
+    return s.finish(builder, config, N, /*fp16=*/false);  // the session's 16 MiB workspace is WORKSPACE_SIZE, lenet/utils.h:18
 }
 
 }  // namespace trtx_host

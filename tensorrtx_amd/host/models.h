@@ -21,15 +21,25 @@ nvinfer1::IHostMemory* buildResnet50(nvinfer1::IBuilder* builder, nvinfer1::IBui
 nvinfer1::IHostMemory* buildRetinaFaceR50(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
                                           int maxBatch, bool fp16, int H = 480, int W = 640);
 
-struct Yolov8Config {
+// What every YOLO family's configuration holds: the reference's compile-time constants (include/config.h of each directory) as run-time
+// arguments.  The batch has two spellings, one per kind of network: `batch` where the reference builds explicit batch (the batch is part
+// of the input dims, so a plan serves exactly that many images per enqueue) and `max_batch` where it builds implicit batch
+// (setMaxBatchSize: a plan serves any batch up to it).  They are one field.
+struct YoloConfig {
     int input_h = 640, input_w = 640;   // kInputH / kInputW
     int num_class = 80;                 // kNumClass
-    int max_batch = 1;                  // kBatchSize
+    union {
+        int batch = 1;                  // kBatchSize
+        int max_batch;
+    };
     int max_out_bbox = 1000;            // kMaxNumOutputBbox
     bool fp16 = true;                   // USE_FP16
+    bool mark_heads = false;            // debugging: also expose the plugin's inputs as outputs "head0..N-1"
+};
+
+struct Yolov8Config : YoloConfig {
     float gd = 0.33f, gw = 0.25f;       // 'n' scale (yolov8_det.cpp:130-133)
     int max_channels = 1024;
-    bool mark_heads = false;            // debugging: also expose the three plugin inputs as outputs "head0..2"
     // 0 det (buildEngineYolov8Det), 1 seg (..Seg, model.cpp:1057-1308: + 32 mask coefficients per cell and the "proto" output),
     // 2 pose (..Pose, :1310-1563: + kNumberOfPoints * 3 keypoint values), 3 obb (..Obb, :2499-2740: + 1 angle logit)
     int task = 0;
@@ -42,16 +52,12 @@ nvinfer1::IHostMemory* buildEngineYolov8Det(nvinfer1::IBuilder* builder, nvinfer
 
 // yolo11/include/config.h constants as run-time configuration.  Explicit batch like the reference (model.cpp:143-149): the batch is
 // part of the input dims, so a plan serves exactly `batch` images per enqueue.
-struct Yolo11Config {
-    int input_h = 640, input_w = 640;   // kInputH / kInputW
-    int num_class = 80;                 // kNumClass
-    int batch = 1;                      // kBatchSize (Dims4{kBatchSize, 3, kInputH, kInputW})
-    int max_out_bbox = 1000;            // kMaxNumOutputBbox
-    bool fp16 = true;                   // USE_FP16
-    float gd = 0.50f, gw = 0.25f;       // 'n' scale (yolo11_det.cpp:120-150; yolo11_scale)
+struct Yolo11Scale {                    // shared with YOLOv12: the two programs carry the same table (yolo11_det.cpp / yolo12_det.cpp:120-150)
+    float gd = 0.50f, gw = 0.25f;       // 'n' scale
     int max_channels = 1024;
-    bool c3k = false;                   // C3k blocks inside C3K2 (m / l / x; model.cpp:160-163)
-    bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
+    bool c3k = false;                   // C3k blocks inside C3K2 (m / l / x; model.cpp:160-163, yolov12 model.cpp:60-63)
+};
+struct Yolo11Config : YoloConfig, Yolo11Scale {
     // 0 det, 1 seg (buildEngineYolo11Seg, model.cpp:509-799: + 32 mask coefficients per cell and the "proto" output), 2 pose
     // (..Pose, :801-1090: + 3 * num_points keypoint values), 3 obb (..Obb, :1092-1389: + 1 angle logit), 4 cls (..Cls, :33-136: logits)
     int task = 0;
@@ -59,7 +65,7 @@ struct Yolo11Config {
     float kpt_conf = 0.5f;              // kConfThreshKeypoints (truncated into the plugin field like the reference)
 };
 // the n / s / m / l / x scale: gd, gw, max_channels and the c3k flag; false for an unknown letter
-bool yolo11_scale(char type, Yolo11Config* cfg);
+bool yolo11_scale(char type, Yolo11Scale* cfg);
 // yolo11/src/model.cpp:138-400 (det), 509-799 (seg), 801-1090 (pose), 1092-1389 (obb) with yolo11/src/block.cpp: one graph, the task adds the
 // cv4 branch (and Proto for seg); task 4 builds the classifier (model.cpp:33-136) instead
 nvinfer1::IHostMemory* buildEngineYolo11Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
@@ -67,18 +73,7 @@ nvinfer1::IHostMemory* buildEngineYolo11Det(nvinfer1::IBuilder* builder, nvinfer
 
 // yolov12/include/config.h constants as run-time configuration; explicit batch like YOLO11.  Detection only (the reference has no other
 // YOLOv12 program).
-struct Yolo12Config {
-    int input_h = 640, input_w = 640;   // kInputH / kInputW
-    int num_class = 80;                 // kNumClass
-    int batch = 1;                      // kBatchSize
-    int max_out_bbox = 1000;            // kMaxNumOutputBbox
-    bool fp16 = true;                   // USE_FP16
-    float gd = 0.50f, gw = 0.25f;       // 'n' scale (yolo12_det.cpp:120-150; yolo12_scale)
-    int max_channels = 1024;
-    bool c3k = false;                   // C3k blocks inside C3K2 (m / l / x; model.cpp:60-63)
-    bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
-};
-bool yolo12_scale(char type, Yolo12Config* cfg);
+struct Yolo12Config : YoloConfig, Yolo11Scale {};   // the scale is YOLO11's table: yolo11_scale
 // yolov12/src/model.cpp:33-302 with yolov12/src/block.cpp (A2C2f / ABlock / AAttn: area attention in the backbone).  Returns null when
 // the stride-16 grid's H * W is not divisible by the attention's area count (4).
 nvinfer1::IHostMemory* buildEngineYolo12Det(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config,
@@ -86,15 +81,9 @@ nvinfer1::IHostMemory* buildEngineYolo12Det(nvinfer1::IBuilder* builder, nvinfer
 
 // yolov5/src/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
 // setMaxBatchSize): a plan serves any batch up to max_batch.  Detection, segmentation and classification: `task`.
-struct Yolov5Config {
-    int input_h = 640, input_w = 640;   // kInputH / kInputW
-    int num_class = 80;                 // kNumClass
-    int max_batch = 1;                  // kBatchSize
-    int max_out_bbox = 1000;            // kMaxNumOutputBbox
-    bool fp16 = true;                   // USE_FP16
+struct Yolov5Config : YoloConfig {
     float gd = 0.33f, gw = 0.25f;       // 'n' scale (yolov5_det.cpp:22-41; yolov5_scale)
     bool p6 = false;                    // the P6 models (n6 ... x6): four detect levels, strides 8 .. 64
-    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes (+ 32)), gh, gw) as "head0..N-1"
     // 0 det (build_det_engine / build_det_p6_engine), 1 seg (build_seg_engine, model.cpp:539-628: + 32 mask coefficients per anchor, the
     // plugin's is_segmentation flag and the "proto" output), 4 cls (build_cls_engine, :479-537: logits; num_class is kClsNumClass, input_h /
     // input_w kClsInputH / kClsInputW).  The numbers are Yolo11Config's.  P5 only: the reference has no P6 seg / cls builder.
@@ -118,16 +107,10 @@ inline nvinfer1::IHostMemory* buildEngineYolov5Det(nvinfer1::IBuilder* builder, 
 
 // yolov9/include/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
 // setMaxBatchSize).  Detection only.
-struct Yolov9Config {
+struct Yolov9Config : YoloConfig {
     std::string model = "yolov9t";      // "yolov9t" / "yolov9s" / "yolov9m" / "yolov9c" / "gelanc": the build_engine_* function (yolov9/src/model.cpp)
-    int input_h = 640, input_w = 640;   // kInputH / kInputW
-    int num_class = 80;                 // kNumClass
-    int max_batch = 1;                  // kBatchSize
-    int max_out_bbox = 1000;            // kMaxNumOutputBbox
-    bool fp16 = true;                   // USE_FP16
     bool converted = false;             // isConvert (t / s / m): the re-parameterised checkpoint without the auxiliary branch: its "model.N"
                                         // numbering and DDetect instead of DualDDetect
-    bool mark_heads = false;            // debugging: also expose the three plugin inputs (4 + classes, cells) as outputs "head0..2"
 };
 // what the builder accepts: the five names, `converted` on t / s / m only (trtx_host_build answers TRTX_ERR_INVALID where it is false)
 bool yolov9_model_valid(const std::string& name, bool converted);
@@ -139,14 +122,8 @@ nvinfer1::IHostMemory* buildEngineYolov9(nvinfer1::IBuilder* builder, nvinfer1::
 
 // yolov7/include/config.h constants as run-time configuration.  Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W},
 // setMaxBatchSize).  Detection, which is all the reference's yolov7 builds.
-struct Yolov7Config {
+struct Yolov7Config : YoloConfig {
     std::string model = "yolov7";       // "yolov7tiny" / "yolov7" / "yolov7x" / "yolov7w6" / "yolov7e6": the build_engine_* function (yolov7/src/model.cpp)
-    int input_h = 640, input_w = 640;   // kInputH / kInputW (ReOrg slices to input_h / 2, input_w / 2)
-    int num_class = 80;                 // kNumClass
-    int max_batch = 1;                  // kBatchSize
-    int max_out_bbox = 1000;            // kMaxNumOutputBbox
-    bool fp16 = true;                   // USE_FP16
-    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes), gh, gw) as "head0..N-1"
 };
 // the five names the builder accepts (yolov7d6 and yolov7e6e are not built), and which of them have four levels (strides 8 .. 64)
 bool yolov7_model_valid(const std::string& name);
@@ -159,14 +136,8 @@ nvinfer1::IHostMemory* buildEngineYolov7(nvinfer1::IBuilder* builder, nvinfer1::
 
 // yolov10/include/config.h constants as run-time configuration.  Explicit batch like the reference (model.cpp:38-44): a plan serves exactly
 // max_batch images per enqueue.  Detection, which is all the reference's yolov10 builds.
-struct Yolov10Config {
+struct Yolov10Config : YoloConfig {
     std::string model = "yolov10n";     // "yolov10n" / "s" / "m" / "b" / "l" / "x": gd, gw, max_channels (yolov10_det.cpp:111-141) and the stage table
-    int input_h = 640, input_w = 640;   // kInputH / kInputW, multiples of 32
-    int num_class = 80;                 // kNumClass
-    int max_batch = 1;                  // kBatchSize (Dims4{kBatchSize, 3, kInputH, kInputW})
-    int max_out_bbox = 1000;            // kMaxNumOutputBbox
-    bool fp16 = true;                   // USE_FP16
-    bool mark_heads = false;            // debugging: also expose the three plugin inputs (B, 4 + classes, grid) as outputs "head0..2"
 };
 // the six names the builder accepts
 bool yolov10_model_valid(const std::string& name);
@@ -179,13 +150,9 @@ nvinfer1::IHostMemory* buildEngineYolov10(nvinfer1::IBuilder* builder, nvinfer1:
 // yolov3/yololayer.h, yolov3-tiny/yololayer.h and yolov4/yololayer.h constants (INPUT_H / INPUT_W 608, CLASS_NUM 80) as run-time configuration.
 // Implicit batch like the reference (createNetworkV2(0U), Dims3{3, H, W}, setMaxBatchSize).  MAX_OUTPUT_BBOX_COUNT (1000) and the anchors are
 // compiled into the reference's plugin and stay what they are there.
-struct DarknetConfig {
+struct DarknetConfig : YoloConfig {
+    DarknetConfig() { input_h = input_w = 608; }   // INPUT_H / INPUT_W: multiples of 32, not necessarily equal.  max_out_bbox is not read.
     std::string model = "yolov4";       // "yolov3" / "yolov3-tiny" / "yolov4": the createEngine of that directory
-    int input_h = 608, input_w = 608;   // INPUT_H / INPUT_W: multiples of 32, not necessarily equal
-    int num_class = 80;                 // CLASS_NUM
-    int max_batch = 1;                  // BATCH_SIZE
-    bool fp16 = true;                   // USE_FP16
-    bool mark_heads = false;            // debugging: also expose the detect convolutions' outputs (3 * (5 + classes), gh, gw) as "head0..N-1", in the plugin's input order
 };
 bool darknet_model_valid(const std::string& name);
 // the model's module table as JSON rows [module, kind, channels, k, s, p, [from ...]] (host/darknet.cpp); "" for another name

@@ -5,7 +5,7 @@
 // the (proposals, C, 14, 14) tensor -> HW mean -> two FullyConnected -> softmax / slice -> PredictorDecode -> BatchedNms.
 // The Mask head (MASK_ON, rcnn.cpp:202-232; off by default in the reference) is built when RcnnConfig::mask_on is set.
 // The reference's file-scope constants (rcnn.cpp:16-60) are the fields of RcnnConfig.
-#include "common.h"
+#include "build.h"
 #include "models.h"
 #include "plugins/rcnn_plugins.h"
 
@@ -22,11 +22,6 @@ REGISTER_TENSORRT_PLUGIN(MaskRcnnInferencePluginCreator);
 
 namespace trtx_host {
 namespace {
-
-struct Ctx {
-    INetworkDefinition* net;
-    WeightMap& wm;
-};
 
 // conv with bias (+ReLU): every convolution of the fused-BN detectron2 export has the same shape of code
 ITensor* conv(Ctx& c, ITensor& in, int out, int k, int stride, int pad, const std::string& name, bool withRelu) {
@@ -72,9 +67,10 @@ std::vector<float> generateAnchors(const std::vector<float>& sizes, const std::v
 }  // namespace
 
 IHostMemory* buildRcnnR50C4(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const RcnnConfig& cfg) {
-    INetworkDefinition* network = builder->createNetworkV2(0U);
-    WeightMap wm = loadWeights(wts);
-    Ctx c{network, wm};
+    Session s(builder, wts);
+    Ctx& c = s.c;
+    WeightMap& wm = s.wm;
+    INetworkDefinition* network = s.net;
 
     // preprocess (rcnn.cpp:79-99)
     ITensor* data = network->addInput("images", DataType::kFLOAT, Dims3{cfg.input_h, cfg.input_w, 3});
@@ -185,13 +181,7 @@ IHostMemory* buildRcnnR50C4(IBuilder* builder, IBuilderConfig* config, const std
         network->markOutput(*proposals);
     }
 
-    builder->setMaxBatchSize(cfg.max_batch);
-    config->setMaxWorkspaceSize(1ULL << 30);
-    if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-    IHostMemory* plan = builder->buildSerializedNetwork(*network, *config);
-    delete network;
-    freeWeights(wm);
-    return plan;
+    return s.finish(builder, config, cfg.max_batch, cfg.fp16, 1ULL << 30);
 }
 
 }  // namespace trtx_host

@@ -1,7 +1,7 @@
 // ResNet-50 classifier (BASELINE config 2).  Mirrors the reference builder (resnet/resnet50.cpp:111-229):
 // 7x7/2 stem + BN + ReLU + maxpool3/2, bottleneck stages [3,4,6,3] with the stride on the 3x3 conv,
 // BN folded into IScaleLayers with eps 1e-5, average pool 7x7 and FC-1000.  Implicit batch.
-#include "common.h"
+#include "build.h"
 #include "models.h"
 
 using namespace nvinfer1;
@@ -34,10 +34,10 @@ ITensor* bottleneck(INetworkDefinition* net, WeightMap& wm, ITensor& in, int inc
 }  // namespace
 
 IHostMemory* buildResnet50(IBuilder* builder, IBuilderConfig* config, const std::string& wts, int maxBatch, bool fp16, int H, int W) {
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    ITensor* x = net->addInput("data", DataType::kFLOAT, Dims3{3, H, W});
-    assert(x);
+    Session s(builder, wts);
+    WeightMap& wm = s.wm;
+    INetworkDefinition* net = s.net;
+    ITensor* x = s.input("data", H, W);
     x = convBn(net, wm, *x, 64, 7, 2, 3, "conv1", "bn1");
     x = net->addActivation(*x, ActivationType::kRELU)->getOutput(0);
     auto* pool = net->addPoolingNd(*x, PoolingType::kMAX, DimsHW{3, 3});
@@ -60,16 +60,8 @@ IHostMemory* buildResnet50(IBuilder* builder, IBuilderConfig* config, const std:
     avg->setStrideNd(DimsHW{1, 1});
     auto* fc = net->addFullyConnected(*avg->getOutput(0), 1000, need(wm, "fc.weight"), need(wm, "fc.bias"));
     assert(fc);
-    fc->getOutput(0)->setName("prob");
-    net->markOutput(*fc->getOutput(0));
-
-    builder->setMaxBatchSize(maxBatch);
-    config->setMaxWorkspaceSize(1 << 20);
-    if (fp16) config->setFlag(BuilderFlag::kFP16);
-    IHostMemory* plan = builder->buildSerializedNetwork(*net, *config);
-    delete net;
-    freeWeights(wm);
-    return plan;
+    s.output(fc->getOutput(0), "prob");
+    return s.finish(builder, config, maxBatch, fp16, 1 << 20);
 }
 
 }  // namespace trtx_host

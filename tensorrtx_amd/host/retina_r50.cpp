@@ -3,18 +3,13 @@
 // upsamples with a 2x2 stride-2 grouped deconvolution of ones (:157-176) -> three SSH context modules (:87-98)
 // -> bbox(8) / class(4) / landmark(20) 1x1 heads per level -> concat -> "Decode_TRT" plugin.
 // Input size is a run-time argument (the reference compiles 480x640 into decode.h:16-17).
-#include "common.h"
 #include "models.h"
+#include "yolo_blocks.h"
 
 using namespace nvinfer1;
 
 namespace trtx_host {
 namespace {
-
-struct Ctx {
-    INetworkDefinition* net;
-    WeightMap& wm;
-};
 
 ITensor* convBn(Ctx& c, ITensor& in, int out, int k, int s, int p, const std::string& conv, const std::string& bn) {
     auto* l = c.net->addConvolutionNd(in, out, DimsHW{k, k}, need(c.wm, conv + ".weight"), noWeights());
@@ -61,11 +56,11 @@ ITensor* upsampleOnes(Ctx& c, ITensor& in, const Weights& ones) {  // :157-166 n
 }  // namespace
 
 IHostMemory* buildRetinaFaceR50(IBuilder* builder, IBuilderConfig* config, const std::string& wts, int maxBatch, bool fp16, int H, int W) {
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    Ctx c{net, wm};
-    ITensor* x = net->addInput("data", DataType::kFLOAT, Dims3{3, H, W});
-    assert(x);
+    Session s(builder, wts);
+    Ctx& c = s.c;
+    WeightMap& wm = s.wm;
+    INetworkDefinition* net = s.net;
+    ITensor* x = s.input("data", H, W);
     x = relu(c, convBn(c, *x, 64, 7, 2, 3, "body.conv1", "body.bn1"));
     auto* pool = net->addPoolingNd(*x, PoolingType::kMAX, DimsHW{3, 3});
     pool->setStrideNd(DimsHW{2, 2});
@@ -110,23 +105,11 @@ IHostMemory* buildRetinaFaceR50(IBuilder* builder, IBuilderConfig* config, const
         ITensor* parts[] = {heads[0][l], heads[1][l], heads[2][l]};
         cats.push_back(net->addConcatenation(parts, 3)->getOutput(0));
     }
-    auto* creator = getPluginRegistry()->getPluginCreator("Decode_TRT", "1");
-    assert(creator && "Decode_TRT creator not registered");
     PluginFieldCollection pfc{};
-    IPluginV2* plugin = creator->createPlugin("decode", &pfc);
-    auto* dec = net->addPluginV2(cats.data(), 3, *plugin);
+    auto* dec = blocks::plugin_layer(c, "Decode_TRT", "decode", &pfc, cats);
     assert(dec);
-    plugin->destroy();
-    dec->getOutput(0)->setName("prob");
-    net->markOutput(*dec->getOutput(0));
-
-    builder->setMaxBatchSize(maxBatch);
-    config->setMaxWorkspaceSize(1 << 20);
-    if (fp16) config->setFlag(BuilderFlag::kFP16);
-    IHostMemory* plan = builder->buildSerializedNetwork(*net, *config);
-    delete net;
-    freeWeights(wm);
-    return plan;
+    s.output(dec->getOutput(0), "prob");
+    return s.finish(builder, config, maxBatch, fp16, 1 << 20);
 }
 
 }  // namespace trtx_host

@@ -1,14 +1,13 @@
 // YOLOv12 detection network through the network-definition API, explicit batch like the reference.
 // Mirrors the reference blocks and builder:
 //   convBnSiLU / bottleneck / DFL / addYoLoLayer / C3k / C3K2 / convBn / DWConv     yolov12/src/block.cpp:73-458 (yolo_blocks.h: the
-//                                                                                   bodies are YOLO11's)
+//                                                                                   bodies are YOLO11's, and so are the detect head and tail)
 //   A2C2f / ABlock / AAttn                                                         yolov12/src/block.cpp:459-625
 //   get_width / get_depth / calculateStrides / buildEngineYolo12Det                yolov12/src/model.cpp:9-302
 // Graph, weight keys ("model.<n>...") and layer order are those of the reference; where the reference is odd it is kept and said so.
 #include <cmath>
 #include <vector>
 
-#include "common.h"
 #include "models.h"
 #include "yolo_blocks.h"
 
@@ -76,8 +75,7 @@ ITensor* AAttn(Ctx& c, ITensor& in, int dim, int num_heads, int area, const std:
     reshape4->setReshapeDimensions(Dims4{B, H, W, C});
     ITensor* vImg = transpose(c, *reshape4->getOutput(0), Permutation{0, 3, 1, 2});
     ITensor* pe = convBn(c, *vImg, all_head_dim * 2, 7, 1, lname + ".pe", all_head_dim * 2, /*bias=*/true);
-    ITensor* sum = c.net->addElementWise(*pe, *oImg, ElementWiseOperation::kSUM)->getOutput(0);
-    return convBn(c, *sum, all_head_dim * 2, 1, 1, lname + ".proj");
+    return convBn(c, *sum(c, *pe, *oImg), all_head_dim * 2, 1, 1, lname + ".proj");
 }
 
 // ABlock (block.cpp:497-520): x + AAttn(x), then + mlp.  `dim` is half the channel count (A2C2f), so mlp.0 has
@@ -86,10 +84,10 @@ ITensor* ABlock(Ctx& c, ITensor& in, int dim, int num_heads, float mlp_ratio, in
     const int mlp_hidden_dim = (int)(dim * mlp_ratio);
     ITensor* attn = AAttn(c, in, dim, num_heads, area, lname + ".attn");
     if (!attn) return nullptr;
-    ITensor* sum = c.net->addElementWise(in, *attn, ElementWiseOperation::kSUM)->getOutput(0);
-    ITensor* mlp1 = convBnSiLU(c, *sum, mlp_hidden_dim * 2, 1, 1, lname + ".mlp.0");
+    ITensor* x = sum(c, in, *attn);
+    ITensor* mlp1 = convBnSiLU(c, *x, mlp_hidden_dim * 2, 1, 1, lname + ".mlp.0");
     ITensor* mlp2 = convBn(c, *mlp1, dim * 2, 1, 1, lname + ".mlp.1");
-    return c.net->addElementWise(*sum, *mlp2, ElementWiseOperation::kSUM)->getOutput(0);
+    return sum(c, *x, *mlp2);
 }
 
 // A2C2f (block.cpp:459-495).  The reference computes c = c2 * e with e = 0.25 where ultralytics has e = 0.5, and then uses 2c for cv1 and
@@ -109,7 +107,7 @@ ITensor* A2C2f(Ctx& c, ITensor& in, int c2, bool a2, int area, float mlp_ratio, 
             if (!y) return nullptr;
             if (i & 1) parts[1 + i / 2] = y;
         }
-        return convBnSiLU(c, *c.net->addConcatenation(parts, 3)->getOutput(0), c2, 1, 1, lname + ".cv2");
+        return convBnSiLU(c, *cat(c, {parts[0], parts[1], parts[2]}), c2, 1, 1, lname + ".cv2");
     }
     ITensor* y = C3k(c, *cv1, ch * 2, 2, shortcut, 0.5f, lname + ".m.0");
     return convBnSiLU(c, *cat2(c, cv1, y), c2, 1, 1, lname + ".cv2");
@@ -117,107 +115,46 @@ ITensor* A2C2f(Ctx& c, ITensor& in, int c2, bool a2, int area, float mlp_ratio, 
 
 }  // namespace
 
-bool yolo12_scale(char type, Yolo12Config* cfg) {  // yolo12_det.cpp:120-150
-    switch (type) {
-        case 'n': cfg->gd = 0.50f; cfg->gw = 0.25f; cfg->max_channels = 1024; break;
-        case 's': cfg->gd = 0.50f; cfg->gw = 0.50f; cfg->max_channels = 1024; break;
-        case 'm': cfg->gd = 0.50f; cfg->gw = 1.00f; cfg->max_channels = 512; break;
-        case 'l': cfg->gd = 1.00f; cfg->gw = 1.00f; cfg->max_channels = 512; break;
-        case 'x': cfg->gd = 1.00f; cfg->gw = 1.50f; cfg->max_channels = 512; break;
-        default: return false;
-    }
-    cfg->c3k = type == 'm' || type == 'l' || type == 'x';   // model.cpp:60-63
-    return true;
-}
-
 IHostMemory* buildEngineYolo12Det(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolo12Config& cfg) {
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(1U << static_cast<uint32_t>(NetworkDefinitionCreationFlag::kEXPLICIT_BATCH));
-    IHostMemory* plan = nullptr;
-    {
-        Ctx c{net, wm, {}};
-        const float gd = cfg.gd, gw = cfg.gw;
-        const int mc = cfg.max_channels, B = cfg.batch, nc = cfg.num_class;
-        const bool c3k = cfg.c3k;
-        auto W = [&](int x) { return get_width(x, gw, mc); };
+    Session s(builder, wts, cfg.batch);
+    Ctx& c = s.c;
+    const float gd = cfg.gd;
+    const int nc = cfg.num_class;
+    const bool c3k = cfg.c3k;
+    auto W = [&](int x) { return get_width(x, cfg.gw, cfg.max_channels); };
 
-        ITensor* data = net->addInput("images", DataType::kFLOAT, Dims4{B, 3, cfg.input_h, cfg.input_w});
-        assert(data);
-        // ---- backbone (model.cpp:52-88): A2C2f with area attention at stride 16 (area 4) and stride 32 (area 1)
-        ITensor* conv0 = convBnSiLU(c, *data, W(64), 3, 2, "model.0");
-        ITensor* conv1 = convBnSiLU(c, *conv0, W(128), 3, 2, "model.1");
-        ITensor* conv2 = C3K2(c, *conv1, W(256), get_depth(2, gd), c3k, true, 0.25f, "model.2");
-        ITensor* conv3 = convBnSiLU(c, *conv2, W(256), 3, 2, "model.3");
-        ITensor* conv4 = C3K2(c, *conv3, W(512), get_depth(2, gd), c3k, true, 0.25f, "model.4");
-        ITensor* conv5 = convBnSiLU(c, *conv4, W(512), 3, 2, "model.5");
-        ITensor* conv6 = A2C2f(c, *conv5, W(512), true, 4, 2.0f, 0.25f, true, "model.6");
-        ITensor* conv7 = conv6 ? convBnSiLU(c, *conv6, W(1024), 3, 2, "model.7") : nullptr;
-        ITensor* conv8 = conv7 ? A2C2f(c, *conv7, W(1024), true, 1, 2.0f, 0.25f, true, "model.8") : nullptr;
-        if (conv8) {
-            // ---- head (model.cpp:94-135): the A2C2f blocks here take the C3k branch (a2 = false)
-            ITensor* conv11 = A2C2f(c, *cat2(c, upsample2x(c, *conv8), conv6), W(512), false, 1, 2.0f, 0.25f, true, "model.11");
-            ITensor* conv14 = A2C2f(c, *cat2(c, upsample2x(c, *conv11), conv4), W(256), false, 1, 2.0f, 0.25f, true, "model.14");
-            ITensor* conv15 = convBnSiLU(c, *conv14, W(256), 3, 2, "model.15");
-            ITensor* conv17 = A2C2f(c, *cat2(c, conv15, conv11), W(512), false, 1, 2.0f, 0.25f, true, "model.17");
-            ITensor* conv18 = convBnSiLU(c, *conv17, W(512), 3, 2, "model.18");
-            ITensor* conv20 = C3K2(c, *cat2(c, conv18, conv8), W(1024), get_depth(2, gd), true, true, 0.5f, "model.20");
+    ITensor* data = s.input("images", cfg.input_h, cfg.input_w);
+    // ---- backbone (model.cpp:52-88): A2C2f with area attention at stride 16 (area 4) and stride 32 (area 1)
+    ITensor* conv0 = convBnSiLU(c, *data, W(64), 3, 2, "model.0");
+    ITensor* conv1 = convBnSiLU(c, *conv0, W(128), 3, 2, "model.1");
+    ITensor* conv2 = C3K2(c, *conv1, W(256), get_depth(2, gd), c3k, true, 0.25f, "model.2");
+    ITensor* conv3 = convBnSiLU(c, *conv2, W(256), 3, 2, "model.3");
+    ITensor* conv4 = C3K2(c, *conv3, W(512), get_depth(2, gd), c3k, true, 0.25f, "model.4");
+    ITensor* conv5 = convBnSiLU(c, *conv4, W(512), 3, 2, "model.5");
+    ITensor* conv6 = A2C2f(c, *conv5, W(512), true, 4, 2.0f, 0.25f, true, "model.6");
+    if (!conv6) return nullptr;   // the grid is not divisible by the area count
+    ITensor* conv7 = convBnSiLU(c, *conv6, W(1024), 3, 2, "model.7");
+    ITensor* conv8 = A2C2f(c, *conv7, W(1024), true, 1, 2.0f, 0.25f, true, "model.8");
+    if (!conv8) return nullptr;
+    // ---- head (model.cpp:94-135): the A2C2f blocks here take the C3k branch (a2 = false)
+    ITensor* conv11 = A2C2f(c, *cat2(c, upsample2x(c, *conv8), conv6), W(512), false, 1, 2.0f, 0.25f, true, "model.11");
+    ITensor* conv14 = A2C2f(c, *cat2(c, upsample2x(c, *conv11), conv4), W(256), false, 1, 2.0f, 0.25f, true, "model.14");
+    ITensor* conv15 = convBnSiLU(c, *conv14, W(256), 3, 2, "model.15");
+    ITensor* conv17 = A2C2f(c, *cat2(c, conv15, conv11), W(512), false, 1, 2.0f, 0.25f, true, "model.17");
+    ITensor* conv18 = convBnSiLU(c, *conv17, W(512), 3, 2, "model.18");
+    ITensor* conv20 = C3K2(c, *cat2(c, conv18, conv8), W(1024), get_depth(2, gd), true, true, 0.5f, "model.20");
 
-            // ---- detect head (model.cpp:141-229): per level a 64-channel box branch and a DWConv class branch
-            const int c2 = std::max(std::max(16, W(256) / 4), 16 * 4);
-            const int c3 = std::max(W(256), std::min(nc, 100));
-            ITensor* feats[3] = {conv14, conv17, conv20};
-            const int feat_w[3] = {W(256), W(512), W(1024)};
-            std::vector<ITensor*> cats;
-            for (int lv = 0; lv < 3; ++lv) {
-                const std::string s = "model.21.cv2." + std::to_string(lv), t = "model.21.cv3." + std::to_string(lv);
-                ITensor* b = convBnSiLU(c, *feats[lv], c2, 3, 1, s + ".0");
-                b = convBnSiLU(c, *b, c2, 3, 1, s + ".1");
-                auto* box = net->addConvolutionNd(*b, 64, DimsHW{1, 1}, need(wm, s + ".2.weight"), need(wm, s + ".2.bias"));
-                box->setStrideNd(DimsHW{1, 1});
-                box->setPaddingNd(DimsHW{0, 0});
-                ITensor* k = DWConv(c, *feats[lv], feat_w[lv], 3, 1, t + ".0.0");
-                k = convBnSiLU(c, *k, c3, 1, 1, t + ".0.1");
-                k = DWConv(c, *k, c3, 3, 1, t + ".1.0");
-                k = convBnSiLU(c, *k, c3, 1, 1, t + ".1.1");
-                auto* cls = net->addConvolutionNd(*k, nc, DimsHW{1, 1}, need(wm, t + ".2.weight"), need(wm, t + ".2.bias"));
-                cls->setStrideNd(DimsHW{1, 1});
-                cls->setPaddingNd(DimsHW{0, 0});
-                cats.push_back(cat2(c, box->getOutput(0), cls->getOutput(0)));
-            }
-            // ---- detect tail (model.cpp:235-290): strides from the backbone maps, flatten, split, DFL, re-join along axis 1
-            std::vector<int> strides;
-            for (ITensor* t : {conv3, conv5, conv7}) strides.push_back(cfg.input_h / (int)t->getDimensions().d[2]);
-            std::vector<ITensor*> dets;
-            for (int lv = 0; lv < 3; ++lv) {
-                const int grid = (cfg.input_h / strides[lv]) * (cfg.input_w / strides[lv]);
-                auto* flat = net->addShuffle(*cats[lv]);
-                flat->setReshapeDimensions(Dims3{B, 64 + nc, grid});
-                ITensor* boxPart = net->addSlice(*flat->getOutput(0), Dims3{0, 0, 0}, Dims3{B, 64, grid}, Dims3{1, 1, 1})->getOutput(0);
-                ITensor* clsPart = net->addSlice(*flat->getOutput(0), Dims3{0, 64, 0}, Dims3{B, nc, grid}, Dims3{1, 1, 1})->getOutput(0);
-                ITensor* v[] = {DFL(c, *boxPart, B, grid, "model.21.dfl.conv.weight"), clsPart};
-                auto* cat = net->addConcatenation(v, 2);
-                cat->setAxis(1);
-                dets.push_back(cat->getOutput(0));
-            }
-            if (cfg.mark_heads)
-                for (size_t i = 0; i < dets.size(); ++i) {
-                    dets[i]->setName(("head" + std::to_string(i)).c_str());
-                    net->markOutput(*dets[i]);
-                }
-            // model.cpp:292-294: detection only (is_seg, is_pose, is_obb all false; the keypoint fields are the config's constants)
-            IPluginV2Layer* yolo = addYoLoLayer(c, dets, strides, {nc, 17, 0, cfg.input_w, cfg.input_h, cfg.max_out_bbox, 0, 0, 0});
-            assert(yolo);
-            yolo->getOutput(0)->setName("output");
-            net->markOutput(*yolo->getOutput(0));
-
-            config->setMaxWorkspaceSize(16 * (1 << 20));
-            if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-            plan = builder->buildSerializedNetwork(*net, *config);
-        }
-    }
-    delete net;
-    freeWeights(wm);
-    return plan;
+    // ---- detect head (model.cpp:141-229) and tail (:235-290)
+    const DetectV8 h{"model.21.", "model.21.dfl.conv.weight", true, std::max(std::max(16, W(256) / 4), 16 * 4), std::max(W(256), std::min(nc, 100)),
+                     nc, cfg.batch, cfg.input_h, cfg.input_w};
+    const std::vector<int> strides = strides_from(cfg.input_h, {conv3, conv5, conv7});
+    const std::vector<ITensor*> dets = detect_v8(c, h, {conv14, conv17, conv20}, strides);
+    if (cfg.mark_heads) s.mark_heads(dets);
+    // model.cpp:292-294: detection only (is_seg, is_pose, is_obb all false; the keypoint fields are the config's constants)
+    IPluginV2Layer* yolo = addYoLoLayer(c, dets, strides, {nc, 17, 0, cfg.input_w, cfg.input_h, cfg.max_out_bbox, 0, 0, 0});
+    assert(yolo);
+    s.output(yolo->getOutput(0), "output");
+    return s.finish(builder, config, cfg.batch, cfg.fp16);
 }
 
 }  // namespace trtx_host

@@ -6,48 +6,26 @@
 // Graph, weight keys ("model.<n>...") and layer order are those of the reference.  Not built: P6 seg / cls (the reference has none),
 // the v1 - v5 era blocks (focus, bottleneckCSP, SPP), INT8.
 #include <cmath>
-#include <cstring>
 #include <vector>
 
-#include "common.h"
 #include "models.h"
 #include "yolo_blocks.h"
 
 using namespace nvinfer1;
 
 namespace trtx_host {
-using blocks::cat2;
-using blocks::Ctx;
-using blocks::silu;
+using namespace blocks;
 namespace {
 
 constexpr int kNumAnchor = 3;   // yolov5/src/config.h:35
 
-struct YoloKernel {   // yolov5/src/types.h:5-9, the element type of the plugin's "kernels" field
-    int width, height;
-    float anchors[kNumAnchor * 2];
-};
-
-int get_width(int x, float gw, int divisor = 8) { return int(ceil((x * gw) / divisor)) * divisor; }   // model.cpp:53-55: ceil to 8, no cap
-
-// model.cpp:57-64.  The reference rounds half away from zero and then takes one off when the fraction is exactly 0.5 and the integer
-// part is even: round-half-to-even, Python's round() that the yaml depths went through.  Kept as written (blocks::get_depth is the same body).
-int get_depth(int x, float gd) { return blocks::get_depth(x, gd); }
-
-// Conv (no bias, padding k / 3: 6 -> 2, 3 -> 1, 1 -> 0) + BN (eps 1e-3) + SiLU spelled sigmoid x product   (model.cpp:99-116)
-ITensor* convBlock(Ctx& c, ITensor& in, int ch, int k, int s, const std::string& lname) {
-    auto* conv = c.net->addConvolutionNd(in, ch, DimsHW{k, k}, need(c.wm, lname + ".conv.weight"), noWeights());
-    assert(conv);
-    conv->setStrideNd(DimsHW{s, s});
-    conv->setPaddingNd(DimsHW{k / 3, k / 3});
-    return silu(c, addBatchNorm2d(c.net, c.wm, *conv->getOutput(0), lname + ".bn", 1e-3f)->getOutput(0));
-}
+// Conv (no bias, padding k / 3: 6 -> 2, 3 -> 1, 1 -> 0) + BN (eps 1e-3) + SiLU   (model.cpp:99-116)
+ITensor* convBlock(Ctx& c, ITensor& in, int ch, int k, int s, const std::string& lname) { return silu(c, conv_p(c, in, ch, k, s, k / 3, lname)); }
 
 ITensor* bottleneck13(Ctx& c, ITensor& in, int c1, int c2, bool shortcut, float e, const std::string& lname) {  // model.cpp:129-137: 1x1 then 3x3 (blocks::bottleneck is 3x3, 3x3)
     ITensor* a = convBlock(c, in, (int)((float)c2 * e), 1, 1, lname + ".cv1");
     ITensor* b = convBlock(c, *a, c2, 3, 1, lname + ".cv2");
-    if (shortcut && c1 == c2) return c.net->addElementWise(in, *b, ElementWiseOperation::kSUM)->getOutput(0);
-    return b;
+    return shortcut && c1 == c2 ? sum(c, in, *b) : b;
 }
 
 ITensor* C3(Ctx& c, ITensor& in, int c2, int n, bool shortcut, const std::string& lname) {  // model.cpp:162-177, e = 0.5
@@ -56,17 +34,6 @@ ITensor* C3(Ctx& c, ITensor& in, int c2, int n, bool shortcut, const std::string
     ITensor* b = convBlock(c, in, c_, 1, 1, lname + ".cv2");
     for (int i = 0; i < n; ++i) y = bottleneck13(c, *y, c_, c_, shortcut, 1.0f, lname + ".m." + std::to_string(i));
     return convBlock(c, *cat2(c, y, b), c2, 1, 1, lname + ".cv3");
-}
-
-ITensor* SPPF(Ctx& c, ITensor& in, int c1, int c2, int k, const std::string& lname) {  // model.cpp:200-217: three chained pools, 4-way concat
-    std::vector<ITensor*> parts{convBlock(c, in, c1 / 2, 1, 1, lname + ".cv1")};
-    for (int i = 0; i < 3; ++i) {
-        auto* pool = c.net->addPoolingNd(*parts.back(), PoolingType::kMAX, DimsHW{k, k});
-        pool->setPaddingNd(DimsHW{k / 2, k / 2});
-        pool->setStrideNd(DimsHW{1, 1});
-        parts.push_back(pool->getOutput(0));
-    }
-    return convBlock(c, *c.net->addConcatenation(parts.data(), 4)->getOutput(0), c2, 1, 1, lname + ".cv2");
 }
 
 // nearest upsample to the lateral tensor's dimensions, joined with it (model.cpp:310-316)
@@ -85,35 +52,15 @@ ITensor* detect(Ctx& c, ITensor& in, int info, const std::string& lname) {
     return det->getOutput(0);
 }
 
-// model.cpp:234-284: the anchors are <detect>.anchor_grid, six floats per level, the strides <detect>.strides (floats, truncated);
-// "netinfo" carries five ints under the field type kFLOAT32 and "kernels" is counted in YoloKernel elements, as the reference does.
-// The registry's YoloLayer_TRT / 1 creator resolves this field set to the anchor plugin.  Null when the weight map does not describe
-// one level per detect convolution.
+// model.cpp:234-284: the strides are <detect>.strides (floats, truncated), "netinfo" five ints, [4] is_segmentation.  The registry's
+// YoloLayer_TRT / 1 creator resolves this field set to the anchor plugin.  Null when the weight map does not describe one level per
+// detect convolution.
 IPluginV2Layer* addYoLoLayer(Ctx& c, const std::string& lname, const std::vector<ITensor*>& dets, const Yolov5Config& cfg) {
-    auto* creator = getPluginRegistry()->getPluginCreator("YoloLayer_TRT", "1");
-    assert(creator && "YoloLayer_TRT creator not registered");
-    const Weights& ag = need(c.wm, lname + ".anchor_grid");
     const Weights& st = need(c.wm, lname + ".strides");
-    const size_t levels = (size_t)ag.count / (kNumAnchor * 2);
-    if (levels != dets.size() || (size_t)st.count < levels) return nullptr;
-    int netinfo[5] = {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox, cfg.task == 1};   // [4]: is_segmentation
-    std::vector<YoloKernel> kernels(levels);
-    for (size_t i = 0; i < levels; ++i) {
-        const int scale = (int)static_cast<const float*>(st.values)[i];
-        if (scale < 1) return nullptr;
-        kernels[i].width = cfg.input_w / scale;
-        kernels[i].height = cfg.input_h / scale;
-        memcpy(kernels[i].anchors, static_cast<const float*>(ag.values) + i * kNumAnchor * 2, sizeof(kernels[i].anchors));
-    }
-    PluginField fields[2] = {PluginField("netinfo", netinfo, PluginFieldType::kFLOAT32, 5),
-                             PluginField("kernels", kernels.data(), PluginFieldType::kFLOAT32, (int32_t)kernels.size())};
-    PluginFieldCollection fc{2, fields};
-    IPluginV2* plugin = creator->createPlugin("yololayer", &fc);
-    if (!plugin) return nullptr;
-    std::vector<ITensor*> ins(dets);
-    auto* layer = c.net->addPluginV2(ins.data(), (int32_t)ins.size(), *plugin);
-    plugin->destroy();  // the network holds its own clone
-    return layer;
+    if ((size_t)st.count < dets.size()) return nullptr;
+    std::vector<int> scales;
+    for (size_t i = 0; i < dets.size(); ++i) scales.push_back((int)static_cast<const float*>(st.values)[i]);
+    return addAnchorYoLoLayer(c, lname, dets, {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox, cfg.task == 1}, scales);
 }
 
 // Proto (model.cpp:219-232): 3x3 convBlock, nearest resize by the scales {1, 2, 2}, 3x3 convBlock, 1x1 convBlock to c2 channels
@@ -128,43 +75,36 @@ ITensor* Proto(Ctx& c, ITensor& in, int c_, int c2, const std::string& lname) {
     return convBlock(c, *cv2, c2, 1, 1, lname + ".cv3");
 }
 
+// the part of the backbone every model shares (model.cpp:295-302, 385-391, 488-496): the 6x6 stride-2 stem with padding 2, then C3
+// stages to model.6; c4 and c6 are the laterals
+ITensor* backbone(Ctx& c, ITensor* data, const Yolov5Config& cfg, ITensor** c4, ITensor** c6) {
+    auto W = [&](int x) { return get_width_v5(x, cfg.gw); };
+    auto D = [&](int x) { return get_depth(x, cfg.gd); };
+    ITensor* x = convBlock(c, *data, W(64), 6, 2, "model.0");
+    x = convBlock(c, *x, W(128), 3, 2, "model.1");
+    x = C3(c, *x, W(128), D(3), true, "model.2");
+    x = convBlock(c, *x, W(256), 3, 2, "model.3");
+    *c4 = C3(c, *x, W(256), D(6), true, "model.4");
+    x = convBlock(c, **c4, W(512), 3, 2, "model.5");
+    return *c6 = C3(c, *x, W(512), D(9), true, "model.6");
+}
+
 // build_cls_engine (model.cpp:479-537): the backbone to model.8, convBlock to 1280 channels, average pool over the whole map, fully
 // connected layer.  The reference pools DimsHW{k, k} with k = kClsInputH / 32, the square case of (h / 32, w / 32).
 IHostMemory* buildCls(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov5Config& cfg) {
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    IHostMemory* plan = nullptr;
-    {
-        Ctx c{net, wm, {}};
-        auto W = [&](int x) { return get_width(x, cfg.gw); };
-        auto D = [&](int x) { return get_depth(x, cfg.gd); };
-        ITensor* data = net->addInput("data", DataType::kFLOAT, Dims3{3, cfg.input_h, cfg.input_w});
-        assert(data);
-        ITensor* x = convBlock(c, *data, W(64), 6, 2, "model.0");
-        x = convBlock(c, *x, W(128), 3, 2, "model.1");
-        x = C3(c, *x, W(128), D(3), true, "model.2");
-        x = convBlock(c, *x, W(256), 3, 2, "model.3");
-        x = C3(c, *x, W(256), D(6), true, "model.4");
-        x = convBlock(c, *x, W(512), 3, 2, "model.5");
-        x = C3(c, *x, W(512), D(9), true, "model.6");
-        x = convBlock(c, *x, W(1024), 3, 2, "model.7");
-        x = C3(c, *x, W(1024), D(3), true, "model.8");
-        ITensor* conv_class = convBlock(c, *x, 1280, 1, 1, "model.9.conv");
-        auto* pool = net->addPoolingNd(*conv_class, PoolingType::kAVERAGE, DimsHW{cfg.input_h / 32, cfg.input_w / 32});
-        assert(pool);
-        auto* fc = net->addFullyConnected(*pool->getOutput(0), cfg.num_class, need(wm, "model.9.linear.weight"), need(wm, "model.9.linear.bias"));
-        assert(fc);
-        fc->getOutput(0)->setName("prob");
-        net->markOutput(*fc->getOutput(0));
-
-        builder->setMaxBatchSize(cfg.max_batch);
-        config->setMaxWorkspaceSize(16 * (1 << 20));
-        if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-        plan = builder->buildSerializedNetwork(*net, *config);
-    }
-    delete net;
-    freeWeights(wm);
-    return plan;
+    Session s(builder, wts);
+    Ctx& c = s.c;
+    ITensor *c4, *c6;
+    ITensor* x = backbone(c, s.input("data", cfg.input_h, cfg.input_w), cfg, &c4, &c6);
+    x = convBlock(c, *c6, get_width_v5(1024, cfg.gw), 3, 2, "model.7");
+    x = C3(c, *x, get_width_v5(1024, cfg.gw), get_depth(3, cfg.gd), true, "model.8");
+    ITensor* conv_class = convBlock(c, *x, 1280, 1, 1, "model.9.conv");
+    auto* pool = s.net->addPoolingNd(*conv_class, PoolingType::kAVERAGE, DimsHW{cfg.input_h / 32, cfg.input_w / 32});
+    assert(pool);
+    auto* fc = s.net->addFullyConnected(*pool->getOutput(0), cfg.num_class, need(s.wm, "model.9.linear.weight"), need(s.wm, "model.9.linear.bias"));
+    assert(fc);
+    s.output(fc->getOutput(0), "prob");
+    return s.finish(builder, config, cfg.max_batch, cfg.fp16);
 }
 
 }  // namespace
@@ -184,94 +124,65 @@ bool yolov5_scale(char type, Yolov5Config* cfg) {  // yolov5_det.cpp:22-41
 IHostMemory* buildEngineYolov5(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov5Config& cfg) {
     if (!yolov5_task_valid(cfg.task, cfg.p6)) return nullptr;
     if (cfg.task == 4) return buildCls(builder, config, wts, cfg);
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    IHostMemory* plan = nullptr;
-    {
-        Ctx c{net, wm, {}};
-        const float gd = cfg.gd;
-        const int nc = cfg.num_class + 5 + (cfg.task == 1 ? 32 : 0);   // values per anchor of a detect convolution
-        auto W = [&](int x) { return get_width(x, cfg.gw); };
-        auto D = [&](int x) { return get_depth(x, gd); };
+    Session s(builder, wts);
+    Ctx& c = s.c;
+    const int nc = cfg.num_class + 5 + (cfg.task == 1 ? 32 : 0);   // values per anchor of a detect convolution
+    auto W = [&](int x) { return get_width_v5(x, cfg.gw); };
+    auto D = [&](int x) { return get_depth(x, cfg.gd); };
 
-        ITensor* data = net->addInput("data", DataType::kFLOAT, Dims3{3, cfg.input_h, cfg.input_w});
-        assert(data);
-        std::vector<ITensor*> dets;
-        std::string detect_name;
-        ITensor* proto_in = nullptr;   // seg: Proto reads model.17's output
-        // ---- backbone, the part P5 and P6 share (model.cpp:295-302, 385-391): the 6x6 stride-2 stem with padding 2, then C3 stages
-        ITensor* x = convBlock(c, *data, W(64), 6, 2, "model.0");
-        x = convBlock(c, *x, W(128), 3, 2, "model.1");
-        x = C3(c, *x, W(128), D(3), true, "model.2");
-        x = convBlock(c, *x, W(256), 3, 2, "model.3");
-        ITensor* c4 = C3(c, *x, W(256), D(6), true, "model.4");
-        x = convBlock(c, *c4, W(512), 3, 2, "model.5");
-        ITensor* c6 = C3(c, *x, W(512), D(9), true, "model.6");
-        if (!cfg.p6) {
-            x = convBlock(c, *c6, W(1024), 3, 2, "model.7");
-            x = C3(c, *x, W(1024), D(3), true, "model.8");
-            x = trtx_host::SPPF(c, *x, W(1024), W(1024), 5, "model.9");   // this file's (qualified: blocks::SPPF is found through Ctx)
-            // ---- head (model.cpp:308-341): the detect convolutions sit where the reference adds them
-            ITensor* c10 = convBlock(c, *x, W(512), 1, 1, "model.10");
-            ITensor* c13 = C3(c, *upcat(c, *c10, c6), W(512), D(3), false, "model.13");
-            ITensor* c14 = convBlock(c, *c13, W(256), 1, 1, "model.14");
-            ITensor* c17 = C3(c, *upcat(c, *c14, c4), W(256), D(3), false, "model.17");
-            dets.push_back(detect(c, *c17, nc, "model.24.m.0"));
-            proto_in = c17;
-            ITensor* c18 = convBlock(c, *c17, W(256), 3, 2, "model.18");
-            ITensor* c20 = C3(c, *cat2(c, c18, c14), W(512), D(3), false, "model.20");
-            dets.push_back(detect(c, *c20, nc, "model.24.m.1"));
-            ITensor* c21 = convBlock(c, *c20, W(512), 3, 2, "model.21");
-            ITensor* c23 = C3(c, *cat2(c, c21, c10), W(1024), D(3), false, "model.23");
-            dets.push_back(detect(c, *c23, nc, "model.24.m.2"));
-            detect_name = "model.24";
-        } else {
-            // ---- P6 backbone tail and head (model.cpp:392-445): four levels, strides 8 .. 64
-            x = convBlock(c, *c6, W(768), 3, 2, "model.7");
-            ITensor* c8 = C3(c, *x, W(768), D(3), true, "model.8");
-            x = convBlock(c, *c8, W(1024), 3, 2, "model.9");
-            x = C3(c, *x, W(1024), D(3), true, "model.10");
-            x = trtx_host::SPPF(c, *x, W(1024), W(1024), 5, "model.11");   // this file's (qualified: blocks::SPPF is found through Ctx)
-            ITensor* c12 = convBlock(c, *x, W(768), 1, 1, "model.12");
-            ITensor* c15 = C3(c, *upcat(c, *c12, c8), W(768), D(3), false, "model.15");
-            ITensor* c16 = convBlock(c, *c15, W(512), 1, 1, "model.16");
-            ITensor* c19 = C3(c, *upcat(c, *c16, c6), W(512), D(3), false, "model.19");
-            ITensor* c20 = convBlock(c, *c19, W(256), 1, 1, "model.20");
-            ITensor* c23 = C3(c, *upcat(c, *c20, c4), W(256), D(3), false, "model.23");
-            ITensor* c24 = convBlock(c, *c23, W(256), 3, 2, "model.24");
-            ITensor* c26 = C3(c, *cat2(c, c24, c20), W(512), D(3), false, "model.26");
-            ITensor* c27 = convBlock(c, *c26, W(512), 3, 2, "model.27");
-            ITensor* c29 = C3(c, *cat2(c, c27, c16), W(768), D(3), false, "model.29");
-            ITensor* c30 = convBlock(c, *c29, W(768), 3, 2, "model.30");
-            ITensor* c32 = C3(c, *cat2(c, c30, c12), W(1024), D(3), false, "model.32");
-            ITensor* feats[4] = {c23, c26, c29, c32};
-            for (int lv = 0; lv < 4; ++lv) dets.push_back(detect(c, *feats[lv], nc, "model.33.m." + std::to_string(lv)));
-            detect_name = "model.33";
-        }
-        if (cfg.mark_heads)
-            for (size_t i = 0; i < dets.size(); ++i) {
-                dets[i]->setName(("head" + std::to_string(i)).c_str());
-                net->markOutput(*dets[i]);
-            }
-        IPluginV2Layer* yolo = addYoLoLayer(c, detect_name, dets, cfg);
-        if (yolo) {
-            yolo->getOutput(0)->setName("prob");
-            net->markOutput(*yolo->getOutput(0));
-            if (cfg.task == 1) {   // model.cpp:598-600: after the plugin, so the bindings are data, prob, proto
-                ITensor* proto = Proto(c, *proto_in, W(256), 32, detect_name + ".proto");
-                proto->setName("proto");
-                net->markOutput(*proto);
-            }
-
-            builder->setMaxBatchSize(cfg.max_batch);
-            config->setMaxWorkspaceSize(16 * (1 << 20));
-            if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-            plan = builder->buildSerializedNetwork(*net, *config);
-        }
+    std::vector<ITensor*> dets;
+    std::string detect_name;
+    ITensor* proto_in = nullptr;   // seg: Proto reads model.17's output
+    ITensor *c4, *c6;
+    ITensor* x = backbone(c, s.input("data", cfg.input_h, cfg.input_w), cfg, &c4, &c6);
+    if (!cfg.p6) {
+        x = convBlock(c, *c6, W(1024), 3, 2, "model.7");
+        x = C3(c, *x, W(1024), D(3), true, "model.8");
+        x = SPPF(c, *x, W(1024), W(1024), 5, "model.9");
+        // ---- head (model.cpp:308-341): the detect convolutions sit where the reference adds them
+        ITensor* c10 = convBlock(c, *x, W(512), 1, 1, "model.10");
+        ITensor* c13 = C3(c, *upcat(c, *c10, c6), W(512), D(3), false, "model.13");
+        ITensor* c14 = convBlock(c, *c13, W(256), 1, 1, "model.14");
+        ITensor* c17 = C3(c, *upcat(c, *c14, c4), W(256), D(3), false, "model.17");
+        dets.push_back(detect(c, *c17, nc, "model.24.m.0"));
+        proto_in = c17;
+        ITensor* c18 = convBlock(c, *c17, W(256), 3, 2, "model.18");
+        ITensor* c20 = C3(c, *cat2(c, c18, c14), W(512), D(3), false, "model.20");
+        dets.push_back(detect(c, *c20, nc, "model.24.m.1"));
+        ITensor* c21 = convBlock(c, *c20, W(512), 3, 2, "model.21");
+        ITensor* c23 = C3(c, *cat2(c, c21, c10), W(1024), D(3), false, "model.23");
+        dets.push_back(detect(c, *c23, nc, "model.24.m.2"));
+        detect_name = "model.24";
+    } else {
+        // ---- P6 backbone tail and head (model.cpp:392-445): four levels, strides 8 .. 64
+        x = convBlock(c, *c6, W(768), 3, 2, "model.7");
+        ITensor* c8 = C3(c, *x, W(768), D(3), true, "model.8");
+        x = convBlock(c, *c8, W(1024), 3, 2, "model.9");
+        x = C3(c, *x, W(1024), D(3), true, "model.10");
+        x = SPPF(c, *x, W(1024), W(1024), 5, "model.11");
+        ITensor* c12 = convBlock(c, *x, W(768), 1, 1, "model.12");
+        ITensor* c15 = C3(c, *upcat(c, *c12, c8), W(768), D(3), false, "model.15");
+        ITensor* c16 = convBlock(c, *c15, W(512), 1, 1, "model.16");
+        ITensor* c19 = C3(c, *upcat(c, *c16, c6), W(512), D(3), false, "model.19");
+        ITensor* c20 = convBlock(c, *c19, W(256), 1, 1, "model.20");
+        ITensor* c23 = C3(c, *upcat(c, *c20, c4), W(256), D(3), false, "model.23");
+        ITensor* c24 = convBlock(c, *c23, W(256), 3, 2, "model.24");
+        ITensor* c26 = C3(c, *cat2(c, c24, c20), W(512), D(3), false, "model.26");
+        ITensor* c27 = convBlock(c, *c26, W(512), 3, 2, "model.27");
+        ITensor* c29 = C3(c, *cat2(c, c27, c16), W(768), D(3), false, "model.29");
+        ITensor* c30 = convBlock(c, *c29, W(768), 3, 2, "model.30");
+        ITensor* c32 = C3(c, *cat2(c, c30, c12), W(1024), D(3), false, "model.32");
+        ITensor* feats[4] = {c23, c26, c29, c32};
+        for (int lv = 0; lv < 4; ++lv) dets.push_back(detect(c, *feats[lv], nc, "model.33.m." + std::to_string(lv)));
+        detect_name = "model.33";
     }
-    delete net;
-    freeWeights(wm);
-    return plan;
+    if (cfg.mark_heads) s.mark_heads(dets);
+    IPluginV2Layer* yolo = addYoLoLayer(c, detect_name, dets, cfg);
+    if (!yolo) return nullptr;
+    s.output(yolo->getOutput(0), "prob");
+    // model.cpp:598-600: after the plugin, so the bindings are data, prob, proto
+    if (cfg.task == 1) s.output(Proto(c, *proto_in, W(256), 32, detect_name + ".proto"), "proto");
+    return s.finish(builder, config, cfg.max_batch, cfg.fp16);
 }
 
 }  // namespace trtx_host

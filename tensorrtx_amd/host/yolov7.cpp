@@ -11,26 +11,16 @@
 // convolutions: like the reference, the builder does not read the implicit `ia` / `im` tensors of the checkpoint (a checkpoint must
 // have them fused in, as the reference's gen_wts does for the deploy model).  Not built: yolov7d6, yolov7e6e, INT8.
 #include <cmath>
-#include <cstring>
 #include <vector>
 
-#include "common.h"
 #include "models.h"
 #include "yolo_blocks.h"
 
 using namespace nvinfer1;
 
 namespace trtx_host {
-using blocks::Ctx;
-using blocks::silu;
+using namespace blocks;
 namespace {
-
-constexpr int kNumAnchor = 3;   // yolov7/include/config.h:28
-
-struct YoloKernel {   // yolov7/include/types.h, the element type of the plugin's "kernels" field
-    int width, height;
-    float anchors[kNumAnchor * 2];
-};
 
 // One model under construction: y[i] is the output of yaml row i.
 struct Rows {
@@ -50,27 +40,13 @@ struct Rows {
         return (int)y.size() - 1;
     }
 
-    // block.cpp:85-104 / 192-206; the builders pass padding 1 with k = 3 and 0 with k = 1
+    // block.cpp:85-104 / 192-206; the builders pass padding 1 with k = 3 and 0 with k = 1.  The convolution layer is named <lname>.conv
     ITensor* convAct(ITensor& in, int ch, int k, int s, const std::string& lname) {
-        auto* conv = c.net->addConvolutionNd(in, ch, DimsHW{k, k}, need(c.wm, lname + ".conv.weight"), noWeights());
-        assert(conv);
-        conv->setName((lname + ".conv").c_str());
-        conv->setStrideNd(DimsHW{s, s});
-        conv->setPaddingNd(DimsHW{k / 2, k / 2});
-        ITensor* bn = addBatchNorm2d(c.net, c.wm, *conv->getOutput(0), lname + ".bn", leaky ? 1e-5f : 1e-3f)->getOutput(0);
-        if (!leaky) return silu(c, bn);
-        auto* act = c.net->addActivation(*bn, ActivationType::kLEAKY_RELU);
-        act->setAlpha(0.1f);
-        return act->getOutput(0);
+        ITensor* bn = conv_bn(c, in, ch, k, s, k / 2, lname + ".conv", lname + ".bn", 1, false, leaky ? 1e-5f : 1e-3f, /*named=*/true);
+        return leaky ? blocks::leaky(c, bn) : silu(c, bn);
     }
-    ITensor* maxpool(ITensor& in, int k, int s, int p) {
-        auto* m = c.net->addPoolingNd(in, PoolingType::kMAX, DimsHW{k, k});
-        assert(m);
-        m->setStrideNd(DimsHW{s, s});
-        m->setPaddingNd(DimsHW{p, p});
-        return m->getOutput(0);
-    }
-    ITensor* concat(const std::vector<ITensor*>& v) { return c.net->addConcatenation(v.data(), (int32_t)v.size())->getOutput(0); }
+    ITensor* maxpool(ITensor& in, int k, int s, int p) { return blocks::maxpool(c, in, k, s, p); }
+    ITensor* concat(const std::vector<ITensor*>& v) { return blocks::cat(c, v); }
 
     // ---- yaml rows
     int conv(int from, int ch, int k, int s) { return push(convAct(*at(from), ch, k, s, name())); }
@@ -80,14 +56,7 @@ struct Rows {
         for (int f : from) v.push_back(at(f));
         return push(concat(v));
     }
-    int up(int from) {   // nn.Upsample(None, 2, 'nearest')
-        auto* r = c.net->addResize(*at(from));
-        assert(r);
-        r->setResizeMode(ResizeMode::kNEAREST);
-        const float scale[] = {1.0f, 2.0f, 2.0f};
-        r->setScales(scale, 3);
-        return push(r->getOutput(0));
-    }
+    int up(int from) { return push(upsample2x(c, *at(from))); }   // nn.Upsample(None, 2, 'nearest')
     int reorg(int from) {   // block.cpp:106-114
         ITensor& in = *at(from);
         const int ch = in.getDimensions().d[0], h = cfg.input_h / 2, w = cfg.input_w / 2;
@@ -121,16 +90,9 @@ struct Rows {
     int repconv(int from, int c2) {   // block.cpp:168-190, k = 3, s = 1: 3x3 + BN and 1x1 + BN summed, then SiLU; no identity branch (c1 != c2)
         const std::string l = name();
         ITensor& in = *at(from);
-        auto* dense = c.net->addConvolutionNd(in, c2, DimsHW{3, 3}, need(c.wm, l + ".rbr_dense.0.weight"), noWeights());
-        assert(dense);
-        dense->setPaddingNd(DimsHW{1, 1});
-        dense->setName((l + ".rbr_dense.0").c_str());
-        ITensor* a = addBatchNorm2d(c.net, c.wm, *dense->getOutput(0), l + ".rbr_dense.1", 1e-3f)->getOutput(0);
-        auto* one = c.net->addConvolutionNd(in, c2, DimsHW{1, 1}, need(c.wm, l + ".rbr_1x1.0.weight"), noWeights());
-        assert(one);
-        one->setName((l + ".rbr_1x1.0").c_str());
-        ITensor* b = addBatchNorm2d(c.net, c.wm, *one->getOutput(0), l + ".rbr_1x1.1", 1e-3f)->getOutput(0);
-        return push(silu(c, c.net->addElementWise(*a, *b, ElementWiseOperation::kSUM)->getOutput(0)));
+        ITensor* a = conv_bn(c, in, c2, 3, 1, 1, l + ".rbr_dense.0", l + ".rbr_dense.1", 1, false, 1e-3f, /*named=*/true);
+        ITensor* b = conv_bn(c, in, c2, 1, 1, 0, l + ".rbr_1x1.0", l + ".rbr_1x1.1", 1, false, 1e-3f, /*named=*/true);
+        return push(silu(c, sum(c, *a, *b)));
     }
 
     // ---- the repeating groups of rows
@@ -160,33 +122,13 @@ struct Rows {
     }
 };
 
-// block.cpp:208-255: anchors from <detect>.anchor_grid, six floats per level; grids are the input over 8, 16, 32 (, 64); "netinfo" carries
-// FOUR ints under the field type kFLOAT32 and "kernels" is counted in YoloKernel elements, as the reference does.  The registry's
-// YoloLayer_TRT / 1 creator resolves this field set to the 6-float plugin.  Null when the weight map does not describe one level per
-// detect convolution.
+// block.cpp:208-255: grids are the input over 8, 16, 32 (, 64); "netinfo" carries FOUR ints.  The registry's YoloLayer_TRT / 1 creator
+// resolves this field set to the 6-float plugin.  Null when <detect>.anchor_grid does not describe exactly one level per detect convolution.
 IPluginV2Layer* addYoLoLayer(Ctx& c, const std::string& lname, const std::vector<ITensor*>& dets, const Yolov7Config& cfg) {
-    auto* creator = getPluginRegistry()->getPluginCreator("YoloLayer_TRT", "1");
-    assert(creator && "YoloLayer_TRT creator not registered");
-    const Weights& ag = need(c.wm, lname + ".anchor_grid");
-    const size_t levels = (size_t)ag.count / (kNumAnchor * 2);
-    if (levels != dets.size() || (size_t)ag.count != levels * kNumAnchor * 2) return nullptr;
-    int netinfo[4] = {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox};
-    std::vector<YoloKernel> kernels(levels);
-    int scale = 8;
-    for (size_t i = 0; i < levels; ++i, scale *= 2) {
-        kernels[i].width = cfg.input_w / scale;
-        kernels[i].height = cfg.input_h / scale;
-        memcpy(kernels[i].anchors, static_cast<const float*>(ag.values) + i * kNumAnchor * 2, sizeof(kernels[i].anchors));
-    }
-    PluginField fields[2] = {PluginField("netinfo", netinfo, PluginFieldType::kFLOAT32, 4),
-                             PluginField("kernels", kernels.data(), PluginFieldType::kFLOAT32, (int32_t)kernels.size())};
-    PluginFieldCollection fc{2, fields};
-    IPluginV2* plugin = creator->createPlugin("yololayer", &fc);
-    if (!plugin) return nullptr;
-    std::vector<ITensor*> ins(dets);
-    auto* layer = c.net->addPluginV2(ins.data(), (int32_t)ins.size(), *plugin);
-    plugin->destroy();  // the network holds its own clone
-    return layer;
+    if ((size_t)need(c.wm, lname + ".anchor_grid").count != dets.size() * 6) return nullptr;
+    std::vector<int> scales;
+    for (size_t i = 0; i < dets.size(); ++i) scales.push_back(8 << i);
+    return addAnchorYoLoLayer(c, lname, dets, {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox}, scales);
 }
 
 // Each function leaves the rows the detect layer reads in `feats`; the detect layer is the next row.
@@ -359,48 +301,29 @@ bool yolov7_model_p6(const std::string& name) { return name == "yolov7w6" || nam
 
 IHostMemory* buildEngineYolov7(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov7Config& cfg) {
     if (!yolov7_model_valid(cfg.model)) return nullptr;
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    IHostMemory* plan = nullptr;
-    {
-        Ctx c{net, wm, {}};
-        ITensor* data = net->addInput("data", DataType::kFLOAT, Dims3{3, cfg.input_h, cfg.input_w});
-        assert(data);
-        Rows r{c, cfg, cfg.model == "yolov7tiny", data, {}};
-        std::vector<int> feats;
-        if (cfg.model == "yolov7tiny") tiny(r, feats);
-        else if (cfg.model == "yolov7") v7(r, feats);
-        else if (cfg.model == "yolov7x") v7x(r, feats);
-        else if (cfg.model == "yolov7w6") w6(r, feats);
-        else e6(r, feats);
+    Session s(builder, wts);
+    Ctx& c = s.c;
+    Rows r{c, cfg, cfg.model == "yolov7tiny", s.input("data", cfg.input_h, cfg.input_w), {}};
+    std::vector<int> feats;
+    if (cfg.model == "yolov7tiny") tiny(r, feats);
+    else if (cfg.model == "yolov7") v7(r, feats);
+    else if (cfg.model == "yolov7x") v7x(r, feats);
+    else if (cfg.model == "yolov7w6") w6(r, feats);
+    else e6(r, feats);
 
-        const std::string detect = r.name();
-        const int info = kNumAnchor * (cfg.num_class + 5);
-        std::vector<ITensor*> dets;
-        for (size_t i = 0; i < feats.size(); ++i) {   // the biased 1x1 `m.i` convolutions
-            const std::string m = detect + ".m." + std::to_string(i);
-            auto* det = net->addConvolutionNd(*r.at(feats[i]), info, DimsHW{1, 1}, need(wm, m + ".weight"), need(wm, m + ".bias"));
-            assert(det);
-            dets.push_back(det->getOutput(0));
-        }
-        if (cfg.mark_heads)
-            for (size_t i = 0; i < dets.size(); ++i) {
-                dets[i]->setName(("head" + std::to_string(i)).c_str());
-                net->markOutput(*dets[i]);
-            }
-        IPluginV2Layer* yolo = addYoLoLayer(c, detect, dets, cfg);
-        if (yolo) {
-            yolo->getOutput(0)->setName("prob");
-            net->markOutput(*yolo->getOutput(0));
-            builder->setMaxBatchSize(cfg.max_batch);
-            config->setMaxWorkspaceSize(16 * (1 << 20));
-            if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-            plan = builder->buildSerializedNetwork(*net, *config);
-        }
+    const std::string detect = r.name();
+    std::vector<ITensor*> dets;
+    for (size_t i = 0; i < feats.size(); ++i) {   // the biased 1x1 `m.i` convolutions
+        const std::string m = detect + ".m." + std::to_string(i);
+        auto* det = s.net->addConvolutionNd(*r.at(feats[i]), 3 * (cfg.num_class + 5), DimsHW{1, 1}, need(s.wm, m + ".weight"), need(s.wm, m + ".bias"));
+        assert(det);
+        dets.push_back(det->getOutput(0));
     }
-    delete net;
-    freeWeights(wm);
-    return plan;
+    if (cfg.mark_heads) s.mark_heads(dets);
+    IPluginV2Layer* yolo = addYoLoLayer(c, detect, dets, cfg);
+    if (!yolo) return nullptr;
+    s.output(yolo->getOutput(0), "prob");
+    return s.finish(builder, config, cfg.max_batch, cfg.fp16);
 }
 
 }  // namespace trtx_host

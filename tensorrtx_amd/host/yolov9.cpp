@@ -18,46 +18,32 @@
 #include <numeric>
 #include <vector>
 
-#include "common.h"
 #include "models.h"
 #include "yolo_blocks.h"
 
 using namespace nvinfer1;
 
 namespace trtx_host {
-using blocks::Ctx;
-using blocks::silu;
+using namespace blocks;
 namespace {
 
-// Conv (no bias, padding p, groups g) + BN (eps 1e-3)   (block.cpp:129-142)
-ITensor* convBnNoAct(Ctx& c, ITensor& in, int ch, int k, int s, int p, const std::string& lname, int g = 1) {
-    auto* conv = c.net->addConvolutionNd(in, ch, DimsHW{k, k}, need(c.wm, lname + ".conv.weight"), noWeights());
-    assert(conv);
-    conv->setStrideNd(DimsHW{s, s});
-    conv->setPaddingNd(DimsHW{p, p});
-    conv->setNbGroups(g);
-    return addBatchNorm2d(c.net, c.wm, *conv->getOutput(0), lname + ".bn", 1e-3f)->getOutput(0);
-}
-
-// ... + SiLU spelled sigmoid x product   (block.cpp:111-128)
-ITensor* convBnSiLU(Ctx& c, ITensor& in, int ch, int k, int s, int p, const std::string& lname, int g = 1) {
-    return silu(c, convBnNoAct(c, in, ch, k, s, p, lname, g));
-}
+// Conv (no bias, padding p, groups g) + BN (eps 1e-3)   (block.cpp:129-142), and ... + SiLU (block.cpp:111-128)
+ITensor* convBnNoAct(Ctx& c, ITensor& in, int ch, int k, int s, int p, const std::string& lname, int g = 1) { return conv_p(c, in, ch, k, s, p, lname, g); }
+ITensor* convBnSiLU(Ctx& c, ITensor& in, int ch, int k, int s, int p, const std::string& lname, int g = 1) { return silu(c, conv_p(c, in, ch, k, s, p, lname, g)); }
 
 // RepConvN (block.cpp:156-170): 3x3 + BN and 1x1 + BN (padding p - k / 2 = 0) on the same input, summed, then SiLU.  The 1x1 is not
 // folded into the 3x3: the graph stays the reference's.
 ITensor* RepConvN(Ctx& c, ITensor& in, int c2, int s, int g, const std::string& lname) {
     ITensor* a = convBnNoAct(c, in, c2, 3, s, 1, lname + ".conv1", g);
     ITensor* b = convBnNoAct(c, in, c2, 1, s, 0, lname + ".conv2", g);
-    return silu(c, c.net->addElementWise(*a, *b, ElementWiseOperation::kSUM)->getOutput(0));
+    return silu(c, sum(c, *a, *b));
 }
 
 ITensor* RepNBottleneck(Ctx& c, ITensor& in, int c1, int c2, bool shortcut, int g, float e, const std::string& lname) {  // block.cpp:172-183
     const int c_ = int(c2 * e);
     ITensor* cv1 = RepConvN(c, in, c_, 1, g, lname + ".cv1");
     ITensor* cv2 = convBnSiLU(c, *cv1, c2, 3, 1, 1, lname + ".cv2", g);
-    if (shortcut && c1 == c2) return c.net->addElementWise(in, *cv2, ElementWiseOperation::kSUM)->getOutput(0);
-    return cv2;
+    return shortcut && c1 == c2 ? sum(c, in, *cv2) : cv2;
 }
 
 ITensor* RepNCSP(Ctx& c, ITensor& in, int c2, int n, bool shortcut, int g, float e, const std::string& lname) {  // block.cpp:185-206
@@ -65,15 +51,7 @@ ITensor* RepNCSP(Ctx& c, ITensor& in, int c2, int n, bool shortcut, int g, float
     ITensor* m = convBnSiLU(c, in, c_, 1, 1, 0, lname + ".cv1");
     for (int i = 0; i < n; ++i) m = RepNBottleneck(c, *m, c_, c_, shortcut, g, 1.0f, lname + ".m." + std::to_string(i));
     ITensor* cv2 = convBnSiLU(c, in, c_, 1, 1, 0, lname + ".cv2");
-    return convBnSiLU(c, *blocks::cat2(c, m, cv2), c2, 1, 1, 0, lname + ".cv3");
-}
-
-// chunk(2, 1) of a (C, H, W) tensor: the two channel halves (block.cpp:213-219)
-void halves(Ctx& c, ITensor& in, ITensor** lo, ITensor** hi) {
-    const Dims d = in.getDimensions();
-    const Dims3 size{d.d[0] / 2, d.d[1], d.d[2]}, unit{1, 1, 1};
-    *lo = c.net->addSlice(in, Dims3{0, 0, 0}, size, unit)->getOutput(0);
-    *hi = c.net->addSlice(in, Dims3{d.d[0] / 2, 0, 0}, size, unit)->getOutput(0);
+    return convBnSiLU(c, *cat2(c, m, cv2), c2, 1, 1, 0, lname + ".cv3");
 }
 
 ITensor* ELAN1(Ctx& c, ITensor& in, int c2, int c3, int c4, const std::string& lname) {  // block.cpp:208-228
@@ -81,8 +59,7 @@ ITensor* ELAN1(Ctx& c, ITensor& in, int c2, int c3, int c4, const std::string& l
     halves(c, *convBnSiLU(c, in, c3, 1, 1, 0, lname + ".cv1"), &s1, &s2);
     ITensor* cv2 = convBnSiLU(c, *s2, c4, 3, 1, 1, lname + ".cv2");
     ITensor* cv3 = convBnSiLU(c, *cv2, c4, 3, 1, 1, lname + ".cv3");
-    ITensor* v[] = {s1, s2, cv2, cv3};
-    return convBnSiLU(c, *c.net->addConcatenation(v, 4)->getOutput(0), c2, 1, 1, 0, lname + ".cv4");
+    return convBnSiLU(c, *cat(c, {s1, s2, cv2, cv3}), c2, 1, 1, 0, lname + ".cv4");
 }
 
 ITensor* RepNCSPELAN4(Ctx& c, ITensor& in, int c2, int c3, int c4, int c5, const std::string& lname) {  // block.cpp:230-254
@@ -90,8 +67,7 @@ ITensor* RepNCSPELAN4(Ctx& c, ITensor& in, int c2, int c3, int c4, int c5, const
     halves(c, *convBnSiLU(c, in, c3, 1, 1, 0, lname + ".cv1"), &s1, &s2);
     ITensor* cv2 = convBnSiLU(c, *RepNCSP(c, *s2, c4, c5, true, 1, 0.5f, lname + ".cv2.0"), c4, 3, 1, 1, lname + ".cv2.1");
     ITensor* cv3 = convBnSiLU(c, *RepNCSP(c, *cv2, c4, c5, true, 1, 0.5f, lname + ".cv3.0"), c4, 3, 1, 1, lname + ".cv3.1");
-    ITensor* v[] = {s1, s2, cv2, cv3};
-    return convBnSiLU(c, *c.net->addConcatenation(v, 4)->getOutput(0), c2, 1, 1, 0, lname + ".cv4");
+    return convBnSiLU(c, *cat(c, {s1, s2, cv2, cv3}), c2, 1, 1, 0, lname + ".cv4");
 }
 
 ITensor* avgPool2(Ctx& c, ITensor& in) {  // avg-pool 2x2, stride 1, padding 0 (block.cpp:258-260, 267-269)
@@ -111,27 +87,18 @@ ITensor* ADown(Ctx& c, ITensor& in, int c2, const std::string& lname) {  // bloc
     ITensor *s1, *s2;
     halves(c, *avgPool2(c, in), &s1, &s2);
     ITensor* cv1 = convBnSiLU(c, *s1, c_, 3, 2, 1, lname + ".cv1");
-    auto* pool2 = c.net->addPoolingNd(*s2, PoolingType::kMAX, DimsHW{3, 3});
-    assert(pool2);
-    pool2->setStrideNd(DimsHW{2, 2});
-    pool2->setPaddingNd(DimsHW{1, 1});
-    ITensor* cv2 = convBnSiLU(c, *pool2->getOutput(0), c_, 1, 1, 0, lname + ".cv2");
-    return blocks::cat2(c, cv1, cv2);
+    ITensor* cv2 = convBnSiLU(c, *maxpool(c, *s2, 3, 2, 1), c_, 1, 1, 0, lname + ".cv2");
+    return cat2(c, cv1, cv2);
 }
 
 // CBLinear (block.cpp:292-312): one biased 1x1 convolution to sum(c2s) channels, sliced into the c2s
 std::vector<ITensor*> CBLinear(Ctx& c, ITensor& in, const std::vector<int>& c2s, const std::string& lname) {
-    auto* conv = c.net->addConvolutionNd(in, std::accumulate(c2s.begin(), c2s.end(), 0), DimsHW{1, 1}, need(c.wm, lname + ".conv.weight"),
-                                         need(c.wm, lname + ".conv.bias"));
-    assert(conv);
+    auto* conv = conv1x1_bias(c, in, std::accumulate(c2s.begin(), c2s.end(), 0), lname + ".conv");
     conv->setName((lname + ".conv").c_str());
-    conv->setStrideNd(DimsHW{1, 1});
-    conv->setPaddingNd(DimsHW{0, 0});
-    const int h = in.getDimensions().d[1], w = in.getDimensions().d[2];
     std::vector<ITensor*> out;
     int start = 0;
     for (int ch : c2s) {
-        out.push_back(c.net->addSlice(*conv->getOutput(0), Dims3{start, 0, 0}, Dims3{ch, h, w}, Dims3{1, 1, 1})->getOutput(0));
+        out.push_back(channels(c, *conv->getOutput(0), start, ch));
         start += ch;
     }
     return out;
@@ -151,31 +118,21 @@ ITensor* CBFuse(Ctx& c, const std::vector<std::vector<ITensor*>>& in, const std:
         up->setScales(scales, 3);
         res[i] = up->getOutput(0);
     }
-    for (size_t i = 1; i < in.size(); ++i) res[0] = c.net->addElementWise(*res[0], *res[i], ElementWiseOperation::kSUM)->getOutput(0);
+    for (size_t i = 1; i < in.size(); ++i) res[0] = sum(c, *res[0], *res[i]);
     return res[0];
 }
 
 ITensor* SPPELAN(Ctx& c, ITensor& in, int c2, int c3, const std::string& lname) {  // block.cpp:334-353: three chained 5x5 stride-1 max-pools
-    std::vector<ITensor*> parts{convBnSiLU(c, in, c3, 1, 1, 0, lname + ".cv1")};
-    for (int i = 0; i < 3; ++i) {
-        auto* pool = c.net->addPoolingNd(*parts.back(), PoolingType::kMAX, DimsHW{5, 5});
-        assert(pool);
-        pool->setPaddingNd(DimsHW{2, 2});
-        pool->setStrideNd(DimsHW{1, 1});
-        parts.push_back(pool->getOutput(0));
-    }
-    return convBnSiLU(c, *c.net->addConcatenation(parts.data(), 4)->getOutput(0), c2, 1, 1, 0, lname + ".cv5");
+    ITensor* x = convBnSiLU(c, in, c3, 1, 1, 0, lname + ".cv1");
+    return convBnSiLU(c, *pool_chain(c, x, 5), c2, 1, 1, 0, lname + ".cv5");
 }
 
 // Conv(x, c2, 3), Conv(c2, c2, 3, g = 4), nn.Conv2d(c2, 4 * reg_max, 1, groups = 4) with bias   (block.cpp:355-366)
 ITensor* DetectBbox_Conv(Ctx& c, ITensor& in, int c2, int reg_max, const std::string& lname) {
     ITensor* cv0 = convBnSiLU(c, in, c2, 3, 1, 1, lname + ".0");
     ITensor* cv1 = convBnSiLU(c, *cv0, c2, 3, 1, 1, lname + ".1", 4);
-    auto* cv2 = c.net->addConvolutionNd(*cv1, reg_max * 4, DimsHW{1, 1}, need(c.wm, lname + ".2.weight"), need(c.wm, lname + ".2.bias"));
-    assert(cv2);
+    auto* cv2 = conv1x1_bias(c, *cv1, reg_max * 4, lname + ".2");
     cv2->setName((lname + ".conv").c_str());
-    cv2->setStrideNd(DimsHW{1, 1});
-    cv2->setPaddingNd(DimsHW{0, 0});
     cv2->setNbGroups(4);
     return cv2->getOutput(0);
 }
@@ -184,30 +141,9 @@ ITensor* DetectBbox_Conv(Ctx& c, ITensor& in, int c2, int reg_max, const std::st
 ITensor* DetectCls_Conv(Ctx& c, ITensor& in, int c3, int cls, const std::string& lname) {
     ITensor* cv0 = convBnSiLU(c, in, c3, 3, 1, 1, lname + ".0");
     ITensor* cv1 = convBnSiLU(c, *cv0, c3, 3, 1, 1, lname + ".1");
-    auto* cv2 = c.net->addConvolutionNd(*cv1, cls, DimsHW{1, 1}, need(c.wm, lname + ".2.weight"), need(c.wm, lname + ".2.bias"));
-    assert(cv2);
+    auto* cv2 = conv1x1_bias(c, *cv1, cls, lname + ".2");
     cv2->setName((lname + ".conv").c_str());
-    cv2->setStrideNd(DimsHW{1, 1});
-    cv2->setPaddingNd(DimsHW{0, 0});
     return cv2->getOutput(0);
-}
-
-// (64, gh, gw) -> (4, 16, grid) -> transpose (16, 4, grid) -> softmax over the 16 bins (the default axis of a 3-d tensor) -> 1x1 conv
-// with lname.conv.weight -> (4, grid)   (block.cpp:380-399)
-ITensor* DFL(Ctx& c, ITensor& in, int ch, const std::string& lname) {
-    const Dims d = in.getDimensions();
-    const int grid = d.d[1] * d.d[2], split = d.d[0] / ch;
-    auto* sh1 = c.net->addShuffle(in);
-    sh1->setReshapeDimensions(Dims3{split, ch, grid});
-    sh1->setSecondTranspose(Permutation{1, 0, 2});
-    auto* sm = c.net->addSoftMax(*sh1->getOutput(0));
-    auto* conv = c.net->addConvolutionNd(*sm->getOutput(0), 1, DimsHW{1, 1}, need(c.wm, lname + ".conv.weight"), noWeights());
-    assert(conv);
-    conv->setStrideNd(DimsHW{1, 1});
-    conv->setPaddingNd(DimsHW{0, 0});
-    auto* sh2 = c.net->addShuffle(*conv->getOutput(0));
-    sh2->setReshapeDimensions(Dims2{4, grid});
-    return sh2->getOutput(0);
 }
 
 // DualDDetect (block.cpp:424-455) and DDetect (:457-489): the same body but for c3 = max(ch0, min(2 nc, 128)) against max(ch0, min(nc, 128)).
@@ -224,23 +160,19 @@ std::vector<ITensor*> detect(Ctx& c, const std::vector<ITensor*>& feats, int cls
         sh->setReshapeDimensions(Dims2{cls, d.d[1] * d.d[2]});
         clss.push_back(sh->getOutput(0));
     }
-    for (size_t i = 0; i < feats.size(); ++i) ret.push_back(blocks::cat2(c, DFL(c, *boxes[i], 16, lname + ".dfl"), clss[i]));
+    for (size_t i = 0; i < feats.size(); ++i) {   // DFL (block.cpp:380-399): blocks::DFL on the (64, gh, gw) arm
+        const Dims d = boxes[i]->getDimensions();
+        ret.push_back(cat2(c, DFL(c, *boxes[i], 0, d.d[1] * d.d[2], lname + ".dfl.conv.weight"), clss[i]));
+    }
     return ret;
 }
 
 // block.cpp:401-422: one field "netinfo" = {classes, W, H, maxOut, isSeg} under the field type kFLOAT32, as the reference does
 IPluginV2Layer* addYoLoLayer(Ctx& c, const std::vector<ITensor*>& dets, const Yolov9Config& cfg) {
-    auto* creator = getPluginRegistry()->getPluginCreator("YoloLayer_TRT", "1");
-    assert(creator && "YoloLayer_TRT creator not registered");
     int netinfo[5] = {cfg.num_class, cfg.input_w, cfg.input_h, cfg.max_out_bbox, 0};
     PluginField field("netinfo", netinfo, PluginFieldType::kFLOAT32, 5);
     PluginFieldCollection fc{1, &field};
-    IPluginV2* plugin = creator->createPlugin("yololayer", &fc);
-    if (!plugin) return nullptr;
-    std::vector<ITensor*> ins(dets);
-    auto* layer = c.net->addPluginV2(ins.data(), (int32_t)ins.size(), *plugin);
-    plugin->destroy();  // the network holds its own clone
-    return layer;
+    return plugin_layer(c, "YoloLayer_TRT", "yololayer", &fc, dets);
 }
 
 struct Rep {   // RepNCSPELAN4's c2, c3, c4 and the RepNCSP repeat count (ELAN1: c2, c3, c4)
@@ -291,89 +223,65 @@ bool yolov9_model_valid(const std::string& name, bool converted) { return spec_o
 IHostMemory* buildEngineYolov9(IBuilder* builder, IBuilderConfig* config, const std::string& wts, const Yolov9Config& cfg) {
     const Spec* sp = spec_of(cfg.model, cfg.converted);
     if (!sp) return nullptr;
-    WeightMap wm = loadWeights(wts);
-    INetworkDefinition* net = builder->createNetworkV2(0U);
-    IHostMemory* plan = nullptr;
-    {
-        Ctx c{net, wm, {}};
-        auto M = [&](int k) { return "model." + std::to_string(k + sp->first); };
-        auto rep = [&](ITensor* x, const Rep& r, const std::string& lname) { return RepNCSPELAN4(c, *x, r.c2, r.c3, r.c4, r.n, lname); };
-        auto down = [&](ITensor* x, int c2, const std::string& lname) { return sp->adown ? ADown(c, *x, c2, lname) : AConv(c, *x, c2, lname); };
-        auto block2 = [&](ITensor* x, const std::string& lname) {
-            return sp->elan1 ? ELAN1(c, *x, sp->b2.c2, sp->b2.c3, sp->b2.c4, lname) : rep(x, sp->b2, lname);
-        };
-        auto upcat = [&](ITensor* x, ITensor* lateral) {   // nn.Upsample(None, 2, 'nearest') and Concat (model.cpp:64-70)
-            auto* up = net->addResize(*x);
-            assert(up);
-            up->setResizeMode(ResizeMode::kNEAREST);
-            const float scales[] = {1.0f, 2.0f, 2.0f};
-            up->setScales(scales, 3);
-            return blocks::cat2(c, up->getOutput(0), lateral);
-        };
+    Session s(builder, wts);
+    Ctx& c = s.c;
+    auto M = [&](int k) { return "model." + std::to_string(k + sp->first); };
+    auto rep = [&](ITensor* x, const Rep& r, const std::string& lname) { return RepNCSPELAN4(c, *x, r.c2, r.c3, r.c4, r.n, lname); };
+    auto down = [&](ITensor* x, int c2, const std::string& lname) { return sp->adown ? ADown(c, *x, c2, lname) : AConv(c, *x, c2, lname); };
+    auto block2 = [&](ITensor* x, const std::string& lname) {
+        return sp->elan1 ? ELAN1(c, *x, sp->b2.c2, sp->b2.c3, sp->b2.c4, lname) : rep(x, sp->b2, lname);
+    };
+    auto upcat = [&](ITensor* x, ITensor* lateral) { return cat2(c, upsample2x(c, *x), lateral); };   // nn.Upsample(None, 2, 'nearest') and Concat (model.cpp:64-70)
 
-        ITensor* data = net->addInput("images", DataType::kFLOAT, Dims3{3, cfg.input_h, cfg.input_w});   // kInputTensorName (include/config.h)
-        assert(data);
-        // ---- backbone: what every model and both heads read
-        ITensor* x = convBnSiLU(c, *data, sp->stem0, 3, 2, 1, M(0));
-        x = convBnSiLU(c, *x, sp->stem1, 3, 2, 1, M(1));
-        x = block2(x, M(2));
-        ITensor* r4 = rep(down(x, sp->d3, M(3)), sp->r4, M(4));
-        ITensor* r6 = rep(down(r4, sp->d5, M(5)), sp->r6, M(6));
-        ITensor* r8 = rep(down(r6, sp->d7, M(7)), sp->r8, M(8));
+    ITensor* data = s.input("images", cfg.input_h, cfg.input_w);   // kInputTensorName (include/config.h)
+    // ---- backbone: what every model and both heads read
+    ITensor* x = convBnSiLU(c, *data, sp->stem0, 3, 2, 1, M(0));
+    x = convBnSiLU(c, *x, sp->stem1, 3, 2, 1, M(1));
+    x = block2(x, M(2));
+    ITensor* r4 = rep(down(x, sp->d3, M(3)), sp->r4, M(4));
+    ITensor* r6 = rep(down(r4, sp->d5, M(5)), sp->r6, M(6));
+    ITensor* r8 = rep(down(r6, sp->d7, M(7)), sp->r8, M(8));
 
-        std::vector<ITensor*> feats;
-        std::string head_name;
-        bool dual;
-        if (!sp->aux) {
-            // ---- main-branch neck (model.cpp:60-109): SPPELAN, two up-concat merges, two down-concat merges
-            ITensor* spp = SPPELAN(c, *r8, sp->spp_c2, sp->spp_c3, M(9));
-            ITensor* r12 = rep(upcat(spp, r6), sp->r12, M(12));
-            ITensor* r15 = rep(upcat(r12, r4), sp->r15, M(15));
-            ITensor* r18 = rep(blocks::cat2(c, down(r15, sp->d16, M(16)), r12), sp->r18, M(18));
-            ITensor* r21 = rep(blocks::cat2(c, down(r18, sp->d19, M(19)), spp), sp->r21, M(21));
-            feats = {r15, r18, r21};
-            // t / s keep the auxiliary branch in the checkpoint (model.22 - 28) until it is converted: DualDDetect is model.29 then
-            // (model.cpp:139-143, 283-287); converted t / s / m and gelan-c: DDetect, model.22 (:142, :521, :1253)
-            dual = sp->elan1 && !cfg.converted;
-            head_name = dual ? "model.29" : "model.22";
-        } else {
-            // ---- multi-level reversible auxiliary branch (model.cpp:441-509, 651-701), fed by the backbone through CBLinear / CBFuse
-            const std::vector<ITensor*> cb23 = CBLinear(c, *r4, {sp->d3}, M(22));
-            const std::vector<ITensor*> cb24 = CBLinear(c, *r6, {sp->d3, sp->d5}, M(23));
-            const std::vector<ITensor*> cb25 = CBLinear(c, *r8, {sp->d3, sp->d5, sp->d7}, M(24));
-            ITensor* a = convBnSiLU(c, *data, sp->stem0, 3, 2, 1, M(25));
-            a = convBnSiLU(c, *a, sp->stem1, 3, 2, 1, M(26));
-            a = rep(a, sp->b2, M(27));
-            ITensor* d29 = down(a, sp->d3, M(28));
-            ITensor* r31 = rep(CBFuse(c, {cb23, cb24, cb25, {d29}}, {0, 0, 0, 0}, {8, 16, 32, 8}), sp->r4, M(30));
-            ITensor* d32 = down(r31, sp->d5, M(31));
-            ITensor* r34 = rep(CBFuse(c, {cb24, cb25, {d32}}, {1, 1, 0}, {16, 32, 16}), sp->r6, M(33));
-            ITensor* d35 = down(r34, sp->d7, M(34));
-            ITensor* r37 = rep(CBFuse(c, {cb25, {d35}}, {2, 0}, {32, 32}), sp->r8, M(36));
-            feats = {r31, r34, r37};
-            dual = true;
-            head_name = M(37);   // model.38 (model.cpp:515-516, 706-708)
-        }
-        const int ch0 = (int)feats[0]->getDimensions().d[0];   // ch[0] of the reference's calls: the stride-8 feature's channels
-        std::vector<ITensor*> dets = detect(c, feats, cfg.num_class, ch0, dual, head_name);
-        if (cfg.mark_heads)
-            for (size_t i = 0; i < dets.size(); ++i) {
-                dets[i]->setName(("head" + std::to_string(i)).c_str());
-                net->markOutput(*dets[i]);
-            }
-        IPluginV2Layer* yolo = addYoLoLayer(c, dets, cfg);
-        if (yolo) {
-            yolo->getOutput(0)->setName("output");   // kOutputTensorName
-            net->markOutput(*yolo->getOutput(0));
-            builder->setMaxBatchSize(cfg.max_batch);
-            config->setMaxWorkspaceSize(16 * (1 << 20));
-            if (cfg.fp16) config->setFlag(BuilderFlag::kFP16);
-            plan = builder->buildSerializedNetwork(*net, *config);
-        }
+    std::vector<ITensor*> feats;
+    std::string head_name;
+    bool dual;
+    if (!sp->aux) {
+        // ---- main-branch neck (model.cpp:60-109): SPPELAN, two up-concat merges, two down-concat merges
+        ITensor* spp = SPPELAN(c, *r8, sp->spp_c2, sp->spp_c3, M(9));
+        ITensor* r12 = rep(upcat(spp, r6), sp->r12, M(12));
+        ITensor* r15 = rep(upcat(r12, r4), sp->r15, M(15));
+        ITensor* r18 = rep(cat2(c, down(r15, sp->d16, M(16)), r12), sp->r18, M(18));
+        ITensor* r21 = rep(cat2(c, down(r18, sp->d19, M(19)), spp), sp->r21, M(21));
+        feats = {r15, r18, r21};
+        // t / s keep the auxiliary branch in the checkpoint (model.22 - 28) until it is converted: DualDDetect is model.29 then
+        // (model.cpp:139-143, 283-287); converted t / s / m and gelan-c: DDetect, model.22 (:142, :521, :1253)
+        dual = sp->elan1 && !cfg.converted;
+        head_name = dual ? "model.29" : "model.22";
+    } else {
+        // ---- multi-level reversible auxiliary branch (model.cpp:441-509, 651-701), fed by the backbone through CBLinear / CBFuse
+        const std::vector<ITensor*> cb23 = CBLinear(c, *r4, {sp->d3}, M(22));
+        const std::vector<ITensor*> cb24 = CBLinear(c, *r6, {sp->d3, sp->d5}, M(23));
+        const std::vector<ITensor*> cb25 = CBLinear(c, *r8, {sp->d3, sp->d5, sp->d7}, M(24));
+        ITensor* a = convBnSiLU(c, *data, sp->stem0, 3, 2, 1, M(25));
+        a = convBnSiLU(c, *a, sp->stem1, 3, 2, 1, M(26));
+        a = rep(a, sp->b2, M(27));
+        ITensor* d29 = down(a, sp->d3, M(28));
+        ITensor* r31 = rep(CBFuse(c, {cb23, cb24, cb25, {d29}}, {0, 0, 0, 0}, {8, 16, 32, 8}), sp->r4, M(30));
+        ITensor* d32 = down(r31, sp->d5, M(31));
+        ITensor* r34 = rep(CBFuse(c, {cb24, cb25, {d32}}, {1, 1, 0}, {16, 32, 16}), sp->r6, M(33));
+        ITensor* d35 = down(r34, sp->d7, M(34));
+        ITensor* r37 = rep(CBFuse(c, {cb25, {d35}}, {2, 0}, {32, 32}), sp->r8, M(36));
+        feats = {r31, r34, r37};
+        dual = true;
+        head_name = M(37);   // model.38 (model.cpp:515-516, 706-708)
     }
-    delete net;
-    freeWeights(wm);
-    return plan;
+    const int ch0 = (int)feats[0]->getDimensions().d[0];   // ch[0] of the reference's calls: the stride-8 feature's channels
+    std::vector<ITensor*> dets = detect(c, feats, cfg.num_class, ch0, dual, head_name);
+    if (cfg.mark_heads) s.mark_heads(dets);
+    IPluginV2Layer* yolo = addYoLoLayer(c, dets, cfg);
+    if (!yolo) return nullptr;
+    s.output(yolo->getOutput(0), "output");   // kOutputTensorName
+    return s.finish(builder, config, cfg.max_batch, cfg.fp16);
 }
 
 }  // namespace trtx_host
