@@ -476,6 +476,23 @@ int32_t trtx_op_conv_bneck_pair_f16(const void* in, int N, int H, int W, int ld_
 int32_t trtx_op_conv_bneck_pair_or_two_f16(const void* in, int N, int H, int W, int ld_in, int in_coff, const void* w1_packed, const float* bias1, int act1,
                                            const void* w2_packed, const float* bias2, int act2, int shortcut, int act_after, void* mid, void* out,
                                            int ld_out, trtx_stream_t stream);
+/* YOLOv13's DSConv (yolov13/src/block.cpp:491-534: depthwise k x k without bias, BatchNorm or activation -> 1x1 -> BatchNorm -> x sigmoid(x); DSBottleneck
+ * adds its input behind the second one) in ONE launch (kernels/conv_dw_pw.hip): in NHWC fp16 [N][H][W] with Cin channels at channel stride ld_in; the
+ * depthwise filter fp32 [k*k][Cin] (tap-major, as trtx_op_conv2d_dw_nhwc takes it), k 3 / 5 / 7 with pad k/2, stride 1 or 2; bias_dw must be NULL and dilation
+ * 1 (what the fused kernel does not take is refused, not computed differently); the 1x1's weights as trtx_conv_pack_weights_f16 packs them for a 1x1 over
+ * cin_pad = Cin (BatchNorm scale folded), bias [Cout_pad] or NULL; act1 / act2 none, ReLU or SiLU around the optional residual (out's dims, channel stride
+ * ld_res); out NHWC fp16 [N][Ho][Wo] with channel stride ld_out.  Cin (<= 1024) and Cout multiples of 8, the channel strides too, pointers 16-byte aligned;
+ * concat slices work as source, destination and residual.  The depthwise result is rounded to fp16 once and never leaves the chip.  TRTX_ERR_INVALID: an
+ * output that lies on the input other than as another channel slice of the same map; TRTX_ERR_UNSUPPORTED: anything else outside the above.  Nothing is
+ * written in either case. */
+int32_t trtx_op_conv_dw_pw_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const float* w_dw_taps_c, const float* bias_dw, int k, int stride,
+                               int dilation, const void* w_pw_packed, const float* bias, int Cout, int act1, const void* residual, int ld_res, int act2, void* out,
+                               int ld_out, trtx_stream_t stream);
+/* What the executor issues for a DSConv: that launch where it is admitted, otherwise the depthwise kernel into `mid` (NHWC fp16 [N][Ho][Wo][Cin], dense,
+ * 16-byte aligned, written only then) and the 1x1 from it on the implicit-GEMM kernel's default tactic. */
+int32_t trtx_op_conv_dw_pw_or_two_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const float* w_dw_taps_c, const float* bias_dw, int k, int stride,
+                                      int dilation, const void* w_pw_packed, const float* bias, int Cout, int act1, const void* residual, int ld_res, int act2,
+                                      void* mid, void* out, int ld_out, trtx_stream_t stream);
 /* 1 <= n <= 3 pairs of convolutions that read the same input, in ONE launch (the dual tile of kernels/igemm_tile.h; the detect head's cv2.x.0 -> 64 and
  * cv3.x.0 -> 80 over three pyramid levels): problem j reads in[j], NHWC fp16 with geom[5 j ..] = {N, H, W, Cin, ld_in}, through one k x k filter geometry
  * (stride, pad) and writes out0[j] (side0[3 j ..] = {Cout, ld_out, act}: 57 .. 64 channels in steps of 8) and out1[j] (side1 likewise: 65 .. 80 channels); weights as

@@ -590,6 +590,44 @@ def conv_bneck_pair_f16(x, w1_packed, bias1, w2_packed, bias2, act1="silu", act2
     return out
 
 
+def conv_dw_pw_f16(x, w_dw, w_pw, bias, k, stride, act, residual=None, out=None, out_ld=None, mid=None, act2="none", bias_dw=None, dilation=1, cout=None,
+                   status_only=False):
+    """YOLOv13's DSConv in one launch (kernels/conv_dw_pw.hip): the depthwise k x k convolution (pad k // 2) of x [N,H,W,Cin] CUDA half - or of a channel
+    slice of a wider tensor, pixel stride x.stride(2) - and the 1x1 convolution behind it, + bias, act, + residual, act2 -> NHWC half [N,Ho,Wo,Cout] (or
+    into `out` with channel stride out_ld).  w_dw: the depthwise filter as a host array [Cin, k, k] (or [Cin, 1, k, k]); w_pw: the 1x1's as a host array
+    [Cout, Cin] (or [Cout, Cin, 1, 1]), BatchNorm scale folded by the caller; both are laid out for the device here.  bias: CUDA fp32 [Cout] or None.
+    mid (NHWC half [N,Ho,Wo,Cin], contiguous): the executor's form - the fused launch where it is admitted, conv_dw and the 1x1 through `mid` where not.
+    bias_dw / dilation: what the fused launch refuses (TrtxError, or the status with status_only)."""
+    import numpy as np
+    import torch
+    N, H, W, C = x.shape
+    assert x.dtype == torch.float16 and x.stride(3) == 1
+    wp = np.asarray(w_pw, dtype=np.float32)
+    cout = cout or wp.shape[0]
+    pad = k // 2
+    Ho, Wo = (H + 2 * pad - dilation * (k - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (k - 1) - 1) // stride + 1
+    taps = torch.from_numpy(np.ascontiguousarray(np.asarray(w_dw, dtype=np.float32).reshape(C, k * k).T)).to(x.device)
+    packed, cout_pad, _, _ = pack_conv_weights_f16(wp.reshape(wp.shape[0], wp.shape[1], 1, 1), cin_pad=(C + 7) // 8 * 8)
+    wq = torch.from_numpy(packed.view(np.int16)).to(x.device)
+    bq = None
+    if bias is not None:   # [Cout_pad], as the implicit-GEMM kernel of the two-launch form reads it
+        bq = torch.zeros(cout_pad, dtype=torch.float32, device=x.device)
+        bq[:bias.numel()] = bias
+    if out is None:
+        out = torch.empty((N, Ho, Wo, cout), dtype=torch.float16, device=x.device)
+    head = (_p(x), N, H, W, C, x.stride(2), _p(taps), _p(bias_dw), k, stride, dilation, _p(wq), _p(bq), cout, ACT[act], _p(residual),
+            residual.stride(2) if residual is not None else 0, ACT[act2])
+    if mid is None:
+        st = lib().trtx_op_conv_dw_pw_f16(*head, _p(out), out_ld or out.shape[-1], _stream())
+    else:
+        assert mid.dtype == torch.float16 and mid.is_contiguous() and tuple(mid.shape) == (N, Ho, Wo, C)
+        st = lib().trtx_op_conv_dw_pw_or_two_f16(*head, _p(mid), _p(out), out_ld or out.shape[-1], _stream())
+    if status_only:
+        return st
+    check(st, "trtx_op_conv_dw_pw_f16")
+    return out
+
+
 def conv_dual_group_f16(xs, w0, b0, outs0, w1, b1, outs1, k=3, stride=1, pad=1, act0="silu", act1="silu", cout0=None, cout1=None, res1=None, i8_1=False,
                         or_two=False, status_only=False):
     """1..3 pairs of convolutions over shared inputs in one launch (the dual tile): xs[j] [N,H,W,Cin] CUDA half (or a channel slice: pixel stride

@@ -189,6 +189,20 @@ int32_t conv_bneck_pair_f16(const ConvArgs& first, const ConvArgs& second, hipSt
 // ... where _possible() holds (it refuses an output that lies on the input other than as a different channel slice of one buffer: the fused kernel cannot run
 // in place), otherwise the two launches: first.out, the tensor between them, is then written and second.in must be it.  What the executor issues at a marked op.
 int32_t conv_bneck_pair_or_two_f16(const ConvArgs& first, const ConvArgs& second, hipStream_t s);
+// YOLOv13's DSConv in one launch (conv_dw_pw.hip): a depthwise k x k convolution and the 1x1 convolution behind it, fp16; the depthwise result lives in LDS
+// as the 1x1's MFMA operand.  `dw` as conv_dw takes it (dw.out is not written), `pw` as conv_igemm_f16 takes a 1x1 (pw.in is not read; the same packed
+// weights, of which rows up to Cout rounded up to 16 and k up to Cin rounded up to 32 are read).  _supported(): the depthwise half is what conv_dw_supported
+// admits, without bias, activation or residual; the 1x1 is stride 1, pad 0, groups 1 over the depthwise channels; Cin and Cout multiples of 8, Cin <= 1024;
+// channel strides multiples of 8; act1 / act2 none, ReLU or SiLU; whatever pointers are set 16-byte aligned.  conv_dw_pw_f16: TRTX_ERR_UNSUPPORTED outside
+// that, TRTX_ERR_INVALID for an output that lies on the input other than as another channel slice of the same map (the halo is read after neighbours may
+// have been written); nothing is written either way.
+bool conv_dw_pw_supported(const ConvArgs& dw, const ConvArgs& pw);
+// ... and where the lowering asks for it: and the executor's entry below takes it: the widths at which the one launch measured faster than the two (Cin and Cout from 16 to 64; conv_dw_pw.hip)
+bool conv_dw_pw_worthwhile(int cin, int cout);
+int32_t conv_dw_pw_f16(const ConvArgs& dw, const ConvArgs& pw, hipStream_t s);
+// ... where it is supported, worthwhile and the output does not lie on the input, otherwise conv_dw into `mid` (NHWC fp16 [N][Ho][Wo][Cin], dense; written only then) and the 1x1 from it on the implicit-GEMM
+// kernel's default tactic.  What the executor issues at an OP_DSCONV.
+int32_t conv_dw_pw_or_two_f16(const ConvArgs& dw, const ConvArgs& pw, void* mid, hipStream_t s);
 // generic direct convolution (any groups / dilation / channel count), T = activation dtype, fp32 weights
 int32_t conv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 // depthwise convolution (conv_dw.hip): groups == Cin == Cout, k 3 / 5 / 7 with pad k/2, stride 1 / 2, no dilation; weights fp32 [kh*kw][C]

@@ -197,6 +197,43 @@ extern "C" int32_t trtx_op_conv_bneck_pair_or_two_f16(const void* in, int N, int
     return op_bneck_pair(in, N, H, W, ld_in, in_coff, w1_packed, bias1, act1, w2_packed, bias2, act2, shortcut, act_after, mid, out, ld_out, true, stream);
 }
 
+// --- YOLOv13's DSConv, depthwise k x k -> 1x1, in one launch (kernels/conv_dw_pw.hip), test / tool entry points
+static int32_t op_dw_pw(const void* in, int N, int H, int W, int Cin, int ld_in, const float* w_dw_taps_c, const float* bias_dw, int k, int stride, int dilation,
+                        const void* w_pw_packed, const float* bias, int Cout, int act1, const void* residual, int ld_res, int act2, void* mid, void* out, int ld_out,
+                        bool or_two, trtx_stream_t stream) {
+    if (!in || !w_dw_taps_c || !w_pw_packed || !out || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || k < 1 || stride < 1 || dilation < 1 || (or_two && !mid))
+        return TRTX_ERR_INVALID;
+    const int pad = k / 2;
+    if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return TRTX_ERR_INVALID;
+    ConvArgs d{};
+    d.in = in; d.wgt = w_dw_taps_c; d.bias = bias_dw; d.out = mid;
+    d.N = N; d.H = H; d.W = W; d.Cin = Cin; d.ld_in = ld_in;
+    d.Ho = (H + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
+    d.Wo = (W + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
+    d.Cout = Cin; d.Cout_pad = Cin; d.ld_out = Cin;
+    d.kh = k; d.kw = k; d.stride_h = stride; d.stride_w = stride; d.pad_h = pad; d.pad_w = pad; d.dil_h = dilation; d.dil_w = dilation;
+    d.groups = Cin;
+    d.K = k * k; d.Kpad = d.K;
+    d.M = N * d.Ho * d.Wo;
+    ConvArgs p = op_conv_args(N, d.Ho, d.Wo, Cin, Cin, Cout, ld_out, 1, 1, 1, 1, 0, 0, act1, residual != nullptr, ld_res, act2);
+    p.in = mid; p.wgt = w_pw_packed; p.bias = bias; p.out = out; p.residual = residual;
+    return or_two ? conv_dw_pw_or_two_f16(d, p, mid, static_cast<hipStream_t>(stream)) : conv_dw_pw_f16(d, p, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trtx_op_conv_dw_pw_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const float* w_dw_taps_c, const float* bias_dw, int k, int stride,
+                                          int dilation, const void* w_pw_packed, const float* bias, int Cout, int act1, const void* residual, int ld_res, int act2,
+                                          void* out, int ld_out, trtx_stream_t stream) {
+    return op_dw_pw(in, N, H, W, Cin, ld_in, w_dw_taps_c, bias_dw, k, stride, dilation, w_pw_packed, bias, Cout, act1, residual, ld_res, act2, nullptr, out, ld_out,
+                    false, stream);
+}
+
+extern "C" int32_t trtx_op_conv_dw_pw_or_two_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const float* w_dw_taps_c, const float* bias_dw, int k,
+                                                 int stride, int dilation, const void* w_pw_packed, const float* bias, int Cout, int act1, const void* residual,
+                                                 int ld_res, int act2, void* mid, void* out, int ld_out, trtx_stream_t stream) {
+    return op_dw_pw(in, N, H, W, Cin, ld_in, w_dw_taps_c, bias_dw, k, stride, dilation, w_pw_packed, bias, Cout, act1, residual, ld_res, act2, mid, out, ld_out, true,
+                    stream);
+}
+
 // --- two sibling groups over the same inputs in one launch (the dual tile of kernels/igemm_tile.h), test / tool entry points
 static int32_t op_dual_group(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0, const float* const* bias0,
                              void* const* out0, const int32_t* side0, const void* const* w1, const float* const* bias1, void* const* out1, const int32_t* side1,

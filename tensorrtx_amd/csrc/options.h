@@ -37,6 +37,8 @@ struct Options {
     bool area_attention = true;  // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
     bool aattn_split = true;     // TRTX_AATTN_SPLIT=0: YOLOv13 area attention (q | k and v from two convolutions) stays on the generic linear path (shuffles, slices, matmul, softmax)
     bool hgconv = true;         // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
+    int dsconv = 1;              // TRTX_DSCONV=0: YOLOv13's DSConv (depthwise k x k -> 1x1) stays two launches, conv_dw and the 1x1 (no kernels/conv_dw_pw.hip);
+                                 //            2: one launch wherever the kernel takes it, also outside the measured widths the lowering keeps to (tools/dsconv_time.py)
     bool gated_add = true;       // TRTX_GATED_ADD=0: a + gate * b with a constant gate (YOLOv13's FullPad_Tunnel, A2C2f's gamma residual) stays a product and a sum
     bool yolo9_head = true;      // TRTX_YOLO9_HEAD=0: the YOLOv9 / GELAN detect tail keeps the plugin route (layout passes, the DFL chain, concat scatters + YoloLayer_TRT)
     bool yolo5_head = true;      // TRTX_YOLO5_HEAD=0: the anchor-based (YOLOv5) detect tail keeps the plugin route (layout passes to fp32 planes + YoloLayer_TRT)

@@ -289,6 +289,23 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     st = conv_direct(a, op.dtype, stream);
                 break;
             }
+            case OP_DSCONV: {   // depthwise k x k -> 1x1: the one fused launch where the kernel takes the run-time pointers, the two launches through the workspace otherwise
+                void* mid = static_cast<char*>(c->d_arena) + op.ws_off;
+                ConvArgs d = op.dw_conv, a = op.conv;
+                d.in = R.ptr(op.in[0]);
+                d.wgt = W + op.dw_off;
+                d.out = mid;
+                a.in = mid;
+                a.out = R.ptr(op.out[0]);
+                a.residual = op.in.size() > 1 ? R.ptr(op.in[1]) : nullptr;
+                a.wgt = W + op.w_off;
+                a.bias = reinterpret_cast<const float*>(W + op.b_off);
+                d.N = a.N = nb(t0);
+                d.M = a.M = a.N * a.Ho * a.Wo;
+                st = op.i[0] ? conv_dw_pw_f16(d, a, stream) : TRTX_ERR_UNSUPPORTED;   // (i[0]: a plan lowered with TRTX_DSCONV=2 fuses beyond the measured widths)
+                if (st == TRTX_ERR_UNSUPPORTED || st == TRTX_ERR_INVALID) st = conv_dw_pw_or_two_f16(d, a, mid, stream);
+                break;
+            }
             case OP_CONV_GROUP: {   // independent convolutions of one kernel instantiation: one launch (conv_igemm_group_f16_kernel)
                 ConvArgs ga[kMaxConvGroup];
                 const int gn = (int)op.group.size();

@@ -418,6 +418,37 @@ struct Lowerer {
         return true;
     }
 
+    // A DSConv (match_dsconv) at its 1x1 convolution's record: ONE op that reads the depthwise convolution's input and writes the record's output; the tensor
+    // between the two halves is no plan tensor, only the op's workspace (dense, the largest batch) for the two-launch form the executor falls back to
+    bool emit_dsconv(const FusedConv& c) {
+        const LayerDef &lp = net.layers[c.conv_layer], &ld = net.layers[c.dw_conv];
+        const int in = need_nhwc(ld.inputs[0]);
+        const int res = c.residual >= 0 ? need_nhwc(c.residual) : -1;
+        const PTensor ti = plan.tensors[in];
+        const int out = new_tensor(c.out_tensor, net.tensors[c.out_tensor].dims, LAY_NHWC, true);
+        std::vector<int> ins = {in};
+        if (res >= 0) ins.push_back(res);
+        POp& op = add_op(OP_DSCONV, ld.name + " -> " + lp.name + " [DSConv]", ins, {out});
+        op.src_layer = c.conv_layer;
+        op.scale_layer = c.scale_layer;
+        op.dw_layer = c.dw_conv;
+        op.i[0] = opt.dsconv >= 2;   // fuse beyond the measured widths too (timing)
+        const PTensor& to = plan.tensors[out];
+        ConvArgs& d = op.dw_conv;
+        d.H = ti.H; d.W = ti.W; d.Cin = d.Cout = d.groups = ti.C; d.Ho = to.H; d.Wo = to.W;
+        d.kh = ld.kernel[0]; d.kw = ld.kernel[1]; d.stride_h = ld.stride[0]; d.stride_w = ld.stride[1];
+        d.pad_h = ld.padding[0]; d.pad_w = ld.padding[1]; d.dil_h = d.dil_w = 1;
+        ConvArgs& a = op.conv;
+        a.H = a.Ho = to.H; a.W = a.Wo = to.W; a.Cin = ti.C; a.Cout = to.C;
+        a.kh = a.kw = 1; a.stride_h = a.stride_w = 1; a.pad_h = a.pad_w = 0; a.dil_h = a.dil_w = 1; a.groups = 1;
+        a.act1 = c.act1; a.alpha1 = c.alpha1; a.act2 = c.act2; a.alpha2 = c.alpha2;
+        const size_t images = (size_t)(ti.nfix ? ti.nfix : plan.max_batch) * ti.nmul;
+        op.ws_bytes = images * to.H * to.W * (size_t)ti.C * 2;
+        op.flops = 2.0 * to.nmul * a.Ho * a.Wo * ((double)ti.C * d.kh * d.kw + (double)to.C * ti.C);
+        pt_of[c.out_tensor] = out;
+        return true;
+    }
+
     bool emit_activation(const LayerDef& l, int code, float alpha) {   // an activation op in the layout its input already has
         const int p = pt_of[l.inputs[0]];
         const bool nhwc = plan.tensors[p].layout == LAY_NHWC;
@@ -1003,7 +1034,15 @@ struct Lowerer {
                 continue;
             }
             if (fu.group_at[li] >= 0) {
-                if (!emit_conv(fu.groups[fu.group_at[li]])) return false;
+                const FusedConv& c = fu.groups[fu.group_at[li]];
+                const bool fast_acts = (c.act1 == ACT_NONE || c.act1 == ACT_RELU || c.act1 == ACT_SILU) && (c.act2 == ACT_NONE || c.act2 == ACT_RELU || c.act2 == ACT_SILU);
+                if (c.dw_conv >= 0 && !fast_acts) {   // an epilogue the fused kernel does not have (LeakyReLU, Mish ...): the depthwise convolution as an op of its own
+                    FusedConv d;
+                    d.conv_layer = c.dw_conv;
+                    d.out_tensor = net.layers[c.dw_conv].outputs[0];
+                    if (!emit_conv(d) || !emit_conv(c)) return false;
+                } else if (!(c.dw_conv >= 0 ? emit_dsconv(c) : emit_conv(c)))
+                    return false;
                 continue;
             }
             if (fu.absorbed[li]) {

@@ -40,6 +40,7 @@ void match_conv_fusion(const NetView& g, Fusions& f) {
         if (!g.spatial(net.tensors[l.inputs[0]].dims)) continue;
         FusedConv c;
         c.conv_layer = (int)li;
+        c.dw_conv = f.dsconv_dw[li];
         int t = l.outputs[0], last = (int)li, nx;
         auto take = [&](int layer, int out) {   // `layer` joins the fused op, whose result is now tensor `out`
             f.absorbed[layer] = true;
@@ -423,6 +424,38 @@ void match_repvggdw_fold(const NetView& g, Fusions& f) {
         f.absorbed[c3] = f.absorbed[s3] = f.absorbed[sum] = true;
         f.repdw_at[li] = (int)f.repdws.size();
         f.repdws.push_back(RepDwFuse{c3, s3, sum});
+    }
+}
+
+// ---- DSConv (yolov13/src/block.cpp:491-534): a depthwise k x k convolution with no bias, no scale and no activation behind it, read only by a 1x1
+// convolution.  The depthwise layer is claimed and recorded at the 1x1 (Fusions::dsconv_dw); match_conv_fusion then builds that convolution's record as it
+// always does - its scale, its sigmoid * product, DSBottleneck's sum - and the record becomes ONE op, OP_DSCONV (kernels/conv_dw_pw.hip).  Depthwise:
+// groups == Cin == Cout (a multiple of 8, up to 1024), k 3 / 5 / 7 with padding k/2, stride 1 or 2, no dilation; its output has no other reader and is
+// no network output.  1x1: stride 1, no padding, one group, Cout a multiple of 8.  fp16 engines only, not kINT8, not with TRTX_DSCONV=0, and only at the
+// widths where the one launch measured faster (conv_dw_pw_worthwhile; TRTX_DSCONV=2 lifts that): anything else keeps the two launches.  A depthwise convolution with a BatchNorm behind it (YOLO11's DWConv, RepVGGDW) is read by a scale layer and never matches.
+void match_dsconv(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (g.opt.dsconv < 1 || g.dt != DT_F16 || net.int8) return;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (f.absorbed[li] || l.kind != L_CONV) continue;
+        const Dims& di = net.tensors[l.inputs[0]].dims;
+        if (!g.spatial(di)) continue;
+        const int64_t C = di.d[di.nb - 3];
+        const int k = l.kernel[0], s = l.stride[0];
+        if (l.kernel[1] != k || (k != 3 && k != 5 && k != 7) || l.stride[1] != s || (s != 1 && s != 2) || l.padding[0] != k / 2 || l.padding[1] != k / 2 ||
+            l.dilation[0] != 1 || l.dilation[1] != 1 || l.groups != C || l.nb_out != C || C % 8 || C > 1024 || !l.w1.empty() ||
+            (int64_t)l.w0.size() != C * k * k)
+            continue;
+        int nx;
+        if (!g.sole_consumer(l.outputs[0], &nx) || f.absorbed[nx]) continue;
+        const LayerDef& p = net.layers[nx];
+        if (p.kind != L_CONV || p.inputs[0] != l.outputs[0] || p.kernel[0] != 1 || p.kernel[1] != 1 || p.stride[0] != 1 || p.stride[1] != 1 || p.padding[0] != 0 ||
+            p.padding[1] != 0 || p.dilation[0] != 1 || p.dilation[1] != 1 || p.groups != 1 || p.nb_out % 8 || (int64_t)p.w0.size() != (int64_t)p.nb_out * C)
+            continue;
+        if (g.opt.dsconv < 2 && !conv_dw_pw_worthwhile((int)C, p.nb_out)) continue;   // two launches measured faster there
+        f.absorbed[li] = true;
+        f.dsconv_dw[nx] = (int)li;
     }
 }
 
@@ -1227,7 +1260,7 @@ bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
 // and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
-// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), the RepVGGDW fold (it claims the 3x3 branch and the sum, and convolution fusion then continues the 7x7 convolution at the sum's output), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), the RepVGGDW fold (it claims the 3x3 branch and the sum, and convolution fusion then continues the 7x7 convolution at the sum's output), DSConv (it claims the depthwise convolution in front of a 1x1 one, whose record convolution fusion then builds as ever), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
@@ -1235,6 +1268,7 @@ Fusions match_fusions(const NetView& g) {
     f.pad_cout.assign(nl, false);
     f.reorg_src.assign(nl, -1);
     f.repdw_at.assign(nl, -1);
+    f.dsconv_dw.assign(nl, -1);
     f.group_at = f.yolo_at = f.attn_at = f.attn_split_at = f.yolo5_at = f.yolo9_at = f.hgconv_at = f.gelu_at = f.softmax_at = f.gated_at = std::vector<int>(nl, -1);
     match_yolo_heads(g, true, f);
     match_yolo_heads(g, false, f);
@@ -1251,6 +1285,7 @@ Fusions match_fusions(const NetView& g) {
     match_gated_add(g, f);
     match_reorg_fold(g, f);
     match_repvggdw_fold(g, f);
+    match_dsconv(g, f);
     match_conv_fusion(g, f);
     match_concat_activation(g, f);
     return f;

@@ -22,6 +22,7 @@ struct FusedConv {
     int out_tensor = -1;  // network tensor the fused op produces
     int emit_at = -1;     // layer index at which the fused op is scheduled
     int fold_conv = -1, fold_scale = -1;   // RepVGGDW (match_repvggdw_fold): the 3x3 depthwise branch and its scale, folded into this 7x7 one's filter
+    int dw_conv = -1;                      // DSConv (match_dsconv): the depthwise convolution in front of this 1x1 one, computed in its launch (OP_DSCONV)
 };
 
 struct YoloHeadFuse {
@@ -119,6 +120,7 @@ struct Fusions {
     std::vector<bool> pad_cout;                // per layer: a detect convolution whose only reader is a fused anchor or DDetect head: its output channels round up to 16 bytes
     std::vector<RepDwFuse> repdws;
     std::vector<int> repdw_at;                 // per layer: the record of a 7x7 depthwise convolution that takes a RepVGGDW's 3x3 branch into its filter, or -1
+    std::vector<int> dsconv_dw;                // per layer: for a 1x1 convolution, the depthwise convolution layer in front of it that match_dsconv claimed, or -1
     std::vector<int> reorg_src;                // per layer: >= 0 for a convolution that absorbed the ReOrg in front of it - the network tensor the four slices read
     std::vector<bool> absorbed;                // per layer: claimed by a fusion (first claim wins), emits nothing of its own
     std::vector<std::pair<int, int>> aliases;  // (dst network tensor, src network tensor): dst is the same data as src

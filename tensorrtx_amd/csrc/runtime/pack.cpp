@@ -160,7 +160,18 @@ bool pack_weights(const Network& net, Plan* plan) {
     }
     for (POp* pop : every) {
         POp& op = *pop;
-        if (op.kind == OP_CONV || op.kind == OP_DECONV) {
+        if (op.kind == OP_DSCONV) {
+            // the depthwise half as conv_dw wants it: fp32 [tap][C] (it has no scale of its own); the 1x1 half is packed below like any convolution's -
+            // the implicit-GEMM layout, which is the fused kernel's too (kernels/conv_dw_pw.hip)
+            const LayerDef& ld = net.layers[op.dw_layer];
+            const int C = op.dw_conv.Cout, taps = op.dw_conv.kh * op.dw_conv.kw;
+            op.dw_off = reserve((size_t)taps * C * 4);
+            float* dst = reinterpret_cast<float*>(blob.data() + op.dw_off);
+            for (int c = 0; c < C; ++c)
+                for (int t = 0; t < taps; ++t) dst[(size_t)t * C + c] = ld.w0[(size_t)c * taps + t];
+            op.bytes += (double)taps * C * 4;
+        }
+        if (op.kind == OP_CONV || op.kind == OP_DECONV || op.kind == OP_DSCONV) {
             const LayerDef& l = net.layers[op.src_layer];
             const ConvArgs& a = op.conv;
             const int cout = a.Cout;

@@ -68,6 +68,9 @@ enum OpKind : int {
     OP_PAD_NHWC,        // IPaddingLayer, zero fill (nhwc_zero_pad): i[0] / i[1] = rows above / columns left of the image; the output tensor's H x W say the rest
     OP_YOLO10_HEAD,     // OP_YOLO_HEAD with YOLOv10's 6-float records and any class count >= 1 (plugins/yolo_decode.hip, trtx_yolov10_head_decode_nhwc): the
                         // same i, at most 5 strides in i[5..9]
+    OP_DSCONV,          // YOLOv13's DSConv, depthwise k x k -> 1x1, as one launch (kernels/conv_dw_pw.hip, conv_dw_pw_or_two_f16): `conv` is the 1x1 with its whole
+                        // epilogue (in[1] = the residual), reading a dense NHWC tensor of the depthwise channels that exists only as the workspace (ws: `mid`, written
+                        // when the fused launch is refused at run time); `dw_conv` / dw_layer the depthwise half, its fp32 tap-major weights at dw_off
 };
 const char* op_kind_name(int k);
 
@@ -144,6 +147,9 @@ struct POp {
     bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one
     int fold_layer = -1, fold_scale = -1;   // >= 0: a 7x7 depthwise convolution that took RepVGGDW's 3x3 branch (match_repvggdw_fold): the network layers
                                // of that branch's convolution and scale; pack_weights adds its scaled filter into the centre and its shift to the shift
+    ConvArgs dw_conv{};        // OP_DSCONV: the depthwise convolution in front of `conv`
+    int dw_layer = -1;         // ... and the network layer that holds its filter
+    size_t dw_off = 0;         // ... packed at this byte offset of the weight blob (fp32 [kh*kw][C])
     int reorg_cin = 0;         // > 0: a convolution that absorbed the ReOrg in front of it (match_reorg_fold): conv is the 2k x 2k stride-2 form over this
                                // many channels and pack_weights re-indexes the layer's k x k filter over 4 x as many (reorg_fold_weights)
     int cout_real = 0;         // > 0: conv.Cout is this channel count rounded up to a 16-byte multiple; the filter rows and biases beyond it are zero

@@ -173,6 +173,38 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
     return op.igemm;
 }
 
+// OP_DSCONV: the strides of the depthwise half, and the 1x1 half set up as choose_conv_kernel sets up a 1x1 over a dense NHWC tensor of the depthwise channels
+// (the workspace `mid`), on the implicit-GEMM kernel: its packed weights are the fused kernel's too (conv_dw_pw_or_two_f16).  False where that kernel does not
+// take the 1x1 (an image of 2 GB).
+bool choose_dsconv_kernels(const Plan& plan, POp& op) {
+    const PTensor& ti = plan.tensors[op.in[0]];
+    const PTensor& to = plan.tensors[op.out[0]];
+    ConvArgs& d = op.dw_conv;
+    d.ld_in = ti.ld;
+    d.ld_out = d.Cout;
+    d.K = d.Kpad = d.kh * d.kw;
+    d.Cout_pad = d.Cout;
+    ConvArgs& a = op.conv;
+    a.ld_in = a.Cin;
+    a.ld_out = to.ld;
+    a.ld_res = op.in.size() > 1 ? plan.tensors[op.in[1]].ld : 0;
+    a.K = a.Kpad = a.Cin;
+    a.Cout_pad = a.Cout;
+    bool vec_out = to.rcoff % 8 == 0 && to.ld % 8 == 0;   // (a slice that starts off a 16-byte boundary: the two launches, element-wise stores)
+    if (op.in.size() > 1) vec_out = vec_out && plan.tensors[op.in[1]].rcoff % 8 == 0 && plan.tensors[op.in[1]].ld % 8 == 0;
+    ConvArgs t = a;
+    t.scalar_out = vec_out ? 0 : 1;
+    t.bn = conv_igemm_pick_bn(t.Cout);
+    t.bk = conv_igemm_pick_bk(t.Cin, 1);
+    t.CinK = conv_igemm_pick_cink(t.Cin, t.bk);
+    t.K = t.CinK;
+    t.Kpad = (t.K + t.bk - 1) / t.bk * t.bk;
+    t.Cout_pad = (t.Cout + t.bn - 1) / t.bn * t.bn;
+    op.igemm = conv_igemm_supported(t);
+    a = t;
+    return op.igemm;
+}
+
 // view geometry (element units: independent of the dtypes assigned next)
 void resolve_view_geometry(Plan& plan) {
     for (auto& t : plan.tensors) {
@@ -350,6 +382,11 @@ void assign_storages(Plan& plan) {
 // convolution kernel selection now that strides/offsets are known, and the bytes each convolution moves
 bool select_conv_kernels(Plan& plan, const PassInputs& e, std::string* err) {
     for (auto& op : plan.ops) {
+        if (op.kind == OP_DSCONV) {   // what the fused launch moves: the input, the output and the residual
+            if (!choose_dsconv_kernels(plan, op)) return fail(err, op.name + ": the 1x1 half of a DSConv cannot take the MFMA path");
+            const ConvArgs &d = op.dw_conv, &a = op.conv;
+            op.bytes = plan.tensors[op.out[0]].nmul * 2.0 * ((double)d.H * d.W * d.Cin + (double)a.Ho * a.Wo * a.Cout * (op.in.size() > 1 ? 2 : 1));
+        }
         if (op.kind != OP_CONV && op.kind != OP_DECONV) continue;
         ConvArgs& a = op.conv;
         const PTensor& ti = plan.tensors[op.in[0]];
@@ -965,7 +1002,7 @@ void plan_arena(Plan& plan, const Ancestors& anc) {
     std::vector<std::pair<int, int>> ws_storage;  // (op, storage)
     for (int k = 0; k < nops; ++k) {
         const int kind = plan.ops[k].kind;
-        if ((kind != OP_PLUGIN && !is_fused_head(kind) && kind != OP_HGCONV) || plan.ops[k].ws_bytes == 0) continue;
+        if ((kind != OP_PLUGIN && !is_fused_head(kind) && kind != OP_HGCONV && kind != OP_DSCONV) || plan.ops[k].ws_bytes == 0) continue;
         Storage s;
         s.kind = ST_ARENA;
         s.bytes = plan.ops[k].ws_bytes;
