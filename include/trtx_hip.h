@@ -549,6 +549,18 @@ int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int ci
 int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out,
                                         int Cout, int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2,
                                         trtx_stream_t stream);
+/* Convolution over channel views that are only 4-byte aligned, on the matrix pipe (tests / tools; kernels/conv_view.hip): groups == 1, k = 1 with pad 0 or
+ * k = 3 with pad 1, stride 1, no dilation; NHWC fp16 in / out / residual, each pointing at the FIRST CHANNEL of its view with its own pixel stride ld_*.
+ * Cin (2 .. 256), Cout, every ld and every channel offset are even: all three base pointers are 4-byte aligned.  Anything else - an odd count, stride or
+ * base, another filter, a Cin above 256 - is TRTX_ERR_UNSUPPORTED with nothing launched; null pointers and non-positive sizes are TRTX_ERR_INVALID.  The
+ * channels beside the view are never read (they may hold NaN) and never written.  wpacked: trtx_conv_pack_weights_f16 with cin_pad = Cin rounded up to 32
+ * (16-byte aligned); bias: Cout floats or NULL.  out = act2(act1(conv + bias) + residual), fp32 accumulation, one fp16 rounding.  These are the layers of
+ * the reference's RepNCSPELAN4 / RepNCSP / RepNBottleneck blocks (yolov9/src/block.cpp) at YOLOv9m's widths: 60- and 90-channel convolutions and the
+ * 180-channel halves of 360-channel tensors.  trtx_conv_view_supported: 1 where the kernel takes such a layer (channel offsets given in channels), else 0. */
+int32_t trtx_conv_view_supported(int N, int H, int W, int Cin, int in_coff, int ld_in, int Cout, int out_coff, int ld_out, int k, int stride, int pad,
+                                 int dilation, int groups, int has_residual, int res_coff, int ld_res);
+int32_t trtx_op_conv2d_view_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out, int Cout,
+                                     int ld_out, int k, int pad, int act1, const void* residual, int ld_res, int act2, trtx_stream_t stream);
 /* Depthwise convolution (tests / tools; kernels/conv_dw.hip: YOLO11's DWConv and the attention's positional conv): groups == C, square k of 3 / 5 / 7 with
  * pad == k / 2, stride 1 or 2, dilation 1 (anything else: TRTX_ERR_UNSUPPORTED, nothing is launched).  dtype: TRTX_DTYPE_FLOAT or TRTX_DTYPE_HALF, the type of
  * in / out / residual, each an NHWC channel slice with its own pixel stride ld_*; the filter is fp32 [k * k][C] (tap-major), bias C floats or NULL, residual

@@ -681,6 +681,28 @@ def conv2d_grouped_nhwc_f16(x, wpacked, bias, cout, groups, k, pad, act1="none",
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- conv over 4-byte aligned channel views (tests / tools)
+def pack_conv_weights_view_f16(w_kcrs, ch_scale=None):
+    """Host: KCRS fp32 numpy [Cout, Cin, k, k] -> packed uint16 [Cout_pad, k * k * CinK] for conv2d_view_nhwc_f16: the implicit-GEMM pack with
+    CinK = Cin rounded up to 32."""
+    return pack_conv_weights_f16(w_kcrs, cin_pad=(w_kcrs.shape[1] + 31) // 32 * 32, ch_scale=ch_scale)[0]
+
+
+def conv2d_view_nhwc_f16(x, wpacked, bias, cout, k, pad, act1="none", residual=None, act2="none", out=None, out_ld=None, status_only=False):
+    """Single launch of the view convolution (kernels/conv_view.hip) on NHWC fp16 tensors; x: [N,H,W,Cin] CUDA half or a channel slice of a wider tensor
+    (its pixel stride is x.stride(2)), residual likewise; out / out_ld: a channel slice of a wider buffer.  status_only: the status instead of raising."""
+    import torch
+    N, H, W, Cin = x.shape
+    if out is None:
+        out = torch.empty((N, H + 2 * pad - k + 1, W + 2 * pad - k + 1, cout), dtype=torch.float16, device=x.device)
+    st = lib().trtx_op_conv2d_view_nhwc_f16(_p(x), N, H, W, Cin, x.stride(2), _p(wpacked), _p(bias), _p(out), cout, out_ld or out.shape[-1], k, pad, ACT[act1],
+                                            _p(residual), residual.stride(2) if residual is not None else 0, ACT[act2], _stream())
+    if status_only:
+        return st
+    check(st, "trtx_op_conv2d_view_nhwc_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- depthwise conv and the attention kernels (tests / tools)
 def conv2d_dw_nhwc(x, w, bias, k, stride, act1="none", residual=None, act2="none", out=None, out_ld=None, alpha1=0.1, alpha2=0.1, pad=None, dilation=1):
     """Single depthwise-convolution launch (kernels/conv_dw.hip) on NHWC fp16 or fp32 tensors.  x: [N,H,W,C] CUDA, or a channel slice of a wider

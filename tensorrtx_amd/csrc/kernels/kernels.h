@@ -251,6 +251,12 @@ int32_t hgconv_f16(const void* x, int ld_x, void* out, int ld_out, int B, int N,
 bool conv_grouped_supported(const ConvArgs& a);
 int conv_grouped_kpad(const ConvArgs& a);
 int32_t conv_grouped(const ConvArgs& a, hipStream_t s);
+// convolution over 4-byte aligned channel views on the matrix pipe (conv_view.hip): fp16, groups == 1, 1x1 pad 0 or 3x3 pad 1, stride 1, no dilation; Cin
+// (2 .. 256), Cout and every channel stride even, whatever pointers are set 4-byte aligned (= even channel offsets).  ld_res != 0 says "there is a residual"
+// where the pointer is not known yet.  Weights: the implicit-GEMM family's fp16 [Cout_pad][Kpad] with CinK = Cin rounded up to 32 and Kpad = kh * kw * CinK
+// (ConvArgs::CinK / Kpad / Cout_pad must say so); bias fp32, Cout values read.  conv_view: TRTX_ERR_UNSUPPORTED outside that, nothing launched.
+bool conv_view_supported(const ConvArgs& a);
+int32_t conv_view(const ConvArgs& a, hipStream_t s);
 // generic transposed convolution, fp32 weights laid out [Cin][kh][kw][Cout/groups]
 int32_t deconv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 

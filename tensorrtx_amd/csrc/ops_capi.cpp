@@ -303,6 +303,48 @@ extern "C" int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H,
     return st;
 }
 
+// --- convolution over 4-byte aligned channel views (kernels/conv_view.hip), test / tool entry points
+static ConvArgs view_args(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int k, int stride, int pad, int dilation, int groups, int ld_res) {
+    ConvArgs a{};
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
+    a.Ho = (H + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
+    a.Wo = (W + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
+    a.Cout = Cout; a.ld_out = ld_out; a.ld_res = ld_res;
+    a.bn = conv_igemm_pick_bn(Cout);
+    a.Cout_pad = (Cout + a.bn - 1) / a.bn * a.bn;
+    a.kh = k; a.kw = k; a.stride_h = stride; a.stride_w = stride; a.pad_h = pad; a.pad_w = pad; a.dil_h = dilation; a.dil_w = dilation;
+    a.groups = groups;
+    a.bk = 32;
+    a.CinK = (Cin + 31) / 32 * 32;
+    a.K = a.Kpad = k * k * a.CinK;
+    a.M = N * a.Ho * a.Wo;
+    a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    return a;
+}
+
+extern "C" int32_t trtx_conv_view_supported(int N, int H, int W, int Cin, int in_coff, int ld_in, int Cout, int out_coff, int ld_out, int k, int stride, int pad,
+                                            int dilation, int groups, int has_residual, int res_coff, int ld_res) {
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || groups < 1 || k < 1 || stride < 1 || pad < 0 || dilation < 1) return 0;
+    if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return 0;
+    if (in_coff < 0 || out_coff < 0 || in_coff % 2 || out_coff % 2 || (has_residual && (res_coff < 0 || res_coff % 2 || ld_res < 1))) return 0;
+    return conv_view_supported(view_args(N, H, W, Cin, ld_in, Cout, ld_out, k, stride, pad, dilation, groups, has_residual ? ld_res : 0)) ? 1 : 0;
+}
+
+extern "C" int32_t trtx_op_conv2d_view_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out,
+                                                int Cout, int ld_out, int k, int pad, int act1, const void* residual, int ld_res, int act2,
+                                                trtx_stream_t stream) {
+    if (!in || !wpacked || !out || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || ld_in < 1 || ld_out < 1 || k < 1 || pad < 0 || (residual && ld_res < 1) ||
+        H + 2 * pad < k || W + 2 * pad < k)
+        return TRTX_ERR_INVALID;
+    ConvArgs a = view_args(N, H, W, Cin, ld_in, Cout, ld_out, k, 1, pad, 1, 1, residual ? ld_res : 0);
+    a.in = in; a.wgt = wpacked; a.bias = bias; a.out = out; a.residual = residual;
+    a.act1 = act1; a.act2 = act2;
+    const int reps = options().op_reps;   // timing tools only
+    int32_t st = TRTX_OK;
+    for (int r = 0; r < reps && st == TRTX_OK; ++r) st = conv_view(a, static_cast<hipStream_t>(stream));
+    return st;
+}
+
 // --- depthwise convolution (kernels/conv_dw.hip) and the two attention kernels (kernels/attention.hip, kernels/attention_mfma.hip), test / tool entry points
 extern "C" int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int H, int W, int C, int ld_in, const float* w_taps_c, const float* bias, void* out,
                                           int ld_out, const void* residual, int ld_res, int k, int stride, int pad, int dilation, int act1, float alpha1,

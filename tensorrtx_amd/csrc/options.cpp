@@ -39,6 +39,7 @@ Options read_options() {
     o.roles = !env_is("TRTX_CONV_ROLES", 0);
     o.f32_mfma = !env_set("TRTX_F32_DIRECT");
     o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
+    o.conv_view = !env_is("TRTX_CONV_VIEW", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.aattn_split = !env_is("TRTX_AATTN_SPLIT", 0);
     o.hgconv = !env_is("TRTX_HGCONV", 0);

@@ -34,7 +34,8 @@ struct Options {
     bool roles = true;           // TRTX_CONV_ROLES=0: no fetching / multiplying wave-role variants among the candidates (fp32 plans)
     bool f32_mfma = true;        // TRTX_F32_DIRECT=1: fp32 engines on the scalar direct kernel of rounds 1-4 (no fp32 MFMA, no fp32 stem kernel)
     bool conv_grouped = true;    // TRTX_CONV_GROUPED=0: grouped (not depthwise) convolutions stay on the scalar direct kernel (no kernels/conv_grouped.hip)
-    bool area_attention = true;  // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
+    bool conv_view = true;       // TRTX_CONV_VIEW=0: groups == 1 convolutions over channel views that are even but no multiple of 8 stay on the scalar direct kernel (no kernels/conv_view.hip)
+    bool area_attention = true; // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
     bool aattn_split = true;     // TRTX_AATTN_SPLIT=0: YOLOv13 area attention (q | k and v from two convolutions) stays on the generic linear path (shuffles, slices, matmul, softmax)
     bool hgconv = true;         // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
     int dsconv = 1;              // TRTX_DSCONV=0: YOLOv13's DSConv (depthwise k x k -> 1x1) stays two launches, conv_dw and the 1x1 (no kernels/conv_dw_pw.hip);

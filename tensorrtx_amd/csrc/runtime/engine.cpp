@@ -285,7 +285,11 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     st = conv_dw(a, op.dtype, stream);
                 else if (op.grouped)
                     st = conv_grouped(a, stream);
-                else
+                else if (op.conv_view) {
+                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
+                    st = conv_view(a, stream);
+                    conv_set_launch_probe(nullptr);
+                } else
                     st = conv_direct(a, op.dtype, stream);
                 break;
             }

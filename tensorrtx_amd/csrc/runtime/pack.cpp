@@ -261,7 +261,7 @@ bool pack_weights(const Network& net, Plan* plan) {
                 op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 4);
                 conv_pack_weights_igemm_f32(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
                                             reinterpret_cast<float*>(blob.data() + op.w_off));
-            } else if (op.igemm) {
+            } else if (op.igemm || op.conv_view) {   // (the view kernel reads the implicit-GEMM layout: kernels/conv_view.hip)
                 op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
                 pack_conv_weights_f16(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
                                       reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
@@ -281,7 +281,7 @@ bool pack_weights(const Network& net, Plan* plan) {
             }
             op.b_off = reserve(bias.size() * 4);
             memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
-            op.bytes += (double)(op.igemm ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (op.grouped ? (size_t)cout * a.Kpad * 2 : (size_t)cout * a.K * 4));
+            op.bytes += (double)(op.igemm || op.conv_view ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (op.grouped ? (size_t)cout * a.Kpad * 2 : (size_t)cout * a.K * 4));
         } else if (head_has_dfl(op.kind)) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);

@@ -68,6 +68,7 @@ std::string Plan::describe_json() const {
               << (op.stem ? 0 : tensors[op.in[0]].nfix);
             if (op.dw) o << ",\"dw\":true";
             if (op.grouped) o << ",\"grouped\":true";
+            if (op.conv_view) o << ",\"view\":true";
             if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
             if (op.reorg_cin) o << ",\"reorg_cin\":" << op.reorg_cin;
             if (op.fold_layer >= 0) o << ",\"repvggdw_fold\":true";

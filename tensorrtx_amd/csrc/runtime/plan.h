@@ -145,6 +145,7 @@ struct POp {
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
     bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
     bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one
+    bool conv_view = false;    // MFMA kernel over 4-byte aligned channel views (kernels/conv_view.hip; weights as the implicit-GEMM family packs them) instead of the direct one
     int fold_layer = -1, fold_scale = -1;   // >= 0: a 7x7 depthwise convolution that took RepVGGDW's 3x3 branch (match_repvggdw_fold): the network layers
                                // of that branch's convolution and scale; pack_weights adds its scaled filter into the centre and its shift to the shift
     ConvArgs dw_conv{};        // OP_DSCONV: the depthwise convolution in front of `conv`

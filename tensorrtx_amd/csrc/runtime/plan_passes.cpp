@@ -170,6 +170,29 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
             a.Kpad = conv_grouped_kpad(a);
         }
     }
+    // groups == 1 over a view whose channel count, offset or stride is even but no multiple of 8 (YOLOv9m's 60- and 90-channel RepNCSP blocks and the
+    // 180-channel halves of its 360-channel tensors; a user's ISliceLayer): kernels/conv_view.hip, after every kernel above has declined.  The weights are
+    // packed as the implicit-GEMM family's with CinK = Cin rounded up to 32.  TRTX_CONV_VIEW=0 leaves such layers on the direct kernel (A/B).
+    op.conv_view = false;
+    if (op.kind == OP_CONV && !op.igemm && !op.dw && !op.grouped && !op.stem && !op.from_deconv && op.extra_in.empty() && e.opt.conv_view && !e.int8 &&
+        !CalibrationLowering::active() && e.dt == DT_F16 && ti.dtype == DT_F16 && to.dtype == DT_F16 && ti.rcoff % 2 == 0 && to.rcoff % 2 == 0) {
+        // only what the implicit-GEMM family declined for its input's alignment: an aligned layer it leaves to the direct kernel (a tiny reduction) stays there
+        bool ok = a.Cin % 8 || ti.rcoff % 8 || ti.ld % 8;
+        if (op.in.size() > 1) {
+            const PTensor& tr = plan.tensors[op.in[1]];
+            ok = ok && tr.dtype == DT_F16 && tr.rcoff % 2 == 0;
+        }
+        ConvArgs t = a;
+        t.bk = 32;
+        t.CinK = (t.Cin + 31) / 32 * 32;
+        t.K = t.Kpad = t.kh * t.kw * t.CinK;
+        t.bn = conv_igemm_pick_bn(t.Cout);
+        t.Cout_pad = (t.Cout + t.bn - 1) / t.bn * t.bn;
+        if (ok && conv_view_supported(t)) {
+            a = t;
+            op.conv_view = true;
+        }
+    }
     return op.igemm;
 }
 
