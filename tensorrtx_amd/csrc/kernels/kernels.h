@@ -40,7 +40,9 @@ enum Wsk : int {
 // first channel of the slice they address and ld_* is the channel stride of the underlying buffer.
 struct ConvArgs {
     const void* in;
-    const void* wgt;    // igemm: fp16 [Cout_pad][Kpad], k = (r*kw+q)*CinK + c.  direct: fp32 [Cout][kh*kw*Cin/groups]
+    const void* wgt;    // one layout per kernel family (runtime/plan.h ConvRoute; runtime/pack.h states each once).  implicit GEMM and view: [Cout_pad][Kpad],
+                        // k = (r*kw+q)*CinK + c, fp16 / int8 / fp32.  grouped: fp16 [Cout][Kpad], k = (r*kw+q)*Cin/groups + c.  direct: fp32 [Cout][kh*kw*Cin/groups].
+                        // depthwise: fp32 [kh*kw][C].  stem: fp32 [(c*kh+r)*kw+q][Cout]
     const float* bias;  // [Cout_pad] (folded BN shift / conv bias) or nullptr
     void* out;
     const void* residual;  // same geometry as out, or nullptr

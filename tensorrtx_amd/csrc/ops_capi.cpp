@@ -40,46 +40,52 @@ extern "C" int32_t trtx_device_count(void) {
     return n;
 }
 
+// The logical part of a single-op launch - geometry, filter, epilogue; pointers null - for the family's conv_layout_*() (runtime/pack.h) to complete
+static ConvArgs conv_geometry(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw, int dilation, int groups,
+                              int act1, int ld_res, int act2) {
+    ConvArgs a{};
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
+    a.Ho = (H + 2 * ph - dilation * (kh - 1) - 1) / sh + 1;
+    a.Wo = (W + 2 * pw - dilation * (kw - 1) - 1) / sw + 1;
+    a.Cout = Cout; a.ld_out = ld_out; a.ld_res = ld_res;
+    a.kh = kh; a.kw = kw; a.stride_h = sh; a.stride_w = sw; a.pad_h = ph; a.pad_w = pw; a.dil_h = dilation; a.dil_w = dilation;
+    a.groups = groups;
+    a.M = N * a.Ho * a.Wo;
+    a.act1 = act1; a.act2 = act2; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    return a;
+}
+
+// the packed layout of a cout x cin_pad x kh x kw filter in the fp16 implicit-GEMM family, at the k-step the single-op launch below takes
+static ConvArgs packed_f16(int cout, int cin_pad, int kh, int kw) {
+    ConvArgs a{};
+    a.Cout = cout; a.Cin = cin_pad; a.kh = kh; a.kw = kw;
+    conv_layout_igemm_f16(&a, conv_igemm_pick_bk(cin_pad, kh * kw));
+    return a;
+}
+
 extern "C" int32_t trtx_conv_packed_dims(int cout, int cin_pad, int kh, int kw, int32_t* cout_pad, int32_t* kpad,
                                          int32_t* bn) {
     if (cout < 1 || cin_pad < 1 || kh < 1 || kw < 1) return TRTX_ERR_INVALID;
-    const int b = conv_igemm_pick_bn(cout);
-    if (bn) *bn = b;
-    if (cout_pad) *cout_pad = (cout + b - 1) / b * b;
-    if (kpad) {
-        const int bk = conv_igemm_pick_bk(cin_pad, kh * kw);
-        *kpad = (kh * kw * conv_igemm_pick_cink(cin_pad, bk) + bk - 1) / bk * bk;
-    }
+    const ConvArgs a = packed_f16(cout, cin_pad, kh, kw);
+    if (bn) *bn = a.bn;
+    if (cout_pad) *cout_pad = a.Cout_pad;
+    if (kpad) *kpad = a.Kpad;
     return TRTX_OK;
 }
 
 extern "C" int32_t trtx_conv_pack_weights_f16(const float* w_kcrs, int cout, int cin, int kh, int kw, int cin_pad,
                                               const float* ch_scale, uint16_t* packed) {
     if (!w_kcrs || !packed || cin_pad < cin) return TRTX_ERR_INVALID;
-    const int bk = conv_igemm_pick_bk(cin_pad, kh * kw);
-    pack_conv_weights_f16(w_kcrs, cout, cin, kh, kw, conv_igemm_pick_cink(cin_pad, bk), bk, ch_scale, packed);
+    const ConvArgs a = packed_f16(cout, cin_pad, kh, kw);
+    pack_conv_weights_f16(w_kcrs, cout, cin, kh, kw, a.CinK, a.Kpad, a.Cout_pad, ch_scale, packed);
     return TRTX_OK;
 }
 
 // geometry of the launch trtx_op_conv2d_nhwc_f16 performs (pointers left null)
 static ConvArgs op_conv_args(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw,
                              int act1, int has_res, int ld_res, int act2) {
-    ConvArgs a{};
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
-    a.Ho = (H + 2 * ph - kh) / sh + 1;
-    a.Wo = (W + 2 * pw - kw) / sw + 1;
-    a.Cout = Cout;
-    a.bn = conv_igemm_pick_bn(Cout);
-    a.Cout_pad = (Cout + a.bn - 1) / a.bn * a.bn;
-    a.ld_out = ld_out; a.ld_res = ld_res;
-    a.kh = kh; a.kw = kw; a.stride_h = sh; a.stride_w = sw; a.pad_h = ph; a.pad_w = pw; a.dil_h = 1; a.dil_w = 1;
-    a.groups = 1;
-    a.bk = conv_igemm_pick_bk(Cin, kh * kw);
-    a.CinK = conv_igemm_pick_cink(Cin, a.bk);
-    a.K = kh * kw * a.CinK;
-    a.Kpad = (a.K + a.bk - 1) / a.bk * a.bk;
-    a.M = N * a.Ho * a.Wo;
-    a.act1 = act1; a.act2 = act2; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, kh, kw, sh, sw, ph, pw, 1, 1, act1, ld_res, act2);
+    conv_layout_igemm_f16(&a, conv_igemm_pick_bk(Cin, kh * kw));
     a.scalar_out = (Cout % 8 || ld_out % 8 || (has_res && ld_res % 8)) ? 1 : 0;
     return a;
 }
@@ -129,17 +135,9 @@ extern "C" int32_t trtx_op_conv2d_nhwc_f16(const void* in, int N, int H, int W, 
 
 // --- the first layer (kernels/conv_stem.hip) and the stem pair in one launch (kernels/conv_stem_pair.hip), test / tool entry points
 static ConvArgs op_stem_args(const float* in, int N, int C, int H, int W, const float* w_taps_cout, const float* bias, int Cout, int k, int stride, int pad, int act) {
-    ConvArgs a{};
+    ConvArgs a = conv_geometry(N, H, W, C, C, Cout, 0, k, k, stride, stride, pad, pad, 1, 1, act, 0, ACT_NONE);
+    conv_layout_unpadded(&a);
     a.in = in; a.wgt = w_taps_cout; a.bias = bias;
-    a.N = N; a.H = H; a.W = W; a.Cin = C; a.ld_in = C;
-    a.Ho = (H + 2 * pad - k) / stride + 1;
-    a.Wo = (W + 2 * pad - k) / stride + 1;
-    a.Cout = Cout; a.Cout_pad = Cout;
-    a.kh = k; a.kw = k; a.stride_h = stride; a.stride_w = stride; a.pad_h = pad; a.pad_w = pad; a.dil_h = 1; a.dil_w = 1;
-    a.groups = 1;
-    a.K = k * k * C; a.Kpad = a.K;
-    a.M = N * a.Ho * a.Wo;
-    a.act1 = act; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
     return a;
 }
 
@@ -205,16 +203,9 @@ static int32_t op_dw_pw(const void* in, int N, int H, int W, int Cin, int ld_in,
         return TRTX_ERR_INVALID;
     const int pad = k / 2;
     if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return TRTX_ERR_INVALID;
-    ConvArgs d{};
+    ConvArgs d = conv_geometry(N, H, W, Cin, ld_in, Cin, Cin, k, k, stride, stride, pad, pad, dilation, Cin, ACT_NONE, 0, ACT_NONE);
+    conv_layout_unpadded(&d);
     d.in = in; d.wgt = w_dw_taps_c; d.bias = bias_dw; d.out = mid;
-    d.N = N; d.H = H; d.W = W; d.Cin = Cin; d.ld_in = ld_in;
-    d.Ho = (H + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
-    d.Wo = (W + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
-    d.Cout = Cin; d.Cout_pad = Cin; d.ld_out = Cin;
-    d.kh = k; d.kw = k; d.stride_h = stride; d.stride_w = stride; d.pad_h = pad; d.pad_w = pad; d.dil_h = dilation; d.dil_w = dilation;
-    d.groups = Cin;
-    d.K = k * k; d.Kpad = d.K;
-    d.M = N * d.Ho * d.Wo;
     ConvArgs p = op_conv_args(N, d.Ho, d.Wo, Cin, Cin, Cout, ld_out, 1, 1, 1, 1, 0, 0, act1, residual != nullptr, ld_res, act2);
     p.in = mid; p.wgt = w_pw_packed; p.bias = bias; p.out = out; p.residual = residual;
     return or_two ? conv_dw_pw_or_two_f16(d, p, mid, static_cast<hipStream_t>(stream)) : conv_dw_pw_f16(d, p, static_cast<hipStream_t>(stream));
@@ -275,9 +266,11 @@ extern "C" int32_t trtx_op_conv_dual_group_or_two_f16(int n, const void* const* 
 extern "C" int32_t trtx_conv_pack_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, const float* ch_scale, uint16_t* packed,
                                                       int32_t* kpad_out) {
     if (!w_kcrs || cout < 1 || cin_g < 1 || kh < 1 || kw < 1) return TRTX_ERR_INVALID;
-    const int kpad = (kh * kw * cin_g + 31) / 32 * 32;
-    if (kpad_out) *kpad_out = kpad;
-    if (packed) pack_conv_weights_grouped_f16(w_kcrs, cout, cin_g, kh, kw, kpad, ch_scale, packed);
+    ConvArgs a{};   // one group's filter
+    a.Cout = cout; a.Cin = cin_g; a.kh = kh; a.kw = kw; a.groups = 1;
+    conv_layout_grouped(&a);
+    if (kpad_out) *kpad_out = a.Kpad;
+    if (packed) pack_conv_weights_grouped_f16(w_kcrs, cout, cin_g, kh, kw, a.Kpad, ch_scale, packed);
     return TRTX_OK;
 }
 
@@ -285,18 +278,9 @@ extern "C" int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H,
                                                    int Cout, int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2,
                                                    trtx_stream_t stream) {
     if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || groups < 1 || k < 1 || pad < 0 || H + 2 * pad < k || W + 2 * pad < k) return TRTX_ERR_INVALID;
-    ConvArgs a{};
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, k, k, 1, 1, pad, pad, 1, groups, act1, ld_res, act2);
+    conv_layout_grouped(&a);
     a.in = in; a.wgt = wpacked; a.bias = bias; a.out = out; a.residual = residual;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
-    a.Ho = H + 2 * pad - k + 1;
-    a.Wo = W + 2 * pad - k + 1;
-    a.Cout = Cout; a.Cout_pad = Cout; a.ld_out = ld_out; a.ld_res = ld_res;
-    a.kh = k; a.kw = k; a.stride_h = 1; a.stride_w = 1; a.pad_h = pad; a.pad_w = pad; a.dil_h = 1; a.dil_w = 1;
-    a.groups = groups;
-    a.K = k * k * (Cin / groups);
-    a.Kpad = conv_grouped_kpad(a);
-    a.M = N * a.Ho * a.Wo;
-    a.act1 = act1; a.act2 = act2; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
     const int reps = options().op_reps;   // timing tools only
     int32_t st = TRTX_OK;
     for (int r = 0; r < reps && st == TRTX_OK; ++r) st = conv_grouped(a, static_cast<hipStream_t>(stream));
@@ -305,20 +289,8 @@ extern "C" int32_t trtx_op_conv2d_grouped_nhwc_f16(const void* in, int N, int H,
 
 // --- convolution over 4-byte aligned channel views (kernels/conv_view.hip), test / tool entry points
 static ConvArgs view_args(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int k, int stride, int pad, int dilation, int groups, int ld_res) {
-    ConvArgs a{};
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
-    a.Ho = (H + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
-    a.Wo = (W + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
-    a.Cout = Cout; a.ld_out = ld_out; a.ld_res = ld_res;
-    a.bn = conv_igemm_pick_bn(Cout);
-    a.Cout_pad = (Cout + a.bn - 1) / a.bn * a.bn;
-    a.kh = k; a.kw = k; a.stride_h = stride; a.stride_w = stride; a.pad_h = pad; a.pad_w = pad; a.dil_h = dilation; a.dil_w = dilation;
-    a.groups = groups;
-    a.bk = 32;
-    a.CinK = (Cin + 31) / 32 * 32;
-    a.K = a.Kpad = k * k * a.CinK;
-    a.M = N * a.Ho * a.Wo;
-    a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, k, k, stride, stride, pad, pad, dilation, groups, ACT_NONE, ld_res, ACT_NONE);
+    conv_layout_view(&a);
     return a;
 }
 
@@ -352,18 +324,10 @@ extern "C" int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int 
     if (!in || !w_taps_c || !out || N < 1 || H < 1 || W < 1 || C < 1 || k < 1 || stride < 1 || pad < 0 || dilation < 1) return TRTX_ERR_INVALID;
     if (dtype != DT_F16 && dtype != DT_F32) return TRTX_ERR_UNSUPPORTED;
     if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return TRTX_ERR_INVALID;
-    ConvArgs a{};
+    ConvArgs a = conv_geometry(N, H, W, C, ld_in, C, ld_out, k, k, stride, stride, pad, pad, dilation, C, act1, ld_res, act2);
+    conv_layout_unpadded(&a);
     a.in = in; a.wgt = w_taps_c; a.bias = bias; a.out = out; a.residual = residual;
-    a.N = N; a.H = H; a.W = W; a.Cin = C; a.ld_in = ld_in;
-    a.Ho = (H + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
-    a.Wo = (W + 2 * pad - dilation * (k - 1) - 1) / stride + 1;
-    a.Cout = C; a.Cout_pad = C; a.ld_out = ld_out; a.ld_res = ld_res;
-    a.kh = k; a.kw = k; a.stride_h = stride; a.stride_w = stride; a.pad_h = pad; a.pad_w = pad; a.dil_h = dilation; a.dil_w = dilation;
-    a.groups = C;
-    a.K = k * k;
-    a.Kpad = a.K;
-    a.M = N * a.Ho * a.Wo;
-    a.act1 = act1; a.act2 = act2; a.alpha1 = alpha1; a.alpha2 = alpha2;
+    a.alpha1 = alpha1; a.alpha2 = alpha2;
     a.f32 = dtype == DT_F32;
     return conv_dw(a, dtype, static_cast<hipStream_t>(stream));
 }
@@ -406,39 +370,32 @@ extern "C" int32_t trtx_op_hgconv_f16(const void* x, int ld_x, void* out, int ld
 // --- fp32 engines: the implicit-GEMM convolution on the fp32 MFMA (kernels/conv_igemm_f32.hip), test / tool entry points
 static ConvArgs op_conv_args_f32(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int kh, int kw, int sh, int sw, int ph, int pw,
                                  int act1, int has_res, int ld_res, int act2) {
-    ConvArgs a{};
-    a.f32 = 1;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in;
-    a.Ho = (H + 2 * ph - kh) / sh + 1;
-    a.Wo = (W + 2 * pw - kw) / sw + 1;
-    a.Cout = Cout;
-    a.Cout_pad = (Cout + 15) / 16 * 16;
-    a.ld_out = ld_out; a.ld_res = ld_res;
-    a.kh = kh; a.kw = kw; a.stride_h = sh; a.stride_w = sw; a.pad_h = ph; a.pad_w = pw; a.dil_h = 1; a.dil_w = 1;
-    a.groups = 1;
-    a.bk = 16;
-    a.CinK = conv_igemm_f32_pick_cink(Cin);
-    a.K = kh * kw * a.CinK;
-    a.Kpad = (a.K + 15) / 16 * 16;
-    a.M = N * a.Ho * a.Wo;
-    a.act1 = act1; a.act2 = act2; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, kh, kw, sh, sw, ph, pw, 1, 1, act1, ld_res, act2);
+    conv_layout_igemm_f32(&a);
     a.scalar_out = (Cout % 4 || ld_out % 4 || (has_res && ld_res % 4)) ? 1 : 0;
+    return a;
+}
+
+static ConvArgs packed_f32(int cout, int cin_pad, int kh, int kw) {
+    ConvArgs a{};
+    a.Cout = cout; a.Cin = cin_pad; a.kh = kh; a.kw = kw;
+    conv_layout_igemm_f32(&a);
     return a;
 }
 
 extern "C" int32_t trtx_conv_packed_dims_f32(int cout, int cin_pad, int kh, int kw, int32_t* cout_pad, int32_t* kpad, int32_t* cink) {
     if (cout < 1 || cin_pad < 1 || kh < 1 || kw < 1) return TRTX_ERR_INVALID;
-    const int ck = conv_igemm_f32_pick_cink(cin_pad);
-    if (cout_pad) *cout_pad = (cout + 15) / 16 * 16;
-    if (kpad) *kpad = (kh * kw * ck + 15) / 16 * 16;
-    if (cink) *cink = ck;
+    const ConvArgs a = packed_f32(cout, cin_pad, kh, kw);
+    if (cout_pad) *cout_pad = a.Cout_pad;
+    if (kpad) *kpad = a.Kpad;
+    if (cink) *cink = a.CinK;
     return TRTX_OK;
 }
 
 extern "C" int32_t trtx_conv_pack_weights_f32(const float* w_kcrs, int cout, int cin, int kh, int kw, int cin_pad, const float* ch_scale, float* packed) {
     if (!w_kcrs || !packed || cin_pad < cin) return TRTX_ERR_INVALID;
-    const int ck = conv_igemm_f32_pick_cink(cin_pad);
-    conv_pack_weights_igemm_f32(w_kcrs, cout, cin, kh, kw, ck, (kh * kw * ck + 15) / 16 * 16, (cout + 15) / 16 * 16, ch_scale, packed);
+    const ConvArgs a = packed_f32(cout, cin_pad, kh, kw);
+    conv_pack_weights_igemm_f32(w_kcrs, cout, cin, kh, kw, a.CinK, a.Kpad, a.Cout_pad, ch_scale, packed);
     return TRTX_OK;
 }
 
@@ -484,11 +441,12 @@ extern "C" int32_t trtx_op_conv2d_nhwc_f32(const void* in, int N, int H, int W, 
 extern "C" int32_t trtx_conv_pack_weights_i8(const float* w_kcrs, int cout, int cin, int kh, int kw, const float* ch_scale, int8_t* packed,
                                              float* wscale_out, int32_t* cout_pad_out, int32_t* kpad_out) {
     if (!w_kcrs || cout < 1 || cin < 1) return TRTX_ERR_INVALID;
-    const int bn = conv_igemm_pick_bn(cout);
-    const int cout_pad = (cout + bn - 1) / bn * bn, cink = (cin + 63) / 64 * 64, kpad = kh * kw * cink;
-    if (cout_pad_out) *cout_pad_out = cout_pad;
-    if (kpad_out) *kpad_out = kpad;
-    if (packed && wscale_out) conv_pack_weights_i8(w_kcrs, cout, cin, kh, kw, cink, ch_scale, cout_pad, kpad, packed, wscale_out);
+    ConvArgs a{};
+    a.Cout = cout; a.Cin = cin; a.kh = kh; a.kw = kw;
+    conv_layout_igemm_i8(&a);   // (CinK and Kpad in 2-byte units)
+    if (cout_pad_out) *cout_pad_out = a.Cout_pad;
+    if (kpad_out) *kpad_out = a.Kpad * 2;
+    if (packed && wscale_out) conv_pack_weights_i8(w_kcrs, cout, cin, kh, kw, a.CinK * 2, ch_scale, a.Cout_pad, a.Kpad * 2, packed, wscale_out);
     return TRTX_OK;
 }
 
@@ -498,27 +456,11 @@ extern "C" int32_t trtx_op_conv2d_nhwc_i8(const void* in, int N, int H, int W, i
                                           int kw, int sh, int sw, int ph, int pw, int act1, const void* residual, int res_is_i8,
                                           float res_scale, int ld_res, int act2, trtx_stream_t stream) {
     if (Cin % 16 || ld_in % 16) return TRTX_ERR_INVALID;
-    ConvArgs a{};
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, kh, kw, sh, sw, ph, pw, 1, 1, act1, ld_res, act2);
+    conv_layout_igemm_i8(&a);   // (the input-side geometry in 2-byte units: pairs of int8 channels)
     a.in = in; a.wgt = wpacked; a.bias = bias; a.out = out; a.residual = residual;
-    a.N = N; a.H = H; a.W = W;
-    a.Ho = (H + 2 * ph - kh) / sh + 1;
-    a.Wo = (W + 2 * pw - kw) / sw + 1;
-    a.Cout = Cout;
-    a.bn = conv_igemm_pick_bn(Cout);
-    a.Cout_pad = (Cout + a.bn - 1) / a.bn * a.bn;
-    a.ld_out = ld_out; a.ld_res = ld_res;
-    a.kh = kh; a.kw = kw; a.stride_h = sh; a.stride_w = sw; a.pad_h = ph; a.pad_w = pw; a.dil_h = 1; a.dil_w = 1; a.groups = 1;
-    a.bk = 32;
-    const int cink = (Cin + 63) / 64 * 64;
-    a.in_i8 = 1; a.out_i8 = out_is_i8; a.res_i8 = res_is_i8;
+    a.out_i8 = out_is_i8; a.res_i8 = res_is_i8;
     a.cscale = cscale; a.out_inv_scale = out_inv_scale; a.res_scale = res_scale;
-    // input-side geometry in 2-byte units (pairs of int8 channels)
-    a.Cin = Cin / 2; a.ld_in = ld_in / 2; a.CinK = cink / 2;
-    a.K = kh * kw * a.CinK;
-    a.Kpad = a.K;
-    a.M = N * a.Ho * a.Wo;
-    a.act1 = act1; a.act2 = act2; a.alpha1 = 0.1f; a.alpha2 = 0.1f;
-    a.scalar_out = 0;
     if (Cout % 8 || ld_out % 8 || (residual && ld_res % 8)) return TRTX_ERR_UNSUPPORTED;
     return conv_igemm_f16(a, stream);
 }

@@ -107,6 +107,16 @@ int32_t run_head(const HeadOp& h, const POp& op, const Resolver& R, int batch, b
     return h.stride_decode[f32](in.p, in.ld, nl, images, op.i[0], op.i[1], op.i[2], &op.i[5], dfl, op.i[3], out, ws, op.ws_bytes, stream);
 }
 
+// The calling thread's launch probe for the lifetime of the object; nothing is set for no probe or one without its events
+struct ScopedLaunchProbe {
+    explicit ScopedLaunchProbe(LaunchProbe* p) {
+        if (p && p->start && p->stop) conv_set_launch_probe(p);
+    }
+    ~ScopedLaunchProbe() { conv_set_launch_probe(nullptr); }
+    ScopedLaunchProbe(const ScopedLaunchProbe&) = delete;
+    ScopedLaunchProbe& operator=(const ScopedLaunchProbe&) = delete;
+};
+
 // add the runtime batch as outermost dimension of a per-sample strided view
 StridedView batch_view(const StridedView& v, int batch, long bs_in, long bs_in2) {
     StridedView o{};
@@ -148,7 +158,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         probes.resize(plan.ops.size());
         if (!no_probe && !c->tuning)  // the tactic timing keeps its own clock (the interval between the stream events)
             for (size_t k = 0; k < plan.ops.size(); ++k)
-                if ((plan.ops[k].kind == OP_CONV && plan.ops[k].igemm) || plan.ops[k].kind == OP_CONV_GROUP)
+                if ((plan.ops[k].kind == OP_CONV && plan.ops[k].route == ROUTE_IGEMM) || plan.ops[k].kind == OP_CONV_GROUP)
                     if (hipEventCreate(&probes[k].start) != hipSuccess || hipEventCreate(&probes[k].stop) != hipSuccess) (void)hipGetLastError();
         TRTX_HIP_TRY(hipEventRecord(evs[0], stream));
     }
@@ -188,7 +198,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
     auto defers_to_next = [&](size_t k) {
         if (c->observer || c->tuning || k + 1 >= plan.ops.size()) return false;
         const POp &o = plan.ops[k], &nx = plan.ops[k + 1];
-        return nx.bneck_pair && nx.kind == OP_CONV && o.kind == OP_CONV && o.igemm && nx.lane == o.lane && nx.in[0] == o.out[0];
+        return nx.bneck_pair && nx.kind == OP_CONV && o.kind == OP_CONV && o.route == ROUTE_IGEMM && nx.lane == o.lane && nx.in[0] == o.out[0];
     };
     // The sibling pair (POp::sibling_pair on op k + 1; the dual tile of kernels/igemm_tile.h): the same shape - the first group launches nothing and the marked
     // group issues both, as one launch where conv_dual_group_or_two_f16 takes the run-time pointers and as today's two otherwise.  Camera-frame contexts keep one
@@ -215,97 +225,81 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
         const PTensor& t0 = plan.tensors[op.in.empty() ? op.out[0] : op.in[0]];
         const PTensor& to = plan.tensors[op.out[0]];
         auto nb = [&](const PTensor& t) { return (t.nfix ? t.nfix : batch) * t.nmul; };
+        // a convolution's arguments as its kernel takes them: the plan's geometry at this batch, and the pointers of this enqueue (a member of a grouped
+        // launch is a complete convolution record too)
+        auto bind = [&](const POp& o) {
+            ConvArgs a = conv_args_at(plan, o, batch);
+            a.in = R.ptr(o.in[0]);
+            a.out = R.ptr(o.out[0]);
+            a.residual = o.in.size() > 1 ? R.ptr(o.in[1]) : nullptr;
+            a.up_in = o.extra_in.empty() ? nullptr : R.ptr(o.extra_in[0]);   // folded upsample: the half-resolution source
+            a.wgt = W + o.w_off;
+            a.bias = reinterpret_cast<const float*>(W + o.b_off);
+            a.cscale = a.in_i8 ? reinterpret_cast<const float*>(W + o.s_off) : nullptr;
+            return a;
+        };
+        LaunchProbe* const probe = prof ? &probes[k] : nullptr;   // (events only where a dispatch is measured: see above)
         int32_t st = TRTX_OK;
         const bool skip = c->tuning && (op.kind == OP_PLUGIN || is_fused_head(op.kind) || op.kind == OP_ROI_ALIGN);
         if (!skip) switch (op.kind) {
             case OP_CONV:
             case OP_DECONV: {
-                ConvArgs a = op.conv;
-                a.in = R.ptr(op.in[0]);
-                a.out = R.ptr(op.out[0]);
-                a.residual = op.in.size() > 1 ? R.ptr(op.in[1]) : nullptr;
-                a.up_in = op.extra_in.empty() ? nullptr : R.ptr(op.extra_in[0]);   // folded upsample: the half-resolution source
-                a.wgt = W + op.w_off;
-                a.bias = reinterpret_cast<const float*>(W + op.b_off);
-                a.cscale = a.in_i8 ? reinterpret_cast<const float*>(W + op.s_off) : nullptr;
-                // (the stem reads the LINEAR network input: in an explicit-batch plan its leading dimension is the image count)
-                a.N = op.stem ? (plan.explicit_batch ? (int)t0.dims.d[0] : batch) : nb(t0);
-                a.M = a.N * a.Ho * a.Wo;
+                const ConvArgs a = bind(op);
                 // The stem pair (POp::stem_pair on the next op; kernels/conv_stem_pair.hip): the stem launches nothing, the marked op issues the one fused
                 // launch from the stem's arguments and its own - so its profile row carries the launch and the stem's reports 0.  Camera frames and the
                 // calibration observer (which reads the tensor between the two) keep the two launches, as does a pointer the kernel cannot take - and the tactic
                 // timing (tune.cpp), so that the marked op still gets a timed tactic of its own for those launches.
-                if (op.stem && !c->frames && !c->observer && !c->tuning && k + 1 < plan.ops.size() && plan.ops[k + 1].stem_pair && plan.ops[k + 1].lane == op.lane) {
-                    const POp& nx = plan.ops[k + 1];
-                    ConvArgs b = nx.conv;
-                    b.out = R.ptr(nx.out[0]);
-                    b.wgt = W + nx.w_off;
-                    b.bias = reinterpret_cast<const float*>(W + nx.b_off);
-                    b.N = nb(to);
-                    b.M = b.N * b.Ho * b.Wo;
-                    if (conv_stem_pair_possible(a, b)) {
-                        pair_stem = a;
-                        pair_pending = true;
-                        break;
-                    }
+                const bool stem = op.route == ROUTE_STEM;
+                if (stem && !c->frames && !c->observer && !c->tuning && k + 1 < plan.ops.size() && plan.ops[k + 1].stem_pair && plan.ops[k + 1].lane == op.lane &&
+                    conv_stem_pair_possible(a, bind(plan.ops[k + 1]))) {
+                    pair_stem = a;
+                    pair_pending = true;
+                    break;
                 }
                 if (op.stem_pair && pair_pending) {
                     pair_pending = false;
-                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
+                    ScopedLaunchProbe probed(probe);
                     st = conv_stem_pair_f16(pair_stem, a, stream);
-                    conv_set_launch_probe(nullptr);
                     break;
                 }
                 if (defers_to_next(k)) break;   // the first convolution of a bottleneck pair: issued by the marked op behind it
                 if (op.bneck_pair && k > 0 && defers_to_next(k - 1)) {   // ... here: its profile row carries the launch and the first op's reports 0
-                    const POp& fo = plan.ops[k - 1];
-                    ConvArgs f = fo.conv;
-                    f.in = R.ptr(fo.in[0]);
-                    f.out = R.ptr(fo.out[0]);
-                    f.wgt = W + fo.w_off;
-                    f.bias = reinterpret_cast<const float*>(W + fo.b_off);
-                    f.N = nb(plan.tensors[fo.in[0]]);
-                    f.M = f.N * f.Ho * f.Wo;
-                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
-                    st = conv_bneck_pair_or_two_f16(f, a, stream);
-                    conv_set_launch_probe(nullptr);
+                    ScopedLaunchProbe probed(probe);
+                    st = conv_bneck_pair_or_two_f16(bind(plan.ops[k - 1]), a, stream);
                     break;
                 }
-                if (op.kind == OP_DECONV)
+                if (op.kind == OP_DECONV) {
                     st = deconv_direct(a, op.dtype, stream);
-                else if (op.stem && c->frames)
-                    st = a.f32 ? TRTX_ERR_UNSUPPORTED : conv_stem_frames_f32(a, c->frames, stream);   // letterbox fused into the stem (trtx_context_enqueue_frames; kFP16 engines)
-                else if (op.stem)
-                    st = a.f32 ? conv_stem_nchw_f32_out_f32(a, stream) : conv_stem_nchw_f32(a, stream);
-                else if (op.igemm) {
-                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
-                    st = a.f32 ? conv_igemm_f32(a, stream) : conv_igemm_f16(a, stream);
-                    conv_set_launch_probe(nullptr);
-                } else if (op.dw)
-                    st = conv_dw(a, op.dtype, stream);
-                else if (op.grouped)
-                    st = conv_grouped(a, stream);
-                else if (op.conv_view) {
-                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
-                    st = conv_view(a, stream);
-                    conv_set_launch_probe(nullptr);
-                } else
-                    st = conv_direct(a, op.dtype, stream);
+                    break;
+                }
+                switch (op.route) {
+                    case ROUTE_STEM:
+                        if (c->frames)
+                            st = a.f32 ? TRTX_ERR_UNSUPPORTED : conv_stem_frames_f32(a, c->frames, stream);   // letterbox fused into the stem (trtx_context_enqueue_frames; kFP16 engines)
+                        else
+                            st = a.f32 ? conv_stem_nchw_f32_out_f32(a, stream) : conv_stem_nchw_f32(a, stream);
+                        break;
+                    case ROUTE_IGEMM: {
+                        ScopedLaunchProbe probed(probe);
+                        st = a.f32 ? conv_igemm_f32(a, stream) : conv_igemm_f16(a, stream);
+                        break;
+                    }
+                    case ROUTE_DW: st = conv_dw(a, op.dtype, stream); break;
+                    case ROUTE_GROUPED: st = conv_grouped(a, stream); break;
+                    case ROUTE_VIEW: st = conv_view(a, stream); break;
+                    case ROUTE_DIRECT: st = conv_direct(a, op.dtype, stream); break;
+                }
                 break;
             }
             case OP_DSCONV: {   // depthwise k x k -> 1x1: the one fused launch where the kernel takes the run-time pointers, the two launches through the workspace otherwise
                 void* mid = static_cast<char*>(c->d_arena) + op.ws_off;
-                ConvArgs d = op.dw_conv, a = op.conv;
-                d.in = R.ptr(op.in[0]);
+                ConvArgs a = bind(op), d = op.dw_conv;
+                d.in = a.in;
                 d.wgt = W + op.dw_off;
                 d.out = mid;
                 a.in = mid;
-                a.out = R.ptr(op.out[0]);
-                a.residual = op.in.size() > 1 ? R.ptr(op.in[1]) : nullptr;
-                a.wgt = W + op.w_off;
-                a.bias = reinterpret_cast<const float*>(W + op.b_off);
-                d.N = a.N = nb(t0);
-                d.M = a.M = a.N * a.Ho * a.Wo;
+                d.N = a.N;
+                d.M = a.M;
                 st = op.i[0] ? conv_dw_pw_f16(d, a, stream) : TRTX_ERR_UNSUPPORTED;   // (i[0]: a plan lowered with TRTX_DSCONV=2 fuses beyond the measured widths)
                 if (st == TRTX_ERR_UNSUPPORTED || st == TRTX_ERR_INVALID) st = conv_dw_pw_or_two_f16(d, a, mid, stream);
                 break;
@@ -315,25 +309,13 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 const int gn = (int)op.group.size();
                 if (gn < 2 || gn > kMaxConvGroup) { st = TRTX_ERR_STATE; break; }
                 if (group_defers_to_next(k)) break;   // the first group of a sibling pair: issued by the marked op behind it
-                auto member_args = [&](const POp& mo, ConvArgs& a) {
-                    a = mo.conv;
-                    a.in = R.ptr(mo.in[0]);
-                    a.out = R.ptr(mo.out[0]);
-                    a.residual = mo.in.size() > 1 ? R.ptr(mo.in[1]) : nullptr;
-                    a.up_in = nullptr;
-                    a.wgt = W + mo.w_off;
-                    a.bias = reinterpret_cast<const float*>(W + mo.b_off);
-                    a.cscale = a.in_i8 ? reinterpret_cast<const float*>(W + mo.s_off) : nullptr;
-                    a.N = nb(plan.tensors[mo.in[0]]);
-                    a.M = a.N * a.Ho * a.Wo;
-                };
-                for (int m = 0; m < gn; ++m) member_args(op.group[m], ga[m]);
+                for (int m = 0; m < gn; ++m) ga[m] = bind(op.group[m]);
                 if (op.sibling_pair && k > 0 && group_defers_to_next(k - 1)) {   // ... here: its profile row carries the launch and the first group's reports 0
                     const POp& fo = plan.ops[k - 1];
                     ConvArgs fa[kMaxConvGroup], sa[kMaxConvGroup];   // the first group's members, and this group's in the order of the tensors those read
                     bool paired = true;
                     for (int m = 0; m < gn; ++m) {
-                        member_args(fo.group[m], fa[m]);
+                        fa[m] = bind(fo.group[m]);
                         int q = 0;
                         while (q < gn && op.group[q].in[0] != fo.group[m].in[0]) ++q;
                         if (q == gn) { paired = false; break; }
@@ -341,14 +323,14 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     }
                     if (!paired) { st = TRTX_ERR_STATE; break; }
                     const bool first64 = fa[0].bn == 64;   // the dual tile's first side is the 64-wide one
-                    if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
+                    ScopedLaunchProbe probed(probe);
                     st = conv_dual_group_or_two_f16(first64 ? fa : sa, first64 ? sa : fa, gn, stream);
-                    conv_set_launch_probe(nullptr);
                     break;
                 }
-                if (prof && probes[k].start && probes[k].stop) conv_set_launch_probe(&probes[k]);
-                st = conv_igemm_group_f16(ga, gn, stream);
-                conv_set_launch_probe(nullptr);
+                {
+                    ScopedLaunchProbe probed(probe);
+                    st = conv_igemm_group_f16(ga, gn, stream);
+                }
                 if (st == TRTX_ERR_UNSUPPORTED) {   // a batch at which the members no longer share an instantiation: one launch each, same bits
                     st = TRTX_OK;
                     for (int m = 0; m < gn && st == TRTX_OK; ++m) st = conv_igemm_f16(ga[m], stream);
@@ -894,7 +876,7 @@ extern "C" int32_t trtx_context_enqueue_frames(trtx_context* c, int32_t batch, c
     int stem = -1, n_in = 0;
     for (size_t b = 0; b < plan.binding_is_input.size(); ++b) n_in += plan.binding_is_input[b] ? 1 : 0;
     for (size_t k = 0; k < plan.ops.size() && stem < 0; ++k)
-        if (plan.ops[k].kind == OP_CONV && plan.ops[k].stem) stem = (int)k;
+        if (plan.ops[k].kind == OP_CONV && plan.ops[k].route == ROUTE_STEM) stem = (int)k;
     if (n_in != 1 || stem < 0 || plan.ops[stem].conv.Cin != 3) return TRTX_ERR_UNSUPPORTED;
     if (plan.ops[stem].conv.f32) return TRTX_ERR_UNSUPPORTED;   // fp32 engines have a stem op too (round 5) but no fused-letterbox form of it: rejected before anything is enqueued
     for (size_t k = 0; k < plan.ops.size(); ++k)   // nothing else may read the input tensor

@@ -366,7 +366,7 @@ struct Lowerer {
         op.fold_layer = c.fold_conv;
         op.fold_scale = c.fold_scale;
         if (c.fold_conv >= 0) op.name += " [RepVGGDW folded]";
-        op.stem = stem;
+        op.route = stem ? ROUTE_STEM : ROUTE_DIRECT;
         ConvArgs& a = op.conv;
         const PTensor& to = plan.tensors[out];
         a.H = ti.H;

@@ -23,11 +23,70 @@ float f16_bits_to_f32(uint16_t u) {
     return (float)h;
 }
 
-void pack_conv_weights_f16(const float* w, int cout, int cin, int kh, int kw, int cin_pad, int bk, const float* ch_scale,
+static int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// the column tile of the fp16 / int8 implicit-GEMM family and the view kernel: rows padded to whole tiles
+static void layout_column_tiles(ConvArgs* a) {
+    a->bn = conv_igemm_pick_bn(a->Cout);
+    a->Cout_pad = round_up(a->Cout, a->bn);
+}
+
+void conv_layout_igemm_f16(ConvArgs* a, int bk) {
+    layout_column_tiles(a);
+    a->bk = bk;
+    a->CinK = conv_igemm_pick_cink(a->Cin, bk);  // a k-step never straddles a filter tap
+    a->K = a->kh * a->kw * a->CinK;
+    a->Kpad = round_up(a->K, bk);
+}
+
+void conv_layout_igemm_i8(ConvArgs* a) {
+    layout_column_tiles(a);
+    a->in_i8 = 1;
+    a->bk = 32;
+    a->CinK = round_up(a->Cin, 64) / 2;
+    a->Cin /= 2;
+    a->ld_in /= 2;
+    a->K = a->Kpad = a->kh * a->kw * a->CinK;
+}
+
+void conv_layout_igemm_f32(ConvArgs* a) {
+    a->f32 = 1;
+    a->bk = 16;
+    a->bn = a->bm = 0;
+    a->CinK = conv_igemm_f32_pick_cink(a->Cin);
+    a->K = a->kh * a->kw * a->CinK;
+    a->Kpad = round_up(a->K, 16);
+    a->Cout_pad = round_up(a->Cout, 16);
+}
+
+void conv_layout_view(ConvArgs* a) {
+    layout_column_tiles(a);
+    a->bk = 32;
+    a->CinK = round_up(a->Cin, 32);
+    a->K = a->Kpad = a->kh * a->kw * a->CinK;
+}
+
+void conv_layout_unpadded(ConvArgs* a) {
+    a->K = a->Kpad = a->kh * a->kw * (a->Cin / a->groups);
+    a->Cout_pad = a->Cout;
+}
+
+void conv_layout_grouped(ConvArgs* a) {
+    conv_layout_unpadded(a);
+    a->Kpad = conv_grouped_kpad(*a);   // K rounded up to 32 (kernels/conv_grouped.hip)
+}
+
+size_t conv_packed_weight_bytes(ConvRoute route, const ConvArgs& a) {
+    switch (route) {
+        case ROUTE_IGEMM:
+        case ROUTE_VIEW: return (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2);   // (int8: Kpad counts 2-byte units)
+        case ROUTE_GROUPED: return (size_t)a.Cout * a.Kpad * 2;
+        default: return (size_t)a.Cout * a.K * 4;
+    }
+}
+
+void pack_conv_weights_f16(const float* w, int cout, int cin, int kh, int kw, int cin_pad, int kpad, int cout_pad, const float* ch_scale,
                            uint16_t* packed) {
-    const int bn = conv_igemm_pick_bn(cout);
-    const int cout_pad = (cout + bn - 1) / bn * bn;
-    const int kpad = (kh * kw * cin_pad + bk - 1) / bk * bk;  // cin_pad = per-tap K stride (CinK); rows padded to the k-step
     memset(packed, 0, sizeof(uint16_t) * (size_t)cout_pad * kpad);
     for (int co = 0; co < cout; ++co) {
         const float sc = ch_scale ? ch_scale[co] : 1.0f;
@@ -212,76 +271,80 @@ bool pack_weights(const Network& net, Plan* plan) {
                 std::fill(sc.begin(), sc.end(), 1.f);
                 w0 = w0_padded.data();
             }
+            if (op.from_deconv) {
+                // CKRS [Cin][Cout][kh][kw] -> KCRS of the stand-in 1x1 conv: output channel (r*kw + q)*Cout + co.  The re-layout
+                // (and the per-sub-position bias) does not depend on which conv kernel runs the stand-in: the kernel choice may refuse
+                // the MFMA path (kh*kw*Cin < 32, > 2 GB images) and the direct kernel must then see the same KCRS weights.
+                const int taps = l.kernel[0] * l.kernel[1], dc = l.nb_out;
+                w0_padded.resize((size_t)cout * cin_logical);
+                for (int ci = 0; ci < cin_logical; ++ci)
+                    for (int co = 0; co < dc; ++co)
+                        for (int t = 0; t < taps; ++t) w0_padded[(size_t)(t * dc + co) * cin_logical + ci] = l.w0[((size_t)ci * dc + co) * taps + t];
+                for (int c = 0; c < cout; ++c) bias[c] = l.w1.empty() ? 0.f : l.w1[c % dc];
+                w0 = w0_padded.data();
+            }
             if (cout_real < cout) {
                 if (w0_padded.empty()) w0_padded = l.w0;
                 w0_padded.resize((size_t)cout * a.kh * a.kw * (cin_logical / a.groups), 0.f);
                 w0 = w0_padded.data();
             }
+            // the fp32 layouts hold the filter itself, re-ordered: sized by the layer's own channel count, which their packers walk
+            const int cin_g = cin_logical / a.groups;
+            const size_t filter_bytes = (size_t)cout * a.kh * a.kw * cin_g * 4;
             if (op.kind == OP_DECONV) {
-                op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
+                op.w_off = reserve(filter_bytes);
                 pack_deconv_weights_f32(l.w0.data(), cin_logical, cout, a.groups, a.kh, a.kw,
                                         reinterpret_cast<float*>(blob.data() + op.w_off));
-            } else if (op.stem) {
-                // [tap = (c*kh + r)*kw + q][cout], BN scale folded
-                op.w_off = reserve((size_t)a.kh * a.kw * cin_logical * cout * 4);
-                float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
-                for (int co = 0; co < cout; ++co)
-                    for (int t = 0; t < cin_logical * a.kh * a.kw; ++t)
-                        dst[(size_t)t * cout + co] = w0[(size_t)co * cin_logical * a.kh * a.kw + t] * sc[co];
-            } else if (op.from_deconv) {
-                // CKRS [Cin][Cout][kh][kw] -> KCRS of the stand-in 1x1 conv: output channel (r*kw + q)*Cout + co.  The re-layout
-                // (and the per-sub-position bias) does not depend on which conv kernel runs the stand-in: the kernel choice may refuse
-                // the MFMA path (kh*kw*Cin < 32, > 2 GB images) and the direct kernel must then see the same KCRS weights.
-                const int taps = l.kernel[0] * l.kernel[1], dc = l.nb_out;
-                std::vector<float> w2((size_t)cout * cin_logical);
-                for (int ci = 0; ci < cin_logical; ++ci)
-                    for (int co = 0; co < dc; ++co)
-                        for (int t = 0; t < taps; ++t) w2[(size_t)(t * dc + co) * cin_logical + ci] = l.w0[((size_t)ci * dc + co) * taps + t];
-                for (int c = 0; c < cout; ++c) bias[c] = l.w1.empty() ? 0.f : l.w1[c % dc];
-                if (op.igemm) {
-                    op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
-                    pack_conv_weights_f16(w2.data(), cout, cin_logical, 1, 1, a.CinK, a.bk, sc.data(),
-                                          reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
-                } else {
-                    op.w_off = reserve((size_t)cout * cin_logical * 4);
-                    pack_conv_weights_f32(w2.data(), cout, cin_logical, 1, 1, sc.data(), reinterpret_cast<float*>(blob.data() + op.w_off));
+            } else switch (op.route) {
+                case ROUTE_STEM: {
+                    // [tap = (c*kh + r)*kw + q][cout], BN scale folded
+                    op.w_off = reserve(filter_bytes);
+                    float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
+                    for (int co = 0; co < cout; ++co)
+                        for (int t = 0; t < cin_logical * a.kh * a.kw; ++t)
+                            dst[(size_t)t * cout + co] = w0[(size_t)co * cin_logical * a.kh * a.kw + t] * sc[co];
+                    break;
                 }
-            } else if (op.igemm && a.in_i8) {
-                // int8 weights, per-output-channel scales; cscale[c] = input tensor scale * weight scale (dequantises the int32 sums)
-                const size_t kpad_bytes = (size_t)a.Kpad * 2;
-                op.w_off = reserve((size_t)a.Cout_pad * kpad_bytes);
-                std::vector<float> wscale(a.Cout_pad, 1.f);
-                conv_pack_weights_i8(w0, cout, cin_logical, a.kh, a.kw, a.CinK * 2, sc.data(), a.Cout_pad, (int)kpad_bytes,
-                                     reinterpret_cast<int8_t*>(blob.data() + op.w_off), wscale.data());
-                const float s_in = plan->tensors[op.in[0]].scale;
-                for (float& v : wscale) v *= s_in;
-                op.s_off = reserve(wscale.size() * 4);
-                memcpy(blob.data() + op.s_off, wscale.data(), wscale.size() * 4);
-            } else if (op.igemm && a.f32) {
-                op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 4);
-                conv_pack_weights_igemm_f32(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
-                                            reinterpret_cast<float*>(blob.data() + op.w_off));
-            } else if (op.igemm || op.conv_view) {   // (the view kernel reads the implicit-GEMM layout: kernels/conv_view.hip)
-                op.w_off = reserve((size_t)a.Cout_pad * a.Kpad * 2);
-                pack_conv_weights_f16(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.bk, sc.data(),
-                                      reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
-            } else if (op.grouped) {
-                op.w_off = reserve((size_t)cout * a.Kpad * 2);
-                pack_conv_weights_grouped_f16(w0, cout, cin_logical / a.groups, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
-            } else if (op.dw) {
-                // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load
-                op.w_off = reserve((size_t)a.kh * a.kw * cout * 4);
-                float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
-                for (int co = 0; co < cout; ++co)
-                    for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = w0[(size_t)co * a.kh * a.kw + t] * sc[co];
-            } else {
-                op.w_off = reserve((size_t)cout * a.kh * a.kw * (cin_logical / a.groups) * 4);
-                pack_conv_weights_f32(w0, cout, cin_logical / a.groups, a.kh, a.kw, sc.data(),
-                                      reinterpret_cast<float*>(blob.data() + op.w_off));
+                case ROUTE_IGEMM:
+                case ROUTE_VIEW:   // (the view kernel reads the fp16 implicit-GEMM layout: kernels/conv_view.hip)
+                    op.w_off = reserve(conv_packed_weight_bytes(op.route, a));
+                    if (a.in_i8) {
+                        // int8 weights, per-output-channel scales; cscale[c] = input tensor scale * weight scale (dequantises the int32 sums)
+                        std::vector<float> wscale(a.Cout_pad, 1.f);
+                        conv_pack_weights_i8(w0, cout, cin_logical, a.kh, a.kw, a.CinK * 2, sc.data(), a.Cout_pad, a.Kpad * 2,
+                                             reinterpret_cast<int8_t*>(blob.data() + op.w_off), wscale.data());
+                        const float s_in = plan->tensors[op.in[0]].scale;
+                        for (float& v : wscale) v *= s_in;
+                        op.s_off = reserve(wscale.size() * 4);
+                        memcpy(blob.data() + op.s_off, wscale.data(), wscale.size() * 4);
+                    } else if (a.f32) {
+                        conv_pack_weights_igemm_f32(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
+                                                    reinterpret_cast<float*>(blob.data() + op.w_off));
+                    } else {
+                        pack_conv_weights_f16(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(),
+                                              reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+                    }
+                    break;
+                case ROUTE_GROUPED:
+                    op.w_off = reserve(conv_packed_weight_bytes(op.route, a));
+                    pack_conv_weights_grouped_f16(w0, cout, cin_g, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+                    break;
+                case ROUTE_DW: {
+                    // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load
+                    op.w_off = reserve(filter_bytes);
+                    float* dst = reinterpret_cast<float*>(blob.data() + op.w_off);
+                    for (int co = 0; co < cout; ++co)
+                        for (int t = 0; t < a.kh * a.kw; ++t) dst[(size_t)t * cout + co] = w0[(size_t)co * a.kh * a.kw + t] * sc[co];
+                    break;
+                }
+                case ROUTE_DIRECT:
+                    op.w_off = reserve(filter_bytes);
+                    pack_conv_weights_f32(w0, cout, cin_g, a.kh, a.kw, sc.data(), reinterpret_cast<float*>(blob.data() + op.w_off));
+                    break;
             }
             op.b_off = reserve(bias.size() * 4);
             memcpy(blob.data() + op.b_off, bias.data(), bias.size() * 4);
-            op.bytes += (double)(op.igemm || op.conv_view ? (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2) : (op.grouped ? (size_t)cout * a.Kpad * 2 : (size_t)cout * a.K * 4));
+            op.bytes += (double)conv_packed_weight_bytes(op.route, a);
         } else if (head_has_dfl(op.kind)) {
             const LayerDef& l = net.layers[op.src_layer];
             op.w_off = reserve(16 * 4);

@@ -5,10 +5,30 @@
 
 namespace trtx {
 
+struct ConvArgs;
+enum ConvRoute : int;
+
+// Each family's packed layout, stated once: the packed-geometry fields of a ConvArgs (bn, bk, CinK, K, Kpad, Cout_pad) from its logical geometry (Cin, Cout,
+// kh, kw, groups).  The lowering, the single-op entry points and the packers below all take the layout from here; a kernel's _supported() checks it.
+//  - fp16 implicit GEMM: the caller chooses the k-step bk (conv_igemm_pick_bk, or 32 where the plan's batch says so); Cin is already a multiple of 8
+void conv_layout_igemm_f16(ConvArgs* a, int bk);
+//  - int8 implicit GEMM: 64-channel k-steps.  Takes Cin and ld_in in channels and leaves them, like CinK / K / Kpad, in 2-byte units (ConvArgs::in_i8, which it sets)
+void conv_layout_igemm_i8(ConvArgs* a);
+//  - fp32 implicit GEMM (ConvArgs::f32, which it sets): 16-channel k-steps, the tile shape left to the launcher (bn = bm = 0)
+void conv_layout_igemm_f32(ConvArgs* a);
+//  - channel views (kernels/conv_view.hip): the fp16 implicit-GEMM rows with CinK = Cin rounded up to 32
+void conv_layout_view(ConvArgs* a);
+//  - grouped (kernels/conv_grouped.hip): K per group, rows of conv_grouped_kpad()
+void conv_layout_grouped(ConvArgs* a);
+//  - direct, depthwise, stem, deconvolution: nothing is padded
+void conv_layout_unpadded(ConvArgs* a);
+// Bytes of the packed filter of a convolution on `route` (what pack_weights reserves, and the weight term of POp::bytes)
+size_t conv_packed_weight_bytes(ConvRoute route, const ConvArgs& a);
+
 // TensorRT conv weights are KCRS fp32 ([Cout][Cin][kh][kw]).  The implicit-GEMM kernel wants
-// fp16 [Cout_pad][Kpad = kh*kw*cin_pad rounded up to bk] with k = (r*kw + q)*cin_pad + c (cin_pad = CinK, the per-tap stride), zero padded; an optional per-output-channel
-// scale (folded BatchNorm, yolov8/src/block.cpp:45-77) is multiplied in before rounding to fp16.
-void pack_conv_weights_f16(const float* w_kcrs, int cout, int cin, int kh, int kw, int cin_pad, int bk,
+// fp16 [cout_pad][kpad] with k = (r*kw + q)*cink + c (cink = CinK, the per-tap stride), zero padded (conv_layout_igemm_f16 / conv_layout_view); an optional
+// per-output-channel scale (folded BatchNorm, yolov8/src/block.cpp:45-77) is multiplied in before rounding to fp16.
+void pack_conv_weights_f16(const float* w_kcrs, int cout, int cin, int kh, int kw, int cink, int kpad, int cout_pad,
                            const float* ch_scale, uint16_t* packed);
 
 // fp32 [Cout][kh][kw][Cin/groups] for the generic direct kernel (KCRS source, Cin here = per group)

@@ -33,6 +33,14 @@ const HeadOp* head_op(int kind) {
     return nullptr;
 }
 
+ConvArgs conv_args_at(const Plan& plan, const POp& op, int batch) {
+    ConvArgs a = op.conv;
+    const PTensor& t0 = plan.tensors[op.in[0]];
+    a.N = op.route == ROUTE_STEM ? (plan.explicit_batch ? (int)t0.dims.d[0] : batch) : (t0.nfix ? t0.nfix : batch) * t0.nmul;
+    a.M = a.N * a.Ho * a.Wo;
+    return a;
+}
+
 std::string Plan::describe_json() const {
     std::ostringstream o;
     double flops = 0, bytes = 0;
@@ -42,7 +50,7 @@ std::string Plan::describe_json() const {
         bytes += op.bytes;
         if (op.kind == OP_CONV) {
             ++n_conv;
-            n_igemm += op.igemm ? 1 : 0;
+            n_igemm += op.route == ROUTE_IGEMM ? 1 : 0;
         }
         n_conv += (int)op.group.size();
         n_igemm += (int)op.group.size();
@@ -58,17 +66,18 @@ std::string Plan::describe_json() const {
         o << "\",\"flops\":" << op.flops << ",\"bytes\":" << op.bytes;
         auto conv_fields = [&](const POp& op) {
             const ConvArgs& a = op.conv;
-            o << ",\"igemm\":" << (op.igemm ? "true" : "false") << ",\"stem\":" << (op.stem ? "true" : "false") << (op.stem_pair ? ",\"stem_pair\":true" : "")
+            const bool stem = op.route == ROUTE_STEM;
+            o << ",\"igemm\":" << (op.route == ROUTE_IGEMM ? "true" : "false") << ",\"stem\":" << (stem ? "true" : "false") << (op.stem_pair ? ",\"stem_pair\":true" : "")
               << (op.bneck_pair ? ",\"bneck_pair\":true" : "") << ",\"cin\":" << (a.in_i8 ? 2 * a.Cin : a.Cin) << ",\"cout\":" << a.Cout
               << ",\"k\":[" << a.kh << "," << a.kw << "],\"stride\":[" << a.stride_h << "," << a.stride_w << "],\"hw_in\":["
               << a.H << "," << a.W << "],\"hw_out\":[" << a.Ho << "," << a.Wo << "],\"act1\":" << a.act1
               << ",\"act2\":" << a.act2 << ",\"alpha1\":" << a.alpha1 << ",\"alpha2\":" << a.alpha2 << ",\"up_c\":" << a.up_C << ",\"residual\":" << (op.in.size() > 1 ? "true" : "false")
               << ",\"bn_folded\":" << (op.scale_layer >= 0 ? "true" : "false") << ",\"ld_in\":" << a.ld_in
-              << ",\"ld_out\":" << a.ld_out << ",\"i8\":[" << a.in_i8 << "," << a.out_i8 << "," << a.res_i8 << "],\"nmul\":" << (op.stem ? 1 : tensors[op.in[0]].nmul) << ",\"nfix\":"
-              << (op.stem ? 0 : tensors[op.in[0]].nfix);
-            if (op.dw) o << ",\"dw\":true";
-            if (op.grouped) o << ",\"grouped\":true";
-            if (op.conv_view) o << ",\"view\":true";
+              << ",\"ld_out\":" << a.ld_out << ",\"i8\":[" << a.in_i8 << "," << a.out_i8 << "," << a.res_i8 << "],\"nmul\":" << (stem ? 1 : tensors[op.in[0]].nmul) << ",\"nfix\":"
+              << (stem ? 0 : tensors[op.in[0]].nfix);
+            if (op.route == ROUTE_DW) o << ",\"dw\":true";
+            if (op.route == ROUTE_GROUPED) o << ",\"grouped\":true";
+            if (op.route == ROUTE_VIEW) o << ",\"view\":true";
             if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
             if (op.reorg_cin) o << ",\"reorg_cin\":" << op.reorg_cin;
             if (op.fold_layer >= 0) o << ",\"repvggdw_fold\":true";

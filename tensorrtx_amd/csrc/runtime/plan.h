@@ -19,7 +19,7 @@ enum Layout : int { LAY_LINEAR = 0, LAY_NHWC = 1 };
 enum StorageKind : int { ST_ARENA = 0, ST_WEIGHTS = 1, ST_BINDING = 2 };
 
 enum OpKind : int {
-    OP_CONV = 0,      // fused conv (+bias/BN, act1, residual, act2): igemm (MFMA) or direct
+    OP_CONV = 0,      // fused conv (+bias/BN, act1, residual, act2) on one of six kernel families: POp::route
     OP_DECONV,
     OP_POOL,
     OP_RESIZE,
@@ -127,6 +127,17 @@ struct Storage {
 };
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }   // every block of the arena and of the weight blob starts on 256 bytes
 
+// Which kernel family runs an OP_CONV, and with it how pack_weights lays its filter out (pack.h).  Exactly one per op: the emission says direct or stem,
+// choose_conv_kernel (plan_passes.cpp) then settles the rest.  The sub-forms of a route are ConvArgs': f32 (implicit GEMM, stem), in_i8 (implicit GEMM).
+enum ConvRoute : int {
+    ROUTE_DIRECT = 0,  // the generic direct kernel (conv_direct; weights fp32 [Cout][kh][kw][Cin/groups]): whatever no other route takes (and the value in every op that is no convolution)
+    ROUTE_STEM,        // conv_stem kernel: reads the LINEAR fp32 input directly (weights fp32 [tap][Cout])
+    ROUTE_IGEMM,       // implicit GEMM on MFMA (kernels/conv_igemm.hip, conv_igemm_f32.hip; weights [Cout_pad][Kpad] fp16 / int8 / fp32); also the 1x1 half of an OP_DSCONV
+    ROUTE_DW,          // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C])
+    ROUTE_GROUPED,     // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad])
+    ROUTE_VIEW,        // MFMA kernel over 4-byte aligned channel views (kernels/conv_view.hip; weights as the implicit-GEMM family packs them)
+};
+
 struct POp {
     int kind = 0;
     std::string name;
@@ -136,16 +147,12 @@ struct POp {
     int dtype = DT_F32;
     // conv / deconv
     ConvArgs conv{};
-    bool igemm = false;
-    bool stem = false;         // conv_stem kernel: reads the LINEAR fp32 input directly
+    ConvRoute route = ROUTE_DIRECT;
     bool stem_pair = false;    // the op right after the stem: the engine computes it straight from the network input in ONE launch with the stem
                                // (kernels/conv_stem_pair.hip); the stem op before it then launches nothing and the tensor between them stays unwritten
     bool bneck_pair = false;   // the second 3x3 convolution of a 16-channel bottleneck: the engine computes it in ONE launch with the convolution right before it
                                // (kernels/conv_bneck_pair.hip); that op then launches nothing and the tensor between them stays unwritten
     bool from_deconv = false;  // 1x1 conv standing in for a kernel == stride deconvolution (weights re-laid from CKRS)
-    bool dw = false;           // depthwise kernel (kernels/conv_dw.hip; weights fp32 [kh*kw][C]) instead of the direct one
-    bool grouped = false;      // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad]) instead of the direct one
-    bool conv_view = false;    // MFMA kernel over 4-byte aligned channel views (kernels/conv_view.hip; weights as the implicit-GEMM family packs them) instead of the direct one
     int fold_layer = -1, fold_scale = -1;   // >= 0: a 7x7 depthwise convolution that took RepVGGDW's 3x3 branch (match_repvggdw_fold): the network layers
                                // of that branch's convolution and scale; pack_weights adds its scaled filter into the centre and its shift to the shift
     ConvArgs dw_conv{};        // OP_DSCONV: the depthwise convolution in front of `conv`
@@ -200,6 +207,11 @@ struct Plan {
 
     std::string describe_json() const;
 };
+
+// op.conv with N and M of `batch` images per enqueue, pointers left null: the geometry execute_plan launches, and what the passes and the tactic timing show
+// the kernels' _possible() checks and tactic lists at the largest batch.  (The stem reads the LINEAR network input: in an explicit-batch plan its leading
+// dimension is the image count.)
+ConvArgs conv_args_at(const Plan& plan, const POp& op, int batch);
 
 // Lower a network into a plan (pure host work; no device needed).  Returns false and sets plan.error.
 bool lower_network(const Network& net, Plan* plan);

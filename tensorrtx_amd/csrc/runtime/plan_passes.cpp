@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "pack.h"
+
 namespace trtx {
 namespace {
 
@@ -20,19 +22,156 @@ size_t tensor_bytes(const Plan& plan, const PTensor& t) {
     return (t.batched ? (size_t)plan.max_batch : 1) * (size_t)t.dims.volume() * es;
 }
 
+// What the candidates of choose_conv_kernel look at: the op and the tensors it touches, strides / offsets resolved and dtypes assigned
+struct ConvSite {
+    const Plan& plan;
+    const PassInputs& e;
+    POp& op;
+    const PTensor &ti, &to;
+    const PTensor* tr;   // the residual, or null
+};
+// Each candidate either declines (false: op untouched) or fills op.conv for its kernel family and names its route.
+
+// fp16 / kINT8 engines: the implicit GEMM on the fp16 / int8 MFMA (kernels/conv_igemm.hip)
+bool take_igemm_f16(const ConvSite& s) {
+    const Plan& plan = s.plan;
+    const PassInputs& e = s.e;
+    const PTensor &ti = s.ti, &to = s.to;
+    ConvArgs& a = s.op.conv;
+    if (e.dt != DT_F16) return false;
+    int cin_eff = a.Cin;
+    bool ok = true;
+    if (cin_eff % 8) {
+        // padded channels are zero only for a freshly converted, un-aliased tensor
+        const PTensor& own = plan.tensors[ti.parent >= 0 ? ti.parent : ti.id];
+        ok = ti.parent < 0 && own.pad_zeroed;
+        cin_eff = (a.Cin + 7) / 8 * 8;
+    }
+    ok = ok && ti.rcoff % 8 == 0 && ti.ld % 8 == 0;
+    const bool in8 = ti.dtype == DT_I8, out8 = to.dtype == DT_I8, res8 = s.tr && s.tr->dtype == DT_I8;
+    if (in8) ok = ok && a.Cin % 16 == 0 && ti.rcoff % 16 == 0 && ti.ld % 16 == 0;
+    // output side: 16-byte stores when everything is a multiple of 8, element-wise stores otherwise
+    const bool vec_out = a.Cout % 8 == 0 && to.rcoff % 8 == 0 && to.ld % 8 == 0 && (!s.tr || (s.tr->rcoff % 8 == 0 && s.tr->ld % 8 == 0));
+    // tiny reductions (K < 32, e.g. the DFL 1x1) stay on the direct kernel - except the square 1x1 over 16 channels (YOLOv5n's first C3
+    // bottleneck, 16 -> 16 on the stride-4 map, the one such layer the builders here produce): a memory-bound layer that the
+    // two-taps-per-step form (CinK = 16; its second tap lies outside the 1x1 filter and loads zeros) streams with 16-byte accesses.
+    // Wider outputs over 16 channels (the qkv convolutions of the attention test graphs) keep the direct kernel: nothing measured
+    // says otherwise.  Not in kINT8 engines either, where such a layer stays the fp16 island it has been.
+    // The square 1x1 over 24 channels is the same case one k-step wider (CinK = 32, channels 24 .. 31 load zeros like the last channels of
+    // any Cin that is no multiple of the step): the 1x1 branch of YOLOv9t's RepConvN on its 24-channel RepNCSP blocks, 18 layers.
+    ok = ok && (a.kh * a.kw * cin_eff >= 32 || (!e.int8 && a.kh == 1 && a.kw == 1 && (a.Cin == 16 || a.Cin == 24) && a.Cout == a.Cin));
+    if (!ok) return false;
+    ConvArgs t = a;
+    t.scalar_out = vec_out ? 0 : 1;
+    t.Cin = cin_eff;
+    if (in8) {
+        conv_layout_igemm_i8(&t);
+    } else {
+        int bk = conv_igemm_pick_bk(cin_eff, t.kh * t.kw);
+        {   // few tiles + long K at the largest batch: keep 32-wide steps so the wave-split-K variant applies
+            const int bn = conv_igemm_pick_bn(t.Cout);
+            const long m_max = (long)(ti.nfix ? ti.nfix : plan.max_batch) * ti.nmul * t.Ho * t.Wo;
+            const long tiles128 = (m_max + 127) / 128 * ((t.Cout + bn - 1) / bn);
+            if (tiles128 <= 256 && (bn == 64 || bn == 80)) bk = 32;
+        }
+        conv_layout_igemm_f16(&t, bk);
+    }
+    t.out_i8 = out8 ? 1 : 0;
+    t.res_i8 = res8 ? 1 : 0;
+    t.out_inv_scale = out8 ? 1.0f / to.scale : 0.f;
+    t.res_scale = res8 ? s.tr->scale : 0.f;
+    // Engines for several execution contexts in flight (setMaxAuxStreams(0)) take the implicit-GEMM operands through
+    // registers instead of LDS-DMA: bit-identical results, and on YOLOv8n b32 with three contexts 34.2-34.5k img/s against
+    // 33.3-33.6k (same box, alternating runs) - a DMA piece costs its wave 60-185 cycles of issue, which co-scheduled
+    // workgroups of other contexts cannot hide for each other; a lone context is 3 % slower with it and keeps the DMA.
+    // ... and only for layers below the MFMA / HBM ridge (312 FLOP per byte): the MFMA-bound GEMMs of res5 lose with it (C5 three
+    // contexts 12.1 vs 11.65 ms; tools/gemm_tactics.py: K = 4608 0.39 vs 0.42 of peak), ResNet-50 gains 2.2 %, RetinaFace is
+    // indifferent (profiles/r03_rs_ab.txt).
+    {
+        const double flop_px = 2.0 * a.Cout * (double)a.kh * a.kw * a.Cin;
+        const double byte_px = 2.0 * ((double)a.Cin * a.stride_h * a.stride_w + (double)a.Cout * (s.tr ? 2 : 1));
+        constexpr double ridge = 312.0;   // the MFMA / HBM ridge, FLOP per byte
+        t.t_rs = (e.max_aux_streams == 0 && flop_px / byte_px < ridge) ? 1 : 0;
+    }
+    if (!conv_igemm_supported(t)) return false;
+    a = t;
+    s.op.route = ROUTE_IGEMM;
+    return true;
+}
+
+// fp32 engines: the same skeleton on the fp32 MFMA (kernels/conv_igemm_f32.hip), 16-channel k-steps; the tile shape is the launcher's
+bool take_igemm_f32(const ConvSite& s) {
+    const PTensor &ti = s.ti, &to = s.to;
+    ConvArgs& a = s.op.conv;
+    if (s.e.dt != DT_F32 || ti.dtype != DT_F32 || to.dtype != DT_F32) return false;
+    int cin_eff = a.Cin;
+    bool ok = s.e.opt.f32_mfma;   // (TRTX_F32_DIRECT=1: the scalar direct kernel of rounds 1-4, an A/B switch)
+    if (cin_eff % 4) {
+        const PTensor& own = s.plan.tensors[ti.parent >= 0 ? ti.parent : ti.id];
+        ok = ok && ti.parent < 0 && own.pad_zeroed;
+        cin_eff = (a.Cin + 3) / 4 * 4;
+    }
+    ok = ok && ti.rcoff % 4 == 0 && ti.ld % 4 == 0;
+    const bool vec_out = a.Cout % 4 == 0 && to.rcoff % 4 == 0 && to.ld % 4 == 0 && (!s.tr || (s.tr->rcoff % 4 == 0 && s.tr->ld % 4 == 0));
+    ok = ok && a.kh * a.kw * cin_eff >= 16 && a.Cout >= 8;   // tiny reductions / single-channel outputs (the DFL 1x1) stay on the direct kernel
+    if (!ok) return false;
+    ConvArgs t = a;
+    t.scalar_out = vec_out ? 0 : 1;
+    t.Cin = cin_eff;
+    conv_layout_igemm_f32(&t);
+    if (!conv_igemm_f32_supported(t)) return false;
+    a = t;
+    s.op.route = ROUTE_IGEMM;
+    return true;
+}
+
+// depthwise (YOLO11 DWConv and the PSA attention's pe): kernels/conv_dw.hip, fp16 and fp32, any channel stride
+bool take_dw(const ConvSite& s) {
+    if (!conv_dw_supported(s.op.conv)) return false;
+    s.op.route = ROUTE_DW;
+    return true;
+}
+
+// grouped, not depthwise (YOLOv9's DetectBbox_Conv: 64 -> 64 with g = 4): kernels/conv_grouped.hip, 16-byte aligned channel views; a.Kpad becomes the
+// packed row length.  TRTX_CONV_GROUPED=0 leaves such layers on the direct kernel (A/B).
+bool take_grouped(const ConvSite& s) {
+    ConvArgs& a = s.op.conv;
+    if (!s.e.opt.conv_grouped || s.ti.rcoff % 8 || s.to.rcoff % 8) return false;
+    if (s.tr && (s.tr->rcoff % 8 || s.tr->ld % 8 || s.tr->ld < a.Cout)) return false;
+    if (!conv_grouped_supported(a)) return false;
+    conv_layout_grouped(&a);
+    s.op.route = ROUTE_GROUPED;
+    return true;
+}
+
+// groups == 1 over a view whose channel count, offset or stride is even but no multiple of 8 (YOLOv9m's 60- and 90-channel RepNCSP blocks and the
+// 180-channel halves of its 360-channel tensors; a user's ISliceLayer): kernels/conv_view.hip, after every kernel above has declined.  The weights are
+// packed as the implicit-GEMM family's with CinK = Cin rounded up to 32.  TRTX_CONV_VIEW=0 leaves such layers on the direct kernel (A/B).
+bool take_view(const ConvSite& s) {
+    ConvArgs& a = s.op.conv;
+    if (!s.e.opt.conv_view || s.ti.rcoff % 2 || s.to.rcoff % 2 || (s.tr && s.tr->rcoff % 2)) return false;
+    // only what the implicit-GEMM family declined for its input's alignment: an aligned layer it leaves to the direct kernel (a tiny reduction) stays there
+    if (!(a.Cin % 8 || s.ti.rcoff % 8 || s.ti.ld % 8)) return false;
+    ConvArgs t = a;
+    conv_layout_view(&t);
+    if (!conv_view_supported(t)) return false;
+    a = t;
+    s.op.route = ROUTE_VIEW;
+    return true;
+}
+
 // Which kernel runs a convolution, given the (resolved) strides / offsets and the dtypes of the tensors it touches: fills op.conv
-// and sets op.igemm when the implicit-GEMM MFMA kernel takes it (the direct kernel otherwise).  ONE predicate for select_conv_kernels(),
+// and names op.route; true when the implicit-GEMM MFMA kernel takes it.  ONE predicate for select_conv_kernels(),
 // fold_upsample's probe and the int8 assignment, which may only put a tensor in int8 if every convolution touching it gets the MFMA path.
 bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
     ConvArgs& a = op.conv;
     const PTensor& ti = plan.tensors[op.in[0]];
     const PTensor& to = plan.tensors[op.out[0]];
+    const PTensor* tr = op.in.size() > 1 ? &plan.tensors[op.in[1]] : nullptr;
     a.ld_in = ti.ld;
     a.ld_out = to.ld;
-    a.ld_res = op.in.size() > 1 ? plan.tensors[op.in[1]].ld : 0;
-    a.K = a.kh * a.kw * (a.Cin / a.groups);
-    a.Cout_pad = a.Cout;
-    a.Kpad = a.K;
+    a.ld_res = tr ? tr->ld : 0;
+    conv_layout_unpadded(&a);
     a.up_C = 0;
     if (!op.extra_in.empty()) {   // folded upsample: geometry of the half-resolution source
         const PTensor& tu = plan.tensors[op.extra_in[0]];
@@ -41,159 +180,19 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
         a.up_H = tu.H;
         a.up_W = tu.W;
     }
-    op.igemm = false;
-    a.f32 = (op.stem && e.dt == DT_F32) ? 1 : 0;   // (the fp32 stem kernel; the MFMA path sets it below)
-    if (op.kind == OP_CONV && !op.stem && e.dt == DT_F16 && a.groups == 1 && a.dil_h == 1 && a.dil_w == 1) {
-        int cin_eff = a.Cin;
-        bool ok = true;
-        if (cin_eff % 8) {
-            // padded channels are zero only for a freshly converted, un-aliased tensor
-            const PTensor& own = plan.tensors[ti.parent >= 0 ? ti.parent : ti.id];
-            ok = ti.parent < 0 && own.pad_zeroed;
-            cin_eff = (a.Cin + 7) / 8 * 8;
-        }
-        ok = ok && ti.rcoff % 8 == 0 && ti.ld % 8 == 0;
-        const bool in8 = ti.dtype == DT_I8, out8 = to.dtype == DT_I8;
-        const bool res8 = op.in.size() > 1 && plan.tensors[op.in[1]].dtype == DT_I8;
-        if (in8) ok = ok && a.Cin % 16 == 0 && ti.rcoff % 16 == 0 && ti.ld % 16 == 0;
-        // output side: 16-byte stores when everything is a multiple of 8, element-wise stores otherwise
-        bool vec_out = a.Cout % 8 == 0 && to.rcoff % 8 == 0 && to.ld % 8 == 0;
-        if (op.in.size() > 1) {
-            const PTensor& tr = plan.tensors[op.in[1]];
-            vec_out = vec_out && tr.rcoff % 8 == 0 && tr.ld % 8 == 0;
-        }
-        // tiny reductions (K < 32, e.g. the DFL 1x1) stay on the direct kernel - except the square 1x1 over 16 channels (YOLOv5n's first C3
-        // bottleneck, 16 -> 16 on the stride-4 map, the one such layer the builders here produce): a memory-bound layer that the
-        // two-taps-per-step form (CinK = 16; its second tap lies outside the 1x1 filter and loads zeros) streams with 16-byte accesses.
-        // Wider outputs over 16 channels (the qkv convolutions of the attention test graphs) keep the direct kernel: nothing measured
-        // says otherwise.  Not in kINT8 engines either, where such a layer stays the fp16 island it has been.
-        // The square 1x1 over 24 channels is the same case one k-step wider (CinK = 32, channels 24 .. 31 load zeros like the last channels of
-        // any Cin that is no multiple of the step): the 1x1 branch of YOLOv9t's RepConvN on its 24-channel RepNCSP blocks, 18 layers.
-        ok = ok && (a.kh * a.kw * cin_eff >= 32 || (!e.int8 && a.kh == 1 && a.kw == 1 && (a.Cin == 16 || a.Cin == 24) && a.Cout == a.Cin));
-        if (ok) {
-            ConvArgs t = a;
-            t.scalar_out = vec_out ? 0 : 1;
-            t.Cin = cin_eff;
-            t.bn = conv_igemm_pick_bn(t.Cout);
-            t.bk = conv_igemm_pick_bk(cin_eff, t.kh * t.kw);
-            {   // few tiles + long K at the largest batch: keep 32-wide steps so the wave-split-K variant applies
-                const long m_max = (long)(ti.nfix ? ti.nfix : plan.max_batch) * ti.nmul * t.Ho * t.Wo;
-                const long tiles128 = (m_max + 127) / 128 * ((t.Cout + t.bn - 1) / t.bn);
-                if (tiles128 <= 256 && (t.bn == 64 || t.bn == 80)) t.bk = 32;
-            }
-            t.CinK = conv_igemm_pick_cink(cin_eff, t.bk);  // a k-step never straddles a filter tap
-            t.K = t.kh * t.kw * t.CinK;
-            t.Kpad = (t.K + t.bk - 1) / t.bk * t.bk;
-            t.bn = conv_igemm_pick_bn(t.Cout);
-            t.Cout_pad = (t.Cout + t.bn - 1) / t.bn * t.bn;
-            if (in8) {  // int8 operands: 64-channel k-steps; the input-side geometry is handed over in 2-byte units (ConvArgs)
-                t.bk = 32;
-                t.in_i8 = 1;
-                t.Cin = a.Cin / 2;
-                t.ld_in = ti.ld / 2;
-                t.CinK = (a.Cin + 63) / 64 * 64 / 2;
-                t.K = t.kh * t.kw * t.CinK;
-                t.Kpad = t.K;
-            }
-            t.out_i8 = out8 ? 1 : 0;
-            t.res_i8 = res8 ? 1 : 0;
-            t.out_inv_scale = out8 ? 1.0f / to.scale : 0.f;
-            t.res_scale = res8 ? plan.tensors[op.in[1]].scale : 0.f;
-            // Engines for several execution contexts in flight (setMaxAuxStreams(0)) take the implicit-GEMM operands through
-            // registers instead of LDS-DMA: bit-identical results, and on YOLOv8n b32 with three contexts 34.2-34.5k img/s against
-            // 33.3-33.6k (same box, alternating runs) - a DMA piece costs its wave 60-185 cycles of issue, which co-scheduled
-            // workgroups of other contexts cannot hide for each other; a lone context is 3 % slower with it and keeps the DMA.
-            // ... and only for layers below the MFMA / HBM ridge (312 FLOP per byte): the MFMA-bound GEMMs of res5 lose with it (C5 three
-            // contexts 12.1 vs 11.65 ms; tools/gemm_tactics.py: K = 4608 0.39 vs 0.42 of peak), ResNet-50 gains 2.2 %, RetinaFace is
-            // indifferent (profiles/r03_rs_ab.txt).
-            {
-                const double flop_px = 2.0 * a.Cout * (double)a.kh * a.kw * a.Cin;
-                const double byte_px = 2.0 * ((double)a.Cin * a.stride_h * a.stride_w + (double)a.Cout * (op.in.size() > 1 ? 2 : 1));
-                constexpr double ridge = 312.0;   // the MFMA / HBM ridge, FLOP per byte
-                t.t_rs = (e.max_aux_streams == 0 && flop_px / byte_px < ridge) ? 1 : 0;
-            }
-            if (conv_igemm_supported(t)) {
-                a = t;
-                op.igemm = true;
-            }
-        }
-    }
-    // fp32 engines: the same skeleton on the fp32 MFMA (kernels/conv_igemm_f32.hip), 16-channel k-steps; the tile shape is the launcher's
-    if (op.kind == OP_CONV && !op.stem && e.dt == DT_F32 && ti.dtype == DT_F32 && to.dtype == DT_F32 && a.groups == 1 && a.dil_h == 1 && a.dil_w == 1) {
-        int cin_eff = a.Cin;
-        bool ok = e.opt.f32_mfma;   // (TRTX_F32_DIRECT=1: the scalar direct kernel of rounds 1-4, an A/B switch)
-        if (cin_eff % 4) {
-            const PTensor& own = plan.tensors[ti.parent >= 0 ? ti.parent : ti.id];
-            ok = ok && ti.parent < 0 && own.pad_zeroed;
-            cin_eff = (a.Cin + 3) / 4 * 4;
-        }
-        ok = ok && ti.rcoff % 4 == 0 && ti.ld % 4 == 0;
-        bool vec_out = a.Cout % 4 == 0 && to.rcoff % 4 == 0 && to.ld % 4 == 0;
-        if (op.in.size() > 1) {
-            const PTensor& tr = plan.tensors[op.in[1]];
-            vec_out = vec_out && tr.rcoff % 4 == 0 && tr.ld % 4 == 0;
-        }
-        ok = ok && a.kh * a.kw * cin_eff >= 16 && a.Cout >= 8;   // tiny reductions / single-channel outputs (the DFL 1x1) stay on the direct kernel
-        if (ok) {
-            ConvArgs t = a;
-            t.f32 = 1;
-            t.scalar_out = vec_out ? 0 : 1;
-            t.Cin = cin_eff;
-            t.bk = 16;
-            t.bn = 0;
-            t.bm = 0;
-            t.CinK = conv_igemm_f32_pick_cink(cin_eff);
-            t.K = t.kh * t.kw * t.CinK;
-            t.Kpad = (t.K + 15) / 16 * 16;
-            t.Cout_pad = (t.Cout + 15) / 16 * 16;
-            if (conv_igemm_f32_supported(t)) {
-                a = t;
-                op.igemm = true;
-            }
-        }
-    }
-    // depthwise (YOLO11 DWConv and the PSA attention's pe): kernels/conv_dw.hip, fp16 and fp32, any channel stride
-    op.dw = op.kind == OP_CONV && !op.igemm && !op.stem && !op.from_deconv && op.extra_in.empty() && ti.dtype == e.dt && to.dtype == e.dt &&
-            (op.in.size() < 2 || plan.tensors[op.in[1]].dtype == e.dt) && conv_dw_supported(a);
-    // grouped, not depthwise (YOLOv9's DetectBbox_Conv: 64 -> 64 with g = 4): kernels/conv_grouped.hip, fp16 engines only, 16-byte aligned channel
-    // views; a.Kpad becomes the packed row length.  TRTX_CONV_GROUPED=0 leaves such layers on the direct kernel (A/B).  Not in kINT8 engines.
-    op.grouped = false;
-    if (op.kind == OP_CONV && !op.igemm && !op.dw && !op.stem && !op.from_deconv && op.extra_in.empty() && e.opt.conv_grouped && !e.int8 &&
-        !CalibrationLowering::active() && e.dt == DT_F16 && ti.dtype == DT_F16 && to.dtype == DT_F16 && ti.rcoff % 8 == 0 && to.rcoff % 8 == 0) {
-        bool ok = true;
-        if (op.in.size() > 1) {
-            const PTensor& tr = plan.tensors[op.in[1]];
-            ok = tr.dtype == DT_F16 && tr.rcoff % 8 == 0 && tr.ld % 8 == 0 && tr.ld >= a.Cout;
-        }
-        if (ok && conv_grouped_supported(a)) {
-            op.grouped = true;
-            a.Kpad = conv_grouped_kpad(a);
-        }
-    }
-    // groups == 1 over a view whose channel count, offset or stride is even but no multiple of 8 (YOLOv9m's 60- and 90-channel RepNCSP blocks and the
-    // 180-channel halves of its 360-channel tensors; a user's ISliceLayer): kernels/conv_view.hip, after every kernel above has declined.  The weights are
-    // packed as the implicit-GEMM family's with CinK = Cin rounded up to 32.  TRTX_CONV_VIEW=0 leaves such layers on the direct kernel (A/B).
-    op.conv_view = false;
-    if (op.kind == OP_CONV && !op.igemm && !op.dw && !op.grouped && !op.stem && !op.from_deconv && op.extra_in.empty() && e.opt.conv_view && !e.int8 &&
-        !CalibrationLowering::active() && e.dt == DT_F16 && ti.dtype == DT_F16 && to.dtype == DT_F16 && ti.rcoff % 2 == 0 && to.rcoff % 2 == 0) {
-        // only what the implicit-GEMM family declined for its input's alignment: an aligned layer it leaves to the direct kernel (a tiny reduction) stays there
-        bool ok = a.Cin % 8 || ti.rcoff % 8 || ti.ld % 8;
-        if (op.in.size() > 1) {
-            const PTensor& tr = plan.tensors[op.in[1]];
-            ok = ok && tr.dtype == DT_F16 && tr.rcoff % 2 == 0;
-        }
-        ConvArgs t = a;
-        t.bk = 32;
-        t.CinK = (t.Cin + 31) / 32 * 32;
-        t.K = t.Kpad = t.kh * t.kw * t.CinK;
-        t.bn = conv_igemm_pick_bn(t.Cout);
-        t.Cout_pad = (t.Cout + t.bn - 1) / t.bn * t.bn;
-        if (ok && conv_view_supported(t)) {
-            a = t;
-            op.conv_view = true;
-        }
-    }
-    return op.igemm;
+    const bool stem = op.route == ROUTE_STEM;   // the emission's choice (lower.cpp, emit_conv)
+    a.f32 = (stem && e.dt == DT_F32) ? 1 : 0;   // (the fp32 stem kernel; the fp32 MFMA path sets it itself)
+    if (op.kind != OP_CONV || stem) return false;   // (a deconvolution has the one kernel)
+    op.route = ROUTE_DIRECT;   // ... unless a candidate takes it, in this order:
+    const ConvSite s{plan, e, op, ti, to, tr};
+    if (a.groups == 1 && a.dil_h == 1 && a.dil_w == 1 && (take_igemm_f16(s) || take_igemm_f32(s))) return true;
+    // the other kernels neither stand in for a deconvolution nor fetch a folded upsample, and every tensor is of the engine's dtype
+    if (op.from_deconv || !op.extra_in.empty() || ti.dtype != e.dt || to.dtype != e.dt || (tr && tr->dtype != e.dt)) return false;
+    if (take_dw(s)) return false;
+    // ... the last two in fp16 engines only, not in kINT8 engines nor in the lowering their calibration runs on
+    if (e.dt != DT_F16 || e.int8 || CalibrationLowering::active()) return false;
+    (void)(take_grouped(s) || take_view(s));
+    return false;
 }
 
 // OP_DSCONV: the strides of the depthwise half, and the 1x1 half set up as choose_conv_kernel sets up a 1x1 over a dense NHWC tensor of the depthwise channels
@@ -202,30 +201,21 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
 bool choose_dsconv_kernels(const Plan& plan, POp& op) {
     const PTensor& ti = plan.tensors[op.in[0]];
     const PTensor& to = plan.tensors[op.out[0]];
+    const PTensor* tr = op.in.size() > 1 ? &plan.tensors[op.in[1]] : nullptr;
     ConvArgs& d = op.dw_conv;
     d.ld_in = ti.ld;
     d.ld_out = d.Cout;
-    d.K = d.Kpad = d.kh * d.kw;
-    d.Cout_pad = d.Cout;
+    conv_layout_unpadded(&d);
     ConvArgs& a = op.conv;
     a.ld_in = a.Cin;
     a.ld_out = to.ld;
-    a.ld_res = op.in.size() > 1 ? plan.tensors[op.in[1]].ld : 0;
-    a.K = a.Kpad = a.Cin;
-    a.Cout_pad = a.Cout;
-    bool vec_out = to.rcoff % 8 == 0 && to.ld % 8 == 0;   // (a slice that starts off a 16-byte boundary: the two launches, element-wise stores)
-    if (op.in.size() > 1) vec_out = vec_out && plan.tensors[op.in[1]].rcoff % 8 == 0 && plan.tensors[op.in[1]].ld % 8 == 0;
-    ConvArgs t = a;
-    t.scalar_out = vec_out ? 0 : 1;
-    t.bn = conv_igemm_pick_bn(t.Cout);
-    t.bk = conv_igemm_pick_bk(t.Cin, 1);
-    t.CinK = conv_igemm_pick_cink(t.Cin, t.bk);
-    t.K = t.CinK;
-    t.Kpad = (t.K + t.bk - 1) / t.bk * t.bk;
-    t.Cout_pad = (t.Cout + t.bn - 1) / t.bn * t.bn;
-    op.igemm = conv_igemm_supported(t);
-    a = t;
-    return op.igemm;
+    a.ld_res = tr ? tr->ld : 0;
+    // (a slice that starts off a 16-byte boundary: the two launches, element-wise stores)
+    const bool vec_out = to.rcoff % 8 == 0 && to.ld % 8 == 0 && (!tr || (tr->rcoff % 8 == 0 && tr->ld % 8 == 0));
+    a.scalar_out = vec_out ? 0 : 1;
+    conv_layout_igemm_f16(&a, conv_igemm_pick_bk(a.Cin, 1));
+    op.route = ROUTE_IGEMM;
+    return conv_igemm_supported(a);
 }
 
 // view geometry (element units: independent of the dtypes assigned next)
@@ -277,7 +267,7 @@ void fold_upsample(Plan& plan, const PassInputs& e) {
         if (n_readers != 1 || is_binding_tensor(plan, owner)) continue;
         POp& cv = plan.ops[reader];
         const ConvArgs& a = cv.conv;
-        if (cv.kind != OP_CONV || cv.stem || cv.from_deconv || cv.in[0] != owner || !cv.extra_in.empty() || a.kh != 1 || a.kw != 1 || a.stride_h != 1 ||
+        if (cv.kind != OP_CONV || cv.route == ROUTE_STEM || cv.from_deconv || cv.in[0] != owner || !cv.extra_in.empty() || a.kh != 1 || a.kw != 1 || a.stride_h != 1 ||
             a.stride_w != 1 || a.pad_h || a.pad_w || a.groups != 1 || a.Cin != plan.tensors[owner].C || up.C >= a.Cin || reader < (int)k)
             continue;
         POp probe = cv;
@@ -312,7 +302,7 @@ void assign_int8(Plan& plan, const PassInputs& e, const std::vector<char>& veto)
     };
     auto conv_ok = [&](const POp& op) {
         const ConvArgs& a = op.conv;
-        return op.kind == OP_CONV && !op.stem && !op.from_deconv && a.groups == 1 && a.dil_h == 1 && a.dil_w == 1 && a.kh * a.kw <= 30;
+        return op.kind == OP_CONV && op.route != ROUTE_STEM && !op.from_deconv && a.groups == 1 && a.dil_h == 1 && a.dil_w == 1 && a.kh * a.kw <= 30;
     };
     for (const POp& op : plan.ops) {
         for (size_t j = 0; j < op.in.size(); ++j) {
@@ -414,16 +404,16 @@ bool select_conv_kernels(Plan& plan, const PassInputs& e, std::string* err) {
         ConvArgs& a = op.conv;
         const PTensor& ti = plan.tensors[op.in[0]];
         const PTensor& to = plan.tensors[op.out[0]];
-        if (op.stem && (e.dt == DT_F16 ? (to.ld % 8 || to.rcoff % 8) : (to.ld % 4 || to.rcoff % 4))) return fail(err, op.name + ": stem convolution output is not 16-byte aligned");
+        if (op.route == ROUTE_STEM && (e.dt == DT_F16 ? (to.ld % 8 || to.rcoff % 8) : (to.ld % 4 || to.rcoff % 4))) return fail(err, op.name + ": stem convolution output is not 16-byte aligned");
         choose_conv_kernel(plan, e, op);
-        if (!op.extra_in.empty() && !op.igemm) return fail(err, op.name + ": folded upsample on a convolution that cannot take the MFMA path");
-        if ((ti.dtype == DT_I8 || to.dtype == DT_I8 || (op.in.size() > 1 && plan.tensors[op.in[1]].dtype == DT_I8)) && !op.igemm)
+        if (!op.extra_in.empty() && op.route != ROUTE_IGEMM) return fail(err, op.name + ": folded upsample on a convolution that cannot take the MFMA path");
+        if ((ti.dtype == DT_I8 || to.dtype == DT_I8 || (op.in.size() > 1 && plan.tensors[op.in[1]].dtype == DT_I8)) && op.route != ROUTE_IGEMM)
             return fail(err, op.name + ": int8 tensor on a convolution that cannot take the MFMA path");
         const double es_in = (double)dtype_size(ti.dtype), es_out = (double)dtype_size(to.dtype);
         const double cin_real = ti.dtype == DT_I8 ? 2.0 * a.Cin : (double)a.Cin;
         // (a folded upsample reads up_C of its input channels from a tensor a quarter the size)
         const double in_elems = (double)a.H * a.W * (cin_real - a.up_C) + (double)a.up_H * a.up_W * a.up_C;
-        op.bytes = to.nmul * ((op.stem ? 4.0 : es_in) * in_elems + es_out * (double)a.Ho * a.Wo * a.Cout * (op.in.size() > 1 ? 2 : 1));
+        op.bytes = to.nmul * ((op.route == ROUTE_STEM ? 4.0 : es_in) * in_elems + es_out * (double)a.Ho * a.Wo * a.Cout * (op.in.size() > 1 ? 2 : 1));
     }
     return true;
 }
@@ -628,15 +618,12 @@ void group_convs(Plan& plan, const PassInputs& e) {
     const std::vector<std::vector<int>> deps = op_dependencies(plan);   // in the current order
     const Ancestors anc = ancestors(plan, deps, false);
     auto args_at_max_batch = [&](const POp& op) {
-        ConvArgs a = op.conv;
-        const PTensor& ti = plan.tensors[op.in[0]];
-        a.N = (ti.nfix ? ti.nfix : plan.max_batch) * ti.nmul;
-        a.M = a.N * a.Ho * a.Wo;
+        ConvArgs a = conv_args_at(plan, op, plan.max_batch);
         a.residual = op.in.size() > 1 ? reinterpret_cast<const void*>(1) : nullptr;   // presence only (alignment rules look at ld_res)
         return a;
     };
     auto candidate = [&](const POp& op) {
-        if (op.kind != OP_CONV || !op.igemm || op.stem || op.from_deconv || !op.extra_in.empty()) return false;
+        if (op.kind != OP_CONV || op.route != ROUTE_IGEMM || op.from_deconv || !op.extra_in.empty()) return false;
         ConvArgs two[2] = {args_at_max_batch(op), args_at_max_batch(op)};
         return conv_igemm_group_supported(two, 2);
     };
@@ -798,8 +785,8 @@ void mark_stem_pair(Plan& plan, const PassInputs& e) {
     for (int k = 0; k + 1 < n; ++k) {
         const POp& st = plan.ops[k];
         POp& cv = plan.ops[k + 1];
-        if (st.kind != OP_CONV || !st.stem || st.conv.f32 || st.out.size() != 1) continue;
-        if (cv.kind != OP_CONV || !cv.igemm || cv.stem || cv.from_deconv || cv.in.size() != 1 || !cv.extra_in.empty() || cv.in[0] != st.out[0]) continue;
+        if (st.kind != OP_CONV || st.route != ROUTE_STEM || st.conv.f32 || st.out.size() != 1) continue;
+        if (cv.kind != OP_CONV || cv.route != ROUTE_IGEMM || cv.from_deconv || cv.in.size() != 1 || !cv.extra_in.empty() || cv.in[0] != st.out[0]) continue;
         const PTensor& mid = plan.tensors[st.out[0]];
         if (mid.storage < 0 || plan.storages[mid.storage].kind != ST_ARENA || is_binding_tensor(plan, mid.id) || is_binding_tensor(plan, owner_of(plan, mid.id))) continue;
         bool shared = false;   // any other op (or member of a grouped launch) that touches the block the intermediate lives in
@@ -815,13 +802,8 @@ void mark_stem_pair(Plan& plan, const PassInputs& e) {
             for (const POp& m : plan.ops[j].group) shared = shared || touches(m);
         }
         if (shared) continue;
-        ConvArgs a = st.conv, b = cv.conv;   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
-        const PTensor& t_in = plan.tensors[st.in[0]];
-        a.N = plan.explicit_batch ? (int)t_in.dims.d[0] : plan.max_batch;
-        a.M = a.N * a.Ho * a.Wo;
-        b.N = (mid.nfix ? mid.nfix : plan.max_batch) * mid.nmul;
-        b.M = b.N * b.Ho * b.Wo;
-        if (!conv_stem_pair_possible(a, b)) continue;
+        // as execute_plan fills them at the largest batch (pointers unset: geometry only)
+        if (!conv_stem_pair_possible(conv_args_at(plan, st, plan.max_batch), conv_args_at(plan, cv, plan.max_batch))) continue;
         cv.stem_pair = true;
     }
 }
@@ -839,7 +821,7 @@ void mark_stem_pair(Plan& plan, const PassInputs& e) {
 void mark_bneck_pair(Plan& plan, const PassInputs& e) {
     if (!e.opt.bneck_pair || e.dt != DT_F16 || e.int8 || CalibrationLowering::active()) return;   // (the calibration engine's observer reads every tensor an op writes)
     const int n = (int)plan.ops.size();
-    auto plain = [](const POp& op) { return op.kind == OP_CONV && op.igemm && !op.stem && !op.stem_pair && !op.bneck_pair && !op.from_deconv && op.extra_in.empty() && op.out.size() == 1; };
+    auto plain = [](const POp& op) { return op.kind == OP_CONV && op.route == ROUTE_IGEMM && !op.stem_pair && !op.bneck_pair && !op.from_deconv && op.extra_in.empty() && op.out.size() == 1; };
     for (int k = 0; k + 1 < n; ++k) {
         const POp& c0 = plan.ops[k];
         POp& c1 = plan.ops[k + 1];
@@ -863,11 +845,9 @@ void mark_bneck_pair(Plan& plan, const PassInputs& e) {
         if (shared || t_in.storage == mid.storage || t_out.storage == mid.storage) continue;
         if (t_in.layout != LAY_NHWC || t_out.layout != LAY_NHWC) continue;
         if (t_in.storage == t_out.storage && t_in.rcoff < t_out.rcoff + std::max(t_out.C, 1) && t_out.rcoff < t_in.rcoff + std::max(t_in.C, 1)) continue;
-        ConvArgs a = c0.conv, b = c1.conv;   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
-        a.N = (t_in.nfix ? t_in.nfix : plan.max_batch) * t_in.nmul;
-        a.M = a.N * a.Ho * a.Wo;
-        b.N = (mid.nfix ? mid.nfix : plan.max_batch) * mid.nmul;
-        b.M = b.N * b.Ho * b.Wo;
+        // as execute_plan fills them at the largest batch (pointers unset: geometry only)
+        const ConvArgs a = conv_args_at(plan, c0, plan.max_batch);
+        ConvArgs b = conv_args_at(plan, c1, plan.max_batch);
         b.residual = c1.in.size() > 1 ? reinterpret_cast<const void*>(1) : nullptr;   // presence only
         if (!conv_bneck_pair_possible(a, b)) continue;
         c1.bneck_pair = true;
@@ -895,13 +875,7 @@ void mark_sibling_pair(Plan& plan, const PassInputs& e) {
     if (lane_limit(e) > 1) return;   // (see above: with several lanes the plan, its op order included, stays what it was)
     const int n = (int)plan.ops.size();
     if (n < 2 || n > 4096) return;
-    auto member_args = [&](const POp& m) {
-        ConvArgs a = m.conv;   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
-        const PTensor& ti = plan.tensors[m.in[0]];
-        a.N = (ti.nfix ? ti.nfix : plan.max_batch) * ti.nmul;
-        a.M = a.N * a.Ho * a.Wo;
-        return a;
-    };
+    auto member_args = [&](const POp& m) { return conv_args_at(plan, m, plan.max_batch); };   // as execute_plan fills them at the largest batch (pointers unset: geometry only)
     auto shares_elements = [&](int t, int u) {
         const PTensor &x = plan.tensors[t], &y = plan.tensors[u];
         if (x.storage != y.storage) return false;

@@ -163,11 +163,8 @@ int32_t tune_engine(trtx_engine* e, bool time_now) {
     std::vector<Item> items;
     for (size_t k = 0; k < plan.ops.size(); ++k) {
         POp& op = plan.ops[k];
-        if (op.kind != OP_CONV || !op.igemm || op.stem) continue;
-        const PTensor& t0 = plan.tensors[op.in[0]];
-        ConvArgs a = op.conv;  // as execute_plan fills it at the largest batch
-        a.N = (t0.nfix ? t0.nfix : plan.max_batch) * t0.nmul;
-        a.M = a.N * a.Ho * a.Wo;
+        if (op.kind != OP_CONV || op.route != ROUTE_IGEMM) continue;
+        ConvArgs a = conv_args_at(plan, op, plan.max_batch);  // as execute_plan fills it at the largest batch
         a.residual = op.in.size() > 1 ? reinterpret_cast<const void*>(1) : nullptr;  // only its presence matters here
         Item it;
         it.op = (int)k;
