@@ -578,6 +578,11 @@ int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld
                                   trtx_stream_t stream);
 int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd, int hd,
                                    float scale, trtx_stream_t stream);
+/* trtx_op_psa_attention_f16's op on the matrix pipe (kernels/attention_mfma.hip; what fp16 engines run for heads of 72, and for heads of 64 with TRTX_PSA_MFMA=2): the same arguments and
+ * refusals, kd 32 / hd 64 or kd 36 / hd 72.  Both products are MFMAs; P is rounded to fp16 as the second one's operand, everything else stays fp32 with one
+ * rounding of O at the store, and the V image holds the input's bits.  Vector accesses where pointers and strides allow, element-wise ones otherwise. */
+int32_t trtx_op_psa_attention_mfma_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
+                                       float scale, trtx_stream_t stream);
 /* The area attention on separate operands (tests / tools; kernels/attention_mfma.hip), as YOLOv13's AAttn has them (yolov13/src/block.cpp:303-423: q | k
  * come from one 1x1 convolution, v from another).  q, k, v: NHWC fp16 [B][N][ld_q / ld_k / ld_v]; head h reads q channels h * kd .., k channels h * kd ..
  * and v channels h * hd ..; out[b][n][h * hd + d] as trtx_op_area_attention_f16 and, given the same values, bit-equal to it.  No V image is written.

@@ -746,6 +746,15 @@ def psa_attention(qkv, heads, scale, out=None, vimg=None, out_ld=None, v_ld=None
     return _attention(lib().trtx_op_psa_attention_f16, "trtx_op_psa_attention_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, ())
 
 
+def psa_attention_mfma(qkv, heads, scale, out=None, vimg=None, out_ld=None, v_ld=None, qkv_ld=None, kd=32, hd=64):
+    """The PSA attention on MFMA (kernels/attention_mfma.hip): psa_attention's tensors and arguments, kd / hd 32 / 64 or 36 / 72.  -> (O, V image)"""
+    import torch
+    B, N, _ = qkv.shape
+    out = torch.empty((B, N, heads * hd), dtype=torch.float16, device=qkv.device) if out is None else out
+    vimg = torch.empty((B, N, heads * hd), dtype=torch.float16, device=qkv.device) if vimg is None else vimg
+    return _attention(lib().trtx_op_psa_attention_mfma_f16, "trtx_op_psa_attention_mfma_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, ())
+
+
 def area_attention(qkv, heads, area, scale, out=None, vimg=None, out_ld=None, v_ld=None, qkv_ld=None, kd=32, hd=32):
     """The area attention on MFMA (kernels/attention_mfma.hip): as psa_attention, the N pixels of an image split into `area` contiguous ranges."""
     import torch

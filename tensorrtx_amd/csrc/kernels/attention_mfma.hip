@@ -200,6 +200,182 @@ __global__ __launch_bounds__(THREADS) void area_attention_mfma_kernel(const _Flo
     }
 }
 
+// 4 consecutive halves: one 8-byte load where the address allows it
+__device__ inline h4 load4(const _Float16* p, bool vec) {
+    if (vec) return *reinterpret_cast<const h4*>(p);
+    h4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = p[i];
+    return r;
+}
+
+// One 32-key group of the online softmax as the area kernel above has it inline (which keeps its text, and with it its instruction stream), a lane's share of it: s0 | s1 are the unscaled scores of the lane's query against the keys key0 .. key0 + 7
+// of the chunk, of which `cnt` are in range.  Raises the running max mx (exchanged over lane >> 4), folds the group into the lane's share lsum of the
+// denominator, leaves exp(s - max) rounded to fp16 in pf and returns the factor exp(old max - new max) that rescales what was accumulated.
+__device__ inline float softmax_group(f4 s0, f4 s1, int key0, int cnt, float scale, float& mx, float& lsum, h8& pf) {
+    float s[8];
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        s[j] = key0 + j < cnt ? (j < 4 ? s0[j] : s1[j - 4]) * scale : -INFINITY;
+        tmax = fmaxf(tmax, s[j]);
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+    const float mnew = fmaxf(mx, tmax);   // finite: the group has a key in range
+    const float alpha = __expf(mx - mnew);
+    mx = mnew;
+    float psum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float p = __expf(s[j] - mnew);
+        psum += p;
+        pf[j] = (_Float16)p;
+    }
+    lsum = lsum * alpha + psum;
+    return alpha;
+}
+
+// PSA attention (YOLO11's C2PSA, YOLOv10's PSA; the tensors and the contract of kernels/attention.hip) in the same transposed mapping: every pixel of the
+// image is a key, the heads are (PKD, HD) = (32, 64) or yolov10m's (36, 72), neither of which the area kernel's one k-step and whole 16-row tiles cover.
+//   * Scores.  Channels 0..31 are the 16x16x32 step as above.  PKD = 36 adds a tail step on v_mfma_f32_16x16x16_f16 (k = 4 (lane >> 4) + j): the lanes
+//     with lane >> 4 == 0 carry channels 32..35 of q and of the K row, the other three groups carry zeros made in registers - the reduction is padded to
+//     48, not 64: the 16-deep step has half the passes of a second 32-deep one and the K rows stay 80 bytes in LDS.  No lane reads past channel 35.
+//   * K rows are fetched in 8-byte pieces (PKD / 4 per row): with heads of 144 halves q and v start on 16-byte boundaries, k at +36 halves does not.
+//   * O^T has ceil(HD / 16) tiles.  HD = 72 makes the fifth one half live: its V^T fragment is the LDS row for lane & 15 < 8 and a register zero above
+//     (V^T has HD rows, none for the padding), and only the lane groups 0 and 1 (channels 64..71) store it.
+// Numerics, masking of keys and queries beyond N, and the V image are the area kernel's.
+template <int PKD, int HD>
+__global__ __launch_bounds__(THREADS) void psa_attention_mfma_kernel(const _Float16* __restrict__ qkv, int ld_qkv, _Float16* __restrict__ out, int ld_out,
+                                                                        _Float16* __restrict__ vimg, int ld_v, int N, float scale, int vec_in, int vec_o,
+                                                                        int vec_v) {
+    constexpr int T = THREADS;
+    constexpr int KG = PKD / 4;                   // 4-channel pieces of a K row
+    constexpr int KL = (KC * KG + T - 1) / T;     // K pieces a thread stages per chunk (the last round partly idle when PKD = 36)
+    constexpr int VG = HD / 8;                    // 8-channel groups of a V row
+    constexpr int VL = (KC * VG + T - 1) / T;
+    constexpr int OT = (HD + 15) / 16;            // accumulator tiles of O^T
+    constexpr bool TAIL = PKD > KD;
+    static_assert((PKD == KD || PKD == KD + 4) && PKD <= KS_LD && HD % 8 == 0, "one 32-deep step, at most one 4-channel tail, whole 8-channel V groups");
+    __shared__ __attribute__((aligned(16))) _Float16 Ks[KC][KS_LD];
+    __shared__ __attribute__((aligned(16))) _Float16 Vt[HD][VT_LD];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int h = blockIdx.y;
+    const long pix0 = (long)blockIdx.z * N;   // first pixel of the image
+    const _Float16* qh = qkv + h * (2 * PKD + HD);
+    const _Float16* kh = qh + PKD;
+    const _Float16* vh = qh + 2 * PKD;
+    const int q0 = blockIdx.x * QB;
+    const h8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const h4 zero4 = {0, 0, 0, 0};
+
+    for (int i = t; i < QB * VG; i += T) {   // the V image of this workgroup's own 64 query pixels
+        const int n = q0 + i / VG, dg = i % VG;
+        if (n < N) store8(vimg + (pix0 + n) * ld_v + h * HD + 8 * dg, load8(vh + (pix0 + n) * ld_qkv + 8 * dg, vec_in), vec_v);
+    }
+    // Q^T fragments: query i16 of the wave, channels 8 g .. 8 g + 7; the tail's channels 32 + 4 g .. 35 + 4 g exist for g == 0 only
+    const int qn = q0 + wave * QW + i16;
+    const h8 qf = qn < N ? load8(qh + (pix0 + qn) * ld_qkv + 8 * g, vec_in) : zero8;
+    h4 qt = zero4;
+    if (TAIL && g == 0 && qn < N) qt = load4(qh + (pix0 + qn) * ld_qkv + KD, vec_in);
+
+    h4 kreg[KL];
+    h8 vreg[VL];
+    auto fetch = [&](int c0) {   // global -> registers; rows beyond the image become zeros without a read
+#pragma unroll
+        for (int u = 0; u < KL; ++u) {
+            const int idx = t + u * T, key = c0 + idx / KG;
+            kreg[u] = idx < KC * KG && key < N ? load4(kh + (pix0 + key) * ld_qkv + 4 * (idx % KG), vec_in) : zero4;
+        }
+#pragma unroll
+        for (int u = 0; u < VL; ++u) {
+            const int idx = t + u * T, kv = c0 + idx / VG;
+            vreg[u] = idx < KC * VG && kv < N ? load8(vh + (pix0 + kv) * ld_qkv + 8 * (idx % VG), vec_in) : zero8;
+        }
+    };
+    auto stage = [&]() {         // registers -> LDS: K rows as they are, V transposed
+#pragma unroll
+        for (int u = 0; u < KL; ++u) {
+            const int idx = t + u * T;
+            if (idx < KC * KG) *reinterpret_cast<h4*>(&Ks[idx / KG][4 * (idx % KG)]) = kreg[u];
+        }
+#pragma unroll
+        for (int u = 0; u < VL; ++u) {
+            const int idx = t + u * T, kv = idx / VG, d0 = 8 * (idx % VG);
+            if (idx < KC * VG) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) Vt[d0 + j][kv] = vreg[u][j];
+            }
+        }
+    };
+
+    f4 acc[OT];
+#pragma unroll
+    for (int o = 0; o < OT; ++o) acc[o] = f4{0.f, 0.f, 0.f, 0.f};
+    float mx = -INFINITY, lsum = 0.f;
+
+    fetch(0);
+    for (int c0 = 0; c0 < N; c0 += KC) {
+        __syncthreads();   // the previous chunk's fragment reads are done
+        stage();
+        __syncthreads();
+        if (c0 + KC < N) fetch(c0 + KC);   // in flight while this chunk is multiplied
+        const int cnt = min(KC, N - c0);
+#pragma unroll
+        for (int sub = 0; sub < KC / 32; ++sub) {
+            if (32 * sub >= cnt) break;   // uniform: no key of this group is in range
+            const int krow = 32 * sub + 8 * (i16 >> 2) + (i16 & 3);
+            const h8 k0 = *reinterpret_cast<const h8*>(&Ks[krow][8 * g]);
+            const h8 k1 = *reinterpret_cast<const h8*>(&Ks[krow + 4][8 * g]);
+            h4 kt0 = zero4, kt1 = zero4;
+            if (TAIL && g == 0) {
+                kt0 = *reinterpret_cast<const h4*>(&Ks[krow][KD]);
+                kt1 = *reinterpret_cast<const h4*>(&Ks[krow + 4][KD]);
+            }
+            h8 vf[OT];
+#pragma unroll
+            for (int o = 0; o < OT; ++o)   // the rows of the last tile beyond HD are zeros
+                vf[o] = 16 * o + i16 < HD ? *reinterpret_cast<const h8*>(&Vt[min(16 * o + i16, HD - 1)][32 * sub + 8 * g]) : zero8;
+            const f4 z = {0.f, 0.f, 0.f, 0.f};
+            f4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, qf, z, 0, 0, 0);
+            f4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, qf, z, 0, 0, 0);
+            // The tail's product starts from zero and is added on the vector ALU.  Chained onto the 32-deep step's accumulator (SrcC = that step's vDst,
+            // two instructions behind it) it gave wrong scores on the MI355X for some queries and key counts (N = 2 .. 5, 17, 24, 31 ...), the same
+            // launches right with this form: the 16-deep MFMA read the accumulator before the 32-deep one had written all of it.
+            if constexpr (TAIL) {
+                s0 += __builtin_amdgcn_mfma_f32_16x16x16f16(kt0, qt, z, 0, 0, 0);
+                s1 += __builtin_amdgcn_mfma_f32_16x16x16f16(kt1, qt, z, 0, 0, 0);
+            }
+            h8 pf;
+            const float alpha = softmax_group(s0, s1, 32 * sub + 8 * g, cnt, scale, mx, lsum, pf);
+#pragma unroll
+            for (int o = 0; o < OT; ++o) {
+                acc[o] *= alpha;
+                acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[o], pf, acc[o], 0, 0, 0);
+            }
+        }
+    }
+    lsum += __shfl_xor(lsum, 16);
+    lsum += __shfl_xor(lsum, 32);
+    if (qn >= N) return;
+    const float inv = 1.0f / lsum;
+    _Float16* op = out + (pix0 + qn) * ld_out + h * HD + 4 * g;   // O^T tile o, rows 4 g + r: channels 16 o + 4 g + r of the query
+#pragma unroll
+    for (int o = 0; o < OT; ++o) {
+        if (16 * o + 4 * g >= HD) continue;   // the padding rows of the last tile (HD is a multiple of 4: a lane's four rows are live or padding together)
+        h4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = (_Float16)(acc[o][j] * inv);
+        if (vec_o) {
+            *reinterpret_cast<h4*>(op + 16 * o) = r;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) op[16 * o + j] = r[j];
+        }
+    }
+}
+
 bool aligned(const void* p, int ld, int bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0 && ((size_t)ld * 2) % bytes == 0; }
 
 }  // namespace
@@ -219,6 +395,26 @@ int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, v
                        ld_qkv, static_cast<_Float16*>(out), ld_out, static_cast<_Float16*>(vimg), ld_v, N, Na, heads, scale, vec_in, vec_in, vec_in,
                        (int)aligned(out, ld_out, 8), (int)aligned(vimg, ld_v, 16));
     return check_launch("area_attention");
+}
+
+bool psa_attention_mfma_supported(int kd, int hd) { return (kd == 32 && hd == 64) || (kd == 36 && hd == 72); }
+
+int32_t psa_attention_mfma_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd, float scale,
+                               hipStream_t s) {
+    if (!psa_attention_mfma_supported(kd, hd) || B < 1 || heads < 1 || N < 1 || B > 65535 || heads > 65535 || ld_qkv < heads * (2 * kd + hd) ||
+        ld_out < heads * hd || ld_v < heads * hd)
+        return TRTX_ERR_UNSUPPORTED;
+    // 16-byte loads of q and v, 8-byte loads of k and 16-byte stores of the V image, 8-byte stores of O where base and channel stride allow (a head's
+    // q, v and O channels then start on such boundaries for both head shapes, k on an 8-byte one); element-wise otherwise
+    const dim3 grid((N + QB - 1) / QB, heads, B);
+    const int vec_in = aligned(qkv, ld_qkv, 16), vec_o = aligned(out, ld_out, 8), vec_v = aligned(vimg, ld_v, 16);
+    if (kd == 36)
+        hipLaunchKernelGGL((psa_attention_mfma_kernel<36, 72>), grid, dim3(THREADS), 0, s, static_cast<const _Float16*>(qkv), ld_qkv, static_cast<_Float16*>(out),
+                           ld_out, static_cast<_Float16*>(vimg), ld_v, N, scale, vec_in, vec_o, vec_v);
+    else
+        hipLaunchKernelGGL((psa_attention_mfma_kernel<32, 64>), grid, dim3(THREADS), 0, s, static_cast<const _Float16*>(qkv), ld_qkv, static_cast<_Float16*>(out),
+                           ld_out, static_cast<_Float16*>(vimg), ld_v, N, scale, vec_in, vec_o, vec_v);
+    return check_launch("psa_attention_mfma");
 }
 
 bool area_attention_split_supported(int kd, int hd) { return area_attention_supported(kd, hd); }

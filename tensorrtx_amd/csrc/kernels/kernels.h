@@ -214,6 +214,12 @@ bool conv_dw_supported(const ConvArgs& a);
 bool psa_attention_supported(int kd, int hd);
 int32_t psa_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
                           float scale, hipStream_t s);
+// the same op on the matrix pipe (attention_mfma.hip): the tensors and arguments of psa_attention_f16, (kd, hd) = (32, 64) or (36, 72); P is rounded to
+// fp16 as the second MFMA's operand (the area kernel's numerics).  16-byte loads of q and v, 8-byte loads of k, 16-byte stores of the V image and 8-byte
+// stores of O where base pointer and channel stride allow, element-wise otherwise.  What the executor issues at an OP_ATTENTION with area 0 and i[5] set.
+bool psa_attention_mfma_supported(int kd, int hd);
+int32_t psa_attention_mfma_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
+                               float scale, hipStream_t s);
 // area attention on the matrix pipe (attention_mfma.hip; YOLOv12's AAttn): the same tensors as psa_attention_f16, the N pixels of an image
 // split into `area` contiguous ranges of N / area pixels that attend within themselves (area = 1: the whole image); kd == hd == 32.
 // A base pointer or channel stride that rules out 16-byte accesses takes element-wise loads / stores, not an error.

@@ -338,6 +338,12 @@ extern "C" int32_t trtx_op_psa_attention_f16(const void* qkv, int ld_qkv, void* 
     return psa_attention_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, kd, hd, scale, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int32_t trtx_op_psa_attention_mfma_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd,
+                                                  int hd, float scale, trtx_stream_t stream) {
+    if (!qkv || !out || !vimg) return TRTX_ERR_INVALID;
+    return psa_attention_mfma_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, kd, hd, scale, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area,
                                               int kd, int hd, float scale, trtx_stream_t stream) {
     if (!qkv || !out || !vimg) return TRTX_ERR_INVALID;

@@ -41,6 +41,7 @@ Options read_options() {
     o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
     o.conv_view = !env_is("TRTX_CONV_VIEW", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
+    o.psa_mfma = env_int("TRTX_PSA_MFMA", 1);
     o.aattn_split = !env_is("TRTX_AATTN_SPLIT", 0);
     o.hgconv = !env_is("TRTX_HGCONV", 0);
     o.dsconv = env_int("TRTX_DSCONV", 1);

@@ -11,6 +11,11 @@ namespace trtx {
 
 namespace {
 
+// The PSA head shapes that take the MFMA kernel unless told otherwise; TRTX_PSA_MFMA=2 takes the others too.  Both shapes measured faster in every pair
+// and stay inside the engine tests' bounds ("PSA attention on the matrix pipe"), but tests/test_yolo12_cpu.py pins the lowered op list of the
+// (32, 64) subgraph as it was before area attention existed, so that shape's default lowering stays what it was.
+bool psa_mfma_default(int kd, int hd) { return kd == 36 && hd == 72; }
+
 int ew_code(int trt_op) {
     switch (trt_op) {
         case TRTX_ELEMENTWISE_SUM: return EW_SUM;
@@ -168,6 +173,8 @@ struct Lowerer {
         POp& op = add_op(OP_ATTENTION, "attention:" + net.tensors[f.qkv].name, {in}, {o, v});
         op.i[0] = f.heads; op.i[1] = f.N; op.i[2] = f.kd; op.i[3] = f.hd;
         op.i[4] = f.area;
+        // PSA on the matrix pipe (psa_attention_mfma_f16) unless TRTX_PSA_MFMA=0; 2 also takes a head shape that is off it by default
+        op.i[5] = f.area == 0 && psa_attention_mfma_supported(f.kd, f.hd) && (opt.psa_mfma >= 2 || (opt.psa_mfma == 1 && psa_mfma_default(f.kd, f.hd)));
         op.f[0] = f.scale;
         const double B = plan.tensors[in].nfix;
         op.flops = 2.0 * B * f.heads * (double)f.N * (f.N / std::max(f.area, 1)) * (f.kd + f.hd);   // area * (N / area)^2 score and value products
