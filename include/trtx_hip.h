@@ -583,6 +583,15 @@ int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void* out, int l
  * rounding of O at the store, and the V image holds the input's bits.  Vector accesses where pointers and strides allow, element-wise ones otherwise. */
 int32_t trtx_op_psa_attention_mfma_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int kd, int hd,
                                        float scale, trtx_stream_t stream);
+/* The attention of fp32 engines (tests / tools; kernels/attention_f32.hip; what an fp32 engine runs with TRTX_ATTENTION_F32=1 in place of the generic
+ * gathers, two matmuls and softmax): the attention of YOLO11's C2PSA (yolo11/src/block.cpp:287-339), YOLOv10's PSA (yolov10/src/block.cpp:297-386) and
+ * YOLOv12's AAttn (yolov12/src/block.cpp:522-625) with trtx_op_area_attention_f16's tensors and arguments, every tensor fp32 (ld_* count floats);
+ * area = 1 is plain multi-head attention.  (kd, hd) = (32, 32), (32, 64) or (36, 72).  Both products run on v_mfma_f32_16x16x4_f32; scores, softmax, P
+ * and O are fp32 throughout and the V image holds the input's bits.  16-byte accesses where base pointers and strides allow, element-wise ones otherwise,
+ * bit-equal either way.  TRTX_ERR_UNSUPPORTED, nothing launched: another kd / hd, a negative count, area < 1, N % area != 0, B > 65535,
+ * heads * area > 65535, ld_qkv < heads * (2 kd + hd), ld_out or ld_v < heads * hd.  B, heads or N of 0: TRTX_OK, nothing launched. */
+int32_t trtx_op_attention_f32(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd, int hd,
+                              float scale, trtx_stream_t stream);
 /* The area attention on separate operands (tests / tools; kernels/attention_mfma.hip), as YOLOv13's AAttn has them (yolov13/src/block.cpp:303-423: q | k
  * come from one 1x1 convolution, v from another).  q, k, v: NHWC fp16 [B][N][ld_q / ld_k / ld_v]; head h reads q channels h * kd .., k channels h * kd ..
  * and v channels h * hd ..; out[b][n][h * hd + d] as trtx_op_area_attention_f16 and, given the same values, bit-equal to it.  No V image is written.

@@ -764,6 +764,20 @@ def area_attention(qkv, heads, area, scale, out=None, vimg=None, out_ld=None, v_
     return _attention(lib().trtx_op_area_attention_f16, "trtx_op_area_attention_f16", qkv, heads, scale, out, vimg, out_ld, v_ld, qkv_ld, kd, hd, (area,))
 
 
+def attention_f32(qkv, heads, area, scale, out=None, vimg=None, out_ld=None, v_ld=None, qkv_ld=None, kd=32, hd=32):
+    """The attention of fp32 engines (kernels/attention_f32.hip): area_attention's tensors and arguments in CUDA fp32, area = 1 being PSA; kd / hd
+    32 / 32, 32 / 64 or 36 / 72.  -> (O, V image)"""
+    import torch
+    B, N, _ = qkv.shape
+    out = torch.empty((B, N, heads * hd), dtype=torch.float32, device=qkv.device) if out is None else out
+    vimg = torch.empty((B, N, heads * hd), dtype=torch.float32, device=qkv.device) if vimg is None else vimg
+    for t in (qkv, out, vimg):
+        assert t.is_cuda and t.dtype == torch.float32
+    check(lib().trtx_op_attention_f32(_p(qkv), qkv_ld or qkv.stride(1), _p(out), out_ld or out.stride(1), _p(vimg), v_ld or vimg.stride(1), B, heads, N, area,
+                                      kd, hd, ctypes.c_float(scale), _stream()), "trtx_op_attention_f32")
+    return out, vimg
+
+
 def area_attention_split(q, k, v, heads, area, scale, out=None, q_ld=None, k_ld=None, v_ld=None, out_ld=None, kd=32, hd=32):
     """The area attention on separate operands (kernels/attention_mfma.hip; YOLOv13's AAttn): q, k: CUDA fp16 [B, N, heads * kd], v: [B, N, heads * hd],
     each a tensor of its own or a channel slice of a wider one (pixel stride t.stride(1), or the *_ld given); out likewise (allocated when None).  -> O"""

@@ -226,6 +226,13 @@ int32_t psa_attention_mfma_f16(const void* qkv, int ld_qkv, void* out, int ld_ou
 bool area_attention_supported(int kd, int hd);
 int32_t area_attention_f16(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd,
                            int hd, float scale, hipStream_t s);
+// attention of fp32 engines on v_mfma_f32_16x16x4_f32 (attention_f32.hip): the tensors and arguments of area_attention_f16 in fp32, area = 1 being PSA;
+// (kd, hd) = (32, 32), (32, 64) or (36, 72).  Everything stays fp32 (P too); the V image holds the input's bits.  16-byte accesses where base pointer and
+// channel stride allow, element-wise otherwise, bit-equal either way.  Empty tensors (B, heads or N of 0) are TRTX_OK without a launch.  What the
+// executor issues at an OP_ATTENTION of dtype DT_F32 (TRTX_ATTENTION_F32=1).
+bool attention_f32_supported(int kd, int hd);
+int32_t attention_f32(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd, int hd,
+                      float scale, hipStream_t s);
 // the same kernel body on separate operands (YOLOv13's AAttn, yolov13/src/block.cpp:303-423: q | k from one convolution, v from another): q, k, v
 // are NHWC fp16 [B][N][ld], head h reads q and k channels h*kd .. and v channels h*hd ..; O as above, no V image (v is a tensor already).  Given the
 // same values O is bit-equal to area_attention_f16's.  16-byte loads / 8-byte stores per operand where its base and stride allow, element-wise otherwise.

@@ -350,6 +350,14 @@ extern "C" int32_t trtx_op_area_attention_f16(const void* qkv, int ld_qkv, void*
     return area_attention_f16(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, area, kd, hd, scale, static_cast<hipStream_t>(stream));
 }
 
+// the attention of fp32 engines (kernels/attention_f32.hip): yolo11/src/block.cpp:287-339, yolov10/src/block.cpp:297-386 (area 1) and
+// yolov12/src/block.cpp:522-625 on fp32 tensors
+extern "C" int32_t trtx_op_attention_f32(const void* qkv, int ld_qkv, void* out, int ld_out, void* vimg, int ld_v, int B, int heads, int N, int area, int kd,
+                                         int hd, float scale, trtx_stream_t stream) {
+    if (!qkv || !out || !vimg) return TRTX_ERR_INVALID;
+    return attention_f32(qkv, ld_qkv, out, ld_out, vimg, ld_v, B, heads, N, area, kd, hd, scale, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int32_t trtx_op_area_attention_split_f16(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, void* out, int ld_out, int B,
                                                     int heads, int N, int area, int kd, int hd, float scale, trtx_stream_t stream) {
     if (!q || !k || !v || !out) return TRTX_ERR_INVALID;

@@ -38,6 +38,8 @@ struct Options {
     bool area_attention = true; // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
     int psa_mfma = 1;            // TRTX_PSA_MFMA=0: PSA attention (YOLO11's C2PSA, YOLOv10's PSA) stays on the vector-ALU kernel (kernels/attention.hip) instead of the MFMA one;
                                  //            unset: the MFMA kernel for heads of kd 36 / hd 72 only; 2: for every head shape it takes, kd 32 / hd 64 too (psa_mfma_default, lower.cpp)
+    bool attention_f32 = false;  // TRTX_ATTENTION_F32=1: fp32 engines run PSA and area attention as one OP_ATTENTION on the fp32 matrix instruction (kernels/attention_f32.hip)
+                                 //            instead of the generic linear path; off by default: three tests pin the fp32 lowering as generic
     bool aattn_split = true;     // TRTX_AATTN_SPLIT=0: YOLOv13 area attention (q | k and v from two convolutions) stays on the generic linear path (shuffles, slices, matmul, softmax)
     bool hgconv = true;         // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
     int dsconv = 1;              // TRTX_DSCONV=0: YOLOv13's DSConv (depthwise k x k -> 1x1) stays two launches, conv_dw and the 1x1 (no kernels/conv_dw_pw.hip);

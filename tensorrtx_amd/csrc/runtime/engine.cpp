@@ -495,7 +495,10 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 break;
             case OP_ATTENTION: {
                 const PTensor &to2 = plan.tensors[op.out[1]];
-                if (op.i[4] > 0)
+                if (op.dtype == DT_F32)   // fp32 engines (TRTX_ATTENTION_F32=1): one kernel for PSA (area 0 -> 1) and area attention
+                    st = attention_f32(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, R.ptr(op.out[1]), to2.ld, nb(t0), op.i[0], op.i[1], std::max(op.i[4], 1),
+                                       op.i[2], op.i[3], op.f[0], stream);
+                else if (op.i[4] > 0)
                     st = area_attention_f16(R.ptr(op.in[0]), t0.ld, R.ptr(op.out[0]), to.ld, R.ptr(op.out[1]), to2.ld, nb(t0), op.i[0], op.i[1], op.i[4],
                                             op.i[2], op.i[3], op.f[0], stream);
                 else if (op.i[5])

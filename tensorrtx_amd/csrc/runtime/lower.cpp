@@ -174,11 +174,12 @@ struct Lowerer {
         op.i[0] = f.heads; op.i[1] = f.N; op.i[2] = f.kd; op.i[3] = f.hd;
         op.i[4] = f.area;
         // PSA on the matrix pipe (psa_attention_mfma_f16) unless TRTX_PSA_MFMA=0; 2 also takes a head shape that is off it by default
-        op.i[5] = f.area == 0 && psa_attention_mfma_supported(f.kd, f.hd) && (opt.psa_mfma >= 2 || (opt.psa_mfma == 1 && psa_mfma_default(f.kd, f.hd)));
+        // (fp16 engines; an fp32 engine's op - op.dtype DT_F32, matched under TRTX_ATTENTION_F32=1 - runs attention_f32 for PSA and area attention alike)
+        op.i[5] = dt == DT_F16 && f.area == 0 && psa_attention_mfma_supported(f.kd, f.hd) && (opt.psa_mfma >= 2 || (opt.psa_mfma == 1 && psa_mfma_default(f.kd, f.hd)));
         op.f[0] = f.scale;
         const double B = plan.tensors[in].nfix;
         op.flops = 2.0 * B * f.heads * (double)f.N * (f.N / std::max(f.area, 1)) * (f.kd + f.hd);   // area * (N / area)^2 score and value products
-        op.bytes = 2.0 * B * f.N * ((double)plan.tensors[in].C + 2.0 * f.heads * f.hd);
+        op.bytes = (dt == DT_F16 ? 2.0 : 4.0) * B * f.N * ((double)plan.tensors[in].C + 2.0 * f.heads * f.hd);
         pt_of[f.out_o] = o;
         pt_of[f.out_v] = v;
         return true;

@@ -631,10 +631,14 @@ void claim_attention(const NetView& g, const AttentionCore& c, std::vector<int> 
 
 // ---- YOLO11 PSA attention (yolo11/src/block.cpp:287-339): qkv -> view (B, heads, 2kd+hd, N) -> the core above -> view
 // (B, heads*hd, H, W), and v viewed the same way for `pe`.  Anything else keeps the generic linear path.
-// fp16 engines only (fp32 engines, the tolerance build, keep the generic path).
+// fp16 engines; fp32 engines (the tolerance build) keep the generic path unless TRTX_ATTENTION_F32=1 hands the head shapes of kernels/attention_f32.hip
+// to that kernel (not kINT8 networks).
+bool attention_f32_admitted(const NetView& g) { return g.dt == DT_F32 && g.opt.attention_f32 && !g.net.int8; }
+
 void match_psa_attention(const NetView& g, Fusions& f) {
     const Network& net = g.net;
-    if (!net.explicit_batch || g.dt != DT_F16) return;
+    const bool f32 = attention_f32_admitted(g);
+    if (!net.explicit_batch || (g.dt != DT_F16 && !f32)) return;
     for (size_t li = 0; li < net.layers.size(); ++li) {
         AttentionCore c;
         if (f.absorbed[li] || !match_attention_core(g, (int)li, &c)) continue;
@@ -657,7 +661,8 @@ void match_psa_attention(const NetView& g, Fusions& f) {
             return r.kind == L_SHUFFLE && ident(r.perm1, 4) && ident(r.perm2, 4) && r.reshape.nb == 4 && o.nb == 4 && o.d[0] == dx.d[0] &&
                    o.d[1] == dx.d[1] * c.hd && o.d[2] == dq.d[2] && o.d[3] == dq.d[3];
         };
-        if (!view_bchw(lre) || !view_bchw(lvre) || !psa_attention_supported((int)c.kd, (int)c.hd)) continue;
+        if (!view_bchw(lre) || !view_bchw(lvre)) continue;
+        if (!(f32 ? attention_f32_supported((int)c.kd, (int)c.hd) : psa_attention_supported((int)c.kd, (int)c.hd))) continue;
         AttentionFuse a;
         a.qkv = tqkv;
         a.out_o = net.layers[lre].outputs[0];
@@ -671,10 +676,11 @@ void match_psa_attention(const NetView& g, Fusions& f) {
 // [reshape (B area, N / area, heads, 96), transpose {0,2,3,1}] -> the core above on q / k / v slices of 32 rows -> transpose {0,3,1,2}
 // -> reshape (B, H, W, C) -> transpose {0,3,1,2}, and v through the same three shuffles for `pe`.  In NHWC that is: area a = the
 // pixel range [a N/area, (a+1) N/area) of an image, head h = channels h*96 + {q | k | v}.  Anything else keeps the generic linear
-// path.  fp16 explicit-batch engines only, and not with TRTX_AREA_ATTENTION=0.
+// path.  fp16 explicit-batch engines, and fp32 ones with TRTX_ATTENTION_F32=1; not with TRTX_AREA_ATTENTION=0.
 void match_area_attention(const NetView& g, Fusions& f) {
     const Network& net = g.net;
-    if (!net.explicit_batch || g.dt != DT_F16 || !g.opt.area_attention) return;
+    const bool f32 = attention_f32_admitted(g);
+    if (!net.explicit_batch || (g.dt != DT_F16 && !f32) || !g.opt.area_attention) return;
     for (size_t li = 0; li < net.layers.size(); ++li) {
         AttentionCore c;
         if (f.absorbed[li] || !match_attention_core(g, (int)li, &c)) continue;
@@ -696,7 +702,8 @@ void match_area_attention(const NetView& g, Fusions& f) {
         if (dl.d[0] != B || dl.d[1] != N || dl.d[2] != C3 || B < 1 || Na < 1 || Ba % B != 0 || heads * rows != C3) continue;
         const int64_t area = Ba / B;
         if (area < 1 || Na * area != N) continue;   // the area count must divide the pixels
-        if (!g.only_used_by(tl, {l2}) || !area_attention_supported((int)c.kd, (int)c.hd)) continue;
+        if (!g.only_used_by(tl, {l2})) continue;
+        if (!(f32 ? attention_f32_supported((int)c.kd, (int)c.hd) : area_attention_supported((int)c.kd, (int)c.hd))) continue;
         // the way back to an image, for O and for v: transpose {0,3,1,2} -> reshape (B, H, W, heads*hd) -> transpose {0,3,1,2}
         auto image_of = [&](int t_from, int skip, int* used3, int* t_img) {
             int a = -1;

@@ -95,6 +95,7 @@ std::string Plan::describe_json() const {
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];
         if (op.kind == OP_ATTENTION && op.i[4] > 0) o << ",\"area\":" << op.i[4] << ",\"kernel\":\"mfma\"";
         if (op.kind == OP_ATTENTION && op.i[5]) o << ",\"mfma\":true";   // PSA on psa_attention_mfma_f16
+        if (op.kind == OP_ATTENTION && op.dtype == DT_F32) o << ",\"f32\":true";   // an fp32 engine's: attention_f32
         if (op.kind == OP_ATTENTION_SPLIT)
             o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3] << ",\"area\":" << op.i[4] << ",\"k_offset\":" << op.i[5];
         if (op.kind == OP_HGCONV)
