@@ -493,6 +493,17 @@ int32_t trtx_op_conv_dw_pw_f16(const void* in, int N, int H, int W, int Cin, int
 int32_t trtx_op_conv_dw_pw_or_two_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const float* w_dw_taps_c, const float* bias_dw, int k, int stride,
                                       int dilation, const void* w_pw_packed, const float* bias, int Cout, int act1, const void* residual, int ld_res, int act2,
                                       void* mid, void* out, int ld_out, trtx_stream_t stream);
+/* YOLOv9's downsamplers (yolov9/src/block.cpp:256-290: AConv = avg-pool 2x2 stride 1 -> 3x3 stride-2 pad-1 convolution -> BatchNorm -> x sigmoid(x); ADown
+ * = the same pool, its first channel half through that convolution, its second through max-pool 3x3 stride 2 pad 1 -> 1x1 convolution) with the pools inside
+ * the convolution's launch (kernels/conv_pool.hip).  mode 0: out = act(conv3x3_s2_p1(avg2x2(in)) + bias); mode 1: out = act(conv1x1(max3x3_s2_p1(avg2x2(in)))
+ * + bias).  in NHWC fp16 [N][H][W], the UNPOOLED tensor, Cin channels at channel stride ld_in; out NHWC fp16 [N][H/2][W/2] with channel stride ld_out.  The
+ * average is formed in fp32 and rounded to fp16 once (what trtx_op_pool_nhwc stores); positions outside the (H-1) x (W-1) pooled map are the convolution's
+ * zero padding (mode 0) or are left out of the maximum (mode 1).  Weights as trtx_conv_pack_weights_f16 packs a 3x3 / 1x1 filter over cin_pad = Cin rounded
+ * up to 32 (BatchNorm scale folded); bias [Cout_pad] or NULL; act as trtx_op_conv2d_nhwc_f16's act1.  H, W >= 2, Cin and Cout multiples of 8, the channel
+ * strides too, pointers 16-byte aligned; channel slices work as source and destination.  TRTX_ERR_INVALID: an output whose bytes overlap the input's;
+ * TRTX_ERR_UNSUPPORTED: anything else outside the above.  Nothing is written in either case. */
+int32_t trtx_op_conv_pool_f16(int mode, const void* in, int N, int H, int W, int Cin, int ld_in, const void* w_packed, const float* bias, int Cout, int act,
+                              void* out, int ld_out, trtx_stream_t stream);
 /* 1 <= n <= 3 pairs of convolutions that read the same input, in ONE launch (the dual tile of kernels/igemm_tile.h; the detect head's cv2.x.0 -> 64 and
  * cv3.x.0 -> 80 over three pyramid levels): problem j reads in[j], NHWC fp16 with geom[5 j ..] = {N, H, W, Cin, ld_in}, through one k x k filter geometry
  * (stride, pad) and writes out0[j] (side0[3 j ..] = {Cout, ld_out, act}: 57 .. 64 channels in steps of 8) and out1[j] (side1 likewise: 65 .. 80 channels); weights as

@@ -628,6 +628,34 @@ def conv_dw_pw_f16(x, w_dw, w_pw, bias, k, stride, act, residual=None, out=None,
     return out
 
 
+def conv_pool_f16(x, w, bias, mode, act="silu", out=None, out_ld=None, status_only=False):
+    """YOLOv9's AConv / ADown halves in one launch (kernels/conv_pool.hip): x [N,H,W,Cin] CUDA half - or a channel slice of a wider tensor, pixel stride
+    x.stride(2) - through avg-pool 2x2 stride 1 and then mode "avg_c3": the 3x3 stride-2 pad-1 convolution, or mode "avgmax_c1": max-pool 3x3 stride 2 pad 1
+    and the 1x1 convolution; + bias, act -> NHWC half [N,H//2,W//2,Cout] (or into `out` with channel stride out_ld).  w: the filter as a host array
+    [Cout, Cin, k, k], BatchNorm scale folded by the caller, laid out for the device here; bias: CUDA fp32 [Cout] or None.  What the launch refuses raises
+    TrtxError (or returns its status with status_only)."""
+    import numpy as np
+    import torch
+    N, H, W, C = x.shape
+    assert x.dtype == torch.float16 and x.stride(3) == 1
+    wk = np.asarray(w, dtype=np.float32)
+    cout = wk.shape[0]
+    packed, cout_pad, _, _ = pack_conv_weights_f16(wk, cin_pad=(C + 31) // 32 * 32)
+    wq = torch.from_numpy(packed.view(np.int16)).to(x.device)
+    bq = None
+    if bias is not None:
+        bq = torch.zeros(cout_pad, dtype=torch.float32, device=x.device)
+        bq[:bias.numel()] = bias
+    if out is None:
+        out = torch.empty((N, H // 2, W // 2, cout), dtype=torch.float16, device=x.device)
+    st = lib().trtx_op_conv_pool_f16({"avg_c3": 0, "avgmax_c1": 1}[mode], _p(x), N, H, W, C, x.stride(2), _p(wq), _p(bq), cout, ACT[act], _p(out),
+                                     out_ld or out.shape[-1], _stream())
+    if status_only:
+        return st
+    check(st, "trtx_op_conv_pool_f16")
+    return out
+
+
 def conv_dual_group_f16(xs, w0, b0, outs0, w1, b1, outs1, k=3, stride=1, pad=1, act0="silu", act1="silu", cout0=None, cout1=None, res1=None, i8_1=False,
                         or_two=False, status_only=False):
     """1..3 pairs of convolutions over shared inputs in one launch (the dual tile): xs[j] [N,H,W,Cin] CUDA half (or a channel slice: pixel stride

@@ -205,6 +205,21 @@ int32_t conv_dw_pw_f16(const ConvArgs& dw, const ConvArgs& pw, hipStream_t s);
 // ... where it is supported, worthwhile and the output does not lie on the input, otherwise conv_dw into `mid` (NHWC fp16 [N][Ho][Wo][Cin], dense; written only then) and the 1x1 from it on the implicit-GEMM
 // kernel's default tactic.  What the executor issues at an OP_DSCONV.
 int32_t conv_dw_pw_or_two_f16(const ConvArgs& dw, const ConvArgs& pw, void* mid, hipStream_t s);
+// YOLOv9's AConv / ADown with the pools in the convolution's launch (conv_pool.hip), fp16: the 2x2 stride-1 average pool (and, in the second mode, the 3x3
+// stride-2 pad-1 max-pool behind it) exists only in LDS, as the MFMA operand of the convolution.  `a` is the CONVOLUTION as conv_igemm_f16 takes one, except
+// that in / H / W / ld_in are the UNPOOLED tensor's (a channel view of it) and Ho = H / 2, Wo = W / 2; weights in the implicit-GEMM family's fp16 layout with
+// CinK = Cin rounded up to 32 and Kpad = kh kw CinK (conv_layout_view).  _supported(): the mode's exact filter (3x3 / 1x1; ConvArgs' stride and padding fields
+// are not read), groups 1, no dilation, H and W >= 2, Cin and Cout multiples of 8, channel strides multiples of 8, no residual or second activation, images
+// below 2 GB, whatever pointers are set 16-byte aligned.  conv_pool_f16: TRTX_ERR_UNSUPPORTED outside that, TRTX_ERR_INVALID for an output whose bytes
+// overlap the input's (the halo is read after neighbours may have been written); nothing is written either way.
+enum ConvPoolMode : int {
+    CONV_POOL_AVG_C3 = 0,      // out = act(conv3x3 s2 p1 (avg2x2 s1 p0 (x)) + bias): positions outside the pooled map are the convolution's zero padding
+    CONV_POOL_AVGMAX_C1 = 1,   // out = act(conv1x1 (max3x3 s2 p1 (avg2x2 s1 p0 (x))) + bias): the maximum over the pooled positions that exist
+};
+bool conv_pool_supported(int mode, const ConvArgs& a);
+// ... and where the lowering asks for it (match_pool_conv): the shape classes at which the one launch measured faster than the pool ops and the convolution (conv_pool.hip)
+bool conv_pool_worthwhile(int mode, int cin, int cout);
+int32_t conv_pool_f16(int mode, const ConvArgs& a, hipStream_t s);
 // generic direct convolution (any groups / dilation / channel count), T = activation dtype, fp32 weights
 int32_t conv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 // depthwise convolution (conv_dw.hip): groups == Cin == Cout, k 3 / 5 / 7 with pad k/2, stride 1 / 2, no dilation; weights fp32 [kh*kw][C]

@@ -225,6 +225,18 @@ extern "C" int32_t trtx_op_conv_dw_pw_or_two_f16(const void* in, int N, int H, i
                     stream);
 }
 
+// --- YOLOv9's AConv / ADown halves, the pools inside the convolution's launch (kernels/conv_pool.hip), test / tool entry point
+extern "C" int32_t trtx_op_conv_pool_f16(int mode, const void* in, int N, int H, int W, int Cin, int ld_in, const void* w_packed, const float* bias, int Cout, int act,
+                                         void* out, int ld_out, trtx_stream_t stream) {
+    if (!in || !w_packed || !out || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (mode != CONV_POOL_AVG_C3 && mode != CONV_POOL_AVGMAX_C1)) return TRTX_ERR_INVALID;
+    const int k = mode == CONV_POOL_AVG_C3 ? 3 : 1;
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, k, k, 1, 1, 0, 0, 1, 1, act, 0, ACT_NONE);
+    a.Ho = H / 2; a.Wo = W / 2; a.M = N * a.Ho * a.Wo;   // of the pooled map under the mode's stride 2
+    conv_layout_view(&a);
+    a.in = in; a.wgt = w_packed; a.bias = bias; a.out = out;
+    return conv_pool_f16(mode, a, static_cast<hipStream_t>(stream));
+}
+
 // --- two sibling groups over the same inputs in one launch (the dual tile of kernels/igemm_tile.h), test / tool entry points
 static int32_t op_dual_group(int n, const void* const* in, const int32_t* geom, int k, int stride, int pad, const void* const* w0, const float* const* bias0,
                              void* const* out0, const int32_t* side0, const void* const* w1, const float* const* bias1, void* const* out1, const int32_t* side1,

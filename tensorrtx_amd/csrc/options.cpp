@@ -46,6 +46,7 @@ Options read_options() {
     o.aattn_split = !env_is("TRTX_AATTN_SPLIT", 0);
     o.hgconv = !env_is("TRTX_HGCONV", 0);
     o.dsconv = env_int("TRTX_DSCONV", 1);
+    o.pool_conv = env_int("TRTX_POOL_CONV", 1);
     o.gated_add = !env_is("TRTX_GATED_ADD", 0);
     o.yolo5_head = !env_is("TRTX_YOLO5_HEAD", 0);
     o.yolo7_head = !env_is("TRTX_YOLO7_HEAD", 0);

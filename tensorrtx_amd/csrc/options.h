@@ -44,6 +44,8 @@ struct Options {
     bool hgconv = true;         // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
     int dsconv = 1;              // TRTX_DSCONV=0: YOLOv13's DSConv (depthwise k x k -> 1x1) stays two launches, conv_dw and the 1x1 (no kernels/conv_dw_pw.hip);
                                  //            2: one launch wherever the kernel takes it, also outside the measured widths the lowering keeps to (tools/dsconv_time.py)
+    int pool_conv = 1;           // TRTX_POOL_CONV=0: YOLOv9's AConv / ADown stay an average pool (and a max-pool) in front of their convolutions (no kernels/conv_pool.hip);
+                                 //            2: one launch per convolution wherever the kernel takes it, also at the shapes the lowering declines because the pool ops measured faster (tools/pool_conv_time.py)
     bool gated_add = true;       // TRTX_GATED_ADD=0: a + gate * b with a constant gate (YOLOv13's FullPad_Tunnel, A2C2f's gamma residual) stays a product and a sum
     bool yolo9_head = true;      // TRTX_YOLO9_HEAD=0: the YOLOv9 / GELAN detect tail keeps the plugin route (layout passes, the DFL chain, concat scatters + YoloLayer_TRT)
     bool yolo5_head = true;      // TRTX_YOLO5_HEAD=0: the anchor-based (YOLOv5) detect tail keeps the plugin route (layout passes to fp32 planes + YoloLayer_TRT)

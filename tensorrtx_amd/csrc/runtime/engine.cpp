@@ -304,6 +304,9 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                 if (st == TRTX_ERR_UNSUPPORTED || st == TRTX_ERR_INVALID) st = conv_dw_pw_or_two_f16(d, a, mid, stream);
                 break;
             }
+            case OP_POOL_CONV:   // an AConv / ADown half: the pools inside the convolution's launch (the plan checked alignment and geometry: no other route)
+                st = conv_pool_f16(op.i[0], bind(op), stream);
+                break;
             case OP_CONV_GROUP: {   // independent convolutions of one kernel instantiation: one launch (conv_igemm_group_f16_kernel)
                 ConvArgs ga[kMaxConvGroup];
                 const int gn = (int)op.group.size();

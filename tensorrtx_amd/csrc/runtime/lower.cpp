@@ -457,6 +457,31 @@ struct Lowerer {
         return true;
     }
 
+    // An AConv / ADown half (match_pool_conv) at its convolution's record: ONE op that reads the average pool's input - for ADown a channel view of it - and
+    // writes the record's output; the pooled tensors are no plan tensors at all
+    bool emit_pool_conv(const FusedConv& c) {
+        const LayerDef& l = net.layers[c.conv_layer];
+        const int src = need_nhwc(c.pool_src);
+        const Dims& di = net.tensors[l.inputs[0]].dims;
+        const int cin = (int)di.d[di.nb - 3];
+        const int in = cin == plan.tensors[src].C ? src : new_view_nhwc(src, c.pool_coff, cin, -1);
+        const PTensor ti = plan.tensors[in];
+        const int out = new_tensor(c.out_tensor, net.tensors[c.out_tensor].dims, LAY_NHWC, true);
+        POp& op = add_op(OP_POOL_CONV, l.name + (c.pool_mode == CONV_POOL_AVG_C3 ? " [avg-pool 2x2 inside]" : " [avg-pool 2x2 + max-pool 3x3 inside]"), {in}, {out});
+        op.src_layer = c.conv_layer;
+        op.scale_layer = c.scale_layer;
+        op.i[0] = c.pool_mode;
+        const PTensor& to = plan.tensors[out];
+        ConvArgs& a = op.conv;
+        a.H = ti.H; a.W = ti.W; a.Cin = ti.C; a.Ho = to.H; a.Wo = to.W; a.Cout = to.C;
+        a.kh = l.kernel[0]; a.kw = l.kernel[1]; a.stride_h = l.stride[0]; a.stride_w = l.stride[1]; a.pad_h = l.padding[0]; a.pad_w = l.padding[1];
+        a.dil_h = a.dil_w = 1; a.groups = 1;
+        a.act1 = c.act1; a.alpha1 = c.alpha1;
+        op.flops = 2.0 * to.nmul * a.Ho * a.Wo * to.C * (double)a.kh * a.kw * a.Cin;
+        pt_of[c.out_tensor] = out;
+        return true;
+    }
+
     bool emit_activation(const LayerDef& l, int code, float alpha) {   // an activation op in the layout its input already has
         const int p = pt_of[l.inputs[0]];
         const bool nhwc = plan.tensors[p].layout == LAY_NHWC;
@@ -1049,7 +1074,7 @@ struct Lowerer {
                     d.conv_layer = c.dw_conv;
                     d.out_tensor = net.layers[c.dw_conv].outputs[0];
                     if (!emit_conv(d) || !emit_conv(c)) return false;
-                } else if (!(c.dw_conv >= 0 ? emit_dsconv(c) : emit_conv(c)))
+                } else if (!(c.dw_conv >= 0 ? emit_dsconv(c) : (c.pool_mode >= 0 ? emit_pool_conv(c) : emit_conv(c))))
                     return false;
                 continue;
             }

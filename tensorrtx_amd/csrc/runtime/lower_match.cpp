@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "plan.h"
+
 namespace trtx {
 
 int act_code(int trt_type) {
@@ -456,6 +458,87 @@ void match_dsconv(const NetView& g, Fusions& f) {
         if (g.opt.dsconv < 2 && !conv_dw_pw_worthwhile((int)C, p.nb_out)) continue;   // two launches measured faster there
         f.absorbed[li] = true;
         f.dsconv_dw[nx] = (int)li;
+    }
+}
+
+// ---- AConv / ADown (yolov9/src/block.cpp:256-290): an average pool 2x2, stride 1, no padding, that is no network output and whose readers are exactly
+//   AConv: one 3x3 stride-2 pad-1 convolution, or
+//   ADown: two channel slices, one read only by such a convolution, the other only by a max-pool 3x3 stride 2 pad 1 that is read only by a 1x1 convolution.
+// Runs AFTER convolution fusion and edits its records, as the concat-activation rewrite does: what it must know of a convolution - no shortcut, no second
+// activation, nothing else folded into it - is in the record.  Every reader must be fusable, otherwise none is: the pooled tensor disappears, it is never
+// computed twice.  Each convolution then becomes ONE op, OP_POOL_CONV (kernels/conv_pool.hip), that reads the pool's input - or its channel slice - directly;
+// the pools and the slices are claimed and emit nothing.  fp16 engines only, not kINT8, not the calibration lowering, not with TRTX_POOL_CONV=0, and only the
+// shape classes conv_pool_worthwhile() admits (TRTX_POOL_CONV=2 lifts that) - which, as measured so far, is none: see there.
+void match_pool_conv(const NetView& g, Fusions& f) {
+    const Network& net = g.net;
+    if (g.opt.pool_conv < 1 || g.dt != DT_F16 || net.int8 || CalibrationLowering::active()) return;
+    auto pool_is = [&](const LayerDef& l, int op, int k, int s, int p) {
+        return l.kind == L_POOLING && l.op == op && l.kernel[0] == k && l.kernel[1] == k && l.stride[0] == s && l.stride[1] == s && l.padding[0] == p && l.padding[1] == p &&
+               g.spatial(net.tensors[l.inputs[0]].dims);
+    };
+    // the record of the convolution that alone reads tensor t with a k x k filter of the mode's geometry, a plain one that no other matcher changed; or null
+    auto conv_reading = [&](int t, int k) -> FusedConv* {
+        int lc;
+        if (!g.sole_consumer(t, &lc)) return nullptr;
+        const LayerDef& l = net.layers[lc];
+        const int s = k == 3 ? 2 : 1, p = k == 3 ? 1 : 0;
+        const Dims& di = net.tensors[t].dims;
+        const int64_t cin = di.d[di.nb - 3];
+        if (l.kind != L_CONV || l.inputs[0] != t || l.kernel[0] != k || l.kernel[1] != k || l.stride[0] != s || l.stride[1] != s || l.padding[0] != p || l.padding[1] != p ||
+            l.dilation[0] != 1 || l.dilation[1] != 1 || l.groups != 1 || cin % 8 || l.nb_out % 8 || (int64_t)l.w0.size() != (int64_t)l.nb_out * cin * k * k ||
+            f.reorg_src[lc] >= 0 || f.pad_cout[lc])
+            return nullptr;
+        for (FusedConv& c : f.groups)
+            if (c.conv_layer == lc)
+                return (c.residual < 0 && c.act2 == ACT_NONE && c.fold_conv < 0 && c.dw_conv < 0 && c.pool_mode < 0 && c.act1 != ACT_EXP &&
+                        (g.opt.pool_conv >= 2 || conv_pool_worthwhile(k == 3 ? CONV_POOL_AVG_C3 : CONV_POOL_AVGMAX_C1, (int)cin, l.nb_out))) ? &c : nullptr;
+        return nullptr;
+    };
+    auto channel_slice = [&](const LayerDef& l, const Dims& di) {
+        if (l.kind != L_SLICE || l.inputs.size() != 1) return false;
+        const int cax = di.nb - 3;
+        for (int k = 0; k < di.nb; ++k)
+            if (l.step.d[k] != 1 || (k != cax && (l.start.d[k] != 0 || l.size.d[k] != di.d[k]))) return false;
+        return l.start.d[cax] % 8 == 0 && l.size.d[cax] % 8 == 0;
+    };
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        const LayerDef& l = net.layers[li];
+        if (f.absorbed[li] || !pool_is(l, TRTX_POOLING_AVERAGE, 2, 1, 0)) continue;
+        const Dims& di = net.tensors[l.inputs[0]].dims;
+        const int tp = l.outputs[0], cax = di.nb - 3;
+        if (net.tensors[tp].is_output || di.d[di.nb - 2] < 2 || di.d[di.nb - 1] < 2) continue;
+        const std::vector<int>& readers = g.consumers[tp];
+        if (readers.size() == 1) {   // AConv
+            FusedConv* c = conv_reading(tp, 3);
+            if (!c) continue;
+            c->pool_mode = CONV_POOL_AVG_C3;
+            c->pool_src = l.inputs[0];
+            f.absorbed[li] = true;
+        } else if (readers.size() == 2 && readers[0] != readers[1]) {   // ADown
+            FusedConv* c3 = nullptr;
+            FusedConv* c1 = nullptr;
+            int s3 = -1, s1 = -1, mp = -1;
+            for (int r : readers) {
+                const LayerDef& ls = net.layers[r];
+                int nx;
+                if (f.absorbed[r] || !channel_slice(ls, net.tensors[tp].dims)) break;
+                if (FusedConv* c = conv_reading(ls.outputs[0], 3)) {
+                    c3 = c;
+                    s3 = r;
+                } else if (g.sole_consumer(ls.outputs[0], &nx) && !f.absorbed[nx] && pool_is(net.layers[nx], TRTX_POOLING_MAX, 3, 2, 1)) {
+                    c1 = conv_reading(net.layers[nx].outputs[0], 1);
+                    s1 = r;
+                    mp = nx;
+                }
+            }
+            if (!c3 || !c1 || s3 == s1) continue;
+            c3->pool_mode = CONV_POOL_AVG_C3;
+            c1->pool_mode = CONV_POOL_AVGMAX_C1;
+            c3->pool_src = c1->pool_src = l.inputs[0];
+            c3->pool_coff = (int)net.layers[s3].start.d[cax];
+            c1->pool_coff = (int)net.layers[s1].start.d[cax];
+            f.absorbed[li] = f.absorbed[s3] = f.absorbed[s1] = f.absorbed[mp] = true;
+        }
     }
 }
 
@@ -1267,7 +1350,7 @@ bool match_tanh_gelu(const NetView& g, int last, GeluFuse* f) {
 
 // The order is part of the behaviour - a layer belongs to the first matcher that claims it: the task head and the detection head
 // and the YOLOv9 head (before conv fusion: they claim the DFL 1x1 convolutions), the anchor heads of YOLOv5 and YOLOv7 (they claim their plugin layer only), PSA attention, area
-// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), the RepVGGDW fold (it claims the 3x3 branch and the sum, and convolution fusion then continues the 7x7 convolution at the sum's output), DSConv (it claims the depthwise convolution in front of a 1x1 one, whose record convolution fusion then builds as ever), convolution fusion, and last the concat-activation rewrite, which edits the convolution records.
+// attention, YOLOv13's area attention on separate qk and v (after the packed form, and before the hypergraph convolution, the softmax chains and the gated adds: its spelled-out softmax and its scale must still be unclaimed), the hypergraph convolution (it claims four fully connected layers and two GELU chains) and then the GELU chains left standing alone, the spelled-out softmax chains, the gated adds (before convolution fusion, which would take their sum as a residual), the ReOrg fold (slices and a concat in front of a convolution that no other matcher looks at), the RepVGGDW fold (it claims the 3x3 branch and the sum, and convolution fusion then continues the 7x7 convolution at the sum's output), DSConv (it claims the depthwise convolution in front of a 1x1 one, whose record convolution fusion then builds as ever), convolution fusion, the concat-activation rewrite, which edits the convolution records, and last AConv / ADown (it marks the records of the convolutions behind an average pool and claims the pools and slices in front of them).
 Fusions match_fusions(const NetView& g) {
     Fusions f;
     const size_t nl = g.net.layers.size();
@@ -1295,6 +1378,7 @@ Fusions match_fusions(const NetView& g) {
     match_dsconv(g, f);
     match_conv_fusion(g, f);
     match_concat_activation(g, f);
+    match_pool_conv(g, f);
     return f;
 }
 

@@ -23,6 +23,8 @@ struct FusedConv {
     int emit_at = -1;     // layer index at which the fused op is scheduled
     int fold_conv = -1, fold_scale = -1;   // RepVGGDW (match_repvggdw_fold): the 3x3 depthwise branch and its scale, folded into this 7x7 one's filter
     int dw_conv = -1;                      // DSConv (match_dsconv): the depthwise convolution in front of this 1x1 one, computed in its launch (OP_DSCONV)
+    int pool_mode = -1;                    // AConv / ADown (match_pool_conv): a ConvPoolMode - the pools in front of this convolution are computed in its launch
+    int pool_src = -1, pool_coff = 0;      // (OP_POOL_CONV), which reads channels [pool_coff, pool_coff + Cin) of network tensor pool_src, the average pool's input
 };
 
 struct YoloHeadFuse {

@@ -230,7 +230,7 @@ bool pack_weights(const Network& net, Plan* plan) {
                 for (int t = 0; t < taps; ++t) dst[(size_t)t * C + c] = ld.w0[(size_t)c * taps + t];
             op.bytes += (double)taps * C * 4;
         }
-        if (op.kind == OP_CONV || op.kind == OP_DECONV || op.kind == OP_DSCONV) {
+        if (op.kind == OP_CONV || op.kind == OP_DECONV || op.kind == OP_DSCONV || op.kind == OP_POOL_CONV) {   // (a pool_conv: ROUTE_IGEMM rows, select_conv_kernels)
             const LayerDef& l = net.layers[op.src_layer];
             const ConvArgs& a = op.conv;
             const int cout = a.Cout;

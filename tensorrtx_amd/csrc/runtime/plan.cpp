@@ -11,8 +11,8 @@ const char* op_kind_name(int k) {
                               "act_lin",  "scale_lin", "softmax",   "matmul",     "reduce_lin", "plugin", "copy_lin", "yolo_head",
                               "pool_chain", "depth_to_space", "roi_align", "conv_chain", "conv_group", "attention",
                               "yolo_task_head", "yolo5_head", "yolo9_head", "yolo7_head", "hgconv", "gated_add", "attention_split",
-                              "darknet_head", "pad_nhwc", "yolo10_head", "dsconv"};
-    return (k >= 0 && k <= OP_DSCONV) ? n[k] : "?";
+                              "darknet_head", "pad_nhwc", "yolo10_head", "dsconv", "pool_conv"};
+    return (k >= 0 && k <= OP_POOL_CONV) ? n[k] : "?";
 }
 
 // In YoloForm's order, the task head behind them
@@ -90,6 +90,10 @@ std::string Plan::describe_json() const {
             o << ",\"dw_k\":" << op.dw_conv.kh << ",\"dw_stride\":" << op.dw_conv.stride_h << ",\"dw_hw_in\":[" << op.dw_conv.H << "," << op.dw_conv.W << "],\"dw_ld_in\":"
               << op.dw_conv.ld_in << ",\"ws_bytes\":" << op.ws_bytes
               << ",\"fused\":" << ((op.i[0] || conv_dw_pw_worthwhile(op.dw_conv.Cin, op.conv.Cout)) && conv_dw_pw_supported(d1, p1) ? "true" : "false");   // the route at run time, pointers permitting
+        }
+        if (op.kind == OP_POOL_CONV) {   // the convolution's fields (hw_in = the unpooled tensor's), and which pools run inside the launch
+            conv_fields(op);
+            o << ",\"mode\":\"" << (op.i[0] == CONV_POOL_AVG_C3 ? "avg_c3" : "avgmax_c1") << "\"";
         }
         if (op.kind == OP_ACT_NHWC || op.kind == OP_ACT_LIN) o << ",\"act\":" << op.i[0];
         if (op.kind == OP_ATTENTION) o << ",\"heads\":" << op.i[0] << ",\"n\":" << op.i[1] << ",\"kd\":" << op.i[2] << ",\"hd\":" << op.i[3];

@@ -72,6 +72,9 @@ enum OpKind : int {
     OP_DSCONV,          // YOLOv13's DSConv, depthwise k x k -> 1x1, as one launch (kernels/conv_dw_pw.hip, conv_dw_pw_or_two_f16): `conv` is the 1x1 with its whole
                         // epilogue (in[1] = the residual), reading a dense NHWC tensor of the depthwise channels that exists only as the workspace (ws: `mid`, written
                         // when the fused launch is refused at run time); `dw_conv` / dw_layer the depthwise half, its fp32 tap-major weights at dw_off
+    OP_POOL_CONV,       // YOLOv9's AConv / ADown halves (kernels/conv_pool.hip, conv_pool_f16): `conv` is the convolution with its folded BatchNorm and activation, except
+                        // that in[0] and conv.H / W / ld_in are the UNPOOLED tensor's (or its channel slice's): the average pool (and ADown's max-pool) in front of it
+                        // exist only inside the launch.  i[0] = the ConvPoolMode; weights in the implicit-GEMM layout with CinK = Cin rounded up to 32
 };
 const char* op_kind_name(int k);
 

@@ -400,6 +400,17 @@ bool select_conv_kernels(Plan& plan, const PassInputs& e, std::string* err) {
             const ConvArgs &d = op.dw_conv, &a = op.conv;
             op.bytes = plan.tensors[op.out[0]].nmul * 2.0 * ((double)d.H * d.W * d.Cin + (double)a.Ho * a.Wo * a.Cout * (op.in.size() > 1 ? 2 : 1));
         }
+        if (op.kind == OP_POOL_CONV) {   // the one kernel; it moves the unpooled input (its halo rows and columns twice: not counted) and the output
+            const PTensor &ti = plan.tensors[op.in[0]], &to = plan.tensors[op.out[0]];
+            ConvArgs& a = op.conv;
+            a.ld_in = ti.ld;
+            a.ld_out = to.ld;
+            conv_layout_view(&a);   // the implicit-GEMM rows with CinK = Cin rounded up to 32
+            op.route = ROUTE_IGEMM;
+            if (ti.rcoff % 8 || to.rcoff % 8 || ti.dtype != DT_F16 || to.dtype != DT_F16 || !conv_pool_supported(op.i[0], conv_args_at(plan, op, plan.max_batch)))
+                return fail(err, op.name + ": a matched AConv / ADown convolution that kernels/conv_pool.hip does not take (a channel offset or stride off 16 bytes)");
+            op.bytes = to.nmul * 2.0 * ((double)a.H * a.W * a.Cin + (double)a.Ho * a.Wo * a.Cout);
+        }
         if (op.kind != OP_CONV && op.kind != OP_DECONV) continue;
         ConvArgs& a = op.conv;
         const PTensor& ti = plan.tensors[op.in[0]];
