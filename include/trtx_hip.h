@@ -572,6 +572,23 @@ int32_t trtx_conv_view_supported(int N, int H, int W, int Cin, int in_coff, int 
                                  int dilation, int groups, int has_residual, int res_coff, int ld_res);
 int32_t trtx_op_conv2d_view_nhwc_f16(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out, int Cout,
                                      int ld_out, int k, int pad, int act1, const void* residual, int ld_res, int act2, trtx_stream_t stream);
+/* Grouped and channel-view convolutions of fp32 engines on v_mfma_f32_16x16x4_f32 (tests / tools; kernels/conv_patch_f32.hip; what an fp32 engine runs with
+ * TRTX_CONV_F32_PATCH=1 in place of the scalar direct kernel): k = 1 with pad 0 or k = 3 with pad 1, stride 1, no dilation; NHWC fp32 in / out / residual, each
+ * pointing at the FIRST CHANNEL of its view with its own pixel stride ld_* (floats); everything stays fp32.  groups == 1: any Cin, Cout, channel offset and
+ * stride - the layers of the reference's RepNCSPELAN4 / RepNCSP blocks (yolov9/src/block.cpp) at YOLOv9m's 90-channel widths.  2 <= groups <= 8: Cin / groups a
+ * multiple of 4 and Cout / groups a multiple of 16, both up to 64, Cout <= 128 - the reference's DetectBbox_Conv (yolov9/src/block.cpp: 64 -> 64, g = 4).
+ * Anything else is TRTX_ERR_UNSUPPORTED, an output whose bytes overlap the input's TRTX_ERR_INVALID (another channel slice of the same map does not overlap),
+ * null pointers and non-positive sizes TRTX_ERR_INVALID; nothing is launched.  The channels beside a view are never read (they may hold NaN) and never written.
+ * trtx_conv_pack_weights_patch_f32: KCRS [cout][cin_g][kh][kw] -> the packed fp32 filter (16-byte aligned for the launch): groups == 1 the rows of
+ * trtx_conv_pack_weights_f32, [cout_pad][kpad]; grouped [cout][kpad], k = tap * cin_g + c, kpad = K rounded up to 32 (packed == NULL: only the sizes); bias:
+ * Cout floats or NULL.  out = act2(act1(conv + bias) + residual).  trtx_conv_patch_f32_supported: 1 where the kernel takes such a layer (channel offsets given
+ * in channels), else 0. */
+int32_t trtx_conv_pack_weights_patch_f32(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int groups, const float* ch_scale, float* packed,
+                                         int32_t* cout_pad_out, int32_t* kpad_out);
+int32_t trtx_conv_patch_f32_supported(int N, int H, int W, int Cin, int in_coff, int ld_in, int Cout, int out_coff, int ld_out, int k, int stride, int pad,
+                                      int dilation, int groups, int has_residual, int res_coff, int ld_res);
+int32_t trtx_op_conv2d_patch_nhwc_f32(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out, int Cout,
+                                      int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2, trtx_stream_t stream);
 /* Depthwise convolution (tests / tools; kernels/conv_dw.hip: YOLO11's DWConv and the attention's positional conv): groups == C, square k of 3 / 5 / 7 with
  * pad == k / 2, stride 1 or 2, dilation 1 (anything else: TRTX_ERR_UNSUPPORTED, nothing is launched).  dtype: TRTX_DTYPE_FLOAT or TRTX_DTYPE_HALF, the type of
  * in / out / residual, each an NHWC channel slice with its own pixel stride ld_*; the filter is fp32 [k * k][C] (tap-major), bias C floats or NULL, residual

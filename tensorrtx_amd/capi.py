@@ -731,6 +731,39 @@ def conv2d_view_nhwc_f16(x, wpacked, bias, cout, k, pad, act1="none", residual=N
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- fp32 engines: grouped / channel-view conv on the fp32 MFMA (tests / tools)
+def pack_conv_weights_patch_f32(w_kcrs, groups=1, ch_scale=None):
+    """Host: KCRS fp32 numpy [Cout, Cin / groups, k, k] -> packed float32 for conv2d_patch_nhwc_f32: groups == 1 the rows of pack_conv_weights_f32
+    [Cout_pad, Kpad], grouped [Cout, Kpad] with k = tap * Cin_g + c."""
+    import numpy as np
+    L = lib()
+    w = np.ascontiguousarray(w_kcrs, dtype=np.float32)
+    cout, cin_g, kh, kw = w.shape
+    cp, kp = ctypes.c_int32(), ctypes.c_int32()
+    sc = None if ch_scale is None else np.ascontiguousarray(ch_scale, dtype=np.float32)
+    args = (w.ctypes.data_as(ctypes.c_void_p), cout, cin_g, kh, kw, groups, sc.ctypes.data_as(ctypes.c_void_p) if sc is not None else None)
+    check(L.trtx_conv_pack_weights_patch_f32(*args, None, ctypes.byref(cp), ctypes.byref(kp)), "trtx_conv_pack_weights_patch_f32 (dims)")
+    packed = np.zeros((cp.value, kp.value), dtype=np.float32)
+    check(L.trtx_conv_pack_weights_patch_f32(*args, packed.ctypes.data_as(ctypes.c_void_p), None, None), "trtx_conv_pack_weights_patch_f32")
+    return packed
+
+
+def conv2d_patch_nhwc_f32(x, wpacked, bias, cout, groups, k, pad, act1="none", residual=None, act2="none", out=None, out_ld=None, status_only=False):
+    """Single launch of the fp32 engines' grouped / channel-view convolution (kernels/conv_patch_f32.hip) on NHWC fp32 tensors; x: [N,H,W,Cin] CUDA float or a
+    channel slice of a wider tensor (its pixel stride is x.stride(2)), residual likewise; out / out_ld: a channel slice of a wider buffer.  status_only: the
+    status instead of raising."""
+    import torch
+    N, H, W, Cin = x.shape
+    if out is None:
+        out = torch.empty((N, H + 2 * pad - k + 1, W + 2 * pad - k + 1, cout), dtype=torch.float32, device=x.device)
+    st = lib().trtx_op_conv2d_patch_nhwc_f32(_p(x), N, H, W, Cin, x.stride(2), _p(wpacked), _p(bias), _p(out), cout, out_ld or out.shape[-1], groups, k, pad,
+                                             ACT[act1], _p(residual), residual.stride(2) if residual is not None else 0, ACT[act2], _stream())
+    if status_only:
+        return st
+    check(st, "trtx_op_conv2d_patch_nhwc_f32")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- depthwise conv and the attention kernels (tests / tools)
 def conv2d_dw_nhwc(x, w, bias, k, stride, act1="none", residual=None, act2="none", out=None, out_ld=None, alpha1=0.1, alpha2=0.1, pad=None, dilation=1):
     """Single depthwise-convolution launch (kernels/conv_dw.hip) on NHWC fp16 or fp32 tensors.  x: [N,H,W,C] CUDA, or a channel slice of a wider

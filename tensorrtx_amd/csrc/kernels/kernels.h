@@ -287,6 +287,14 @@ int32_t conv_grouped(const ConvArgs& a, hipStream_t s);
 // (ConvArgs::CinK / Kpad / Cout_pad must say so); bias fp32, Cout values read.  conv_view: TRTX_ERR_UNSUPPORTED outside that, nothing launched.
 bool conv_view_supported(const ConvArgs& a);
 int32_t conv_view(const ConvArgs& a, hipStream_t s);
+// grouped and channel-view convolutions of fp32 engines on v_mfma_f32_16x16x4_f32 (conv_patch_f32.hip): fp32 NHWC in / out / residual, 1x1 pad 0 or 3x3 pad 1,
+// stride 1, no dilation; groups == 1 with any Cin, Cout, channel offset and stride, or 2 <= groups <= 8 with Cin / groups a multiple of 4 and Cout / groups a
+// multiple of 16, both up to 64, Cout <= 128; whatever pointers are set 4-byte aligned.  ld_res != 0 says "there is a residual" where the pointer is not known
+// yet.  Weights (conv_layout_patch_f32): groups == 1 the fp32 implicit-GEMM rows [Cout_pad][Kpad]; grouped fp32 [group][Cout_g][Kpad], k = tap * Cin_g + c,
+// Kpad = conv_grouped_kpad(); bias fp32, Cout values read.  conv_patch_f32: TRTX_ERR_UNSUPPORTED outside that, TRTX_ERR_INVALID for an output whose bytes
+// overlap the input's (another channel slice of the same map does not); nothing is launched either way.  What an fp32 engine runs with TRTX_CONV_F32_PATCH=1.
+bool conv_patch_f32_supported(const ConvArgs& a);
+int32_t conv_patch_f32(const ConvArgs& a, hipStream_t s);
 // generic transposed convolution, fp32 weights laid out [Cin][kh][kw][Cout/groups]
 int32_t deconv_direct(const ConvArgs& a, int dtype, hipStream_t s);
 

@@ -329,6 +329,50 @@ extern "C" int32_t trtx_op_conv2d_view_nhwc_f16(const void* in, int N, int H, in
     return st;
 }
 
+// --- grouped and channel-view convolutions of fp32 engines (kernels/conv_patch_f32.hip), test / tool entry points: yolov9/src/block.cpp, DetectBbox_Conv
+// (64 -> 64, g = 4) and RepNCSPELAN4 / RepNCSP at YOLOv9m's 90-channel widths
+static ConvArgs patch_f32_args(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int k, int stride, int pad, int dilation, int groups, int ld_res) {
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, k, k, stride, stride, pad, pad, dilation, groups, ACT_NONE, ld_res, ACT_NONE);
+    conv_layout_patch_f32(&a);
+    return a;
+}
+
+extern "C" int32_t trtx_conv_pack_weights_patch_f32(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int groups, const float* ch_scale, float* packed,
+                                                    int32_t* cout_pad_out, int32_t* kpad_out) {
+    if (!w_kcrs || cout < 1 || cin_g < 1 || kh < 1 || kw < 1 || groups < 1 || cout % groups) return TRTX_ERR_INVALID;
+    ConvArgs a{};
+    a.Cout = cout; a.Cin = cin_g * groups; a.kh = kh; a.kw = kw; a.groups = groups;
+    conv_layout_patch_f32(&a);
+    if (cout_pad_out) *cout_pad_out = a.Cout_pad;
+    if (kpad_out) *kpad_out = a.Kpad;
+    if (packed && groups == 1) conv_pack_weights_igemm_f32(w_kcrs, cout, cin_g, kh, kw, a.CinK, a.Kpad, a.Cout_pad, ch_scale, packed);
+    if (packed && groups > 1) pack_conv_weights_grouped_f32(w_kcrs, cout, cin_g, kh, kw, a.Kpad, ch_scale, packed);
+    return TRTX_OK;
+}
+
+extern "C" int32_t trtx_conv_patch_f32_supported(int N, int H, int W, int Cin, int in_coff, int ld_in, int Cout, int out_coff, int ld_out, int k, int stride, int pad,
+                                                 int dilation, int groups, int has_residual, int res_coff, int ld_res) {
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || groups < 1 || k < 1 || stride < 1 || pad < 0 || dilation < 1) return 0;
+    if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return 0;
+    if (in_coff < 0 || out_coff < 0 || in_coff + Cin > ld_in || out_coff + Cout > ld_out || (has_residual && (res_coff < 0 || res_coff + Cout > ld_res))) return 0;
+    return conv_patch_f32_supported(patch_f32_args(N, H, W, Cin, ld_in, Cout, ld_out, k, stride, pad, dilation, groups, has_residual ? ld_res : 0)) ? 1 : 0;
+}
+
+extern "C" int32_t trtx_op_conv2d_patch_nhwc_f32(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out,
+                                                 int Cout, int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2,
+                                                 trtx_stream_t stream) {
+    if (!in || !wpacked || !out || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || ld_in < 1 || ld_out < 1 || groups < 1 || k < 1 || pad < 0 ||
+        (residual && ld_res < 1) || H + 2 * pad < k || W + 2 * pad < k)
+        return TRTX_ERR_INVALID;
+    ConvArgs a = patch_f32_args(N, H, W, Cin, ld_in, Cout, ld_out, k, 1, pad, 1, groups, residual ? ld_res : 0);
+    a.in = in; a.wgt = wpacked; a.bias = bias; a.out = out; a.residual = residual;
+    a.act1 = act1; a.act2 = act2;
+    const int reps = options().op_reps;   // timing tools only
+    int32_t st = TRTX_OK;
+    for (int r = 0; r < reps && st == TRTX_OK; ++r) st = conv_patch_f32(a, static_cast<hipStream_t>(stream));
+    return st;
+}
+
 // --- depthwise convolution (kernels/conv_dw.hip) and the two attention kernels (kernels/attention.hip, kernels/attention_mfma.hip), test / tool entry points
 extern "C" int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int H, int W, int C, int ld_in, const float* w_taps_c, const float* bias, void* out,
                                           int ld_out, const void* residual, int ld_res, int k, int stride, int pad, int dilation, int act1, float alpha1,

@@ -43,6 +43,7 @@ Options read_options() {
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.psa_mfma = env_int("TRTX_PSA_MFMA", 1);
     o.attention_f32 = env_is("TRTX_ATTENTION_F32", 1);
+    o.conv_f32_patch = env_is("TRTX_CONV_F32_PATCH", 1);
     o.aattn_split = !env_is("TRTX_AATTN_SPLIT", 0);
     o.hgconv = !env_is("TRTX_HGCONV", 0);
     o.dsconv = env_int("TRTX_DSCONV", 1);

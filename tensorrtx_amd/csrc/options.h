@@ -40,6 +40,8 @@ struct Options {
                                  //            unset: the MFMA kernel for heads of kd 36 / hd 72 only; 2: for every head shape it takes, kd 32 / hd 64 too (psa_mfma_default, lower.cpp)
     bool attention_f32 = false;  // TRTX_ATTENTION_F32=1: fp32 engines run PSA and area attention as one OP_ATTENTION on the fp32 matrix instruction (kernels/attention_f32.hip)
                                  //            instead of the generic linear path; off by default: three tests pin the fp32 lowering as generic
+    bool conv_f32_patch = false; // TRTX_CONV_F32_PATCH=1: fp32 engines run grouped (not depthwise) convolutions and groups == 1 convolutions over channel views that are not 16-byte aligned on the
+                                 //            fp32 matrix instruction (kernels/conv_patch_f32.hip) instead of the scalar direct kernel; off by default: two tests pin those fp32 lowerings to the direct kernel
     bool aattn_split = true;     // TRTX_AATTN_SPLIT=0: YOLOv13 area attention (q | k and v from two convolutions) stays on the generic linear path (shuffles, slices, matmul, softmax)
     bool hgconv = true;         // TRTX_HGCONV=0: YOLOv13's hypergraph convolution (AdaHGConv) stays on the generic linear path (reduces, matmuls, softmax, element-wise GELU chains)
     int dsconv = 1;              // TRTX_DSCONV=0: YOLOv13's DSConv (depthwise k x k -> 1x1) stays two launches, conv_dw and the 1x1 (no kernels/conv_dw_pw.hip);

@@ -287,6 +287,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     case ROUTE_DW: st = conv_dw(a, op.dtype, stream); break;
                     case ROUTE_GROUPED: st = conv_grouped(a, stream); break;
                     case ROUTE_VIEW: st = conv_view(a, stream); break;
+                    case ROUTE_PATCH_F32: st = conv_patch_f32(a, stream); break;
                     case ROUTE_DIRECT: st = conv_direct(a, op.dtype, stream); break;
                 }
                 break;

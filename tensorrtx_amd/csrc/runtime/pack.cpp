@@ -76,8 +76,18 @@ void conv_layout_grouped(ConvArgs* a) {
     a->Kpad = conv_grouped_kpad(*a);   // K rounded up to 32 (kernels/conv_grouped.hip)
 }
 
+void conv_layout_patch_f32(ConvArgs* a) {
+    if (a->groups == 1) {
+        conv_layout_igemm_f32(a);
+    } else {
+        conv_layout_grouped(a);
+        a->f32 = 1;
+    }
+}
+
 size_t conv_packed_weight_bytes(ConvRoute route, const ConvArgs& a) {
     switch (route) {
+        case ROUTE_PATCH_F32: return (size_t)a.Cout_pad * a.Kpad * 4;   // (grouped: Cout_pad == Cout)
         case ROUTE_IGEMM:
         case ROUTE_VIEW: return (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2);   // (int8: Kpad counts 2-byte units)
         case ROUTE_GROUPED: return (size_t)a.Cout * a.Kpad * 2;
@@ -147,6 +157,17 @@ void pack_conv_weights_grouped_f16(const float* w, int cout, int cin_g, int kh, 
             for (int r = 0; r < kh; ++r)
                 for (int q = 0; q < kw; ++q)
                     packed[(size_t)co * kpad + (size_t)(r * kw + q) * cin_g + c] = f32_to_f16_bits(w[(((size_t)co * cin_g + c) * kh + r) * kw + q] * sc);
+    }
+}
+
+void pack_conv_weights_grouped_f32(const float* w, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, float* packed) {
+    memset(packed, 0, sizeof(float) * (size_t)cout * kpad);
+    for (int co = 0; co < cout; ++co) {
+        const float sc = ch_scale ? ch_scale[co] : 1.0f;
+        for (int c = 0; c < cin_g; ++c)
+            for (int r = 0; r < kh; ++r)
+                for (int q = 0; q < kw; ++q)
+                    packed[(size_t)co * kpad + (size_t)(r * kw + q) * cin_g + c] = w[(((size_t)co * cin_g + c) * kh + r) * kw + q] * sc;
     }
 }
 
@@ -328,6 +349,13 @@ bool pack_weights(const Network& net, Plan* plan) {
                 case ROUTE_GROUPED:
                     op.w_off = reserve(conv_packed_weight_bytes(op.route, a));
                     pack_conv_weights_grouped_f16(w0, cout, cin_g, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+                    break;
+                case ROUTE_PATCH_F32:   // (kernels/conv_patch_f32.hip: the fp32 implicit-GEMM rows, or the grouped kernel's rows in fp32)
+                    op.w_off = reserve(conv_packed_weight_bytes(op.route, a));
+                    if (a.groups == 1)
+                        conv_pack_weights_igemm_f32(w0, cout, cin_logical, a.kh, a.kw, a.CinK, a.Kpad, a.Cout_pad, sc.data(), reinterpret_cast<float*>(blob.data() + op.w_off));
+                    else
+                        pack_conv_weights_grouped_f32(w0, cout, cin_g, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<float*>(blob.data() + op.w_off));
                     break;
                 case ROUTE_DW: {
                     // [tap][C], BN scale folded: a lane reads its channel vector of one tap as one 16-byte load

@@ -20,6 +20,9 @@ void conv_layout_igemm_f32(ConvArgs* a);
 void conv_layout_view(ConvArgs* a);
 //  - grouped (kernels/conv_grouped.hip): K per group, rows of conv_grouped_kpad()
 void conv_layout_grouped(ConvArgs* a);
+//  - fp32 engines' grouped / channel-view kernel (kernels/conv_patch_f32.hip; sets ConvArgs::f32): groups == 1 the fp32 implicit-GEMM rows exactly, grouped the
+//    rows of conv_layout_grouped.  No layout of its own: the kernel reads what those two families pack, in fp32
+void conv_layout_patch_f32(ConvArgs* a);
 //  - direct, depthwise, stem, deconvolution: nothing is padded
 void conv_layout_unpadded(ConvArgs* a);
 // Bytes of the packed filter of a convolution on `route` (what pack_weights reserves, and the weight term of POp::bytes)
@@ -38,6 +41,9 @@ void pack_conv_weights_f32(const float* w_kcrs, int cout, int cin_g, int kh, int
 // fp16 [group][Cout_g][kpad] = rows [Cout][kpad] for the grouped MFMA kernel (kernels/conv_grouped.hip): k = (r*kw + q)*cin_g + c, kpad = K rounded
 // up to 32, zero padded; the per-output-channel scale is multiplied in before rounding to fp16, as in pack_conv_weights_f16
 void pack_conv_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed);
+
+// ... and the same rows in fp32 (kernels/conv_patch_f32.hip, grouped layers)
+void pack_conv_weights_grouped_f32(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, float* packed);
 
 // TensorRT deconvolution weights are CKRS ([Cin][Cout/groups][kh][kw]); gather form for
 // deconv_direct is [Cout][kh][kw][Cin/groups].

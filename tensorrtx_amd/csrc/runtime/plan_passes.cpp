@@ -160,6 +160,21 @@ bool take_view(const ConvSite& s) {
     return true;
 }
 
+// fp32 engines under TRTX_CONV_F32_PATCH=1: grouped, not depthwise, and groups == 1 over any channel view (kernels/conv_patch_f32.hip), after the fp32 implicit
+// GEMM and the depthwise kernel have declined.  A groups == 1 layer is taken only where the implicit GEMM declined for its input's alignment: an aligned layer
+// it leaves to the direct kernel (a tiny reduction, a single-channel output) stays there.
+bool take_patch_f32(const ConvSite& s) {
+    ConvArgs& a = s.op.conv;
+    if (!s.e.opt.conv_f32_patch) return false;
+    if (a.groups == 1 && !(a.Cin % 4 || s.ti.rcoff % 4 || s.ti.ld % 4)) return false;
+    ConvArgs t = a;
+    conv_layout_patch_f32(&t);
+    if (!conv_patch_f32_supported(t)) return false;
+    a = t;
+    s.op.route = ROUTE_PATCH_F32;
+    return true;
+}
+
 // Which kernel runs a convolution, given the (resolved) strides / offsets and the dtypes of the tensors it touches: fills op.conv
 // and names op.route; true when the implicit-GEMM MFMA kernel takes it.  ONE predicate for select_conv_kernels(),
 // fold_upsample's probe and the int8 assignment, which may only put a tensor in int8 if every convolution touching it gets the MFMA path.
@@ -189,9 +204,10 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
     // the other kernels neither stand in for a deconvolution nor fetch a folded upsample, and every tensor is of the engine's dtype
     if (op.from_deconv || !op.extra_in.empty() || ti.dtype != e.dt || to.dtype != e.dt || (tr && tr->dtype != e.dt)) return false;
     if (take_dw(s)) return false;
-    // ... the last two in fp16 engines only, not in kINT8 engines nor in the lowering their calibration runs on
-    if (e.dt != DT_F16 || e.int8 || CalibrationLowering::active()) return false;
-    (void)(take_grouped(s) || take_view(s));
+    // ... the last three not in kINT8 engines nor in the lowering their calibration runs on: two in fp16 engines, one in fp32 engines
+    if (e.int8 || CalibrationLowering::active()) return false;
+    if (e.dt == DT_F32) (void)take_patch_f32(s);
+    if (e.dt == DT_F16) (void)(take_grouped(s) || take_view(s));
     return false;
 }
 
