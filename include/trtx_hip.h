@@ -589,6 +589,22 @@ int32_t trtx_conv_patch_f32_supported(int N, int H, int W, int Cin, int in_coff,
                                       int dilation, int groups, int has_residual, int res_coff, int ld_res);
 int32_t trtx_op_conv2d_patch_nhwc_f32(const void* in, int N, int H, int W, int Cin, int ld_in, const void* wpacked, const float* bias, void* out, int Cout,
                                       int ld_out, int groups, int k, int pad, int act1, const void* residual, int ld_res, int act2, trtx_stream_t stream);
+/* 3x3 convolutions of many narrow groups on the matrix pipe (tests / tools; kernels/conv_slab.hip; what an fp16 engine runs for the 32-group layers of
+ * ResNeXt-50 32x4d, resnet/resnext50_32x4d.cpp:111-154): Cin == Cout == C a multiple of 16, C / groups of 4, 8, 16 or 32, k = 3 with pad 1, stride 1 or 2,
+ * no dilation; NHWC fp16 in / out / residual, each pointing at the FIRST CHANNEL of its view with its own pixel stride ld_* (halves); channel offsets and
+ * pixel strides multiples of 8.  Anything else is TRTX_ERR_UNSUPPORTED, null pointers and non-positive sizes TRTX_ERR_INVALID; nothing is launched.
+ * out = act2(act1(conv + bias) + residual), one fp16 rounding.  The zeros of the block-diagonal filter are multiplied: a non-finite input channel makes the
+ * outputs of its whole 16-channel slab NaN, not only its group's (4 and 8 channels per group).
+ * trtx_conv_pack_weights_slab_f16 (resnet/resnext50_32x4d.cpp:111-154): KCRS [c][c / groups][3][3] -> the packed fp16 filter (16-byte aligned for the
+ * launch), rows [c][kpad] with k = tap * S + c_local, S = max(16, c / groups), kpad = 9 S rounded up to 32, zero outside the row's group (packed == NULL:
+ * only kpad); ch_scale: c floats multiplied in before the rounding, or NULL.  Channel counts and groups the kernel refuses: TRTX_ERR_UNSUPPORTED, nothing written.
+ * trtx_conv_slab_supported (resnet/resnext50_32x4d.cpp:111-154): 1 where the kernel takes such a layer (channel offsets given in channels), else 0.
+ * trtx_op_conv2d_slab_nhwc_f16 (resnet/resnext50_32x4d.cpp:111-154): one launch; bias: C floats or NULL. */
+int32_t trtx_conv_pack_weights_slab_f16(const float* w_kcrs, int c, int groups, const float* ch_scale, uint16_t* packed, int32_t* kpad_out);
+int32_t trtx_conv_slab_supported(int N, int H, int W, int Cin, int in_coff, int ld_in, int Cout, int out_coff, int ld_out, int k, int stride, int pad,
+                                 int dilation, int groups, int has_residual, int res_coff, int ld_res);
+int32_t trtx_op_conv2d_slab_nhwc_f16(const void* in, int N, int H, int W, int C, int ld_in, const void* wpacked, const float* bias, void* out, int ld_out,
+                                     int groups, int stride, int act1, const void* residual, int ld_res, int act2, trtx_stream_t stream);
 /* Depthwise convolution (tests / tools; kernels/conv_dw.hip: YOLO11's DWConv and the attention's positional conv): groups == C, square k of 3 / 5 / 7 with
  * pad == k / 2, stride 1 or 2, dilation 1 (anything else: TRTX_ERR_UNSUPPORTED, nothing is launched).  dtype: TRTX_DTYPE_FLOAT or TRTX_DTYPE_HALF, the type of
  * in / out / residual, each an NHWC channel slice with its own pixel stride ld_*; the filter is fp32 [k * k][C] (tap-major), bias C floats or NULL, residual

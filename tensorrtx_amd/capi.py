@@ -764,6 +764,39 @@ def conv2d_patch_nhwc_f32(x, wpacked, bias, cout, groups, k, pad, act1="none", r
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- 3x3 conv of many narrow groups (ResNeXt; tests / tools)
+def pack_conv_weights_slab_f16(w_kcrs, groups, ch_scale=None):
+    """Host: KCRS fp32 numpy [C, C / groups, 3, 3] -> packed uint16 (fp16 bits) [C, Kpad] for conv2d_slab_nhwc_f16: k = tap * S + c_local with
+    S = max(16, C / groups), zero outside the row's own group."""
+    import numpy as np
+    L = lib()
+    w = np.ascontiguousarray(w_kcrs, dtype=np.float32)
+    assert w.shape[2:] == (3, 3) and w.shape[1] * groups == w.shape[0], w.shape
+    kp = ctypes.c_int32()
+    sc = None if ch_scale is None else np.ascontiguousarray(ch_scale, dtype=np.float32)
+    args = (w.ctypes.data_as(ctypes.c_void_p), w.shape[0], groups, sc.ctypes.data_as(ctypes.c_void_p) if sc is not None else None)
+    check(L.trtx_conv_pack_weights_slab_f16(*args, None, ctypes.byref(kp)), "trtx_conv_pack_weights_slab_f16 (dims)")
+    packed = np.zeros((w.shape[0], kp.value), dtype=np.uint16)
+    check(L.trtx_conv_pack_weights_slab_f16(*args, packed.ctypes.data_as(ctypes.c_void_p), None), "trtx_conv_pack_weights_slab_f16")
+    return packed
+
+
+def conv2d_slab_nhwc_f16(x, wpacked, bias, groups, stride=1, act1="none", residual=None, act2="none", out=None, out_ld=None, status_only=False):
+    """Single launch of the many-narrow-groups 3x3 convolution (kernels/conv_slab.hip) on NHWC fp16 tensors; x: [N,H,W,C] CUDA half or a channel slice of a
+    wider tensor (its pixel stride is x.stride(2)), residual likewise; wpacked: the fp16 view of pack_conv_weights_slab_f16's rows on the device; out /
+    out_ld: a channel slice of a wider buffer.  status_only: the status instead of raising."""
+    import torch
+    N, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((N, (H - 1) // stride + 1, (W - 1) // stride + 1, C), dtype=torch.float16, device=x.device)
+    st = lib().trtx_op_conv2d_slab_nhwc_f16(_p(x), N, H, W, C, x.stride(2), _p(wpacked), _p(bias), _p(out), out_ld or out.shape[-1], groups, stride,
+                                            ACT[act1], _p(residual), residual.stride(2) if residual is not None else 0, ACT[act2], _stream())
+    if status_only:
+        return st
+    check(st, "trtx_op_conv2d_slab_nhwc_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- depthwise conv and the attention kernels (tests / tools)
 def conv2d_dw_nhwc(x, w, bias, k, stride, act1="none", residual=None, act2="none", out=None, out_ld=None, alpha1=0.1, alpha2=0.1, pad=None, dilation=1):
     """Single depthwise-convolution launch (kernels/conv_dw.hip) on NHWC fp16 or fp32 tensors.  x: [N,H,W,C] CUDA, or a channel slice of a wider

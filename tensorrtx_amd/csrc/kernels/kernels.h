@@ -281,6 +281,17 @@ int32_t hgconv_f16(const void* x, int ld_x, void* out, int ld_out, int B, int N,
 bool conv_grouped_supported(const ConvArgs& a);
 int conv_grouped_kpad(const ConvArgs& a);
 int32_t conv_grouped(const ConvArgs& a, hipStream_t s);
+// grouped 3x3 convolution with many narrow groups on the matrix pipe (conv_slab.hip; ResNeXt's 32-group layers): fp16, Cin == Cout == C a multiple of 16,
+// C / groups in {4, 8, 16, 32}, 3x3 pad 1, stride 1 or 2, no dilation, channel strides multiples of 8, no cap on C or the group count.  ld_res != 0 says
+// "there is a residual" where the pointer is not known yet.  Weights (conv_layout_slab): fp16 rows [C][Kpad], k = tap * S + c_local with S =
+// conv_slab_width() = max(16, C / groups) and Kpad = conv_slab_kpad() = 9 S rounded up to 32 (ConvArgs::Kpad must say so), zero outside the row's own
+// group; bias fp32 [C].  launch_conv_slab_f16: TRTX_ERR_UNSUPPORTED outside that, TRTX_ERR_INVALID for null or misaligned pointers; nothing is launched
+// either way.  conv_layout_slab (runtime/pack.cpp, with the other layouts): fills K / Kpad / Cout_pad of such a layer.
+bool conv_slab_supported(const ConvArgs& a);
+int conv_slab_width(const ConvArgs& a);
+int conv_slab_kpad(const ConvArgs& a);
+void conv_layout_slab(ConvArgs* a);
+int32_t launch_conv_slab_f16(const ConvArgs& a, hipStream_t s);
 // convolution over 4-byte aligned channel views on the matrix pipe (conv_view.hip): fp16, groups == 1, 1x1 pad 0 or 3x3 pad 1, stride 1, no dilation; Cin
 // (2 .. 256), Cout and every channel stride even, whatever pointers are set 4-byte aligned (= even channel offsets).  ld_res != 0 says "there is a residual"
 // where the pointer is not known yet.  Weights: the implicit-GEMM family's fp16 [Cout_pad][Kpad] with CinK = Cin rounded up to 32 and Kpad = kh * kw * CinK

@@ -373,6 +373,47 @@ extern "C" int32_t trtx_op_conv2d_patch_nhwc_f32(const void* in, int N, int H, i
     return st;
 }
 
+// --- 3x3 convolutions of many narrow groups (kernels/conv_slab.hip), test / tool entry points: resnet/resnext50_32x4d.cpp:111-154, setNbGroups(32)
+static ConvArgs slab_args(int N, int H, int W, int Cin, int ld_in, int Cout, int ld_out, int k, int stride, int pad, int dilation, int groups, int ld_res) {
+    ConvArgs a = conv_geometry(N, H, W, Cin, ld_in, Cout, ld_out, k, k, stride, stride, pad, pad, dilation, groups, ACT_NONE, ld_res, ACT_NONE);
+    conv_layout_slab(&a);
+    return a;
+}
+
+extern "C" int32_t trtx_conv_pack_weights_slab_f16(const float* w_kcrs, int c, int groups, const float* ch_scale, uint16_t* packed, int32_t* kpad_out) {
+    if (!w_kcrs || c < 1 || groups < 1 || c % groups) return TRTX_ERR_INVALID;
+    const ConvArgs a = slab_args(1, 3, 3, c, c, c, c, 3, 1, 1, 1, groups, 0);   // the channel counts and groups of the kernel's own predicate, on some map
+    if (!conv_slab_supported(a)) return TRTX_ERR_UNSUPPORTED;
+    if (kpad_out) *kpad_out = a.Kpad;
+    if (packed) pack_conv_weights_grouped_f16(w_kcrs, c, c / groups, 3, 3, a.Kpad, ch_scale, packed, conv_slab_width(a));
+    return TRTX_OK;
+}
+
+extern "C" int32_t trtx_conv_slab_supported(int N, int H, int W, int Cin, int in_coff, int ld_in, int Cout, int out_coff, int ld_out, int k, int stride, int pad,
+                                            int dilation, int groups, int has_residual, int res_coff, int ld_res) {
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || groups < 1 || k < 1 || stride < 1 || pad < 0 || dilation < 1) return 0;
+    if (H + 2 * pad < dilation * (k - 1) + 1 || W + 2 * pad < dilation * (k - 1) + 1) return 0;
+    if (in_coff < 0 || out_coff < 0 || in_coff + Cin > ld_in || out_coff + Cout > ld_out || (has_residual && (res_coff < 0 || res_coff + Cout > ld_res))) return 0;
+    if (in_coff % 8 || out_coff % 8 || (has_residual && res_coff % 8)) return 0;   // 16-byte accesses from the view's first channel on
+    return conv_slab_supported(slab_args(N, H, W, Cin, ld_in, Cout, ld_out, k, stride, pad, dilation, groups, has_residual ? ld_res : 0)) ? 1 : 0;
+}
+
+extern "C" int32_t trtx_op_conv2d_slab_nhwc_f16(const void* in, int N, int H, int W, int C, int ld_in, const void* wpacked, const float* bias, void* out,
+                                                int ld_out, int groups, int stride, int act1, const void* residual, int ld_res, int act2, trtx_stream_t stream) {
+    if (!in || !wpacked || !out || N < 1 || H < 1 || W < 1 || C < 1 || ld_in < 1 || ld_out < 1 || groups < 1 || stride < 1 || (residual && ld_res < 1))
+        return TRTX_ERR_INVALID;
+    ConvArgs a = slab_args(N, H, W, C, ld_in, C, ld_out, 3, stride, 1, 1, groups, residual ? ld_res : 0);
+    a.in = in; a.wgt = wpacked; a.bias = bias; a.out = out; a.residual = residual;
+    a.act1 = act1; a.act2 = act2;
+    // a view's first channel that is no multiple of 8 shows as a pointer off the 16-byte grid: outside the scope, like a pixel stride that is no multiple of 8
+    for (const void* ptr : {in, static_cast<const void*>(out), residual})
+        if (reinterpret_cast<uintptr_t>(ptr) & 15) return TRTX_ERR_UNSUPPORTED;
+    const int reps = options().op_reps;   // timing tools only
+    int32_t st = TRTX_OK;
+    for (int r = 0; r < reps && st == TRTX_OK; ++r) st = launch_conv_slab_f16(a, static_cast<hipStream_t>(stream));
+    return st;
+}
+
 // --- depthwise convolution (kernels/conv_dw.hip) and the two attention kernels (kernels/attention.hip, kernels/attention_mfma.hip), test / tool entry points
 extern "C" int32_t trtx_op_conv2d_dw_nhwc(const void* in, int dtype, int N, int H, int W, int C, int ld_in, const float* w_taps_c, const float* bias, void* out,
                                           int ld_out, const void* residual, int ld_res, int k, int stride, int pad, int dilation, int act1, float alpha1,

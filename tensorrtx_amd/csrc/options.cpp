@@ -39,6 +39,7 @@ Options read_options() {
     o.roles = !env_is("TRTX_CONV_ROLES", 0);
     o.f32_mfma = !env_set("TRTX_F32_DIRECT");
     o.conv_grouped = !env_is("TRTX_CONV_GROUPED", 0);
+    o.conv_slab = !env_is("TRTX_CONV_SLAB", 0);
     o.conv_view = !env_is("TRTX_CONV_VIEW", 0);
     o.area_attention = !env_is("TRTX_AREA_ATTENTION", 0);
     o.psa_mfma = env_int("TRTX_PSA_MFMA", 1);

@@ -34,6 +34,7 @@ struct Options {
     bool roles = true;           // TRTX_CONV_ROLES=0: no fetching / multiplying wave-role variants among the candidates (fp32 plans)
     bool f32_mfma = true;        // TRTX_F32_DIRECT=1: fp32 engines on the scalar direct kernel of rounds 1-4 (no fp32 MFMA, no fp32 stem kernel)
     bool conv_grouped = true;    // TRTX_CONV_GROUPED=0: grouped (not depthwise) convolutions stay on the scalar direct kernel (no kernels/conv_grouped.hip)
+    bool conv_slab = true;       // TRTX_CONV_SLAB=0: 3x3 convolutions of 32 and more narrow groups (ResNeXt) stay on the scalar direct kernel (no kernels/conv_slab.hip)
     bool conv_view = true;       // TRTX_CONV_VIEW=0: groups == 1 convolutions over channel views that are even but no multiple of 8 stay on the scalar direct kernel (no kernels/conv_view.hip)
     bool area_attention = true; // TRTX_AREA_ATTENTION=0: YOLOv12 area attention stays on the generic linear path (shuffles, matmul, softmax); PSA attention is not affected
     int psa_mfma = 1;            // TRTX_PSA_MFMA=0: PSA attention (YOLO11's C2PSA, YOLOv10's PSA) stays on the vector-ALU kernel (kernels/attention.hip) instead of the MFMA one;

@@ -288,6 +288,7 @@ int32_t execute_plan(trtx_context* c, int batch, void* const* bindings, hipStrea
                     case ROUTE_GROUPED: st = conv_grouped(a, stream); break;
                     case ROUTE_VIEW: st = conv_view(a, stream); break;
                     case ROUTE_PATCH_F32: st = conv_patch_f32(a, stream); break;
+                    case ROUTE_SLAB: st = launch_conv_slab_f16(a, stream); break;
                     case ROUTE_DIRECT: st = conv_direct(a, op.dtype, stream); break;
                 }
                 break;

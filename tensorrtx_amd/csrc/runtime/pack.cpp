@@ -76,6 +76,11 @@ void conv_layout_grouped(ConvArgs* a) {
     a->Kpad = conv_grouped_kpad(*a);   // K rounded up to 32 (kernels/conv_grouped.hip)
 }
 
+void conv_layout_slab(ConvArgs* a) {
+    conv_layout_unpadded(a);
+    a->Kpad = conv_slab_kpad(*a);   // 9 taps of max(16, Cin / groups) channels, rounded up to 32 (kernels/conv_slab.hip)
+}
+
 void conv_layout_patch_f32(ConvArgs* a) {
     if (a->groups == 1) {
         conv_layout_igemm_f32(a);
@@ -90,7 +95,8 @@ size_t conv_packed_weight_bytes(ConvRoute route, const ConvArgs& a) {
         case ROUTE_PATCH_F32: return (size_t)a.Cout_pad * a.Kpad * 4;   // (grouped: Cout_pad == Cout)
         case ROUTE_IGEMM:
         case ROUTE_VIEW: return (size_t)a.Cout_pad * a.Kpad * (a.f32 ? 4 : 2);   // (int8: Kpad counts 2-byte units)
-        case ROUTE_GROUPED: return (size_t)a.Cout * a.Kpad * 2;
+        case ROUTE_GROUPED:
+        case ROUTE_SLAB: return (size_t)a.Cout * a.Kpad * 2;
         default: return (size_t)a.Cout * a.K * 4;
     }
 }
@@ -149,14 +155,16 @@ void pack_conv_weights_f32(const float* w, int cout, int cin_g, int kh, int kw, 
     }
 }
 
-void pack_conv_weights_grouped_f16(const float* w, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed) {
+void pack_conv_weights_grouped_f16(const float* w, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed, int slab) {
     memset(packed, 0, sizeof(uint16_t) * (size_t)cout * kpad);
+    const int tap_stride = std::max(slab, cin_g);
     for (int co = 0; co < cout; ++co) {   // (KCRS rows are already group-major: channel co belongs to group co / Cout_g)
         const float sc = ch_scale ? ch_scale[co] : 1.0f;
+        const int c_first = slab > cin_g ? (co % slab) / cin_g * cin_g : 0;   // the group's first channel inside its slab
         for (int c = 0; c < cin_g; ++c)
             for (int r = 0; r < kh; ++r)
                 for (int q = 0; q < kw; ++q)
-                    packed[(size_t)co * kpad + (size_t)(r * kw + q) * cin_g + c] = f32_to_f16_bits(w[(((size_t)co * cin_g + c) * kh + r) * kw + q] * sc);
+                    packed[(size_t)co * kpad + (size_t)(r * kw + q) * tap_stride + c_first + c] = f32_to_f16_bits(w[(((size_t)co * cin_g + c) * kh + r) * kw + q] * sc);
     }
 }
 
@@ -349,6 +357,10 @@ bool pack_weights(const Network& net, Plan* plan) {
                 case ROUTE_GROUPED:
                     op.w_off = reserve(conv_packed_weight_bytes(op.route, a));
                     pack_conv_weights_grouped_f16(w0, cout, cin_g, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<uint16_t*>(blob.data() + op.w_off));
+                    break;
+                case ROUTE_SLAB:   // (kernels/conv_slab.hip: the grouped kernel's rows, block-diagonal inside a slab below 16 channels per group)
+                    op.w_off = reserve(conv_packed_weight_bytes(op.route, a));
+                    pack_conv_weights_grouped_f16(w0, cout, cin_g, a.kh, a.kw, a.Kpad, sc.data(), reinterpret_cast<uint16_t*>(blob.data() + op.w_off), conv_slab_width(a));
                     break;
                 case ROUTE_PATCH_F32:   // (kernels/conv_patch_f32.hip: the fp32 implicit-GEMM rows, or the grouped kernel's rows in fp32)
                     op.w_off = reserve(conv_packed_weight_bytes(op.route, a));

@@ -23,6 +23,8 @@ void conv_layout_grouped(ConvArgs* a);
 //  - fp32 engines' grouped / channel-view kernel (kernels/conv_patch_f32.hip; sets ConvArgs::f32): groups == 1 the fp32 implicit-GEMM rows exactly, grouped the
 //    rows of conv_layout_grouped.  No layout of its own: the kernel reads what those two families pack, in fp32
 void conv_layout_patch_f32(ConvArgs* a);
+//  - many narrow groups (kernels/conv_slab.hip): conv_layout_slab, declared with the kernel in kernels/kernels.h: rows of conv_slab_kpad(); for 16 and 32
+//    channels per group these are conv_layout_grouped's rows
 //  - direct, depthwise, stem, deconvolution: nothing is padded
 void conv_layout_unpadded(ConvArgs* a);
 // Bytes of the packed filter of a convolution on `route` (what pack_weights reserves, and the weight term of POp::bytes)
@@ -39,8 +41,10 @@ void pack_conv_weights_f32(const float* w_kcrs, int cout, int cin_g, int kh, int
                            float* packed);
 
 // fp16 [group][Cout_g][kpad] = rows [Cout][kpad] for the grouped MFMA kernel (kernels/conv_grouped.hip): k = (r*kw + q)*cin_g + c, kpad = K rounded
-// up to 32, zero padded; the per-output-channel scale is multiplied in before rounding to fp16, as in pack_conv_weights_f16
-void pack_conv_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed);
+// up to 32, zero padded; the per-output-channel scale is multiplied in before rounding to fp16, as in pack_conv_weights_f16.
+// slab > cin_g (kernels/conv_slab.hip, Cout_g == Cin_g below 16): the rows are block-diagonal inside slabs of `slab` channels, k = (r*kw + q)*slab + c_local
+// with c_local = the row's group's first channel inside its slab + c, zero outside the group (conv_layout_slab); slab <= cin_g: the rows above exactly
+void pack_conv_weights_grouped_f16(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, uint16_t* packed, int slab = 0);
 
 // ... and the same rows in fp32 (kernels/conv_patch_f32.hip, grouped layers)
 void pack_conv_weights_grouped_f32(const float* w_kcrs, int cout, int cin_g, int kh, int kw, int kpad, const float* ch_scale, float* packed);

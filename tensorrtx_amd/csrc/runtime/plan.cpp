@@ -79,6 +79,7 @@ std::string Plan::describe_json() const {
             if (op.route == ROUTE_GROUPED) o << ",\"grouped\":true";
             if (op.route == ROUTE_VIEW) o << ",\"view\":true";
             if (op.route == ROUTE_PATCH_F32) o << ",\"patch_f32\":true";
+            if (op.route == ROUTE_SLAB) o << ",\"slab\":true";
             if (op.cout_real) o << ",\"cout_real\":" << op.cout_real;
             if (op.reorg_cin) o << ",\"reorg_cin\":" << op.reorg_cin;
             if (op.fold_layer >= 0) o << ",\"repvggdw_fold\":true";

@@ -141,6 +141,7 @@ enum ConvRoute : int {
     ROUTE_GROUPED,     // grouped MFMA kernel (kernels/conv_grouped.hip; weights fp16 [group][Cout_g][Kpad])
     ROUTE_VIEW,        // MFMA kernel over 4-byte aligned channel views (kernels/conv_view.hip; weights as the implicit-GEMM family packs them)
     ROUTE_PATCH_F32,   // fp32 engines' grouped / channel-view MFMA kernel (kernels/conv_patch_f32.hip; weights fp32, the implicit-GEMM rows or [group][Cout_g][Kpad])
+    ROUTE_SLAB,        // MFMA kernel for 3x3 convolutions of many narrow groups (kernels/conv_slab.hip; weights fp16 [C][Kpad], block-diagonal inside a 16- or 32-channel slab)
 };
 
 struct POp {

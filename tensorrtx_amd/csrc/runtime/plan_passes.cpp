@@ -144,6 +144,18 @@ bool take_grouped(const ConvSite& s) {
     return true;
 }
 
+// 3x3 with 32 or more narrow groups (ResNeXt-50 32x4d, resnet/resnext50_32x4d.cpp:111-154: 4, 8, 16 and 32 channels per group, stride 1 and 2):
+// kernels/conv_slab.hip, 16-byte aligned channel views; a.Kpad becomes the packed row length.  The kernel takes fewer groups too; the lowering asks for it
+// from cardinality 32 on, which is what was measured.  TRTX_CONV_SLAB=0 leaves such layers on the direct kernel (A/B).
+bool take_slab(const ConvSite& s) {
+    ConvArgs& a = s.op.conv;
+    if (!s.e.opt.conv_slab || a.groups < 32 || s.ti.rcoff % 8 || s.to.rcoff % 8 || (s.tr && s.tr->rcoff % 8)) return false;
+    if (!conv_slab_supported(a)) return false;
+    conv_layout_slab(&a);
+    s.op.route = ROUTE_SLAB;
+    return true;
+}
+
 // groups == 1 over a view whose channel count, offset or stride is even but no multiple of 8 (YOLOv9m's 60- and 90-channel RepNCSP blocks and the
 // 180-channel halves of its 360-channel tensors; a user's ISliceLayer): kernels/conv_view.hip, after every kernel above has declined.  The weights are
 // packed as the implicit-GEMM family's with CinK = Cin rounded up to 32.  TRTX_CONV_VIEW=0 leaves such layers on the direct kernel (A/B).
@@ -204,10 +216,10 @@ bool choose_conv_kernel(const Plan& plan, const PassInputs& e, POp& op) {
     // the other kernels neither stand in for a deconvolution nor fetch a folded upsample, and every tensor is of the engine's dtype
     if (op.from_deconv || !op.extra_in.empty() || ti.dtype != e.dt || to.dtype != e.dt || (tr && tr->dtype != e.dt)) return false;
     if (take_dw(s)) return false;
-    // ... the last three not in kINT8 engines nor in the lowering their calibration runs on: two in fp16 engines, one in fp32 engines
+    // ... the last four not in kINT8 engines nor in the lowering their calibration runs on: three in fp16 engines, one in fp32 engines
     if (e.int8 || CalibrationLowering::active()) return false;
     if (e.dt == DT_F32) (void)take_patch_f32(s);
-    if (e.dt == DT_F16) (void)(take_grouped(s) || take_view(s));
+    if (e.dt == DT_F16) (void)(take_grouped(s) || take_slab(s) || take_view(s));
     return false;
 }
 

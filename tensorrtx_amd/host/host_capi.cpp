@@ -95,6 +95,8 @@ const Family kFamilies[] = {
      BUILD { return trtx_host::buildLenet(k.b, k.bc, k.wts, k.c.batch); }},
     {[](const std::string& m) { return m == "resnet50"; }, nullptr, ANY, 224, 224, false, 0, 0, ANY, NONE, "data", TRTX_ERR_UNSUPPORTED,
      BUILD { return trtx_host::buildResnet50(k.b, k.bc, k.wts, k.c.batch, k.c.fp16, k.c.input_h, k.c.input_w); }},
+    {[](const std::string& m) { return m == "resnext50_32x4d"; }, nullptr, ANY, 224, 224, false, 0, 0, ANY, NONE, "data", TRTX_ERR_UNSUPPORTED,
+     BUILD { return trtx_host::buildResnet50(k.b, k.bc, k.wts, k.c.batch, k.c.fp16, k.c.input_h, k.c.input_w, 32); }},
     {[](const std::string& m) { return m == "retinaface_r50"; }, nullptr, ANY, 480, 640, false, 0, 0, ANY, NONE, "data", TRTX_ERR_UNSUPPORTED,
      BUILD { return trtx_host::buildRetinaFaceR50(k.b, k.bc, k.wts, k.c.batch, k.c.fp16, k.c.input_h, k.c.input_w); }},
     {[](const std::string& m) { return m == "yolov8n"; }, nullptr, ANY, 640, 640, false, 0, 0, DET | SEG | POSE | OBB, NONE, "images", TRTX_ERR_UNSUPPORTED,

@@ -13,9 +13,10 @@ namespace trtx_host {
 // lenet/lenet.cpp:36-155
 nvinfer1::IHostMemory* buildLenet(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
                                   int32_t N);
-// resnet/resnet50.cpp:155-229
+// resnet/resnet50.cpp:155-229; groups = 32: ResNeXt-50 32x4d (resnet/resnext50_32x4d.cpp:111-230), the same graph and .wts keys with 32-group 3x3
+// convolutions of width outch * 4 / 64 * 32
 nvinfer1::IHostMemory* buildResnet50(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,
-                                     int maxBatch, bool fp16, int H = 224, int W = 224);
+                                     int maxBatch, bool fp16, int H = 224, int W = 224, int groups = 1);
 
 // retinaface/retina_r50.cpp:100-242
 nvinfer1::IHostMemory* buildRetinaFaceR50(nvinfer1::IBuilder* builder, nvinfer1::IBuilderConfig* config, const std::string& wts,

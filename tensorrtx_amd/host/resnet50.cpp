@@ -1,6 +1,8 @@
 // ResNet-50 classifier (BASELINE config 2).  Mirrors the reference builder (resnet/resnet50.cpp:111-229):
 // 7x7/2 stem + BN + ReLU + maxpool3/2, bottleneck stages [3,4,6,3] with the stride on the 3x3 conv,
 // BN folded into IScaleLayers with eps 1e-5, average pool 7x7 and FC-1000.  Implicit batch.
+// With groups = 32 the same builder is ResNeXt-50 32x4d (resnet/resnext50_32x4d.cpp:111-230): the graph, the layer order and the torchvision keys are
+// ResNet-50's; only the bottleneck's 3x3 changes (setNbGroups(32), width = outch * 4 / 64 * 32).
 #include "build.h"
 #include "models.h"
 
@@ -10,19 +12,21 @@ namespace trtx_host {
 namespace {
 
 ITensor* convBn(INetworkDefinition* net, WeightMap& wm, ITensor& in, int out, int k, int s, int p, const std::string& conv,
-                const std::string& bn) {
+                const std::string& bn, int groups = 1) {
     auto* c = net->addConvolutionNd(in, out, DimsHW{k, k}, need(wm, conv + ".weight"), noWeights());
     assert(c);
     c->setStrideNd(DimsHW{s, s});
     c->setPaddingNd(DimsHW{p, p});
+    c->setNbGroups(groups);
     return addBatchNorm2d(net, wm, *c->getOutput(0), bn, 1e-5f, /*sqrt_in_double=*/true)->getOutput(0);
 }
 
-// resnet50.cpp:111-151
-ITensor* bottleneck(INetworkDefinition* net, WeightMap& wm, ITensor& in, int inch, int outch, int stride, const std::string& l) {
-    ITensor* a = convBn(net, wm, in, outch, 1, 1, 0, l + "conv1", l + "bn1");
+// resnet50.cpp:111-151; groups > 1: resnext50_32x4d.cpp:111-154
+ITensor* bottleneck(INetworkDefinition* net, WeightMap& wm, ITensor& in, int inch, int outch, int stride, int groups, const std::string& l) {
+    const int width = groups > 1 ? outch * 4 / 64 * groups : outch;
+    ITensor* a = convBn(net, wm, in, width, 1, 1, 0, l + "conv1", l + "bn1");
     a = net->addActivation(*a, ActivationType::kRELU)->getOutput(0);
-    ITensor* b = convBn(net, wm, *a, outch, 3, stride, 1, l + "conv2", l + "bn2");
+    ITensor* b = convBn(net, wm, *a, width, 3, stride, 1, l + "conv2", l + "bn2", groups);
     b = net->addActivation(*b, ActivationType::kRELU)->getOutput(0);
     ITensor* c = convBn(net, wm, *b, outch * 4, 1, 1, 0, l + "conv3", l + "bn3");
     ITensor* shortcut = &in;
@@ -33,7 +37,7 @@ ITensor* bottleneck(INetworkDefinition* net, WeightMap& wm, ITensor& in, int inc
 
 }  // namespace
 
-IHostMemory* buildResnet50(IBuilder* builder, IBuilderConfig* config, const std::string& wts, int maxBatch, bool fp16, int H, int W) {
+IHostMemory* buildResnet50(IBuilder* builder, IBuilderConfig* config, const std::string& wts, int maxBatch, bool fp16, int H, int W, int groups) {
     Session s(builder, wts);
     WeightMap& wm = s.wm;
     INetworkDefinition* net = s.net;
@@ -51,7 +55,7 @@ IHostMemory* buildResnet50(IBuilder* builder, IBuilderConfig* config, const std:
         const int width = 64 << stage;
         for (int b = 0; b < blocks[stage]; ++b) {
             const int stride = (b == 0 && stage > 0) ? 2 : 1;
-            x = bottleneck(net, wm, *x, inch, width, stride, "layer" + std::to_string(stage + 1) + "." + std::to_string(b) + ".");
+            x = bottleneck(net, wm, *x, inch, width, stride, groups, "layer" + std::to_string(stage + 1) + "." + std::to_string(b) + ".");
             inch = width * 4;
         }
     }

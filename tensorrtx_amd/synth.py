@@ -467,8 +467,9 @@ class _Draw:
         return OrderedDict((k, v.numpy()) for k, v in self.sd.items())
 
 
-def _resnet50_body(d, prefix, bn3_gamma):
-    """conv1 / bn1 + the 16 bottlenecks of torchvision's ResNet-50 naming (resnet/resnet50.cpp:155-229, retinaface/retina_r50.cpp:100-140)"""
+def _resnet50_body(d, prefix, bn3_gamma, groups=1):
+    """conv1 / bn1 + the 16 bottlenecks of torchvision's ResNet-50 naming (resnet/resnet50.cpp:155-229, retinaface/retina_r50.cpp:100-140); groups = 32:
+    ResNeXt-50 32x4d's (resnet/resnext50_32x4d.cpp:111-154), the 3x3 grouped and of width outch * 4 / 64 * 32"""
     def conv_bn(cname, bname, cout, cin, k):
         d.conv_w(cname + ".weight", cout, cin, k)
         d.bn(bname, cout, bn3_gamma if bname.endswith("bn3") else 1.0)
@@ -479,22 +480,28 @@ def _resnet50_body(d, prefix, bn3_gamma):
         for b in range(nblk):
             l = f"{prefix}layer{stage + 1}.{b}."
             stride = 2 if (b == 0 and stage > 0) else 1
-            conv_bn(l + "conv1", l + "bn1", width, inch, 1)
-            conv_bn(l + "conv2", l + "bn2", width, width, 3)
-            conv_bn(l + "conv3", l + "bn3", width * 4, width, 1)
+            mid = width * 4 // 64 * groups if groups > 1 else width
+            conv_bn(l + "conv1", l + "bn1", mid, inch, 1)
+            conv_bn(l + "conv2", l + "bn2", mid, mid // groups, 3)
+            conv_bn(l + "conv3", l + "bn3", width * 4, mid, 1)
             if stride != 1 or inch != width * 4:
                 conv_bn(l + "downsample.0", l + "downsample.1", width * 4, inch, 1)
             inch = width * 4
 
 
-def resnet50_state(seed=0):
+def resnet50_state(seed=0, groups=1):
     """Seeded synthetic ResNet-50 weights under the keys resnet/resnet50.cpp reads (torchvision state_dict): OrderedDict name -> fp32 array."""
     import math
     d = _Draw(seed)
-    _resnet50_body(d, "", 1.0)
+    _resnet50_body(d, "", 1.0, groups)
     d.sd["fc.weight"] = (d.randn(1000, 2048) * math.sqrt(1.0 / 2048)).float()
     d.sd["fc.bias"] = (0.1 * d.randn(1000)).float()
     return d.state()
+
+
+def resnext50_32x4d_state(seed=0):
+    """... and ResNeXt-50 32x4d's, under the same keys (resnet/resnext50_32x4d.cpp:111-230)"""
+    return resnet50_state(seed, groups=32)
 
 
 def retinaface_r50_state(seed=0, head_gain=0.5):
@@ -565,7 +572,7 @@ def rcnn_r50c4_state(seed=0, num_classes=80, anchors=15):
     return d.state()
 
 
-STATE = {"resnet50": resnet50_state, "retinaface_r50": retinaface_r50_state, "rcnn_r50c4": rcnn_r50c4_state}   # (yolov8n_state is added below its definition)
+STATE = {"resnet50": resnet50_state, "resnext50_32x4d": resnext50_32x4d_state, "retinaface_r50": retinaface_r50_state, "rcnn_r50c4": rcnn_r50c4_state}   # (yolov8n_state is added below its definition)
 
 
 YOLOV5_ANCHORS = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]  # yolov5s P3/P4/P5 (ultralytics yaml)
